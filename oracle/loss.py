@@ -1,6 +1,6 @@
 """Oracle restatement of `MultiTaskLitModel._multitask_loss` (`/root/reference/src/running_main_v3.py:232-387`).
 
-TEST INFRASTRUCTURE (CPU, fp32).  Pinned: `tests/golden/ref_blocks.pt` holds inputs and the outputs of the REAL reference
+TEST INFRASTRUCTURE (CPU, fp32).  Pinned: `tests/golden/ref_loss.pt` holds inputs and the outputs of the REAL reference
 method (called unbound on a stand-in `self`, see tests/golden/make_ref_fixtures.py); tests/test_oracle_golden.py checks
 this restatement against them.
 

@@ -1,4 +1,4 @@
-"""Generate `ref_blocks.pt`: golden input/output vectors from the REAL reference classes.
+"""Generate `ref_blocks.pt`, `ref_bifpn.pt` and `ref_loss.pt`: golden input/output vectors from the REAL reference classes.
 
 Run in the build container only (needs /root/reference; never runs on the GPU box):
 
@@ -19,7 +19,9 @@ import types
 import torch
 
 REF_SRC = "/root/reference/src"
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_blocks.pt")
+OUT_DIR = os.path.dirname(os.path.abspath(__file__))
+# the cases are split over files that each stay under 1 MiB; every key not listed goes to ref_blocks.pt
+SHARDS = {"ref_bifpn.pt": ("BiFPN",), "ref_loss.pt": ("loss_train", "loss_train_nosmooth", "loss_eval")}
 
 
 class _Anything:
@@ -192,8 +194,11 @@ def main():
                            "output": [o.detach().clone() if isinstance(o, torch.Tensor) else torch.tensor(float(o)) for o in out]}
             print(name, [round(float(o), 5) for o in cases[name]["output"]])
 
-    torch.save(cases, OUT)
-    print("wrote", OUT, os.path.getsize(OUT), "bytes;", list(cases))
+    taken = {k for keys in SHARDS.values() for k in keys}
+    for name, keys in list(SHARDS.items()) + [("ref_blocks.pt", tuple(k for k in cases if k not in taken))]:
+        out = os.path.join(OUT_DIR, name)
+        torch.save({k: cases[k] for k in keys if k in cases}, out)
+        print("wrote", out, os.path.getsize(out), "bytes;", [k for k in keys if k in cases])
 
 
 if __name__ == "__main__":

@@ -17,7 +17,7 @@ DEV = "cuda:0"
 
 @pytest.fixture(scope="module")
 def cases():
-    return torch.load(os.path.join(os.path.dirname(__file__), "golden", "ref_blocks.pt"), weights_only=True)
+    return torch.load(os.path.join(os.path.dirname(__file__), "golden", "ref_loss.pt"), weights_only=True)
 
 
 @pytest.mark.parametrize("name", ["loss_train", "loss_train_nosmooth", "loss_eval"])

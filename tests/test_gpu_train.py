@@ -192,14 +192,17 @@ def test_eval_mode_backbone_backward_fp32():
 
 
 def test_bf16_training_step_gradients_are_close_and_finite():
-    """bf16 storage (the throughput mode): gradients stay finite and point the same way as fp32 autograd's."""
+    """bf16 storage (the throughput mode): gradients stay finite and point the same way as autograd's through the oracle.  The oracle
+    runs in fp64: a conv bias in front of a batch-statistic BatchNorm has an exactly-zero gradient (HIP leaves it zero), and fp32
+    autograd returns rounding noise there whose size -- above or below the 1e-6 floor -- depends on the host's CPU thread count."""
     ora, hip = build("main", seed=3)
+    ora.double()
     hip.set_compute_dtype(torch.bfloat16)
     g = torch.Generator().manual_seed(11)
     x = torch.rand(4, 3, 128, 128, generator=g)
-    ro, ho = flat_outputs(ora(x, "train")), flat_outputs(hip(x.to(DEV), "train"))
+    ro, ho = flat_outputs(ora(x.double(), "train")), flat_outputs(hip(x.to(DEV), "train"))
     probes = [torch.randn(r.shape, generator=g) / r[0].numel() ** 0.5 for r in ro]
-    sum((r * w).sum() for r, w in zip(ro, probes)).backward()
+    sum((r * w.double()).sum() for r, w in zip(ro, probes)).backward()
     sum((h * w.to(DEV)).sum() for h, w in zip(ho, probes)).backward()
     torch.cuda.synchronize()
     hp = dict(hip.named_parameters())
@@ -212,10 +215,10 @@ def test_bf16_training_step_gradients_are_close_and_finite():
         assert torch.isfinite(gh).all(), name
         if p.grad.numel() < 64 or p.grad.abs().max().item() < 1e-6:
             continue
-        cos = torch.nn.functional.cosine_similarity(gh.flatten(), p.grad.flatten(), dim=0).item()
+        cos = torch.nn.functional.cosine_similarity(gh.double().flatten(), p.grad.flatten(), dim=0).item()
         if cos < 0.9:
             low.append(f"{name}: cos {cos:.3f}")
-    assert len(low) <= 8, "bf16 gradients diverge from fp32 autograd:\n" + "\n".join(low[:40])
+    assert len(low) <= 8, "bf16 gradients diverge from fp64 autograd:\n" + "\n".join(low[:40])
 
 
 def test_stale_backward_is_refused():

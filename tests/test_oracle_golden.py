@@ -1,6 +1,6 @@
 """Pin the oracle to the reference: every reference-owned block must reproduce, bit for bit, the
 outputs the REAL reference classes gave for the same state_dict and inputs
-(fixtures: tests/golden/ref_blocks.pt, made by tests/golden/make_ref_fixtures.py)."""
+(fixtures: tests/golden/ref_blocks.pt, ref_bifpn.pt and ref_loss.pt, made by tests/golden/make_ref_fixtures.py)."""
 import os
 
 import pytest
@@ -11,7 +11,10 @@ from oracle import blocks, postprocess
 
 @pytest.fixture(scope="module")
 def cases(golden_dir):
-    return torch.load(os.path.join(golden_dir, "ref_blocks.pt"), weights_only=True)
+    out = {}
+    for f in ("ref_blocks.pt", "ref_bifpn.pt", "ref_loss.pt"):
+        out.update(torch.load(os.path.join(golden_dir, f), weights_only=True))
+    return out
 
 
 BUILDERS = {

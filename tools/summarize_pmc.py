@@ -2,7 +2,7 @@
 """Per-launch HBM-side traffic of the kernel families of the forward plan from two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE).
 
 usage: summarize_pmc.py FETCH_DIR WRITE_DIR PLAN_EXECUTIONS > profiles/rNN_traffic.json
-PLAN_EXECUTIONS = how many times the profiled command ran the launch plan (bench.py --no-graph: warm-ups + timed steps + 1 result step +
+PLAN_EXECUTIONS = how many times the profiled command ran the launch plan (bench.py --full --no-graph: warm-ups + timed steps +
 3 instrumented replays), so that launches_per_step is per PLAN execution.
 Corrections per /opt/skills/guides/MI355X_MICROARCH.md (HBM section): both counters are in KiB; on gfx950 FETCH_SIZE counts
 128-byte requests at 64 bytes, so wide coalesced reads (16 B per lane: every read of these kernels) are DOUBLED; WRITE_SIZE
