@@ -58,7 +58,7 @@ extern "C" {
 #define MTBT_ABI_VERSION 5
 int mtbt_abi_version(void);
 /* sizeof() of the argument structs as the LIBRARY was compiled: which = 0 mtbt_conv_args, 1 mtbt_fuse_args, 2 mtbt_decode_args,
- * 3 mtbt_mask_args, 4 mtbt_loss_args, 5 mtbt_prep_desc, 6 mtbt_raw_image, 7 mtbt_upconv_args, 8 mtbt_node_args; -1 for any other value.  A binding compares them with its
+ * 3 mtbt_mask_args, 4 mtbt_loss_args, 5 mtbt_prep_desc, 6 mtbt_raw_image, 7 mtbt_upconv_args, 8 mtbt_node_args, 9 mtbt_box_eval_args; -1 for any other value.  A binding compares them with its
  * own layout at load time (a stale prebuilt .so would otherwise read pointers from the wrong offsets). */
 int mtbt_sizeof_args(int which);
 /* "gfx950" */
@@ -401,6 +401,39 @@ int mtbt_letterbox_batch(const mtbt_raw_image* images, int count, int img_size, 
 int64_t mtbt_seg_confusion_workspace_bytes(int B);
 int mtbt_seg_confusion(const float* logits, const float* gt, int B, int64_t n_per_image, int64_t* counts, float* prob_sum,
                        void* workspace, int64_t workspace_bytes, void* stream);
+
+/* COCO box matching for the box mAP (torchmetrics MeanAveragePrecision of running_main_v3.py:209-217, evaluate_model.py:81-93):
+ * pycocotools COCOeval.evaluateImg (bbox, no crowd) for B images x the 4 COCO area ranges x T IoU thresholds in one launch.
+ *   boxes [B][K][4] xyxy f32 (16-byte aligned), scores [B][K] f32, labels [B][K] int64 (class ids within int32), counts [B] int32
+ *   (valid slots per image; NULL => all K) -- exactly what mtbt_nms_batched writes;
+ *   gt [M][6] f32 rows (batch_idx, cls, a, b, c, d): gt_format 0 = (cx, cy, w, h) normalised, converted to clamped xyxy pixels with
+ *   img_size by validation_step's per-box formula (:566); 1 = (x1, y1, x2, y2) pixels.  Rows need not be grouped by image.
+ *   iou_thresholds[0..T-1] (fp64, 1 <= T <= 32); max_det = the largest max-detection threshold.
+ * Outputs: rank [B][K] int32 (position in the (image, class) score order, stable on the slot; -1 = invalid or beyond max_det);
+ *   match / ignore [B][K][4] uint32 (word = area range all / small / medium / large, bit t = IoU threshold t); gt_area [M] uint32
+ *   (bit a: the row is not ignored in area range a; 0 for rows of no image); status: set to 1 when an image has more than 1024 GT
+ *   rows (the caller zeroes it; that image's detections come back invalid).  Caps: K <= 1024, 1024 GT boxes per image.
+ * IoU in fp64 in metrics.box_iou_xyxy's operation order, no contraction: decisions bit-identical to the host metric.  Semantics
+ * spelled out in csrc/box_eval.hip.  MTBT_EINVAL for NULL pointers, T outside [1, 32], K outside [1, 1024], max_det < 1, a bad
+ * gt_format; MTBT_EALIGN for misaligned pointers.  Asynchronous, deterministic, no workspace. */
+typedef struct mtbt_box_eval_args {
+  const float* boxes;
+  const float* scores;
+  const int64_t* labels;
+  const int32_t* counts;
+  const float* gt;
+  int32_t* rank;
+  uint32_t* match;
+  uint32_t* ignore;
+  uint32_t* gt_area;
+  int32_t* status;
+  double iou_thresholds[32];
+  int32_t B, K, M, T;
+  int32_t max_det;
+  int32_t gt_format;
+  float img_size;
+} mtbt_box_eval_args;
+int mtbt_box_eval(const mtbt_box_eval_args* args, void* stream);
 
 /* Weight gradient of a k x k convolution (any stride / padding; 1x1 and the 2x2 stride-2 downsample included), bf16 (MFMA) or fp32 operands:
  *   dw[k][r][s][c] (fp32, packed [K][R*S*C] like the forward weight) (+)= sum_p dy[p][k] * x[n][y*stride + r - pad][x*stride + s - pad][c]

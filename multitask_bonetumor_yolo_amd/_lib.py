@@ -83,6 +83,13 @@ class LossArgs(C.Structure):
     ]
 
 
+class BoxEvalArgs(C.Structure):  # mtbt_box_eval_args
+    _fields_ = [("boxes", C.c_void_p), ("scores", C.c_void_p), ("labels", C.c_void_p), ("counts", C.c_void_p), ("gt", C.c_void_p),
+                ("rank", C.c_void_p), ("match", C.c_void_p), ("ignore", C.c_void_p), ("gt_area", C.c_void_p), ("status", C.c_void_p),
+                ("iou_thresholds", C.c_double * 32), ("B", C.c_int32), ("K", C.c_int32), ("M", C.c_int32), ("T", C.c_int32),
+                ("max_det", C.c_int32), ("gt_format", C.c_int32), ("img_size", C.c_float)]
+
+
 # every symbol include/mtbt_hip.h declares: name -> (restype, argtypes)
 class PrepDesc(C.Structure):  # mtbt_prep_desc
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("scale0", C.c_void_p), ("scale1", C.c_void_p),
@@ -186,9 +193,10 @@ SYMBOLS = {
     "mtbt_stem_wgrad_workspace_bytes": (C.c_int64, [C.c_int]),
     "mtbt_stem_wgrad": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "mtbt_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "mtbt_box_eval": (C.c_int, [C.POINTER(BoxEvalArgs), C.c_void_p]),
 }
 
-ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs)   # order of mtbt_sizeof_args(which)
+ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
 _lib = None
 
 

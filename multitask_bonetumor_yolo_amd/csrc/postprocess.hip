@@ -612,6 +612,7 @@ extern "C" int mtbt_sizeof_args(int which) {
     case 6: return (int)sizeof(mtbt_raw_image);
     case 7: return (int)sizeof(mtbt_upconv_args);
     case 8: return (int)sizeof(mtbt_node_args);
+    case 9: return (int)sizeof(mtbt_box_eval_args);
     default: return -1;
   }
 }

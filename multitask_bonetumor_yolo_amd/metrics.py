@@ -11,6 +11,10 @@ torchmetrics' binary stat-score definitions.
                           :480-497 from those counts in `compute`.
   MeanAveragePrecision    COCO box mAP over IoU thresholds with `max_detection_thresholds` (mAP@0.5 and @0.5:0.95 of :206-214):
                           host-side numpy -- at most 100 kept boxes per image after the device NMS, a few GT boxes.
+  DeviceMeanAveragePrecision
+                          torchmetrics' full bbox key set (the four COCO area ranges, per-class values with `class_metrics`): the
+                          per-image matching on the device (`mtbt_box_eval`, straight from the NMS output and the collated GT rows,
+                          no host sync per step), `accumulate` / `summarize` once per epoch in vectorised numpy (`_accumulate`).
 
 Data-parallel validation (configs[3]: one process per GPU, each rank sees its shard of the validation set): the reference's metric
 objects are built with `dist_sync_on_step=True` (`running_main_v3.py:193-218`), i.e. torchmetrics gathers every rank's state before it
@@ -152,6 +156,239 @@ class MeanAveragePrecision:
         for m, maxdet in enumerate(self.max_dets):
             out[f"mar_{maxdet}"] = mean(recall[:, :, m])
         return out
+
+
+AREA_RANGES = ("all", "small", "medium", "large")   # COCO: [0, 1e10], [0, 32^2], [32^2, 96^2], [96^2, 1e10], bounds inclusive
+BOX_EVAL_CAP = 1024                                 # detections per image slot row (K) and GT boxes per image (csrc/box_eval.hip)
+
+
+def _accumulate(records: Dict[str, np.ndarray], iou_thresholds: Sequence[float], max_dets: Sequence[int],
+                class_metrics: bool = False) -> Dict[str, object]:
+    """pycocotools `accumulate` + `summarize` over per-detection records of the device matching (`mtbt_box_eval`), vectorised.
+
+    records: `image` [N] (update order), `rank` [N] (within (image, class); < 0 = not kept), `score` [N], `label` [N],
+    `match` / `ignore` [N, 4] uint32 (word = area range, bit t = IoU threshold t), `gt_label` [G], `gt_area` [G] uint32
+    (bit a = the GT box is not ignored in area range a)."""
+    thr = np.asarray(iou_thresholds, np.float64)
+    max_dets = sorted(int(m) for m in max_dets)
+    T, A, Md = len(thr), len(AREA_RANGES), len(max_dets)
+    rec_thr = np.linspace(0.0, 1.0, 101)
+    R = len(rec_thr)
+    rank = np.asarray(records["rank"], np.int64).ravel()
+    ok = rank >= 0
+    rank, image = rank[ok], np.asarray(records["image"], np.int64).ravel()[ok]
+    score, label = np.asarray(records["score"], np.float64).ravel()[ok], np.asarray(records["label"], np.int64).ravel()[ok]
+    match = np.asarray(records["match"], np.uint32).reshape(-1, A)[ok]
+    ignore = np.asarray(records["ignore"], np.uint32).reshape(-1, A)[ok]
+    gt_label, gt_area = np.asarray(records["gt_label"], np.int64).ravel(), np.asarray(records["gt_area"], np.uint32).ravel()
+    classes = sorted(set(label.tolist()) | set(gt_label.tolist()))
+    precision, recall = -np.ones((T, R, len(classes), A, Md)), -np.ones((T, len(classes), A, Md))
+    bits = np.uint32(1) << np.arange(T, dtype=np.uint32)
+    for k, c in enumerate(classes):
+        sel = np.nonzero(label == c)[0]
+        sel = sel[np.lexsort((rank[sel], image[sel]))]                      # images in update order, then score order within each
+        g_area, r_sel, s_sel = gt_area[gt_label == c], rank[sel], score[sel]
+        for a in range(A):
+            npig = int(np.count_nonzero((g_area >> np.uint32(a)) & np.uint32(1)))
+            if npig == 0:
+                continue
+            dtm = (match[sel, a][:, None] & bits) != 0                       # [n, T]
+            dtig = (ignore[sel, a][:, None] & bits) != 0
+            for m, maxdet in enumerate(max_dets):
+                keep = np.nonzero(r_sel < maxdet)[0]
+                keep = keep[np.argsort(-s_sel[keep], kind="mergesort")]
+                tm, ti = dtm[keep].T, dtig[keep].T
+                tps = np.cumsum(tm & ~ti, axis=1).astype(np.float64)
+                fps = np.cumsum(~tm & ~ti, axis=1).astype(np.float64)
+                nd = tps.shape[1]
+                rc = tps / npig
+                pr = tps / (fps + tps + np.spacing(1))
+                recall[:, k, a, m] = rc[:, -1] if nd else 0.0
+                pr = np.maximum.accumulate(pr[:, ::-1], axis=1)[:, ::-1]          # precision envelope
+                for t in range(T):
+                    inds = np.searchsorted(rc[t], rec_thr, side="left")
+                    q = np.zeros(R)
+                    hit = inds < nd
+                    q[hit] = pr[t, inds[hit]]
+                    precision[t, :, k, a, m] = q
+
+    def mean(v):
+        v = v[v > -1]
+        return float(v.mean()) if v.size else -1.0
+
+    out = {"map": mean(precision[:, :, :, 0, -1])}
+    for name, t in (("map_50", 0.5), ("map_75", 0.75)):
+        hit = np.nonzero(np.isclose(thr, t))[0]
+        out[name] = mean(precision[hit[0], :, :, 0, -1]) if len(hit) else -1.0
+    for a, name in enumerate(AREA_RANGES[1:], 1):
+        out[f"map_{name}"] = mean(precision[:, :, :, a, -1])
+    for m, maxdet in enumerate(max_dets):
+        out[f"mar_{maxdet}"] = mean(recall[:, :, 0, m])
+    for a, name in enumerate(AREA_RANGES[1:], 1):
+        out[f"mar_{name}"] = mean(recall[:, :, a, -1])
+    if class_metrics:
+        out["classes"] = list(classes)
+        out["map_per_class"] = [mean(precision[:, :, k, 0, -1]) for k in range(len(classes))]
+        out[f"mar_{max_dets[-1]}_per_class"] = [mean(recall[:, k, 0, -1]) for k in range(len(classes))]
+    return out
+
+
+class DeviceMeanAveragePrecision:
+    """COCO box mAP / mAR with torchmetrics' bbox key set -- the four area ranges and, with `class_metrics`, per-class values --
+    with the per-image matching on the device (`mtbt_box_eval`) and the once-per-epoch accumulation in vectorised numpy.
+
+    `update_batched(det, gt_rows, img_size)`: `det` = the dict `postprocess.detect_and_segment` / `nms_batched` returns (boxes
+    [B,K,4] xyxy, scores [B,K], labels [B,K], counts [B]), `gt_rows` = the collated [M,6] rows (batch_idx, cls, cx, cy, w, h)
+    normalised (`preprocess.collate_boxes`), both on the device.  One launch, no host synchronisation.
+    `update(preds, targets)`: the torchmetrics list-of-dicts layout the reference builds (running_main_v3.py:554-570), one
+    host-to-device copy per call.  `compute()` copies the records to the host once; with a live process group (and
+    `dist_sync`) it gathers every rank's records in rank order first (a collective: every rank must call it)."""
+
+    def __init__(self, iou_thresholds: Optional[Sequence[float]] = None, max_detection_thresholds: Sequence[int] = (1, 10, 100),
+                 class_metrics: bool = False, dist_sync: bool = True, process_group=None, box_format: str = "xyxy", iou_type: str = "bbox"):
+        if box_format != "xyxy":
+            raise ValueError(f"DeviceMeanAveragePrecision: box_format {box_format!r} is not supported (only 'xyxy')")
+        if iou_type != "bbox":
+            raise ValueError(f"DeviceMeanAveragePrecision: iou_type {iou_type!r} is not supported (only 'bbox')")
+        self.iou_thresholds = np.asarray(iou_thresholds if iou_thresholds is not None else np.linspace(0.5, 0.95, 10), np.float64).ravel()
+        if not 1 <= len(self.iou_thresholds) <= 32:
+            raise ValueError("DeviceMeanAveragePrecision: between 1 and 32 IoU thresholds")
+        self.max_dets = sorted(int(m) for m in max_detection_thresholds)
+        if not self.max_dets or self.max_dets[0] < 1:
+            raise ValueError("DeviceMeanAveragePrecision: max_detection_thresholds must be positive")
+        self.class_metrics, self.dist_sync, self.group = bool(class_metrics), dist_sync, process_group
+        self.reset()
+
+    def reset(self):
+        self._dets: List[torch.Tensor] = []     # per update: [B*K, 11] int32 = score bits, label, rank, match[4], ignore[4]
+        self._gts: List[torch.Tensor] = []      # per update: [M, 3] int32 = batch_idx bits, cls bits, area-range set
+        self._shapes: List[tuple] = []          # per update: (B, K, M)
+        self._status: Optional[torch.Tensor] = None
+
+    def _launch(self, boxes, scores, labels, counts, gt, gt_format: int, img_size: float):
+        lib = L.load()
+        dev = boxes.device
+        B, K = scores.shape
+        M = gt.shape[0]
+        if K > BOX_EVAL_CAP:
+            raise ValueError(f"DeviceMeanAveragePrecision: {K} detection slots per image, at most {BOX_EVAL_CAP}")
+        if self._status is None:
+            self._status = torch.zeros(4, dtype=torch.int32, device=dev)
+        elif self._status.device != dev:
+            raise ValueError(f"DeviceMeanAveragePrecision: this metric keeps its records on {self._status.device}, the batch is on {dev}")
+        rank = torch.empty((B, K), dtype=torch.int32, device=dev)
+        mi = torch.empty((2, B, K, 4), dtype=torch.int32, device=dev)          # match, ignore (uint32 bit sets)
+        gt_area = torch.empty((M,), dtype=torch.int32, device=dev)
+        a = L.BoxEvalArgs()
+        a.boxes, a.scores, a.labels = boxes.data_ptr(), scores.data_ptr(), labels.data_ptr()
+        a.counts = counts.data_ptr() if counts is not None else None
+        a.gt, a.gt_area = (gt.data_ptr(), gt_area.data_ptr()) if M else (None, None)
+        a.rank, a.match, a.ignore, a.status = rank.data_ptr(), mi[0].data_ptr(), mi[1].data_ptr(), self._status.data_ptr()
+        for t, v in enumerate(self.iou_thresholds):
+            a.iou_thresholds[t] = float(v)
+        a.B, a.K, a.M, a.T, a.max_det, a.gt_format, a.img_size = B, K, M, len(self.iou_thresholds), self.max_dets[-1], gt_format, float(img_size)
+        with torch.cuda.device(dev):                                            # launch on the tensors' device, whatever is current
+            L.check(lib.mtbt_box_eval(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_box_eval")
+        self._dets.append(torch.cat([scores.reshape(-1, 1).view(torch.int32), labels.reshape(-1, 1).to(torch.int32), rank.reshape(-1, 1),
+                                     mi[0].reshape(-1, 4), mi[1].reshape(-1, 4)], 1))
+        self._gts.append(torch.cat([gt[:, :2].view(torch.int32), gt_area.reshape(-1, 1)], 1))
+        self._shapes.append((B, K, M))
+
+    def update_batched(self, det: Dict[str, torch.Tensor], gt_rows: torch.Tensor, img_size: float):
+        """Asynchronous: launches on the current stream, keeps its records on the device, never synchronises with the host."""
+        boxes, scores, labels, counts = det["boxes"], det["scores"], det["labels"], det.get("counts")
+        if not all(t.is_cuda for t in (boxes, scores, labels, gt_rows)) or (counts is not None and not counts.is_cuda):
+            raise RuntimeError("DeviceMeanAveragePrecision.update_batched: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+        devs = {t.device for t in (boxes, scores, labels, gt_rows) + ((counts,) if counts is not None else ())}
+        if len(devs) != 1:
+            raise ValueError(f"DeviceMeanAveragePrecision.update_batched: detections and GT rows on different devices {sorted(map(str, devs))}")
+        if boxes.dim() != 3 or boxes.shape[2] != 4 or scores.shape != boxes.shape[:2] or labels.shape != scores.shape:
+            raise ValueError("DeviceMeanAveragePrecision.update_batched: boxes [B,K,4], scores [B,K], labels [B,K]")
+        if gt_rows.dim() != 2 or gt_rows.shape[1] != 6:
+            raise ValueError("DeviceMeanAveragePrecision.update_batched: gt_rows must be [M, 6] (batch_idx, cls, cx, cy, w, h)")
+        if boxes.shape[0] == 0:
+            return
+        boxes = boxes.to(torch.float32).contiguous()
+        if boxes.data_ptr() % 16:
+            boxes = boxes.clone()
+        counts = counts.to(torch.int32).contiguous() if counts is not None else None
+        self._launch(boxes, scores.to(torch.float32).contiguous(), labels.to(torch.int64).contiguous(), counts,
+                     gt_rows.to(torch.float32).contiguous(), 0, img_size)
+
+    def update(self, preds: Sequence[Dict], targets: Sequence[Dict]):
+        """torchmetrics layout: per image dict(boxes [D,4] xyxy, scores [D], labels [D]) and dict(boxes [G,4] xyxy pixels, labels [G])."""
+        if len(preds) != len(targets):
+            raise ValueError("DeviceMeanAveragePrecision.update: preds and targets differ in length")
+        if not torch.cuda.is_available():
+            raise RuntimeError("DeviceMeanAveragePrecision.update: needs the MI355X (no CPU path)")
+        if not preds:
+            return
+        np_ = MeanAveragePrecision._np
+        B = len(preds)
+        db = [np_(p["boxes"], np.float32).reshape(-1, 4) for p in preds]
+        K = max(1, max(len(d) for d in db))
+        if K > BOX_EVAL_CAP:
+            raise ValueError(f"DeviceMeanAveragePrecision.update: {K} detections in one image, at most {BOX_EVAL_CAP}")
+        boxes, scores = np.zeros((B, K, 4), np.float32), np.zeros((B, K), np.float32)
+        labels, counts = np.zeros((B, K), np.int64), np.zeros(B, np.int32)
+        rows = []
+        for b, (p, t) in enumerate(zip(preds, targets)):
+            n = len(db[b])
+            boxes[b, :n], scores[b, :n], labels[b, :n], counts[b] = db[b], np_(p["scores"], np.float32).ravel(), np_(p["labels"], np.int64).ravel(), n
+            gb, gl = np_(t["boxes"], np.float32).reshape(-1, 4), np_(t["labels"], np.float32).ravel()
+            rows.append(np.concatenate([np.full((len(gb), 1), b, np.float32), gl[:, None], gb], 1))
+        gt = np.concatenate(rows).astype(np.float32)
+        parts, offs, off = [boxes, scores, labels, counts, gt], [], 0
+        for x in parts:                                                          # one buffer, 16-byte aligned pieces: one copy
+            offs.append(off)
+            off += -(-x.nbytes // 16) * 16
+        buf = np.zeros(max(off, 16), np.uint8)
+        for x, o in zip(parts, offs):
+            buf[o:o + x.nbytes] = np.ascontiguousarray(x).view(np.uint8).ravel()
+        dbuf = torch.from_numpy(buf).to(self._status.device if self._status is not None else torch.device("cuda", torch.cuda.current_device()))
+        views = [dbuf[o:o + x.nbytes].view(getattr(torch, x.dtype.name)).reshape(x.shape) for x, o in zip(parts, offs)]
+        self._launch(views[0], views[1], views[2], views[3], views[4], 1, 0.0)
+
+    def _records(self):
+        """-> (records dict over this process's images, number of images, status word) on the host."""
+        if self._dets:
+            dets = torch.cat(self._dets).cpu().numpy()
+            gts = torch.cat(self._gts).cpu().numpy()
+            status = int(self._status.cpu().numpy().max())
+        else:
+            dets, gts, status = np.zeros((0, 11), np.int32), np.zeros((0, 3), np.int32), 0
+        image, gt_keep, n_img = [], [], 0
+        for B, K, M in self._shapes:
+            image.append(np.repeat(np.arange(n_img, n_img + B), K))
+            n_img += B
+        for (B, K, M), lo in zip(self._shapes, np.cumsum([0] + [s[2] for s in self._shapes])):
+            bidx = gts[lo:lo + M, 0].view(np.float32)
+            gt_keep.append((bidx >= 0) & (bidx < B) & (bidx == np.trunc(bidx)))    # rows of an image of their batch
+        keep = np.concatenate(gt_keep) if gt_keep else np.zeros(0, bool)
+        rec = {"image": np.concatenate(image) if image else np.zeros(0, np.int64), "score": dets[:, 0].view(np.float32).astype(np.float64),
+               "label": dets[:, 1].astype(np.int64), "rank": dets[:, 2], "match": dets[:, 3:7].view(np.uint32),
+               "ignore": dets[:, 7:11].view(np.uint32),
+               "gt_label": np.trunc(gts[keep, 1].view(np.float32)).astype(np.int64), "gt_area": gts[keep, 2].view(np.uint32)}
+        kept = rec["rank"] >= 0
+        for k in ("image", "score", "label", "rank", "match", "ignore"):
+            rec[k] = rec[k][kept]
+        return rec, n_img, status
+
+    def compute(self) -> Dict[str, object]:
+        """With a live process group (and dist_sync): over the images of ALL ranks -- a collective, every rank must call it."""
+        rec, n_img, status = self._records()
+        if self.dist_sync and _world(self.group) > 1:
+            parts = _all_gather_records([(rec, n_img, status)], self.group)
+            off, image = 0, []
+            for r, n, _ in parts:
+                image.append(r["image"] + off)
+                off += n
+            rec = {k: np.concatenate([p[0][k] for p in parts]) for k in rec}
+            rec["image"] = np.concatenate(image)
+            status = max(p[2] for p in parts)
+        if status:
+            raise RuntimeError(f"DeviceMeanAveragePrecision.compute: an image holds more than {BOX_EVAL_CAP} GT boxes (mtbt_box_eval cap)")
+        return _accumulate(rec, self.iou_thresholds, self.max_dets, self.class_metrics)
 
 
 class SegmentationMetrics:
