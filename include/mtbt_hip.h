@@ -328,6 +328,22 @@ int mtbt_multitask_loss(const mtbt_loss_args* a, void* stream);
 int mtbt_multitask_loss_grad(const mtbt_loss_args* a, float* const* d_map, const int32_t* d_map_pixel_stride, float* d_seg_logits,
                              float* d_img_logits, void* stream);
 
+/* Confusion matrices of the validation epoch (running_main_v3.py:193-195 image classes, :218 + :349-350 + :710-722 matched anchors).
+ * counts [nc][nc] int64, row = target, column = prediction (torchmetrics' layout); the kernels ADD to it (the caller zeroes it once).
+ * pred = argmax of the nc logits with torch semantics: the first maximum wins and a NaN counts as the maximum.  A target outside
+ * [0, nc) is not counted and sets bit 0 of *status (the caller zeroes it).  Integer sums per workgroup in LDS, then one global atomic
+ * add per non-zero bin: deterministic.  nc <= MTBT_CONFUSION_MAX_NC.  MTBT_EINVAL before any launch for NULL pointers, N < 1,
+ * nc < 1 or nc above the cap.  Asynchronous, no workspace.
+ *
+ * mtbt_det_confusion reads the detection fields of the loss's own argument block -- map / h / w / map_pixel_stride / n_levels, N,
+ * nc, reg_max, img_size, gt_xyxy / gt_cls / gt_off, iou_thresh -- and validates only those (MTBT_EALIGN for a misaligned gt_xyxy).
+ * Every anchor is decoded and matched exactly as mtbt_multitask_loss does (one shared prologue): its positives are the loss's
+ * positives; each adds 1 at [gt_cls of its matched GT][argmax of its nc raw class logits].
+ * mtbt_cls_confusion: logits [N][nc] f32 contiguous, target [N] int64; adds 1 at [target][argmax] per row. */
+#define MTBT_CONFUSION_MAX_NC 64
+int mtbt_det_confusion(const mtbt_loss_args* a, int64_t* counts, int32_t* status, void* stream);
+int mtbt_cls_confusion(const float* logits, const int64_t* target, int N, int nc, int64_t* counts, int32_t* status, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * ConvTranspose2d(C, Cm, 2, stride 2, bias) -> Conv 3x3 (Cm -> K, pad 1) + per-channel shift + activation as ONE direct convolution
  * over the LOW-resolution map (inference).  Replaces ultralytics `Proto.upsample` followed by `Proto.cv2` (conv + folded BatchNorm +

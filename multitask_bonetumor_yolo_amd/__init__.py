@@ -4,6 +4,7 @@
     from multitask_bonetumor_yolo_amd import postprocess                 # decode / NMS / masks on the GPU
     from multitask_bonetumor_yolo_amd import preprocess                  # letterbox / BGR->RGB / /255 of a batch on the GPU
     from multitask_bonetumor_yolo_amd import multitask_loss              # == MultiTaskLitModel._multitask_loss (value)
+    from multitask_bonetumor_yolo_amd import ValidationStep              # == validation_step + the epoch-end metrics, on the device
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
@@ -12,5 +13,7 @@ from . import postprocess, preprocess  # noqa: F401
 from .loss import multitask_loss  # noqa: F401
 from .checkpoints import load_pretrained_heads, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401
-from .metrics import DeviceMeanAveragePrecision, MeanAveragePrecision, SegmentationMetrics  # noqa: F401
+from .metrics import (DetectionConfusionMatrix, DeviceMeanAveragePrecision, ImageClassificationMetrics, MeanAveragePrecision,  # noqa: F401
+                      SegmentationMetrics)
+from .validate import ValidationStep  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

@@ -10,6 +10,7 @@ F32, BF16, F16 = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_ELU, ACT_GELU, ACT_GELU_POLY, ACT_DSILU, ACT_DELU, ACT_DGELU, ACT_DGELU_POLY = 0, 1, 2, 3, 4, 5, 6, 7, 8
 OUT_NHWC, OUT_CONVT2X2 = 0, 1
 RES_ID, RES_UP_BILINEAR, RES_DOWN_MEAN, RES_UP_NEAREST, RES_MAXPOOL = 0, 1, 2, 3, 4
+CONFUSION_MAX_NC = 64    # include/mtbt_hip.h MTBT_CONFUSION_MAX_NC: classes of mtbt_det_confusion / mtbt_cls_confusion
 
 ERRORS = {-1: "MTBT_EINVAL (bad argument / unsupported shape)", -2: "MTBT_EALIGN (misaligned pointer or stride)",
           -3: "MTBT_ELAUNCH (kernel launch failed)", -4: "MTBT_EWORKSPACE (workspace too small)"}
@@ -194,6 +195,8 @@ SYMBOLS = {
     "mtbt_stem_wgrad": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "mtbt_cast": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "mtbt_box_eval": (C.c_int, [C.POINTER(BoxEvalArgs), C.c_void_p]),
+    "mtbt_det_confusion": (C.c_int, [C.POINTER(LossArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtbt_cls_confusion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)

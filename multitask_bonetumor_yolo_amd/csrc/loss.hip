@@ -1,5 +1,5 @@
 // Multitask loss VALUE on the device (`MultiTaskLitModel._multitask_loss`, running_main_v3.py:232-387):
-// no per-image Python loop, no `.item()` synchronisation.  Forward only (the backward pass is not built yet).
+// no per-image Python loop, no `.item()` synchronisation.  The value, its gradient (below) and the eval-mode confusion counts.
 //
 //   det_loss_kernel   4 lanes per (image, anchor), one per box side: softmax expectation of the side's 16-bin
 //                     distribution (+ its log-sum-exp for the DFL cross-entropy), box decode, IoU against the image's
@@ -10,6 +10,10 @@
 //                     mtbt_mask_assemble's projector path), workgroup partials.
 //   finalize_kernel   fixed-order reduction of the partials, image-classification cross-entropy, normalisation by the
 //                     batch's positive count (batch size if none), weighted total.  One workgroup.
+//   det_confusion_kernel
+//                     the detection confusion matrix of the eval-mode loss (`temp_matched_preds_for_cm`, :349-350): the same
+//                     anchors and positives, argmax of each positive's class logits against its GT class, integer counts.
+// det_loss_kernel, det_loss_grad_kernel and det_confusion_kernel share one per-anchor decode + match prologue (match_anchor).
 // Deterministic (fixed reduction orders); fp32 with libm exp / log (this file is built with -ffp-contract=off like the rest
 // of the post-process so that the IoU matches torch's arithmetic).
 #include <cmath>
@@ -44,13 +48,28 @@ __device__ __forceinline__ float bce_logits(float x, float t) {  // torch: max(x
   return fmaxf(x, 0.f) - x * t + log1pf(expf(-fabsf(x)));
 }
 
-__global__ __launch_bounds__(256) void det_loss_kernel(const LossP p) {
-  __shared__ float red[4][5];
-  const long g = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
-  const int side = threadIdx.x & 3;
+// Per-anchor prologue shared by det_loss_kernel, det_loss_grad_kernel and det_confusion_kernel: 4 lanes per (image, anchor)
+// g, one per box side.  Softmax expectation of the side's reg_max-bin distribution, trainer decode (stride = img_size / w,
+// running_main_v3.py:266-290), IoU against the image's GT boxes (:316, first maximum wins like torch.max), positive = max IoU >
+// iou_thresh (:319-321).  Every lane of a wave must call it (the decode exchanges the four sides with __shfl); lanes of an anchor
+// beyond N * A compute anchor 0 of image 0 and come back with live = pos = false.
+struct AnchorMatch {
+  const float* row;     // the anchor's map row: 4 * reg_max distribution logits, then nc class logits
+  const float* d;       // this lane's side: row + side * reg_max
+  long pix;             // n * h_l * w_l + cell: the anchor's pixel in level l's maps
+  int l, bi;            // level; matched GT row (-1 if the image has none)
+  float m, s, dist;     // side distribution: max logit, sum of exp(logit - m), expectation
+  float st, ax, ay;     // stride, anchor point in pixels
+  float x1, y1, x2, y2; // decoded box
+  float best;           // max IoU
+  bool live, pos;
+};
+
+__device__ __forceinline__ AnchorMatch match_anchor(const LossP& p, long g, int side) {
+  AnchorMatch r;
   const long total = (long)p.N * p.A;
-  const bool live = g < total;
-  const long gg = live ? g : 0;
+  r.live = g < total;
+  const long gg = r.live ? g : 0;
   const int n = (int)(gg / p.A), a = (int)(gg - (long)n * p.A);
   int l = 0;
   if (p.n_levels > 1 && a >= p.off[1]) l = 1;
@@ -58,23 +77,27 @@ __global__ __launch_bounds__(256) void det_loss_kernel(const LossP p) {
   const int cell = a - p.off[l];
   const int w = p.w[l], hw = p.h[l] * w;
   const int cy = cell / w, cx = cell - cy * w;
-  const float* row = p.map[l] + ((long)n * hw + cell) * p.ld[l];
-  const float* d = row + side * p.reg_max;
+  r.l = l;
+  r.pix = (long)n * hw + cell;
+  r.row = p.map[l] + r.pix * p.ld[l];
+  r.d = r.row + side * p.reg_max;
+  const float* d = r.d;
 
-  // this side's distribution: expectation and log-sum-exp
+  // this side's distribution: expectation (and the pieces of its log-sum-exp)
   float m = -INFINITY;
   for (int i = 0; i < p.reg_max; ++i) m = fmaxf(m, d[i]);
   float s = 0.f;
   for (int i = 0; i < p.reg_max; ++i) s += expf(d[i] - m);
   float dist = 0.f;
   for (int i = 0; i < p.reg_max; ++i) dist += (expf(d[i] - m) / s) * (float)i;
-  const float lse = m + logf(s);
+  r.m = m; r.s = s; r.dist = dist;
 
   const int qbase = (threadIdx.x & 63) & ~3;
   const float st = p.stride[l];
   const float ax = (cx + 0.5f) * st, ay = (cy + 0.5f) * st;
-  const float x1 = ax - __shfl(dist, qbase + 0, 64) * st, y1 = ay - __shfl(dist, qbase + 1, 64) * st;
-  const float x2 = ax + __shfl(dist, qbase + 2, 64) * st, y2 = ay + __shfl(dist, qbase + 3, 64) * st;
+  r.st = st; r.ax = ax; r.ay = ay;
+  r.x1 = ax - __shfl(dist, qbase + 0, 64) * st; r.y1 = ay - __shfl(dist, qbase + 1, 64) * st;
+  r.x2 = ax + __shfl(dist, qbase + 2, 64) * st; r.y2 = ay + __shfl(dist, qbase + 3, 64) * st;
 
   // match against this image's GT boxes (every lane of the group computes the same thing)
   const int g0 = p.gt_off[n], g1 = p.gt_off[n + 1];
@@ -82,10 +105,24 @@ __global__ __launch_bounds__(256) void det_loss_kernel(const LossP p) {
   int bi = -1;
   for (int k = g0; k < g1; ++k) {
     const float4 b = *reinterpret_cast<const float4*>(p.gt_xyxy + 4 * k);
-    const float v = iou_xyxy(x1, y1, x2, y2, b.x, b.y, b.z, b.w);
+    const float v = iou_xyxy(r.x1, r.y1, r.x2, r.y2, b.x, b.y, b.z, b.w);
     if (v > best) { best = v; bi = k; }
   }
-  const bool pos = live && bi >= 0 && best > p.iou_thresh;
+  r.best = best; r.bi = bi;
+  r.pos = r.live && bi >= 0 && best > p.iou_thresh;
+  return r;
+}
+
+__global__ __launch_bounds__(256) void det_loss_kernel(const LossP p) {
+  __shared__ float red[4][5];
+  const AnchorMatch am = match_anchor(p, (long)blockIdx.x * 64 + (threadIdx.x >> 2), threadIdx.x & 3);
+  const int side = threadIdx.x & 3;
+  const float* row = am.row;
+  const float* d = am.d;
+  const float lse = am.m + logf(am.s);
+  const float ax = am.ax, ay = am.ay, st = am.st, best = am.best;
+  const int bi = am.bi;
+  const bool pos = am.pos;
 
   float v_cnt = 0.f, v_box = 0.f, v_iou = 0.f, v_cls = 0.f, v_dfl = 0.f;
   if (pos) {
@@ -200,44 +237,16 @@ struct GradP {
 
 __global__ __launch_bounds__(256) void det_loss_grad_kernel(const GradP q) {
   const LossP& p = q.l;
-  const long g = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
+  const AnchorMatch am = match_anchor(p, (long)blockIdx.x * 64 + (threadIdx.x >> 2), threadIdx.x & 3);
   const int side = threadIdx.x & 3;
-  const long total = (long)p.N * p.A;
-  const bool live = g < total;
-  const long gg = live ? g : 0;
-  const int n = (int)(gg / p.A), a = (int)(gg - (long)n * p.A);
-  int l = 0;
-  if (p.n_levels > 1 && a >= p.off[1]) l = 1;
-  if (p.n_levels > 2 && a >= p.off[2]) l = 2;
-  const int cell = a - p.off[l];
-  const int w = p.w[l], hw = p.h[l] * w;
-  const int cy = cell / w, cx = cell - cy * w;
-  const float* row = p.map[l] + ((long)n * hw + cell) * p.ld[l];
-  const float* d = row + side * p.reg_max;
-  float* drow = q.dmap[l] + ((long)n * hw + cell) * q.dld[l];
-
-  float m = -INFINITY;
-  for (int i = 0; i < p.reg_max; ++i) m = fmaxf(m, d[i]);
-  float s = 0.f;
-  for (int i = 0; i < p.reg_max; ++i) s += expf(d[i] - m);
-  float dist = 0.f;
-  for (int i = 0; i < p.reg_max; ++i) dist += (expf(d[i] - m) / s) * (float)i;
-
-  const int qbase = (threadIdx.x & 63) & ~3;
-  const float st = p.stride[l];
-  const float ax = (cx + 0.5f) * st, ay = (cy + 0.5f) * st;
-  const float x1 = ax - __shfl(dist, qbase + 0, 64) * st, y1 = ay - __shfl(dist, qbase + 1, 64) * st;
-  const float x2 = ax + __shfl(dist, qbase + 2, 64) * st, y2 = ay + __shfl(dist, qbase + 3, 64) * st;
-
-  const int g0 = p.gt_off[n], g1 = p.gt_off[n + 1];
-  float best = -INFINITY;
-  int bi = -1;
-  for (int k = g0; k < g1; ++k) {
-    const float4 b = *reinterpret_cast<const float4*>(p.gt_xyxy + 4 * k);
-    const float v = iou_xyxy(x1, y1, x2, y2, b.x, b.y, b.z, b.w);
-    if (v > best) { best = v; bi = k; }
-  }
-  const bool pos = live && bi >= 0 && best > p.iou_thresh;
+  const float* row = am.row;
+  const float* d = am.d;
+  float* drow = q.dmap[am.l] + am.pix * q.dld[am.l];
+  const float m = am.m, s = am.s, dist = am.dist;
+  const float ax = am.ax, ay = am.ay, st = am.st;
+  const float x1 = am.x1, y1 = am.y1, x2 = am.x2, y2 = am.y2;
+  const int bi = am.bi;
+  const bool live = am.live, pos = am.pos;
   if (!live) return;
   const int no = 4 * p.reg_max + p.nc;
   if (!pos) {
@@ -308,13 +317,49 @@ __global__ __launch_bounds__(256) void seg_img_grad_kernel(const float* __restri
   }
 }
 
+
+// ---- detection confusion matrix of `_multitask_loss` in eval mode (running_main_v3.py:349-350, :710-722) ----
+// Same anchors, decode and match as det_loss_kernel (match_anchor), so its positives are the loss's positives.  Per positive:
+// pred = argmax of the nc raw class logits (torch semantics: the first maximum wins, a NaN counts as the maximum), one count at
+// [gt_cls][pred].  Counts are summed per workgroup in LDS, then one 64-bit global atomicAdd per non-zero bin per workgroup: integer
+// sums, so the result does not depend on the order.  A positive whose GT class lies outside [0, nc) is not counted and sets bit 0 of
+// *status (a plain read-modify-write: every writer sets the same bit).  The grid strides over the anchors, 64 per pass.
+__global__ __launch_bounds__(256) void det_confusion_kernel(const LossP p, unsigned long long* __restrict__ counts, int* __restrict__ status) {
+  __shared__ unsigned int bins[MTBT_CONFUSION_MAX_NC * MTBT_CONFUSION_MAX_NC];
+  __shared__ int bad;
+  const int nbins = p.nc * p.nc;
+  for (int i = threadIdx.x; i < nbins; i += 256) bins[i] = 0u;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  const int side = threadIdx.x & 3;
+  const long total = (long)p.N * p.A;
+  for (long base = (long)blockIdx.x * 64; base < total; base += (long)gridDim.x * 64) {   // block-uniform: every lane takes part
+    const AnchorMatch am = match_anchor(p, base + (threadIdx.x >> 2), side);
+    if (am.pos && side == 0) {
+      const float* lg = am.row + 4 * p.reg_max;
+      int pred = 0;
+      float v = lg[0];
+      for (int c = 1; c < p.nc && v == v; ++c) {      // stops at the first NaN
+        const float x = lg[c];
+        if (x != x || x > v) { v = x; pred = c; }
+      }
+      const int gc = p.gt_cls[am.bi];
+      if (gc >= 0 && gc < p.nc) atomicAdd(&bins[gc * p.nc + pred], 1u);
+      else bad = 1;
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nbins; i += 256)
+    if (bins[i]) atomicAdd(counts + i, (unsigned long long)bins[i]);
+  if (threadIdx.x == 0 && bad) *status = *status | 1;
+}
+
 }  // namespace
 
-// validated kernel parameters shared by the value and the gradient entry points
-static int fill_loss_params(const mtbt_loss_args* a, LossP& p, int& A) {
-  if (!a || !a->out || a->n_levels < 1 || a->n_levels > 3 || a->N <= 0 || a->nc <= 0 || a->reg_max <= 0 || a->reg_max > 64) return MTBT_EINVAL;
-  if (!a->gt_xyxy || !a->gt_cls || !a->gt_off || !a->img_logits || !a->img_gt || a->n_img_classes <= 0) return MTBT_EINVAL;
-  if ((a->seg_n > 0) != (a->seg_logits != nullptr && a->seg_targets != nullptr)) return MTBT_EINVAL;
+// validated detection fields (maps, GT boxes, match threshold): what det_loss_kernel's prologue reads
+static int fill_det_params(const mtbt_loss_args* a, LossP& p, int& A) {
+  if (a->n_levels < 1 || a->n_levels > 3 || a->N <= 0 || a->nc <= 0 || a->reg_max <= 0 || a->reg_max > 64) return MTBT_EINVAL;
+  if (!a->gt_xyxy || !a->gt_cls || !a->gt_off) return MTBT_EINVAL;
   if (!aligned16(a->gt_xyxy)) return MTBT_EALIGN;
   A = 0;
   for (int l = 0; l < 3; ++l) {
@@ -330,7 +375,15 @@ static int fill_loss_params(const mtbt_loss_args* a, LossP& p, int& A) {
   p.n_levels = a->n_levels; p.N = a->N; p.A = A; p.nc = a->nc; p.reg_max = a->reg_max;
   p.gt_xyxy = a->gt_xyxy; p.gt_cls = a->gt_cls; p.gt_off = a->gt_off;
   p.iou_thresh = a->iou_thresh; p.smoothing = a->label_smoothing; p.training = a->training;
+  p.partial = nullptr;
   return MTBT_OK;
+}
+
+// validated kernel parameters shared by the value and the gradient entry points
+static int fill_loss_params(const mtbt_loss_args* a, LossP& p, int& A) {
+  if (!a || !a->out || !a->img_logits || !a->img_gt || a->n_img_classes <= 0) return MTBT_EINVAL;
+  if ((a->seg_n > 0) != (a->seg_logits != nullptr && a->seg_targets != nullptr)) return MTBT_EINVAL;
+  return fill_det_params(a, p, A);
 }
 
 extern "C" int64_t mtbt_loss_workspace_bytes(int N, int A, int64_t seg_n) {
@@ -386,6 +439,19 @@ extern "C" int mtbt_multitask_loss_grad(const mtbt_loss_args* a, float* const* d
   hipLaunchKernelGGL(seg_img_grad_kernel, dim3((unsigned)sb), dim3(256), 0, s, a->seg_logits, a->seg_targets, a->seg_bias, (long)a->seg_n,
                      a->seg_n > 0 ? a->w_seg / (float)a->seg_n : 0.f, d_seg_logits, a->img_logits, reinterpret_cast<const long long*>(a->img_gt), a->N,
                      a->n_img_classes, a->w_img / (float)a->N, d_img_logits);
+  MTBT_LAUNCH_CHECK();
+  return MTBT_OK;
+}
+
+extern "C" int mtbt_det_confusion(const mtbt_loss_args* a, int64_t* counts, int32_t* status, void* stream) {
+  if (!a || !counts || !status || a->nc > MTBT_CONFUSION_MAX_NC) return MTBT_EINVAL;
+  LossP p;
+  int A = 0;
+  if (int rc = fill_det_params(a, p, A)) return rc;
+  const long db = det_blocks_of(a->N, A);
+  const unsigned grid = (unsigned)(db < 1024 ? db : 1024);
+  hipLaunchKernelGGL(det_confusion_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p,
+                     reinterpret_cast<unsigned long long*>(counts), reinterpret_cast<int*>(status));
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }

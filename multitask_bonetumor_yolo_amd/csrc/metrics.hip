@@ -10,6 +10,9 @@
 //   prediction  sigmoid(x) > 0.5 in fp32  <=>  x > 2^-24 (for 0 < x <= 2^-24, exp(-x) rounds to 1 and the quotient to 0.5)
 //   target      masks_gt.int() > 0.5      <=>  trunc(t) >= 1
 // Deterministic: fixed grid, per-workgroup partials, fixed-order second pass.
+//
+// cls_confusion_kernel: the image-class confusion matrix (MulticlassConfusionMatrix / MulticlassAccuracy of :193-195, fed with
+// argmax(logits) at :458-459): one row per lane, counts summed per workgroup in LDS, one 64-bit global atomic add per non-zero bin.
 #include <cmath>
 
 #include "common.h"
@@ -65,6 +68,33 @@ __global__ __launch_bounds__(64) void seg_confusion_finish(const Part* __restric
   prob_sum[b] = ps;
 }
 
+
+__global__ __launch_bounds__(256) void cls_confusion_kernel(const float* __restrict__ logits, const long long* __restrict__ target, int N, int nc,
+                                                            unsigned long long* __restrict__ counts, int* __restrict__ status) {
+  __shared__ unsigned int bins[MTBT_CONFUSION_MAX_NC * MTBT_CONFUSION_MAX_NC];
+  __shared__ int bad;
+  const int nbins = nc * nc;
+  for (int i = threadIdx.x; i < nbins; i += 256) bins[i] = 0u;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  for (long r = (long)blockIdx.x * 256 + threadIdx.x; r < N; r += (long)gridDim.x * 256) {
+    const float* lg = logits + r * nc;
+    int pred = 0;
+    float v = lg[0];
+    for (int c = 1; c < nc && v == v; ++c) {      // torch argmax: first maximum, a NaN wins (stops at the first one)
+      const float x = lg[c];
+      if (x != x || x > v) { v = x; pred = c; }
+    }
+    const long long t = target[r];
+    if (t >= 0 && t < nc) atomicAdd(&bins[(int)t * nc + pred], 1u);
+    else bad = 1;
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < nbins; i += 256)
+    if (bins[i]) atomicAdd(counts + i, (unsigned long long)bins[i]);
+  if (threadIdx.x == 0 && bad) *status = *status | 1;
+}
+
 }  // namespace
 
 extern "C" int64_t mtbt_seg_confusion_workspace_bytes(int B) { return (int64_t)(B > 0 ? B : 0) * NB * (int64_t)sizeof(Part); }
@@ -80,6 +110,15 @@ extern "C" int mtbt_seg_confusion(const float* logits, const float* gt, int B, i
   MTBT_LAUNCH_CHECK();
   hipLaunchKernelGGL(seg_confusion_finish, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, reinterpret_cast<const Part*>(workspace),
                      (long)n_per_image, reinterpret_cast<long long*>(counts), prob_sum, B);
+  MTBT_LAUNCH_CHECK();
+  return MTBT_OK;
+}
+
+extern "C" int mtbt_cls_confusion(const float* logits, const int64_t* target, int N, int nc, int64_t* counts, int32_t* status, void* stream) {
+  if (!logits || !target || !counts || !status || N < 1 || nc < 1 || nc > MTBT_CONFUSION_MAX_NC) return MTBT_EINVAL;
+  const long blocks = ((long)N + 255) / 256;
+  hipLaunchKernelGGL(cls_confusion_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), logits,
+                     reinterpret_cast<const long long*>(target), N, nc, reinterpret_cast<unsigned long long*>(counts), reinterpret_cast<int*>(status));
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }

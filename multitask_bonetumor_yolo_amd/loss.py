@@ -42,6 +42,28 @@ def group_gt_boxes(gt_boxes: torch.Tensor, n_images: int, img_size: float):
     return xyxy.contiguous(), g[:, 1].int().contiguous(), off
 
 
+def det_loss_args(det_maps: Sequence[torch.Tensor], gt_boxes: torch.Tensor, *, img_size: float, nc_det: int, reg_max: int = 16,
+                  iou_match_thresh: float = 0.5):
+    """The detection fields of the loss's argument block (`L.LossArgs`): the raw Detect maps as NHWC rows, the GT rows grouped by
+    image (`group_gt_boxes`), nc, reg_max, img_size and the match threshold.  -> (args, tensors the args point into: keep them alive
+    until the launch is issued).  Shared by `multitask_loss` and `metrics.DetectionConfusionMatrix`, so that both decode and match the
+    same anchors."""
+    dev = det_maps[0].device
+    B = det_maps[0].shape[0]
+    a = L.LossArgs()
+    keep = []
+    for i, m in enumerate(det_maps):
+        t, ld = _nhwc_rows(m)
+        keep.append(t)
+        a.map[i], a.h[i], a.w[i], a.map_pixel_stride[i] = t.data_ptr(), m.shape[2], m.shape[3], ld
+    a.n_levels, a.N, a.nc, a.reg_max, a.img_size = len(det_maps), B, nc_det, reg_max, float(img_size)
+    xyxy, gcls, off = group_gt_boxes(gt_boxes.to(dev), B, float(img_size))
+    keep += [xyxy, gcls, off]
+    a.gt_xyxy, a.gt_cls, a.gt_off = xyxy.data_ptr(), gcls.data_ptr(), off.data_ptr()
+    a.iou_thresh = float(iou_match_thresh)
+    return a, keep
+
+
 def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_logits: torch.Tensor, gt_boxes: torch.Tensor,
                    gt_masks: torch.Tensor, gt_cls: torch.Tensor, proj_weight: torch.Tensor, proj_bias: torch.Tensor, *, img_size: int,
                    nc_det: int, reg_max: int = 16, iou_match_thresh: float = 0.5, label_smoothing: float = 0.0, training: bool = True,
@@ -55,18 +77,9 @@ def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_l
     _need_cuda(det_maps[0], "multitask_loss")
     dev = det_maps[0].device
     B = det_maps[0].shape[0]
-    a = L.LossArgs()
-    keep = []
-    A = 0
-    for i, m in enumerate(det_maps):
-        t, ld = _nhwc_rows(m)
-        keep.append(t)
-        a.map[i], a.h[i], a.w[i], a.map_pixel_stride[i] = t.data_ptr(), m.shape[2], m.shape[3], ld
-        A += m.shape[2] * m.shape[3]
-    a.n_levels, a.N, a.nc, a.reg_max, a.img_size = len(det_maps), B, nc_det, reg_max, float(img_size)
-    xyxy, gcls, off = group_gt_boxes(gt_boxes.to(dev), B, float(img_size))
-    a.gt_xyxy, a.gt_cls, a.gt_off = xyxy.data_ptr(), gcls.data_ptr(), off.data_ptr()
-    a.iou_thresh, a.label_smoothing, a.training = float(iou_match_thresh), float(label_smoothing), int(training)
+    a, keep = det_loss_args(det_maps, gt_boxes, img_size=img_size, nc_det=nc_det, reg_max=reg_max, iou_match_thresh=iou_match_thresh)
+    A = sum(m.shape[2] * m.shape[3] for m in det_maps)
+    a.label_smoothing, a.training = float(label_smoothing), int(training)
     # segmentation logits: Conv1x1(protos) -> bilinear S x S (mtbt_mask_assemble's projector path), bias added in the kernel
     w = proj_weight.detach().reshape(-1).float().contiguous()
     seg_logits, _ = _mask_call(protos, w, 0, 0, 1, None, None, 0.0, 1, (img_size, img_size), True, False)

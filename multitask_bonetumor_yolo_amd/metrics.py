@@ -15,6 +15,12 @@ torchmetrics' binary stat-score definitions.
                           torchmetrics' full bbox key set (the four COCO area ranges, per-class values with `class_metrics`): the
                           per-image matching on the device (`mtbt_box_eval`, straight from the NMS output and the collated GT rows,
                           no host sync per step), `accumulate` / `summarize` once per epoch in vectorised numpy (`_accumulate`).
+  ImageClassificationMetrics
+                          image-class accuracy, normalised confusion matrix (:193-195, :458-459, :609-616) and the macro precision /
+                          recall / F1 of evaluate_model.py:244-272 from a device-side confusion matrix (`mtbt_cls_confusion`).
+  DetectionConfusionMatrix
+                          the confusion matrix of the eval-mode loss's matched anchors (:218, :349-350, :710-722), counted on the
+                          device by the loss's own decode and match (`mtbt_det_confusion`).
 
 Data-parallel validation (configs[3]: one process per GPU, each rank sees its shard of the validation set): the reference's metric
 objects are built with `dist_sync_on_step=True` (`running_main_v3.py:193-218`), i.e. torchmetrics gathers every rank's state before it
@@ -453,3 +459,163 @@ class SegmentationMetrics:
         seg = m.compute() if len(c) else {"map": -1.0, "map_50": -1.0}
         out["seg_map"], out["seg_map_50"] = seg["map"], seg["map_50"]
         return out
+
+    def compute_map(self) -> Dict[str, float]:
+        """The segmentation mAP's standard COCO key set (torchmetrics `MeanAveragePrecision(iou_type="segm")` of :206, logged per scalar
+        key at :624-633): map, map_50, map_75, map_small / medium / large, mar_1 / 10 / 100, mar_small / medium / large.
+
+        From the per-image counts `update` keeps: each image holds one predicted and one GT instance, both class 0; the score is the
+        mask score of `per_image`; mask IoU = TP / (TP + FP + FN), 0 when the union is empty (pycocotools' value for two empty masks);
+        areas are pixel counts, detection TP + FP, GT TP + FN, ranges and inclusive bounds of `AREA_RANGES`.  Matching and ignore flags
+        follow pycocotools `evaluateImg`: a detection matched to a GT outside the area range is ignored, so is an unmatched detection
+        outside it.  Accumulated by `_accumulate` (IoU thresholds 0.50:0.05:0.95, max detections 1 / 10 / 100).  torchmetrics'
+        version-dependent extras (`classes`, and the `map_per_class` / `mar_100_per_class` placeholders) are not reproduced.
+        With a live process group (and dist_sync): over the images of ALL ranks -- a collective."""
+        c, score = self.per_image(sync=self.dist_sync)
+        return _segm_map(c, score)
+
+
+def _segm_map(c: np.ndarray, score: np.ndarray) -> Dict[str, float]:
+    """SegmentationMetrics.compute_map from per-image counts c [N,4] (TP, FP, FN, TN) and mask scores [N]."""
+    c = np.asarray(c, np.int64).reshape(-1, 4)
+    n = len(c)
+    thr = np.linspace(0.5, 0.95, 10)
+    union = (c[:, 0] + c[:, 1] + c[:, 2]).astype(np.float64)
+    iou = np.where(union > 0, c[:, 0] / np.maximum(union, 1), 0.0)
+    d_area, g_area = (c[:, 0] + c[:, 1]).astype(np.float64), (c[:, 0] + c[:, 2]).astype(np.float64)
+    bounds = [(0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10)]     # AREA_RANGES, inclusive
+    matched = iou[:, None] >= np.minimum(thr, 1 - 1e-10)[None, :]                          # [N, T]: the one GT of the image
+    tbits = (np.uint32(1) << np.arange(len(thr), dtype=np.uint32))
+    match, ignore, gt_bits = np.zeros((n, 4), np.uint32), np.zeros((n, 4), np.uint32), np.zeros(n, np.uint32)
+    for a, (lo, hi) in enumerate(bounds):
+        g_in = (g_area >= lo) & (g_area <= hi)
+        d_in = (d_area >= lo) & (d_area <= hi)
+        gt_bits |= np.where(g_in, np.uint32(1 << a), np.uint32(0))
+        ig = np.where(matched, ~g_in[:, None], ~d_in[:, None])                              # matched: the GT's flag; else the detection's
+        match[:, a] = (matched * tbits).sum(1).astype(np.uint32)
+        ignore[:, a] = (ig * tbits).sum(1).astype(np.uint32)
+    rec = {"image": np.arange(n, dtype=np.int64), "rank": np.zeros(n, np.int64), "score": np.asarray(score, np.float64).ravel(),
+           "label": np.zeros(n, np.int64), "match": match, "ignore": ignore, "gt_label": np.zeros(n, np.int64), "gt_area": gt_bits}
+    return _accumulate(rec, thr, (1, 10, 100))
+
+
+class _ConfusionCounts:
+    """A [nc, nc] int64 confusion matrix (row = target, column = prediction) that a kernel adds to on the device, plus its status
+    word, in ONE device buffer of nc * nc + 1 int64 (the status is the int32 low word of the last one): `compute()` copies it once."""
+
+    def __init__(self, num_classes: int, dist_sync: bool, process_group):
+        num_classes = int(num_classes)
+        if not 1 <= num_classes <= L.CONFUSION_MAX_NC:
+            raise ValueError(f"{type(self).__name__}: between 1 and {L.CONFUSION_MAX_NC} classes, got {num_classes}")
+        self.num_classes, self.dist_sync, self.group = num_classes, dist_sync, process_group
+        self.reset()
+
+    def reset(self):
+        self._state: Optional[torch.Tensor] = None
+
+    def _buffers(self, dev):
+        """-> (counts pointer, status pointer) on `dev`, zeroed at the first update after a reset."""
+        nc = self.num_classes
+        if self._state is None:
+            self._state = torch.zeros(nc * nc + 1, dtype=torch.int64, device=dev)
+        elif self._state.device != dev:
+            raise ValueError(f"{type(self).__name__}: this metric keeps its counts on {self._state.device}, the batch is on {dev}")
+        return self._state.data_ptr(), self._state[nc * nc:].view(torch.int32).data_ptr()
+
+    def counts(self) -> np.ndarray:
+        """[nc, nc] int64 over this process's updates -- or, with a live process group (and dist_sync), the sum over ALL ranks (a
+        collective; the local state is left as it is).  Raises ValueError when a target class was outside [0, nc)."""
+        nc = self.num_classes
+        st = self._state.cpu().numpy() if self._state is not None else np.zeros(nc * nc + 1, np.int64)
+        if self.dist_sync and _world(self.group) > 1:
+            parts = _all_gather_records([st], self.group)
+            st = np.concatenate([np.sum([p[:-1] for p in parts], axis=0), [max(int(p[-1]) for p in parts)]])
+        if st[-1]:
+            raise ValueError(f"{type(self).__name__}.compute: a target class outside [0, {nc}) was seen (those samples are not counted)")
+        return st[:-1].reshape(nc, nc).astype(np.int64)
+
+
+def _normalize_rows(cm: np.ndarray) -> np.ndarray:
+    """torchmetrics normalize="true": each row divided by its sum; a row without samples stays all zeros."""
+    rows = cm.sum(axis=1, keepdims=True).astype(np.float64)
+    return np.where(rows > 0, cm / np.maximum(rows, 1), 0.0)
+
+
+class ImageClassificationMetrics(_ConfusionCounts):
+    """Image-class metrics of the validation epoch: MulticlassAccuracy(average="micro") and MulticlassConfusionMatrix(normalize="true")
+    of running_main_v3.py:193-195 (fed at :458-459, logged at :609-616), and the macro precision / recall / F1 of
+    evaluate_model.py:244-272 -- all from one device-side confusion matrix (`mtbt_cls_confusion`).
+
+    `update(logits [B, nc], target [B])` is asynchronous (no host synchronisation) and rejects CPU tensors.  `compute()` ->
+    accuracy (micro: correct / N, 0.0 without samples), confusion_matrix (row-normalised, a row without samples is all zeros),
+    confusion_counts, precision_macro / recall_macro / f1_macro (per class 0 where the denominator is 0; the mean runs over the
+    classes with tp + fp + fn > 0, 0.0 if there are none).  A target outside [0, nc) makes `compute()` raise ValueError, as
+    torchmetrics' target validation does."""
+
+    def __init__(self, num_classes: int, dist_sync: bool = True, process_group=None):
+        super().__init__(num_classes, dist_sync, process_group)
+
+    def update(self, logits: torch.Tensor, target: torch.Tensor):
+        if not (logits.is_cuda and target.is_cuda):
+            raise RuntimeError("ImageClassificationMetrics.update: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+        if logits.dim() != 2 or logits.shape[1] != self.num_classes or target.shape != logits.shape[:1]:
+            raise ValueError(f"ImageClassificationMetrics.update: logits [B, {self.num_classes}] and target [B]")
+        if logits.device != target.device:
+            raise ValueError("ImageClassificationMetrics.update: logits and target on different devices")
+        if logits.shape[0] == 0:
+            return
+        lib = L.load()
+        dev = logits.device
+        x, t = logits.float().contiguous(), target.long().contiguous()
+        counts, status = self._buffers(dev)
+        L.check(lib.mtbt_cls_confusion(x.data_ptr(), t.data_ptr(), x.shape[0], self.num_classes, counts, status,
+                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_cls_confusion")
+
+    def compute(self) -> Dict[str, object]:
+        cm = self.counts()
+        tp = np.diag(cm).astype(np.float64)
+        fp, fn = cm.sum(axis=0) - tp, cm.sum(axis=1) - tp
+        n = float(cm.sum())
+        div = lambda a, b: np.where(b > 0, a / np.where(b > 0, b, 1), 0.0)
+        present = (tp + fp + fn) > 0
+        macro = lambda v: float(v[present].mean()) if present.any() else 0.0
+        return {"accuracy": float(tp.sum()) / n if n else 0.0, "confusion_matrix": _normalize_rows(cm), "confusion_counts": cm,
+                "precision_macro": macro(div(tp, tp + fp)), "recall_macro": macro(div(tp, tp + fn)), "f1_macro": macro(div(2 * tp, 2 * tp + fp + fn))}
+
+
+class DetectionConfusionMatrix(_ConfusionCounts):
+    """The detection confusion matrix of the validation epoch (MulticlassConfusionMatrix(nc_det, normalize="true") of
+    running_main_v3.py:218, fed at :710-722 with the (argmax of the class logits, GT class) pairs that the eval-mode `_multitask_loss`
+    collects over its positive anchors at :349-350).
+
+    `update(det_maps, gt_rows)`: the raw Detect maps of `forward(x, "train")` and the collated [M, 6] GT rows -- the inputs
+    `multitask_loss` takes.  One `mtbt_det_confusion` launch decodes and matches every anchor exactly as the loss does (its argument
+    block is built by the same helper, `loss.det_loss_args`), so the counted anchors are the loss's positives.  Asynchronous; rejects
+    CPU tensors.  `compute()` -> confusion_matrix (row-normalised, empty rows all zeros) and confusion_counts; a GT class outside
+    [0, nc_det) makes it raise ValueError."""
+
+    def __init__(self, nc_det: int, img_size: int, iou_match_thresh: float = 0.5, reg_max: int = 16, dist_sync: bool = True, process_group=None):
+        super().__init__(nc_det, dist_sync, process_group)
+        self.img_size, self.iou_match_thresh, self.reg_max = img_size, float(iou_match_thresh), int(reg_max)
+
+    def update(self, det_maps: Sequence[torch.Tensor], gt_rows: torch.Tensor):
+        if not (all(m.is_cuda for m in det_maps) and gt_rows.is_cuda):
+            raise RuntimeError("DetectionConfusionMatrix.update: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+        if not 1 <= len(det_maps) <= 3 or any(m.dim() != 4 or m.shape[1] != 4 * self.reg_max + self.num_classes for m in det_maps):
+            raise ValueError(f"DetectionConfusionMatrix.update: 1 to 3 Detect maps [B, {4 * self.reg_max + self.num_classes}, h, w]")
+        if gt_rows.dim() != 2 or gt_rows.shape[1] != 6:
+            raise ValueError("DetectionConfusionMatrix.update: gt_rows must be [M, 6] (batch_idx, cls, cx, cy, w, h)")
+        if det_maps[0].shape[0] == 0:
+            return
+        from .loss import det_loss_args
+        lib = L.load()
+        dev = det_maps[0].device
+        a, keep = det_loss_args(det_maps, gt_rows, img_size=self.img_size, nc_det=self.num_classes, reg_max=self.reg_max,
+                                iou_match_thresh=self.iou_match_thresh)
+        counts, status = self._buffers(dev)
+        L.check(lib.mtbt_det_confusion(C.byref(a), counts, status, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_det_confusion")
+        del keep
+
+    def compute(self) -> Dict[str, object]:
+        cm = self.counts()
+        return {"confusion_matrix": _normalize_rows(cm), "confusion_counts": cm}

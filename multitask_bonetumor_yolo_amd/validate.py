@@ -1,0 +1,144 @@
+"""The whole validation step as device work with no host synchronisation -- the counterpart of `trainstep.TrainStep`.
+
+    vs = ValidationStep(model, projector=lit.seg_proto_projector, img_size=640)
+    for ids, imgs, det_gt, masks_gt, cls_gt in val_loader:          # device tensors
+        losses = vs.step(imgs, det_gt, masks_gt, cls_gt)            # 6 x 0-d device tensors
+    logs = vs.compute()                                             # the reference's log keys; a collective under DDP
+    vs.reset()
+
+`step()` is `/root/reference/src/running_main_v3.py:447-599` (`validation_step`) per batch, every part fed from the SAME train-mode
+maps: forward(x, "train") -> eval-mode `_multitask_loss` -> segmentation counts -> image and detection confusion matrices -> decode /
+NMS -> the two box mAPs.  `compute()` is the epoch end (`:605-729`): the batch-size-weighted loss means and every metric under the
+key the reference logs it with.
+"""
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .loss import multitask_loss
+from .metrics import (DetectionConfusionMatrix, DeviceMeanAveragePrecision, ImageClassificationMetrics, SegmentationMetrics, _all_gather_records,
+                      _world)
+from .postprocess import CONF_TH, NMS_IOU, TOP_K, decode_boxes, nms_batched, proto_projector_logits
+
+LOSS_NAMES = ("total", "seg", "box_iou", "dfl", "det_cls", "img_cls")       # running_main_v3.py:578-582
+
+
+class BatchWeightedMeans:
+    """Epoch means of per-batch 0-d device tensors weighted by the batch size: sum over every step of every rank of B * value, divided
+    by the sum of B.  This is what Lightning's `log(..., on_epoch=True, sync_dist=True)` reduces to for a mean (the Lightning version is
+    unpinned in the reference; this definition is the one implemented).  `update` adds on the device (fp64), without a host sync;
+    `compute()` copies the sums once and, with a live process group (and dist_sync), adds every rank's sums and batch counts (a
+    collective) and leaves the local state untouched."""
+
+    def __init__(self, n: int, dist_sync: bool = True, process_group=None):
+        self.n, self.dist_sync, self.group = int(n), dist_sync, process_group
+        self.reset()
+
+    def reset(self):
+        self._sum: Optional[torch.Tensor] = None
+        self._count = 0
+
+    def update(self, values: Sequence[torch.Tensor], batch_size: int):
+        v = torch.stack([t.reshape(()) for t in values[: self.n]]).to(torch.float64) * float(batch_size)
+        self._sum = v if self._sum is None else self._sum.add_(v)
+        self._count += int(batch_size)
+
+    def compute(self) -> np.ndarray:
+        s = self._sum.cpu().numpy() if self._sum is not None else np.zeros(self.n, np.float64)
+        count = self._count
+        if self.dist_sync and _world(self.group) > 1:
+            parts = _all_gather_records([(s, count)], self.group)
+            s, count = np.sum([p[0] for p in parts], axis=0), sum(p[1] for p in parts)
+        return s / count if count else np.zeros(self.n, np.float64)
+
+
+class ValidationStep:
+    def __init__(self, model, *, projector: Optional[nn.Conv2d] = None, img_size: int = 640, iou_match_thresh: float = 0.5,
+                 label_smoothing: float = 0.1, loss_weights=(1.0, 2.0, 1.5, 0.5, 1.0), conf_th: float = CONF_TH, nms_iou: float = NMS_IOU,
+                 top_k: int = TOP_K, map_max_detections: int = 100, dist_sync: bool = True, process_group=None):
+        """`projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1), running_main_v3.py:186); created with torch's default
+        init when not given.  The loss hyper-parameters default to the reference's (and TrainStep's); `label_smoothing` is accepted for
+        symmetry with TrainStep but the eval-mode loss never smooths (:337).  conf_th / nms_iou / top_k: `:54-56`;
+        `map_max_detections`: the trainer's hparam of :209-217."""
+        if not hasattr(model, "detect"):
+            raise NotImplementedError("ValidationStep drives the canonical model (running_main_v3.py needs .detect, SURVEY F4)")
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("ValidationStep: the model must live on an MI355X (no CPU path)")
+        self.m, self.dev, self.S = model, dev, int(img_size)
+        self.projector = (projector if projector is not None else nn.Conv2d(model.proto_ch, 1, 1)).to(dev)
+        self.nc_det, self.reg_max = model.nc_det, model.detect.reg_max
+        self.loss_kw = dict(img_size=self.S, nc_det=self.nc_det, reg_max=self.reg_max, iou_match_thresh=iou_match_thresh,
+                            label_smoothing=label_smoothing, training=False, weights=loss_weights)
+        self.nms_kw = dict(conf_th=conf_th, iou_th=nms_iou, top_k=top_k)
+        sync = dict(dist_sync=dist_sync, process_group=process_group)
+        self.losses = BatchWeightedMeans(len(LOSS_NAMES), **sync)
+        self.seg = SegmentationMetrics(**sync)
+        self.img = ImageClassificationMetrics(model.nc_img, **sync)
+        self.det_cm = DetectionConfusionMatrix(self.nc_det, self.S, iou_match_thresh, self.reg_max, **sync)
+        max_dets = (1, 10, int(map_max_detections))
+        self.map50 = DeviceMeanAveragePrecision([0.5], max_dets, **sync)
+        self.map50_95 = DeviceMeanAveragePrecision(None, max_dets, **sync)
+
+    def reset(self):
+        for m in (self.losses, self.seg, self.img, self.det_cm, self.map50, self.map50_95):
+            m.reset()
+
+    def forward(self, x: torch.Tensor):
+        """forward(x, "train") under no_grad with the module in eval mode, as Lightning runs `validation_step`: the backbone and neck use
+        their running statistics while the heads -- which forward(mode="train") switches to train mode -- run on batch statistics (the
+        reference's flag quirk; kept).  Every module's `.training` flag is restored afterwards."""
+        flags = [(mod, mod.training) for mod in self.m.modules()]
+        self.m.eval()
+        try:
+            with torch.no_grad():
+                return self.m(x, "train")
+        finally:
+            for mod, f in flags:
+                mod.training = f
+
+    def step(self, imgs: torch.Tensor, det_gt: torch.Tensor, masks_gt: torch.Tensor, cls_gt: torch.Tensor):
+        """One validation batch: imgs [B,3,S,S], det_gt [M,6] collated rows, masks_gt [B,1,S,S], cls_gt [B], all on the model's device.
+        Returns the eval-mode loss tuple (total, seg, box, dfl, cls_det, img_cls) as 0-d device tensors; no host synchronisation."""
+        if not all(t.is_cuda for t in (imgs, det_gt, masks_gt, cls_gt)):
+            raise RuntimeError("ValidationStep.step: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+        B = imgs.shape[0]
+        det, seg_out, logits = self.forward(imgs)
+        protos = seg_out[2]
+        pj = self.projector
+        losses = multitask_loss(det, protos, logits, det_gt, masks_gt, cls_gt, pj.weight, pj.bias, **self.loss_kw)
+        self.losses.update(losses, B)
+        self.seg.update(proto_projector_logits(protos, pj.weight, pj.bias, self.S), masks_gt)
+        self.img.update(logits, cls_gt)
+        self.det_cm.update(det, det_gt)
+        d = decode_boxes(det, self.S, reg_max=self.reg_max, want_scores=False)
+        k = nms_batched(d["boxes"], d["best_score"], d["best_label"], float(self.S), **self.nms_kw)
+        self.map50.update_batched(k, det_gt, self.S)
+        self.map50_95.update_batched(k, det_gt, self.S)
+        return losses
+
+    def compute(self) -> Dict[str, object]:
+        """The epoch's numbers under the reference's log keys (running_main_v3.py:578-582, :605-729; evaluate_model.py:244-272 for the
+        macro image scores), plus the alias `val_epoch_map_iou50/map` that the checkpoint callback monitors (:803).  Confusion matrices
+        are row-normalised numpy arrays.  With a live process group: over every rank's batches (a collective, every rank must call it)."""
+        out: Dict[str, object] = {}
+        for name, v in zip(LOSS_NAMES, self.losses.compute()):
+            out[f"val_epoch/loss_{name}"] = float(v)
+        img = self.img.compute()
+        out["val_epoch/img_accuracy_epoch"] = img["accuracy"]
+        out["val_epoch/img_confusion_matrix_epoch"] = img["confusion_matrix"]
+        for k in ("precision", "recall", "f1"):
+            out[f"val_epoch/img_{k}_macro"] = img[f"{k}_macro"]
+        out["val_epoch/det_confusion_matrix_epoch"] = self.det_cm.compute()["confusion_matrix"]
+        seg = self.seg.compute()
+        for k in ("f1", "precision", "recall", "accuracy", "dice"):
+            out[f"val_epoch/seg_{k}_epoch"] = seg[k]
+        for k, v in self.seg.compute_map().items():
+            out[f"val_epoch/seg_map_{k}"] = v
+        for prefix, m in (("val_epoch/map_iou50_95", self.map50_95), ("val_epoch/map_iou50", self.map50)):
+            for k, v in m.compute().items():
+                out[f"{prefix}_{k}"] = v
+        out["val_epoch_map_iou50/map"] = out["val_epoch/map_iou50_map"]
+        return out
