@@ -10,17 +10,20 @@ torchmetrics' binary stat-score definitions.
                           `update`); F1 / precision / recall / accuracy / Dice / IoU and the single-instance mask mAP of
                           :480-497 from those counts in `compute`.
   MeanAveragePrecision    COCO box mAP over IoU thresholds with `max_detection_thresholds` (mAP@0.5 and @0.5:0.95 of :206-214):
-                          host-side numpy -- at most 100 kept boxes per image after the device NMS, a few GT boxes.
+                          host-side numpy matching -- at most 100 kept boxes per image after the device NMS, a few GT boxes.
   DeviceMeanAveragePrecision
                           torchmetrics' full bbox key set (the four COCO area ranges, per-class values with `class_metrics`): the
                           per-image matching on the device (`mtbt_box_eval`, straight from the NMS output and the collated GT rows,
-                          no host sync per step), `accumulate` / `summarize` once per epoch in vectorised numpy (`_accumulate`).
+                          no host sync per step).
   ImageClassificationMetrics
                           image-class accuracy, normalised confusion matrix (:193-195, :458-459, :609-616) and the macro precision /
                           recall / F1 of evaluate_model.py:244-272 from a device-side confusion matrix (`mtbt_cls_confusion`).
   DetectionConfusionMatrix
                           the confusion matrix of the eval-mode loss's matched anchors (:218, :349-350, :710-722), counted on the
                           device by the loss's own decode and match (`mtbt_det_confusion`).
+
+The two box classes and the segmentation mAP differ only in how they match; all three accumulate and summarise (pycocotools
+`accumulate` / `summarize`) through one vectorised numpy function, `_accumulate`, once per epoch.
 
 Data-parallel validation (configs[3]: one process per GPU, each rank sees its shard of the validation set): the reference's metric
 objects are built with `dist_sync_on_step=True` (`running_main_v3.py:193-218`), i.e. torchmetrics gathers every rank's state before it
@@ -54,6 +57,20 @@ def _all_gather_records(local, group=None):
     return [rec for part in parts for rec in part]
 
 
+def _sum_over_ranks(x: np.ndarray, group=None) -> np.ndarray:
+    """`x` summed over the ranks of a live multi-rank process group, in rank order (a collective: all ranks must call it); without
+    one, `x` itself."""
+    return np.sum(_all_gather_records([x], group), axis=0) if _world(group) > 1 else x
+
+
+COCO_IOU_THRESHOLDS = tuple(np.linspace(0.5, 0.95, 10))     # 0.50:0.05:0.95, the default of every mAP here (COCOeval.Params.iouThrs)
+
+
+def _iou_limits(iou_thresholds) -> np.ndarray:
+    """The IoU a match needs at each threshold: pycocotools evaluateImg caps the threshold just below 1."""
+    return np.minimum(np.asarray(iou_thresholds, np.float64), 1 - 1e-10)
+
+
 def box_iou_xyxy(a: np.ndarray, b: np.ndarray) -> np.ndarray:
     """COCO box IoU in float64 (pycocotools `bbIou` without crowd boxes): [D,4] x [G,4] -> [D,G]."""
     a, b = np.asarray(a, np.float64).reshape(-1, 4), np.asarray(b, np.float64).reshape(-1, 4)
@@ -66,7 +83,7 @@ def box_iou_xyxy(a: np.ndarray, b: np.ndarray) -> np.ndarray:
 
 
 class MeanAveragePrecision:
-    """COCO mAP / mAR for one area range ("all"), any IoU thresholds, any max-detection thresholds.
+    """COCO mAP / mAR for one area range ("all"), up to 32 IoU thresholds, any max-detection thresholds.
 
     `update(preds, targets)` takes the torchmetrics layout the reference builds (`running_main_v3.py:553-575`): per image
     `dict(boxes [D,4] xyxy, scores [D], labels [D])` and `dict(boxes [G,4], labels [G])`."""
@@ -74,9 +91,10 @@ class MeanAveragePrecision:
     def __init__(self, iou_thresholds: Optional[Sequence[float]] = None, max_detection_thresholds: Sequence[int] = (1, 10, 100),
                  dist_sync: bool = True, process_group=None):
         self.dist_sync, self.group = dist_sync, process_group
-        self.iou_thresholds = np.asarray(iou_thresholds if iou_thresholds is not None else np.linspace(0.5, 0.95, 10), np.float64)
+        self.iou_thresholds = np.asarray(iou_thresholds if iou_thresholds is not None else COCO_IOU_THRESHOLDS, np.float64)
+        if self.iou_thresholds.size > 32:
+            raise ValueError("MeanAveragePrecision: at most 32 IoU thresholds (one bit each in a match word)")
         self.max_dets = sorted(int(m) for m in max_detection_thresholds)
-        self.rec_thresholds = np.linspace(0.0, 1.0, 101)
         self._images: List[tuple] = []
 
     def reset(self):
@@ -94,74 +112,50 @@ class MeanAveragePrecision:
             self.add_image(self._np(p["scores"], np.float64), self._np(p["labels"], np.int64), self._np(t["labels"], np.int64), box_iou_xyxy(db, gb))
 
     def add_image(self, scores, labels, gt_labels, iou):
-        """One image with a precomputed IoU matrix [D, G] (boxes above; mask IoU for the segmentation mAP)."""
+        """One image with a precomputed IoU matrix [D, G] (`update` computes it from the boxes)."""
         scores, labels, gt_labels = np.asarray(scores, np.float64).ravel(), np.asarray(labels, np.int64).ravel(), np.asarray(gt_labels, np.int64).ravel()
         iou = np.asarray(iou, np.float64).reshape(len(scores), len(gt_labels))
         self._images.append((scores, labels, gt_labels, iou))
 
     def _match(self, iou: np.ndarray) -> np.ndarray:
         """pycocotools evaluateImg without crowd / ignore flags: detections in score order, each takes the still unmatched GT
-        of highest IoU >= threshold (of equal IoUs the later GT).  -> matched [T, D] bool."""
+        of highest IoU >= threshold (of equal IoUs the later GT).  -> match words [D] uint32, bit t = matched at threshold t."""
         D, G = iou.shape
-        out = np.zeros((len(self.iou_thresholds), D), bool)
+        word = np.zeros(D, np.uint32)
         if G == 0:
-            return out
-        for ti, t in enumerate(self.iou_thresholds):
+            return word
+        for t, lim in enumerate(_iou_limits(self.iou_thresholds)):
             free = np.ones(G, bool)
-            lim = min(t, 1 - 1e-10)
             for d in range(D):
                 v = np.where(free, iou[d], -1.0)
                 m = G - 1 - int(np.argmax(v[::-1]))
                 if v[m] >= lim:
                     free[m] = False
-                    out[ti, d] = True
-        return out
+                    word[d] |= np.uint32(1 << t)
+        return word
 
     def compute(self) -> Dict[str, float]:
-        """With a live process group (and dist_sync): over the images of ALL ranks -- a collective, every rank must call it."""
+        """With a live process group (and dist_sync): over the images of ALL ranks -- a collective, every rank must call it.
+
+        The detections become `_accumulate` records of the area range "all" (no boxes reach `add_image`, so no other range is
+        defined): rank = position in the stable score order of its (image, class), -1 past max_detection_thresholds[-1]; the match
+        word of `_match` over those ranked detections (greedy in score order: every max-detection prefix matches as the whole list
+        does); no ignore flags."""
         images = _all_gather_records(self._images, self.group) if self.dist_sync else self._images
-        T, R, M = len(self.iou_thresholds), len(self.rec_thresholds), len(self.max_dets)
-        classes = sorted(set(int(c) for im in images for c in np.concatenate([im[1], im[2]])))
-        precision, recall = -np.ones((T, R, len(classes), M)), -np.ones((T, len(classes), M))
-        for k, c in enumerate(classes):
-            per_image, npig = [], 0
-            for scores, labels, gt_labels, iou in images:
-                di, gi = np.nonzero(labels == c)[0], np.nonzero(gt_labels == c)[0]
-                npig += len(gi)
-                if len(di):
-                    di = di[np.argsort(-scores[di], kind="mergesort")][: self.max_dets[-1]]
-                    per_image.append((scores[di], iou[np.ix_(di, gi)]))
-            if npig == 0:
-                continue
-            for m, maxdet in enumerate(self.max_dets):
-                sc = np.concatenate([s[:maxdet] for s, _ in per_image]) if per_image else np.zeros(0)
-                tp = np.concatenate([self._match(i[:maxdet]) for _, i in per_image], axis=1) if per_image else np.zeros((T, 0), bool)
-                order = np.argsort(-sc, kind="mergesort")
-                tp = tp[:, order]
-                tps, fps = np.cumsum(tp, axis=1).astype(np.float64), np.cumsum(~tp, axis=1).astype(np.float64)
-                for t in range(T):
-                    nd = tps.shape[1]
-                    rc = tps[t] / npig
-                    pr = tps[t] / (fps[t] + tps[t] + np.spacing(1))
-                    recall[t, k, m] = rc[-1] if nd else 0.0
-                    pr = np.maximum.accumulate(pr[::-1])[::-1]                       # precision envelope
-                    inds = np.searchsorted(rc, self.rec_thresholds, side="left")
-                    q = np.zeros(R)
-                    ok = inds < nd
-                    q[ok] = pr[inds[ok]]
-                    precision[t, :, k, m] = q
-
-        def mean(a):
-            a = a[a > -1]
-            return float(a.mean()) if a.size else -1.0
-
-        out = {"map": mean(precision[:, :, :, -1])}
-        for name, thr in (("map_50", 0.5), ("map_75", 0.75)):
-            hit = np.nonzero(np.isclose(self.iou_thresholds, thr))[0]
-            out[name] = mean(precision[hit[0], :, :, -1]) if len(hit) else -1.0
-        for m, maxdet in enumerate(self.max_dets):
-            out[f"mar_{maxdet}"] = mean(recall[:, :, m])
-        return out
+        n = [len(im[0]) for im in images]
+        cat = lambda k, dtype: np.concatenate([np.zeros(0, dtype)] + [im[k] for im in images])
+        rank, match = np.full(sum(n), -1, np.int64), np.zeros((sum(n), len(AREA_RANGES)), np.uint32)
+        for (scores, labels, gt_labels, iou), off in zip(images, np.cumsum([0] + n)):
+            for c in np.unique(labels):
+                di = np.nonzero(labels == c)[0]
+                di = di[np.argsort(-scores[di], kind="mergesort")][: self.max_dets[-1]]
+                rank[off + di] = np.arange(len(di))
+                match[off + di, 0] = self._match(iou[np.ix_(di, np.nonzero(gt_labels == c)[0])])
+        gt_label = cat(2, np.int64)
+        rec = {"image": np.repeat(np.arange(len(images)), n), "rank": rank, "score": cat(0, np.float64), "label": cat(1, np.int64),
+               "match": match, "ignore": np.zeros_like(match), "gt_label": gt_label, "gt_area": np.ones(len(gt_label), np.uint32)}
+        out = _accumulate(rec, self.iou_thresholds, self.max_dets)
+        return {k: out[k] for k in ("map", "map_50", "map_75", *(f"mar_{m}" for m in self.max_dets))}
 
 
 AREA_RANGES = ("all", "small", "medium", "large")   # COCO: [0, 1e10], [0, 32^2], [32^2, 96^2], [96^2, 1e10], bounds inclusive
@@ -170,7 +164,8 @@ BOX_EVAL_CAP = 1024                                 # detections per image slot 
 
 def _accumulate(records: Dict[str, np.ndarray], iou_thresholds: Sequence[float], max_dets: Sequence[int],
                 class_metrics: bool = False) -> Dict[str, object]:
-    """pycocotools `accumulate` + `summarize` over per-detection records of the device matching (`mtbt_box_eval`), vectorised.
+    """pycocotools `accumulate` + `summarize` over per-detection records, vectorised: the one implementation behind every mAP here
+    (the records of the device matching `mtbt_box_eval`, of `MeanAveragePrecision._match` and of `_segm_map`).
 
     records: `image` [N] (update order), `rank` [N] (within (image, class); < 0 = not kept), `score` [N], `label` [N],
     `match` / `ignore` [N, 4] uint32 (word = area range, bit t = IoU threshold t), `gt_label` [G], `gt_area` [G] uint32
@@ -256,7 +251,7 @@ class DeviceMeanAveragePrecision:
             raise ValueError(f"DeviceMeanAveragePrecision: box_format {box_format!r} is not supported (only 'xyxy')")
         if iou_type != "bbox":
             raise ValueError(f"DeviceMeanAveragePrecision: iou_type {iou_type!r} is not supported (only 'bbox')")
-        self.iou_thresholds = np.asarray(iou_thresholds if iou_thresholds is not None else np.linspace(0.5, 0.95, 10), np.float64).ravel()
+        self.iou_thresholds = np.asarray(iou_thresholds if iou_thresholds is not None else COCO_IOU_THRESHOLDS, np.float64).ravel()
         if not 1 <= len(self.iou_thresholds) <= 32:
             raise ValueError("DeviceMeanAveragePrecision: between 1 and 32 IoU thresholds")
         self.max_dets = sorted(int(m) for m in max_detection_thresholds)
@@ -441,7 +436,8 @@ class SegmentationMetrics:
         return c, (p / ((c[:, 0] + c[:, 1]).astype(np.float32) + np.float32(1e-6))).astype(np.float32)
 
     def compute(self) -> Dict[str, float]:
-        """With a live process group (and dist_sync): from the pixel counts of ALL ranks -- a collective, every rank must call it."""
+        """With a live process group (and dist_sync): from the pixel counts of ALL ranks -- a collective, every rank must call it.
+        seg_map / seg_map_50 are the map / map_50 of `compute_map` (:478-497), -1.0 without images."""
         c, score = self.per_image(sync=self.dist_sync)
         tp, fp, fn, tn = (float(v) for v in c.sum(axis=0)) if len(c) else (0.0, 0.0, 0.0, 0.0)
         div = lambda a, b: a / b if b else 0.0                                    # torchmetrics _safe_divide
@@ -450,13 +446,7 @@ class SegmentationMetrics:
         den = (2 * c[:, 0] + c[:, 1] + c[:, 2]).astype(np.float64)
         dice = np.where(den > 0, 2 * c[:, 0] / np.maximum(den, 1), np.nan)         # per sample; empty-vs-empty samples are skipped
         out["dice"] = float(np.nanmean(dice)) if np.any(den > 0) else 0.0
-        # segmentation mAP (:478-497): one predicted instance (class 0) and one GT instance per image
-        m = MeanAveragePrecision(dist_sync=False)                              # (c, score already hold every rank's images)
-        union = (c[:, 0] + c[:, 1] + c[:, 2]).astype(np.float64)
-        iou = np.where(union > 0, c[:, 0] / np.maximum(union, 1), 0.0)
-        for i in range(len(c)):
-            m.add_image([score[i]], [0], [0], [[iou[i]]])
-        seg = m.compute() if len(c) else {"map": -1.0, "map_50": -1.0}
+        seg = _segm_map(c, score)
         out["seg_map"], out["seg_map_50"] = seg["map"], seg["map_50"]
         return out
 
@@ -479,12 +469,12 @@ def _segm_map(c: np.ndarray, score: np.ndarray) -> Dict[str, float]:
     """SegmentationMetrics.compute_map from per-image counts c [N,4] (TP, FP, FN, TN) and mask scores [N]."""
     c = np.asarray(c, np.int64).reshape(-1, 4)
     n = len(c)
-    thr = np.linspace(0.5, 0.95, 10)
+    thr = COCO_IOU_THRESHOLDS
     union = (c[:, 0] + c[:, 1] + c[:, 2]).astype(np.float64)
     iou = np.where(union > 0, c[:, 0] / np.maximum(union, 1), 0.0)
     d_area, g_area = (c[:, 0] + c[:, 1]).astype(np.float64), (c[:, 0] + c[:, 2]).astype(np.float64)
     bounds = [(0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10)]     # AREA_RANGES, inclusive
-    matched = iou[:, None] >= np.minimum(thr, 1 - 1e-10)[None, :]                          # [N, T]: the one GT of the image
+    matched = iou[:, None] >= _iou_limits(thr)[None, :]                                     # [N, T]: the one GT of the image
     tbits = (np.uint32(1) << np.arange(len(thr), dtype=np.uint32))
     match, ignore, gt_bits = np.zeros((n, 4), np.uint32), np.zeros((n, 4), np.uint32), np.zeros(n, np.uint32)
     for a, (lo, hi) in enumerate(bounds):
@@ -527,12 +517,12 @@ class _ConfusionCounts:
         collective; the local state is left as it is).  Raises ValueError when a target class was outside [0, nc)."""
         nc = self.num_classes
         st = self._state.cpu().numpy() if self._state is not None else np.zeros(nc * nc + 1, np.int64)
-        if self.dist_sync and _world(self.group) > 1:
-            parts = _all_gather_records([st], self.group)
-            st = np.concatenate([np.sum([p[:-1] for p in parts], axis=0), [max(int(p[-1]) for p in parts)]])
-        if st[-1]:
+        cm, status = st[:-1], int(st[-1])
+        if self.dist_sync:
+            cm, status = _sum_over_ranks(cm, self.group), max(_all_gather_records([status], self.group))
+        if status:
             raise ValueError(f"{type(self).__name__}.compute: a target class outside [0, {nc}) was seen (those samples are not counted)")
-        return st[:-1].reshape(nc, nc).astype(np.int64)
+        return cm.reshape(nc, nc).astype(np.int64)
 
 
 def _normalize_rows(cm: np.ndarray) -> np.ndarray:

@@ -18,8 +18,7 @@ import torch
 import torch.nn as nn
 
 from .loss import multitask_loss
-from .metrics import (DetectionConfusionMatrix, DeviceMeanAveragePrecision, ImageClassificationMetrics, SegmentationMetrics, _all_gather_records,
-                      _world)
+from .metrics import DetectionConfusionMatrix, DeviceMeanAveragePrecision, ImageClassificationMetrics, SegmentationMetrics, _sum_over_ranks
 from .postprocess import CONF_TH, NMS_IOU, TOP_K, decode_boxes, nms_batched, proto_projector_logits
 
 LOSS_NAMES = ("total", "seg", "box_iou", "dfl", "det_cls", "img_cls")       # running_main_v3.py:578-582
@@ -46,12 +45,10 @@ class BatchWeightedMeans:
         self._count += int(batch_size)
 
     def compute(self) -> np.ndarray:
-        s = self._sum.cpu().numpy() if self._sum is not None else np.zeros(self.n, np.float64)
-        count = self._count
-        if self.dist_sync and _world(self.group) > 1:
-            parts = _all_gather_records([(s, count)], self.group)
-            s, count = np.sum([p[0] for p in parts], axis=0), sum(p[1] for p in parts)
-        return s / count if count else np.zeros(self.n, np.float64)
+        s = np.append(self._sum.cpu().numpy() if self._sum is not None else np.zeros(self.n), self._count)   # the sums, then the count
+        if self.dist_sync:
+            s = _sum_over_ranks(s, self.group)
+        return s[:-1] / s[-1] if s[-1] else np.zeros(self.n, np.float64)
 
 
 class ValidationStep:

@@ -1,10 +1,14 @@
-"""COCO mAP host logic (multitask_bonetumor_yolo_amd.metrics) against hand-computed cases and the loop-form oracle.
-torchmetrics / pycocotools are absent: PARITY UNPINNED against them; the algorithm is pycocotools' published one."""
+"""COCO mAP host logic (multitask_bonetumor_yolo_amd.metrics) against hand-computed cases and two loop-form restatements (the oracle's
+and tests/coco_reference.py's).  torchmetrics / pycocotools are absent: PARITY UNPINNED against them; the algorithm is pycocotools'
+published one."""
 import numpy as np
+import pytest
 import torch
 
 from oracle import metrics as O
 from multitask_bonetumor_yolo_amd.metrics import MeanAveragePrecision, box_iou_xyxy
+
+from coco_reference import COCO, _random_set, coco_loop
 
 
 def _box(x, y, w=10.0, h=10.0):
@@ -66,6 +70,22 @@ def test_matches_loop_oracle_on_random_sets():
         assert set(got) == set(want)
         for k in want:
             assert abs(got[k] - want[k]) < 1e-12, (trial, k, got[k], want[k])
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+@pytest.mark.parametrize("max_dets", [[1, 3, 10], [1, 10, 100]])
+@pytest.mark.parametrize("thr", [[0.5], COCO])
+def test_equals_coco_reference_restatement(seed, max_dets, thr):
+    """The host matching plus the shared `_accumulate` against the restatement that shares no code with either, on the keys the
+    host class returns (area range "all"; 32^2 / 96^2 boxes, tied scores and IoUs, classes without GT in the set)."""
+    preds, targets = _random_set(seed)
+    m = MeanAveragePrecision(iou_thresholds=thr, max_detection_thresholds=max_dets)
+    m.update(preds, targets)
+    got, want = m.compute(), coco_loop(preds, targets, thr, max_dets)
+    assert list(got) == ["map", "map_50", "map_75"] + [f"mar_{k}" for k in max_dets]
+    assert want["map"] > 0.05
+    for k in got:
+        assert abs(got[k] - want[k]) <= 1e-12, (k, got[k], want[k])
 
 
 def test_gloo_world_size_2_metric_sync(tmp_path):

@@ -1,7 +1,7 @@
 """CPU checks of the validation metrics: the argument checks of the two confusion-matrix entry points (`mtbt_det_confusion`,
 `mtbt_cls_confusion`), the host arithmetic of ImageClassificationMetrics / DetectionConfusionMatrix on injected counts,
-SegmentationMetrics.compute_map on hand-built pixel counts, and the data-parallel reduction of the new classes and of the loss means
-under gloo."""
+SegmentationMetrics.compute_map on hand-built pixel counts and against the plain-loop COCO restatement, and the data-parallel reduction
+of the new classes and of the loss means under gloo."""
 import ctypes as C
 import os
 import subprocess
@@ -15,6 +15,8 @@ from multitask_bonetumor_yolo_amd import _lib as L
 from multitask_bonetumor_yolo_amd import build as B
 from multitask_bonetumor_yolo_amd.metrics import DetectionConfusionMatrix, ImageClassificationMetrics, SegmentationMetrics
 from multitask_bonetumor_yolo_amd.validate import BatchWeightedMeans
+
+from coco_reference import COCO, coco_loop_iou
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -135,17 +137,37 @@ def test_compute_map_empty_against_empty_is_iou_zero():
     assert _seg(np.zeros((0, 4)), []).compute_map()["map"] == -1.0
 
 
-def test_compute_map_agrees_with_compute_on_random_counts():
+def _seg_on_random_counts():
     rng = np.random.default_rng(11)
     n = 60
     tp, fp, fn = rng.integers(0, 3000, n), rng.integers(0, 1500, n), rng.integers(0, 1500, n)
     tp[:5] = 0
     fp[:3] = 0
     counts = np.stack([tp, fp, fn, 128 * 128 - tp - fp - fn], 1)
-    s = _seg(counts, rng.uniform(0.5, 1.0, n).round(3))
+    return _seg(counts, rng.uniform(0.5, 1.0, n).round(3))
+
+
+def test_compute_map_agrees_with_compute_on_random_counts():
+    s = _seg_on_random_counts()
     full, segm = s.compute(), s.compute_map()
     assert abs(segm["map"] - full["seg_map"]) <= 1e-12 and abs(segm["map_50"] - full["seg_map_50"]) <= 1e-12
     assert 0.0 < segm["map"] < 1.0
+
+
+def test_segm_map_equals_coco_reference_restatement():
+    """compute_map and compute's seg_map / seg_map_50 against the plain-loop restatement (no code shared with `_accumulate`), fed what
+    the metric defines per image: one detection (its mask score, area TP + FP) and one GT (area TP + FN), both class 0, mask IoU
+    TP / (TP + FP + FN) (0 for an empty union)."""
+    s = _seg_on_random_counts()
+    c, score = s.per_image()
+    images = [([float(p)], [0], [tp + fp], [0], [tp + fn], [[tp / (tp + fp + fn) if tp + fp + fn else 0.0]])
+              for (tp, fp, fn, _), p in zip(c.tolist(), score)]
+    want = coco_loop_iou(images, COCO, [1, 10, 100])
+    full, segm = s.compute(), s.compute_map()
+    assert set(segm) == set(want) == KEYS and 0.0 < want["map"] < 1.0
+    for k in KEYS:
+        assert abs(segm[k] - want[k]) <= 1e-12, (k, segm[k], want[k])
+    assert abs(full["seg_map"] - want["map"]) <= 1e-12 and abs(full["seg_map_50"] - want["map_50"]) <= 1e-12
 
 
 def test_batch_weighted_means():
