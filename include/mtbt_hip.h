@@ -126,6 +126,20 @@ int mtbt_conv_colsum_layout(const mtbt_conv_args* a, int64_t* rows, int32_t* pit
  * 16 x 16 halo tile); [3] = 128-byte K-steps (implicit GEMM) or first formulation (direct).  For tests of the tile rules and tools. */
 int mtbt_conv_kernel_choice(const mtbt_conv_args* a, int32_t* choice);
 
+/* n convolutions of ONE shape (1 <= n <= 8) as one launch; result by result what n calls of mtbt_conv2d_nhwc give.
+ * Members agree in N, H, W, C, K, R, S, stride, pad, Ho, Wo, dtype, out_dtype, act, out_mode (MTBT_OUT_NHWC only), tile_hint, policy,
+ * debug and in which of scale / shift / res are NULL; they may differ in every pointer and in every batch / pixel stride (channel slices of
+ * one buffer, fp32 maps of different pitch).  y2, colsum and colsum_ws must be NULL (training forms: single calls).  The output regions of
+ * two members must not overlap (disjoint byte ranges, or channel slices of the same rows: equal pixel / batch stride, the batch stride a
+ * multiple of the pixel stride); no member's output may be another member's input.
+ * ONE kernel for the whole batch: the single call's rules with the workgroup count taken over all members.  The batched kernels exist for
+ * the implicit GEMM with 128-byte K-steps (C * element size a multiple of 128) at 64x64, 128x128, 128x64 and 32x64 tiles, for the row-reuse
+ * direct 3x3 at 64-channel tiles (K >= 96: set policy bit 5) and for the streaming head conv at K <= 32; a batch whose rules give
+ * anything else returns MTBT_EINVAL (a tile_hint selects an instantiated tile).  Alignment rules per member (MTBT_EALIGN). */
+int mtbt_conv2d_nhwc_batch(const mtbt_conv_args* calls, int n, void* stream);
+/* The choice of mtbt_conv2d_nhwc_batch for these members, as mtbt_conv_kernel_choice reports it (nothing is launched); the same errors. */
+int mtbt_conv_batch_kernel_choice(const mtbt_conv_args* calls, int n, int32_t* choice);
+
 /* ---------------------------------------------------------------------------------------------
  * ConvNeXt stem: Conv2d(3,Cout,4,stride 4,bias) on the caller's NCHW fp32 image + LayerNorm2d.
  * Replaces timm `stem_0`/`stem_1` (main_model.py:21-26,34 [timm]).
@@ -146,6 +160,12 @@ int mtbt_stem_conv4x4_ln(const float* x, const float* w, const float* bias, cons
 int mtbt_dwconv_nhwc(const void* x, const void* w, const float* bias, const float* ln_w,
                      const float* ln_b, float ln_eps, const float* scale, const float* shift, int act,
                      void* y, int N, int H, int W, int C, int ksize, int dtype, void* stream);
+/* Depthwise 3 x 3 with a depth multiplier M in {1, 2} (a grouped conv with groups = C and M * C outputs, regrouped): x [N,H,W,C] dense,
+ * y [N,H,W,M*C] dense, w [9][M*C] tap-major, scale / shift [M*C]; output channel j reads input channel j mod C, then scale[j] * v + shift[j]
+ * and the activation.  Channels [m*C, (m+1)*C) are bit-identical to mtbt_dwconv_nhwc (ksize 3, scale / shift form) on the m-th block of
+ * w / scale / shift: two depthwise branches off one tensor as one launch.  C % 128 == 0, M * C <= 768. */
+int mtbt_dwconv3x3_mult_nhwc(const void* x, const void* w, const float* scale, const float* shift, int act, void* y,
+                             int N, int H, int W, int C, int M, int dtype, void* stream);
 
 /* LayerNorm over C of an NHWC dense tensor (timm LayerNorm2d in `stages_i.downsample.0`). */
 int mtbt_layernorm_nhwc(const void* x, const float* w, const float* b, float eps, void* y,

@@ -22,6 +22,12 @@ MTBT_DECL(f16)
 // pw_stream.hip: the heads' output 1x1 convolutions (few input channels, <= 64 outputs, fp32 strided store) without LDS
 bool mtbt_pw_stream_applies(const ConvP& p, int dtype, bool any_width);
 int mtbt_pw_stream(const ConvP& p, int dtype, hipStream_t s);
+bool mtbt_pw_stream_batch_applies(const ConvP& p, int dtype);
+int mtbt_pw_stream_batch(const ConvBatchP& b, int n, int dtype, hipStream_t s);
+// conv_batch_<dtype>.hip: the batched kernels (kind 0 implicit GEMM with 128-byte K-steps, 1 row-reuse direct 3x3)
+int mtbt_conv_batch_dispatch_bf16(const ConvBatchP& b, int n, int kind, int TC, int TP, hipStream_t s);
+int mtbt_conv_batch_dispatch_f16(const ConvBatchP& b, int n, int kind, int TC, int TP, hipStream_t s);
+int mtbt_conv_batch_dispatch_f32(const ConvBatchP& b, int n, int kind, int TC, int TP, hipStream_t s);
 
 // Tile heuristics, from the sweep in tools/conv_tune.py on the shapes of the 640x640 batch-16 forward
 // (numbers in DESIGN.md):
@@ -120,7 +126,10 @@ static int colsum_finish(const mtbt_conv_args* a, const ConvP& p, long rows, hip
 }
 
 // `layout` non-null: validate and choose the kernel as a launch would, report the column-sum partial layout, launch nothing.
-static int conv_impl(const mtbt_conv_args* a, void* stream, int64_t* layout /* [6]: rows, pitch, kernel kind, TC, TP, 128-byte K-steps */) {
+// `nmem` > 0 (with `layout`): the call is a member of a batch of nmem equal shapes -- the tile rules count the workgroups of the whole
+// batch, and `pout` receives the member's kernel parameters.
+static int conv_impl(const mtbt_conv_args* a, void* stream, int64_t* layout /* [6]: rows, pitch, kernel kind, TC, TP, 128-byte K-steps */,
+                     int nmem = 0, ConvP* pout = nullptr) {
   if (!a || !a->x || !a->w || !a->y) return MTBT_EINVAL;
   if (a->dtype != MTBT_F32 && a->dtype != MTBT_BF16 && a->dtype != MTBT_F16) return MTBT_EINVAL;
   if (a->out_dtype != a->dtype && a->out_dtype != MTBT_F32) return MTBT_EINVAL;
@@ -174,11 +183,13 @@ static int conv_impl(const mtbt_conv_args* a, void* stream, int64_t* layout /* [
   if (a->out_mode == MTBT_OUT_CONVT2X2) vec = vec && (kq % 8 == 0);
   if (a->res) vec = vec && (a->res_pixel_stride % epc == 0) && (a->res_batch_stride % epc == 0) && aligned16(a->res);
   p.vec_ok = vec ? 1 : 0;
+  if (pout) *pout = p;
 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // narrow 1x1 convolutions into an fp32 map (the heads' output convs): streaming kernel, same arithmetic (a tile hint keeps the call on
   // the implicit-GEMM kernel: tests, A/B)
-  if (!a->tile_hint && (pol & 64) == 0 && (long)a->K * a->C * es < 0x7fff0000L && mtbt_pw_stream_applies(p, a->dtype, (pol & 128) != 0)) {
+  if (!a->tile_hint && (pol & 64) == 0 && (long)a->K * a->C * es < 0x7fff0000L &&
+      (nmem ? mtbt_pw_stream_batch_applies(p, a->dtype) : mtbt_pw_stream_applies(p, a->dtype, (pol & 128) != 0))) {
     if (layout) { layout[0] = layout[1] = 0; layout[2] = 2; layout[3] = a->K; layout[4] = 128; layout[5] = 0; return MTBT_OK; }   // (no column sums on this path)
     return mtbt_pw_stream(p, a->dtype, s);
   }
@@ -204,7 +215,7 @@ static int conv_impl(const mtbt_conv_args* a, void* stream, int64_t* layout /* [
   int TC, TP, nbuf = 0;
   if (a->tile_hint) { nbuf = (a->tile_hint >> 28) & 7; TC = (a->tile_hint >> 16) & 0x1ff; TP = a->tile_hint & 0xffff; }
   int narrow = (a->tile_hint >> 27) & 1;  // hint bit 27: force 64-byte K-steps
-  if (!a->tile_hint || !TC || !TP) pick_tile(pol, a->K, p.M, a->R * a->S, a->C, es, &TC, &TP, &narrow, want_cs, a->act);
+  if (!a->tile_hint || !TC || !TP) pick_tile(pol, a->K, nmem ? (long)p.M * nmem : (long)p.M, a->R * a->S, a->C, es, &TC, &TP, &narrow, want_cs, a->act);
   if (want_cs && TC == 96) return MTBT_EINVAL;   // (a wave's 48 / 96 channels are not a power-of-two number of 8-channel pieces)
   const int wide = (a->C % (128 / es) == 0 && !narrow) ? 1 : 0;
   if (nbuf < 2 || nbuf > 4) nbuf = pick_nbuf(TC, TP, wide ? 128 : 64, a->R * a->S * a->C / ((wide ? 128 : 64) / es));
@@ -243,4 +254,71 @@ extern "C" int mtbt_conv_kernel_choice(const mtbt_conv_args* a, int32_t* choice)
   if (rc != MTBT_OK) return rc;
   for (int i = 0; i < 4; ++i) choice[i] = (int32_t)lay[2 + i];
   return MTBT_OK;
+}
+
+// ---- batched form: n convolutions of one shape in one launch ---------------------------------------------------------------------------
+// Validation and the ONE kernel choice of the batch: every member passes the single call's checks (conv_impl in query mode, with the
+// batch's total workgroup count in the tile rules), the members agree in everything that selects or shapes the kernel, and the choice is
+// one the batched kernels are instantiated for: implicit GEMM 64x64 / 128x128 / 128x64 / 32x64 with 128-byte K-steps, the row-reuse direct
+// 3x3 at 64 channels (policy bit 5 asks for it from 96 output channels on), the streaming head conv up to 32 output channels.
+static bool batch_same_shape(const mtbt_conv_args& a, const mtbt_conv_args& b) {
+  return a.N == b.N && a.H == b.H && a.W == b.W && a.C == b.C && a.K == b.K && a.R == b.R && a.S == b.S && a.stride == b.stride && a.pad == b.pad &&
+         a.Ho == b.Ho && a.Wo == b.Wo && a.dtype == b.dtype && a.out_dtype == b.out_dtype && a.act == b.act && a.out_mode == b.out_mode &&
+         a.tile_hint == b.tile_hint && a.policy == b.policy && a.debug == b.debug && !a.scale == !b.scale && !a.shift == !b.shift && !a.res == !b.res;
+}
+
+// Output regions of two members (equal shapes): disjoint byte ranges, or channel slices of the same rows (equal pitch and batch stride, the
+// batch stride a whole number of rows) that do not meet.
+static bool batch_outputs_overlap(const mtbt_conv_args& a, const mtbt_conv_args& b) {
+  const long oes = a.out_dtype == MTBT_F32 ? 4 : 2;
+  const long ext_a = ((long)(a.N - 1) * a.y_batch_stride + ((long)a.Ho * a.Wo - 1) * a.y_pixel_stride + a.K) * oes;
+  const long ext_b = ((long)(b.N - 1) * b.y_batch_stride + ((long)b.Ho * b.Wo - 1) * b.y_pixel_stride + b.K) * oes;
+  const char* ya = reinterpret_cast<const char*>(a.y);
+  const char* yb = reinterpret_cast<const char*>(b.y);
+  if (ya + ext_a <= yb || yb + ext_b <= ya) return false;
+  const long ld = a.y_pixel_stride;
+  if (ld != b.y_pixel_stride || a.y_batch_stride != b.y_batch_stride || ld <= 0 || a.y_batch_stride % ld != 0) return true;
+  const long db = yb - ya;
+  if (db % oes != 0) return true;
+  const long r = ((db / oes) % ld + ld) % ld;      // member b's first channel inside member a's rows
+  return !(r >= a.K && r + a.K <= ld);
+}
+
+static int conv_batch_impl(const mtbt_conv_args* calls, int n, void* stream, int32_t* choice) {
+  if (!calls || n < 1 || n > MTBT_CONV_BATCH_MAX) return MTBT_EINVAL;
+  ConvBatchP b;
+  int64_t lay0[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < n; ++i) {
+    const mtbt_conv_args& a = calls[i];
+    if (a.y2 || a.colsum || a.colsum_ws || a.out_mode != MTBT_OUT_NHWC) return MTBT_EINVAL;     // training forms and the ConvT scatter: single calls only
+    if (i && !batch_same_shape(calls[0], a)) return MTBT_EINVAL;
+    int64_t lay[6] = {0, 0, 0, 0, 0, 0};
+    ConvP p;
+    if (const int rc = conv_impl(&a, nullptr, lay, n, &p)) return rc;
+    if (i == 0) { b.p = p; for (int k = 0; k < 6; ++k) lay0[k] = lay[k]; }
+    else if (lay[2] != lay0[2] || lay[3] != lay0[3] || lay[4] != lay0[4] || lay[5] != lay0[5]) return MTBT_EINVAL;
+    ConvMember& m = b.m[i];
+    m.x = p.x; m.w = p.w; m.y = p.y; m.scale = p.scale; m.shift = p.shift; m.res = p.res;
+    m.xbs = p.xbs; m.ybs = p.ybs; m.rbs = p.rbs; m.ldx = p.ldx; m.ldy = p.ldy; m.ldr = p.ldr;
+    m.vec_ok = p.vec_ok; m.y_linear = p.y_linear; m.pad_ = 0;
+    for (int j = 0; j < i; ++j)
+      if (batch_outputs_overlap(calls[j], a)) return MTBT_EINVAL;
+  }
+  for (int i = n; i < MTBT_CONV_BATCH_MAX; ++i) b.m[i] = b.m[0];
+  const int kind = (int)lay0[2], TC = (int)lay0[3], TP = (int)lay0[4], flag = (int)lay0[5];
+  if (kind == 0 && !(flag == 1 && ((TC == 128 && (TP == 128 || TP == 64)) || ((TC == 64 || TC == 32) && TP == 64)))) return MTBT_EINVAL;
+  if (kind == 1 && !(TC == 64 && flag == 0)) return MTBT_EINVAL;
+  if (choice) { choice[0] = kind; choice[1] = TC; choice[2] = TP; choice[3] = flag; return MTBT_OK; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int dt = calls[0].dtype;
+  if (kind == 2) return mtbt_pw_stream_batch(b, n, dt, s);
+  return dt == MTBT_F32 ? mtbt_conv_batch_dispatch_f32(b, n, kind, TC, TP, s)
+                        : (dt == MTBT_F16 ? mtbt_conv_batch_dispatch_f16(b, n, kind, TC, TP, s) : mtbt_conv_batch_dispatch_bf16(b, n, kind, TC, TP, s));
+}
+
+extern "C" int mtbt_conv2d_nhwc_batch(const mtbt_conv_args* calls, int n, void* stream) { return conv_batch_impl(calls, n, stream, nullptr); }
+
+extern "C" int mtbt_conv_batch_kernel_choice(const mtbt_conv_args* calls, int n, int32_t* choice) {
+  if (!choice) return MTBT_EINVAL;
+  return conv_batch_impl(calls, n, nullptr, choice);
 }

@@ -32,3 +32,36 @@ struct ConvP {
 #else
 #define MTBT_ABL(p, bit) 0
 #endif
+
+// Batched launch (mtbt_conv2d_nhwc_batch): n convolutions of ONE shape as one grid.  `p` carries everything the members share (and member
+// 0's pointers); the table holds what may differ.  The member index is a grid dimension (blockIdx.y), so it is wave-uniform: the selected
+// row is read with scalar loads from the kernel-argument segment and the kernel bodies run unchanged on the patched ConvP.
+#define MTBT_CONV_BATCH_MAX 8
+struct ConvMember {
+  const void* x;
+  const void* w;
+  void* y;
+  const float* scale;
+  const float* shift;
+  const void* res;
+  long xbs, ybs, rbs;
+  int ldx, ldy, ldr;
+  int vec_ok, y_linear, pad_;
+};
+
+struct ConvBatchP {
+  ConvP p;
+  ConvMember m[MTBT_CONV_BATCH_MAX];
+};
+
+#if defined(__HIPCC__)
+__device__ __forceinline__ ConvP conv_member(const ConvBatchP& b, int i) {
+  ConvP p = b.p;
+  const ConvMember& m = b.m[i];
+  p.x = m.x; p.w = m.w; p.y = m.y; p.scale = m.scale; p.shift = m.shift; p.res = m.res;
+  p.xbs = m.xbs; p.ybs = m.ybs; p.rbs = m.rbs;
+  p.ldx = m.ldx; p.ldy = m.ldy; p.ldr = m.ldr;
+  p.vec_ok = m.vec_ok; p.y_linear = m.y_linear;
+  return p;
+}
+#endif

@@ -11,3 +11,7 @@ struct DwArgs {
 int mtbt_dw_run_bf16(const DwArgs& a, hipStream_t s);
 int mtbt_dw_run_f16(const DwArgs& a, hipStream_t s);
 int mtbt_dw_run_f32(const DwArgs& a, hipStream_t s);
+// depth-multiplier form (3x3, scale / shift): a.C = the OUTPUT channels M * Cx, Cx = the input's
+int mtbt_dw_run_mult_bf16(const DwArgs& a, int Cx, hipStream_t s);
+int mtbt_dw_run_mult_f16(const DwArgs& a, int Cx, hipStream_t s);
+int mtbt_dw_run_mult_f32(const DwArgs& a, int Cx, hipStream_t s);

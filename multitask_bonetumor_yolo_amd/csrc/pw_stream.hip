@@ -16,12 +16,12 @@
 namespace {
 
 template <typename T, int NST, int FC>
-__global__ __launch_bounds__(256) void pw_stream_kernel(const ConvP p) {
+__device__ __forceinline__ void pw_stream_body(const ConvP& p, const int bid) {
   constexpr int FP = 2, C = NST * 32;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lr = lane & 15, lq = lane >> 4;
-  const long pix0 = ((long)blockIdx.x * 4 + wave) * (FP * 16);
+  const long pix0 = ((long)bid * 4 + wave) * (FP * 16);
   if (pix0 >= p.M) return;
   const int HW = p.H * p.W;
   const T* const xb = reinterpret_cast<const T*>(p.x);
@@ -89,6 +89,41 @@ __global__ __launch_bounds__(256) void pw_stream_kernel(const ConvP p) {
   }
 }
 
+template <typename T, int NST, int FC>
+__global__ __launch_bounds__(256) void pw_stream_kernel(const ConvP p) {
+  pw_stream_body<T, NST, FC>(p, (int)blockIdx.x);
+}
+
+// Batched form (conv_params.h): the member is blockIdx.y.  Only the widths the kernel takes by default (<= 32 outputs: the class / coefficient convs).
+template <typename T, int NST, int FC>
+__global__ __launch_bounds__(256) void pw_stream_batch_kernel(const ConvBatchP b) {
+  const ConvP p = conv_member(b, (int)blockIdx.y);
+  pw_stream_body<T, NST, FC>(p, (int)blockIdx.x);
+}
+
+template <typename T, int NST>
+int launch_batch_nst(const ConvBatchP& b, int n, hipStream_t s) {
+  const long blocks = ((long)b.p.M + 127) / 128;
+  if (blocks <= 0 || blocks > 0x7fffffffL || n < 1 || n > MTBT_CONV_BATCH_MAX) return MTBT_EINVAL;
+  const int fc = (b.p.K + 15) / 16;
+  if (fc == 1) hipLaunchKernelGGL((pw_stream_batch_kernel<T, NST, 1>), dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, s, b);
+  else if (fc == 2) hipLaunchKernelGGL((pw_stream_batch_kernel<T, NST, 2>), dim3((unsigned)blocks, (unsigned)n), dim3(256), 0, s, b);
+  else return MTBT_EINVAL;
+  MTBT_LAUNCH_CHECK();
+  return MTBT_OK;
+}
+
+template <typename T>
+int launch_batch_t(const ConvBatchP& b, int n, hipStream_t s) {
+  switch (b.p.C / 32) {
+    case 1: return launch_batch_nst<T, 1>(b, n, s);
+    case 2: return launch_batch_nst<T, 2>(b, n, s);
+    case 4: return launch_batch_nst<T, 4>(b, n, s);
+    case 8: return launch_batch_nst<T, 8>(b, n, s);
+    default: return MTBT_EINVAL;
+  }
+}
+
 template <typename T, int NST>
 int launch_nst(const ConvP& p, hipStream_t s) {
   const long blocks = ((long)p.M + 127) / 128;
@@ -129,6 +164,15 @@ bool mtbt_pw_stream_applies(const ConvP& p, int dtype, bool any_width) {
   const bool shape = (p.C == 32 || p.C == 64 || p.C == 128 || p.C == 256) && p.K <= (any_width ? 64 : 32);
   return (dtype == MTBT_BF16 || dtype == MTBT_F16) && p.R == 1 && p.S == 1 && p.stride == 1 && p.pad == 0 && shape &&
          p.out_f32 && p.out_mode == MTBT_OUT_NHWC && p.act == MTBT_ACT_NONE && !p.scale && !p.res && !p.y2 && !p.cs_part && !p.debug;
+}
+
+// The shapes the batched form instantiates: the streaming kernel's default rule (at most 32 outputs; policy bit 7 widens single calls only).
+bool mtbt_pw_stream_batch_applies(const ConvP& p, int dtype) {
+  return mtbt_pw_stream_applies(p, dtype, false);
+}
+
+int mtbt_pw_stream_batch(const ConvBatchP& b, int n, int dtype, hipStream_t s) {
+  return dtype == MTBT_F16 ? launch_batch_t<f16_t>(b, n, s) : launch_batch_t<bf16_t>(b, n, s);
 }
 
 int mtbt_pw_stream(const ConvP& p, int dtype, hipStream_t s) {

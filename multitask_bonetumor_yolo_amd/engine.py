@@ -412,8 +412,51 @@ class Plan:
 
     # ---- op builders ----
     def conv(self, x: Act, w: torch.Tensor, y: Act, *, R=1, S=1, stride=1, pad=0, scale=None, shift=None,
-             act=L.ACT_NONE, res: Optional[Act] = None, out_mode=L.OUT_NHWC, name="conv", tile_hint=0):
-        """w: packed [K, R*S*C] in x's dtype.  y: output view (dtype may be f32)."""
+             act=L.ACT_NONE, res: Optional[Act] = None, out_mode=L.OUT_NHWC, name="conv", tile_hint=0, policy=0):
+        """w: packed [K, R*S*C] in x's dtype.  y: output view (dtype may be f32).  `policy`: kernel-selection bits of this call, ORed onto
+        the plan's (include/mtbt_hip.h, mtbt_conv_args.policy; e.g. 32 = 64-channel tiles on the direct 3x3 kernel)."""
+        a, flops, byts = self._conv_args(x, w, y, R, S, stride, pad, scale, shift, act, res, out_mode, tile_hint, policy)
+        self.launches.append(Launch(self.lib.mtbt_conv2d_nhwc, (C.byref(a),), name, (a, x.buf, w, y.buf, scale, shift, res), flops, byts))
+        self._io([x, res, w, scale, shift], [y])     # (weights / affine vectors too: a training plan rewrites them at its head)
+        return a
+
+    def call_policy(self, bits: int) -> int:
+        """The plan's conv policy with `bits` set on top (the default policy is bits 0-2)."""
+        if not bits:
+            return self.conv_policy
+        return 0x100 | ((self.conv_policy & 0xff) if self.conv_policy else 7) | (bits & 0xff)
+
+    def conv_batch(self, members, *, R=1, S=1, stride=1, pad=0, act=L.ACT_NONE, name="conv_batch", tile_hint=0, policy=0):
+        """n convolutions of one shape as ONE launch (mtbt_conv2d_nhwc_batch).  members: (x, w, y, shift) each -- input view, packed weights
+        [K, R*S*C], output view, fp32 shift or None (all or none).  The launch reads the union of the members' inputs / weights / shifts and
+        writes the members' outputs, which must not overlap; FLOPs and bytes are the members' sums."""
+        members = [tuple(m) for m in members]
+        if not 1 <= len(members) <= 8:
+            raise ValueError(f"{name}: a batch has 1 to 8 members, got {len(members)}")
+        arr = (L.ConvArgs * len(members))()
+        flops = byts = 0.0
+        keep, reads, writes = [arr], [], []
+        for i, (x, w, y, shift) in enumerate(members):
+            a, f, b = self._conv_args(x, w, y, R, S, stride, pad, None, shift, act, None, L.OUT_NHWC, tile_hint, policy)
+            C.memmove(C.byref(arr, i * C.sizeof(L.ConvArgs)), C.byref(a), C.sizeof(L.ConvArgs))
+            flops, byts = flops + f, byts + b
+            keep += [x.buf, w, y.buf, shift]
+            reads += [x, w, shift]
+            writes.append(y)
+        a0 = arr[0]
+        for a in arr:
+            if any(getattr(a, k) != getattr(a0, k) for k in ("N", "H", "W", "C", "K", "dtype", "out_dtype")) or bool(a.shift) != bool(a0.shift):
+                raise ValueError(f"{name}: the members of a batch must have one shape")
+        regions = [_region(y) for y in writes]
+        for i in range(len(regions)):
+            for j in range(i):
+                if _overlap(regions[i], regions[j]):
+                    raise ValueError(f"{name}: the outputs of members {j} and {i} overlap")
+        self.launches.append(Launch(self.lib.mtbt_conv2d_nhwc_batch, (C.cast(arr, C.c_void_p), len(members)), name, tuple(keep), flops, byts))
+        self._io(reads, writes)
+        return arr
+
+    def _conv_args(self, x, w, y, R, S, stride, pad, scale, shift, act, res, out_mode, tile_hint, policy):
         K = w.shape[0]
         assert w.shape[1] == R * S * x.C, (w.shape, R, S, x.C)
         Ho = (x.H + 2 * pad - R) // stride + 1
@@ -431,12 +474,10 @@ class Plan:
         a.N, a.H, a.W, a.C, a.K, a.R, a.S = x.N, x.H, x.W, x.C, K, R, S
         a.stride, a.pad, a.Ho, a.Wo = stride, pad, Ho, Wo
         a.dtype, a.out_dtype, a.act, a.out_mode, a.tile_hint = x.code, y.code, act, out_mode, tile_hint
-        a.policy, a.debug = self.conv_policy, self.conv_debug
+        a.policy, a.debug = self.call_policy(policy), self.conv_debug
         flops = 2.0 * x.N * Ho * Wo * K * R * S * x.C
         byts = (x.N * x.H * x.W * x.C + K * R * S * x.C) * ESIZE[x.code] + x.N * Ho * Wo * K * ESIZE[y.code]
-        self.launches.append(Launch(self.lib.mtbt_conv2d_nhwc, (C.byref(a),), name, (a, x.buf, w, y.buf, scale, shift, res), flops, byts))
-        self._io([x, res, w, scale, shift], [y])     # (weights / affine vectors too: a training plan rewrites them at its head)
-        return a
+        return a, flops, byts
 
     def stem(self, x_nchw: torch.Tensor, w, b, lnw, lnb, eps, y: Act, name="stem"):
         N, _, H, W = x_nchw.shape
@@ -449,8 +490,19 @@ class Plan:
 
     def dwconv(self, x: Act, w, y: Act, ksize, *, bias=None, lnw=None, lnb=None, eps=0.0, scale=None, shift=None,
                act=L.ACT_NONE, name="dwconv"):
-        assert x.dense and y.dense and x.C == y.C
+        assert x.dense and y.dense
         p = lambda t: t.data_ptr() if t is not None else None
+        if y.C != x.C:
+            # depth multiplier (mtbt_dwconv3x3_mult_nhwc): y.C = M * x.C, output channel j reads input channel j mod x.C -- two depthwise
+            # branches off one tensor as one launch; w [9][M*C], scale / shift [M*C]
+            M = y.C // x.C
+            assert ksize == 3 and y.C == M * x.C and bias is None and lnw is None and scale is not None and shift is not None
+            args = (x.ptr, w.data_ptr(), p(scale), p(shift), act, y.ptr, x.N, x.H, x.W, x.C, M, x.code)
+            n = x.N * x.H * x.W
+            self.launches.append(Launch(self.lib.mtbt_dwconv3x3_mult_nhwc, args, name, (x.buf, w, scale, shift, y.buf),
+                                        2.0 * n * y.C * 9, 1.0 * n * (x.C + y.C) * ESIZE[x.code]))
+            self._io([x, w], [y])
+            return
         args = (x.ptr, w.data_ptr(), p(bias), p(lnw), p(lnb), C.c_float(eps), p(scale), p(shift), act, y.ptr,
                 x.N, x.H, x.W, x.C, ksize, x.code)
         n = x.N * x.H * x.W * x.C

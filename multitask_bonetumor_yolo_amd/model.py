@@ -10,6 +10,7 @@ weights version) into a launch plan (engine.Plan) of C-ABI calls and replays it.
 
 There is no CPU path: tensors must live on an MI355X and the HIP library must be built.
 """
+import ctypes as C
 import math
 import os
 from typing import List
@@ -245,13 +246,40 @@ def compose_upconv(wt: torch.Tensor, bt: torch.Tensor, w3: torch.Tensor, scale: 
     return w.reshape(4 * K, 4 * Ci).float(), shift9.float()
 
 
-PLAN_OPTION_DEFAULTS = {"NODE_FUSED": "0", "ADAPTOR_EARLY": "0", "HEADS_EARLY": "0", "SEG_GATE": "0", "LANES": None, "LANE_WIDE_US": None}
+def pack_convblocks(mods):
+    """Eval-mode conv + BN blocks that read ONE tensor, as one convolution: weights [sum K, R*S*C] with each block's BN scale folded into its
+    rows, shifts concatenated (fp32).  Slice j equals what `_Lowering.convblock` packs for block j alone."""
+    ws, shs = [], []
+    for m in mods:
+        scale, shift = _bn_fold(m.bn, m.conv.bias)
+        ws.append(_krsc(m.conv.weight).float() * scale[:, None])
+        shs.append(shift)
+    return torch.cat(ws, 0), torch.cat(shs, 0)
+
+
+def pack_dwblocks(mods):
+    """Eval-mode depthwise 3x3 + BN blocks side by side: taps [9][sum C] (tap-major), scale and shift [sum C] (fp32).  Blocks that read
+    different tensors concatenate into the plain depthwise form over the concatenated input; blocks that read the SAME tensor are the
+    depth-multiplier form (`mtbt_dwconv3x3_mult_nhwc`)."""
+    ws, scs, shs = [], [], []
+    for m in mods:
+        scale, shift = _bn_fold(m.bn)
+        ws.append(m.conv.weight.detach().reshape(m.conv.out_channels, 9).t())
+        scs.append(scale)
+        shs.append(shift)
+    return torch.cat(ws, 1).contiguous(), torch.cat(scs, 0), torch.cat(shs, 0)
+
+
+PLAN_OPTION_DEFAULTS = {"NODE_FUSED": "0", "ADAPTOR_EARLY": "0", "HEADS_EARLY": "0", "SEG_GATE": "0", "HEADS_MERGED": "0", "LANES": None, "LANE_WIDE_US": None}
 
 
 def plan_option(model, name: str):
     """A scheduling / lowering knob of the inference plan: `model.plan_options[name]` (set by `GraphedInference(autotune=True)`, which times a
     few combinations and keeps the fastest) > the environment variable MTBT_<name> (development A/B) > the default.  Every combination
-    computes the same values up to the fused kernels' accumulation order; only the launch schedule differs."""
+    computes the same values up to the fused kernels' accumulation order; only the launch schedule differs.
+    HEADS_MERGED=1 lowers the eval-mode Detect / Segment branches of a pyramid level as shared launches (`_Lowering.heads_level_merged`:
+    19 -> 9 per level); Segment's box / class chain then has no launches of its own, so SEG_GATE is ignored with it, and HEADS_EARLY marks the
+    shared launches `side` as it does the separate ones.  Not an autotune knob: off unless asked for."""
     v = model.__dict__.get("plan_options", {}).get(name)
     if v is None:
         v = os.environ.get("MTBT_" + name, PLAN_OPTION_DEFAULTS[name])
@@ -604,6 +632,115 @@ class _Lowering:
         self.p.release(t2)
         return full
 
+    def heads_mergeable(self, i, heads, f: Act) -> bool:
+        """Whether level i of these heads (Detect and / or Segment, the Segment last) can share launches: every BatchNorm of the level's
+        branches folds (eval mode) and the heads agree in their widths."""
+        seg = heads[-1][0]
+        if not isinstance(seg, Segment) or f.C % 128 or not f.dense:
+            return False
+        mods = [m for h, _ in heads for br in (h.cv2[i], h.cv3[i]) for m in br.modules()] + list(seg.cv4[i].modules())
+        if any(m.training for m in mods if isinstance(m, nn.BatchNorm2d)):
+            return False
+        c2 = {h.cv2[i][0].conv.out_channels for h, _ in heads} | {seg.cv4[i][0].conv.out_channels}
+        c3 = {h.cv3[i][0][1].conv.out_channels for h, _ in heads}
+        same = len(c2) == 1 and len(c3) == 1 and len({(h.nc, h.reg_max, h.no) for h, _ in heads}) == 1
+        return same and c3 == {f.C} and all(h.cv3[i][1][0].conv.groups == f.C for h, _ in heads)
+
+    def _batch(self, members, name, **kw):
+        """One batched launch, or -- where the library has no batched kernel for the shape -- the members as launches of their own."""
+        names = name.split(" + ")
+        if len(members) > 1:
+            first = len(self.p.launches)
+            arr = self.p.conv_batch(members, name=name, **kw)
+            choice = (C.c_int32 * 4)()
+            if self.p.lib.mtbt_conv_batch_kernel_choice(C.cast(arr, C.c_void_p), len(members), choice) == 0:
+                return
+            del self.p.launches[first:]
+        for (x, w, y, shift), nm in zip(members, names):
+            self.p.conv(x, w, y, shift=shift, name=nm, **{k: v for k, v in kw.items()})
+
+    def heads_level_merged(self, i, f: Act, heads, maps, mc: torch.Tensor, off: int, A: int):
+        """Level i of Detect + Segment (or of Segment alone) with the branches that read one tensor sharing launches (plan option
+        HEADS_MERGED): the first box / mask-coefficient convs as ONE 3x3 conv with concatenated output channels, the class chains' depthwise
+        convs as one depth-multiplier launch and one concatenated launch, every later stage as a batch of equal convolutions over channel
+        slices.  Every output element is computed by the arithmetic of the separate lowering.  heads: [(module, tag)], the Segment last;
+        maps: their [N,h,w,no] fp32 output maps (pitch rounded up to 4 floats, as det_level makes them)."""
+        seg = heads[-1][0]
+        nh, c2, c3 = len(heads), seg.cv4[i][0].conv.out_channels, f.C
+        N, H, W = f.N, f.H, f.W
+
+        def box_chains():
+            # (1) cv2[0] of every head + cv4[0]: one conv, K = (nh + 1) * c2.  Direct 3x3 kernel: whole 64-channel tiles when K is no multiple of 128
+            firsts = [h.cv2[i][0] for h, _ in heads] + [seg.cv4[i][0]]
+            tags = [f"{t}.cv2.{i}" for _, t in heads] + [f"segment.cv4.{i}"]
+            w1, sh1 = pack_convblocks(firsts)
+            t1 = self.p.new(N, H, W, w1.shape[0], self.code)
+            self.p.conv(f, self.W(w1), t1, R=3, S=3, pad=1, shift=self.F(sh1), act=L.ACT_SILU, name=" + ".join(f"{t}.0" for t in tags),
+                        policy=32 if w1.shape[0] % 128 else 0)
+            # (3) the second 3x3 convs: a batch over the channel slices of (1)
+            t2 = self.p.new(N, H, W, w1.shape[0], self.code)
+            seconds = [h.cv2[i][1] for h, _ in heads] + [seg.cv4[i][1]]
+            members = []
+            for j, m in enumerate(seconds):
+                wj, sj = pack_convblocks([m])
+                members.append((t1.slice(j * c2, c2), self.W(wj), t2.slice(j * c2, c2), self.F(sj)))
+            self._batch(members, " + ".join(f"{t}.1" for t in tags), R=3, S=3, pad=1, act=L.ACT_SILU)
+            self.p.release(t1)
+            # (7) box outputs into the fp32 maps, (9) mask coefficients
+            outs = [h.cv2[i][2] for h, _ in heads]
+            self._batch([(t2.slice(j * c2, c2), self.W(_krsc(cv.weight)), maps[j].slice(0, 4 * h.reg_max), self.F(cv.bias))
+                         for j, ((h, _), cv) in enumerate(zip(heads, outs))], " + ".join(f"{t}.cv2.{i}.2" for _, t in heads))
+            lvl = Act(mc, off * seg.nm, N, H, W, seg.nm, seg.nm, A * seg.nm)
+            self.conv_plain(t2.slice(nh * c2, c2), seg.cv4[i][2], lvl, f"segment.cv4.{i}.2")
+            self.p.release(t2)
+
+        # the class chains (two depthwise + two 1x1 + output conv) are the longer ones: first, as in det_level.  (2) depthwise x nh off f,
+        # (4) 1x1, (5) depthwise over the concatenation, (6) 1x1, (8) class outputs
+        if nh == 1:
+            h, t = heads[0]
+            s = h.cv3[i]
+            d1 = self.dwblock(f, s[0][0], f"{t}.cv3.{i}.0.0")
+            u1 = self.convblock(d1, s[0][1], None, f"{t}.cv3.{i}.0.1")
+            self.p.release(d1)
+            d2 = self.dwblock(u1, s[1][0], f"{t}.cv3.{i}.1.0")
+            self.p.release(u1)
+            u2 = self.convblock(d2, s[1][1], None, f"{t}.cv3.{i}.1.1")
+            self.p.release(d2)
+            self.conv_plain(u2, s[2], maps[0].slice(4 * h.reg_max, h.nc), f"{t}.cv3.{i}.2")
+            self.p.release(u2)
+            return box_chains()
+        ctags = [f"{t}.cv3.{i}" for _, t in heads]
+        wd, scd, shd = pack_dwblocks([h.cv3[i][0][0] for h, _ in heads])
+        d1 = self.p.new(N, H, W, nh * c3, self.code)
+        self.p.dwconv(f, self.W(wd), d1, 3, scale=self.F(scd), shift=self.F(shd), act=L.ACT_SILU, name=" + ".join(f"{t}.0.0" for t in ctags))
+        u1 = self.p.new(N, H, W, nh * c3, self.code)
+
+        def pointwise(src, dst, k):
+            members = []
+            for j, (h, _) in enumerate(heads):
+                wj, sj = pack_convblocks([h.cv3[i][k][1]])
+                members.append((src.slice(j * c3, c3), self.W(wj), dst.slice(j * c3, c3), self.F(sj)))
+            self._batch(members, " + ".join(f"{t}.{k}.1" for t in ctags), act=L.ACT_SILU)
+        pointwise(d1, u1, 0)
+        self.p.release(d1)
+        wd, scd, shd = pack_dwblocks([h.cv3[i][1][0] for h, _ in heads])
+        d2 = self.p.new(N, H, W, nh * c3, self.code)
+        self.p.dwconv(u1, self.W(wd), d2, 3, scale=self.F(scd), shift=self.F(shd), act=L.ACT_SILU, name=" + ".join(f"{t}.1.0" for t in ctags))
+        self.p.release(u1)
+        u2 = self.p.new(N, H, W, nh * c3, self.code)
+        pointwise(d2, u2, 1)
+        self.p.release(d2)
+        self._batch([(u2.slice(j * c3, c3), self.W(_krsc(h.cv3[i][2].weight)), maps[j].slice(4 * h.reg_max, h.nc), self.F(h.cv3[i][2].bias))
+                     for j, (h, _) in enumerate(heads)], " + ".join(f"{t}.2" for t in ctags))
+        self.p.release(u2)
+        box_chains()
+
+    def head_map(self, f: Act, head: Detect) -> Act:
+        """The [N,h,w,no] fp32 output map of one level (pixel pitch rounded up to 4 floats: see det_level)."""
+        ld = (head.no + 3) // 4 * 4
+        buf = torch.empty((f.N, f.H, f.W, ld), dtype=torch.float32, device=self.x.device)
+        return Act(buf, 0, f.N, f.H, f.W, head.no, ld, f.H * f.W * ld)
+
     def det_branch(self, feats, head: Detect, tag, gate=None):
         return [self.det_level(i, f, head, tag, gate[i] if gate is not None else None) for i, f in enumerate(feats)]
 
@@ -768,6 +905,7 @@ class _Base(nn.Module):
             state = {}
             gate_mode = int(plan_option(self, "SEG_GATE"))
             early = plan_option(self, "HEADS_EARLY") == "1" and not isinstance(self, ConvNeXtBiFPNYOLOv0)
+            merged = plan_option(self, "HEADS_MERGED") == "1" and not isinstance(self, ConvNeXtBiFPNYOLOv0)
 
             def heads_of_level(i, f, shapes):
                 """Everything that hangs off pyramid level i, in the order of what the post-process waits for: the prototype chain (the
@@ -781,11 +919,19 @@ class _Base(nn.Module):
                     state["mc"], state["offs"], state["A"] = lo.mc_buffer(shapes, self.segment)
                 if i == 0:
                     state["protos"] = lo.proto(f, self.segment)
-                if has_det:
-                    det_maps[i] = lo.det_level(i, f, self.detect, "detect")
-                lo.cv4_level(i, f, self.segment, state["mc"], state["offs"][i], state["A"])
-                gate = [det_maps[i]] if (has_det and gate_mode >= 1) else None
-                seg_maps[i] = lo.det_level(i, f, self.segment, "segment", gate)
+                heads = ([(self.detect, "detect")] if has_det else []) + [(self.segment, "segment")]
+                if merged and lo.heads_mergeable(i, heads, f):
+                    maps = [lo.head_map(f, h) for h, _ in heads]
+                    lo.heads_level_merged(i, f, heads, maps, state["mc"], state["offs"][i], state["A"])
+                    if has_det:
+                        det_maps[i] = maps[0]
+                    seg_maps[i] = maps[-1]
+                else:
+                    if has_det:
+                        det_maps[i] = lo.det_level(i, f, self.detect, "detect")
+                    lo.cv4_level(i, f, self.segment, state["mc"], state["offs"][i], state["A"])
+                    gate = [det_maps[i]] if (has_det and gate_mode >= 1) else None
+                    seg_maps[i] = lo.det_level(i, f, self.segment, "segment", gate)
                 if early:                         # lowered in the middle of the neck: branch work, off the neck's main chain
                     for l in lo.p.launches[first:]:
                         l.side = True
