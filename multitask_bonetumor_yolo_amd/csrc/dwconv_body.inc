@@ -91,7 +91,9 @@
       const int iy = ty_ * TH + row - PAD;
       const bool rowok = (unsigned)iy < (unsigned)H;
       srd_t srd = make_srd(xn + (long)(rowok ? iy : 0) * rowbytes);
-      srd.z = __builtin_amdgcn_readfirstlane(rowok ? rowbytes : 0u);
+      // (the row's bytes from THIS chunk's first channel on: `x` is shifted by cgx, and a descriptor of the whole row's length would reach
+      // cgx channels past the row -- past the tensor on its last row, where a last chunk narrower than 128 channels reads them)
+      srd.z = __builtin_amdgcn_readfirstlane(rowok ? rowbytes - (unsigned)(cgx * ES) : 0u);
       srd.w = __builtin_amdgcn_readfirstlane(srd.w);
       const int ix0 = tx_ * TW - PAD + seg * PXI;                // first pixel of this segment (may be < 0)
       const unsigned vo = (unsigned)(ix0 + lane / PARTS) < (unsigned)W ? vlane + (unsigned)((ix0 * Cx + cb) * ES) : 0x80000000u;

@@ -152,7 +152,13 @@ int launch_node(const NodeP& p, hipStream_t s) {
 extern "C" int mtbt_bifpn_node_nhwc(const mtbt_node_args* a, void* stream) {
   if (!a || !a->w || !a->y || !a->shift) return MTBT_EINVAL;
   const mtbt_fuse_args& f = a->fuse;
-  if (f.n_in < 1 || f.n_in > 3 || f.N <= 0 || f.H <= 0 || f.W <= 0 || f.add_weight_bug) return MTBT_EINVAL;
+  if (f.N <= 0 || f.H <= 0 || f.W <= 0 || f.add_weight_bug) return MTBT_EINVAL;
+  // the two node shapes of BiFPNUnit.forward and nothing else (include/mtbt_hip.h; modes: 0 identity, 1 bilinear x2, 2 2x2 mean): launch_node()
+  // has no kernel for any other combination
+  const bool top_down = f.n_in == 2 && f.resample[0] == 0 && f.resample[1] == 1;
+  const bool output = f.n_in == 3 && f.resample[0] == 0 && f.resample[1] == 0 && f.resample[2] == 2;
+  if (!top_down && !output) return MTBT_EINVAL;
+  if (top_down && ((f.H & 1) || (f.W & 1))) return MTBT_EINVAL;
   if (f.dtype != MTBT_BF16 && f.dtype != MTBT_F16) return MTBT_EINVAL;       // (fp32 parity mode: mtbt_bifpn_fuse + mtbt_conv2d_nhwc)
   if ((f.C != 128 && f.C != 256) || a->K != f.C) return MTBT_EINVAL;   // square nodes; the B image's slot swizzle spans 16 slots = 128 channels
   if (a->act < 0 || a->act > MTBT_ACT_GELU_POLY) return MTBT_EINVAL;
@@ -164,8 +170,7 @@ extern "C" int mtbt_bifpn_node_nhwc(const mtbt_node_args* a, void* stream) {
     p.f.wgt[i] = f.wgt[i];
     p.f.resample[i] = f.resample[i];
     if (i < f.n_in) {
-      if (!f.x[i] || f.resample[i] < 0 || f.resample[i] > 4) return MTBT_EINVAL;
-      if ((f.resample[i] == 1 || f.resample[i] == 3) && ((f.H & 1) || (f.W & 1))) return MTBT_EINVAL;
+      if (!f.x[i]) return MTBT_EINVAL;
       if (!aligned16(f.x[i])) return MTBT_EALIGN;
     }
   }

@@ -6,6 +6,8 @@ Running the plan is a tight loop of ctypes calls on the caller's current HIP str
 no host synchronisation, so it can be captured into a HIP graph.  PyTorch only owns the memory.
 """
 import ctypes as C
+import os
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Callable, List, Optional
 
@@ -75,7 +77,6 @@ class Pool:
         self.free_list = {}
         self.all = []
         self.bytes = 0
-        import os
         self.reuse = os.environ.get("MTBT_POOL_REUSE", "1") == "1"  # False: released buffers are never handed out again
 
     def get(self, shape, dtype) -> torch.Tensor:
@@ -171,7 +172,6 @@ class Plan:
         self.launches: List[Launch] = []
         self.consts = []  # folded weights etc. (kept alive)
         # development A/B knobs are read ONCE per plan on the host and travel in the argument blocks (the library reads no environment)
-        import os
         pol = os.environ.get("MTBT_CONV_POLICY")
         self.conv_policy = (0x100 | (int(pol) & 0xff)) if pol is not None else 0
         if os.environ.get("MTBT_DIRECT_TC64"):
@@ -182,7 +182,6 @@ class Plan:
     def reload_env(self):
         """(Re-)read the lane knobs from the environment.  They are read HERE, once per plan, not per step: run() / schedule() are
         per-step host work (an eager training step issues ~950 launches).  Tests and tools that flip a knob on a live plan call this."""
-        import os
         self.n_lanes = max(1, int(os.environ.get("MTBT_LANES", "4")))
         self.lane_serial = os.environ.get("MTBT_LANE_SERIAL") == "1"     # dev: total order across lanes (no two launches overlap)
         # launches estimated longer than this fill the machine and stay serialized on lane 0 (round 2: 60 -> 600 us after the kernels got
@@ -410,6 +409,31 @@ class Plan:
     def release(self, a: Act):
         self.pool.put(a.buf)
 
+    # ---- launch records: only the plan edits them ----
+    def amend(self, i=-1, *, keep=(), reads=(), writes=()):
+        """Add to recorded launch i: objects it keeps alive, and what else it reads / writes (activation views or tensors).  An extra read
+        is an ordinary read-after-write edge for the lane scheduler: the way to make a launch WAIT for something it does not consume."""
+        l = self.launches[i]
+        l.keep = l.keep + tuple(keep)
+        l.reads = l.reads + tuple(_region(a) for a in reads)
+        l.writes = l.writes + tuple(_region(a) for a in writes)
+
+    @contextmanager
+    def branch(self, side: bool, reuse: Optional[bool] = None):
+        """Launches appended inside the block are branch work: marked `side` (off lane 0 whenever a side lane is allowed) if `side`;
+        `reuse=False` hands out no recycled buffers inside it, so that independent branches share no buffer and the lane scheduler sees
+        no false dependencies between them."""
+        first, keep = len(self.launches), self.pool.reuse
+        if reuse is not None:
+            self.pool.reuse = keep and reuse
+        try:
+            yield
+        finally:
+            self.pool.reuse = keep
+            if side:
+                for l in self.launches[first:]:
+                    l.side = True
+
     # ---- op builders ----
     def conv(self, x: Act, w: torch.Tensor, y: Act, *, R=1, S=1, stride=1, pad=0, scale=None, shift=None,
              act=L.ACT_NONE, res: Optional[Act] = None, out_mode=L.OUT_NHWC, name="conv", tile_hint=0, policy=0):
@@ -518,17 +542,21 @@ class Plan:
                                     2.0 * pixels * x.C * ESIZE[x.code]))
         self._io([x], [y])
 
-    def fuse(self, inputs, weights, modes, y: Act, bug=False, name="bifpn_fuse"):
+    def fuse(self, inputs, weights, modes, y: Act, bug=False, name="bifpn_fuse", wgt_dev: Optional[torch.Tensor] = None, wgt_first=0):
+        """`wgt_dev`: fp32 tensor in device memory whose elements wgt_first .. wgt_first + n_in are used instead of `weights` (training: the
+        fusion weights are parameters, normalised on the device every step)."""
         a = L.FuseArgs()
         for i, (t, wv, m) in enumerate(zip(inputs, weights, modes)):
             assert t.dense
             a.x[i], a.wgt[i], a.resample[i] = t.ptr, float(wv), m
         a.n_in, a.y = len(inputs), y.ptr
         a.N, a.H, a.W, a.C, a.dtype, a.add_weight_bug = y.N, y.H, y.W, y.C, y.code, int(bug)
+        if wgt_dev is not None:
+            a.wgt_dev = wgt_dev.data_ptr() + 4 * wgt_first
         n = y.N * y.H * y.W * y.C
-        self.launches.append(Launch(self.lib.mtbt_bifpn_fuse, (C.byref(a),), name, (a, y.buf) + tuple(t.buf for t in inputs),
+        self.launches.append(Launch(self.lib.mtbt_bifpn_fuse, (C.byref(a),), name, (a, y.buf, wgt_dev) + tuple(t.buf for t in inputs),
                                     0.0, n * ESIZE[y.code] * (1 + len(inputs))))
-        self._io(list(inputs), [y])
+        self._io(list(inputs) + [wgt_dev], [y])
         return a
 
     def gap_fc(self, x: Act, w, b, y: torch.Tensor, name="gap_fc"):

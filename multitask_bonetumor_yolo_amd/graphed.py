@@ -80,20 +80,10 @@ class GraphedInference:
                 self.fwd, self.out = self._step()
             # Keep the plan alive for as long as the graph: the model's plan cache may evict it (weight update, BatchNorm mode flip),
             # which would hand its buffers back to the caching allocator while the captured kernels still read and write them.
-            self._compiled = self._eval_compile()
+            with model._heads_mode(False):
+                self._compiled = model.compile(x)
             self._sig = self._compiled.sig
         torch.cuda.current_stream(x.device).wait_stream(self.stream)
-
-    def _eval_compile(self):
-        heads = [h for h in (getattr(self.model, "detect", None), self.model.segment) if h is not None]
-        flags = [h.training for h in heads]
-        try:
-            for h in heads:
-                h.eval()
-            return self.model.compile(self.x)
-        finally:
-            for h, f in zip(heads, flags):
-                h.training = f
 
     def _step(self):
         img_size, conf_th, iou_th, top_k, masks = self.args
@@ -106,12 +96,7 @@ class GraphedInference:
         # of a 20-step measurement).  A stale replay only rewrites this object's own static outputs, and the caller still gets the error
         # instead of them.
         self.graph.replay()
-        if self.model._weights_sig(self._compiled_modes()) != self._sig:
+        if self.model._weights_sig(self.model._bn_modes(heads_eval=True)) != self._sig:
             raise RuntimeError("GraphedInference: the model's weights / BatchNorm statistics changed since the capture (the graph replays "
                                "kernels over the OLD folded weights): build a new GraphedInference")
         return self.out
-
-    def _compiled_modes(self):
-        import torch.nn as nn
-        heads = {id(m) for h in (getattr(self.model, "detect", None), self.model.segment) if h is not None for m in h.modules()}
-        return tuple((False if id(m) in heads else m.training) for m in self.model.modules() if isinstance(m, nn.BatchNorm2d))

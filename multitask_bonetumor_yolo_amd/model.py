@@ -13,6 +13,7 @@ There is no CPU path: tensors must live on an MI355X and the HIP library must be
 import ctypes as C
 import math
 import os
+from contextlib import contextmanager
 from typing import List
 
 import torch
@@ -246,6 +247,15 @@ def compose_upconv(wt: torch.Tensor, bt: torch.Tensor, w3: torch.Tensor, scale: 
     return w.reshape(4 * K, 4 * Ci).float(), shift9.float()
 
 
+def fold_dwblock(mod: DepthwiseConvBlock):
+    """Eval-mode DepthwiseConvBlock (k = 1) as one 1x1 convolution: the per-channel depthwise scale and the BatchNorm scale folded into the
+    pointwise weight -> (weights [K, C], shift [K]), fp32."""
+    dw = mod.depthwise.weight.detach().float().reshape(1, -1)
+    pw = mod.pointwise.weight.detach().float().reshape(mod.pointwise.out_channels, -1) * dw
+    scale, shift = _bn_fold(mod.bn)
+    return pw * scale[:, None], shift
+
+
 def pack_convblocks(mods):
     """Eval-mode conv + BN blocks that read ONE tensor, as one convolution: weights [sum K, R*S*C] with each block's BN scale folded into its
     rows, shifts concatenated (fp32).  Slice j equals what `_Lowering.convblock` packs for block j alone."""
@@ -287,14 +297,16 @@ def plan_option(model, name: str):
 
 
 class _Lowering:
-    """Builds the launch plan for one (batch, size, dtype, mode) from the module tree."""
+    """Builds the launch plan for one (batch, size, dtype, mode) from the module tree: `lower()`.  Lowering allocates buffers on `device` and
+    records launches; it issues nothing, so it also runs on torch.device("cpu") (tools/dump_schedule.py, the plan-signature tests)."""
 
-    def __init__(self, model, x: torch.Tensor, code: int):
+    def __init__(self, model, shape, device, code: int):
         self.m = model
         self.code = code
         self.dt = TORCH_DTYPE[code]
-        self.p = Plan(x.device)
-        self.x = x
+        self.device = device
+        self.p = Plan(device)
+        self.x = torch.empty(tuple(shape), dtype=torch.float32, device=device)   # the plan's own input buffer (`_Base._bind_input`)
         self.train_bns = []  # BatchNorms lowered with batch statistics (their num_batches_tracked advances per run)
 
     # constants
@@ -380,11 +392,9 @@ class _Lowering:
         """DepthwiseConvBlock (k=1): per-channel scale folded into the pointwise weight, BN folded, ELU."""
         if mod.bn.training:
             raise NotImplementedError(f"{name}: BiFPN DepthwiseConvBlock with batch-statistic BatchNorm (model.train()) is not lowered yet")
-        dw = mod.depthwise.weight.detach().float().reshape(1, -1)
-        pw = mod.pointwise.weight.detach().float().reshape(mod.pointwise.out_channels, -1) * dw
-        scale, shift = _bn_fold(mod.bn)
-        y = self.p.new(x.N, x.H, x.W, pw.shape[0], self.code)
-        self.p.conv(x, self.W(pw * scale[:, None]), y, shift=self.F(shift), act=L.ACT_ELU, name=name)
+        w, shift = fold_dwblock(mod)
+        y = self.p.new(x.N, x.H, x.W, w.shape[0], self.code)
+        self.p.conv(x, self.W(w), y, shift=self.F(shift), act=L.ACT_ELU, name=name)
         return y
 
     @staticmethod
@@ -395,18 +405,6 @@ class _Lowering:
         HBM; d = 768 is not built (one weight stage is 98 KiB of LDS).  MTBT_FUSED_DIMS="96:192" restores the two-GEMM form (A/B)."""
         env = os.environ.get("MTBT_FUSED_DIMS")
         return tuple(int(v) for v in env.replace(":", ",").split(",")) if env else (96, 192, 384)
-
-    def subbatch(self, stage: int, a: Act) -> int:
-        """Images per depth-first pass of a ConvNeXt stage.  Measured (bench.py --ab MTBT_SUBBATCH=...): keeping the 4d-wide
-        intermediate Infinity-Cache-resident by running 2-8 images at a time does NOT pay on MI355X at batch 16 -- the
-        smaller launches lose more to ramp/tail than the cache saves (9.75 ms at 4:8 vs 9.46 ms whole-batch) -- so the
-        default is the whole batch; MTBT_SUBBATCH="s0:s1:s2:s3" overrides for experiments."""
-        import os
-        env = os.environ.get("MTBT_SUBBATCH")
-        if env:
-            v = int(env.split(":")[stage])
-            return a.N if v <= 0 else min(v, a.N)
-        return a.N
 
     # -- backbone (main_model.py:33-38) --
     def backbone(self):
@@ -422,11 +420,8 @@ class _Lowering:
 
         def hook(si, a):
             if early:
-                first = len(self.p.launches)
-                outs[si] = self.c2f(a, *mods[si])
-                if si < 3:                       # (the last adaptor has nothing left to hide under: it continues the main chain)
-                    for l in self.p.launches[first:]:
-                        l.side = True
+                with self.p.branch(side=si < 3):     # (the last adaptor has nothing left to hide under: it continues the main chain)
+                    outs[si] = self.c2f(a, *mods[si])
         feats = self.features(bb.body, hook)
         if not early:
             for si in (1, 2, 3):
@@ -457,15 +452,11 @@ class _Lowering:
                     self.p.release(a)
                 a = nxt
             d = a.C
-            # Sub-batching (depth-first over the stage's blocks): the 4d-wide MLP intermediate of a full batch does not fit
-            # the 256 MiB Infinity Cache in the early stages (16 x 160^2 x 384 bf16 = 315 MB); running all blocks of the
-            # stage on a few images at a time keeps t / h / o cache-resident instead of round-tripping through HBM.
-            sb = self.subbatch(si, a)
-            out_full = self.p.new(a.N, a.H, a.W, d, self.code)
-            t = self.p.new(sb, a.H, a.W, d, self.code)
-            fused = self.code in (L.BF16, L.F16) and d in self.fused_dims() and sb == a.N and os.environ.get("MTBT_FUSED_MLP", "1") == "1"
-            h = None if fused else self.p.new(sb, a.H, a.W, 4 * d, self.code)
-            pp_ = [self.p.new(sb, a.H, a.W, d, self.code) for _ in range(2)] if len(st.blocks) > 1 else []
+            out = self.p.new(a.N, a.H, a.W, d, self.code)
+            t = self.p.new(a.N, a.H, a.W, d, self.code)
+            fused = self.code in (L.BF16, L.F16) and d in self.fused_dims() and os.environ.get("MTBT_FUSED_MLP", "1") == "1"
+            h = None if fused else self.p.new(a.N, a.H, a.W, 4 * d, self.code)
+            pp_ = [self.p.new(a.N, a.H, a.W, d, self.code) for _ in range(2)] if len(st.blocks) > 1 else []
             consts = []
             for blk in st.blocks:
                 g = blk.gamma.detach().float()
@@ -474,27 +465,23 @@ class _Lowering:
                                self.W(blk.mlp.fc2.weight.detach().float() * g[:, None]), self.F(g * blk.mlp.fc2.bias.detach().float())))
             w2p = [self.p.const(_permute_hidden(c_[6]), self.dt) for c_ in consts] if fused else None
             # bf16 mode: polynomial GELU (|err| <= 2.3e-4, below bf16 resolution); fp32 parity mode: the erf form
-            gelu = L.ACT_GELU_POLY if self.code in (L.BF16, L.F16) and os.environ.get("MTBT_GELU_POLY", "1") == "1" else L.ACT_GELU
-            for n0 in range(0, a.N, sb):
-                nn_ = min(sb, a.N - n0)
-                view = lambda act, k=nn_, o=n0: Act(act.buf, act.off + o * act.bs, k, act.H, act.W, act.C, act.ld, act.bs)
-                local = lambda act, k=nn_: Act(act.buf, act.off, k, act.H, act.W, act.C, act.ld, act.bs)
-                cur = view(a)
-                for bi, blk in enumerate(st.blocks):
-                    bn_ = f"{nm}.blocks.{bi}" + (f"[{n0}:{n0 + nn_}]" if sb < a.N else "")
-                    dww, dwb, lnw, lnb, w1, b1, w2, b2 = consts[bi]
-                    self.p.dwconv(cur, dww, local(t), 7, bias=dwb, lnw=lnw, lnb=lnb, eps=blk.norm.eps, name=bn_ + ".conv_dw+norm")
-                    dst = view(out_full) if bi == len(st.blocks) - 1 else local(pp_[bi % 2])
-                    if fused:   # stages 0-1 in bf16: the 4d-wide hidden tensor stays on chip (mlp_fused.hip)
-                        self.p.mlp_fused(local(t), cur, w1, b1, w2p[bi], b2, dst, name=bn_ + ".mlp(fused)")
-                    else:
-                        self.p.conv(local(t), w1, local(h), shift=b1, act=gelu, name=bn_ + ".mlp.fc1")
-                        self.p.conv(local(h), w2, dst, shift=b2, res=cur, name=bn_ + ".mlp.fc2")
-                    cur = dst
+            gelu = L.ACT_GELU_POLY if self.code in (L.BF16, L.F16) else L.ACT_GELU
+            cur = a
+            for bi, blk in enumerate(st.blocks):
+                bn_ = f"{nm}.blocks.{bi}"
+                dww, dwb, lnw, lnb, w1, b1, w2, b2 = consts[bi]
+                self.p.dwconv(cur, dww, t, 7, bias=dwb, lnw=lnw, lnb=lnb, eps=blk.norm.eps, name=bn_ + ".conv_dw+norm")
+                dst = out if bi == len(st.blocks) - 1 else pp_[bi % 2]
+                if fused:   # stages 0-2 in bf16 / fp16: the 4d-wide hidden tensor stays on chip (mlp_fused.hip)
+                    self.p.mlp_fused(t, cur, w1, b1, w2p[bi], b2, dst, name=bn_ + ".mlp(fused)")
+                else:
+                    self.p.conv(t, w1, h, shift=b1, act=gelu, name=bn_ + ".mlp.fc1")
+                    self.p.conv(h, w2, dst, shift=b2, res=cur, name=bn_ + ".mlp.fc2")
+                cur = dst
             for buf in [t] + ([] if h is None else [h]) + pp_:
                 self.p.release(buf)
             self.p.release(a)        # stage input: stem / downsample output, never a feature
-            a = out_full
+            a = out
             if si >= 1:
                 feats.append(a)      # stage outputs 1..3 stay live until the adaptors have read them
                 if on_feature is not None:
@@ -555,11 +542,9 @@ class _Lowering:
                 if (self.code in (L.BF16, L.F16) and like.C in (128, 256) and K == like.C and list(modes) in shapes and not conv.bn.training
                         and plan_option(self.m, "NODE_FUSED") == "1"):
                     # weighted sum + resample + DepthwiseConvBlock (scale folded, BN folded, ELU) in ONE launch: the fused map never reaches HBM
-                    dw = conv.depthwise.weight.detach().float().reshape(1, -1)
-                    pw = conv.pointwise.weight.detach().float().reshape(K, -1) * dw
-                    scale, shift = _bn_fold(conv.bn)
+                    w, shift = fold_dwblock(conv)
                     d = self.p.new(like.N, like.H, like.W, K, self.code)
-                    self.p.node(inputs, [float(v) for v in weights], modes, self.W(pw * scale[:, None]), self.F(shift), d, act=L.ACT_ELU,
+                    self.p.node(inputs, [float(v) for v in weights], modes, self.W(w), self.F(shift), d, act=L.ACT_ELU,
                                 name=f"{nm}.{tag}.fuse+conv")
                 else:
                     s = self.p.new(like.N, like.H, like.W, like.C, self.code)
@@ -590,47 +575,51 @@ class _Lowering:
 
     # -- heads [ultralytics] --
     def f32_out(self, N, H, W, Cc) -> Act:
-        return Act.of(torch.empty((N, H, W, Cc), dtype=torch.float32, device=self.x.device))
+        return Act.of(torch.empty((N, H, W, Cc), dtype=torch.float32, device=self.device))
 
-    def det_level(self, i, f: Act, head: Detect, tag, gate=None) -> Act:
-        """Level i of Detect.forward: cv2 (box, 4*reg_max ch) and cv3 (cls, nc ch) write side by side into one [N,h,w,no] fp32 map
-        (the `torch.cat((cv2_i, cv3_i), 1)` of Detect.forward without the copy).
-        `gate`: activations / tensors the first launch of each of the two chains is made to WAIT for (recorded as extra reads, i.e.
-        ordinary read-after-write edges for the lane scheduler): the caller's way of keeping a branch nobody is waiting for off the
-        machine until the branches on the post-process's critical path are through."""
-        from .engine import _region
-
-        def gated(first):
-            if gate:
-                l = self.p.launches[first]
-                l.reads = l.reads + tuple(_region(g) for g in gate)
+    def head_map(self, f: Act, head: Detect) -> Act:
+        """The [N,h,w,no] fp32 output map of one level: cv2 (box, 4*reg_max ch) and cv3 (cls, nc ch) write side by side into it (the
+        `torch.cat((cv2_i, cv3_i), 1)` of Detect.forward without the copy)."""
         # pixel pitch rounded up to 4 floats (66 -> 68): the 64-channel box slice then starts every pixel on a 16-byte boundary and the
         # conv epilogue stores it with 16-byte accesses (at pitch 66 it fell back to 64 scalar stores per pixel: 43 us per P3 map, 0.11 of HBM)
         ld = (head.no + 3) // 4 * 4
-        buf = torch.empty((f.N, f.H, f.W, ld), dtype=torch.float32, device=self.x.device)
-        full = Act(buf, 0, f.N, f.H, f.W, head.no, ld, f.H * f.W * ld)
-        # the class chain (two depthwise + two 1x1 + output conv) is the longer one: first
+        buf = torch.empty((f.N, f.H, f.W, ld), dtype=torch.float32, device=self.device)
+        return Act(buf, 0, f.N, f.H, f.W, head.no, ld, f.H * f.W * ld)
+
+    def cls_chain(self, i, f: Act, head: Detect, tag, dst: Act):
+        """Class chain of level i (cv3: two depthwise 3x3 + 1x1 pairs, then the output conv) into `dst`."""
         s = head.cv3[i]
-        first = len(self.p.launches)
         d1 = self.dwblock(f, s[0][0], f"{tag}.cv3.{i}.0.0")
-        gated(first)
         t1 = self.convblock(d1, s[0][1], None, f"{tag}.cv3.{i}.0.1")
         self.p.release(d1)
         d2 = self.dwblock(t1, s[1][0], f"{tag}.cv3.{i}.1.0")
         self.p.release(t1)
         t2 = self.convblock(d2, s[1][1], None, f"{tag}.cv3.{i}.1.1")
         self.p.release(d2)
-        self.conv_plain(t2, s[2], full.slice(4 * head.reg_max, head.nc), f"{tag}.cv3.{i}.2")
+        self.conv_plain(t2, s[2], dst, f"{tag}.cv3.{i}.2")
         self.p.release(t2)
-        s = head.cv2[i]
-        first = len(self.p.launches)
-        t1 = self.convblock(f, s[0], None, f"{tag}.cv2.{i}.0")
-        gated(first)
-        t2 = self.convblock(t1, s[1], None, f"{tag}.cv2.{i}.1")
+
+    def conv_chain(self, f: Act, s, name, dst: Act):
+        """Two 3x3 conv blocks and the output conv (Detect.cv2[i], Segment.cv4[i]) into `dst`."""
+        t1 = self.convblock(f, s[0], None, name + ".0")
+        t2 = self.convblock(t1, s[1], None, name + ".1")
         self.p.release(t1)
-        self.conv_plain(t2, s[2], full.slice(0, 4 * head.reg_max), f"{tag}.cv2.{i}.2")
+        self.conv_plain(t2, s[2], dst, name + ".2")
         self.p.release(t2)
-        return full
+
+    def det_level(self, i, f: Act, head: Detect, tag, full: Act, gate=None):
+        """Level i of Detect.forward into the head map `full`.
+        `gate`: activations / tensors the first launch of each of the two chains is made to WAIT for (recorded as extra reads, i.e.
+        ordinary read-after-write edges for the lane scheduler): the caller's way of keeping a branch nobody is waiting for off the
+        machine until the branches on the post-process's critical path are through."""
+        # the class chain (two depthwise + two 1x1 + output conv) is the longer one: first
+        first = len(self.p.launches)
+        self.cls_chain(i, f, head, tag, full.slice(4 * head.reg_max, head.nc))
+        box = len(self.p.launches)
+        self.conv_chain(f, head.cv2[i], f"{tag}.cv2.{i}", full.slice(0, 4 * head.reg_max))
+        if gate:
+            self.p.amend(first, reads=gate)
+            self.p.amend(box, reads=gate)
 
     def heads_mergeable(self, i, heads, f: Act) -> bool:
         """Whether level i of these heads (Detect and / or Segment, the Segment last) can share launches: every BatchNorm of the level's
@@ -659,12 +648,12 @@ class _Lowering:
         for (x, w, y, shift), nm in zip(members, names):
             self.p.conv(x, w, y, shift=shift, name=nm, **{k: v for k, v in kw.items()})
 
-    def heads_level_merged(self, i, f: Act, heads, maps, mc: torch.Tensor, off: int, A: int):
+    def heads_level_merged(self, i, f: Act, heads, maps):
         """Level i of Detect + Segment (or of Segment alone) with the branches that read one tensor sharing launches (plan option
         HEADS_MERGED): the first box / mask-coefficient convs as ONE 3x3 conv with concatenated output channels, the class chains' depthwise
         convs as one depth-multiplier launch and one concatenated launch, every later stage as a batch of equal convolutions over channel
         slices.  Every output element is computed by the arithmetic of the separate lowering.  heads: [(module, tag)], the Segment last;
-        maps: their [N,h,w,no] fp32 output maps (pitch rounded up to 4 floats, as det_level makes them)."""
+        maps: their `head_map`s."""
         seg = heads[-1][0]
         nh, c2, c3 = len(heads), seg.cv4[i][0].conv.out_channels, f.C
         N, H, W = f.N, f.H, f.W
@@ -690,24 +679,14 @@ class _Lowering:
             outs = [h.cv2[i][2] for h, _ in heads]
             self._batch([(t2.slice(j * c2, c2), self.W(_krsc(cv.weight)), maps[j].slice(0, 4 * h.reg_max), self.F(cv.bias))
                          for j, ((h, _), cv) in enumerate(zip(heads, outs))], " + ".join(f"{t}.cv2.{i}.2" for _, t in heads))
-            lvl = Act(mc, off * seg.nm, N, H, W, seg.nm, seg.nm, A * seg.nm)
-            self.conv_plain(t2.slice(nh * c2, c2), seg.cv4[i][2], lvl, f"segment.cv4.{i}.2")
+            self.conv_plain(t2.slice(nh * c2, c2), seg.cv4[i][2], self.mc_level(i, f), f"segment.cv4.{i}.2")
             self.p.release(t2)
 
         # the class chains (two depthwise + two 1x1 + output conv) are the longer ones: first, as in det_level.  (2) depthwise x nh off f,
         # (4) 1x1, (5) depthwise over the concatenation, (6) 1x1, (8) class outputs
         if nh == 1:
             h, t = heads[0]
-            s = h.cv3[i]
-            d1 = self.dwblock(f, s[0][0], f"{t}.cv3.{i}.0.0")
-            u1 = self.convblock(d1, s[0][1], None, f"{t}.cv3.{i}.0.1")
-            self.p.release(d1)
-            d2 = self.dwblock(u1, s[1][0], f"{t}.cv3.{i}.1.0")
-            self.p.release(u1)
-            u2 = self.convblock(d2, s[1][1], None, f"{t}.cv3.{i}.1.1")
-            self.p.release(d2)
-            self.conv_plain(u2, s[2], maps[0].slice(4 * h.reg_max, h.nc), f"{t}.cv3.{i}.2")
-            self.p.release(u2)
+            self.cls_chain(i, f, h, t, maps[0].slice(4 * h.reg_max, h.nc))
             return box_chains()
         ctags = [f"{t}.cv3.{i}" for _, t in heads]
         wd, scd, shd = pack_dwblocks([h.cv3[i][0][0] for h, _ in heads])
@@ -735,15 +714,6 @@ class _Lowering:
         self.p.release(u2)
         box_chains()
 
-    def head_map(self, f: Act, head: Detect) -> Act:
-        """The [N,h,w,no] fp32 output map of one level (pixel pitch rounded up to 4 floats: see det_level)."""
-        ld = (head.no + 3) // 4 * 4
-        buf = torch.empty((f.N, f.H, f.W, ld), dtype=torch.float32, device=self.x.device)
-        return Act(buf, 0, f.N, f.H, f.W, head.no, ld, f.H * f.W * ld)
-
-    def det_branch(self, feats, head: Detect, tag, gate=None):
-        return [self.det_level(i, f, head, tag, gate[i] if gate is not None else None) for i, f in enumerate(feats)]
-
     def mc_buffer(self, shapes, head: Segment):
         """[N, A, nm] fp32 buffer of the mask coefficients of all levels + the anchor offset of every level."""
         N = shapes[0][0]
@@ -752,23 +722,18 @@ class _Lowering:
         for _, h, w in shapes:
             offs.append(off)
             off += h * w
-        return torch.empty((N, A, head.nm), dtype=torch.float32, device=self.x.device), offs, A
+        return torch.empty((N, A, head.nm), dtype=torch.float32, device=self.device), offs, A
 
-    def cv4_level(self, i, f: Act, head: Segment, mc: torch.Tensor, off: int, A: int):
-        s = head.cv4[i]
-        t1 = self.convblock(f, s[0], None, f"segment.cv4.{i}.0")
-        t2 = self.convblock(t1, s[1], None, f"segment.cv4.{i}.1")
-        self.p.release(t1)
-        lvl = Act(mc, off * head.nm, f.N, f.H, f.W, head.nm, head.nm, A * head.nm)
-        self.conv_plain(t2, s[2], lvl, f"segment.cv4.{i}.2")
-        self.p.release(t2)
+    def mc_level(self, i, f: Act) -> Act:
+        """Level i's [N,h,w,nm] view into the [N,A,nm] mask-coefficient buffer."""
+        nm = self.m.segment.nm
+        return Act(self.mc, self.offs[i] * nm, f.N, f.H, f.W, nm, nm, self.A * nm)
 
     def proto(self, f: Act, head: Segment) -> Act:
         """ultralytics Proto on P3: cv1 3x3 -> upsample (ConvTranspose 2x2 / 2) -> cv2 3x3 -> cv3 1x1."""
         pr = head.proto
         t1 = self.convblock(f, pr.cv1, None, "segment.proto.cv1")
-        if (not pr.cv2.bn.training and f.H % 16 == 0 and f.W % 16 == 0 and pr.cv2.conv.out_channels % 128 == 0
-                and os.environ.get("MTBT_PROTO_FUSED", "1") == "1"):
+        if not pr.cv2.bn.training and f.H % 16 == 0 and f.W % 16 == 0 and pr.cv2.conv.out_channels % 128 == 0:
             # upsample (ConvTranspose 2x2 / 2 + bias) and cv2 (3x3 + BN + SiLU) are linear with nothing in between: ONE 2x2-tap direct conv
             # per output parity on the low-resolution map -- 4/10 of the MACs, no [N, 2H, 2W, 256] tensor written and read back
             sc, sh = _bn_fold(pr.cv2.bn)
@@ -789,26 +754,89 @@ class _Lowering:
         self.p.release(t2)
         return protos
 
-    def seg_extras(self, feats, head: Segment):
-        """Mask coefficients (cv4, all levels into one [N,A,nm] buffer) and prototypes (Proto on P3)."""
-        mc, offs, A = self.mc_buffer([(f.N, f.H, f.W) for f in feats], head)
-        for i, f in enumerate(feats):
-            self.cv4_level(i, f, head, mc, offs[i], A)
-        return mc, self.proto(feats[0], head)
-
     def cls_head(self, n5: Act):
-        logits = torch.empty((n5.N, self.m.cls_fc.out_features), dtype=torch.float32, device=self.x.device)
+        logits = torch.empty((n5.N, self.m.cls_fc.out_features), dtype=torch.float32, device=self.device)
         self.p.gap_fc(n5, self.F(self.m.cls_fc.weight), self.F(self.m.cls_fc.bias), logits, name="cls_pool+cls_fc")
         return logits
 
+    def level_heads(self, i, f: Act):
+        """Everything that hangs off pyramid level i, in the order of what the post-process waits for: the prototype chain (the
+        longest, P3 only), Detect's branches (decode -> NMS), the mask coefficients, then Segment's own box / class branches
+        (they feed `segment_preds_cat` only: optionally gated behind Detect's map of the level, MTBT_SEG_GATE=1)."""
+        seg = self.m.segment
+        # the head branches are independent: no buffer recycling between them, so the lane scheduler sees no false dependencies;
+        # lowered in the middle of the neck (HEADS_EARLY) they are branch work, off the neck's main chain
+        with self.p.branch(side=self.early, reuse=False):
+            if i == 0:
+                self.protos = self.proto(f, seg)
+            maps = [self.head_map(f, h) for h, _ in self.heads]
+            if self.merged and self.heads_mergeable(i, self.heads, f):
+                self.heads_level_merged(i, f, self.heads, maps)
+            else:
+                for (h, tag), full in zip(self.heads[:-1], maps):
+                    self.det_level(i, f, h, tag, full)
+                self.conv_chain(f, seg.cv4[i], f"segment.cv4.{i}", self.mc_level(i, f))
+                self.det_level(i, f, seg, "segment", maps[-1], maps[:-1] if self.gate else None)
+        if self.det_maps is not None:
+            self.det_maps[i] = maps[0]
+        self.seg_maps[i] = maps[-1]
+
+    def lower(self, sig=None) -> "_Compiled":
+        """The complete inference plan of the model for this lowering's shape / dtype; `sig`: the weights signature it is cached under."""
+        m, p = self.m, self.p
+        if plan_option(m, "LANES") is not None:
+            p.n_lanes = max(1, int(plan_option(m, "LANES")))
+        if plan_option(m, "LANE_WIDE_US") is not None:
+            p.lane_wide_s = float(plan_option(m, "LANE_WIDE_US")) * 1e-6
+        v0 = isinstance(m, ConvNeXtBiFPNYOLOv0)
+        self.early = plan_option(m, "HEADS_EARLY") == "1" and not v0
+        self.merged = plan_option(m, "HEADS_MERGED") == "1" and not v0
+        self.gate = int(plan_option(m, "SEG_GATE")) >= 1
+        self.heads = ([(m.detect, "detect")] if hasattr(m, "detect") else []) + [(m.segment, "segment")]     # the Segment last
+        self.det_maps, self.seg_maps = ([None] * 3 if hasattr(m, "detect") else None), [None] * 3
+        N, _, H, W = self.x.shape
+        self.mc, self.offs, self.A = self.mc_buffer([(N, H // s_, W // s_) for s_ in (8, 16, 32)], m.segment)
+        with torch.no_grad():
+            if v0:
+                feats = self.neck_v0(*self.features(m.backbone.body))
+            else:
+                # MTBT_HEADS_EARLY (default): the heads of a pyramid level are lowered -- and therefore issued / captured -- the moment the
+                # LAST BiFPN unit has produced that level.  P3 comes first (top-down node), and P3 carries most of the head work (the
+                # prototype chain, the 80x80 branches): it then runs beside the unit's P4 / P5 output nodes, small launches that leave most
+                # of the machine idle, instead of queueing behind them; and the chains the post-process waits for (prototypes, Detect)
+                # are first in line.  (Round 2 lowered all heads after the neck, Detect -> cv4 -> Proto -> Segment: in the replayed graph
+                # the prototype chain started up to 0.6 ms after its input existed and the mask assembly waited for it at the end.)
+                feats = self.neck(*self.backbone(), on_level=self.level_heads if self.early else None)
+            if not self.early:
+                for i, f in enumerate(feats):
+                    self.level_heads(i, f)
+            logits = self.cls_head(feats[2])
+
+        def writers(*tensors):
+            keys = {t.untyped_storage().data_ptr() for t in tensors}
+            return [i for i, l in enumerate(p.launches) if any(w[0] in keys for w in l.writes)]
+        # launches that write the maps the box decode reads: the post-process forks as soon as these are done
+        det_marks = writers(*[a.buf for a in (self.det_maps if self.det_maps is not None else self.seg_maps)])
+        mask_marks = writers(self.mc, self.protos.buf)
+        return _Compiled(p, self.x, self.det_maps, self.seg_maps, self.mc, self.protos, logits, sig, det_marks, mask_marks, self.train_bns)
+
 
 class _Compiled:
-    """One lowered forward: the plan plus the tensors it writes (plan-owned, overwritten every run)."""
+    """One lowered forward: the plan plus the tensors it writes (plan-owned, overwritten every run).  det_marks / mask_marks: the launches
+    the box decode / the mask assembly wait for; train_bns: the BatchNorms lowered with batch statistics."""
 
-    def __init__(self, plan, x_static, det_maps, seg_maps, mc, protos, logits, sig):
+    def __init__(self, plan, x_static, det_maps, seg_maps, mc, protos, logits, sig, det_marks, mask_marks, train_bns):
         self.plan, self.x = plan, x_static
         self.det_maps, self.seg_maps, self.mc, self.protos, self.logits = det_maps, seg_maps, mc, protos, logits
         self.sig = sig
+        self.det_marks, self.mask_marks, self.train_bns = det_marks, mask_marks, train_bns
+
+    def outputs(self, own=True):
+        """(Detect maps | None, Segment maps, mc [N,nm,A], protos, logits) in the reference's layouts: fresh copies, or with own=False
+        views of the plan's buffers (valid until the next run)."""
+        cp = (lambda t: t.clone()) if own else (lambda t: t)
+        det = [cp(m.nchw()) for m in self.det_maps] if self.det_maps is not None else None
+        return det, [cp(m.nchw()) for m in self.seg_maps], cp(self.mc.permute(0, 2, 1)), cp(self.protos.nchw()), cp(self.logits)
 
 
 class _Base(nn.Module):
@@ -847,11 +875,12 @@ class _Base(nn.Module):
         # per-tensor (address, version) PAIRS, hashed as a tuple: additive sums (round 2) let two changes cancel (a re-homed parameter
         # whose low pointer bits drop by a version bump, two swapped storages) and a plan with stale folded weights be reused
         ver = hash(tuple((p.data_ptr(), p._version) for p in self.parameters()))
-        bns = self.__dict__.get("_bn_list")
-        if bns is None:
-            bns = self.__dict__["_bn_list"] = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
+        bns = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
+        modes = [m.training for m in bns] if bn_modes is None else list(bn_modes)
+        if len(modes) != len(bns):
+            raise ValueError(f"{len(modes)} BatchNorm modes for a model with {len(bns)} BatchNorm2d modules")
         st = []
-        for m, tr in zip(bns, bn_modes if bn_modes is not None else [m.training for m in bns]):
+        for m, tr in zip(bns, modes):
             if not tr:      # eval-mode BatchNorm: this plan FOLDED its running statistics (`_mtbt_epoch`: in-kernel updates of them)
                 st.append((m.running_mean.data_ptr(), m.running_mean._version, m.running_var.data_ptr(), m.running_var._version,
                            m.__dict__.get("_mtbt_epoch", 0)))
@@ -864,25 +893,49 @@ class _Base(nn.Module):
         return self
 
     def _heads(self):
-        raise NotImplementedError
+        """The head modules forward() switches between train and eval: Detect (where the variant has one) and Segment."""
+        return [h for h in (getattr(self, "detect", None), self.segment) if h is not None]
+
+    def _bn_modes(self, heads_eval=False):
+        """`.training` of every BatchNorm2d in `modules()` order -- what a plan is keyed by and `_weights_sig` pairs with the modules;
+        `heads_eval`: as they are once forward(x, "infer") has put the heads in eval mode."""
+        heads = {id(m) for h in self._heads() for m in h.modules()} if heads_eval else ()
+        return tuple(m.training and id(m) not in heads for m in self.modules() if isinstance(m, nn.BatchNorm2d))
+
+    @contextmanager
+    def _heads_mode(self, training: bool):
+        """Detect / Segment in train or eval mode for one call; afterwards the top-level flags only are restored, as the reference does
+        (main_model.py:391-393)."""
+        heads = self._heads()
+        flags = [h.training for h in heads]
+        try:
+            for h in heads:
+                h.train(training)
+            yield
+        finally:
+            for h, flag in zip(heads, flags):
+                h.training = flag
 
     def _wants_training_plan(self) -> bool:
         """forward(x, "train") goes through the training lowering when autograd is recording on a trainable model, or when a
         backbone / neck BatchNorm is in train mode (batch statistics into C2f slices: only train.py lowers those)."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             return True
-        heads = {id(m) for h in (getattr(self, "detect", None), self.segment) if h is not None for m in h.modules()}
-        return any(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d) and id(m) not in heads)
+        return any(self._bn_modes(heads_eval=True))
 
-    def compile(self, x: torch.Tensor) -> "_Compiled":
-        """Lower the graph for this input's shape/dtype policy (cached until weights or BN modes change)."""
+    @staticmethod
+    def check_input(x: torch.Tensor):
         if not x.is_cuda:
             raise RuntimeError("ConvNeXtBiFPNYOLO (HIP) needs CUDA/HIP tensors on an MI355X; there is no CPU path")
         if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
             raise ValueError(f"expected [B,3,S,S] with S a multiple of 32, got {tuple(x.shape)}")
+
+    def compile(self, x: torch.Tensor) -> "_Compiled":
+        """Lower the graph for this input's shape/dtype policy (cached until weights or BN modes change)."""
+        self.check_input(x)
         # one plan per BatchNorm-mode tuple: alternating forward(x, "infer") and forward(x, "train") (validation: heads on batch
         # statistics) no longer evict each other, and a train-mode call does not invalidate its own plan
-        bn_modes = tuple(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d))
+        bn_modes = self._bn_modes()
         opts = tuple(plan_option(self, k) for k in sorted(PLAN_OPTION_DEFAULTS))
         key = (tuple(x.shape), self.compute_dtype, x.device.index, bn_modes, opts)
         sig = self._weights_sig(bn_modes)
@@ -890,80 +943,8 @@ class _Base(nn.Module):
         if len(cache) > 8:                                # bounded: stale (shape, mode) plans hold buffer pools
             cache.pop(next(iter(cache)))
         c = cache.get(key)
-        if c is not None and c.sig == sig:
-            return c
-        with torch.no_grad():
-            xs = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
-            lo = _Lowering(self, xs, code_of(self.compute_dtype))
-            if plan_option(self, "LANES") is not None:
-                lo.p.n_lanes = max(1, int(plan_option(self, "LANES")))
-            if plan_option(self, "LANE_WIDE_US") is not None:
-                lo.p.lane_wide_s = float(plan_option(self, "LANE_WIDE_US")) * 1e-6
-            has_det = hasattr(self, "detect")
-            det_maps = [None] * 3 if has_det else None
-            seg_maps = [None] * 3
-            state = {}
-            gate_mode = int(plan_option(self, "SEG_GATE"))
-            early = plan_option(self, "HEADS_EARLY") == "1" and not isinstance(self, ConvNeXtBiFPNYOLOv0)
-            merged = plan_option(self, "HEADS_MERGED") == "1" and not isinstance(self, ConvNeXtBiFPNYOLOv0)
-
-            def heads_of_level(i, f, shapes):
-                """Everything that hangs off pyramid level i, in the order of what the post-process waits for: the prototype chain (the
-                longest, P3 only), Detect's branches (decode -> NMS), the mask coefficients, then Segment's own box / class branches
-                (they feed `segment_preds_cat` only: optionally gated behind Detect's map of the level, MTBT_SEG_GATE=1)."""
-                # the head branches are independent: no buffer recycling between them, so the lane scheduler sees no false dependencies
-                keep = lo.p.pool.reuse
-                lo.p.pool.reuse = keep and os.environ.get("MTBT_HEAD_REUSE", "0") == "1"
-                first = len(lo.p.launches)
-                if "mc" not in state:
-                    state["mc"], state["offs"], state["A"] = lo.mc_buffer(shapes, self.segment)
-                if i == 0:
-                    state["protos"] = lo.proto(f, self.segment)
-                heads = ([(self.detect, "detect")] if has_det else []) + [(self.segment, "segment")]
-                if merged and lo.heads_mergeable(i, heads, f):
-                    maps = [lo.head_map(f, h) for h, _ in heads]
-                    lo.heads_level_merged(i, f, heads, maps, state["mc"], state["offs"][i], state["A"])
-                    if has_det:
-                        det_maps[i] = maps[0]
-                    seg_maps[i] = maps[-1]
-                else:
-                    if has_det:
-                        det_maps[i] = lo.det_level(i, f, self.detect, "detect")
-                    lo.cv4_level(i, f, self.segment, state["mc"], state["offs"][i], state["A"])
-                    gate = [det_maps[i]] if (has_det and gate_mode >= 1) else None
-                    seg_maps[i] = lo.det_level(i, f, self.segment, "segment", gate)
-                if early:                         # lowered in the middle of the neck: branch work, off the neck's main chain
-                    for l in lo.p.launches[first:]:
-                        l.side = True
-                lo.p.pool.reuse = keep
-
-            S_ = x.shape[2]
-            shapes = [(x.shape[0], S_ // 8, x.shape[3] // 8), (x.shape[0], S_ // 16, x.shape[3] // 16), (x.shape[0], S_ // 32, x.shape[3] // 32)]
-            if isinstance(self, ConvNeXtBiFPNYOLOv0):
-                n3, n4, n5 = lo.neck_v0(*lo.features(self.backbone.body))
-            else:
-                c3, c4, c5 = lo.backbone()
-                # MTBT_HEADS_EARLY (default): the heads of a pyramid level are lowered -- and therefore issued / captured -- the moment the
-                # LAST BiFPN unit has produced that level.  P3 comes first (top-down node), and P3 carries most of the head work (the
-                # prototype chain, the 80x80 branches): it then runs beside the unit's P4 / P5 output nodes, small launches that leave most
-                # of the machine idle, instead of queueing behind them; and the chains the post-process waits for (prototypes, Detect)
-                # are first in line.  (Round 2 lowered all heads after the neck, Detect -> cv4 -> Proto -> Segment: in the replayed graph
-                # the prototype chain started up to 0.6 ms after its input existed and the mask assembly waited for it at the end.)
-                n3, n4, n5 = lo.neck(c3, c4, c5, on_level=(lambda i, f: heads_of_level(i, f, shapes)) if early else None)
-            feats = [n3, n4, n5]
-            if not early:
-                for i, f in enumerate(feats):
-                    heads_of_level(i, f, [(t.N, t.H, t.W) for t in feats])
-            mc, protos = state["mc"], state["protos"]
-            logits = lo.cls_head(n5)
-        c = _Compiled(lo.p, xs, det_maps, seg_maps, mc, protos, logits, sig)
-        # launches that write the maps the box decode reads: the post-process forks as soon as these are done
-        keys = {m.buf.untyped_storage().data_ptr() for m in (det_maps if det_maps is not None else seg_maps)}
-        c.det_marks = [i for i, l in enumerate(lo.p.launches) if any(w[0] in keys for w in l.writes)]
-        mkeys = {mc.untyped_storage().data_ptr(), protos.buf.untyped_storage().data_ptr()}
-        c.mask_marks = [i for i, l in enumerate(lo.p.launches) if any(w[0] in mkeys for w in l.writes)]
-        c.train_bns = lo.train_bns
-        cache[key] = c
+        if c is None or c.sig != sig:
+            c = cache[key] = _Lowering(self, x.shape, x.device, code_of(self.compute_dtype)).lower(sig)
         return c
 
     def _bind_input(self, c: "_Compiled", x: torch.Tensor):
@@ -986,11 +967,7 @@ class _Base(nn.Module):
         (overwritten by the next call) instead of the fresh copies `forward()` hands out -- what a graph replay wants.
         Returns (forward dict, detections dict)."""
         from . import postprocess as pp
-        det_flag, seg_flag = getattr(self, "detect", self.segment).training, self.segment.training
-        try:
-            if hasattr(self, "detect"):
-                self.detect.eval()
-            self.segment.eval()
+        with self._heads_mode(False):
             c = self.compile(x)
             self._bind_input(c, x)
             maps = c.det_maps if c.det_maps is not None else c.seg_maps
@@ -1019,10 +996,6 @@ class _Base(nn.Module):
             for t in [d["boxes"], d["best_score"], d["best_label"]] + [v for v in out.values() if isinstance(v, torch.Tensor)]:
                 t.record_stream(main)
             return fwd, out
-        finally:
-            if hasattr(self, "detect"):
-                self.detect.training = det_flag
-            self.segment.training = seg_flag
 
     def _run(self, x: torch.Tensor) -> "_Compiled":
         c = self.compile(x)
@@ -1044,111 +1017,67 @@ class _Base(nn.Module):
         from . import postprocess as pp
         return pp.detect_inference(maps, head, mc)
 
+    def _assemble(self, backbone, neck, width: int, nc_det: int, nc_img: int, proto_ch: int, detect: bool = True):
+        """The constructor body the variants share (submodule names and registration order of the reference)."""
+        L.load()  # fail loudly at construction if the HIP library is absent
+        self.backbone, self.neck = backbone, neck
+        ch = [width] * 3
+        if detect:
+            self.detect = Detect(nc=nc_det, ch=ch)
+        self.segment = Segment(nc=nc_det, nm=proto_ch, npr=width, ch=ch)
+        self.cls_pool = nn.AdaptiveAvgPool2d(1)
+        self.cls_fc = nn.Linear(width, nc_img)
+        self.nc_det, self.nc_img, self.proto_ch = nc_det, nc_img, proto_ch
+
+    def _infer_dict(self, c, own=True):
+        """The dict of forward(x, "infer") (main_model.py:378-386; without Detect, main_modelv2.py:371-378: its boxes are the Segment
+        head's).  own=False: views of plan buffers, valid until the next call."""
+        det, seg, mc, protos, logits = c.outputs(own)
+        out = {}
+        if det is not None:
+            out["detect_features"] = det
+            out["detect_preds_cat"] = self._preds_cat(c.det_maps, self.detect)
+        seg_cat = self._preds_cat(c.seg_maps, self.segment, c.mc)
+        if det is None:
+            out["detect_preds_cat"] = seg_cat[:, : 4 + self.nc_det]
+        out.update(segment_protos=(seg, mc, protos), segment_preds_cat=seg_cat, img_cls_logits=logits, img_cls_probs=logits.softmax(dim=1))
+        return out
+
+    def forward(self, x, mode: str = "train"):
+        """main_model.py:342-393 / main_modelv2.py:340-385: `(det,) (seg, mc, protos), logits` in "train" mode, the dict in "infer" mode."""
+        if mode not in ("train", "infer"):
+            raise ValueError(f"Unknown mode for ConvNeXtBiFPNYOLO.forward: {mode}. Expected 'train' or 'infer'.")
+        with self._heads_mode(mode == "train"):
+            if mode == "infer":
+                return self._infer_dict(self._run(x))
+            if self._wants_training_plan():
+                # model.train() and / or autograd recording: the training lowering (train.py) keeps what backward needs and
+                # returns tensors whose grad_fn runs the backward plan -- `total_loss.backward()` of running_main_v3.py:393-445
+                from .train import train_forward
+                det, seg, mc, protos, logits = train_forward(self, x)
+            else:
+                det, seg, mc, protos, logits = self._run(x).outputs()
+            return ((seg, mc, protos), logits) if det is None else (det, (seg, mc, protos), logits)
+
 
 class ConvNeXtBiFPNYOLO(_Base):
     """Canonical variant, `/root/reference/src/main_model.py:300-393`."""
 
-    def _infer_dict(self, c, own=True):  # main_model.py:378-386
-        cp = (lambda t: t.clone()) if own else (lambda t: t)   # own=False: views of plan buffers, valid until the next call
-        det_feats = [cp(m.nchw()) for m in c.det_maps]
-        seg_feats = [cp(m.nchw()) for m in c.seg_maps]
-        mc = cp(c.mc.permute(0, 2, 1))
-        logits = cp(c.logits)
-        return {
-            "detect_features": det_feats,
-            "detect_preds_cat": self._preds_cat(c.det_maps, self.detect),
-            "segment_protos": (seg_feats, mc, cp(c.protos.nchw())),
-            "segment_preds_cat": self._preds_cat(c.seg_maps, self.segment, c.mc),
-            "img_cls_logits": logits,
-            "img_cls_probs": logits.softmax(dim=1),
-        }
-
     def __init__(self, nc_det: int, nc_img: int, proto_ch: int = 32, bifpn_feature_size: int = 256,
                  bifpn_num_layers: int = 2, pretrained_backbone: bool = True):
         super().__init__()
-        L.load()  # fail loudly at construction if the HIP library is absent
-        self.backbone = ConvNeXtTiny(pretrained=pretrained_backbone)
-        self.neck = BiFPN(size=[256, 384, 512], feature_size=bifpn_feature_size, num_layers=bifpn_num_layers)
-        ch = [bifpn_feature_size] * 3
-        self.detect = Detect(nc=nc_det, ch=ch)
-        self.segment = Segment(nc=nc_det, nm=proto_ch, npr=bifpn_feature_size, ch=ch)
-        self.cls_pool = nn.AdaptiveAvgPool2d(1)
-        self.cls_fc = nn.Linear(bifpn_feature_size, nc_img)
-        self.nc_det, self.nc_img, self.proto_ch = nc_det, nc_img, proto_ch
-
-    def forward(self, x, mode: str = "train"):
-        det_flag, seg_flag = self.detect.training, self.segment.training
-        try:
-            if mode == "train":      # main_model.py:357-365
-                self.detect.train()
-                self.segment.train()
-                if self._wants_training_plan():
-                    # model.train() and / or autograd recording: the training lowering (train.py) keeps what backward needs and
-                    # returns tensors whose grad_fn runs the backward plan -- `total_loss.backward()` of running_main_v3.py:393-445
-                    from .train import train_forward
-                    det, seg, mc, protos, logits = train_forward(self, x)
-                    return det, (seg, mc, protos), logits
-                c = self._run(x)
-                det = [m.nchw().clone() for m in c.det_maps]
-                seg = [m.nchw().clone() for m in c.seg_maps]
-                return det, (seg, c.mc.permute(0, 2, 1).clone(), c.protos.nchw().clone()), c.logits.clone()
-            if mode == "infer":      # main_model.py:367-386
-                self.detect.eval()
-                self.segment.eval()
-                return self._infer_dict(self._run(x))
-            raise ValueError(f"Unknown mode for ConvNeXtBiFPNYOLO.forward: {mode}. Expected 'train' or 'infer'.")
-        finally:  # top-level flags only, as the reference does (main_model.py:391-393, SURVEY F14)
-            self.detect.training = det_flag
-            self.segment.training = seg_flag
+        self._assemble(ConvNeXtTiny(pretrained=pretrained_backbone), BiFPN(size=[256, 384, 512], feature_size=bifpn_feature_size, num_layers=bifpn_num_layers),
+                       bifpn_feature_size, nc_det, nc_img, proto_ch)
 
 
 class ConvNeXtBiFPNYOLOv2(_Base):
     """Segment-only variant, `/root/reference/src/main_modelv2.py:300-385`."""
 
-    def _infer_dict(self, c, own=True):  # main_modelv2.py:371-378
-        cp = (lambda t: t.clone()) if own else (lambda t: t)
-        seg_feats = [cp(m.nchw()) for m in c.seg_maps]
-        mc = cp(c.mc.permute(0, 2, 1))
-        seg_cat = self._preds_cat(c.seg_maps, self.segment, c.mc)
-        logits = cp(c.logits)
-        return {
-            "detect_preds_cat": seg_cat[:, : 4 + self.nc_det],
-            "segment_protos": (seg_feats, mc, cp(c.protos.nchw())),
-            "segment_preds_cat": seg_cat,
-            "img_cls_logits": logits,
-            "img_cls_probs": logits.softmax(dim=1),
-        }
-
     def __init__(self, nc_det: int, nc_img: int, proto_ch: int = 32, bifpn_feature_size: int = 256,
                  bifpn_num_layers: int = 2, pretrained_backbone: bool = True):
         super().__init__()
-        L.load()
-        self.backbone = ConvNeXtTiny(pretrained=pretrained_backbone)
-        self.neck = BiFPN(size=[256, 384, 512], feature_size=bifpn_feature_size, num_layers=bifpn_num_layers)
-        ch = [bifpn_feature_size] * 3
-        self.segment = Segment(nc=nc_det, nm=proto_ch, npr=bifpn_feature_size, ch=ch)
-        self.cls_pool = nn.AdaptiveAvgPool2d(1)
-        self.cls_fc = nn.Linear(bifpn_feature_size, nc_img)
-        self.nc_det, self.nc_img, self.proto_ch = nc_det, nc_img, proto_ch
-
-    def forward(self, x, mode: str = "train"):
-        seg_flag = self.segment.training
-        try:
-            if mode == "train":      # main_modelv2.py:353-360
-                self.segment.train()
-                if self._wants_training_plan():
-                    from .train import train_forward
-                    _, seg, mc, protos, logits = train_forward(self, x)
-                    return (seg, mc, protos), logits
-                c = self._run(x)
-                seg = [m.nchw().clone() for m in c.seg_maps]
-                return (seg, c.mc.permute(0, 2, 1).clone(), c.protos.nchw().clone()), c.logits.clone()
-            if mode == "infer":      # main_modelv2.py:362-378
-                self.segment.eval()
-                return self._infer_dict(self._run(x))
-            raise ValueError(f"Unknown mode for ConvNeXtBiFPNYOLO.forward: {mode}. Expected 'train' or 'infer'.")
-        finally:
-            self.segment.training = seg_flag
+        self._assemble(ConvNeXtTiny(pretrained=pretrained_backbone), BiFPN(size=[256, 384, 512], feature_size=bifpn_feature_size, num_layers=bifpn_num_layers),
+                       bifpn_feature_size, nc_det, nc_img, proto_ch, detect=False)
 
 
 class _WeightedAdd(_Params):
@@ -1191,15 +1120,8 @@ class ConvNeXtBiFPNYOLOv0(_Base):
 
     def __init__(self, nc_det: int, nc_img: int, proto_ch: int = 32):
         super().__init__()
-        L.load()
-        self.backbone = _BackboneV0()
-        self.neck = _BiFPNV0(self.backbone.out_channels, repeats=2)
-        ch = (256, 256, 256)
-        self.detect = Detect(nc_det, ch=ch)
-        self.segment = Segment(nc_det, nm=proto_ch, ch=ch)
-        self.cls_pool = nn.AdaptiveAvgPool2d(1)
-        self.cls_fc = nn.Linear(256, nc_img)
-        self.nc_det, self.nc_img, self.proto_ch = nc_det, nc_img, proto_ch
+        backbone = _BackboneV0()
+        self._assemble(backbone, _BiFPNV0(backbone.out_channels, repeats=2), 256, nc_det, nc_img, proto_ch)
 
     def forward(self, x, mode: str = "infer"):
         if self.detect.training != self.segment.training:
@@ -1214,12 +1136,9 @@ class ConvNeXtBiFPNYOLOv0(_Base):
         if any(m.training for m in self.modules() if isinstance(m, nn.BatchNorm2d)):
             raise NotImplementedError("the src/model.py variant: eval-mode heads over train-mode BatchNorm layers are not lowered")
         c = self._run(x)
-        det_feats = [m.nchw().clone() for m in c.det_maps]
-        seg_feats = [m.nchw().clone() for m in c.seg_maps]
-        mc = c.mc.permute(0, 2, 1).clone()
+        det_feats, seg_feats, mc, protos, logits = c.outputs()
         det_out = (self._preds_cat(c.det_maps, self.detect), det_feats)
-        seg_out = (self._preds_cat(c.seg_maps, self.segment, c.mc), (seg_feats, mc, c.protos.nchw().clone()))
-        logits = c.logits.clone()
+        seg_out = (self._preds_cat(c.seg_maps, self.segment, c.mc), (seg_feats, mc, protos))
         if mode == "infer":
             return {"detect": det_out, "segment": (seg_out[0], seg_out[1]), "img_cls": logits.softmax(1)}
         return det_out, seg_out, logits

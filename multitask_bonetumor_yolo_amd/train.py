@@ -27,7 +27,7 @@ import torch.nn as nn
 from . import _lib as L
 from . import model as M
 from .dist_train import FlatBuckets
-from .engine import Act, ESIZE, Launch, Plan, TORCH_DTYPE, _region
+from .engine import Act, ESIZE, Launch, Plan, TORCH_DTYPE, _region, code_of
 
 # column sums from the conv epilogue (BatchNorm batch statistics, d fc1.bias) instead of separate passes; MTBT_FUSED_COLSUM=0 turns them off (A/B)
 FUSED_BN_STATS = os.environ.get("MTBT_FUSED_COLSUM", "1") != "0"
@@ -120,12 +120,10 @@ class TPlan(Plan):
               colsum_shift: Optional[torch.Tensor] = None, **kw):
         """`colsum` [K] / [2K] fp32: per-channel sums (and sums of squares) of the stored output minus `colsum_shift`, from the conv epilogue."""
         a = self.conv(x, w, y, **kw)
-        l = self.launches[-1]
         if y2 is not None:
             assert y2.ld == y.ld and y2.bs == y.bs and y2.code == y.code
             a.y2 = y2.ptr
-            l.keep = l.keep + (y2.buf,)
-            l.writes = l.writes + (_region(y2),)
+            self.amend(keep=(y2.buf,), writes=[y2])
         if colsum is not None:
             K = w.shape[0]
             partial_only = colsum is True      # the consumer reduces the partial rows itself (BatchNorm): see colsum_partials()
@@ -145,10 +143,9 @@ class TPlan(Plan):
                 a.colsum_ws = self._ws(nbytes)
                 self.cs_partial = self.cur_ws
             a.colsum_ws_bytes = nbytes
-            l.keep = l.keep + (colsum if not partial_only else None, colsum_shift, self.cs_partial)
-            l.writes = l.writes + ((_region(colsum),) if not partial_only else ()) + (_region(self.cs_partial),)
-            if colsum_shift is not None:
-                l.reads = l.reads + (_region(colsum_shift),)
+            self.amend(keep=(colsum if not partial_only else None, colsum_shift, self.cs_partial),
+                       reads=[colsum_shift] if colsum_shift is not None else [],
+                       writes=([colsum] if not partial_only else []) + [self.cs_partial])
         return a
 
     @staticmethod
@@ -430,9 +427,8 @@ class TrainPlan:
         self.prep_table = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
         self.prep_starts = torch.tensor(starts, dtype=torch.int32).to(self.device)
         keep = (self.prep_table, self.prep_starts, tuple(d["src"] for d in self.prep), tuple(d["dst"] for d in self.prep))
-        launch = Launch(self.lib.mtbt_weight_prep, (self.prep_table.data_ptr(), self.prep_starts.data_ptr(), n, total), "weight_prep", keep)
-        launch.writes = tuple(_region(d["dst"]) for d in self.prep)
-        self.fwd.launches.insert(0, launch)
+        self.fwd.launches.insert(0, Launch(self.lib.mtbt_weight_prep, (self.prep_table.data_ptr(), self.prep_starts.data_ptr(), n, total), "weight_prep", keep,
+                                           writes=tuple(_region(d["dst"]) for d in self.prep)))
 
     # ------------------------------------------------------------------------------------------------------------------
     # small helpers
@@ -515,6 +511,23 @@ class TrainPlan:
         acc = self.acc(x)
         self.bwd.conv2(d_raw, wd, gx, R=R, S=R, stride=1, pad=R - 1 - pad, res=gx if acc else None, name=name + ".dgrad", **kw)
 
+    def _conv_bn(self, x: Act, wf, raw: Act, y: Act, bn, act, name: str, **conv_kw) -> torch.Tensor:
+        """conv into `raw` -> BatchNorm -> activation into `y`; returns the (mean, var) slot the backward reads."""
+        K = wf.shape[0]
+        running = not bn.training
+        # batch statistics: the conv's own epilogue accumulates sum / sum of squares of what it stores (about the running mean)
+        sums = None
+        if not running and self.fwd.colsum_ok(K) and FUSED_BN_STATS:
+            self.fwd.conv2(x, wf, raw, name=name, colsum=True, colsum_sq=True, colsum_shift=bn.running_mean, **conv_kw)
+            sums = self.fwd.cs_layout
+        else:
+            self.fwd.conv(x, wf, raw, name=name, **conv_kw)
+        st = self.stats(K)
+        if not running:
+            self.train_bns.append(bn)
+        self.fwd.bn_forward(raw, y, bn, act, st, running, name + ".bn", sums=sums)
+        return st
+
     def conv_bn_act(self, x: Act, mod, y: Optional[Act], act, name: str) -> Act:
         """ConvBlock (main_model.py:113-141, conv bias) / ultralytics Conv (no bias): conv -> BatchNorm -> activation."""
         conv, bn = mod.conv, mod.bn
@@ -523,19 +536,9 @@ class TrainPlan:
         raw = self.new(x.N, x.H, x.W, K)
         bias = _dense_vec(conv.bias, name + ".bias") if conv.bias is not None else None
         running = not bn.training
-        # batch statistics: the conv's own epilogue accumulates sum / sum of squares of what it stores (about the running mean)
-        sums = None
-        if not running and self.fwd.colsum_ok(K) and FUSED_BN_STATS:
-            self.fwd.conv2(x, wf, raw, R=k, S=k, stride=1, pad=k // 2, shift=bias, name=name, colsum=True, colsum_sq=True, colsum_shift=bn.running_mean)
-            sums = self.fwd.cs_layout
-        else:
-            self.fwd.conv(x, wf, raw, R=k, S=k, stride=1, pad=k // 2, shift=bias, name=name)
         if y is None:
             y = self.new(x.N, x.H, x.W, K)
-        st = self.stats(K)
-        if not running:
-            self.train_bns.append(bn)
-        self.fwd.bn_forward(raw, y, bn, act, st, running, name + ".bn", sums=sums)
+        st = self._conv_bn(x, wf, raw, y, bn, act, name, R=k, S=k, stride=1, pad=k // 2, shift=bias)
 
         def bwd():
             if not self.has_grad(y):
@@ -627,16 +630,7 @@ class TrainPlan:
         bn = mod.bn
         raw, y = self.new(x.N, x.H, x.W, K), self.new(x.N, x.H, x.W, K)
         running = not bn.training
-        sums = None
-        if not running and self.fwd.colsum_ok(K) and FUSED_BN_STATS:
-            self.fwd.conv2(x, wf, raw, name=name, colsum=True, colsum_sq=True, colsum_shift=bn.running_mean)
-            sums = self.fwd.cs_layout
-        else:
-            self.fwd.conv(x, wf, raw, name=name)
-        st = self.stats(K)
-        if not running:
-            self.train_bns.append(bn)
-        self.fwd.bn_forward(raw, y, bn, L.ACT_ELU, st, running, name + ".bn", sums=sums)
+        st = self._conv_bn(x, wf, raw, y, bn, L.ACT_ELU, name)
         gtmp = torch.empty(K, Cc, dtype=torch.float32, device=self.device)
 
         def bwd():
@@ -831,10 +825,7 @@ class TrainPlan:
 
             def node(inputs, wn, dwn, col, n, modes, like, conv, cf, tag, nm=nm):
                 s = self.new(like.N, like.H, like.W, like.C)
-                a = self.fwd.fuse(inputs, [0.0] * len(inputs), modes, s, name=f"{nm}.{tag}.fuse")
-                a.wgt_dev = wn.data_ptr() + 4 * col * n
-                self.fwd.launches[-1].keep += (wn,)
-                self.fwd.launches[-1].reads += (_region(wn),)
+                self.fwd.fuse(inputs, [0.0] * len(inputs), modes, s, name=f"{nm}.{tag}.fuse", wgt_dev=wn, wgt_first=col * n)
 
                 def bwd():
                     if not self.has_grad(s):
@@ -880,10 +871,7 @@ class TrainPlan:
                 self.fwd.raw(self.lib.mtbt_wadd_norm_weights, (w.data_ptr(), n, C.c_float(add.eps), wn.data_ptr()), f"{nm}.add_{key}.norm", keep=(w, wn),
                              reads=[w], writes=[wn])
                 s_ = self.new(like.N, like.H, like.W, like.C)
-                a = self.fwd.fuse(inputs, [0.0] * n, modes, s_, bug=True, name=f"{nm}.add_{key}")
-                a.wgt_dev = wn.data_ptr()
-                self.fwd.launches[-1].keep += (wn,)
-                self.fwd.launches[-1].reads += (_region(wn),)
+                self.fwd.fuse(inputs, [0.0] * n, modes, s_, bug=True, name=f"{nm}.add_{key}", wgt_dev=wn)
 
                 def bwd():
                     if not self.has_grad(s_):
@@ -1119,10 +1107,6 @@ class TrainPlan:
         return plan
 
 
-def _bn_mode_sig(model) -> Tuple[bool, ...]:
-    return tuple(m.training for m in model.modules() if isinstance(m, nn.BatchNorm2d))
-
-
 class _TrainFn(torch.autograd.Function):
     """`forward(x, "train")` as ONE autograd node: the reference's `total_loss.backward()` (running_main_v3.py:445 via Lightning) lands here
     with the gradients of the head outputs and leaves with one gradient per parameter."""
@@ -1175,15 +1159,11 @@ class _TrainFn(torch.autograd.Function):
 
 def train_forward(model, x: torch.Tensor):
     """`forward(x, "train")` with autograd history: returns (det maps | None, seg maps, mc, protos, logits) as fresh tensors."""
-    from .engine import code_of
-    if not x.is_cuda:
-        raise RuntimeError("ConvNeXtBiFPNYOLO (HIP) needs CUDA/HIP tensors on an MI355X; there is no CPU path")
-    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
-        raise ValueError(f"expected [B,3,S,S] with S a multiple of 32, got {tuple(x.shape)}")
+    model.check_input(x)
     if model.compute_dtype == torch.float16:
         raise NotImplementedError("float16 is an inference arithmetic mode (BASELINE configs[4]); train in bfloat16 or float32")
     cache = model.__dict__.setdefault("_train_plans", {})
-    key = (tuple(x.shape), model.compute_dtype, x.device.index, _bn_mode_sig(model))
+    key = (tuple(x.shape), model.compute_dtype, x.device.index, model._bn_modes())
     tp = cache.get(key)
     if tp is None:
         tp = cache[key] = TrainPlan(model, x.shape, x.device, code_of(model.compute_dtype))

@@ -1,6 +1,7 @@
 """CPU checks of the drop-in boundary: the C-ABI library builds for gfx950, loads without a GPU, exports
 every symbol include/mtbt_hip.h declares, and its entry points reject bad arguments before any launch."""
 import ctypes as C
+import itertools
 import os
 import re
 
@@ -86,6 +87,23 @@ def test_entry_points_reject_bad_arguments_without_launching(lib):
     a.x = a.w = a.y = 16  # non-null dummies: shape validation must fire first
     a.N, a.H, a.W, a.C, a.K, a.R, a.S, a.stride, a.pad, a.Ho, a.Wo, a.dtype, a.out_dtype = 1, 8, 8, 40, 8, 1, 1, 1, 0, 8, 8, L.BF16, L.BF16
     assert lib.mtbt_conv2d_nhwc(C.byref(a), None) == -1  # C % 32 != 0 for bf16
+    # mtbt_bifpn_node_nhwc takes the two node shapes of BiFPNUnit.forward -- (identity, bilinear x2), (identity, identity, 2x2 mean) -- and
+    # refuses every other mode combination as the header says, before it looks at a pointer
+    n = L.NodeArgs()
+    n.w = n.shift = n.y = 16
+    n.fuse.N, n.fuse.H, n.fuse.W, n.fuse.C, n.fuse.dtype, n.K, n.y_pixel_stride, n.act = 1, 8, 8, 128, L.BF16, 128, 128, L.ACT_ELU
+    shapes = ([L.RES_ID, L.RES_UP_BILINEAR], [L.RES_ID, L.RES_ID, L.RES_DOWN_MEAN])
+    for n_in in (0, 1, 2, 3, 4):
+        for modes in itertools.product(range(-1, 6), repeat=min(max(n_in, 1), 3)):
+            if list(modes) in shapes and n_in == len(modes):
+                continue
+            n.fuse.n_in = n_in
+            for i in range(3):
+                n.fuse.x[i], n.fuse.resample[i] = 16, (modes[i] if i < len(modes) else 0)
+            assert lib.mtbt_bifpn_node_nhwc(C.byref(n), None) == -1, (n_in, modes)
+    n.fuse.n_in, n.fuse.H = 2, 7                       # a valid shape on an odd map: no bilinear x2
+    n.fuse.resample[0], n.fuse.resample[1] = L.RES_ID, L.RES_UP_BILINEAR
+    assert lib.mtbt_bifpn_node_nhwc(C.byref(n), None) == -1
 
 
 def test_missing_library_is_loud(monkeypatch):
