@@ -300,6 +300,57 @@ typedef struct mtbt_mask_args {
 int mtbt_mask_assemble(const mtbt_mask_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Instance masks and boxes in the ORIGINAL image frame, masks one bit per pixel: the inverse of the top-left letterbox
+ * (dataset_btxrdv2.py:109-134) applied to the post-process results, one launch for up to 32 images of different sizes.
+ * A frame is (height H0, width W0, scale = S / max(H0, W0) as the letterbox returned it); `step` = (float)((double)scale / up)
+ * is the number of prototype pixels per frame pixel (up = S / wp letterboxed pixels per prototype pixel, 4 for the models).
+ * SUPPORTED RANGE 0 < step <= 1: the image's long side is at least the prototype grid's (>= 160 px at S = 640); anything
+ * else returns MTBT_EINVAL.
+ *   boxes_frame[n,k] = clamp(boxes[n,k] / scale_n, 0, (W0, H0, W0, H0))   true fp32 division; rows k >= counts[n] are zeros
+ *   low[n,k,y,x]     = sum_c coeff[n,k,c] * protos[n,y,x,c]
+ *   logit(n,k,Y,X)   = bilinear tap of low at the ORIGINAL pixel (torch's align_corners=False rule, all fp32, no S x S plane):
+ *                      sx = max((X + 0.5f) * step - 0.5f, 0); x0 = min((int)sx, wp-1); x1 = min(x0+1, wp-1); lx = clamp(sx - x0, 0, 1);
+ *                      the same for y with hp; v = (1-ly)*((1-lx)*low[y0,x0] + lx*low[y0,x1]) + ly*((1-lx)*low[y1,x0] + lx*low[y1,x1])
+ *   bit(n,k,Y,X)     = v > 0, and with `crop` additionally x1f <= X < x2f && y1f <= Y < y2f of boxes_frame[n,k] (ultralytics crop_mask)
+ * Packed layout: plane k of image n is H0 rows of pitch = 8 * ceil(W0 / 64) bytes at out + offset_n + k * H0 * pitch; pixel X is
+ * bit X & 7 of byte X >> 3 (numpy.packbits(bitorder="little")); padding bits X >= W0 are 0; planes k >= counts[n] are zero.
+ * EVERY byte of every plane is written by the launch (the buffer may be uninitialised); image n occupies K * H0 * pitch bytes,
+ * e.g. 113 MB for a 3000 x 3000 image at K = 100 -- lower top_k for large images.
+ * protos / coeff / gather_idx / counts as in mtbt_mask_args (nm must be 32); boxes [N,K,4] xyxy in letterboxed pixels (may be NULL
+ * when neither crop nor boxes_frame is wanted); boxes_frame [N,K,4] or NULL.  The frame descriptors are read on the host and
+ * travel in the kernel arguments: no copy, no synchronisation.
+ * MTBT_EINVAL before any launch: NULL a / frames / protos / coeff / out, n_frames outside 1..32 or != N, step outside (0, 1],
+ * pitch != 8 * ceil(width / 64), offset not a multiple of 16, a plane range past out_bytes, nm != 32, crop or boxes_frame without
+ * boxes.  MTBT_EALIGN for protos / out not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mtbt_frame {
+  int32_t height, width; /* H0, W0 of the original image */
+  float step;            /* prototype pixels per frame pixel: (float)((double)scale / up) */
+  float scale;           /* the letterbox scale S / max(H0, W0): divides the boxes */
+  int32_t pitch;         /* bytes per packed row: 8 * ceil(width / 64) */
+  int32_t reserved;
+  int64_t offset;        /* byte offset of this image's K planes in `out`, a multiple of 16 */
+} mtbt_frame;
+
+typedef struct mtbt_frame_mask_args {
+  const float* protos;
+  const float* coeff;
+  int64_t coeff_batch_stride, coeff_k_stride, coeff_c_stride;
+  const int32_t* gather_idx; /* [N,K] or NULL */
+  const int32_t* counts;     /* [N] or NULL */
+  const float* boxes;        /* [N,K,4] letterboxed xyxy, or NULL */
+  float* boxes_frame;        /* [N,K,4] or NULL */
+  uint8_t* out;              /* packed planes of all images */
+  int64_t out_bytes;
+  int32_t N, K, nm, hp, wp;
+  int32_t crop;
+} mtbt_frame_mask_args;
+
+int mtbt_masks_to_frames(const mtbt_frame_mask_args* a, const mtbt_frame* frames, int n_frames, void* stream);
+/* sizeof() of the two structs above as the library was compiled: which = 0 mtbt_frame, 1 mtbt_frame_mask_args; -1 otherwise */
+int mtbt_sizeof_frame_args(int which);
+
+/* ---------------------------------------------------------------------------------------------
  * Multitask loss VALUE (forward only), MultiTaskLitModel._multitask_loss, running_main_v3.py:232-387:
  *   per (image, anchor): trainer decode (:268-290), IoU against the image's GT boxes (:316), positives = max IoU >
  *   iou_thresh (:319-321), sum(1 - IoU) (:331), BCE-with-logits(sum) of the class logits against one-hot /

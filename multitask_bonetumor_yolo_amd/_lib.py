@@ -103,6 +103,19 @@ class RawImage(C.Structure):  # mtbt_raw_image
                 ("row_stride", C.c_int64), ("mask_row_stride", C.c_int64)]
 
 
+class Frame(C.Structure):  # mtbt_frame
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("step", C.c_float), ("scale", C.c_float), ("pitch", C.c_int32),
+                ("reserved", C.c_int32), ("offset", C.c_int64)]
+
+
+class FrameMaskArgs(C.Structure):  # mtbt_frame_mask_args
+    _fields_ = [("protos", C.c_void_p), ("coeff", C.c_void_p),
+                ("coeff_batch_stride", C.c_int64), ("coeff_k_stride", C.c_int64), ("coeff_c_stride", C.c_int64),
+                ("gather_idx", C.c_void_p), ("counts", C.c_void_p), ("boxes", C.c_void_p), ("boxes_frame", C.c_void_p),
+                ("out", C.c_void_p), ("out_bytes", C.c_int64),
+                ("N", C.c_int32), ("K", C.c_int32), ("nm", C.c_int32), ("hp", C.c_int32), ("wp", C.c_int32), ("crop", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -200,9 +213,12 @@ SYMBOLS = {
     "mtbt_box_eval": (C.c_int, [C.POINTER(BoxEvalArgs), C.c_void_p]),
     "mtbt_det_confusion": (C.c_int, [C.POINTER(LossArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtbt_cls_confusion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtbt_masks_to_frames": (C.c_int, [C.POINTER(FrameMaskArgs), C.POINTER(Frame), C.c_int, C.c_void_p]),
+    "mtbt_sizeof_frame_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
+FRAME_STRUCTS = (Frame, FrameMaskArgs)   # order of mtbt_sizeof_frame_args(which)
 _lib = None
 
 
@@ -224,6 +240,10 @@ def load():
             if lib.mtbt_sizeof_args(which) != C.sizeof(st):
                 raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {lib.mtbt_sizeof_args(which)}, this binding lays it out in "
                                    f"{C.sizeof(st)} bytes: stale library, rebuild")
+        for which, st in enumerate(FRAME_STRUCTS):
+            if lib.mtbt_sizeof_frame_args(which) != C.sizeof(st):
+                raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {lib.mtbt_sizeof_frame_args(which)}, this binding lays it "
+                                   f"out in {C.sizeof(st)} bytes: stale library, rebuild")
         _lib = lib
     return _lib
 

@@ -182,13 +182,115 @@ def proto_projector_logits(protos: torch.Tensor, weight: torch.Tensor, bias: tor
     return logits.add_(bias.detach().reshape(1, 1, 1, 1).to(logits.dtype))      # device-side add: no host synchronisation (bilinear weights sum to 1)
 
 
+MAX_FRAMES = 32   # images per mtbt_masks_to_frames launch (the frame descriptors travel as kernel arguments)
+
+
+def frames_of(images: Sequence[torch.Tensor], scales: Sequence[float]):
+    """The frames of the raw images `letterbox_batch` was given: [(H0, W0, scale)] with the scales it returned."""
+    return [(int(im.shape[0]), int(im.shape[1]), float(s)) for im, s in zip(images, scales)]
+
+
+def _frame_layout(frames, K: int, up: float):
+    """Per image (H0, W0, step, scale, pitch, offset) and the byte size of the packed buffer."""
+    rows, total = [], 0
+    for H0, W0, scale in frames:
+        H0, W0, scale = int(H0), int(W0), float(scale)
+        step = C.c_float(scale / up).value if scale > 0 else 0.0
+        if H0 < 1 or W0 < 1 or not 0.0 < step <= 1.0:
+            raise ValueError(f"masks_to_frames: frame ({H0}, {W0}, scale {scale}) gives {step} prototype pixels per image pixel; the supported "
+                             "range is 0 < scale / up <= 1, i.e. the image's long side is at least the prototype grid's (>= 160 px at S = 640)")
+        pitch = 8 * ((W0 + 63) // 64)
+        rows.append((H0, W0, step, C.c_float(scale).value, pitch, total))
+        total = (total + K * H0 * pitch + 15) // 16 * 16
+    return rows, total
+
+
+def masks_to_frames(protos: torch.Tensor, mc: torch.Tensor, keep_anchor: torch.Tensor, counts: Optional[torch.Tensor],
+                    boxes: Optional[torch.Tensor], frames, up: Optional[float] = None, crop: bool = False, out: Optional[torch.Tensor] = None):
+    """Kept boxes and their instance masks in the coordinates of the ORIGINAL images, masks one bit per pixel.
+
+    `frames`: one (H0, W0, scale) per image, scale = S / max(H0, W0) as `letterbox_batch` returns it (see `frames_of`); images keep
+    their own sizes.  `up` = letterboxed pixels per prototype pixel (S / wp; 4 when not given).  Supported range: 0 < scale / up <= 1
+    (the image's long side is at least the prototype grid's, e.g. >= 160 px at S = 640); anything else raises ValueError.
+    protos / mc / keep_anchor / counts as in `assemble_masks`; boxes [B,K,4] letterboxed xyxy (the NMS output).
+
+      boxes[b,k]  = clamp(boxes[b,k] / float32(scale_b), 0, (W0, H0, W0, H0)); rows k >= counts[b] are zeros
+      mask bit    = bilinear tap of the prototype-resolution logits at the original pixel (align_corners=False, one step, no S x S
+                    plane) > 0; with `crop` also x1 <= X < x2 and y1 <= Y < y2 of the frame box (ultralytics crop_mask)
+
+    Returns {"boxes": [B,K,4], "masks": list of uint8 [K, H0_b, pitch_b] views, "buffer": the flat uint8 buffer they view}.
+    pitch_b = 8 * ceil(W0_b / 64) bytes; pixel X is bit X & 7 of byte X >> 3 (numpy.packbits(bitorder="little")); padding bits and
+    planes k >= counts[b] are zero; every byte is written by the kernel.  Image b takes K * H0_b * pitch_b bytes (16-byte aligned
+    starts): a 3000 x 3000 image at K = 100 is 113 MB, so lower `top_k` for large images.  `out=` takes a caller's flat uint8 buffer
+    of at least that total.  `unpack_masks` gives bool planes."""
+    lib = L.load()
+    _need_cuda(protos, "masks_to_frames")
+    assert mc.dtype == torch.float32
+    pr, ld = _nhwc_rows(protos)
+    B, nm, hp, wp = protos.shape
+    if ld != nm:
+        pr = pr.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    dev = protos.device
+    keep_anchor = keep_anchor.contiguous().to(torch.int32)
+    K = keep_anchor.shape[1]
+    if len(frames) != B:
+        raise ValueError(f"masks_to_frames: {len(frames)} frames for a batch of {B}")
+    if crop and boxes is None:
+        raise ValueError("masks_to_frames: crop=True needs the boxes")
+    rows, total = _frame_layout(frames, K, 4.0 if up is None else float(up))
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total or out.device != dev:
+        raise ValueError(f"masks_to_frames: out must be a contiguous flat uint8 buffer of at least {total} bytes on {dev}")
+    if counts is not None:
+        counts = counts.contiguous().to(torch.int32)
+    boxes_frame = None
+    if boxes is not None:
+        boxes = boxes.contiguous().float()
+        boxes_frame = torch.empty((B, K, 4), dtype=torch.float32, device=dev)
+    for c0 in range(0, B, MAX_FRAMES):
+        nb = min(MAX_FRAMES, B - c0)
+        a = L.FrameMaskArgs()
+        a.protos, a.coeff = pr[c0:].data_ptr(), mc[c0:].data_ptr()
+        a.coeff_batch_stride, a.coeff_k_stride, a.coeff_c_stride = mc.stride(0), mc.stride(2), mc.stride(1)
+        a.gather_idx = keep_anchor[c0:].data_ptr()
+        a.counts = counts[c0:].data_ptr() if counts is not None else None
+        a.boxes = boxes[c0:].data_ptr() if boxes is not None else None
+        a.boxes_frame = boxes_frame[c0:].data_ptr() if boxes_frame is not None else None
+        a.out, a.out_bytes = out.data_ptr(), out.numel()
+        a.N, a.K, a.nm, a.hp, a.wp, a.crop = nb, K, nm, hp, wp, int(bool(crop))
+        fr = (L.Frame * nb)()
+        for i, (H0, W0, step, scale, pitch, off) in enumerate(rows[c0:c0 + nb]):
+            fr[i].height, fr[i].width, fr[i].step, fr[i].scale, fr[i].pitch, fr[i].offset = H0, W0, step, scale, pitch, off
+        rc = lib.mtbt_masks_to_frames(C.byref(a), fr, nb, _stream(dev))
+        if rc == -1 and nm != 32:
+            raise ValueError(f"masks_to_frames: {nm} prototype channels; the kernel supports 32")
+        L.check(rc, "mtbt_masks_to_frames")
+    views = [out[off:off + K * H0 * pitch].view(K, H0, pitch) for H0, W0, step, scale, pitch, off in rows]
+    return {"boxes": boxes_frame, "masks": views, "buffer": out}
+
+
+def unpack_masks(packed: torch.Tensor, W0: int) -> torch.Tensor:
+    """uint8 [K, H0, pitch] bit planes of `masks_to_frames` -> bool [K, H0, W0], on the tensor's device."""
+    shifts = torch.arange(8, dtype=torch.uint8, device=packed.device)
+    bits = (packed.unsqueeze(-1) >> shifts) & 1
+    return bits.reshape(packed.shape[0], packed.shape[1], packed.shape[2] * 8)[:, :, :W0].bool()
+
+
 def detect_and_segment(det_maps: List[torch.Tensor], mc: torch.Tensor, protos: torch.Tensor, img_size: int,
-                       conf_th: float = CONF_TH, iou_th: float = NMS_IOU, top_k: int = TOP_K, masks: bool = True):
-    """The whole validation post-process for a batch: decode -> filter/NMS/top-k -> instance masks."""
+                       conf_th: float = CONF_TH, iou_th: float = NMS_IOU, top_k: int = TOP_K, masks: bool = True,
+                       frames=None, crop: bool = False):
+    """The whole validation post-process for a batch: decode -> filter/NMS/top-k -> instance masks.
+    With `frames` ([(H0, W0, scale)] per image, see `frames_of`) the results come in the original images' coordinates instead of
+    the dense letterboxed masks: `boxes_frame` [B,K,4] and `masks_frame` (bit-packed uint8 [K, H0_b, pitch_b] per image, cropped to
+    the boxes with `crop`), as `masks_to_frames` documents them."""
     d = decode_boxes(det_maps, img_size, want_scores=False)
     k = nms_batched(d["boxes"], d["best_score"], d["best_label"], float(img_size), conf_th, iou_th, top_k)
     out = {"boxes": k["boxes"], "scores": k["scores"], "labels": k["labels"], "counts": k["counts"],
            "keep_idx": k["keep_idx"], "keep_anchor": k["keep_anchor"], "n_cand": k["n_cand"]}
-    if masks:
+    if frames is not None:
+        r = masks_to_frames(protos, mc, k["keep_anchor"], k["counts"], k["boxes"], frames, up=img_size / protos.shape[3], crop=crop)
+        out["boxes_frame"], out["masks_frame"] = r["boxes"], r["masks"]
+    elif masks:
         out["masks"], _ = assemble_masks(protos, mc, k["keep_anchor"], k["counts"], (img_size, img_size))
     return out
