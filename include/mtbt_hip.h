@@ -522,6 +522,108 @@ typedef struct mtbt_box_eval_args {
 } mtbt_box_eval_args;
 int mtbt_box_eval(const mtbt_box_eval_args* args, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Instance-mask COCO evaluation from bit-packed planes (csrc/mask_eval.hip): three entry points that turn packed detection and
+ * ground-truth masks into the per-detection records mtbt_box_eval writes for boxes.  Every count is an exact integer and every
+ * IoU a quotient of exact integers in fp64: results are bit-reproducible against numpy.
+ * Packed layout (the one mtbt_masks_to_frames writes): a plane is H rows of pitch = 8 * ceil(W / 64) bytes, pixel X is bit X & 7
+ * of byte X >> 3, padding bits X >= W are zero (inputs may rely on that).  Planes are 8-byte aligned, NOT more: with H odd and
+ * pitch = 8 mod 16 every second plane sits on an odd 8-byte boundary, so the kernels use 8-byte accesses only.
+ * All three are asynchronous on `stream`, deterministic, free of global atomics (the matching walk
+ * sets its match bit sets with LDS atomicOr, as mtbt_box_eval does) and need no workspace.
+ * ------------------------------------------------------------------------------------------- */
+
+/* mtbt_pack_masks: dense planes -> packed planes.
+ *   src       [n_src] planes of H rows; element (s, Y, X) at src + s * plane_stride + Y * row_stride + X (strides in ELEMENTS);
+ *             dtype 0 = uint8 (bool storage), 1 = float32
+ *   plane_of  int32 [n_out] or NULL: output j is made from source plane plane_of[j] (NULL: j, then n_out <= n_src is required);
+ *             a value outside [0, n_src) gives a zero plane
+ *   boxes     float32 [n_out][4] xyxy pixels or NULL: output j keeps only x1 <= X < x2 && y1 <= Y < y2, compared in fp32 (the crop
+ *             rule of mtbt_masks_to_frames); pixels outside the box are not read; a NaN corner gives a zero plane
+ *   out       [n_out][H][pitch]; bit = value > 0 (NaN -> 0).  EVERY byte is written, padding included.
+ * MTBT_EINVAL before any launch: NULL a / out, NULL src with n_src > 0, n_src < 0, n_out < 0, H < 1, W < 1, H * W >= 2^31,
+ * pitch != 8 * ceil(W / 64), row_stride < W, plane_stride < 0, a dtype other than 0 / 1, plane_of == NULL with n_out > n_src.
+ * MTBT_EALIGN: out not 8-byte aligned, a float32 src / boxes / plane_of not 4-byte aligned.  n_out == 0 launches nothing. */
+typedef struct mtbt_pack_masks_args {
+  const void* src;
+  const int32_t* plane_of; /* [n_out] or NULL */
+  const float* boxes;      /* [n_out][4] or NULL */
+  uint8_t* out;            /* [n_out][H][pitch] */
+  int64_t plane_stride, row_stride; /* elements */
+  int32_t n_src, n_out, H, W, pitch;
+  int32_t dtype;           /* 0 uint8, 1 float32 */
+} mtbt_pack_masks_args;
+int mtbt_pack_masks(const mtbt_pack_masks_args* a, void* stream);
+
+/* mtbt_mask_pair_counts: pixel-count tables of one launch of up to 32 images, each with its own size.
+ * Image b: K packed detection planes at det (plane k at det + k * H * pitch) and its ground-truth planes addressed from gt_base:
+ * flat GT plane m (0 <= m < M) belongs to image gt_image[m] of THIS launch (device int32; a value outside [0, n_images) = no image)
+ * and lives at gt_base_b + (m - g0_b) * H_b * pitch_b; a row with m - g0_b outside [0, gt_planes_b) is treated as of no image.
+ * One rule, two layouts: a list of images with their own GT tensors (g0_b = index of the image's first flat row, gt_planes_b = its
+ * G_b), or a uniform batch whose GT planes are one flat [M][H][pitch] buffer (every image: gt_base = the buffer, g0 = 0, gt_planes = M;
+ * membership is known only on the device).  The descriptors are read on the host and travel as kernel arguments.
+ *   inter    uint32 [M][K]  popcount(gt_m & det_{b(m),k});  det_area uint32 [n_images][K];  gt_area uint32 [M]
+ *   counts   int32 [n_images] or NULL (all K): planes k >= counts[b] count as empty and are NOT read
+ * Rows of no image give zeros.  Every output word is defined after the call (the entry point clears inter and gt_area on the stream
+ * before the launch; the kernel writes det_area whole): the caller does not pre-zero.  One workgroup owns one (image, plane k).
+ * MTBT_EINVAL before any launch: NULL a / images / det_area, M > 0 with NULL inter / gt_image / gt_area (all three
+ * may be NULL when M == 0: nothing of them is read or written), K outside [1, 1024],
+ * n_images outside [1, 32] or != a->B, M < 0, and per image NULL det / gt_base, H < 1, W < 1, H * W >= 2^31,
+ * pitch != 8 * ceil(W / 64), gt_planes < 0.  MTBT_EALIGN: det / gt_base not 8-byte aligned, the tables not 4-byte aligned. */
+typedef struct mtbt_mask_image {
+  const uint8_t* det;     /* K packed planes (only the first counts[b] are read) */
+  const uint8_t* gt_base; /* see the addressing rule above; any non-NULL 8-byte aligned pointer when the image has no GT */
+  int32_t H, W, pitch;
+  int32_t g0;             /* flat row of the plane at gt_base */
+  int32_t gt_planes;      /* planes addressable from gt_base */
+  int32_t reserved;
+} mtbt_mask_image;
+
+typedef struct mtbt_mask_pair_args {
+  const int32_t* counts;   /* [B] or NULL */
+  const int32_t* gt_image; /* [M] */
+  uint32_t* inter;         /* [M][K]; NULL allowed when M == 0 */
+  uint32_t* det_area;      /* [B][K] */
+  uint32_t* gt_area;       /* [M]; NULL allowed when M == 0 */
+  int32_t B, K, M;
+  int32_t reserved;
+} mtbt_mask_pair_args;
+int mtbt_mask_pair_counts(const mtbt_mask_pair_args* a, const mtbt_mask_image* images, int n_images, void* stream);
+
+/* mtbt_mask_eval: the matching walk of mtbt_box_eval (semantics at the top of csrc/box_eval.hip: per (image, class), score order
+ * stable on the slot, max_det, the four inclusive area ranges, lim = min(t, 1 - 1e-10), highest IoU / later GT on ties, the
+ * non-ignored / ignored two-candidate rule, detection ignore flags) over the tables of mtbt_mask_pair_counts:
+ *   IoU  = inter / (det_area + gt_px - inter) in fp64 from the integers, 0 when the union is 0; areas are the pixel counts;
+ *   GT membership, order and class come from gt_image [M] (a value outside [0, B) = no image) and gt_label [M], both int32.
+ * B is not limited here (the tables of several pair-count launches may be evaluated together).  Outputs as mtbt_box_eval: rank
+ * [B][K] int32, match / ignore [B][K][4] uint32, gt_area [M] uint32 area-range sets (0 for rows of no image), status set to 1 when
+ * an image holds more than 1024 GT planes (the caller zeroes it; that image's detections come back invalid).
+ * MTBT_EINVAL: NULL pointers (inter / gt_px / gt_image / gt_label / gt_area may be NULL only when M == 0), T outside [1, 32],
+ * K outside [1, 1024], B < 0, M < 0, max_det < 1.  MTBT_EALIGN for misaligned pointers. */
+typedef struct mtbt_mask_eval_args {
+  const uint32_t* inter;    /* [M][K] */
+  const uint32_t* det_area; /* [B][K] */
+  const uint32_t* gt_px;    /* [M] pixel counts */
+  const float* scores;      /* [B][K] */
+  const int64_t* labels;    /* [B][K] */
+  const int32_t* counts;    /* [B] or NULL */
+  const int32_t* gt_image;  /* [M] */
+  const int32_t* gt_label;  /* [M] */
+  int32_t* rank;
+  uint32_t* match;
+  uint32_t* ignore;
+  uint32_t* gt_area;
+  int32_t* status;
+  double iou_thresholds[32];
+  int32_t B, K, M, T;
+  int32_t max_det;
+  int32_t reserved;
+} mtbt_mask_eval_args;
+int mtbt_mask_eval(const mtbt_mask_eval_args* args, void* stream);
+/* sizeof() of the four structs above as the library was compiled: which = 0 mtbt_pack_masks_args, 1 mtbt_mask_image,
+ * 2 mtbt_mask_pair_args, 3 mtbt_mask_eval_args; -1 otherwise */
+int mtbt_sizeof_mask_eval_args(int which);
+
 /* Weight gradient of a k x k convolution (any stride / padding; 1x1 and the 2x2 stride-2 downsample included), bf16 (MFMA) or fp32 operands:
  *   dw[k][r][s][c] (fp32, packed [K][R*S*C] like the forward weight) (+)= sum_p dy[p][k] * x[n][y*stride + r - pad][x*stride + s - pad][c]
  * x [N,H,W,C], dy [N,Ho,Wo,K] (Ho = (H + 2 pad - R) / stride + 1) NHWC with pixel / batch strides in elements (multiples of 8; C % 8 == K % 8 == 0;

@@ -13,7 +13,7 @@ from . import postprocess, preprocess  # noqa: F401
 from .loss import multitask_loss  # noqa: F401
 from .checkpoints import load_pretrained_heads, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401
-from .metrics import (DetectionConfusionMatrix, DeviceMeanAveragePrecision, ImageClassificationMetrics, MeanAveragePrecision,  # noqa: F401
-                      SegmentationMetrics)
+from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision,  # noqa: F401
+                      ImageClassificationMetrics, MeanAveragePrecision, SegmentationMetrics)
 from .validate import ValidationStep  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

@@ -116,6 +116,30 @@ class FrameMaskArgs(C.Structure):  # mtbt_frame_mask_args
                 ("N", C.c_int32), ("K", C.c_int32), ("nm", C.c_int32), ("hp", C.c_int32), ("wp", C.c_int32), ("crop", C.c_int32)]
 
 
+class PackMasksArgs(C.Structure):  # mtbt_pack_masks_args
+    _fields_ = [("src", C.c_void_p), ("plane_of", C.c_void_p), ("boxes", C.c_void_p), ("out", C.c_void_p),
+                ("plane_stride", C.c_int64), ("row_stride", C.c_int64),
+                ("n_src", C.c_int32), ("n_out", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32), ("dtype", C.c_int32)]
+
+
+class MaskImage(C.Structure):  # mtbt_mask_image
+    _fields_ = [("det", C.c_void_p), ("gt_base", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32),
+                ("g0", C.c_int32), ("gt_planes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MaskPairArgs(C.Structure):  # mtbt_mask_pair_args
+    _fields_ = [("counts", C.c_void_p), ("gt_image", C.c_void_p), ("inter", C.c_void_p), ("det_area", C.c_void_p), ("gt_area", C.c_void_p),
+                ("B", C.c_int32), ("K", C.c_int32), ("M", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MaskEvalArgs(C.Structure):  # mtbt_mask_eval_args
+    _fields_ = [("inter", C.c_void_p), ("det_area", C.c_void_p), ("gt_px", C.c_void_p), ("scores", C.c_void_p), ("labels", C.c_void_p),
+                ("counts", C.c_void_p), ("gt_image", C.c_void_p), ("gt_label", C.c_void_p),
+                ("rank", C.c_void_p), ("match", C.c_void_p), ("ignore", C.c_void_p), ("gt_area", C.c_void_p), ("status", C.c_void_p),
+                ("iou_thresholds", C.c_double * 32), ("B", C.c_int32), ("K", C.c_int32), ("M", C.c_int32), ("T", C.c_int32),
+                ("max_det", C.c_int32), ("reserved", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -215,10 +239,15 @@ SYMBOLS = {
     "mtbt_cls_confusion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtbt_masks_to_frames": (C.c_int, [C.POINTER(FrameMaskArgs), C.POINTER(Frame), C.c_int, C.c_void_p]),
     "mtbt_sizeof_frame_args": (C.c_int, [C.c_int]),
+    "mtbt_pack_masks": (C.c_int, [C.POINTER(PackMasksArgs), C.c_void_p]),
+    "mtbt_mask_pair_counts": (C.c_int, [C.POINTER(MaskPairArgs), C.POINTER(MaskImage), C.c_int, C.c_void_p]),
+    "mtbt_mask_eval": (C.c_int, [C.POINTER(MaskEvalArgs), C.c_void_p]),
+    "mtbt_sizeof_mask_eval_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
 FRAME_STRUCTS = (Frame, FrameMaskArgs)   # order of mtbt_sizeof_frame_args(which)
+MASK_EVAL_STRUCTS = (PackMasksArgs, MaskImage, MaskPairArgs, MaskEvalArgs)   # order of mtbt_sizeof_mask_eval_args(which)
 _lib = None
 
 
@@ -240,10 +269,11 @@ def load():
             if lib.mtbt_sizeof_args(which) != C.sizeof(st):
                 raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {lib.mtbt_sizeof_args(which)}, this binding lays it out in "
                                    f"{C.sizeof(st)} bytes: stale library, rebuild")
-        for which, st in enumerate(FRAME_STRUCTS):
-            if lib.mtbt_sizeof_frame_args(which) != C.sizeof(st):
-                raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {lib.mtbt_sizeof_frame_args(which)}, this binding lays it "
-                                   f"out in {C.sizeof(st)} bytes: stale library, rebuild")
+        for sizeof, structs in ((lib.mtbt_sizeof_frame_args, FRAME_STRUCTS), (lib.mtbt_sizeof_mask_eval_args, MASK_EVAL_STRUCTS)):
+            for which, st in enumerate(structs):
+                if sizeof(which) != C.sizeof(st):
+                    raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "
+                                       f"out in {C.sizeof(st)} bytes: stale library, rebuild")
         _lib = lib
     return _lib
 

@@ -15,6 +15,9 @@ torchmetrics' binary stat-score definitions.
                           torchmetrics' full bbox key set (the four COCO area ranges, per-class values with `class_metrics`): the
                           per-image matching on the device (`mtbt_box_eval`, straight from the NMS output and the collated GT rows,
                           no host sync per step).
+  DeviceMaskMeanAveragePrecision
+                          the same key set for INSTANCE MASKS (torchmetrics iou_type="segm"), from bit-packed masks: popcount tables
+                          (`mtbt_mask_pair_counts`) and the same matching walk over them (`mtbt_mask_eval`), all on the device.
   ImageClassificationMetrics
                           image-class accuracy, normalised confusion matrix (:193-195, :458-459, :609-616) and the macro precision /
                           recall / F1 of evaluate_model.py:244-272 from a device-side confusion matrix (`mtbt_cls_confusion`).
@@ -234,7 +237,106 @@ def _accumulate(records: Dict[str, np.ndarray], iou_thresholds: Sequence[float],
     return out
 
 
-class DeviceMeanAveragePrecision:
+def _upload(parts: Sequence[np.ndarray], dev) -> List[torch.Tensor]:
+    """Host arrays -> device tensors through ONE buffer of 16-byte aligned pieces: one host-to-device copy."""
+    offs, off = [], 0
+    for x in parts:
+        offs.append(off)
+        off += -(-x.nbytes // 16) * 16
+    buf = np.zeros(max(off, 16), np.uint8)
+    for x, o in zip(parts, offs):
+        buf[o:o + x.nbytes] = np.ascontiguousarray(x).view(np.uint8).ravel()
+    dbuf = torch.from_numpy(buf).to(dev)
+    return [dbuf[o:o + x.nbytes].view(getattr(torch, x.dtype.name)).reshape(x.shape) for x, o in zip(parts, offs)]
+
+
+class _DeviceCocoRecords:
+    """What the device mAP classes share: the constructor's checks, the per-update device records a matching kernel (`mtbt_box_eval`,
+    `mtbt_mask_eval`) writes, their one copy to the host, the cross-rank gather and the accumulation through `_accumulate`."""
+    _what = "GT boxes"
+
+    def __init__(self, iou_thresholds, max_detection_thresholds, class_metrics, dist_sync, process_group):
+        name = type(self).__name__
+        self.iou_thresholds = np.asarray(iou_thresholds if iou_thresholds is not None else COCO_IOU_THRESHOLDS, np.float64).ravel()
+        if not 1 <= len(self.iou_thresholds) <= 32:
+            raise ValueError(f"{name}: between 1 and 32 IoU thresholds")
+        self.max_dets = sorted(int(m) for m in max_detection_thresholds)
+        if not self.max_dets or self.max_dets[0] < 1:
+            raise ValueError(f"{name}: max_detection_thresholds must be positive")
+        self.class_metrics, self.dist_sync, self.group = bool(class_metrics), dist_sync, process_group
+        self.reset()
+
+    def reset(self):
+        self._dets: List[torch.Tensor] = []     # per update: [B*K, 11] int32 = score bits, label, rank, match[4], ignore[4]
+        self._gts: List[torch.Tensor] = []      # per update: [M, 3] int32 = image, class (as `_gt_fields` reads them), area-range set
+        self._shapes: List[tuple] = []          # per update: (B, K, M)
+        self._status: Optional[torch.Tensor] = None
+
+    def _status_on(self, dev) -> torch.Tensor:
+        if self._status is None:
+            self._status = torch.zeros(4, dtype=torch.int32, device=dev)
+        elif self._status.device != dev:
+            raise ValueError(f"{type(self).__name__}: this metric keeps its records on {self._status.device}, the batch is on {dev}")
+        return self._status
+
+    def _keep(self, scores, labels, rank, mi, gt_cols, gt_area):
+        """One update's records, kept on the device: scores [B,K] f32, labels [B,K], rank [B,K] i32, mi [2,B,K,4] (match, ignore),
+        gt_cols [M,2] int32 (image, class), gt_area [M] int32."""
+        B, K = scores.shape
+        self._dets.append(torch.cat([scores.reshape(-1, 1).view(torch.int32), labels.reshape(-1, 1).to(torch.int32), rank.reshape(-1, 1),
+                                     mi[0].reshape(-1, 4), mi[1].reshape(-1, 4)], 1))
+        self._gts.append(torch.cat([gt_cols, gt_area.reshape(-1, 1)], 1))
+        self._shapes.append((B, K, gt_cols.shape[0]))
+
+    def _records(self):
+        """-> (records dict over this process's images, number of images, status word) on the host."""
+        if self._dets:
+            dets = torch.cat(self._dets).cpu().numpy()
+            gts = torch.cat(self._gts).cpu().numpy()
+            status = int(self._status.cpu().numpy().max())
+        else:
+            dets, gts, status = np.zeros((0, 11), np.int32), np.zeros((0, 3), np.int32), 0
+        image, gt_keep, gt_label, n_img = [], [], [], 0
+        for B, K, M in self._shapes:
+            image.append(np.repeat(np.arange(n_img, n_img + B), K))
+            n_img += B
+        for (B, K, M), lo in zip(self._shapes, np.cumsum([0] + [s[2] for s in self._shapes])):
+            keep_u, label_u = self._gt_fields(gts[lo:lo + M], B)                   # rows of an image of their batch, their classes
+            gt_keep.append(keep_u)
+            gt_label.append(label_u)
+        keep = np.concatenate(gt_keep) if gt_keep else np.zeros(0, bool)
+        rec = {"image": np.concatenate(image) if image else np.zeros(0, np.int64), "score": dets[:, 0].view(np.float32).astype(np.float64),
+               "label": dets[:, 1].astype(np.int64), "rank": dets[:, 2], "match": dets[:, 3:7].view(np.uint32),
+               "ignore": dets[:, 7:11].view(np.uint32),
+               "gt_label": (np.concatenate(gt_label) if gt_label else np.zeros(0, np.int64))[keep], "gt_area": gts[keep, 2].view(np.uint32)}
+        kept = rec["rank"] >= 0
+        for k in ("image", "score", "label", "rank", "match", "ignore"):
+            rec[k] = rec[k][kept]
+        return rec, n_img, status
+
+    def compute(self) -> Dict[str, object]:
+        """With a live process group (and dist_sync): over the images of ALL ranks -- a collective, every rank must call it."""
+        rec, n_img, status = self._records()
+        if self.dist_sync and _world(self.group) > 1:
+            parts = _all_gather_records([(rec, n_img, status)], self.group)
+            off, image = 0, []
+            for r, n, _ in parts:
+                image.append(r["image"] + off)
+                off += n
+            rec = {k: np.concatenate([p[0][k] for p in parts]) for k in rec}
+            rec["image"] = np.concatenate(image)
+            status = max(p[2] for p in parts)
+        if status:
+            raise RuntimeError(f"{type(self).__name__}.compute: an image holds more than {BOX_EVAL_CAP} {self._what} (the matching kernel's cap)")
+        return _accumulate(rec, self.iou_thresholds, self.max_dets, self.class_metrics)
+
+    @staticmethod
+    def _gt_fields(gts: np.ndarray, B: int):
+        """-> (rows of an image of their batch [M] bool, class [M] int64) from the first two int32 columns of one update's GT records."""
+        raise NotImplementedError
+
+
+class DeviceMeanAveragePrecision(_DeviceCocoRecords):
     """COCO box mAP / mAR with torchmetrics' bbox key set -- the four area ranges and, with `class_metrics`, per-class values --
     with the per-image matching on the device (`mtbt_box_eval`) and the once-per-epoch accumulation in vectorised numpy.
 
@@ -243,28 +345,22 @@ class DeviceMeanAveragePrecision:
     normalised (`preprocess.collate_boxes`), both on the device.  One launch, no host synchronisation.
     `update(preds, targets)`: the torchmetrics list-of-dicts layout the reference builds (running_main_v3.py:554-570), one
     host-to-device copy per call.  `compute()` copies the records to the host once; with a live process group (and
-    `dist_sync`) it gathers every rank's records in rank order first (a collective: every rank must call it)."""
+    `dist_sync`) it gathers every rank's records in rank order first (a collective: every rank must call it).
+    Instance masks (`iou_type="segm"`) are `DeviceMaskMeanAveragePrecision`."""
 
     def __init__(self, iou_thresholds: Optional[Sequence[float]] = None, max_detection_thresholds: Sequence[int] = (1, 10, 100),
                  class_metrics: bool = False, dist_sync: bool = True, process_group=None, box_format: str = "xyxy", iou_type: str = "bbox"):
         if box_format != "xyxy":
             raise ValueError(f"DeviceMeanAveragePrecision: box_format {box_format!r} is not supported (only 'xyxy')")
         if iou_type != "bbox":
-            raise ValueError(f"DeviceMeanAveragePrecision: iou_type {iou_type!r} is not supported (only 'bbox')")
-        self.iou_thresholds = np.asarray(iou_thresholds if iou_thresholds is not None else COCO_IOU_THRESHOLDS, np.float64).ravel()
-        if not 1 <= len(self.iou_thresholds) <= 32:
-            raise ValueError("DeviceMeanAveragePrecision: between 1 and 32 IoU thresholds")
-        self.max_dets = sorted(int(m) for m in max_detection_thresholds)
-        if not self.max_dets or self.max_dets[0] < 1:
-            raise ValueError("DeviceMeanAveragePrecision: max_detection_thresholds must be positive")
-        self.class_metrics, self.dist_sync, self.group = bool(class_metrics), dist_sync, process_group
-        self.reset()
+            raise ValueError(f"DeviceMeanAveragePrecision: iou_type {iou_type!r} is not supported (only 'bbox'; instance masks are "
+                             "DeviceMaskMeanAveragePrecision)")
+        super().__init__(iou_thresholds, max_detection_thresholds, class_metrics, dist_sync, process_group)
 
-    def reset(self):
-        self._dets: List[torch.Tensor] = []     # per update: [B*K, 11] int32 = score bits, label, rank, match[4], ignore[4]
-        self._gts: List[torch.Tensor] = []      # per update: [M, 3] int32 = batch_idx bits, cls bits, area-range set
-        self._shapes: List[tuple] = []          # per update: (B, K, M)
-        self._status: Optional[torch.Tensor] = None
+    @staticmethod
+    def _gt_fields(gts, B):
+        bidx = gts[:, 0].view(np.float32)                                        # the collated rows' (batch_idx, cls) float bits
+        return (bidx >= 0) & (bidx < B) & (bidx == np.trunc(bidx)), np.trunc(gts[:, 1].view(np.float32)).astype(np.int64)
 
     def _launch(self, boxes, scores, labels, counts, gt, gt_format: int, img_size: float):
         lib = L.load()
@@ -273,10 +369,7 @@ class DeviceMeanAveragePrecision:
         M = gt.shape[0]
         if K > BOX_EVAL_CAP:
             raise ValueError(f"DeviceMeanAveragePrecision: {K} detection slots per image, at most {BOX_EVAL_CAP}")
-        if self._status is None:
-            self._status = torch.zeros(4, dtype=torch.int32, device=dev)
-        elif self._status.device != dev:
-            raise ValueError(f"DeviceMeanAveragePrecision: this metric keeps its records on {self._status.device}, the batch is on {dev}")
+        status = self._status_on(dev)
         rank = torch.empty((B, K), dtype=torch.int32, device=dev)
         mi = torch.empty((2, B, K, 4), dtype=torch.int32, device=dev)          # match, ignore (uint32 bit sets)
         gt_area = torch.empty((M,), dtype=torch.int32, device=dev)
@@ -284,16 +377,13 @@ class DeviceMeanAveragePrecision:
         a.boxes, a.scores, a.labels = boxes.data_ptr(), scores.data_ptr(), labels.data_ptr()
         a.counts = counts.data_ptr() if counts is not None else None
         a.gt, a.gt_area = (gt.data_ptr(), gt_area.data_ptr()) if M else (None, None)
-        a.rank, a.match, a.ignore, a.status = rank.data_ptr(), mi[0].data_ptr(), mi[1].data_ptr(), self._status.data_ptr()
+        a.rank, a.match, a.ignore, a.status = rank.data_ptr(), mi[0].data_ptr(), mi[1].data_ptr(), status.data_ptr()
         for t, v in enumerate(self.iou_thresholds):
             a.iou_thresholds[t] = float(v)
         a.B, a.K, a.M, a.T, a.max_det, a.gt_format, a.img_size = B, K, M, len(self.iou_thresholds), self.max_dets[-1], gt_format, float(img_size)
         with torch.cuda.device(dev):                                            # launch on the tensors' device, whatever is current
             L.check(lib.mtbt_box_eval(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_box_eval")
-        self._dets.append(torch.cat([scores.reshape(-1, 1).view(torch.int32), labels.reshape(-1, 1).to(torch.int32), rank.reshape(-1, 1),
-                                     mi[0].reshape(-1, 4), mi[1].reshape(-1, 4)], 1))
-        self._gts.append(torch.cat([gt[:, :2].view(torch.int32), gt_area.reshape(-1, 1)], 1))
-        self._shapes.append((B, K, M))
+        self._keep(scores, labels, rank, mi, gt[:, :2].view(torch.int32), gt_area)
 
     def update_batched(self, det: Dict[str, torch.Tensor], gt_rows: torch.Tensor, img_size: float):
         """Asynchronous: launches on the current stream, keeps its records on the device, never synchronises with the host."""
@@ -339,57 +429,261 @@ class DeviceMeanAveragePrecision:
             gb, gl = np_(t["boxes"], np.float32).reshape(-1, 4), np_(t["labels"], np.float32).ravel()
             rows.append(np.concatenate([np.full((len(gb), 1), b, np.float32), gl[:, None], gb], 1))
         gt = np.concatenate(rows).astype(np.float32)
-        parts, offs, off = [boxes, scores, labels, counts, gt], [], 0
-        for x in parts:                                                          # one buffer, 16-byte aligned pieces: one copy
-            offs.append(off)
-            off += -(-x.nbytes // 16) * 16
-        buf = np.zeros(max(off, 16), np.uint8)
-        for x, o in zip(parts, offs):
-            buf[o:o + x.nbytes] = np.ascontiguousarray(x).view(np.uint8).ravel()
-        dbuf = torch.from_numpy(buf).to(self._status.device if self._status is not None else torch.device("cuda", torch.cuda.current_device()))
-        views = [dbuf[o:o + x.nbytes].view(getattr(torch, x.dtype.name)).reshape(x.shape) for x, o in zip(parts, offs)]
+        views = _upload([boxes, scores, labels, counts, gt], self._status.device if self._status is not None else torch.device("cuda", torch.cuda.current_device()))
         self._launch(views[0], views[1], views[2], views[3], views[4], 1, 0.0)
 
-    def _records(self):
-        """-> (records dict over this process's images, number of images, status word) on the host."""
-        if self._dets:
-            dets = torch.cat(self._dets).cpu().numpy()
-            gts = torch.cat(self._gts).cpu().numpy()
-            status = int(self._status.cpu().numpy().max())
-        else:
-            dets, gts, status = np.zeros((0, 11), np.int32), np.zeros((0, 3), np.int32), 0
-        image, gt_keep, n_img = [], [], 0
-        for B, K, M in self._shapes:
-            image.append(np.repeat(np.arange(n_img, n_img + B), K))
-            n_img += B
-        for (B, K, M), lo in zip(self._shapes, np.cumsum([0] + [s[2] for s in self._shapes])):
-            bidx = gts[lo:lo + M, 0].view(np.float32)
-            gt_keep.append((bidx >= 0) & (bidx < B) & (bidx == np.trunc(bidx)))    # rows of an image of their batch
-        keep = np.concatenate(gt_keep) if gt_keep else np.zeros(0, bool)
-        rec = {"image": np.concatenate(image) if image else np.zeros(0, np.int64), "score": dets[:, 0].view(np.float32).astype(np.float64),
-               "label": dets[:, 1].astype(np.int64), "rank": dets[:, 2], "match": dets[:, 3:7].view(np.uint32),
-               "ignore": dets[:, 7:11].view(np.uint32),
-               "gt_label": np.trunc(gts[keep, 1].view(np.float32)).astype(np.int64), "gt_area": gts[keep, 2].view(np.uint32)}
-        kept = rec["rank"] >= 0
-        for k in ("image", "score", "label", "rank", "match", "ignore"):
-            rec[k] = rec[k][kept]
-        return rec, n_img, status
 
-    def compute(self) -> Dict[str, object]:
-        """With a live process group (and dist_sync): over the images of ALL ranks -- a collective, every rank must call it."""
-        rec, n_img, status = self._records()
-        if self.dist_sync and _world(self.group) > 1:
-            parts = _all_gather_records([(rec, n_img, status)], self.group)
-            off, image = 0, []
-            for r, n, _ in parts:
-                image.append(r["image"] + off)
-                off += n
-            rec = {k: np.concatenate([p[0][k] for p in parts]) for k in rec}
-            rec["image"] = np.concatenate(image)
-            status = max(p[2] for p in parts)
-        if status:
-            raise RuntimeError(f"DeviceMeanAveragePrecision.compute: an image holds more than {BOX_EVAL_CAP} GT boxes (mtbt_box_eval cap)")
-        return _accumulate(rec, self.iou_thresholds, self.max_dets, self.class_metrics)
+MASK_EVAL_MAX_IMAGES = 32    # images per mtbt_mask_pair_counts launch (the image descriptors travel as kernel arguments)
+
+
+def _mask_pitch(W: int) -> int:
+    return 8 * ((int(W) + 63) // 64)
+
+
+def _mask_launch_layout(n_gt: Sequence[int], chunk: int = MASK_EVAL_MAX_IMAGES):
+    """A list of images with n_gt[b] ground-truth planes each -> the launches of `mtbt_mask_pair_counts`, `chunk` images at a time:
+    [(first image, one past the last image, g0 per image, gt_image int32 [M])].  The GT planes of a launch form one flat row list in
+    image order; g0[i] is the flat row of image i's first plane (its own GT tensor is addressed from there) and gt_image[m] the image
+    OF THE LAUNCH that row m belongs to."""
+    out = []
+    for c0 in range(0, len(n_gt), chunk):
+        g = [int(v) for v in n_gt[c0:c0 + chunk]]
+        if any(v < 0 for v in g):
+            raise ValueError("_mask_launch_layout: a negative plane count")
+        g0 = np.cumsum([0] + g)[:-1].astype(np.int64).tolist()
+        out.append((c0, c0 + len(g), g0, np.repeat(np.arange(len(g), dtype=np.int32), g)))
+    return out
+
+
+def _pair_counts(images, K: int, counts, gt_image, M: int, dev, out=None):
+    """One `mtbt_mask_pair_counts` launch.  images: [(H, W, det tensor, gt tensor, g0, gt_planes)], at most 32; counts int32 [B] or
+    None; gt_image int32 [M] on the device.  -> (inter [M,K], det_area [B,K], gt_px [M]) int32 tensors holding the uint32 counts;
+    `out=` takes the caller's three contiguous tensors of those shapes instead (every word is defined afterwards, whatever they held)."""
+    lib = L.load()
+    B = len(images)
+    if out is None:
+        out = (torch.empty((M, K), dtype=torch.int32, device=dev), torch.empty((B, K), dtype=torch.int32, device=dev),
+               torch.empty((M,), dtype=torch.int32, device=dev))
+    inter, det_area, gt_px = out
+    for t, shape in zip(out, ((M, K), (B, K), (M,))):
+        if t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"_pair_counts: out must be contiguous int32 tensors [{M},{K}], [{B},{K}], [{M}] on the device")
+    a = L.MaskPairArgs()
+    a.counts = counts.data_ptr() if counts is not None else None
+    a.gt_image, a.gt_area, a.inter = (gt_image.data_ptr(), gt_px.data_ptr(), inter.data_ptr()) if M else (None, None, None)
+    a.det_area = det_area.data_ptr()
+    a.B, a.K, a.M = B, K, M
+    im = (L.MaskImage * B)()
+    for i, (H, W, det, gt, g0, planes) in enumerate(images):
+        im[i].det, im[i].gt_base = det.data_ptr(), gt.data_ptr()
+        im[i].H, im[i].W, im[i].pitch, im[i].g0, im[i].gt_planes = H, W, _mask_pitch(W), g0, planes
+    with torch.cuda.device(dev):
+        L.check(lib.mtbt_mask_pair_counts(C.byref(a), im, B, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_mask_pair_counts")
+    return inter, det_area, gt_px
+
+
+class DeviceMaskMeanAveragePrecision(_DeviceCocoRecords):
+    """COCO instance-mask mAP / mAR (torchmetrics `MeanAveragePrecision(iou_type="segm")`, no crowd annotations) with the key set of
+    `DeviceMeanAveragePrecision`, from BIT-PACKED masks (`postprocess.masks_to_frames` / `pack_masks`: pitch = 8 * ceil(W / 64) bytes per
+    row, pixel X = bit X & 7 of byte X >> 3) and entirely on the device: popcount tables of every (GT, detection) pair of an image
+    (`mtbt_mask_pair_counts`), then pycocotools' matching walk with IoU = inter / (det + gt - inter) in fp64 from those exact integers
+    (`mtbt_mask_eval`; 0 when the union is empty; areas are pixel counts).  Accumulated once per epoch like the box class.
+
+    `update(preds, targets)`: torchmetrics' segm layout, per image dict(masks bool [D,H,W], scores [D], labels [D]) and
+    dict(masks bool [G,H,W], labels [G]) on the device; a dict may instead hold packed uint8 masks [., H, pitch] with `"width": W`.
+    Images keep their own sizes.  One host-to-device copy per 32 images.
+    `update_batched(det, gt_masks, gt_labels)`: `det` = the dict `postprocess.detect_and_segment(..., frames=...)` returns
+    (masks_frame, scores, labels, counts); gt_masks = a list of packed [G_b, H0_b, pitch_b]; gt_labels = a list of int tensors.
+    `update_uniform(det_packed [B,K,S,pitch], scores, labels, counts, gt_packed [M,S,pitch], gt_rows [M,6])`: letterboxed batches;
+    image and class of a GT plane come from the device-resident collated rows by `mtbt_box_eval`'s rule.  No host synchronisation,
+    no host copy."""
+    _what = "GT masks"
+
+    def __init__(self, iou_thresholds: Optional[Sequence[float]] = None, max_detection_thresholds: Sequence[int] = (1, 10, 100),
+                 class_metrics: bool = False, dist_sync: bool = True, process_group=None):
+        super().__init__(iou_thresholds, max_detection_thresholds, class_metrics, dist_sync, process_group)
+
+    @staticmethod
+    def _gt_fields(gts, B):
+        return (gts[:, 0] >= 0) & (gts[:, 0] < B), gts[:, 1].astype(np.int64)
+
+    def _evaluate(self, tables, scores, labels, counts, gt_image, gt_label):
+        """`mtbt_mask_eval` over the pair-count tables of B images, then the records are kept.  All device tensors."""
+        lib = L.load()
+        inter, det_area, gt_px = tables
+        dev = scores.device
+        B, K = scores.shape
+        M = gt_image.shape[0]
+        status = self._status_on(dev)
+        rank = torch.empty((B, K), dtype=torch.int32, device=dev)
+        mi = torch.empty((2, B, K, 4), dtype=torch.int32, device=dev)          # match, ignore (uint32 bit sets)
+        gt_area = torch.empty((M,), dtype=torch.int32, device=dev)
+        a = L.MaskEvalArgs()
+        a.det_area, a.scores, a.labels = det_area.data_ptr(), scores.data_ptr(), labels.data_ptr()
+        a.counts = counts.data_ptr() if counts is not None else None
+        if M:
+            a.inter, a.gt_px, a.gt_image, a.gt_label, a.gt_area = (t.data_ptr() for t in (inter, gt_px, gt_image, gt_label, gt_area))
+        a.rank, a.match, a.ignore, a.status = rank.data_ptr(), mi[0].data_ptr(), mi[1].data_ptr(), status.data_ptr()
+        for t, v in enumerate(self.iou_thresholds):
+            a.iou_thresholds[t] = float(v)
+        a.B, a.K, a.M, a.T, a.max_det = B, K, M, len(self.iou_thresholds), self.max_dets[-1]
+        with torch.cuda.device(dev):
+            L.check(lib.mtbt_mask_eval(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_mask_eval")
+        self._keep(scores, labels, rank, mi, torch.stack([gt_image, gt_label], 1), gt_area)
+
+    # ---- images with their own sizes -------------------------------------------------------------------------------------------
+    @staticmethod
+    def _packed_of(d: Dict, who: str):
+        """-> (packed uint8 [n, H, pitch] on the device, H, W) of one image's dict."""
+        from .postprocess import pack_masks
+        m = d["masks"]
+        if not isinstance(m, torch.Tensor) or not m.is_cuda or m.dim() != 3:
+            raise RuntimeError(f"DeviceMaskMeanAveragePrecision.{who}: masks must be [n, H, W] CUDA/HIP tensors on an MI355X (no CPU path)")
+        if "width" in d:
+            W = int(d["width"])
+            if m.dtype != torch.uint8 or m.shape[2] != _mask_pitch(W):
+                raise ValueError(f"DeviceMaskMeanAveragePrecision.{who}: packed masks of width {W} are uint8 [n, H, {_mask_pitch(W)}]")
+            m = m.contiguous()
+            return (m if m.data_ptr() % 8 == 0 else m.clone()), int(m.shape[1]), W
+        return pack_masks(m), int(m.shape[1]), int(m.shape[2])
+
+    def _update_list(self, det_planes, sizes, n_det, scores, labels, gt_planes, gt_labels, dev):
+        """det_planes / gt_planes: per image packed [>= n_det[b], H, pitch] / [G_b, H, pitch]; sizes (H, W); scores / labels: host arrays
+        per image; gt_labels: host int arrays per image."""
+        K = max(1, max(n_det))
+        if K > BOX_EVAL_CAP:
+            raise ValueError(f"DeviceMaskMeanAveragePrecision: {K} detections in one image, at most {BOX_EVAL_CAP}")
+        for c0, c1, g0, gi in _mask_launch_layout([int(g.shape[0]) for g in gt_planes]):
+            nb = c1 - c0
+            sc, lb, cn = np.zeros((nb, K), np.float32), np.zeros((nb, K), np.int64), np.zeros(nb, np.int32)
+            for i in range(nb):
+                n = n_det[c0 + i]
+                sc[i, :n], lb[i, :n], cn[i] = scores[c0 + i][:n], labels[c0 + i][:n], n
+            gl = np.concatenate([np.zeros(0, np.int32)] + [np.asarray(g, np.int32).ravel() for g in gt_labels[c0:c1]])
+            if len(gl) != len(gi):
+                raise ValueError("DeviceMaskMeanAveragePrecision: one label per GT mask")
+            d_sc, d_lb, d_cn, d_gi, d_gl = _upload([sc, lb, cn, gi, gl], dev)
+            images = []
+            for i in range(nb):
+                H, W = sizes[c0 + i]
+                det, gt = det_planes[c0 + i], gt_planes[c0 + i]
+                images.append((H, W, det if det.numel() else d_sc, gt if gt.numel() else d_sc, g0[i], int(gt.shape[0])))
+            tables = _pair_counts(images, K, d_cn, d_gi, len(gi), dev)
+            self._evaluate(tables, d_sc, d_lb, d_cn, d_gi, d_gl)
+
+    def update(self, preds: Sequence[Dict], targets: Sequence[Dict]):
+        if len(preds) != len(targets):
+            raise ValueError("DeviceMaskMeanAveragePrecision.update: preds and targets differ in length")
+        if not preds:
+            return
+        np_ = MeanAveragePrecision._np
+        det, gt, sizes = [], [], []
+        for p, t in zip(preds, targets):
+            dp, H, W = self._packed_of(p, "update")
+            gp, Hg, Wg = self._packed_of(t, "update")
+            if (H, W) != (Hg, Wg):
+                raise ValueError(f"DeviceMaskMeanAveragePrecision.update: predicted masks are {H} x {W}, the image's GT masks {Hg} x {Wg}")
+            det.append(dp)
+            gt.append(gp)
+            sizes.append((H, W))
+        dev = det[0].device
+        if any(t.device != dev for t in det + gt):
+            raise ValueError("DeviceMaskMeanAveragePrecision.update: masks on different devices")
+        scores, labels = [np_(p["scores"], np.float32).ravel() for p in preds], [np_(p["labels"], np.int64).ravel() for p in preds]
+        n_det = [int(d.shape[0]) for d in det]
+        if any(len(s) != n or len(l) != n for s, l, n in zip(scores, labels, n_det)):
+            raise ValueError("DeviceMaskMeanAveragePrecision.update: one score and one label per predicted mask")
+        self._update_list(det, sizes, n_det, scores, labels, gt, [np_(t["labels"], np.int32).ravel() for t in targets], dev)
+
+    def update_batched(self, det: Dict, gt_masks: Sequence[torch.Tensor], gt_labels: Sequence[torch.Tensor]):
+        """`det["masks_frame"]`: packed [K, H0_b, pitch_b] per image (only the first counts[b] planes are read).  The scores, labels and
+        counts stay on the device; only the GT plane layout (a few integers per image) is uploaded."""
+        planes, scores, labels, counts = det["masks_frame"], det["scores"], det["labels"], det.get("counts")
+        B = len(planes)
+        if len(gt_masks) != B or len(gt_labels) != B or scores.shape[0] != B:
+            raise ValueError("DeviceMaskMeanAveragePrecision.update_batched: one GT mask stack and one label tensor per image")
+        if not all(t.is_cuda for t in list(planes) + list(gt_masks) + [scores, labels]):
+            raise RuntimeError("DeviceMaskMeanAveragePrecision.update_batched: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+        if B == 0:
+            return
+        dev = scores.device
+        K = scores.shape[1]
+        if K > BOX_EVAL_CAP:
+            raise ValueError(f"DeviceMaskMeanAveragePrecision.update_batched: {K} detection slots per image, at most {BOX_EVAL_CAP}")
+        for d, g in zip(planes, gt_masks):
+            if d.dtype != torch.uint8 or g.dtype != torch.uint8 or d.dim() != 3 or g.dim() != 3 or d.shape[0] != K or d.shape[1:] != g.shape[1:]:
+                raise ValueError("DeviceMaskMeanAveragePrecision.update_batched: per image packed uint8 [K, H0, pitch] detections and "
+                                 "[G, H0, pitch] GT planes of the same size")
+        scores, labels = scores.to(torch.float32).contiguous(), labels.to(torch.int64).contiguous()
+        counts = counts.to(torch.int32).contiguous() if counts is not None else None
+        gl = torch.cat([torch.zeros(0, dtype=torch.int32, device=dev)] + [l.reshape(-1).to(device=dev, dtype=torch.int32) for l in gt_labels])
+        if gl.numel() != sum(int(g.shape[0]) for g in gt_masks):
+            raise ValueError("DeviceMaskMeanAveragePrecision.update_batched: one label per GT mask")
+        m0 = 0
+        for c0, c1, g0, gi in _mask_launch_layout([int(g.shape[0]) for g in gt_masks]):
+            d_gi, = _upload([gi], dev)
+            images = []
+            for i, b in enumerate(range(c0, c1)):
+                d, g = planes[b].contiguous(), gt_masks[b].contiguous()
+                # the width is not needed beyond the pitch: the padding bits of both sides are zero
+                images.append((int(d.shape[1]), int(d.shape[2]) * 8, d, g if g.numel() else d, g0[i], int(g.shape[0])))
+            cn = counts[c0:c1] if counts is not None else None
+            tables = _pair_counts(images, K, cn, d_gi, len(gi), dev)
+            self._evaluate(tables, scores[c0:c1], labels[c0:c1], cn, d_gi, gl[m0:m0 + len(gi)])
+            m0 += len(gi)
+
+    # ---- letterboxed batches: everything stays on the device -------------------------------------------------------------------
+    @staticmethod
+    def gt_rows_fields(gt_rows: torch.Tensor, B: int):
+        """The collated [M,6] rows -> (image int32 [M], -1 for a row of no image of the batch; class int32 [M]) by `mtbt_box_eval`'s rule
+        (batch_idx an integer in [0, B); the class truncated), on the device."""
+        bi = gt_rows[:, 0].to(torch.float32)
+        ok = (bi >= 0) & (bi < B) & (bi == bi.trunc())
+        return torch.where(ok, bi, torch.full_like(bi, -1.0)).to(torch.int32), gt_rows[:, 1].to(torch.float32).to(torch.int64).to(torch.int32)
+
+    @staticmethod
+    def pair_tables_uniform(det_packed: torch.Tensor, counts: Optional[torch.Tensor], gt_packed: torch.Tensor, gt_image: torch.Tensor):
+        """The pixel-count tables of a uniform batch (all images S x pitch): (inter [M,K], det_area [B,K], gt_px [M]).  They do not depend
+        on the IoU thresholds: several metric objects may share them (`update_uniform(..., tables=)`)."""
+        B, K, S, pitch = det_packed.shape
+        M = gt_packed.shape[0]
+        dev = det_packed.device
+        counts = counts.to(torch.int32).contiguous() if counts is not None else None
+        parts = []
+        for c0 in range(0, B, MASK_EVAL_MAX_IMAGES):
+            nb = min(MASK_EVAL_MAX_IMAGES, B - c0)
+            gi = gt_image if B <= MASK_EVAL_MAX_IMAGES else torch.where((gt_image >= c0) & (gt_image < c0 + nb), gt_image - c0, torch.full_like(gt_image, -1))
+            images = [(S, pitch * 8, det_packed[b], gt_packed if M else det_packed, 0, M) for b in range(c0, c0 + nb)]
+            parts.append(_pair_counts(images, K, counts[c0:] if counts is not None else None, gi, M, dev))
+        if len(parts) == 1:
+            return parts[0]
+        # a GT row is counted by the launch that holds its image and is zero in every other one
+        return sum(p[0] for p in parts), torch.cat([p[1] for p in parts]), sum(p[2] for p in parts)
+
+    def update_uniform(self, det_packed: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, counts: Optional[torch.Tensor],
+                       gt_packed: torch.Tensor, gt_rows: torch.Tensor, tables=None):
+        """Asynchronous: launches on the current stream, keeps its records on the device, never synchronises with the host."""
+        ts = (det_packed, scores, labels, gt_packed, gt_rows) + ((counts,) if counts is not None else ())
+        if not all(t.is_cuda for t in ts):
+            raise RuntimeError("DeviceMaskMeanAveragePrecision.update_uniform: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+        if len({t.device for t in ts}) != 1:
+            raise ValueError("DeviceMaskMeanAveragePrecision.update_uniform: tensors on different devices")
+        if det_packed.dim() != 4 or det_packed.dtype != torch.uint8 or scores.shape != det_packed.shape[:2] or labels.shape != scores.shape:
+            raise ValueError("DeviceMaskMeanAveragePrecision.update_uniform: det_packed uint8 [B,K,S,pitch], scores [B,K], labels [B,K]")
+        if gt_packed.dim() != 3 or gt_packed.dtype != torch.uint8 or gt_packed.shape[1:] != det_packed.shape[2:] or det_packed.shape[3] % 8:
+            raise ValueError("DeviceMaskMeanAveragePrecision.update_uniform: gt_packed uint8 [M,S,pitch] of the detections' plane size")
+        if gt_rows.dim() != 2 or gt_rows.shape[1] != 6 or gt_rows.shape[0] != gt_packed.shape[0]:
+            raise ValueError("DeviceMaskMeanAveragePrecision.update_uniform: gt_rows must be [M, 6] (batch_idx, cls, ...), one row per GT plane")
+        B, K = scores.shape
+        if B == 0:
+            return
+        if K > BOX_EVAL_CAP:
+            raise ValueError(f"DeviceMaskMeanAveragePrecision.update_uniform: {K} detection slots per image, at most {BOX_EVAL_CAP}")
+        counts = counts.to(torch.int32).contiguous() if counts is not None else None
+        gt_image, gt_label = self.gt_rows_fields(gt_rows, B)
+        if tables is None:
+            tables = self.pair_tables_uniform(det_packed.contiguous(), counts, gt_packed.contiguous(), gt_image)
+        self._evaluate(tables, scores.to(torch.float32).contiguous(), labels.to(torch.int64).contiguous(), counts, gt_image, gt_label)
 
 
 class SegmentationMetrics:

@@ -277,6 +277,56 @@ def unpack_masks(packed: torch.Tensor, W0: int) -> torch.Tensor:
     return bits.reshape(packed.shape[0], packed.shape[1], packed.shape[2] * 8)[:, :, :W0].bool()
 
 
+def pack_masks(planes: torch.Tensor, boxes: Optional[torch.Tensor] = None, plane_of: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Dense masks -> the bit-packed planes of `masks_to_frames` (`unpack_masks` is the inverse), on the device (`mtbt_pack_masks`).
+
+    planes [n, H, W] bool, uint8 or float32 (bit = value > 0, NaN -> 0).  `plane_of` (int [n_out]): output j is made from source plane
+    plane_of[j]; an index outside [0, n) gives a zero plane.  `boxes` (float32 [n_out, 4] xyxy pixels): output j keeps only
+    x1 <= X < x2 and y1 <= Y < y2, the crop rule of `masks_to_frames`.  Together they build per-box instance ground truth from one mask
+    per image and its box rows.  Returns uint8 [n_out, H, pitch], pitch = 8 * ceil(W / 64), padding bits zero.  `out=` takes a caller's
+    contiguous uint8 [n_out, H, pitch] tensor (8-byte aligned); every byte of it is written, whatever it held.  Asynchronous."""
+    lib = L.load()
+    _need_cuda(planes, "pack_masks")
+    if planes.dim() != 3 or planes.dtype not in (torch.bool, torch.uint8, torch.float32):
+        raise ValueError("pack_masks: planes must be [n, H, W] bool, uint8 or float32")
+    n, H, W = planes.shape
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"pack_masks: planes of {H} x {W} pixels (1 <= H * W < 2^31)")
+    dev = planes.device
+    if planes.dtype == torch.bool:
+        planes = planes.view(torch.uint8)
+    if n and (planes.stride(2) != 1 or planes.stride(1) < W or planes.stride(0) < 0):
+        planes = planes.contiguous()
+    n_out = n
+    if plane_of is not None:
+        _need_cuda(plane_of, "pack_masks")
+        plane_of = plane_of.reshape(-1).to(torch.int32).contiguous()
+        n_out = plane_of.numel()
+    if boxes is not None:
+        _need_cuda(boxes, "pack_masks")
+        boxes = boxes.to(torch.float32).contiguous()
+        if boxes.dim() != 2 or boxes.shape[1] != 4 or (plane_of is not None and boxes.shape[0] != n_out) or (plane_of is None and boxes.shape[0] != n):
+            raise ValueError(f"pack_masks: boxes must be [{n_out}, 4] xyxy, one row per output plane")
+    pitch = 8 * ((W + 63) // 64)
+    if out is None:
+        out = torch.empty((n_out, H, pitch), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n_out, H, pitch) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"pack_masks: out must be a contiguous uint8 [{n_out}, {H}, {pitch}] tensor on {dev}")
+    if n_out == 0:
+        return out
+    a = L.PackMasksArgs()
+    a.src = planes.data_ptr() if n else None
+    a.plane_of = plane_of.data_ptr() if plane_of is not None else None
+    a.boxes = boxes.data_ptr() if boxes is not None else None
+    a.out = out.data_ptr()
+    a.plane_stride, a.row_stride = (planes.stride(0), planes.stride(1)) if n else (H * W, W)
+    a.n_src, a.n_out, a.H, a.W, a.pitch, a.dtype = n, n_out, H, W, pitch, int(planes.dtype == torch.float32)
+    with torch.cuda.device(dev):
+        L.check(lib.mtbt_pack_masks(C.byref(a), _stream(dev)), "mtbt_pack_masks")
+    return out
+
+
 def detect_and_segment(det_maps: List[torch.Tensor], mc: torch.Tensor, protos: torch.Tensor, img_size: int,
                        conf_th: float = CONF_TH, iou_th: float = NMS_IOU, top_k: int = TOP_K, masks: bool = True,
                        frames=None, crop: bool = False):

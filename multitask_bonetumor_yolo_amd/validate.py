@@ -18,8 +18,9 @@ import torch
 import torch.nn as nn
 
 from .loss import multitask_loss
-from .metrics import DetectionConfusionMatrix, DeviceMeanAveragePrecision, ImageClassificationMetrics, SegmentationMetrics, _sum_over_ranks
-from .postprocess import CONF_TH, NMS_IOU, TOP_K, decode_boxes, nms_batched, proto_projector_logits
+from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision, ImageClassificationMetrics,
+                      SegmentationMetrics, _sum_over_ranks)
+from .postprocess import CONF_TH, NMS_IOU, TOP_K, decode_boxes, masks_to_frames, nms_batched, pack_masks, proto_projector_logits
 
 LOSS_NAMES = ("total", "seg", "box_iou", "dfl", "det_cls", "img_cls")       # running_main_v3.py:578-582
 
@@ -54,11 +55,16 @@ class BatchWeightedMeans:
 class ValidationStep:
     def __init__(self, model, *, projector: Optional[nn.Conv2d] = None, img_size: int = 640, iou_match_thresh: float = 0.5,
                  label_smoothing: float = 0.1, loss_weights=(1.0, 2.0, 1.5, 0.5, 1.0), conf_th: float = CONF_TH, nms_iou: float = NMS_IOU,
-                 top_k: int = TOP_K, map_max_detections: int = 100, dist_sync: bool = True, process_group=None):
+                 top_k: int = TOP_K, map_max_detections: int = 100, dist_sync: bool = True, process_group=None,
+                 instance_masks: bool = False, mask_crop: bool = True):
         """`projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1), running_main_v3.py:186); created with torch's default
         init when not given.  The loss hyper-parameters default to the reference's (and TrainStep's); `label_smoothing` is accepted for
         symmetry with TrainStep but the eval-mode loss never smooths (:337).  conf_th / nms_iou / top_k: `:54-56`;
-        `map_max_detections`: the trainer's hparam of :209-217."""
+        `map_max_detections`: the trainer's hparam of :209-217.
+        `instance_masks`: also score the Segment head's INSTANCE masks (COCO mask mAP next to the box mAP; nothing in the reference
+        computes it): the kept boxes' masks at S x S, bit-packed (`masks_to_frames` with identity frames, cropped to their boxes with
+        `mask_crop`), against per-box ground truth cut out of the image's one mask by its box rows (`pack_masks`).  Off: `step`
+        launches nothing more and `compute()` returns the reference's keys only."""
         if not hasattr(model, "detect"):
             raise NotImplementedError("ValidationStep drives the canonical model (running_main_v3.py needs .detect, SURVEY F4)")
         dev = next(model.parameters()).device
@@ -78,10 +84,14 @@ class ValidationStep:
         max_dets = (1, 10, int(map_max_detections))
         self.map50 = DeviceMeanAveragePrecision([0.5], max_dets, **sync)
         self.map50_95 = DeviceMeanAveragePrecision(None, max_dets, **sync)
+        self.instance_masks, self.mask_crop = bool(instance_masks), bool(mask_crop)
+        self.mask_map50 = DeviceMaskMeanAveragePrecision([0.5], max_dets, **sync) if self.instance_masks else None
+        self.mask_map50_95 = DeviceMaskMeanAveragePrecision(None, max_dets, **sync) if self.instance_masks else None
 
     def reset(self):
-        for m in (self.losses, self.seg, self.img, self.det_cm, self.map50, self.map50_95):
-            m.reset()
+        for m in (self.losses, self.seg, self.img, self.det_cm, self.map50, self.map50_95, self.mask_map50, self.mask_map50_95):
+            if m is not None:
+                m.reset()
 
     def forward(self, x: torch.Tensor):
         """forward(x, "train") under no_grad with the module in eval mode, as Lightning runs `validation_step`: the backbone and neck use
@@ -98,7 +108,8 @@ class ValidationStep:
 
     def step(self, imgs: torch.Tensor, det_gt: torch.Tensor, masks_gt: torch.Tensor, cls_gt: torch.Tensor):
         """One validation batch: imgs [B,3,S,S], det_gt [M,6] collated rows, masks_gt [B,1,S,S], cls_gt [B], all on the model's device.
-        Returns the eval-mode loss tuple (total, seg, box, dfl, cls_det, img_cls) as 0-d device tensors; no host synchronisation."""
+        Returns the eval-mode loss tuple (total, seg, box, dfl, cls_det, img_cls) as 0-d device tensors; no host synchronisation.
+        With `instance_masks`, masks_gt must be bool, uint8 or float32 (what `pack_masks` takes; anything else raises ValueError)."""
         if not all(t.is_cuda for t in (imgs, det_gt, masks_gt, cls_gt)):
             raise RuntimeError("ValidationStep.step: expected CUDA/HIP tensors on an MI355X (no CPU path)")
         B = imgs.shape[0]
@@ -114,7 +125,28 @@ class ValidationStep:
         k = nms_batched(d["boxes"], d["best_score"], d["best_label"], float(self.S), **self.nms_kw)
         self.map50.update_batched(k, det_gt, self.S)
         self.map50_95.update_batched(k, det_gt, self.S)
+        if self.instance_masks:
+            self._mask_update(seg_out[1], protos, k, det_gt, masks_gt)
         return losses
+
+    def _mask_update(self, mc, protos, k, det_gt, masks_gt):
+        """The instance-mask mAP's share of a step: detections' masks and per-box ground truth as packed S x S planes, one pair-count
+        pass for both threshold sets.  Device work only."""
+        S, B, K = self.S, protos.shape[0], k["scores"].shape[1]
+        r = masks_to_frames(protos, mc.float(), k["keep_anchor"], k["counts"], k["boxes"], [(S, S, 1.0)] * B, up=S / protos.shape[3], crop=self.mask_crop)
+        pitch = r["masks"][0].shape[2]
+        plane = K * S * pitch
+        # masks_to_frames starts every image on a 16-byte boundary (`_frame_layout`): the images are back to back, and the buffer is one
+        # [B, K, S, pitch] tensor, exactly when an image's K planes are a multiple of 16 bytes; otherwise the views are gathered
+        det = r["buffer"][:B * plane].view(B, K, S, pitch) if plane % 16 == 0 else torch.stack(r["masks"])
+        rows = det_gt.to(torch.float32)
+        gt_image, _ = DeviceMaskMeanAveragePrecision.gt_rows_fields(rows, B)
+        cx, cy, w, h = rows[:, 2], rows[:, 3], rows[:, 4], rows[:, 5]      # mtbt_box_eval's gt_format 0, one fp32 operation at a time
+        px = torch.stack([(cx - w / 2) * S, (cy - h / 2) * S, (cx + w / 2) * S, (cy + h / 2) * S], 1).clamp_(0, S)
+        gt = pack_masks(masks_gt[:, 0], boxes=px, plane_of=gt_image)
+        tables = DeviceMaskMeanAveragePrecision.pair_tables_uniform(det, k["counts"], gt, gt_image)
+        for m in (self.mask_map50_95, self.mask_map50):
+            m.update_uniform(det, k["scores"], k["labels"], k["counts"], gt, rows, tables=tables)
 
     def compute(self) -> Dict[str, object]:
         """The epoch's numbers under the reference's log keys (running_main_v3.py:578-582, :605-729; evaluate_model.py:244-272 for the
@@ -138,4 +170,8 @@ class ValidationStep:
             for k, v in m.compute().items():
                 out[f"{prefix}_{k}"] = v
         out["val_epoch_map_iou50/map"] = out["val_epoch/map_iou50_map"]
+        if self.instance_masks:
+            for prefix, m in (("val_epoch/mask_map_iou50_95", self.mask_map50_95), ("val_epoch/mask_map_iou50", self.mask_map50)):
+                for k, v in m.compute().items():
+                    out[f"{prefix}_{k}"] = v
         return out
