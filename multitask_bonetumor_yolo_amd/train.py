@@ -1,15 +1,18 @@
 """Training lowering of `ConvNeXtBiFPNYOLO`: forward in train mode that KEEPS what the backward pass needs, the backward
 launch plan, and the autograd boundary that lets the reference trainer's `total_loss.backward()` drive it
-(`/root/reference/src/running_main_v3.py:393-445` over `/root/reference/src/main_model.py:342-365`).
+(the reference's `running_main_v3.py:393-445` over `main_model.py:342-365`).
 
 What the forward keeps (HBM is 288 GB: nothing is recomputed, nothing is checkpointed):
   * every convolution input (its weight gradient's operand) and, per BatchNorm, the conv output it normalised plus the (mean, var) used;
   * per ConvNeXt block the depthwise output before the LayerNorm, the LayerNorm output, fc1's pre-activation (second epilogue output
     of the GEMM) and its GELU;  per fusion node the inputs.
-The backward is a static plan too: a tape of closures recorded while lowering the forward is replayed in reverse and emits C-ABI
-launches (dgrad = the forward conv kernel on dY with re-laid-out weights, `mtbt_conv_wgrad`, `mtbt_bn_backward_nhwc`, ...).  Gradient
-fan-in (C2f concat slices, ConvNeXt residuals, pyramid levels feeding six head branches) is accumulation INSIDE the producing
-kernels (residual input of the conv epilogue, `accumulate` flags) -- a residual connection is a buffer alias, not a kernel.
+The backward is a static plan too: lowering the forward records a tape of closures `fn(b)`; `backward_plan(active)` makes one
+`_BackwardPass` b -- the plan being emitted, the live gradient buffers, the parameters written, all that exists for this one plan --
+and replays the tape in reverse with it, which emits C-ABI launches (dgrad = the forward conv kernel on dY with re-laid-out weights,
+`mtbt_conv_wgrad`, `mtbt_bn_backward_nhwc`, ...).  The tape and `TrainPlan` keep nothing of a pass: any set of outputs, in any order,
+lowers to the plan a fresh `TrainPlan` would give it.  Gradient fan-in (C2f concat slices, ConvNeXt residuals, pyramid levels feeding
+six head branches) is accumulation INSIDE the producing kernels (residual input of the conv epilogue, `accumulate` flags;
+`_BackwardPass.into`) -- a residual connection is a buffer alias, not a kernel.
 
 Weights change every step, so the packed compute-dtype copies the kernels read (forward KRSC, dgrad CRSK with flipped taps, folded
 layer scale / depthwise scale) are regenerated from the fp32 master parameters by ONE table-driven launch (`mtbt_weight_prep`) at
@@ -92,14 +95,14 @@ class TPlan(Plan):
         super().__init__(device)
         self.wsp = ws
         self.lane_any = os.environ.get("MTBT_TRAIN_LANE_ANY", "1") != "0"   # eager execution only: no capture-topology restriction on cross-lane waits
-        self.cur_ws: Optional[torch.Tensor] = None
         self._late: List[torch.Tensor] = []
         self.pool.reuse = False
 
-    def _ws(self, nbytes: int) -> int:
-        """Scratch for the launch being built: returns its pointer; `self.cur_ws` (the tensor) goes into that launch's write set."""
-        self.cur_ws = self.wsp.get(nbytes)
-        return self.cur_ws.data_ptr()
+    def raw_ws(self, fn, args, nbytes: int, name, keep=(), reads=(), writes=()):
+        """`raw` for a kernel whose trailing arguments are (scratch pointer, scratch bytes): takes the next rotating buffer of the pool (one
+        `get` per launch, in launch order) and records it as written by this launch."""
+        ws = self.wsp.get(nbytes)
+        self.raw(fn, tuple(args) + (ws.data_ptr(), nbytes), name, keep=keep, reads=reads, writes=list(writes) + [ws])
 
     def release(self, a: Act):
         """Return a temporary to the pool -- a few releases LATER: handed out again at once, the buffer would tie its next writer (on the
@@ -118,35 +121,35 @@ class TPlan(Plan):
 
     def conv2(self, x: Act, w, y: Act, *, y2: Optional[Act] = None, colsum: Optional[torch.Tensor] = None, colsum_sq=False,
               colsum_shift: Optional[torch.Tensor] = None, **kw):
-        """`colsum` [K] / [2K] fp32: per-channel sums (and sums of squares) of the stored output minus `colsum_shift`, from the conv epilogue."""
+        """`colsum` [K] / [2K] fp32: per-channel sums (and sums of squares) of the stored output minus `colsum_shift`, from the conv epilogue.
+        `colsum=True`: the consumer reduces the partial rows itself (BatchNorm) -- they are returned as (buffer, rows, pitch)."""
         a = self.conv(x, w, y, **kw)
         if y2 is not None:
             assert y2.ld == y.ld and y2.bs == y.bs and y2.code == y.code
             a.y2 = y2.ptr
             self.amend(keep=(y2.buf,), writes=[y2])
-        if colsum is not None:
-            K = w.shape[0]
-            partial_only = colsum is True      # the consumer reduces the partial rows itself (BatchNorm): see colsum_partials()
-            assert K % 8 == 0 and (partial_only or (colsum.dtype == torch.float32 and colsum.numel() == K * (2 if colsum_sq else 1)))
-            nbytes = self.lib.mtbt_conv_colsum_workspace_bytes(a.N * a.Ho * a.Wo, K, int(colsum_sq))
-            a.colsum, a.colsum_sq, a.colsum_accumulate = (None if partial_only else colsum.data_ptr()), int(colsum_sq), 0
-            a.colsum_shift = colsum_shift.data_ptr() if colsum_shift is not None else None
-            if partial_only:                   # the partial rows outlive the launch: a buffer of their own (exact size), not the rotating scratch
-                a.colsum_ws, a.colsum_ws_bytes = 16, nbytes          # (placeholder for the layout query)
-                rows, pitch = C.c_int64(0), C.c_int32(0)
-                L.check(self.lib.mtbt_conv_colsum_layout(C.byref(a), C.byref(rows), C.byref(pitch)), "colsum layout")
-                nbytes = rows.value * pitch.value * 4
-                self.cs_partial = torch.empty(rows.value * pitch.value, dtype=torch.float32, device=self.device)
-                a.colsum_ws = self.cs_partial.data_ptr()
-                self.cs_layout = (self.cs_partial, rows.value, pitch.value)
-            else:
-                a.colsum_ws = self._ws(nbytes)
-                self.cs_partial = self.cur_ws
-            a.colsum_ws_bytes = nbytes
-            self.amend(keep=(colsum if not partial_only else None, colsum_shift, self.cs_partial),
-                       reads=[colsum_shift] if colsum_shift is not None else [],
-                       writes=([colsum] if not partial_only else []) + [self.cs_partial])
-        return a
+        if colsum is None:
+            return None
+        K = w.shape[0]
+        partial_only = colsum is True
+        assert K % 8 == 0 and (partial_only or (colsum.dtype == torch.float32 and colsum.numel() == K * (2 if colsum_sq else 1)))
+        nbytes = self.lib.mtbt_conv_colsum_workspace_bytes(a.N * a.Ho * a.Wo, K, int(colsum_sq))
+        a.colsum, a.colsum_sq, a.colsum_accumulate = (None if partial_only else colsum.data_ptr()), int(colsum_sq), 0
+        a.colsum_shift = colsum_shift.data_ptr() if colsum_shift is not None else None
+        layout = None
+        if partial_only:                   # the partial rows outlive the launch: a buffer of their own (exact size), not the rotating scratch
+            a.colsum_ws, a.colsum_ws_bytes = 16, nbytes          # (placeholder for the layout query)
+            rows, pitch = C.c_int64(0), C.c_int32(0)
+            L.check(self.lib.mtbt_conv_colsum_layout(C.byref(a), C.byref(rows), C.byref(pitch)), "colsum layout")
+            nbytes = rows.value * pitch.value * 4
+            part = torch.empty(rows.value * pitch.value, dtype=torch.float32, device=self.device)
+            layout = (part, rows.value, pitch.value)
+        else:
+            part = self.wsp.get(nbytes)
+        a.colsum_ws, a.colsum_ws_bytes = part.data_ptr(), nbytes
+        self.amend(keep=(colsum if not partial_only else None, colsum_shift, part), reads=[colsum_shift] if colsum_shift is not None else [],
+                   writes=([colsum] if not partial_only else []) + [part])
+        return layout
 
     @staticmethod
     def colsum_ok(K: int) -> bool:
@@ -171,8 +174,8 @@ class TPlan(Plan):
         nbytes = self.lib.mtbt_bn_train_workspace_bytes(pixels, x.C)
         g, b = _dense_vec(bn.weight, name + ".weight"), _dense_vec(bn.bias, name + ".bias")
         args = (x.ptr, y.ptr, y.ld, g.data_ptr(), b.data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), C.c_float(bn.momentum),
-                C.c_float(bn.eps), act, pixels, x.C, x.code, int(use_running), stats.data_ptr(), self._ws(nbytes), nbytes)
-        self.raw(self.lib.mtbt_bn_forward_nhwc, args, name, keep=(x.buf, y.buf, stats, bn), reads=[x], writes=[y, stats, self.cur_ws])
+                C.c_float(bn.eps), act, pixels, x.C, x.code, int(use_running), stats.data_ptr())
+        self.raw_ws(self.lib.mtbt_bn_forward_nhwc, args, nbytes, name, keep=(x.buf, y.buf, stats, bn), reads=[x], writes=[y, stats])
         self.est(3.0 * pixels * x.C * ESIZE[x.code])
 
     def bn_backward(self, dy: Act, x: Act, stats, bn, act, use_running: bool, dx: Act, dgamma, dbeta, name):
@@ -180,9 +183,9 @@ class TPlan(Plan):
         pixels = x.N * x.H * x.W
         nbytes = self.lib.mtbt_bn_backward_workspace_bytes(pixels, x.C)
         args = (dy.ptr, dy.ld, x.ptr, stats.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), C.c_float(bn.eps), act, int(use_running), dx.ptr,
-                _ptr(dgamma), _ptr(dbeta), 0, pixels, x.C, x.code, self._ws(nbytes), nbytes)
-        self.raw(self.lib.mtbt_bn_backward_nhwc, args, name, keep=(dy.buf, x.buf, stats, dx.buf, dgamma, dbeta, bn), reads=[dy, x, stats],
-                 writes=[dx, dgamma, dbeta, self.cur_ws])
+                _ptr(dgamma), _ptr(dbeta), 0, pixels, x.C, x.code)
+        self.raw_ws(self.lib.mtbt_bn_backward_nhwc, args, nbytes, name, keep=(dy.buf, x.buf, stats, dx.buf, dgamma, dbeta, bn), reads=[dy, x, stats],
+                    writes=[dx, dgamma, dbeta])
         self.est(5.0 * pixels * x.C * ESIZE[x.code])
 
     def wgrad(self, x: Act, dy: Act, out: torch.Tensor, *, R, S, pad, stride=1, dbias: Optional[torch.Tensor] = None, x_act: int = 0, name="wgrad"):
@@ -192,16 +195,14 @@ class TPlan(Plan):
         assert out.numel() == dy.C * R * S * x.C, (out.shape, dy.C, R, S, x.C)
         assert dbias is None or (dbias.numel() == dy.C and dbias.dtype == torch.float32)
         nbytes = self.lib.mtbt_conv_wgrad_workspace_bytes(x.N, max(x.H, dy.H), max(x.W, dy.W), x.C, dy.C, R, S)
-        tail = (x.N, x.H, x.W, x.C, dy.C, R, S, pad, stride, x.batch_stride, x.ld, dy.batch_stride, dy.ld, x.code, 0, self._ws(nbytes), nbytes)
+        geom = (x.N, x.H, x.W, x.C, dy.C, R, S, pad, stride, x.batch_stride, x.ld, dy.batch_stride, dy.ld, x.code)
+        outs = (out,) if dbias is None else (out, dbias)
         if x_act:
             assert dbias is None
-            args = (x.ptr, dy.ptr, out.data_ptr()) + tail[:14] + (x_act,) + tail[14:]
-            self.raw(self.lib.mtbt_conv_wgrad_xact, args, name, keep=(x.buf, dy.buf, out), reads=[x, dy], writes=[out, self.cur_ws])
-        elif dbias is None:
-            self.raw(self.lib.mtbt_conv_wgrad, (x.ptr, dy.ptr, out.data_ptr()) + tail, name, keep=(x.buf, dy.buf, out), reads=[x, dy], writes=[out, self.cur_ws])
+            fn, tail = self.lib.mtbt_conv_wgrad_xact, geom + (x_act, 0)
         else:
-            self.raw(self.lib.mtbt_conv_wgrad_bias, (x.ptr, dy.ptr, out.data_ptr(), dbias.data_ptr()) + tail, name, keep=(x.buf, dy.buf, out, dbias),
-                     reads=[x, dy], writes=[out, dbias, self.cur_ws])
+            fn, tail = (self.lib.mtbt_conv_wgrad if dbias is None else self.lib.mtbt_conv_wgrad_bias), geom + (0,)
+        self.raw_ws(fn, (x.ptr, dy.ptr) + tuple(o.data_ptr() for o in outs) + tail, nbytes, name, keep=(x.buf, dy.buf) + outs, reads=[x, dy], writes=outs)
         self.est(1.0 * dy.N * dy.H * dy.W * (dy.C + x.C) * ESIZE[x.code], 2.0 * dy.N * dy.H * dy.W * dy.C * R * S * x.C)
 
     def mlp_fused_train(self, t: Act, res: Act, w1p, b1p, w2, b2, y: Act, hpre: Act, name):
@@ -216,10 +217,8 @@ class TPlan(Plan):
         assert x.bs == x.H * x.W * x.ld and (times is None or (times.bs == times.H * times.W * times.ld and times.code == x.code))
         P = x.N * x.H * x.W
         nbytes = self.lib.mtbt_channel_sum_workspace_bytes(P, x.C)
-        args = (x.ptr, times.ptr if times is not None else None, P, x.C, x.ld, times.ld if times is not None else 0, x.code, out.data_ptr(), 0,
-                self._ws(nbytes), nbytes)
-        self.raw(self.lib.mtbt_channel_sum, args, name, keep=(x.buf, times.buf if times is not None else None, out), reads=[x, times],
-                 writes=[out, self.cur_ws])
+        args = (x.ptr, times.ptr if times is not None else None, P, x.C, x.ld, times.ld if times is not None else 0, x.code, out.data_ptr(), 0)
+        self.raw_ws(self.lib.mtbt_channel_sum, args, nbytes, name, keep=(x.buf, times.buf if times is not None else None, out), reads=[x, times], writes=[out])
         self.est(1.0 * P * x.C * ESIZE[x.code] * (2 if times is not None else 1))
 
     def ln_backward_params(self, x: Act, dy: Act, gamma: torch.Tensor, eps, dx: Act, accumulate: bool, dgamma: torch.Tensor, dbeta: torch.Tensor, name):
@@ -227,10 +226,9 @@ class TPlan(Plan):
         assert x.dense and dy.dense and dx.dense
         P = x.N * x.H * x.W
         nbytes = self.lib.mtbt_layernorm_backward_params_workspace_bytes(P, x.C)
-        args = (x.ptr, dy.ptr, gamma.data_ptr(), C.c_float(eps), dx.ptr, P, x.C, x.code, int(accumulate), dgamma.data_ptr(), dbeta.data_ptr(), 0,
-                self._ws(nbytes), nbytes)
-        self.raw(self.lib.mtbt_layernorm_backward_params_nhwc, args, name, keep=(x.buf, dy.buf, gamma, dx.buf, dgamma, dbeta),
-                 reads=[x, dy] + ([dx] if accumulate else []), writes=[dx, dgamma, dbeta, self.cur_ws])
+        args = (x.ptr, dy.ptr, gamma.data_ptr(), C.c_float(eps), dx.ptr, P, x.C, x.code, int(accumulate), dgamma.data_ptr(), dbeta.data_ptr(), 0)
+        self.raw_ws(self.lib.mtbt_layernorm_backward_params_nhwc, args, nbytes, name, keep=(x.buf, dy.buf, gamma, dx.buf, dgamma, dbeta),
+                    reads=[x, dy] + ([dx] if accumulate else []), writes=[dx, dgamma, dbeta])
         self.est(3.0 * P * x.C * ESIZE[x.code])
 
     def dwconv_t(self, x: Act, w, y: Act, ksize, *, bias=None, lnw=None, lnb=None, eps=0.0, scale=None, shift=None, act=L.ACT_NONE,
@@ -241,17 +239,14 @@ class TPlan(Plan):
         self.raw(self.lib.mtbt_dwconv_nhwc_train, args, name, keep=(x.buf, w, bias, lnw, lnb, scale, shift, y.buf, raw and raw.buf, res and res.buf),
                  reads=[x, res, w, bias, lnw, lnb, scale, shift], writes=[y, raw])
         n = x.N * x.H * x.W * x.C
-        self.launches[-1].flops, self.launches[-1].bytes = 2.0 * n * ksize * ksize, 2.0 * n * ESIZE[x.code]
+        self.est(2.0 * n * ESIZE[x.code], 2.0 * n * ksize * ksize)
 
     def dw_wgrad(self, x: Act, dy: Act, out: torch.Tensor, ksize, name, dbias: Optional[torch.Tensor] = None):
         assert x.dense and dy.dense
         nbytes = self.lib.mtbt_dwconv_wgrad_workspace_bytes(x.N, x.H, x.W, x.C, ksize)
-        tail = (x.N, x.H, x.W, x.C, ksize, x.code, 0, self._ws(nbytes), nbytes)
-        if dbias is None:
-            self.raw(self.lib.mtbt_dwconv_wgrad, (x.ptr, dy.ptr, out.data_ptr()) + tail, name, keep=(x.buf, dy.buf, out), reads=[x, dy], writes=[out, self.cur_ws])
-        else:
-            self.raw(self.lib.mtbt_dwconv_wgrad_bias, (x.ptr, dy.ptr, out.data_ptr(), dbias.data_ptr()) + tail, name, keep=(x.buf, dy.buf, out, dbias),
-                     reads=[x, dy], writes=[out, dbias, self.cur_ws])
+        fn, outs = (self.lib.mtbt_dwconv_wgrad, (out,)) if dbias is None else (self.lib.mtbt_dwconv_wgrad_bias, (out, dbias))
+        args = (x.ptr, dy.ptr) + tuple(o.data_ptr() for o in outs) + (x.N, x.H, x.W, x.C, ksize, x.code, 0)
+        self.raw_ws(fn, args, nbytes, name, keep=(x.buf, dy.buf) + outs, reads=[x, dy], writes=outs)
         self.est(6.0 * x.N * x.H * x.W * x.C * ESIZE[x.code])
 
     def copy_strided(self, src_ptr, src_code, sbs, sld, dst: Act, N, pixels, Cc, Cpad, keep, name):
@@ -273,7 +268,7 @@ def arena_specs(model, tail_prefixes: Sequence[str] = ()):
             continue
         owner = mods[name.rsplit(".", 1)[0]] if "." in name else model
         leaf = name.rsplit(".", 1)[-1]
-        kshape, back = tuple(p.shape), None
+        kshape, back = tuple(p.shape), (lambda v: v)
         if isinstance(owner, nn.ConvTranspose2d) and leaf == "weight":
             ci, co, r, s = p.shape
             kshape, back = (ci, r, s, co), (lambda v: v.permute(0, 3, 1, 2))
@@ -321,6 +316,112 @@ class _GradBuf:
         self.t, self.init, self.left = t, [], channels
 
 
+def _gkey(a: Act):
+    return a.buf.data_ptr()
+
+
+def _crange(a: Act):
+    c0 = a.off % a.ld if a.ld != a.C else 0
+    return c0, c0 + a.C
+
+
+class _BackwardPass:
+    """What exists only while ONE backward plan is emitted: the plan, the gradient buffers alive at this point of the reverse walk, the
+    parameters that received a gradient, and what a tape entry leaves for a later one.  Every tape entry is called with the pass."""
+
+    def __init__(self, tp: "TrainPlan", active: Sequence[str]):
+        self.tp, self.outputs = tp, frozenset(active)        # the outputs that carry a gradient
+        self.plan = TPlan(tp.device, tp.ws)
+        self.plan.pool.reuse = True
+        self.grads: Dict[int, _GradBuf] = {}
+        self.touched = set()                                  # names of the parameters this plan writes a gradient for
+        self.fused = set()                                    # BiFPN units whose normalised fusion weights received a gradient
+        self.memo: Dict[object, object] = {}
+
+    def once(self, key, make):
+        """`make()` the first time `key` is asked for in this pass, the same object afterwards (two tape entries sharing one operand)."""
+        if key not in self.memo:
+            self.memo[key] = make()
+        return self.memo[key]
+
+    def pg(self, p: torch.Tensor) -> torch.Tensor:
+        """Gradient slot of parameter p (kernel layout, fp32, inside a flat bucket); records that this plan writes it."""
+        name = self.tp.pname[id(p)]
+        self.touched.add(name)
+        return self.tp.arena.views[name]
+
+    def G(self, a: Act) -> Act:
+        """The gradient view matching forward activation `a` (allocated on first use)."""
+        gb = self.grads.get(_gkey(a))
+        if gb is None:
+            t = self.plan.pool.get(tuple(a.buf.shape), self.tp.dt)
+            gb = self.grads[_gkey(a)] = _GradBuf(t, a.buf.shape[-1])
+        return Act(gb.t, a.off, a.N, a.H, a.W, a.C, a.ld, a.bs)
+
+    def seed(self, a: Act, t: torch.Tensor):
+        """grad(a) := t, an input of the plan: complete, and never returned to the pool."""
+        gb = self.grads[_gkey(a)] = _GradBuf(t, a.C)
+        gb.init, gb.left = [(0, a.C)], 1 << 30
+
+    def has_grad(self, a: Act) -> bool:
+        gb = self.grads.get(_gkey(a))
+        if gb is None:
+            return False
+        c0, c1 = _crange(a)
+        return any(lo < c1 and c0 < hi for lo, hi in gb.init)
+
+    def acc(self, a: Act) -> bool:
+        """True if a's channels already hold a gradient (the writer must accumulate); marks them written."""
+        self.G(a)
+        gb = self.grads[_gkey(a)]
+        c0, c1 = _crange(a)
+        covered = [r for r in gb.init if r[0] < c1 and c0 < r[1]]
+        if covered:
+            lo, hi = min(r[0] for r in covered), max(r[1] for r in covered)
+            if not (lo <= c0 and c1 <= hi and sum(r[1] - r[0] for r in covered) >= c1 - c0):
+                raise RuntimeError("partially initialised gradient region")
+            return True
+        gb.init.append((c0, c1))
+        return False
+
+    def into(self, x: Act) -> Tuple[Act, bool]:
+        """Gradient fan-in: (grad(x), whether its writer must ACCUMULATE because an earlier consumer of x already wrote it).  Callers pass
+        `res=gx if accumulate else None` / `int(accumulate)` to the kernel and add gx to its reads when accumulating."""
+        gx = self.G(x)
+        return gx, self.acc(x)
+
+    def done(self, a: Act):
+        """a's producer has consumed its gradient: release the buffer once all channels are consumed."""
+        gb = self.grads.get(_gkey(a))
+        if gb is None:
+            return
+        gb.left -= a.C
+        if gb.left <= 0:
+            self.plan.release_buf(gb.t)
+            del self.grads[_gkey(a)]
+
+    def alias_grad(self, dst_fwd: Act, src_fwd: Act):
+        """grad(dst_fwd) := the buffer of grad(src_fwd) (a residual connection: d x = d y + ...); ownership moves."""
+        assert dst_fwd.dense and src_fwd.dense and tuple(dst_fwd.buf.shape) == tuple(src_fwd.buf.shape)
+        gb = self.grads.pop(_gkey(src_fwd))
+        gb.left = dst_fwd.C
+        gb.init = [(0, dst_fwd.C)]
+        self.grads[_gkey(dst_fwd)] = gb
+
+    def bn_tail(self, y: Act, raw: Act, st, bn, act, running: bool, name) -> Act:
+        """Head of every conv -> BatchNorm -> activation backward: consumes grad(y); returns d raw (the conv output's gradient), with d gamma
+        and d beta written on the way."""
+        d_raw = self.plan.new(raw.N, raw.H, raw.W, raw.C, self.tp.code)
+        self.plan.bn_backward(self.G(y), raw, st, bn, act, running, d_raw, self.pg(bn.weight), self.pg(bn.bias), name + ".bn.bwd")
+        self.done(y)
+        return d_raw
+
+    def dgrad(self, d_raw: Act, wd, x: Act, R, pad, name, **kw):
+        """dx (+)= conv(d_raw, wd) into grad(x) through the forward kernel (stride-1 'same' convs and 1x1)."""
+        gx, acc = self.into(x)
+        self.plan.conv2(d_raw, wd, gx, R=R, S=R, stride=1, pad=R - 1 - pad, res=gx if acc else None, name=name + ".dgrad", **kw)
+
+
 class TrainPlan:
     """Forward + backward launch plans of the canonical model for one (batch shape, compute dtype, BatchNorm-mode tuple)."""
 
@@ -341,11 +442,12 @@ class TrainPlan:
         self.x = torch.empty(self.shape, dtype=torch.float32, device=device)
         self._ones: Dict[int, torch.Tensor] = {}
         self._zeros: Dict[int, torch.Tensor] = {}
-        self._build_arena()
+        self.arena, self.as_param, self.n_tail_buckets = make_arena(model, device, self.tail_prefixes)     # parameter gradients, in the kernels' layouts
+        self.pname = {id(p): n for n, p in model.named_parameters()}
         with torch.no_grad():
             self._lower_forward()
         self._finish_prep()
-        self._bwd_cache: Dict[Tuple[bool, ...], Tuple[TPlan, List[str]]] = {}
+        self._bwd_cache: Dict[Tuple[str, ...], TPlan] = {}     # sorted active outputs -> backward plan
         self.param_ptrs = [p.data_ptr() for p in model.parameters()]
         self.use_lanes = os.environ.get("MTBT_TRAIN_LANES", "1") == "1"
 
@@ -355,25 +457,6 @@ class TrainPlan:
         for plan in [self.fwd] + list(self._bwd_cache.values()):
             plan.reload_env()
         return self
-
-    # ------------------------------------------------------------------------------------------------------------------
-    # parameter-gradient arena (kernel layouts)
-    # ------------------------------------------------------------------------------------------------------------------
-    def _build_arena(self):
-        self.arena, self._gview, self.n_tail_buckets = make_arena(self.m, self.device, self.tail_prefixes)
-        self.pname = {id(p): n for n, p in self.m.named_parameters()}
-
-    def pg(self, p: torch.Tensor) -> torch.Tensor:
-        """Gradient slot of parameter p (kernel layout, fp32, inside a flat bucket); called while a backward plan is being emitted, it
-        also records that this plan writes the slot."""
-        name = self.pname[id(p)]
-        self._touched.add(name)
-        return self.arena.views[name]
-
-    def param_grad(self, name: str) -> torch.Tensor:
-        v = self.arena.views[name]
-        back = self._gview[name]
-        return back(v) if back is not None else v
 
     # ------------------------------------------------------------------------------------------------------------------
     # weight preparation table
@@ -447,86 +530,26 @@ class TrainPlan:
         self._stats_chunks.append(t)
         return t
 
-    # ---- gradient bookkeeping (used while emitting the backward plan) ----
-    def _gkey(self, a: Act):
-        return a.buf.data_ptr()
-
-    def _crange(self, a: Act):
-        c0 = a.off % a.ld if a.ld != a.C else 0
-        return c0, c0 + a.C
-
-    def G(self, a: Act) -> Act:
-        """The gradient view matching forward activation `a` (allocated on first use)."""
-        gb = self.gmap.get(self._gkey(a))
-        if gb is None:
-            t = self.bwd.pool.get(tuple(a.buf.shape), self.dt)
-            gb = self.gmap[self._gkey(a)] = _GradBuf(t, a.buf.shape[-1])
-        return Act(gb.t, a.off, a.N, a.H, a.W, a.C, a.ld, a.bs)
-
-    def has_grad(self, a: Act) -> bool:
-        gb = self.gmap.get(self._gkey(a))
-        if gb is None:
-            return False
-        c0, c1 = self._crange(a)
-        return any(lo < c1 and c0 < hi for lo, hi in gb.init)
-
-    def acc(self, a: Act) -> bool:
-        """True if a's channels already hold a gradient (the writer must accumulate); marks them written."""
-        self.G(a)
-        gb = self.gmap[self._gkey(a)]
-        c0, c1 = self._crange(a)
-        covered = [r for r in gb.init if r[0] < c1 and c0 < r[1]]
-        if covered:
-            lo, hi = min(r[0] for r in covered), max(r[1] for r in covered)
-            if not (lo <= c0 and c1 <= hi and sum(r[1] - r[0] for r in covered) >= c1 - c0):
-                raise RuntimeError("partially initialised gradient region")
-            return True
-        gb.init.append((c0, c1))
-        return False
-
-    def done(self, a: Act):
-        """a's producer has consumed its gradient: release the buffer once all channels are consumed."""
-        gb = self.gmap.get(self._gkey(a))
-        if gb is None:
-            return
-        gb.left -= a.C
-        if gb.left <= 0:
-            self.bwd.release_buf(gb.t)
-            del self.gmap[self._gkey(a)]
-
-    def alias_grad(self, dst_fwd: Act, src_fwd: Act):
-        """grad(dst_fwd) := the buffer of grad(src_fwd) (a residual connection: d x = d y + ...); ownership moves."""
-        assert dst_fwd.dense and src_fwd.dense and tuple(dst_fwd.buf.shape) == tuple(src_fwd.buf.shape)
-        gb = self.gmap.pop(self._gkey(src_fwd))
-        gb.left = dst_fwd.C
-        gb.init = [(0, dst_fwd.C)]
-        self.gmap[self._gkey(dst_fwd)] = gb
-
     # ------------------------------------------------------------------------------------------------------------------
-    # building blocks: forward launches + a backward closure on the tape
+    # building blocks: forward launches + a backward closure on the tape, called with the `_BackwardPass` being emitted
     # ------------------------------------------------------------------------------------------------------------------
-    def _dgrad(self, d_raw: Act, wd, x: Act, R, pad, name, stride=1, **kw):
-        """dx (+)= conv(d_raw, wd) into grad(x) through the forward kernel (stride-1 'same' convs and 1x1)."""
-        gx = self.G(x)
-        acc = self.acc(x)
-        self.bwd.conv2(d_raw, wd, gx, R=R, S=R, stride=1, pad=R - 1 - pad, res=gx if acc else None, name=name + ".dgrad", **kw)
+    def _bn(self, raw: Act, y: Act, bn, act, name: str, sums=None) -> torch.Tensor:
+        """BatchNorm -> activation of `raw` into `y`; returns the (mean, var) slot the backward reads."""
+        st = self.stats(raw.C)
+        if bn.training:
+            self.train_bns.append(bn)
+        self.fwd.bn_forward(raw, y, bn, act, st, not bn.training, name + ".bn", sums=sums)
+        return st
 
     def _conv_bn(self, x: Act, wf, raw: Act, y: Act, bn, act, name: str, **conv_kw) -> torch.Tensor:
-        """conv into `raw` -> BatchNorm -> activation into `y`; returns the (mean, var) slot the backward reads."""
-        K = wf.shape[0]
-        running = not bn.training
+        """conv into `raw` -> BatchNorm -> activation into `y`; returns the (mean, var) slot."""
         # batch statistics: the conv's own epilogue accumulates sum / sum of squares of what it stores (about the running mean)
         sums = None
-        if not running and self.fwd.colsum_ok(K) and FUSED_BN_STATS:
-            self.fwd.conv2(x, wf, raw, name=name, colsum=True, colsum_sq=True, colsum_shift=bn.running_mean, **conv_kw)
-            sums = self.fwd.cs_layout
+        if bn.training and self.fwd.colsum_ok(wf.shape[0]) and FUSED_BN_STATS:
+            sums = self.fwd.conv2(x, wf, raw, name=name, colsum=True, colsum_sq=True, colsum_shift=bn.running_mean, **conv_kw)
         else:
             self.fwd.conv(x, wf, raw, name=name, **conv_kw)
-        st = self.stats(K)
-        if not running:
-            self.train_bns.append(bn)
-        self.fwd.bn_forward(raw, y, bn, act, st, running, name + ".bn", sums=sums)
-        return st
+        return self._bn(raw, y, bn, act, name, sums)
 
     def conv_bn_act(self, x: Act, mod, y: Optional[Act], act, name: str) -> Act:
         """ConvBlock (main_model.py:113-141, conv bias) / ultralytics Conv (no bias): conv -> BatchNorm -> activation."""
@@ -540,36 +563,34 @@ class TrainPlan:
             y = self.new(x.N, x.H, x.W, K)
         st = self._conv_bn(x, wf, raw, y, bn, act, name, R=k, S=k, stride=1, pad=k // 2, shift=bias)
 
-        def bwd():
-            if not self.has_grad(y):
+        def bwd(b):
+            if not b.has_grad(y):
                 return
-            d_raw = self.bwd.new(x.N, x.H, x.W, K, self.code)
-            self.bwd.bn_backward(self.G(y), raw, st, bn, act, running, d_raw, self.pg(bn.weight), self.pg(bn.bias), name + ".bn.bwd")
-            self.done(y)
+            d_raw = b.bn_tail(y, raw, st, bn, act, running, name)
             # bias gradient: running statistics -> sum_p d_raw, from the weight-gradient launch itself.  Batch statistics: sum_p d_raw = 0
             # EXACTLY (a bias in front of a batch-statistic BatchNorm cannot move the output), so the slot keeps the arena's zero --
             # autograd returns rounding noise of the order 1e-9 there
-            slot = self.pg(conv.bias) if bias is not None else None
-            self.bwd.wgrad(x, d_raw, self.pg(conv.weight), R=k, S=k, pad=k // 2, dbias=slot if running else None, name=name + ".wgrad")
-            self._dgrad(d_raw, wd, x, k, k // 2, name)
-            self.bwd.release(d_raw)
+            slot = b.pg(conv.bias) if bias is not None else None
+            b.plan.wgrad(x, d_raw, b.pg(conv.weight), R=k, S=k, pad=k // 2, dbias=slot if running else None, name=name + ".wgrad")
+            b.dgrad(d_raw, wd, x, k, k // 2, name)
+            b.plan.release(d_raw)
         self.tape.append(bwd)
         return y
 
     def conv_out(self, x: Act, conv: nn.Conv2d, y: Act, dy_src, name: str):
-        """Head output conv (Conv2d 1x1 + bias, no BN) writing a channel slice of an fp32 output map.  `dy_src()` returns the dense
+        """Head output conv (Conv2d 1x1 + bias, no BN) writing a channel slice of an fp32 output map.  `dy_src(b)` returns the dense
         compute-dtype gradient of that slice (channels zero-padded to a multiple of 8) or None when the output has no gradient."""
         K = conv.out_channels
         Kp = K if K % 8 == 0 else CLS_PAD
         wf, wd = self.w_fwd(conv.weight), self.w_dgrad(conv.weight, k_pad=Kp)
         self.fwd.conv(x, wf, y, shift=_dense_vec(conv.bias, name + ".bias"), name=name)
 
-        def bwd():
-            dy = dy_src()
+        def bwd(b):
+            dy = dy_src(b)
             if dy is None:
                 return
-            self.bwd.wgrad(x, dy, self.pg(conv.weight), R=1, S=1, pad=0, dbias=self.pg(conv.bias), name=name + ".wgrad")
-            self._dgrad(dy, wd, x, 1, 0, name)
+            b.plan.wgrad(x, dy, b.pg(conv.weight), R=1, S=1, pad=0, dbias=b.pg(conv.bias), name=name + ".wgrad")
+            b.dgrad(dy, wd, x, 1, 0, name)
         self.tape.append(bwd)
 
     def dw_bn_act(self, x: Act, mod, name: str) -> Act:
@@ -582,23 +603,16 @@ class TrainPlan:
         one, zero = self.ones(Cc)
         raw, y = self.new(x.N, x.H, x.W, Cc), self.new(x.N, x.H, x.W, Cc)
         self.fwd.dwconv_t(x, taps, raw, 3, scale=one, shift=zero, name=name)
-        st = self.stats(Cc)
-        running = not bn.training
-        if not running:
-            self.train_bns.append(bn)
-        self.fwd.bn_forward(raw, y, bn, L.ACT_SILU, st, running, name + ".bn")
+        st, running = self._bn(raw, y, bn, L.ACT_SILU, name), not bn.training
 
-        def bwd():
-            if not self.has_grad(y):
+        def bwd(b):
+            if not b.has_grad(y):
                 return
-            d_raw = self.bwd.new(x.N, x.H, x.W, Cc, self.code)
-            self.bwd.bn_backward(self.G(y), raw, st, bn, L.ACT_SILU, running, d_raw, self.pg(bn.weight), self.pg(bn.bias), name + ".bn.bwd")
-            self.done(y)
-            self.bwd.dw_wgrad(x, d_raw, self.pg(conv.weight), 3, name + ".wgrad")
-            gx = self.G(x)
-            acc = self.acc(x)
-            self.bwd.dwconv_t(d_raw, taps_f, gx, 3, scale=one, shift=zero, res=gx if acc else None, name=name + ".dgrad")
-            self.bwd.release(d_raw)
+            d_raw = b.bn_tail(y, raw, st, bn, L.ACT_SILU, running, name)
+            b.plan.dw_wgrad(x, d_raw, b.pg(conv.weight), 3, name + ".wgrad")
+            gx, acc = b.into(x)
+            b.plan.dwconv_t(d_raw, taps_f, gx, 3, scale=one, shift=zero, res=gx if acc else None, name=name + ".dgrad")
+            b.plan.release(d_raw)
         self.tape.append(bwd)
         return y
 
@@ -633,18 +647,16 @@ class TrainPlan:
         st = self._conv_bn(x, wf, raw, y, bn, L.ACT_ELU, name)
         gtmp = torch.empty(K, Cc, dtype=torch.float32, device=self.device)
 
-        def bwd():
-            if not self.has_grad(y):
+        def bwd(b):
+            if not b.has_grad(y):
                 return
-            d_raw = self.bwd.new(x.N, x.H, x.W, K, self.code)
-            self.bwd.bn_backward(self.G(y), raw, st, bn, L.ACT_ELU, running, d_raw, self.pg(bn.weight), self.pg(bn.bias), name + ".bn.bwd")
-            self.done(y)
-            self.bwd.wgrad(x, d_raw, gtmp, R=1, S=1, pad=0, name=name + ".wgrad")
-            dW, dv = self.pg(pw), self.pg(dwv)
-            self.bwd.raw(self.lib.mtbt_scale_grad, (1, gtmp.data_ptr(), pw.data_ptr(), vec.data_ptr(), None, None, dW.data_ptr(), dv.data_ptr(), None,
+            d_raw = b.bn_tail(y, raw, st, bn, L.ACT_ELU, running, name)
+            b.plan.wgrad(x, d_raw, gtmp, R=1, S=1, pad=0, name=name + ".wgrad")
+            dW, dv = b.pg(pw), b.pg(dwv)
+            b.plan.raw(self.lib.mtbt_scale_grad, (1, gtmp.data_ptr(), pw.data_ptr(), vec.data_ptr(), None, None, dW.data_ptr(), dv.data_ptr(), None,
                                                     K, Cc, 0), name + ".scale_grad", keep=(gtmp, pw, vec, dW, dv), reads=[gtmp], writes=[dW, dv])
-            self._dgrad(d_raw, wd, x, 1, 0, name)
-            self.bwd.release(d_raw)
+            b.dgrad(d_raw, wd, x, 1, 0, name)
+            b.plan.release(d_raw)
         self.tape.append(bwd)
         return y
 
@@ -659,20 +671,19 @@ class TrainPlan:
                 C.c_float(body.stem_1.eps), a.ptr, raw0.ptr, N, H, W, a.C, T)
         self.fwd.raw(self.lib.mtbt_stem_conv4x4_ln_train, args, "backbone.body.stem", keep=(self.x, w0, a.buf, raw0.buf), reads=[self.x], writes=[a, raw0])
 
-        def stem_bwd(a=a, raw0=raw0):
-            if not self.has_grad(a):
+        def stem_bwd(b, a=a, raw0=raw0):
+            if not b.has_grad(a):
                 return
-            d_raw = self.bwd.new(a.N, a.H, a.W, a.C, T)
-            self.bwd.ln_backward_params(raw0, self.G(a), body.stem_1.weight, body.stem_1.eps, d_raw, False, self.pg(body.stem_1.weight),
-                                        self.pg(body.stem_1.bias), "stem.ln.bwd")
-            self.done(a)
-            self.bwd.channel_sum(d_raw, self.pg(st0.bias), name="stem.dbias")
-            nbytes = self.lib.mtbt_stem_wgrad_workspace_bytes(a.C)
-            dW = self.pg(st0.weight)
-            self.bwd.raw(self.lib.mtbt_stem_wgrad, (self.x.data_ptr(), d_raw.ptr, dW.data_ptr(), N, H, W, a.C, T, 0, self.bwd._ws(nbytes), nbytes),
-                         "stem.wgrad", keep=(self.x, d_raw.buf, dW), reads=[self.x, d_raw], writes=[dW, self.bwd.cur_ws])
-            self.bwd.est(1.0 * N * 3 * H * W * 4)
-            self.bwd.release(d_raw)
+            d_raw = b.plan.new(a.N, a.H, a.W, a.C, T)
+            b.plan.ln_backward_params(raw0, b.G(a), body.stem_1.weight, body.stem_1.eps, d_raw, False, b.pg(body.stem_1.weight),
+                                      b.pg(body.stem_1.bias), "stem.ln.bwd")
+            b.done(a)
+            b.plan.channel_sum(d_raw, b.pg(st0.bias), name="stem.dbias")
+            dW = b.pg(st0.weight)
+            b.plan.raw_ws(self.lib.mtbt_stem_wgrad, (self.x.data_ptr(), d_raw.ptr, dW.data_ptr(), N, H, W, a.C, T, 0),
+                          self.lib.mtbt_stem_wgrad_workspace_bytes(a.C), "stem.wgrad", keep=(self.x, d_raw.buf, dW), reads=[self.x, d_raw], writes=[dW])
+            b.plan.est(1.0 * N * 3 * H * W * 4)
+            b.plan.release(d_raw)
         self.tape.append(stem_bwd)
 
         feats = []
@@ -699,18 +710,17 @@ class TrainPlan:
         wd = self.prep_w(w, (2, 2, a.C, K), (w.stride(2), w.stride(3), w.stride(1), w.stride(0))).view(4 * a.C, K)   # OUT_CONVT2X2 rows (r,s,c)
         self.fwd.conv(t, wf, nxt, R=2, S=2, stride=2, pad=0, shift=_dense_vec(cv.bias, name), name=name + ".1")
 
-        def bwd():
-            if not self.has_grad(nxt):
+        def bwd(b):
+            if not b.has_grad(nxt):
                 return
-            dy = self.G(nxt)
-            self.bwd.wgrad(t, dy, self.pg(cv.weight), R=2, S=2, pad=0, stride=2, dbias=self.pg(cv.bias), name=name + ".1.wgrad")
-            d_t = self.bwd.new(a.N, a.H, a.W, a.C, T)
-            self.bwd.conv2(dy, wd, d_t, out_mode=L.OUT_CONVT2X2, name=name + ".1.dgrad")
-            self.done(nxt)
-            ga = self.G(a)
-            acc = self.acc(a)
-            self.bwd.ln_backward_params(a, d_t, ln.weight, ln.eps, ga, acc, self.pg(ln.weight), self.pg(ln.bias), name + ".0.bwd")
-            self.bwd.release(d_t)
+            dy = b.G(nxt)
+            b.plan.wgrad(t, dy, b.pg(cv.weight), R=2, S=2, pad=0, stride=2, dbias=b.pg(cv.bias), name=name + ".1.wgrad")
+            d_t = b.plan.new(a.N, a.H, a.W, a.C, T)
+            b.plan.conv2(dy, wd, d_t, out_mode=L.OUT_CONVT2X2, name=name + ".1.dgrad")
+            b.done(nxt)
+            ga, acc = b.into(a)
+            b.plan.ln_backward_params(a, d_t, ln.weight, ln.eps, ga, acc, b.pg(ln.weight), b.pg(ln.bias), name + ".0.bwd")
+            b.plan.release(d_t)
         self.tape.append(bwd)
         return nxt
 
@@ -758,42 +768,42 @@ class TrainPlan:
         ssum = torch.empty(d, dtype=torch.float32, device=self.device)
         one, zero = self.ones(d)
 
-        def bwd():
-            if not self.has_grad(y):
+        def bwd(b):
+            if not b.has_grad(y):
                 return
-            dy = self.G(y)
+            dy = b.G(y)
             # (sum_p dy and the fc1 bias gradient stay separate channel sums: in these GEMM-shaped weight gradients EVERY workgroup would
             #  carry the 25 % extra MFMAs of the fused form -- measured +2.0 ms against the 2.8 ms of the two sums)
-            self.bwd.channel_sum(dy, ssum, name=name + ".sum_dy")
+            b.plan.channel_sum(dy, ssum, name=name + ".sum_dy")
             if fused_mlp:
-                self.bwd.wgrad(hpre, dy, gtmp, R=1, S=1, pad=0, x_act=L.ACT_GELU_POLY, name=name + ".fc2.wgrad")
+                b.plan.wgrad(hpre, dy, gtmp, R=1, S=1, pad=0, x_act=L.ACT_GELU_POLY, name=name + ".fc2.wgrad")
             else:
-                self.bwd.wgrad(h, dy, gtmp, R=1, S=1, pad=0, name=name + ".fc2.wgrad")
-            dW2, dg, db2 = self.pg(fc2.weight), self.pg(gamma), self.pg(fc2.bias)
-            self.bwd.raw(self.lib.mtbt_scale_grad, (0, gtmp.data_ptr(), fc2.weight.data_ptr(), gamma.data_ptr(), fc2.bias.data_ptr(), ssum.data_ptr(),
+                b.plan.wgrad(h, dy, gtmp, R=1, S=1, pad=0, name=name + ".fc2.wgrad")
+            dW2, dg, db2 = b.pg(fc2.weight), b.pg(gamma), b.pg(fc2.bias)
+            b.plan.raw(self.lib.mtbt_scale_grad, (0, gtmp.data_ptr(), fc2.weight.data_ptr(), gamma.data_ptr(), fc2.bias.data_ptr(), ssum.data_ptr(),
                                                     dW2.data_ptr(), dg.data_ptr(), db2.data_ptr(), d, 4 * d, 0), name + ".fc2.scale_grad",
                          keep=(gtmp, ssum, dW2, dg, db2), reads=[gtmp, ssum], writes=[dW2, dg, db2])
-            d_hpre = self.bwd.new(N, H, W, 4 * d, T)
+            d_hpre = b.plan.new(N, H, W, 4 * d, T)
             # (d fc1.bias = sum_p d_hpre comes out of the same launch: column sums in the epilogue instead of a pass over the 4d-wide tensor)
-            fused_db = self.bwd.colsum_ok(4 * d) and FUSED_BN_STATS
-            self.bwd.conv2(dy, w2d, d_hpre, act=L.ACT_DGELU_POLY if poly else L.ACT_DGELU, res=hpre, name=name + ".fc2.dgrad*gelu'", colsum=self.pg(fc1.bias).view(-1) if fused_db else None)
-            self.bwd.wgrad(t, d_hpre, self.pg(fc1.weight), R=1, S=1, pad=0, name=name + ".fc1.wgrad")
+            fused_db = b.plan.colsum_ok(4 * d) and FUSED_BN_STATS
+            b.plan.conv2(dy, w2d, d_hpre, act=L.ACT_DGELU_POLY if poly else L.ACT_DGELU, res=hpre, name=name + ".fc2.dgrad*gelu'", colsum=b.pg(fc1.bias).view(-1) if fused_db else None)
+            b.plan.wgrad(t, d_hpre, b.pg(fc1.weight), R=1, S=1, pad=0, name=name + ".fc1.wgrad")
             if not fused_db:
-                self.bwd.channel_sum(d_hpre, self.pg(fc1.bias), name=name + ".fc1.dbias")
-            d_t = self.bwd.new(N, H, W, d, T)
-            self.bwd.conv2(d_hpre, w1d, d_t, name=name + ".fc1.dgrad")
-            self.bwd.release(d_hpre)
-            d_r = self.bwd.new(N, H, W, d, T)
-            self.bwd.ln_backward_params(r, d_t, blk.norm.weight, blk.norm.eps, d_r, False, self.pg(blk.norm.weight), self.pg(blk.norm.bias), name + ".norm.bwd")
-            self.bwd.release(d_t)
-            self.bwd.dw_wgrad(cur, d_r, self.pg(dw), 7, name + ".conv_dw.wgrad", dbias=self.pg(blk.conv_dw.bias))
+                b.plan.channel_sum(d_hpre, b.pg(fc1.bias), name=name + ".fc1.dbias")
+            d_t = b.plan.new(N, H, W, d, T)
+            b.plan.conv2(d_hpre, w1d, d_t, name=name + ".fc1.dgrad")
+            b.plan.release(d_hpre)
+            d_r = b.plan.new(N, H, W, d, T)
+            b.plan.ln_backward_params(r, d_t, blk.norm.weight, blk.norm.eps, d_r, False, b.pg(blk.norm.weight), b.pg(blk.norm.bias), name + ".norm.bwd")
+            b.plan.release(d_t)
+            b.plan.dw_wgrad(cur, d_r, b.pg(dw), 7, name + ".conv_dw.wgrad", dbias=b.pg(blk.conv_dw.bias))
             # residual: d cur = d y + dwconv^T(d_r) -- grad(y)'s buffer BECOMES grad(cur), the depthwise dgrad accumulates into it
-            if self.has_grad(cur):
+            if b.has_grad(cur):
                 raise NotImplementedError("a ConvNeXt block input with a second consumer")
-            self.alias_grad(cur, y)
-            gc = self.G(cur)
-            self.bwd.dwconv_t(d_r, taps_f, gc, 7, scale=one, shift=zero, res=gc, name=name + ".conv_dw.dgrad")
-            self.bwd.release(d_r)
+            b.alias_grad(cur, y)
+            gc = b.G(cur)
+            b.plan.dwconv_t(d_r, taps_f, gc, 7, scale=one, shift=zero, res=gc, name=name + ".conv_dw.dgrad")
+            b.plan.release(d_r)
         self.tape.append(bwd)
         return y
 
@@ -813,36 +823,35 @@ class TrainPlan:
             self.fwd.raw(self.lib.mtbt_bifpn_norm_weights, (w1.data_ptr(), 2, C.c_float(u.eps), wn1.data_ptr()), nm + ".w1.norm", keep=(w1, wn1), writes=[wn1])
             self.fwd.raw(self.lib.mtbt_bifpn_norm_weights, (w2.data_ptr(), 3, C.c_float(u.eps), wn2.data_ptr()), nm + ".w2.norm", keep=(w2, wn2), writes=[wn2])
 
-            def norm_bwd(u=u, w1=w1, w2=w2, dwn1=dwn1, dwn2=dwn2, nm=nm):
-                if not getattr(self, "_fuse_touched", {}).get(nm):
+            def norm_bwd(b, u=u, w1=w1, w2=w2, dwn1=dwn1, dwn2=dwn2, nm=nm):
+                if nm not in b.fused:
                     return
-                g1, g2 = self.pg(u.w1), self.pg(u.w2)
-                self.bwd.raw(self.lib.mtbt_bifpn_norm_weights_backward, (w1.data_ptr(), 2, C.c_float(u.eps), dwn1.data_ptr(), g1.data_ptr(), 0),
-                             nm + ".w1.norm.bwd", keep=(w1, dwn1, g1), reads=[dwn1], writes=[g1])
-                self.bwd.raw(self.lib.mtbt_bifpn_norm_weights_backward, (w2.data_ptr(), 3, C.c_float(u.eps), dwn2.data_ptr(), g2.data_ptr(), 0),
-                             nm + ".w2.norm.bwd", keep=(w2, dwn2, g2), reads=[dwn2], writes=[g2])
+                g1, g2 = b.pg(u.w1), b.pg(u.w2)
+                b.plan.raw(self.lib.mtbt_bifpn_norm_weights_backward, (w1.data_ptr(), 2, C.c_float(u.eps), dwn1.data_ptr(), g1.data_ptr(), 0),
+                           nm + ".w1.norm.bwd", keep=(w1, dwn1, g1), reads=[dwn1], writes=[g1])
+                b.plan.raw(self.lib.mtbt_bifpn_norm_weights_backward, (w2.data_ptr(), 3, C.c_float(u.eps), dwn2.data_ptr(), g2.data_ptr(), 0),
+                           nm + ".w2.norm.bwd", keep=(w2, dwn2, g2), reads=[dwn2], writes=[g2])
             self.tape.append(norm_bwd)
 
             def node(inputs, wn, dwn, col, n, modes, like, conv, cf, tag, nm=nm):
                 s = self.new(like.N, like.H, like.W, like.C)
                 self.fwd.fuse(inputs, [0.0] * len(inputs), modes, s, name=f"{nm}.{tag}.fuse", wgt_dev=wn, wgt_first=col * n)
 
-                def bwd():
-                    if not self.has_grad(s):
+                def bwd(b):
+                    if not b.has_grad(s):
                         return
-                    self.__dict__.setdefault("_fuse_touched", {})[nm] = True
-                    ds = self.G(s)
+                    b.fused.add(nm)
+                    ds = b.G(s)
                     nbytes = self.lib.mtbt_bifpn_fuse_backward_workspace_bytes()
                     for i, (xin, mode) in enumerate(zip(inputs, modes)):
-                        gx = self.G(xin)
-                        acc = self.acc(xin)
+                        gx, acc = b.into(xin)
                         # the same tensor may enter a node twice (p5_out: w*p5 + w*p5 + ..., main_model.py:236-240): its weight gradients are separate
                         args = (ds.ptr, xin.ptr, mode, wn.data_ptr() + 4 * (col * n + i), gx.ptr, int(acc), dwn.data_ptr() + 4 * (col * n + i), 0,
-                                s.N, s.H, s.W, s.C, self.code, self.bwd._ws(nbytes), nbytes)
-                        self.bwd.raw(self.lib.mtbt_bifpn_fuse_backward, args, f"{nm}.{tag}.fuse.bwd{i}", keep=(ds.buf, xin.buf, wn, gx.buf, dwn),
-                                     reads=[ds, xin, wn] + ([gx] if acc else []), writes=[gx, dwn, self.bwd.cur_ws])
-                        self.bwd.est(2.0 * s.N * s.H * s.W * s.C * ESIZE[self.code])
-                    self.done(s)
+                                s.N, s.H, s.W, s.C, self.code)
+                        b.plan.raw_ws(self.lib.mtbt_bifpn_fuse_backward, args, nbytes, f"{nm}.{tag}.fuse.bwd{i}", keep=(ds.buf, xin.buf, wn, gx.buf, dwn),
+                                      reads=[ds, xin, wn] + ([gx] if acc else []), writes=[gx, dwn])
+                        b.plan.est(2.0 * s.N * s.H * s.W * s.C * ESIZE[self.code])
+                    b.done(s)
                 self.tape.append(bwd)
                 dd = self.dw_pointwise(s, conv, f"{nm}.{tag}_conv")
                 return self.c2f(dd, cf, f"{nm}.{tag}_cf")
@@ -873,24 +882,23 @@ class TrainPlan:
                 s_ = self.new(like.N, like.H, like.W, like.C)
                 self.fwd.fuse(inputs, [0.0] * n, modes, s_, bug=True, name=f"{nm}.add_{key}", wgt_dev=wn)
 
-                def bwd():
-                    if not self.has_grad(s_):
+                def bwd(b):
+                    if not b.has_grad(s_):
                         return
-                    ds = self.G(s_)
+                    ds = b.G(s_)
                     # d w: the node adds s / (s + eps) to EVERY element, so d w_j = [w_j > 0] eps / (s + eps)^2 sum(dy)
                     cs = torch.zeros(s_.C, dtype=torch.float32, device=self.device)
-                    self.bwd.channel_sum(ds, cs, name=f"{nm}.add_{key}.dysum")
-                    gw = self.pg(add.w)
-                    self.bwd.raw(self.lib.mtbt_wadd_norm_weights_backward, (w.data_ptr(), n, C.c_float(add.eps), cs.data_ptr(), s_.C, gw.data_ptr(), 0),
-                                 f"{nm}.add_{key}.norm.bwd", keep=(w, cs, gw), reads=[w, cs], writes=[gw])
+                    b.plan.channel_sum(ds, cs, name=f"{nm}.add_{key}.dysum")
+                    gw = b.pg(add.w)
+                    b.plan.raw(self.lib.mtbt_wadd_norm_weights_backward, (w.data_ptr(), n, C.c_float(add.eps), cs.data_ptr(), s_.C, gw.data_ptr(), 0),
+                               f"{nm}.add_{key}.norm.bwd", keep=(w, cs, gw), reads=[w, cs], writes=[gw])
                     for i, (xin, mode) in enumerate(zip(inputs, modes)):
-                        gx = self.G(xin)
-                        acc = self.acc(xin)
+                        gx, acc = b.into(xin)
                         args = (ds.ptr, xin.ptr, mode, gx.ptr, int(acc), s_.N, s_.H, s_.W, s_.C, self.code)
-                        self.bwd.raw(self.lib.mtbt_resample_backward, args, f"{nm}.add_{key}.bwd{i}", keep=(ds.buf, xin.buf, gx.buf),
-                                     reads=[ds, xin] + ([gx] if acc else []), writes=[gx])
-                        self.bwd.est(2.0 * s_.N * s_.H * s_.W * s_.C * ESIZE[self.code])
-                    self.done(s_)
+                        b.plan.raw(self.lib.mtbt_resample_backward, args, f"{nm}.add_{key}.bwd{i}", keep=(ds.buf, xin.buf, gx.buf),
+                                   reads=[ds, xin] + ([gx] if acc else []), writes=[gx])
+                        b.plan.est(2.0 * s_.N * s_.H * s_.W * s_.C * ESIZE[self.code])
+                    b.done(s_)
                 self.tape.append(bwd)
                 return self.dw_bn_act(s_, u.conv[key], f"{nm}.conv.{key}")
 
@@ -913,31 +921,27 @@ class TrainPlan:
         for i, f in enumerate(feats):
             full = Act.of(self._f32(f.N, f.H, f.W, head.no))
             dfull = Act.of(self._f32(f.N, f.H, f.W, head.no))
-            holder = {}
 
-            def split(f=f, dfull=dfull, holder=holder, i=i):
-                """(once per backward plan) dense gradient operands of the two output convs"""
-                if key not in self.active:
-                    return None
-                if "box" not in holder:
-                    box = self.bwd.new(f.N, f.H, f.W, nb, self.code)
-                    cls = self.bwd.new(f.N, f.H, f.W, CLS_PAD if head.nc % 8 else head.nc, self.code)
+            def split(b, which, f=f, dfull=dfull, i=i):
+                """dense gradient operand of the box (0) / class (1) output conv; both are made once per backward plan"""
+                def make():
+                    box = b.plan.new(f.N, f.H, f.W, nb, self.code)
+                    cls = b.plan.new(f.N, f.H, f.W, CLS_PAD if head.nc % 8 else head.nc, self.code)
                     P = f.H * f.W
-                    self.bwd.copy_strided(dfull.ptr, L.F32, dfull.bs, dfull.ld, box, f.N, P, nb, nb, (dfull.buf,), f"{tag}.{i}.dbox")
-                    self.bwd.copy_strided(dfull.ptr + 4 * nb, L.F32, dfull.bs, dfull.ld, cls, f.N, P, head.nc, cls.C, (dfull.buf,), f"{tag}.{i}.dcls")
-                    holder["box"], holder["cls"] = box, cls
-                return holder
+                    b.plan.copy_strided(dfull.ptr, L.F32, dfull.bs, dfull.ld, box, f.N, P, nb, nb, (dfull.buf,), f"{tag}.{i}.dbox")
+                    b.plan.copy_strided(dfull.ptr + 4 * nb, L.F32, dfull.bs, dfull.ld, cls, f.N, P, head.nc, cls.C, (dfull.buf,), f"{tag}.{i}.dcls")
+                    return box, cls
+                return b.once((tag, i), make)[which] if key in b.outputs else None
             sq = head.cv2[i]
             t1 = self.conv_bn_act(f, sq[0], None, L.ACT_SILU, f"{tag}.cv2.{i}.0")
             t2 = self.conv_bn_act(t1, sq[1], None, L.ACT_SILU, f"{tag}.cv2.{i}.1")
-            self.conv_out(t2, sq[2], full.slice(0, nb), (lambda split=split: (split() or {}).get("box")), f"{tag}.cv2.{i}.2")
+            self.conv_out(t2, sq[2], full.slice(0, nb), (lambda b, split=split: split(b, 0)), f"{tag}.cv2.{i}.2")
             sq = head.cv3[i]
             d1 = self.dw_bn_act(f, sq[0][0], f"{tag}.cv3.{i}.0.0")
             u1 = self.conv_bn_act(d1, sq[0][1], None, L.ACT_SILU, f"{tag}.cv3.{i}.0.1")
             d2 = self.dw_bn_act(u1, sq[1][0], f"{tag}.cv3.{i}.1.0")
             u2 = self.conv_bn_act(d2, sq[1][1], None, L.ACT_SILU, f"{tag}.cv3.{i}.1.1")
-            self.conv_out(u2, sq[2], full.slice(nb, head.nc), (lambda split=split: (split() or {}).get("cls")), f"{tag}.cv3.{i}.2")
-            self._holders.append(holder)
+            self.conv_out(u2, sq[2], full.slice(nb, head.nc), (lambda b, split=split: split(b, 1)), f"{tag}.cv3.{i}.2")
             maps.append(full)
             dmaps.append(dfull)
         self.d_in[key] = dmaps
@@ -954,19 +958,15 @@ class TrainPlan:
             t1 = self.conv_bn_act(f, sq[0], None, L.ACT_SILU, f"segment.cv4.{i}.0")
             t2 = self.conv_bn_act(t1, sq[1], None, L.ACT_SILU, f"segment.cv4.{i}.1")
             lvl = Act(mc, off * head.nm, N, f.H, f.W, head.nm, head.nm, A * head.nm)
-            holder = {}
 
-            def dsrc(f=f, off=off, holder=holder, i=i):
-                if "mc" not in self.active:
+            def dsrc(b, f=f, off=off, i=i):
+                if "mc" not in b.outputs:
                     return None
-                if "d" not in holder:
-                    d = self.bwd.new(f.N, f.H, f.W, head.nm, self.code)
-                    self.bwd.copy_strided(dmc.data_ptr() + 4 * off * head.nm, L.F32, A * head.nm, head.nm, d, f.N, f.H * f.W, head.nm, head.nm, (dmc,),
-                                          f"segment.cv4.{i}.dmc")
-                    holder["d"] = d
-                return holder["d"]
+                d = b.plan.new(f.N, f.H, f.W, head.nm, self.code)
+                b.plan.copy_strided(dmc.data_ptr() + 4 * off * head.nm, L.F32, A * head.nm, head.nm, d, f.N, f.H * f.W, head.nm, head.nm, (dmc,),
+                                    f"segment.cv4.{i}.dmc")
+                return d
             self.conv_out(t2, sq[2], lvl, dsrc, f"segment.cv4.{i}.2")
-            self._holders.append(holder)
             off += f.H * f.W
         self.d_in["mc"] = dmc
         # Proto on P3: Conv 3x3 -> ConvTranspose2d(2, 2, bias) -> Conv 3x3 -> Conv 1x1 (each Conv = conv + BN + SiLU)
@@ -981,17 +981,16 @@ class TrainPlan:
         bias4 = self.prep_w(ub, (1, 1, 4, Co), (0, 0, 0, 1), dtype=torch.float32).view(4 * Co)
         self.fwd.conv(t1, wf, up, shift=bias4, out_mode=L.OUT_CONVT2X2, name="segment.proto.upsample")
 
-        def up_bwd():
-            if not self.has_grad(up):
+        def up_bwd(b):
+            if not b.has_grad(up):
                 return
-            dy = self.G(up)
+            dy = b.G(up)
             # dW[ci][dy][dx][co] = sum_p X[p][ci] * dY[2p + (dy,dx)][co]: the 2x2 / stride-2 weight gradient with the operand roles swapped
-            self.bwd.wgrad(dy, t1, self.pg(wt), R=2, S=2, pad=0, stride=2, name="segment.proto.upsample.wgrad")
-            self.bwd.channel_sum(dy, self.pg(ub), name="segment.proto.upsample.dbias")
-            g1 = self.G(t1)
-            acc = self.acc(t1)
-            self.bwd.conv2(dy, wd, g1, R=2, S=2, stride=2, pad=0, res=g1 if acc else None, name="segment.proto.upsample.dgrad")
-            self.done(up)
+            b.plan.wgrad(dy, t1, b.pg(wt), R=2, S=2, pad=0, stride=2, name="segment.proto.upsample.wgrad")
+            b.plan.channel_sum(dy, b.pg(ub), name="segment.proto.upsample.dbias")
+            g1, acc = b.into(t1)
+            b.plan.conv2(dy, wd, g1, R=2, S=2, stride=2, pad=0, res=g1 if acc else None, name="segment.proto.upsample.dgrad")
+            b.done(up)
         self.tape.append(up_bwd)
         t2 = self.conv_bn_act(up, pr.cv2, None, L.ACT_SILU, "segment.proto.cv2")
         pT = self.conv_bn_act(t2, pr.cv3, None, L.ACT_SILU, "segment.proto.cv3")
@@ -1003,12 +1002,10 @@ class TrainPlan:
             self.fwd.cast(pT, protos, name="segment.proto.cast")
         self.d_in["protos"] = torch.zeros(tuple(pT.buf.shape), dtype=self.dt, device=self.device)
 
-        def protos_seed():
-            if "protos" not in self.active:
-                return
-            self.gmap[self._gkey(pT)] = gb = _GradBuf(self.d_in["protos"], pT.C)
-            gb.init = [(0, pT.C)]
-            gb.left = 1 << 30                                               # plan input: never returned to the pool
+
+        def protos_seed(b):
+            if "protos" in b.outputs:
+                b.seed(pT, self.d_in["protos"])
         self.tape.append(protos_seed)
         return mc, protos
 
@@ -1021,24 +1018,21 @@ class TrainPlan:
         pool_ws = self._f32(n5.N, n5.C)
         self.d_in["logits"] = dlog
 
-        def bwd():
-            if "logits" not in self.active:
+        def bwd(b):
+            if "logits" not in b.outputs:
                 return
-            g5 = self.G(n5)
-            acc = self.acc(n5)
-            dW, db = self.pg(fc.weight), self.pg(fc.bias)
+            g5, acc = b.into(n5)
+            dW, db = b.pg(fc.weight), b.pg(fc.bias)
             args = (n5.ptr, dlog.data_ptr(), w.data_ptr(), g5.ptr, int(acc), dW.data_ptr(), db.data_ptr(), 0, pool_ws.data_ptr(), n5.N, n5.H * n5.W, n5.C,
                     fc.out_features, self.code)
-            self.bwd.raw(self.lib.mtbt_gap_fc_backward, args, "cls_fc.bwd", keep=(n5.buf, dlog, w, g5.buf, dW, db, pool_ws),
-                         reads=[n5, dlog] + ([g5] if acc else []), writes=[g5, dW, db, pool_ws])
+            b.plan.raw(self.lib.mtbt_gap_fc_backward, args, "cls_fc.bwd", keep=(n5.buf, dlog, w, g5.buf, dW, db, pool_ws),
+                       reads=[n5, dlog] + ([g5] if acc else []), writes=[g5, dW, db, pool_ws])
         self.tape.append(bwd)
         return logits
 
     # ------------------------------------------------------------------------------------------------------------------
     def _lower_forward(self):
         self.d_in: Dict[str, object] = {}
-        self._holders: List[dict] = []
-        self.active = set()
         m = self.m
         bb = m.backbone
         f3, f4, f5 = self.features(bb.body)
@@ -1058,23 +1052,14 @@ class TrainPlan:
     def backward_plan(self, active: Sequence[str]) -> TPlan:
         """The backward launch plan for the set of outputs that carry a gradient (built once per set)."""
         key = tuple(sorted(active))
-        hit = self._bwd_cache.get(key)
-        if hit is not None:
-            return hit
-        self.active = set(active)
-        self.bwd = TPlan(self.device, self.ws)
-        self.bwd.pool.reuse = True
-        self.gmap: Dict[int, _GradBuf] = {}
-        self.__dict__["_fuse_touched"] = {}
-        self._touched = set()
-        for h in self._holders:
-            h.clear()
-        with torch.no_grad():
-            for fn in reversed(self.tape):
-                fn()
-        plan = self.bwd
-        plan.written = sorted(self._touched)      # parameters this plan produces a gradient for (the others stay None / zero: SURVEY F13)
-        self._bwd_cache[key] = plan
+        plan = self._bwd_cache.get(key)
+        if plan is None:
+            b = _BackwardPass(self, key)
+            with torch.no_grad():
+                for fn in reversed(self.tape):
+                    fn(b)
+            plan = self._bwd_cache[key] = b.plan
+            plan.written = sorted(b.touched)      # parameters this plan produces a gradient for (the others stay None / zero: SURVEY F13)
         return plan
 
     # ------------------------------------------------------------------------------------------------------------------
@@ -1153,7 +1138,7 @@ class _TrainFn(torch.autograd.Function):
         # depthwise weights, the class bias), and the next backward pass rewrites the arena in place -- `.grad += new` would then add a
         # buffer to itself (gradient accumulation, `zero_grad(set_to_none=False)`, two losses through one forward).
         snap = tp.arena.snapshot_views([n for n, p in tp.m.named_parameters() if p.requires_grad and n in written])
-        grads = tuple((tp._gview[n](snap[n]) if tp._gview[n] is not None else snap[n]) if n in snap else None for n, p in tp.m.named_parameters())
+        grads = tuple(tp.as_param[n](snap[n]) if n in snap else None for n, p in tp.m.named_parameters())
         return (None, None, None) + grads
 
 

@@ -81,8 +81,7 @@ class TrainStep:
             for name, p in model.named_parameters():
                 if not p.requires_grad:
                     continue
-                v = self.params.views[name]
-                v = gview[name](v) if gview[name] is not None else v
+                v = gview[name](self.params.views[name])
                 v.copy_(p.data)
                 p.data = v
             if self.world > 1:

@@ -11,6 +11,7 @@ Run as a script it prints the full record of one case, so that the records of tw
     python tests/plan_signature.py canonical-bf16-merged
 """
 import bisect
+import contextlib
 import ctypes as C
 import hashlib
 import itertools
@@ -183,7 +184,21 @@ def inference_cases():
     return cases
 
 
-TRAINING_CASES = {"train-canonical-bf16": ("canonical", "bf16"), "train-canonical-fp32": ("canonical", "fp32"), "train-v0-fp32": ("v0", "fp32")}
+def _training_case(variant, dtype, active=None, bn_eval=False, tail=False, **switches):
+    """`active`: the outputs that carry a gradient (None: all five, and the entry holds the forward plan too); `bn_eval`: every BatchNorm2d
+    in eval mode; `tail`: `tail_prefixes` = what the native training step passes; `switches`: module attributes of `train` for the lowering."""
+    return {"variant": variant, "dtype": dtype, "active": active, "bn_eval": bn_eval, "tail": tail, "switches": switches}
+
+
+SUBSETS = {"step": ("det", "logits", "protos"), "logits": ("logits",), "segmc": ("seg", "mc"), "protos": ("protos",)}
+TRAINING_CASES = {
+    "train-canonical-bf16": _training_case("canonical", "bf16"), "train-canonical-fp32": _training_case("canonical", "fp32"),
+    "train-v0-fp32": _training_case("v0", "fp32"),
+    "train-v2-fp32": _training_case("v2", "fp32"),
+    "train-canonical-fp32-bneval": _training_case("canonical", "fp32", bn_eval=True),
+    "train-canonical-bf16-tail": _training_case("canonical", "bf16", tail=True),
+    "train-canonical-bf16-unfused": _training_case("canonical", "bf16", FUSED_BN_STATS=False, FUSED_TRAIN_MLP=False),
+    **{f"train-canonical-bf16-{k}": _training_case("canonical", "bf16", active=a) for k, a in SUBSETS.items()}}
 
 
 def make_model(variant, dtype, options=None, train_heads=False, train=False):
@@ -215,27 +230,62 @@ def inference_record(case_id):
     return compiled_record(model, lower_inference(model, shape))
 
 
-def training_records(case_id):
-    """(forward record, backward record for all five outputs) of a `TrainPlan` at (2, 3, 64, 64)."""
+@contextlib.contextmanager
+def dry_lowering(**switches):
+    """`train.DRY_LOWERING` on and the given module attributes of `train` set while a plan is lowered; restored afterwards."""
     from multitask_bonetumor_yolo_amd import train as T
-    from multitask_bonetumor_yolo_amd.engine import code_of
-    variant, dtype = TRAINING_CASES[case_id]
-    model = make_model(variant, dtype, train=True)
-    dry, T.DRY_LOWERING = T.DRY_LOWERING, True
+    values = {"DRY_LOWERING": True, **switches}
+    saved = {k: getattr(T, k) for k in values}
+    for k, v in values.items():
+        setattr(T, k, v)
     try:
-        tp = T.TrainPlan(model, (2, 3, 64, 64), torch.device("cpu"), code_of(DTYPES[dtype]))
-        bwd = tp.backward_plan(tp.OUT_NAMES)
+        yield T
     finally:
-        T.DRY_LOWERING = dry
+        for k, v in saved.items():
+            setattr(T, k, v)
+
+
+def lower_training(case_id):
+    """(model, `TrainPlan` at (2, 3, 64, 64)) of a training case, lowered on CPU tensors."""
+    from multitask_bonetumor_yolo_amd.engine import code_of
+    c = TRAINING_CASES[case_id]
+    model = make_model(c["variant"], c["dtype"], train=True)
+    if c["bn_eval"]:
+        for m in model.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                m.eval()
+    tail = ()
+    if c["tail"]:
+        from multitask_bonetumor_yolo_amd.trainstep import UNUSED_BY_THE_LOSS as tail
+    with dry_lowering(**c["switches"]) as T:
+        return model, T.TrainPlan(model, (2, 3, 64, 64), torch.device("cpu"), code_of(DTYPES[c["dtype"]]), tail_prefixes=tail)
+
+
+def training_plan_record(model, tp, active=None, switches=None):
+    """Record of `tp`'s backward plan for the outputs `active` (lowered here, under `switches`); of its forward plan with `active` None."""
+    plan = tp.fwd
+    if active is not None:
+        with dry_lowering(**(switches or {})):
+            plan = tp.backward_plan(active)
     roots = [model, tp.x, tp.ws.small, tp.ws.big, tp.arena.buckets, tp.fwd.pool.all, tp.fwd.consts]
-    return plan_record(tp.fwd, roots), plan_record(bwd, roots)
+    return plan_record(plan, roots)
+
+
+def training_records(case_id):
+    """The records of a training case: [forward, backward for all outputs], or [backward] alone for a case that names its active outputs."""
+    model, tp = lower_training(case_id)
+    active, switches = TRAINING_CASES[case_id]["active"], TRAINING_CASES[case_id]["switches"]
+    if active is not None:
+        return [training_plan_record(model, tp, active, switches)]
+    outputs = tp.OUT_NAMES if tp.det_maps is not None else tuple(n for n in tp.OUT_NAMES if n != "det")
+    return [training_plan_record(model, tp), training_plan_record(model, tp, outputs, switches)]
 
 
 def case_entry(case_id):
     """What the fixture holds for one case: launch count(s) and digest(s)."""
     if case_id in TRAINING_CASES:
-        fwd, bwd = training_records(case_id)
-        return {"launches": [len(fwd["launches"]), len(bwd["launches"])], "sha256": [digest(fwd), digest(bwd)]}
+        recs = training_records(case_id)
+        return {"launches": [len(r["launches"]) for r in recs], "sha256": [digest(r) for r in recs]}
     rec = inference_record(case_id)
     return {"launches": len(rec["launches"]), "sha256": digest(rec)}
 

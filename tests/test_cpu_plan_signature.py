@@ -8,6 +8,11 @@ tensors although it launched nothing) and `train.TrainPlan` under `train.DRY_LOW
 The digests are never regenerated from the code under test: a lowering change that is meant to change a plan replaces the fixture from
 the old code's point of view, by hand, with the reason.
 
+The training cases after the first three (`train-v2-fp32` ... `train-canonical-bf16-protos`: another variant, BatchNorm in eval, tail
+buckets, the fused switches off, four subsets of active outputs) were added the same way from commit 7dca8d6, the parent of the change
+that moved the state of one backward lowering into `train._BackwardPass`: that commit's unmodified package with this helper copied
+in, two separate processes, identical digests.  The 38 older entries were left byte for byte as they were.
+
 On a mismatch: `python tests/plan_signature.py <case>` prints the full record; diff it against the same command in the other checkout."""
 import json
 
@@ -29,11 +34,14 @@ def clean_environment(monkeypatch):
 
 def test_fixture_holds_exactly_the_cases():
     assert sorted(GOLDEN) == sorted(PS.all_case_ids())
-    assert len(PS.inference_cases()) == 33 + 2 and len(PS.TRAINING_CASES) == 3
+    assert len(PS.inference_cases()) == 33 + 2 and len(PS.TRAINING_CASES) == 3 + 8
     # the parent's launch counts the cases were specified with
     assert [GOLDEN[f"canonical-bf16-{k}"]["launches"] for k in ("default", "merged", "early", "trainheads")] == [193, 163, 185, 239]
     assert [GOLDEN[f"canonical-bf16-{k}-16x640"]["launches"] for k in ("default", "merged")] == [192, 162]
-    assert [GOLDEN[k]["launches"] for k in PS.TRAINING_CASES] == [[330, 621], [335, 621], [207, 425]]
+    assert [GOLDEN[k]["launches"] for k in PS.TRAINING_CASES] == [
+        [330, 621], [335, 621], [207, 425],
+        [293, 549], [335, 621], [330, 621], [336, 639],            # v2-fp32, fp32-bneval, bf16-tail, bf16-unfused
+        [522], [438], [536], [399]]                                # bf16-step, -logits, -segmc, -protos: the backward plan alone
 
 
 @pytest.mark.parametrize("case", list(PS.inference_cases()))
@@ -44,6 +52,27 @@ def test_inference_plan_is_the_parents_plan(case):
 @pytest.mark.parametrize("case", list(PS.TRAINING_CASES))
 def test_training_plans_are_the_parents_plans(case):
     assert PS.case_entry(case) == GOLDEN[case]
+
+
+ACTIVE_SETS = {**PS.SUBSETS, "all": ("det", "seg", "mc", "protos", "logits")}
+
+
+def test_backward_plans_do_not_depend_on_the_plans_built_before():
+    """Nothing of one backward lowering outlives it: on ONE `TrainPlan` the plans for four subsets of the outputs and then for all five
+    are each the plan a fresh `TrainPlan` lowers first (the fixture's entries, which come from a fresh plan per case)."""
+    model, tp = PS.lower_training("train-canonical-bf16")
+    for k, active in ACTIVE_SETS.items():
+        rec = PS.training_plan_record(model, tp, active)
+        want = GOLDEN["train-canonical-bf16" + ("" if k == "all" else "-" + k)]
+        assert (len(rec["launches"]), PS.digest(rec)) == (want["launches"][-1], want["sha256"][-1]), k
+
+
+def test_backward_plan_is_built_once_per_set_of_outputs():
+    _, tp = PS.lower_training("train-canonical-bf16")
+    with PS.dry_lowering():
+        plan = tp.backward_plan(("det", "logits", "protos"))
+        assert tp.backward_plan(("protos", "det", "logits")) is plan and tp.backward_plan(["logits", "protos", "det"]) is plan
+        assert tp.backward_plan(("logits",)) is not plan
 
 
 @pytest.mark.parametrize("variant,fewer", [("canonical", 30), ("v2", 6)])
