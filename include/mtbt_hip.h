@@ -416,6 +416,55 @@ int mtbt_det_confusion(const mtbt_loss_args* a, int64_t* counts, int32_t* status
 int mtbt_cls_confusion(const float* logits, const int64_t* target, int N, int nc, int64_t* counts, int32_t* status, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Instance-mask loss (YOLOv8-seg `v8SegmentationLoss.single_mask_loss` / `crop_mask`; an extension beyond `_multitask_loss`, which
+ * reads the prototypes only through the 1x1 projector) and its gradient with respect to the mask coefficients and the prototypes.
+ *   positives   mtbt_multitask_loss's own rule (the shared decode + match prologue) against gt_xyxy, where every GT row is its own
+ *               box in pixels of the img_size frame, grouped by image with gt_off [N+1]; rows at or beyond gt_off[N] belong to no image
+ *   target      t[b][y][x] = gt_masks[b][y * (S / hp)][x * (S / wp)] (nearest), S = img_size, S % hp == S % wp == 0
+ *   per positive a matched to row g:  q = gt_xyxy[g] * (wp / S, hp / S, wp / S, hp / S); pixel (x, y) is inside iff
+ *               x >= q.x1 && x < q.x2 && y >= q.y1 && y < q.y2;  logit = sum_c mc[b][a][c] * protos[b][y][x][c];
+ *               loss_a = sum_inside bce_with_logits(logit, t) / ((q.x2 - q.x1) * (q.y2 - q.y1))
+ *   out[0] = sum_a loss_a / norm, out[1] = #positives;  norm = #positives of the batch, N if there are none
+ *   gradients of weight * out[0]:  r = weight * (sigmoid(logit) - t) / (norm * area) on inside pixels,
+ *               d_mc[b][a][c] = sum_px r * protos[b][px][c],  d_protos[b][px][c] = sum_a r * mc[b][a][c]
+ * map / h / w / map_pixel_stride / n_levels / N / reg_max / img_size / iou_thresh: as in mtbt_loss_args (the class channels are not read).
+ * mc: fp32, element (b, a, c) at mc[b * mc_batch_stride + a * mc_anchor_stride + c * mc_channel_stride].  protos: fp32 dense NHWC
+ * [N][hp][wp][nm], 16-byte aligned.  gt_masks: fp32 [N][S][S] dense.  nm must be 32.  n_gt rows in gt_xyxy, n_gt <= N * A.
+ * d_mc (optional): fp32 dense [N][A][nm]; d_protos (optional): dense NHWC in dprotos_dtype (MTBT_F32 / BF16 / F16, rounded once from
+ * fp32).  Both are written whole (zeros for anchors that are not positives and for pixels outside every matched box), or added to
+ * when their accumulate flag is set.  Deterministic (fixed-order sums, no floating-point atomics); no host synchronisation.
+ * MTBT_EINVAL before any launch: NULL args / maps / gt_xyxy / gt_off / mc / protos / gt_masks / out / workspace, a non-integral
+ * img_size or one that hp or wp does not divide, nm != 32, n_gt < 0 or > N * A, workspace_bytes below
+ * mtbt_mask_loss_workspace_bytes(N, A, hp, wp, nm), an unknown dprotos_dtype.  MTBT_EALIGN for misaligned gt_xyxy / protos / d_mc / d_protos.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mtbt_mask_loss_args {
+  const float* map[3];
+  int32_t h[3], w[3];
+  int32_t map_pixel_stride[3];
+  int32_t n_levels, N, reg_max;
+  float img_size, iou_thresh;
+  int32_t n_gt;
+  const float* gt_xyxy; /* [n_gt][4] pixels */
+  const int32_t* gt_off; /* [N+1] */
+  const float* mc;
+  int64_t mc_batch_stride, mc_anchor_stride, mc_channel_stride;
+  const float* protos;
+  const float* gt_masks;
+  int32_t hp, wp, nm;
+  float weight;
+  float* d_mc;
+  void* d_protos;
+  int32_t accumulate_dmc, dprotos_dtype, accumulate_dprotos;
+  int32_t reserved;
+  void* workspace;
+  int64_t workspace_bytes;
+  float* out; /* [2]: mask loss, #positives */
+} mtbt_mask_loss_args;
+int64_t mtbt_mask_loss_workspace_bytes(int N, int A, int hp, int wp, int nm);
+int mtbt_instance_mask_loss(const mtbt_mask_loss_args* a, void* stream);
+int mtbt_sizeof_mask_loss_args(void);
+
+/* ---------------------------------------------------------------------------------------------
  * ConvTranspose2d(C, Cm, 2, stride 2, bias) -> Conv 3x3 (Cm -> K, pad 1) + per-channel shift + activation as ONE direct convolution
  * over the LOW-resolution map (inference).  Replaces ultralytics `Proto.upsample` followed by `Proto.cv2` (conv + folded BatchNorm +
  * SiLU): main_model.py:326-328 [ultralytics Proto], SURVEY 8a row 10.  Both operators are linear with nothing in between: per output

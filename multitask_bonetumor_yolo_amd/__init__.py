@@ -4,13 +4,14 @@
     from multitask_bonetumor_yolo_amd import postprocess                 # decode / NMS / masks on the GPU
     from multitask_bonetumor_yolo_amd import preprocess                  # letterbox / BGR->RGB / /255 of a batch on the GPU
     from multitask_bonetumor_yolo_amd import multitask_loss              # == MultiTaskLitModel._multitask_loss (value)
+    from multitask_bonetumor_yolo_amd import instance_mask_loss          # YOLOv8-seg instance-mask loss + gradients (opt-in extension)
     from multitask_bonetumor_yolo_amd import ValidationStep              # == validation_step + the epoch-end metrics, on the device
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
 """
 from . import postprocess, preprocess  # noqa: F401
-from .loss import multitask_loss  # noqa: F401
+from .loss import InstanceMaskLoss, instance_mask_loss, multitask_loss  # noqa: F401
 from .checkpoints import load_pretrained_heads, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision,  # noqa: F401

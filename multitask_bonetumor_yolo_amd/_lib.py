@@ -140,6 +140,17 @@ class MaskEvalArgs(C.Structure):  # mtbt_mask_eval_args
                 ("max_det", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MaskLossArgs(C.Structure):  # mtbt_mask_loss_args
+    _fields_ = [("map", C.c_void_p * 3), ("h", C.c_int32 * 3), ("w", C.c_int32 * 3), ("map_pixel_stride", C.c_int32 * 3),
+                ("n_levels", C.c_int32), ("N", C.c_int32), ("reg_max", C.c_int32), ("img_size", C.c_float), ("iou_thresh", C.c_float),
+                ("n_gt", C.c_int32), ("gt_xyxy", C.c_void_p), ("gt_off", C.c_void_p), ("mc", C.c_void_p),
+                ("mc_batch_stride", C.c_int64), ("mc_anchor_stride", C.c_int64), ("mc_channel_stride", C.c_int64),
+                ("protos", C.c_void_p), ("gt_masks", C.c_void_p), ("hp", C.c_int32), ("wp", C.c_int32), ("nm", C.c_int32), ("weight", C.c_float),
+                ("d_mc", C.c_void_p), ("d_protos", C.c_void_p), ("accumulate_dmc", C.c_int32), ("dprotos_dtype", C.c_int32),
+                ("accumulate_dprotos", C.c_int32), ("reserved", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("out", C.c_void_p)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -243,6 +254,9 @@ SYMBOLS = {
     "mtbt_mask_pair_counts": (C.c_int, [C.POINTER(MaskPairArgs), C.POINTER(MaskImage), C.c_int, C.c_void_p]),
     "mtbt_mask_eval": (C.c_int, [C.POINTER(MaskEvalArgs), C.c_void_p]),
     "mtbt_sizeof_mask_eval_args": (C.c_int, [C.c_int]),
+    "mtbt_mask_loss_workspace_bytes": (C.c_int64, [C.c_int] * 5),
+    "mtbt_instance_mask_loss": (C.c_int, [C.POINTER(MaskLossArgs), C.c_void_p]),
+    "mtbt_sizeof_mask_loss_args": (C.c_int, []),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -274,6 +288,9 @@ def load():
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "
                                        f"out in {C.sizeof(st)} bytes: stale library, rebuild")
+        if lib.mtbt_sizeof_mask_loss_args() != C.sizeof(MaskLossArgs):
+            raise RuntimeError(f"libmtbt_hip.so was built with sizeof(MaskLossArgs) = {lib.mtbt_sizeof_mask_loss_args()}, this binding lays it "
+                               f"out in {C.sizeof(MaskLossArgs)} bytes: stale library, rebuild")
         _lib = lib
     return _lib
 

@@ -8,7 +8,7 @@ used instead, on the tensors `forward(x, "train")` returns.)
 No host synchronisation: the ground-truth boxes are grouped by image with device-side tensor ops, the positive count and
 the mean matched IoU come back as tensors (the reference returns Python floats, `:385`)."""
 import ctypes as C
-from typing import Sequence
+from typing import Optional, Sequence
 
 import torch
 
@@ -113,3 +113,132 @@ def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_l
     grads = {"det_maps": [t.permute(0, 3, 1, 2) for t in d_maps],      # [B, no, h, w] views of channels-last memory
              "seg_logits": d_seg.view(B, 1, img_size, img_size), "img_logits": d_img}
     return res, grads
+
+
+# ---- instance-mask loss (YOLOv8-seg single_mask_loss / crop_mask): csrc/mask_loss.hip ------------------------------------------
+_CODE_OF = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}
+
+
+def group_gt_rows(gt_boxes: torch.Tensor, n_images: int, img_size: float):
+    """[G,6] = (batch_idx, cls, cx, cy, w, h) normalised  ->  (xyxy [G,4] pixels, off [N+1] int32): every GT row is its OWN box
+    (x1 = (cx - w / 2) * S, ...), rows grouped by image in stable order.  Unlike `group_gt_boxes` this is not the reference's
+    column-concatenated layout, which mixes coordinates of different boxes of an image: a mask target cropped to such a box means
+    nothing.  Rows with a non-positive width or height (or an image index outside the batch) are moved behind `off[N]`: they belong
+    to no image and are never matched.  Device-side tensor ops only, no host synchronisation."""
+    dev = gt_boxes.device
+    G = gt_boxes.shape[0]
+    off = torch.zeros(n_images + 1, dtype=torch.int32, device=dev)
+    if G == 0:
+        return torch.zeros((1, 4), dtype=torch.float32, device=dev), off
+    g = gt_boxes.float()
+    bidx = g[:, 0].long()
+    skip = (g[:, 4] <= 0) | (g[:, 5] <= 0) | (bidx < 0) | (bidx >= n_images)
+    bidx = torch.where(skip, torch.full_like(bidx, n_images), bidx)
+    order = torch.argsort(bidx, stable=True)
+    g, bidx = g[order], bidx[order]
+    counts = torch.zeros(n_images + 1, dtype=torch.long, device=dev).scatter_add_(0, bidx, torch.ones_like(bidx))
+    off[1:] = torch.cumsum(counts[:n_images], 0).int()
+    xyxy = torch.stack([(g[:, 2] - g[:, 4] / 2) * img_size, (g[:, 3] - g[:, 5] / 2) * img_size,
+                        (g[:, 2] + g[:, 4] / 2) * img_size, (g[:, 3] + g[:, 5] / 2) * img_size], 1)
+    return xyxy.contiguous(), off
+
+
+def instance_mask_loss(box_maps: Sequence[torch.Tensor], mc: torch.Tensor, protos: torch.Tensor, gt_boxes: torch.Tensor,
+                       gt_masks: torch.Tensor, *, img_size: int, reg_max: int = 16, iou_match_thresh: float = 0.5, weight: float = 1.0,
+                       with_grads: bool = False, grad_out=None, accumulate: bool = False, protos_grad_dtype=torch.float32,
+                       mc_layout: Optional[str] = None):
+    """The YOLOv8-seg instance-mask loss on the device (definition: include/mtbt_hip.h, `mtbt_mask_loss_args`).  An extension beyond the
+    reference's `_multitask_loss`, whose only use of the prototypes is the 1x1 projector.
+
+    box_maps: the raw Detect maps (3 x [B, 4*reg_max+nc, h, w]); mc: the mask coefficients [B, A, nm] (`mc_layout="bAn"`) or the
+    module's [B, nm, A] view ("bnA"), any strides -- with `mc_layout=None` the shape decides, and a shape that fits both (A == nm) is
+    refused; protos [B, nm, hp, wp]; gt_boxes [G, 6]; gt_masks [B, 1, S, S] float.
+    Returns (mask_loss, n_pos) as 0-d fp32 device tensors without autograd history.  `with_grads=True` returns
+    `((mask_loss, n_pos), {"mc": [B, A, nm] fp32, "protos": [B, nm, hp, wp] view of channels-last memory in protos_grad_dtype})`,
+    the gradient of `weight * mask_loss`.  `grad_out={"mc": [B, A, nm] fp32, "protos": NHWC buffer (fp32 / bf16 / fp16)}` writes them
+    straight into a training plan's input buffers; `accumulate=True` adds to the buffers instead of overwriting them."""
+    lib = L.load()
+    _need_cuda(box_maps[0], "instance_mask_loss")
+    _need_cuda(mc, "instance_mask_loss")
+    _need_cuda(protos, "instance_mask_loss")
+    dev = box_maps[0].device
+    B, nm, hp, wp = protos.shape
+    A = sum(m.shape[2] * m.shape[3] for m in box_maps)
+    S = int(img_size)
+    a = L.MaskLossArgs()
+    keep = []
+    for i, m in enumerate(box_maps):
+        t, ld = _nhwc_rows(m)
+        keep.append(t)
+        a.map[i], a.h[i], a.w[i], a.map_pixel_stride[i] = t.data_ptr(), m.shape[2], m.shape[3], ld
+    a.n_levels, a.N, a.reg_max, a.img_size, a.iou_thresh = len(box_maps), B, reg_max, float(img_size), float(iou_match_thresh)
+    xyxy, off = group_gt_rows(gt_boxes.to(dev), B, float(img_size))
+    a.n_gt, a.gt_xyxy, a.gt_off = int(gt_boxes.shape[0]), xyxy.data_ptr(), off.data_ptr()
+    mcf = mc.detach()
+    mcf = mcf if mcf.dtype == torch.float32 else mcf.float()
+    if mc_layout is None:
+        fits = [k for k, shp in (("bAn", (B, A, nm)), ("bnA", (B, nm, A))) if tuple(mcf.shape) == shp]
+        if len(fits) != 1:
+            raise ValueError(f"instance_mask_loss: mc {tuple(mc.shape)} fits {'both' if fits else 'neither'} of [B, A, nm] = {(B, A, nm)} and "
+                             "[B, nm, A]: pass mc_layout")
+        mc_layout = fits[0]
+    if mc_layout not in ("bAn", "bnA") or tuple(mcf.shape) != ((B, A, nm) if mc_layout == "bAn" else (B, nm, A)):
+        raise ValueError(f"instance_mask_loss: mc {tuple(mc.shape)} is not the {mc_layout!r} layout of B, A, nm = {(B, A, nm)}")
+    a.mc_batch_stride = mcf.stride(0)
+    a.mc_anchor_stride, a.mc_channel_stride = (mcf.stride(1), mcf.stride(2)) if mc_layout == "bAn" else (mcf.stride(2), mcf.stride(1))
+    pt, pld = _nhwc_rows(protos.detach())
+    if pld != nm:
+        pt = pt.contiguous(memory_format=torch.channels_last)
+    tgt = gt_masks.to(dev).float().contiguous()
+    if tgt.numel() != B * S * S:
+        raise ValueError(f"instance_mask_loss: gt_masks {tuple(gt_masks.shape)} is not [B, 1, {S}, {S}]")
+    keep += [xyxy, off, mcf, pt, tgt]
+    a.mc, a.protos, a.gt_masks = mcf.data_ptr(), pt.data_ptr(), tgt.data_ptr()
+    a.hp, a.wp, a.nm, a.weight = hp, wp, nm, float(weight)
+    grads = None
+    if with_grads or grad_out is not None:
+        if grad_out is not None:
+            d_mc, d_pr = grad_out["mc"], grad_out["protos"]
+            if d_mc.dtype != torch.float32 or d_mc.numel() != B * A * nm or not d_mc.is_contiguous():
+                raise ValueError("instance_mask_loss: grad_out['mc'] must be a contiguous fp32 [B, A, nm] buffer")
+            if d_pr.dtype not in _CODE_OF or d_pr.numel() != B * hp * wp * nm or not d_pr.is_contiguous():
+                raise ValueError("instance_mask_loss: grad_out['protos'] must be a contiguous [B, hp, wp, nm] buffer (fp32 / bf16 / fp16)")
+        else:
+            mk = torch.zeros if accumulate else torch.empty
+            d_mc = mk(B, A, nm, dtype=torch.float32, device=dev)
+            d_pr = mk(B, hp, wp, nm, dtype=protos_grad_dtype, device=dev)
+        a.d_mc, a.d_protos, a.dprotos_dtype = d_mc.data_ptr(), d_pr.data_ptr(), _CODE_OF[d_pr.dtype]
+        a.accumulate_dmc = a.accumulate_dprotos = int(accumulate)
+        grads = {"mc": d_mc.view(B, A, nm), "protos": d_pr.view(B, hp, wp, nm).permute(0, 3, 1, 2)}
+    nbytes = lib.mtbt_mask_loss_workspace_bytes(B, A, hp, wp, nm)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
+    L.check(lib.mtbt_instance_mask_loss(C.byref(a), _stream(dev)), "mtbt_instance_mask_loss")
+    del keep
+    res = (out[0], out[1])
+    return (res, grads) if grads is not None else res
+
+
+class InstanceMaskLoss(torch.autograd.Function):
+    """`weight * mask_loss` as an autograd node for the drop-in route: a trainer adds it to the loss it computes on the outputs of
+    `model(x, "train")`.
+        InstanceMaskLoss.apply(mc, protos, gt_boxes, gt_masks, img_size, reg_max, iou_match_thresh, weight, mc_layout, *box_maps)
+    -> (weight * mask_loss, n_pos).  `mc_layout` names the layout of `mc`: "bnA" (the module's [B, nm, A]) or "bAn".  Forward runs the
+    value and both gradients; backward scales them by the incoming gradient and hands them out in the inputs' dtypes.  The matching
+    carries no gradient: the box maps get None."""
+
+    @staticmethod
+    def forward(ctx, mc, protos, gt_boxes, gt_masks, img_size, reg_max, iou_match_thresh, weight, mc_layout, *box_maps):
+        (loss, n_pos), g = instance_mask_loss([m.detach() for m in box_maps], mc, protos, gt_boxes, gt_masks, img_size=img_size, reg_max=reg_max,
+                                              iou_match_thresh=iou_match_thresh, weight=weight, with_grads=True, mc_layout=mc_layout)
+        d_mc = g["mc"] if mc_layout == "bAn" else g["mc"].permute(0, 2, 1)
+        ctx.save_for_backward(d_mc, g["protos"])
+        ctx.dtypes, ctx.n_maps = (mc.dtype, protos.dtype), len(box_maps)
+        ctx.mark_non_differentiable(n_pos)
+        return loss * weight, n_pos
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_npos):
+        d_mc, d_pr = ctx.saved_tensors
+        return ((d_mc * g_loss).to(ctx.dtypes[0]), (d_pr * g_loss).to(ctx.dtypes[1])) + (None,) * (7 + ctx.n_maps)

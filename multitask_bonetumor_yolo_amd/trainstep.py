@@ -24,10 +24,11 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import code_of, reserved_stream
-from .loss import multitask_loss
+from .loss import instance_mask_loss, multitask_loss
 from .train import TrainPlan, make_arena
 
 UNUSED_BY_THE_LOSS = ("segment.cv2.", "segment.cv3.", "segment.cv4.")   # running_main_v3.py:239-257 reads only seg_head_outputs[2]
+UNUSED_WITH_MASK_LOSS = ("segment.cv2.", "segment.cv3.")                 # the instance-mask term reaches the coefficient branch (cv4)
 
 
 def _s(dev):
@@ -57,10 +58,12 @@ class TrainStep:
     def __init__(self, model, batch_shape: Sequence[int], *, optimizer: str = "adamw", lr: float = 1e-4, weight_decay: float = 5e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.9, nesterov: bool = False, clip_norm: Optional[float] = 10.0,
                  iou_match_thresh: float = 0.5, label_smoothing: float = 0.1, loss_weights=(1.0, 2.0, 1.5, 0.5, 1.0),
-                 projector: Optional[nn.Conv2d] = None, process_group=None, overlap: bool = True):
+                 projector: Optional[nn.Conv2d] = None, process_group=None, overlap: bool = True, instance_mask_weight: float = 0.0):
         """batch_shape [B,3,S,S] per rank.  `projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1),
         running_main_v3.py:186); created (seeded default init) when not given.  A live `torch.distributed` process group with more than
-        one rank turns on the gradient exchange; parameters are broadcast from rank 0 first (what DDP does at construction)."""
+        one rank turns on the gradient exchange; parameters are broadcast from rank 0 first (what DDP does at construction).
+        `instance_mask_weight` > 0 adds `weight * instance_mask_loss` (csrc/mask_loss.hip; not a term of the reference's loss) to the
+        total: Segment.cv4 then trains like any other parameter and the step returns 10 elements.  At 0 (default) nothing changes."""
         if not hasattr(model, "detect"):
             raise NotImplementedError("TrainStep drives the canonical model (running_main_v3.py needs .detect, SURVEY F4)")
         self.m = model
@@ -76,7 +79,11 @@ class TrainStep:
         self.group = process_group
         self._host_staged = self._host_staged_logged = False
         # ---- re-home the parameters into flat buckets with the gradient arena's layout ----
-        self.params, gview, self.n_skip = make_arena(model, dev, UNUSED_BY_THE_LOSS)
+        self.mask_w = float(instance_mask_weight)
+        if self.mask_w < 0:
+            raise ValueError("instance_mask_weight must be >= 0")
+        unused = UNUSED_WITH_MASK_LOSS if self.mask_w > 0 else UNUSED_BY_THE_LOSS
+        self.params, gview, self.n_skip = make_arena(model, dev, unused)
         with torch.no_grad():
             for name, p in model.named_parameters():
                 if not p.requires_grad:
@@ -88,10 +95,10 @@ class TrainStep:
                 for t in list(self.params.buckets) + list(model.buffers()) + [p.data for p in self.projector.parameters()]:
                     self._bcast(t, 0)
         model.__dict__.pop("_train_plans", None)
-        self.tp = TrainPlan(model, tuple(batch_shape), dev, code_of(model.compute_dtype), tail_prefixes=UNUSED_BY_THE_LOSS)
+        self.tp = TrainPlan(model, tuple(batch_shape), dev, code_of(model.compute_dtype), tail_prefixes=unused)
         assert [b.numel() for b in self.tp.arena.buckets] == [b.numel() for b in self.params.buckets]
         self.grads = self.tp.arena
-        self.active = ("det", "logits", "protos")
+        self.active = ("det", "logits", "protos") + (("mc",) if self.mask_w > 0 else ())
         self.bwd = self.tp.backward_plan(self.active)
         # the projector's three tensors: tiny flat buffers of their own
         nm = model.proto_ch
@@ -123,7 +130,8 @@ class TrainStep:
     # ------------------------------------------------------------------------------------------------------------------
     def step(self, x: torch.Tensor, gt_boxes: torch.Tensor, gt_masks: torch.Tensor, gt_cls: torch.Tensor) -> torch.Tensor:
         """One optimisation step on this rank's shard.  Returns the loss tuple of `_multitask_loss` as an 8-element device tensor view
-        (total, seg, box, dfl, cls_det, img_cls, #positives, mean matched IoU) -- no host synchronisation."""
+        (total, seg, box, dfl, cls_det, img_cls, #positives, mean matched IoU) -- no host synchronisation.  With `instance_mask_weight` > 0
+        the total includes `weight * mask_loss` and two elements are appended: mask_loss and its positive count."""
         loss = self.forward_backward(x, gt_boxes, gt_masks, gt_cls)
         self._clip_and_update()
         self.m.mark_weights_updated()                      # inference plans folded the old weights
@@ -139,11 +147,18 @@ class TrainStep:
                                 self.projector.bias, with_grads=True,
                                 grad_out={"det_maps": [d.buf for d in tp.d_in["det"]], "img_logits": tp.d_in["logits"]}, **self.loss_kw)
         dseg = g["seg_logits"]
-        L.check(lib.mtbt_projector_backward(dseg.data_ptr(), tp.protos.ptr, self.pj.data_ptr(), tp.d_in["protos"].data_ptr(), tp.code, 0,
+        mask = None
+        if self.mask_w > 0:          # writes d_in["mc"] and d_in["protos"] whole; the projector's share is then ADDED to the latter
+            mask = instance_mask_loss([m.nchw() for m in tp.det_maps], tp.mc, tp.protos.nchw(), gt_boxes, gt_masks, img_size=self.S,
+                                      reg_max=self.loss_kw["reg_max"], iou_match_thresh=self.loss_kw["iou_match_thresh"], weight=self.mask_w,
+                                      mc_layout="bAn", grad_out={"mc": tp.d_in["mc"], "protos": tp.d_in["protos"]})[0]
+        L.check(lib.mtbt_projector_backward(dseg.data_ptr(), tp.protos.ptr, self.pj.data_ptr(), tp.d_in["protos"].data_ptr(), tp.code, int(mask is not None),
                                             self.pj_grad.data_ptr(), self.pj_grad.data_ptr() + 4 * nm, 0, self.B, self.S // 4, self.S // 4, nm, self.S, self.S,
                                             self.pj_ws.data_ptr(), self.pj_ws.numel() * 4, _s(dev)), "mtbt_projector_backward")
         self._backward_and_exchange()
-        return torch.stack(res)
+        if mask is None:
+            return torch.stack(res)
+        return torch.stack((res[0] + self.mask_w * mask[0],) + tuple(res[1:]) + mask)
 
     def _backward_and_exchange(self):
         main = torch.cuda.current_stream(self.dev)
