@@ -94,7 +94,8 @@ typedef struct mtbt_conv_args {
   int32_t act;         /* MTBT_ACT_* */
   int32_t out_mode;    /* MTBT_OUT_* */
   int32_t tile_hint;   /* 0 = heuristic; else (TC<<16)|TP to force a tile (tests / tuning); bit 25 = row-reuse direct 3x3
-                          kernel, bit 26 = keep a 3x3 on the implicit-GEMM kernel, bit 27 = 64-byte K-steps, bits 28-30 = stages */
+                          kernel, bit 26 = keep a 3x3 on the implicit-GEMM kernel, bit 27 = 64-byte K-steps, bits 28-30 ignored
+                          (once the number of LDS stages: every kernel has two) */
   void* y2;            /* optional second output (training forward): the PRE-activation conv * scale + shift, addressed and typed
                           like y (no residual added); NULL = not written.  MTBT_OUT_NHWC only. */
   int32_t policy;      /* 0 = default kernel-selection policy; else 0x100 | bits (bit0 small 1x1 tiles, bit1 64x64 tiles for small k x k,

@@ -24,6 +24,7 @@
 #include "conv_dma.h"
 #include "conv_epilogue.h"
 #include "conv_params.h"
+#include "conv_tiles.h"
 
 namespace {
 
@@ -155,25 +156,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_direct_kernel(const ConvP p) {
     yoff = (long)n * p.ybs + pixoff * p.ldy + ch;
     roff = (long)n * p.rbs + pixoff * p.ldr + ch;
     return true;
-  }, seq, true, (long)ptile * 4 + wave);     // column-sum partial rows: 4 per tile (each wave owns four tile rows)
+  }, seq, true, (long)ptile * DIRECT_CS_ROWS + wave);     // column-sum partial rows: 4 per tile (each wave owns four tile rows)
 }
 
 template <typename T, int TC>
-int launch_direct3x3(const ConvP& p, hipStream_t stream) {
-  ConvP q = p;
-  q.ctiles = (p.K + TC - 1) / TC;
-  const long ptiles = (long)p.N * (p.H >> 4) * (p.W >> 4);
-  q.ptiles_per_xcd = (int)((ptiles + 7) / 8);
-  const long blocks = (long)q.ptiles_per_xcd * 8 * q.ctiles;
-  if (blocks <= 0 || blocks > 0x7fffffffL) return MTBT_EINVAL;
+int launch_direct3x3(ConvP q, hipStream_t stream) {
   constexpr int XBYTES = ((324 * 8 + 255) / 256) * 256 * 16;
   constexpr int lds_main = XBYTES + 2 * TC * 128;
   constexpr int lds_epi = 4 * 16 * (TC * 4 + 16);
   constexpr int lds = (lds_main > lds_epi ? lds_main : lds_epi) + 2 * TC * 4;
-  if (int rc = mtbt_allow_lds(conv3x3_direct_kernel<T, TC>, lds)) return rc;
-  hipLaunchKernelGGL((conv3x3_direct_kernel<T, TC>), dim3((unsigned)blocks), dim3(256), lds, stream, q);
-  MTBT_LAUNCH_CHECK();
-  return MTBT_OK;
+  return conv_launch_tiles(conv3x3_direct_kernel<T, TC>, q, TC, (long)q.N * (q.H >> 4) * (q.W >> 4), 1, lds, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -202,38 +194,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_rr_batch_kernel(const ConvBatc
   const unsigned bid = blockIdx.x;
 #include "conv3x3_rr_body.inc"
 }
-
-template <typename T, int TC>
-int launch_direct3x3_rr_batch(const ConvBatchP& b, int n, hipStream_t stream) {
-  ConvBatchP q = b;
-  q.p.ctiles = (b.p.K + TC - 1) / TC;
-  const long ptiles = (long)b.p.N * (b.p.H >> 4) * (b.p.W >> 4);
-  q.p.ptiles_per_xcd = (int)((ptiles + 7) / 8);
-  const long blocks = (long)q.p.ptiles_per_xcd * 8 * q.p.ctiles;
-  if (blocks <= 0 || blocks > 0x7fffffffL || n < 1 || n > MTBT_CONV_BATCH_MAX) return MTBT_EINVAL;
-  constexpr int XBYTES = ((324 * 4 + 255) / 256) * 256 * 16;
-  constexpr int lds = XBYTES + 2 * 3 * TC * 64 + 2 * TC * 4;
-  if (int rc = mtbt_allow_lds(conv3x3_rr_batch_kernel<T, TC>, lds)) return rc;
-  hipLaunchKernelGGL((conv3x3_rr_batch_kernel<T, TC>), dim3((unsigned)blocks, (unsigned)n), dim3(256), lds, stream, q);
-  MTBT_LAUNCH_CHECK();
-  return MTBT_OK;
-}
 #endif
 
-template <typename T, int TC>
-int launch_direct3x3_rr(const ConvP& p, hipStream_t stream) {
-  ConvP q = p;
-  q.ctiles = (p.K + TC - 1) / TC;
-  const long ptiles = (long)p.N * (p.H >> 4) * (p.W >> 4);
-  q.ptiles_per_xcd = (int)((ptiles + 7) / 8);
-  const long blocks = (long)q.ptiles_per_xcd * 8 * q.ctiles;
-  if (blocks <= 0 || blocks > 0x7fffffffL) return MTBT_EINVAL;
+// One call (q a ConvP, n = 1) or one batch (q a ConvBatchP) of a row-reuse kernel: one workgroup per (16 x 16 tile, TC channels); LDS =
+// halo [324 px][64 B] incl. the zero-filled DMA tail, 2 x 3 weight tap tiles, the affine copy.
+template <int TC, typename Kernel, typename Params>
+int launch_direct3x3_rr(Kernel kernel, Params q, int n, hipStream_t stream) {
   constexpr int XBYTES = ((324 * 4 + 255) / 256) * 256 * 16;
   constexpr int lds = XBYTES + 2 * 3 * TC * 64 + 2 * TC * 4;
-  if (int rc = mtbt_allow_lds(conv3x3_rr_kernel<T, TC>, lds)) return rc;
-  hipLaunchKernelGGL((conv3x3_rr_kernel<T, TC>), dim3((unsigned)blocks), dim3(256), lds, stream, q);
-  MTBT_LAUNCH_CHECK();
-  return MTBT_OK;
+  const ConvP& p = conv_of(q);
+  return conv_launch_tiles(kernel, q, TC, (long)p.N * (p.H >> 4) * (p.W >> 4), n, lds, stream);
+}
+
+// both formulations at 128- and 64-channel tiles
+template <typename T>
+int dispatch_direct3x3(const ConvP& p, int TC, bool row_reuse, hipStream_t s) {
+  if (row_reuse && TC == 128) return launch_direct3x3_rr<128>(conv3x3_rr_kernel<T, 128>, p, 1, s);
+  if (row_reuse && TC == 64) return launch_direct3x3_rr<64>(conv3x3_rr_kernel<T, 64>, p, 1, s);
+  if (TC == 128) return launch_direct3x3<T, 128>(p, s);
+  if (TC == 64) return launch_direct3x3<T, 64>(p, s);
+  return MTBT_EINVAL;
 }
 
 }  // namespace

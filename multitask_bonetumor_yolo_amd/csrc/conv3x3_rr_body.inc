@@ -133,4 +133,4 @@
     yoff = (long)n * p.ybs + pixoff * p.ldy + ch;
     roff = (long)n * p.rbs + pixoff * p.ldr + ch;
     return true;
-  }, seq, true, (long)ptile * 2 + wr);       // column-sum partial rows: 2 per tile (the wave's row half; the channel halves write disjoint columns)
+  }, seq, true, (long)ptile * DIRECT_RR_CS_ROWS + wr);       // column-sum partial rows: 2 per tile (the wave's row half; the channel halves write disjoint columns)

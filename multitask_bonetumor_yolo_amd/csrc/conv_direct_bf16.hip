@@ -1,10 +1,4 @@
 // bf16 instantiations of the direct 3x3 convolution kernels (conv3x3_direct.inc).
 #include "conv3x3_direct.inc"
 
-int mtbt_conv3x3_direct_bf16(const ConvP& p, int TC, hipStream_t s) {
-  if (TC == (128 | 0x1000)) return launch_direct3x3_rr<bf16_t, 128>(p, s);
-  if (TC == (64 | 0x1000)) return launch_direct3x3_rr<bf16_t, 64>(p, s);
-  if (TC == 128) return launch_direct3x3<bf16_t, 128>(p, s);
-  if (TC == 64) return launch_direct3x3<bf16_t, 64>(p, s);
-  return MTBT_EINVAL;
-}
+int mtbt_conv3x3_direct_bf16(const ConvP& p, int TC, bool row_reuse, hipStream_t s) { return dispatch_direct3x3<bf16_t>(p, TC, row_reuse, s); }

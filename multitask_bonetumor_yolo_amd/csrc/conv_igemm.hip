@@ -1,33 +1,36 @@
-// C entry point of the implicit-GEMM convolution: argument validation, tile / pipeline-depth heuristics and
-// dispatch to the per-dtype translation units (conv_igemm_bf16.hip, conv_igemm_f32.hip; kernel in conv_igemm.inc).
+// C entry points of the convolution family, host side only: argument validation (conv_validate), the kernel / tile choice (conv_choose;
+// the tiles themselves are stated in conv_tiles.h) and the dispatch to the per-dtype translation units (conv_launch; kernels in
+// conv_igemm.inc, conv3x3_direct.inc, pw_stream.hip).
 #include "common.h"
 #include "conv_params.h"
+#include "conv_tiles.h"
 #include "rowreduce.h"
 
 // per (storage type, K-step width) translation units; two LDS stages (deeper pipelines never paid: residency beats prefetch depth -- re-checked in
 // round 3 inside a dependent launch chain with 4 / 6 / 8 stages on 64x64, 128x64, 64x32 and 128x32 tiles: level on the 20x20 maps, 1.5 - 2.5x
-// slower wherever the grid needs the residency; profiles/r03_chain_probe_deep_pipelines.txt)
+// slower wherever the grid needs the residency; profiles/r03_chain_probe_deep_pipelines.txt).  conv_batch_<dtype>.hip: the batched kernels
+// (implicit GEMM with 128-byte K-steps on the table's batched tiles, row-reuse direct 3x3 at 64 channels).
+struct ConvUnit {
+  int (*gemm[2])(const ConvP& p, int TC, int TP, hipStream_t s);      // [0] 64-byte, [1] 128-byte K-steps
+  int (*direct3x3)(const ConvP& p, int TC, bool row_reuse, hipStream_t s);
+  int (*batch)(const ConvBatchP& b, int n, const ConvChoice& c, hipStream_t s);
+};
 #define MTBT_DECL(dt)                                                                      \
   int mtbt_conv_dispatch_##dt##_wide(const ConvP& p, int TC, int TP, hipStream_t s);       \
   int mtbt_conv_dispatch_##dt##_narrow(const ConvP& p, int TC, int TP, hipStream_t s);     \
-  int mtbt_conv3x3_direct_##dt(const ConvP& p, int TC, hipStream_t s);                     \
-  static int mtbt_conv_dispatch_##dt(const ConvP& p, int TC, int TP, int wide, int nbuf, hipStream_t s) { \
-    (void)nbuf;                                                                            \
-    return wide ? mtbt_conv_dispatch_##dt##_wide(p, TC, TP, s) : mtbt_conv_dispatch_##dt##_narrow(p, TC, TP, s); \
-  }
+  int mtbt_conv3x3_direct_##dt(const ConvP& p, int TC, bool row_reuse, hipStream_t s);     \
+  int mtbt_conv_batch_dispatch_##dt(const ConvBatchP& b, int n, const ConvChoice& c, hipStream_t s); \
+  static const ConvUnit conv_unit_##dt = {{mtbt_conv_dispatch_##dt##_narrow, mtbt_conv_dispatch_##dt##_wide}, mtbt_conv3x3_direct_##dt, mtbt_conv_batch_dispatch_##dt};
 MTBT_DECL(bf16)
 MTBT_DECL(f32)
 MTBT_DECL(f16)
 #undef MTBT_DECL
+static const ConvUnit& conv_unit(int dtype) { return dtype == MTBT_F32 ? conv_unit_f32 : (dtype == MTBT_F16 ? conv_unit_f16 : conv_unit_bf16); }
 // pw_stream.hip: the heads' output 1x1 convolutions (few input channels, <= 64 outputs, fp32 strided store) without LDS
 bool mtbt_pw_stream_applies(const ConvP& p, int dtype, bool any_width);
 int mtbt_pw_stream(const ConvP& p, int dtype, hipStream_t s);
 bool mtbt_pw_stream_batch_applies(const ConvP& p, int dtype);
 int mtbt_pw_stream_batch(const ConvBatchP& b, int n, int dtype, hipStream_t s);
-// conv_batch_<dtype>.hip: the batched kernels (kind 0 implicit GEMM with 128-byte K-steps, 1 row-reuse direct 3x3)
-int mtbt_conv_batch_dispatch_bf16(const ConvBatchP& b, int n, int kind, int TC, int TP, hipStream_t s);
-int mtbt_conv_batch_dispatch_f16(const ConvBatchP& b, int n, int kind, int TC, int TP, hipStream_t s);
-int mtbt_conv_batch_dispatch_f32(const ConvBatchP& b, int n, int kind, int TC, int TP, hipStream_t s);
 
 // Tile heuristics, from the sweep in tools/conv_tune.py on the shapes of the 640x640 batch-16 forward
 // (numbers in DESIGN.md):
@@ -96,18 +99,6 @@ static void pick_tile(int pol, int K, long M, int taps, int C, int es, int* TC, 
   if (no96 && *TC == 96) *TC = 64;
 }
 
-// LDS stages: as deep as fits 64 KiB (two workgroups per CU stay resident), at least 2, no deeper than the K loop.
-static int pick_nbuf(int TC, int TP, int BKB, int nsteps) {
-  const int cpr = BKB / 16;
-  const int tcs = ((TC * cpr + 255) / 256) * 256 / cpr;
-  const int bufsz = (tcs + TP) * BKB;
-  int n = 64 * 1024 / bufsz;
-  if (n > 2) n = 2;  // deeper pipelines never paid in the sweep: residency (workgroups per CU) beats prefetch depth
-  if (n > nsteps) n = nsteps;
-  if (n < 2) n = 2;
-  return n;
-}
-
 extern "C" int64_t mtbt_conv_colsum_workspace_bytes(int64_t pixels, int K, int with_squares) {
   if (pixels <= 0 || K <= 0) return 0;
   return (pixels / 64 + 1) * 4 * (int64_t)K * (with_squares ? 2 : 1) * (int64_t)sizeof(float);   // <= 4 partial rows per 64 pixels
@@ -125,11 +116,8 @@ static int colsum_finish(const mtbt_conv_args* a, const ConvP& p, long rows, hip
   return MTBT_OK;
 }
 
-// `layout` non-null: validate and choose the kernel as a launch would, report the column-sum partial layout, launch nothing.
-// `nmem` > 0 (with `layout`): the call is a member of a batch of nmem equal shapes -- the tile rules count the workgroups of the whole
-// batch, and `pout` receives the member's kernel parameters.
-static int conv_impl(const mtbt_conv_args* a, void* stream, int64_t* layout /* [6]: rows, pitch, kernel kind, TC, TP, 128-byte K-steps */,
-                     int nmem = 0, ConvP* pout = nullptr) {
+// Step 1: every argument check, in a fixed order (the first fault of a block answers), and the kernel parameters.
+static int conv_validate(const mtbt_conv_args* a, ConvP* pp) {
   if (!a || !a->x || !a->w || !a->y) return MTBT_EINVAL;
   if (a->dtype != MTBT_F32 && a->dtype != MTBT_BF16 && a->dtype != MTBT_F16) return MTBT_EINVAL;
   if (a->out_dtype != a->dtype && a->out_dtype != MTBT_F32) return MTBT_EINVAL;
@@ -147,7 +135,7 @@ static int conv_impl(const mtbt_conv_args* a, void* stream, int64_t* layout /* [
   if (!aligned16(a->x) || !aligned16(a->w) || a->x_pixel_stride % epc != 0 || a->x_batch_stride % epc != 0) return MTBT_EALIGN;
   if (a->x_pixel_stride < a->C) return MTBT_EINVAL;
 
-  ConvP p;
+  ConvP& p = *pp;
   p.x = a->x; p.w = a->w; p.y = a->y; p.scale = a->scale; p.shift = a->shift; p.res = a->res; p.y2 = a->y2;
   p.xbs = a->x_batch_stride; p.ybs = a->y_batch_stride; p.rbs = a->res_batch_stride;
   p.ldx = a->x_pixel_stride; p.ldy = a->y_pixel_stride; p.ldr = a->res_pixel_stride;
@@ -161,15 +149,13 @@ static int conv_impl(const mtbt_conv_args* a, void* stream, int64_t* layout /* [
   p.ctiles = 0;
   p.ptiles_per_xcd = 0;
   p.debug = a->debug;
-  // column sums (header): partial rows in the caller's workspace, second level after the conv
+  // column sums (header): partial rows in the caller's workspace (cs_part set = asked for), second level after the conv
   p.cs_part = nullptr; p.cs_shift = a->colsum_shift; p.cs_sq = a->colsum_sq ? 1 : 0; p.cs_pitch = a->K * (a->colsum_sq ? 2 : 1);
-  const bool want_cs = a->colsum_ws != nullptr;      // partial rows (and, with colsum, the finished sums)
-  if (a->colsum && !want_cs) return MTBT_EINVAL;
-  if (want_cs) {
+  if (a->colsum && !a->colsum_ws) return MTBT_EINVAL;
+  if (a->colsum_ws) {
     if (a->out_mode != MTBT_OUT_NHWC || !aligned16(a->colsum_ws)) return MTBT_EINVAL;
     p.cs_part = reinterpret_cast<float*>(a->colsum_ws);
   }
-  const int pol = (a->policy & 0x100) ? (a->policy & 0xff) : 7;   // 0 = the default policy
   // LDS-DMA addressing: 32-bit byte offsets below 2 GiB relative to (first image of a tile, weight tile row 0)
   if ((double)a->R * a->S > 31) return MTBT_EINVAL;
   if (((long)(128 / (a->Ho * a->Wo) + 2) * a->x_batch_stride + 2L * ((long)a->pad * a->W + a->pad) * a->x_pixel_stride) * es >= 0x7fff0000L) return MTBT_EINVAL;
@@ -183,63 +169,83 @@ static int conv_impl(const mtbt_conv_args* a, void* stream, int64_t* layout /* [
   if (a->out_mode == MTBT_OUT_CONVT2X2) vec = vec && (kq % 8 == 0);
   if (a->res) vec = vec && (a->res_pixel_stride % epc == 0) && (a->res_batch_stride % epc == 0) && aligned16(a->res);
   p.vec_ok = vec ? 1 : 0;
-  if (pout) *pout = p;
+  return MTBT_OK;
+}
 
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+// Step 2: which kernel and tile a validated call runs and the column-sum partial layout it writes.  Pure: no stream, no launch.
+// `nmem` > 0: the call is a member of a batch of nmem equal shapes -- the tile rules count the workgroups of the whole batch.
+static int conv_choose(const mtbt_conv_args* a, const ConvP& p, int nmem, ConvChoice* c) {
+  const int es = a->dtype == MTBT_F32 ? 4 : 2;
+  const int pol = (a->policy & 0x100) ? (a->policy & 0xff) : 7;   // 0 = the default policy
+  const bool want_cs = p.cs_part != nullptr;      // partial rows (and, with colsum, the finished sums)
   // narrow 1x1 convolutions into an fp32 map (the heads' output convs): streaming kernel, same arithmetic (a tile hint keeps the call on
   // the implicit-GEMM kernel: tests, A/B)
   if (!a->tile_hint && (pol & 64) == 0 && (long)a->K * a->C * es < 0x7fff0000L &&
       (nmem ? mtbt_pw_stream_batch_applies(p, a->dtype) : mtbt_pw_stream_applies(p, a->dtype, (pol & 128) != 0))) {
-    if (layout) { layout[0] = layout[1] = 0; layout[2] = 2; layout[3] = a->K; layout[4] = 128; layout[5] = 0; return MTBT_OK; }   // (no column sums on this path)
-    return mtbt_pw_stream(p, a->dtype, s);
+    *c = ConvChoice{CONV_PW_STREAM, a->K, 128, false, false, 0, 0};   // (no column sums on this path)
+    return MTBT_OK;
   }
   // 3x3 / stride 1 / pad 1 on 16-aligned maps: direct convolution with an LDS-resident halo tile (conv3x3_direct.inc).
   // tile_hint bit 26 (or MTBT_CONV_POLICY bit 2 cleared) keeps such a conv on the implicit-GEMM kernel (tests, A/B).
-  {
-    if ((pol & 4) && !((a->tile_hint >> 26) & 1) && !a->y2 && a->act < MTBT_ACT_DSILU && a->R == 3 && a->S == 3 && a->stride == 1 && a->pad == 1 && a->H % 16 == 0 &&
-        a->W % 16 == 0 && a->out_mode == MTBT_OUT_NHWC && a->C % (128 / es) == 0 && a->K > 32 &&
-        (long)a->H * a->W * a->x_pixel_stride * es < 0x7fff0000L && (long)128 * 9 * a->C * es < 0x7fff0000L) {
-      int tc = (a->K >= 96 && !(pol & 32)) ? 128 : 64;
-      // row-reuse variant (conv3x3_rr_kernel): the default (round 1: only for 64-channel tiles; after the epilogue split it is also
-      // 9 % faster on the 128-channel C2f convs and 3 % on Proto -- MTBT_CONV_POLICY A/B, 7.20 -> 7.15 ms per step); policy bit 4
-      // selects the first formulation, hint bit 25 / policy bit 3 force this one
-      if ((pol & 8) || ((a->tile_hint >> 25) & 1) || !(pol & 16)) tc |= 0x1000;
-      const long rows = (long)a->N * (a->H >> 4) * (a->W >> 4) * ((tc & 0x1000) ? 2 : 4);   // partial rows per 16x16 tile: see conv3x3_direct.inc
-      if (layout) { layout[0] = rows; layout[1] = p.cs_pitch; layout[2] = 1; layout[3] = tc & 0xfff; layout[4] = 256; layout[5] = (tc & 0x1000) ? 0 : 1; return MTBT_OK; }
-      if (want_cs && a->colsum_ws_bytes < rows * p.cs_pitch * (int64_t)sizeof(float)) return MTBT_EWORKSPACE;
-      const int rc = a->dtype == MTBT_F32 ? mtbt_conv3x3_direct_f32(p, tc, s) : (a->dtype == MTBT_F16 ? mtbt_conv3x3_direct_f16(p, tc, s) : mtbt_conv3x3_direct_bf16(p, tc, s));
-      if (rc != MTBT_OK || !a->colsum) return rc;
-      return colsum_finish(a, p, rows, s);
-    }
+  if ((pol & 4) && !((a->tile_hint >> 26) & 1) && !a->y2 && a->act < MTBT_ACT_DSILU && a->R == 3 && a->S == 3 && a->stride == 1 && a->pad == 1 && a->H % 16 == 0 &&
+      a->W % 16 == 0 && a->out_mode == MTBT_OUT_NHWC && a->C % (128 / es) == 0 && a->K > 32 &&
+      (long)a->H * a->W * a->x_pixel_stride * es < 0x7fff0000L && (long)128 * 9 * a->C * es < 0x7fff0000L) {
+    // row-reuse variant (conv3x3_rr_kernel): the default (round 1: only for 64-channel tiles; after the epilogue split it is also
+    // 9 % faster on the 128-channel C2f convs and 3 % on Proto -- MTBT_CONV_POLICY A/B, 7.20 -> 7.15 ms per step); policy bit 4
+    // selects the first formulation, hint bit 25 / policy bit 3 force this one
+    const bool rr = (pol & 8) || ((a->tile_hint >> 25) & 1) || !(pol & 16);
+    const long rows = (long)a->N * (a->H >> 4) * (a->W >> 4) * (rr ? DIRECT_RR_CS_ROWS : DIRECT_CS_ROWS);
+    *c = ConvChoice{CONV_DIRECT3X3, (a->K >= 96 && !(pol & 32)) ? 128 : 64, DIRECT_TP, false, rr, rows, p.cs_pitch};
+    return MTBT_OK;
   }
-  int TC, TP, nbuf = 0;
-  if (a->tile_hint) { nbuf = (a->tile_hint >> 28) & 7; TC = (a->tile_hint >> 16) & 0x1ff; TP = a->tile_hint & 0xffff; }
+  // tile_hint bits 28..30 once chose the LDS pipeline depth: accepted and ignored (every kernel has two stages)
+  int TC = (a->tile_hint >> 16) & 0x1ff, TP = a->tile_hint & 0xffff;
   int narrow = (a->tile_hint >> 27) & 1;  // hint bit 27: force 64-byte K-steps
   if (!a->tile_hint || !TC || !TP) pick_tile(pol, a->K, nmem ? (long)p.M * nmem : (long)p.M, a->R * a->S, a->C, es, &TC, &TP, &narrow, want_cs, a->act);
   if (want_cs && TC == 96) return MTBT_EINVAL;   // (a wave's 48 / 96 channels are not a power-of-two number of 8-channel pieces)
-  const int wide = (a->C % (128 / es) == 0 && !narrow) ? 1 : 0;
-  if (nbuf < 2 || nbuf > 4) nbuf = pick_nbuf(TC, TP, wide ? 128 : 64, a->R * a->S * a->C / ((wide ? 128 : 64) / es));
-  const int waves_p = (TC == 128 || (TC == 96 && TP == 64)) ? 2 : 4;    // wave layouts of conv_igemm.inc's dispatch_tile
-  const long rows = (((long)p.M + TP - 1) / TP) * waves_p;
-  if (layout) { layout[0] = rows; layout[1] = p.cs_pitch; layout[2] = 0; layout[3] = TC; layout[4] = TP; layout[5] = wide; return MTBT_OK; }
-  if (want_cs && a->colsum_ws_bytes < rows * p.cs_pitch * (int64_t)sizeof(float)) return MTBT_EWORKSPACE;
-  const int rc = a->dtype == MTBT_F32 ? mtbt_conv_dispatch_f32(p, TC, TP, wide, nbuf, s)
-                                      : (a->dtype == MTBT_F16 ? mtbt_conv_dispatch_f16(p, TC, TP, wide, nbuf, s) : mtbt_conv_dispatch_bf16(p, TC, TP, wide, nbuf, s));
-  if (rc != MTBT_OK || !a->colsum) return rc;
-  return colsum_finish(a, p, rows, s);
+  const int waves_p = conv_tile_waves_p(TC, TP);   // (a hinted tile outside the table: sized for 4 wave rows here, refused by conv_launch)
+  *c = ConvChoice{CONV_IGEMM, TC, TP, a->C % (128 / es) == 0 && !narrow, false, (((long)p.M + TP - 1) / TP) * (waves_p ? waves_p : 4), p.cs_pitch};
+  return MTBT_OK;
 }
 
-extern "C" int mtbt_conv2d_nhwc(const mtbt_conv_args* a, void* stream) { return conv_impl(a, stream, nullptr); }
+// Step 3: the workspace check, the launch and the second level of the column sums.
+static int conv_launch(const mtbt_conv_args* a, const ConvP& p, const ConvChoice& c, hipStream_t s) {
+  if (c.kind == CONV_PW_STREAM) return mtbt_pw_stream(p, a->dtype, s);
+  if (p.cs_part && a->colsum_ws_bytes < c.cs_rows * c.cs_pitch * (int64_t)sizeof(float)) return MTBT_EWORKSPACE;
+  const ConvUnit& u = conv_unit(a->dtype);
+  const int rc = c.kind == CONV_DIRECT3X3 ? u.direct3x3(p, c.TC, c.row_reuse, s) : u.gemm[c.wide](p, c.TC, c.TP, s);
+  if (rc != MTBT_OK || !a->colsum) return rc;
+  return colsum_finish(a, p, c.cs_rows, s);
+}
+
+// validate + choose: what every entry point starts with
+static int conv_plan(const mtbt_conv_args* a, int nmem, ConvP* p, ConvChoice* c) {
+  if (const int rc = conv_validate(a, p)) return rc;
+  return conv_choose(a, *p, nmem, c);
+}
+
+// the public choice[0..3] of a ConvChoice: [3] = 128-byte K-steps (implicit GEMM) / first formulation (direct) / 0 (streaming kernel)
+static void conv_report(const ConvChoice& c, int32_t* choice) {
+  choice[0] = c.kind; choice[1] = c.TC; choice[2] = c.TP;
+  choice[3] = c.kind == CONV_IGEMM ? c.wide : (c.kind == CONV_DIRECT3X3 ? !c.row_reuse : 0);
+}
+
+extern "C" int mtbt_conv2d_nhwc(const mtbt_conv_args* a, void* stream) {
+  ConvP p;
+  ConvChoice c;
+  if (const int rc = conv_plan(a, 0, &p, &c)) return rc;
+  return conv_launch(a, p, c, reinterpret_cast<hipStream_t>(stream));
+}
 
 // The partial rows a call with these arguments writes into colsum_ws: rows x pitch floats, row r = [sum (K) | sum of squares (K, with
 // colsum_sq)] of one (pixel tile, wave row); rows that cover no pixel hold zeros.  For a consumer that reduces them itself
 // (mtbt_bn_forward_partials_nhwc) instead of asking for the finished sums.
 extern "C" int mtbt_conv_colsum_layout(const mtbt_conv_args* a, int64_t* rows, int32_t* pitch) {
   if (!rows || !pitch || !a || !a->colsum_ws) return MTBT_EINVAL;
-  int64_t lay[6] = {0, 0, 0, 0, 0, 0};
-  const int rc = conv_impl(a, nullptr, lay);
-  if (rc != MTBT_OK) return rc;
-  *rows = lay[0]; *pitch = (int32_t)lay[1];
+  ConvP p;
+  ConvChoice c;
+  if (const int rc = conv_plan(a, 0, &p, &c)) return rc;
+  *rows = c.cs_rows; *pitch = c.cs_pitch;
   return MTBT_OK;
 }
 
@@ -249,15 +255,15 @@ extern "C" int mtbt_conv_colsum_layout(const mtbt_conv_args* a, int64_t* rows, i
 // rules (tests/test_cpu_host_logic.py) and for tools.
 extern "C" int mtbt_conv_kernel_choice(const mtbt_conv_args* a, int32_t* choice) {
   if (!a || !choice) return MTBT_EINVAL;
-  int64_t lay[6] = {0, 0, 0, 0, 0, 0};
-  const int rc = conv_impl(a, nullptr, lay);
-  if (rc != MTBT_OK) return rc;
-  for (int i = 0; i < 4; ++i) choice[i] = (int32_t)lay[2 + i];
+  ConvP p;
+  ConvChoice c;
+  if (const int rc = conv_plan(a, 0, &p, &c)) return rc;
+  conv_report(c, choice);
   return MTBT_OK;
 }
 
 // ---- batched form: n convolutions of one shape in one launch ---------------------------------------------------------------------------
-// Validation and the ONE kernel choice of the batch: every member passes the single call's checks (conv_impl in query mode, with the
+// Validation and the ONE kernel choice of the batch: every member passes the single call's checks and choice (conv_validate, conv_choose with the
 // batch's total workgroup count in the tile rules), the members agree in everything that selects or shapes the kernel, and the choice is
 // one the batched kernels are instantiated for: implicit GEMM 64x64 / 128x128 / 128x64 / 32x64 with 128-byte K-steps, the row-reuse direct
 // 3x3 at 64 channels (policy bit 5 asks for it from 96 output channels on), the streaming head conv up to 32 output channels.
@@ -284,19 +290,20 @@ static bool batch_outputs_overlap(const mtbt_conv_args& a, const mtbt_conv_args&
   return !(r >= a.K && r + a.K <= ld);
 }
 
+
 static int conv_batch_impl(const mtbt_conv_args* calls, int n, void* stream, int32_t* choice) {
   if (!calls || n < 1 || n > MTBT_CONV_BATCH_MAX) return MTBT_EINVAL;
   ConvBatchP b;
-  int64_t lay0[6] = {0, 0, 0, 0, 0, 0};
+  ConvChoice c0;
   for (int i = 0; i < n; ++i) {
     const mtbt_conv_args& a = calls[i];
     if (a.y2 || a.colsum || a.colsum_ws || a.out_mode != MTBT_OUT_NHWC) return MTBT_EINVAL;     // training forms and the ConvT scatter: single calls only
     if (i && !batch_same_shape(calls[0], a)) return MTBT_EINVAL;
-    int64_t lay[6] = {0, 0, 0, 0, 0, 0};
     ConvP p;
-    if (const int rc = conv_impl(&a, nullptr, lay, n, &p)) return rc;
-    if (i == 0) { b.p = p; for (int k = 0; k < 6; ++k) lay0[k] = lay[k]; }
-    else if (lay[2] != lay0[2] || lay[3] != lay0[3] || lay[4] != lay0[4] || lay[5] != lay0[5]) return MTBT_EINVAL;
+    ConvChoice c;
+    if (const int rc = conv_plan(&a, n, &p, &c)) return rc;
+    if (i == 0) { b.p = p; c0 = c; }
+    else if (c.kind != c0.kind || c.TC != c0.TC || c.TP != c0.TP || c.wide != c0.wide || c.row_reuse != c0.row_reuse) return MTBT_EINVAL;
     ConvMember& m = b.m[i];
     m.x = p.x; m.w = p.w; m.y = p.y; m.scale = p.scale; m.shift = p.shift; m.res = p.res;
     m.xbs = p.xbs; m.ybs = p.ybs; m.rbs = p.rbs; m.ldx = p.ldx; m.ldy = p.ldy; m.ldr = p.ldr;
@@ -305,15 +312,12 @@ static int conv_batch_impl(const mtbt_conv_args* calls, int n, void* stream, int
       if (batch_outputs_overlap(calls[j], a)) return MTBT_EINVAL;
   }
   for (int i = n; i < MTBT_CONV_BATCH_MAX; ++i) b.m[i] = b.m[0];
-  const int kind = (int)lay0[2], TC = (int)lay0[3], TP = (int)lay0[4], flag = (int)lay0[5];
-  if (kind == 0 && !(flag == 1 && ((TC == 128 && (TP == 128 || TP == 64)) || ((TC == 64 || TC == 32) && TP == 64)))) return MTBT_EINVAL;
-  if (kind == 1 && !(TC == 64 && flag == 0)) return MTBT_EINVAL;
-  if (choice) { choice[0] = kind; choice[1] = TC; choice[2] = TP; choice[3] = flag; return MTBT_OK; }
+  if (c0.kind == CONV_IGEMM && !(c0.wide && conv_tile_batched(c0.TC, c0.TP))) return MTBT_EINVAL;
+  if (c0.kind == CONV_DIRECT3X3 && !(c0.TC == 64 && c0.row_reuse)) return MTBT_EINVAL;
+  if (choice) { conv_report(c0, choice); return MTBT_OK; }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int dt = calls[0].dtype;
-  if (kind == 2) return mtbt_pw_stream_batch(b, n, dt, s);
-  return dt == MTBT_F32 ? mtbt_conv_batch_dispatch_f32(b, n, kind, TC, TP, s)
-                        : (dt == MTBT_F16 ? mtbt_conv_batch_dispatch_f16(b, n, kind, TC, TP, s) : mtbt_conv_batch_dispatch_bf16(b, n, kind, TC, TP, s));
+  if (c0.kind == CONV_PW_STREAM) return mtbt_pw_stream_batch(b, n, calls[0].dtype, s);
+  return conv_unit(calls[0].dtype).batch(b, n, c0, s);
 }
 
 extern "C" int mtbt_conv2d_nhwc_batch(const mtbt_conv_args* calls, int n, void* stream) { return conv_batch_impl(calls, n, stream, nullptr); }

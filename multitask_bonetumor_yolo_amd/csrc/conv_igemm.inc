@@ -21,6 +21,7 @@
 #pragma once
 #include "common.h"
 #include "conv_params.h"
+#include "conv_tiles.h"
 #include "conv_dma.h"
 #include "conv_epilogue.h"
 
@@ -47,68 +48,40 @@ __global__ __launch_bounds__(256, 2) void conv_igemm_batch_kernel(const ConvBatc
   const unsigned bid = blockIdx.x;
 #include "conv_igemm_body.inc"
 }
-
-template <typename T, int TC, int TP, int WAVES_C, int WAVES_P, int BKB, int NBUF>
-int launch_batch(const ConvBatchP& b, int n, hipStream_t stream) {
-  ConvBatchP q = b;
-  q.p.ctiles = (b.p.K + TC - 1) / TC;
-  const long ptiles = ((long)b.p.M + TP - 1) / TP;
-  q.p.ptiles_per_xcd = (int)((ptiles + 7) / 8);
-  const long blocks = (long)q.p.ptiles_per_xcd * 8 * q.p.ctiles;
-  if (blocks <= 0 || blocks > 0x7fffffffL || n < 1 || n > MTBT_CONV_BATCH_MAX) return MTBT_EINVAL;
-  constexpr int CPR = BKB / 16;
-  constexpr int TCS = ((TC * CPR + 255) / 256) * 256 / CPR;
-  constexpr int lds_main = NBUF * (TCS + TP) * BKB;
-  constexpr int lds_epi = 2 * 4 * 16 * ((TC / WAVES_C) * 4 + 16);
-  constexpr int lds = (lds_main > lds_epi ? lds_main : lds_epi) + 2 * TC * 4;
-  static_assert(lds <= 160 * 1024, "LDS");
-  if (int rc = mtbt_allow_lds(conv_igemm_batch_kernel<T, TC, TP, WAVES_C, WAVES_P, BKB, NBUF>, lds)) return rc;
-  hipLaunchKernelGGL((conv_igemm_batch_kernel<T, TC, TP, WAVES_C, WAVES_P, BKB, NBUF>), dim3((unsigned)blocks, (unsigned)n), dim3(256), lds, stream, q);
-  MTBT_LAUNCH_CHECK();
-  return MTBT_OK;
-}
 #endif
 
-template <typename T, int TC, int TP, int WAVES_C, int WAVES_P, int BKB, int NBUF>
-int launch(const ConvP& p, hipStream_t stream) {
-  ConvP q = p;
-  q.ctiles = (p.K + TC - 1) / TC;
-  const long ptiles = ((long)p.M + TP - 1) / TP;
-  q.ptiles_per_xcd = (int)((ptiles + 7) / 8);
-  const long blocks = (long)q.ptiles_per_xcd * 8 * q.ctiles;
-  if (blocks <= 0 || blocks > 0x7fffffffL) return MTBT_EINVAL;
+// One call (q a ConvP, n = 1) or one batch (q a ConvBatchP) of `kernel` on TC x TP tiles: the grid and the LDS bytes.
+template <int TC, int TP, int WAVES_C, int BKB, int NBUF, typename Kernel, typename Params>
+int launch_tile(Kernel kernel, Params q, int n, hipStream_t stream) {
   constexpr int CPR = BKB / 16;
   constexpr int TCS = ((TC * CPR + 255) / 256) * 256 / CPR;
   constexpr int lds_main = NBUF * (TCS + TP) * BKB;
   constexpr int lds_epi = 2 * 4 * 16 * ((TC / WAVES_C) * 4 + 16);
   constexpr int lds = (lds_main > lds_epi ? lds_main : lds_epi) + 2 * TC * 4;
-  if constexpr (lds > 160 * 1024) {
-    return MTBT_EINVAL;  // this (tile, depth) does not fit the CU's 160 KiB of LDS
-  } else {
-  if (int rc = mtbt_allow_lds(conv_igemm_kernel<T, TC, TP, WAVES_C, WAVES_P, BKB, NBUF>, lds)) return rc;
-  hipLaunchKernelGGL((conv_igemm_kernel<T, TC, TP, WAVES_C, WAVES_P, BKB, NBUF>), dim3((unsigned)blocks), dim3(256), lds, stream, q);
-  MTBT_LAUNCH_CHECK();
-  return MTBT_OK;
-  }
+  static_assert(lds <= 160 * 1024, "this (tile, depth) does not fit the CU's 160 KiB of LDS");
+  return conv_launch_tiles(kernel, q, TC, ((long)conv_of(q).M + TP - 1) / TP, n, lds, stream);
 }
 
+// every tile of the table (conv_tiles.h)
 template <typename T, int BKB, int NBUF>
 int dispatch_tile(const ConvP& p, int TC, int TP, hipStream_t s) {
-  // wave layouts keep each wave's output row >= 128 B (64 bf16 channels) wherever the tile allows: full-line stores.
-  // (Round 1 also built 256-pixel tiles, 3- and 4-deep pipelines and alternative wave layouts for the sweep in tools/conv_tune.py; none
-  // was ever the best choice, and with one epilogue body per activation they cost minutes of build time: removed.)
-  if (TP == 128) {
-    if (TC == 128) return launch<T, 128, 128, 2, 2, BKB, NBUF>(p, s);
-    if (TC == 96) return launch<T, 96, 128, 1, 4, BKB, NBUF>(p, s);
-    if (TC == 64) return launch<T, 64, 128, 1, 4, BKB, NBUF>(p, s);
-    if (TC == 32) return launch<T, 32, 128, 1, 4, BKB, NBUF>(p, s);
-  } else if (TP == 64) {
-    if (TC == 128) return launch<T, 128, 64, 2, 2, BKB, NBUF>(p, s);
-    if (TC == 96) return launch<T, 96, 64, 2, 2, BKB, NBUF>(p, s);
-    if (TC == 64) return launch<T, 64, 64, 1, 4, BKB, NBUF>(p, s);
-    if (TC == 32) return launch<T, 32, 64, 1, 4, BKB, NBUF>(p, s);
-  }
+#define MTBT_X(tc, tp, wc, wp, batched) \
+  if (TC == tc && TP == tp) return launch_tile<tc, tp, wc, BKB, NBUF>(conv_igemm_kernel<T, tc, tp, wc, wp, BKB, NBUF>, p, 1, s);
+  MTBT_CONV_TILES(MTBT_X)
+#undef MTBT_X
   return MTBT_EINVAL;
 }
+
+#ifdef MTBT_CONV_BATCH_UNIT
+// the table's batched tiles, with 128-byte K-steps
+template <typename T>
+int dispatch_tile_batch(const ConvBatchP& b, int n, int TC, int TP, hipStream_t s) {
+#define MTBT_X(tc, tp, wc, wp, batched) \
+  if constexpr (batched) { if (TC == tc && TP == tp) return launch_tile<tc, tp, wc, 128, 2>(conv_igemm_batch_kernel<T, tc, tp, wc, wp, 128, 2>, b, n, s); }
+  MTBT_CONV_TILES(MTBT_X)
+#undef MTBT_X
+  return MTBT_EINVAL;
+}
+#endif
 
 }  // namespace

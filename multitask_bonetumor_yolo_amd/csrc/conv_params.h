@@ -55,6 +55,23 @@ struct ConvBatchP {
 };
 
 #if defined(__HIPCC__)
+// Host side of every conv launch: `kernel` for one call (q a ConvP, n = 1) or one batch (q a ConvBatchP, n members) on `ptiles` pixel
+// tiles (in 8 XCD-contiguous ranges) of TC-channel tiles, 256 threads, `lds` bytes of dynamic LDS.  Fills q's tile counts.
+inline ConvP& conv_of(ConvP& p) { return p; }
+inline ConvP& conv_of(ConvBatchP& b) { return b.p; }
+template <typename Kernel, typename Params>
+int conv_launch_tiles(Kernel kernel, Params& q, int TC, long ptiles, int n, int lds, hipStream_t stream) {
+  ConvP& p = conv_of(q);
+  p.ctiles = (p.K + TC - 1) / TC;
+  p.ptiles_per_xcd = (int)((ptiles + 7) / 8);
+  const long blocks = (long)p.ptiles_per_xcd * 8 * p.ctiles;
+  if (blocks <= 0 || blocks > 0x7fffffffL || n < 1 || n > MTBT_CONV_BATCH_MAX) return MTBT_EINVAL;
+  if (int rc = mtbt_allow_lds(kernel, lds)) return rc;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks, (unsigned)n), dim3(256), lds, stream, q);
+  MTBT_LAUNCH_CHECK();
+  return MTBT_OK;
+}
+
 __device__ __forceinline__ ConvP conv_member(const ConvBatchP& b, int i) {
   ConvP p = b.p;
   const ConvMember& m = b.m[i];

@@ -663,3 +663,65 @@ def test_conv_column_sums(dtype, cfg):
     assert torch.equal(out2, out) or (out2.float() - out.float()).abs().max().item() <= 2e-2
     a.colsum_ws_bytes = part.numel() * 4 - 4
     assert lib.mtbt_conv2d_nhwc(C.byref(a), S()) == -4, "a partial buffer smaller than the layout is refused (MTBT_EWORKSPACE)"
+
+
+# every row of the implicit-GEMM tile table (csrc/conv_tiles.h) with both K-step widths, and the two direct 3x3 formulations:
+# (kind, channel tile, pixel tile, flag, hint, policy bits) -- flag = 128-byte K-steps (GEMM) / first formulation (direct)
+_NARROW, _ROW_REUSE, _FIRST_FORM = 1 << 27, 1 << 25, 16
+COLSUM_TILES = [(0, tc, tp, wide, (tc << 16) | tp | (0 if wide else _NARROW), 0) for tc in (128, 96, 64, 32) for tp in (128, 64) for wide in (1, 0)]
+COLSUM_DIRECT = [(1, tc, 256, first, 0 if first else _ROW_REUSE, _FIRST_FORM if first else 0) for tc in (64, 128) for first in (1, 0)]
+# partial rows per pixel tile, stated here independently of the table: the kernels' wave rows / the direct kernels' rows per 16 x 16 tile
+COLSUM_ROWS_PER_TILE = {(0, 128): 2, (0, 64): 4, (0, 32): 4, (1, 1): 4, (1, 0): 2}
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("tile", COLSUM_TILES + COLSUM_DIRECT, ids=lambda t: f"{'gemm' if t[0] == 0 else 'direct'}{t[1]}x{t[2]}-{t[3]}")
+def test_conv_column_sum_rows_of_every_tile(dtype, tile):
+    """The partial rows mtbt_conv_colsum_layout announces are exactly what the kernel of EVERY tile writes: the announced floats all
+    written, nothing behind them touched, their column sums the sums over the stored output, a buffer 4 bytes short refused.  The
+    96-channel tiles are refused with column sums (MTBT_EINVAL)."""
+    kind, TC, TP, flag, hint, policy = tile
+    lib = L.load()
+    torch.manual_seed(33)
+    if kind == 0:
+        N, H, W, Cc, K, k = 2, 9, 7, 64, TC + 8, 1          # 126 pixels: ragged for both pixel tiles; a channel tail and two channel tiles
+    else:
+        N, H, W, Cc, K, k = 1, 16, 16, 64, {64: 48, 128: 136}[TC], 3
+    x = torch.randn(N, Cc, H, W).to(dtype).float()
+    w = (torch.randn(K, Cc, k, k) / (Cc * k * k) ** 0.5).to(dtype).float()
+    shift = (torch.randn(K) * 0.1 + 0.4).to(DEV)
+    p = Plan(torch.device(DEV))
+    y = Act.of(torch.empty(N, H, W, K, dtype=dtype, device=DEV))
+    wp = w.permute(0, 2, 3, 1).reshape(K, -1).contiguous().to(DEV, dtype)
+    a = p.conv(Act.of(nhwc(x, dtype)), wp, y, R=k, S=k, pad=k // 2, shift=(torch.randn(K) * 0.3 + 0.5).to(DEV), tile_hint=hint, policy=policy)
+    a.colsum_shift, a.colsum_sq = shift.data_ptr(), 1
+    a.colsum_ws, a.colsum_ws_bytes = 0x1000, 1 << 30        # (the queries dereference nothing)
+    rows, pitch = C.c_int64(0), C.c_int32(0)
+    if TC == 96 and kind == 0:
+        assert lib.mtbt_conv_colsum_layout(C.byref(a), C.byref(rows), C.byref(pitch)) == -1
+        assert lib.mtbt_conv2d_nhwc(C.byref(a), S()) == -1, "96-channel tiles write no column sums (MTBT_EINVAL before any launch)"
+        return
+    choice = (C.c_int32 * 4)()
+    L.check(lib.mtbt_conv_kernel_choice(C.byref(a), choice), "choice")
+    assert tuple(choice) == (kind, TC, TP, flag)
+    L.check(lib.mtbt_conv_colsum_layout(C.byref(a), C.byref(rows), C.byref(pitch)), "layout")
+    ptiles = -(-N * H * W // TP) if kind == 0 else N * (H // 16) * (W // 16)
+    assert (rows.value, pitch.value) == (ptiles * COLSUM_ROWS_PER_TILE[(0, TC) if kind == 0 else (1, flag)], 2 * K)
+    n, GUARD, SENTINEL = rows.value * pitch.value, 4096, -12345.0
+    buf = torch.cat([torch.full((n,), float("nan")), torch.full((GUARD,), SENTINEL)]).to(DEV)
+    a.colsum_ws, a.colsum_ws_bytes = buf.data_ptr(), n * 4
+    p.run()
+    torch.cuda.synchronize()
+    part = buf[:n].cpu()
+    assert torch.isfinite(part).all(), "every announced float is written"
+    assert bool((buf[n:] == SENTINEL).all()), "nothing behind the announced rows is touched"
+    d = y.buf.float().cpu().reshape(-1, K).double() - shift.cpu().double()
+    got = part.double().view(rows.value, pitch.value).sum(0)
+    want1, want2 = d.sum(0), (d ** 2).sum(0)
+    tol = 2e-5 if dtype == torch.float32 else 2e-4        # (as test_conv_column_sums: accumulation order only, the summed values are the stored ones)
+    e1, b1 = (got[:K] - want1).abs().max().item(), tol * d.abs().sum(0).max().item() + 1e-6
+    e2, b2 = (got[K:] - want2).abs().max().item(), tol * want2.max().item() + 1e-6
+    print(f"column sums: err {e1:.3e} (bound {b1:.3e}), squares: err {e2:.3e} (bound {b2:.3e})")
+    assert e1 <= b1 and e2 <= b2
+    a.colsum_ws_bytes = n * 4 - 4
+    assert lib.mtbt_conv2d_nhwc(C.byref(a), S()) == -4, "a buffer 4 bytes short is refused (MTBT_EWORKSPACE)"
