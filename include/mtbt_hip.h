@@ -531,6 +531,27 @@ typedef struct {
 int mtbt_letterbox_batch(const mtbt_raw_image* images, int count, int img_size, float* out_images, float* out_masks,
                          double* out_scales, void* stream);
 
+/* Training augmentation fused into the same work: scale / aspect jitter, shift / crop, the eight dihedral orientations and a
+ * per-image intensity table, one launch per <= 32 images.  The reference has NO augmentation; this arithmetic is the project's own
+ * definition (which is why oracle/ holds no counterpart; tests/augment_reference.py restates it in numpy).
+ * geom: HOST int32 [count][geom_stride], geom_stride must be 8:
+ *   [0] new_w, [1] new_h   size of the resized image R, each in [1, 32768], independent of each other and of S
+ *   [2] off_x, [3] off_y   canvas offset of the oriented image, any int32 (negative offsets crop)
+ *   [4] orient             bit 0 flips x, bit 1 flips y, bit 2 transposes;  [5..7] reserved, must be 0
+ * R is the source resized to new_w x new_h by mtbt_letterbox_batch's arithmetic (8-bit INTER_LINEAR image, INTER_NEAREST mask, source
+ * step 1.0 / ((double)new / (double)old) per axis); it is never materialised.  The oriented image Q is (qh, qw) = (new_h, new_w), or
+ * (new_w, new_h) when transposed:  Q[y][x] = R[y'][x'] with x1 = bit 0 ? qw-1-x : x, y1 = bit 1 ? qh-1-y : y, (x', y') = bit 2 ? (y1, x1) : (x1, y1).
+ * Canvas O[dy][dx] = Q[dy-off_y][dx-off_x] where that lies inside Q; elsewhere the image is 114/255 and the mask 0 (an image wholly
+ * outside gives a pure pad image).  lut: DEVICE uint8 [count][3][256] in the source's BGR channel order or NULL (identity), applied to
+ * each resized 8-bit channel value before the one correctly rounded /255; pad pixels are not remapped.  Outputs as
+ * mtbt_letterbox_batch.  With the letterbox's new_w / new_h, zero offsets, orient 0 and no table the output equals
+ * mtbt_letterbox_batch bit for bit.  Every source index is clamped to the source: no geometry addresses outside it.
+ * MTBT_EINVAL before any launch: NULL images / geom / out_images, geom_stride != 8, img_size <= 0 or % 4, count < 0, new_w or new_h
+ * outside [1, 32768], orient outside 0..7, a non-zero reserved field, a descriptor mtbt_letterbox_batch refuses.  MTBT_EALIGN for
+ * outputs not 16-byte aligned. */
+int mtbt_augment_batch(const mtbt_raw_image* images, int count, int img_size, const int32_t* geom, int geom_stride,
+                       const uint8_t* lut, float* out_images, float* out_masks, void* stream);
+
 /* Segmentation metric accumulators (running_main_v3.py:466-498 feeding the torchmetrics objects of :198-203), SURVEY §8f N3.
  * logits, gt: [B][n_per_image] f32 (n % 4 == 0); prediction = sigmoid(logit) > 0.5, target = int(gt) >= 1.
  * counts [B][4] int64 = TP, FP, FN, TN per image; prob_sum [B] = sum of sigmoid(logit) over predicted-foreground pixels

@@ -19,6 +19,11 @@
 // One thread produces 4 horizontally adjacent output pixels of one image: three float4 plane stores + one mask
 // float4 store (the output, 16 B per pixel, is the HBM traffic that bounds the kernel); the <= 12 source bytes per pixel
 // are gathered through L2.
+//
+// augment_kernel is the same work with the sampling place chosen by the caller (the reference has NO augmentation: this
+// geometry is the project's own definition, include/mtbt_hip.h mtbt_augment_batch).  R = the source resized to new_w x new_h
+// by the arithmetic above (never materialised); Q = R under one of the eight dihedral orientations; the canvas shows Q at
+// (off_x, off_y), pad elsewhere; an optional 256-entry table per channel remaps the resized byte before the /255.
 #include "common.h"
 
 namespace {
@@ -33,6 +38,8 @@ struct RawImage {
   double scale_x, scale_y;   // source step per output pixel (cv2's 1 / inv_scale)
 };
 struct Batch { RawImage im[MAX_IMAGES]; };
+struct Placement { int off_x, off_y, orient, reserved; };   // of the oriented image Q on the canvas
+struct Placements { Placement p[MAX_IMAGES]; };              // 2048 + 512 bytes of kernel arguments with Batch
 
 __device__ __forceinline__ void linear_tap(int d, double scale, int size, int& s0, int& s1, int& c0, int& c1) {
   float f = (float)((d + 0.5) * scale - 0.5);
@@ -95,6 +102,89 @@ __global__ __launch_bounds__(256) void letterbox_kernel(const Batch b, int S, fl
   if (out_mask) *reinterpret_cast<float4*>(out_mask + (long)blockIdx.y * plane + (long)dy * S + dx0) = make_float4(m[0], m[1], m[2], m[3]);
 }
 
+// One thread = 4 horizontally adjacent canvas pixels, as above.  They lie on one row of Q, which is one row of R (a shared
+// vertical tap) or, transposed, one column of R (a shared horizontal tap); the other tap is per pixel.  Every source index
+// comes out of linear_tap / the clamped nearest index, so it lies in [0, size-1] whatever the geometry is.
+__global__ __launch_bounds__(256) void augment_kernel(const Batch b, const Placements pl, int S, const uint8_t* __restrict__ lut,
+                                                      float* __restrict__ out_img, float* __restrict__ out_mask) {
+  const RawImage& im = b.im[blockIdx.y];
+  const Placement& g = pl.p[blockIdx.y];
+  const int quads = S >> 2;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= S * quads) return;
+  const int dy = q / quads, dx0 = (q - dy * quads) << 2;
+  const bool flip_x = g.orient & 1, flip_y = g.orient & 2, transposed = g.orient & 4;
+  const int qw = transposed ? im.new_h : im.new_w, qh = transposed ? im.new_w : im.new_h;
+  // the axis of R that runs along a row of Q (per pixel) and the one across it (shared)
+  const double scale_p = transposed ? im.scale_y : im.scale_x, scale_s = transposed ? im.scale_x : im.scale_y;
+  const int size_p = transposed ? im.H0 : im.W0, size_s = transposed ? im.W0 : im.H0;
+  const uint8_t* table = lut ? lut + (long)blockIdx.y * 768 : nullptr;
+  float r[4], gr[4], bl[4], m[4];
+  const float pad = __fdiv_rn(114.f, 255.f);
+  const int qy = dy - g.off_y;
+  const bool row_in = qy >= 0 && qy < qh;
+  int s0 = 0, s1 = 0, cs0 = 0, cs1 = 0, ms = 0;
+  if (row_in) {
+    const int u = flip_y ? qh - 1 - qy : qy;
+    linear_tap(u, scale_s, size_s, s0, s1, cs0, cs1);
+    ms = max(min((int)floor(u * scale_s), size_s - 1), 0);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int qx = dx0 + i - g.off_x;
+    r[i] = gr[i] = bl[i] = pad;
+    m[i] = 0.f;
+    if (row_in && qx >= 0 && qx < qw) {
+      const int v = flip_x ? qw - 1 - qx : qx;
+      int p0, p1, cp0, cp1;
+      linear_tap(v, scale_p, size_p, p0, p1, cp0, cp1);
+      const int sx0 = transposed ? s0 : p0, sx1 = transposed ? s1 : p1, a0 = transposed ? cs0 : cp0, a1 = transposed ? cs1 : cp1;
+      const int sy0 = transposed ? p0 : s0, sy1 = transposed ? p1 : s1, b0 = transposed ? cp0 : cs0, b1 = transposed ? cp1 : cs1;
+      const uint8_t* row0 = im.bgr + sy0 * im.row_stride;
+      const uint8_t* row1 = im.bgr + sy1 * im.row_stride;
+      int o[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int r0 = row0[sx0 * 3 + c] * a0 + row0[sx1 * 3 + c] * a1;
+        const int r1 = row1[sx0 * 3 + c] * a0 + row1[sx1 * 3 + c] * a1;
+        const int t = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
+        o[c] = min(max(t, 0), 255);
+        if (table) o[c] = table[c * 256 + o[c]];
+      }
+      bl[i] = __fdiv_rn((float)o[0], 255.f);
+      gr[i] = __fdiv_rn((float)o[1], 255.f);
+      r[i] = __fdiv_rn((float)o[2], 255.f);
+      if (im.mask) {
+        const int mp = max(min((int)floor(v * scale_p), size_p - 1), 0);
+        const int mx = transposed ? ms : mp, my = transposed ? mp : ms;
+        m[i] = im.mask[my * im.mask_stride + mx] >= 128 ? 1.f : 0.f;
+      }
+    }
+  }
+  const long plane = (long)S * S;
+  float* o = out_img + (long)blockIdx.y * 3 * plane + (long)dy * S + dx0;
+  *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
+  *reinterpret_cast<float4*>(o + plane) = make_float4(gr[0], gr[1], gr[2], gr[3]);
+  *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(bl[0], bl[1], bl[2], bl[3]);
+  if (out_mask) *reinterpret_cast<float4*>(out_mask + (long)blockIdx.y * plane + (long)dy * S + dx0) = make_float4(m[0], m[1], m[2], m[3]);
+}
+
+// the descriptor checks both entry points make; fills everything but the resized size
+bool source_of(const mtbt_raw_image& s, RawImage& d) {
+  if (!s.bgr || s.height <= 0 || s.width <= 0 || s.row_stride < (int64_t)s.width * 3 || (s.mask && s.mask_row_stride < s.width) ||
+      (long)s.height * s.row_stride >= 0x7fffffffL)
+    return false;
+  d.bgr = s.bgr; d.mask = s.mask; d.row_stride = s.row_stride; d.mask_stride = s.mask_row_stride;
+  d.H0 = s.height; d.W0 = s.width;
+  return true;
+}
+
+void resized_to(RawImage& d, int new_w, int new_h) {
+  d.new_w = new_w; d.new_h = new_h;
+  d.scale_x = 1.0 / ((double)new_w / (double)d.W0);
+  d.scale_y = 1.0 / ((double)new_h / (double)d.H0);
+}
+
 }  // namespace
 
 extern "C" int mtbt_letterbox_batch(const mtbt_raw_image* images, int count, int img_size, float* out_images, float* out_masks,
@@ -107,25 +197,55 @@ extern "C" int mtbt_letterbox_batch(const mtbt_raw_image* images, int count, int
     Batch b;
     for (int i = 0; i < nb; ++i) {
       const mtbt_raw_image& s = images[first + i];
-      if (!s.bgr || s.height <= 0 || s.width <= 0 || s.row_stride < (int64_t)s.width * 3 || (s.mask && s.mask_row_stride < s.width) ||
-          (long)s.height * s.row_stride >= 0x7fffffffL)
-        return MTBT_EINVAL;
       RawImage& d = b.im[i];
-      d.bgr = s.bgr; d.mask = s.mask; d.row_stride = s.row_stride; d.mask_stride = s.mask_row_stride;
-      d.H0 = s.height; d.W0 = s.width;
+      if (!source_of(s, d)) return MTBT_EINVAL;
       // dataset_btxrdv2.py:114-117 in the same double arithmetic as Python's floats
       const double scale = (double)img_size / (double)(s.height > s.width ? s.height : s.width);
       const int nw = (int)((double)s.width * scale), nh = (int)((double)s.height * scale);
-      d.new_w = nw < 1 ? 1 : nw;
-      d.new_h = nh < 1 ? 1 : nh;
+      resized_to(d, nw < 1 ? 1 : nw, nh < 1 ? 1 : nh);
       if (d.new_w > img_size || d.new_h > img_size) return MTBT_EINVAL;   // cannot happen for scale = S / max(H0, W0)
-      d.scale_x = 1.0 / ((double)d.new_w / (double)s.width);
-      d.scale_y = 1.0 / ((double)d.new_h / (double)s.height);
       if (out_scales) out_scales[first + i] = scale;
     }
     const unsigned gx = (unsigned)((plane / 4 + 255) / 256);
     hipLaunchKernelGGL(letterbox_kernel, dim3(gx, (unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b, img_size,
                        out_images + (long)first * 3 * plane, out_masks ? out_masks + (long)first * plane : nullptr);
+    MTBT_LAUNCH_CHECK();
+  }
+  return MTBT_OK;
+}
+
+extern "C" int mtbt_augment_batch(const mtbt_raw_image* images, int count, int img_size, const int32_t* geom, int geom_stride,
+                                  const uint8_t* lut, float* out_images, float* out_masks, void* stream) {
+  if (!images || !geom || !out_images || count < 0 || img_size <= 0 || img_size % 4 || geom_stride != 8) return MTBT_EINVAL;
+  if (!aligned16(out_images) || (out_masks && !aligned16(out_masks))) return MTBT_EALIGN;
+  RawImage probe;
+  for (int i = 0; i < count; ++i) {   // every image is checked before the first launch
+    const int32_t* g = geom + (long)i * geom_stride;
+    if (!source_of(images[i], probe)) return MTBT_EINVAL;
+    if (g[0] < 1 || g[0] > 32768 || g[1] < 1 || g[1] > 32768 || g[4] < 0 || g[4] > 7 || g[5] || g[6] || g[7]) return MTBT_EINVAL;
+  }
+  const long plane = (long)img_size * img_size;
+  for (int first = 0; first < count; first += MAX_IMAGES) {
+    const int nb = count - first < MAX_IMAGES ? count - first : MAX_IMAGES;
+    Batch b;
+    Placements pl;
+    for (int i = 0; i < nb; ++i) {
+      const int32_t* g = geom + (long)(first + i) * geom_stride;
+      RawImage& d = b.im[i];
+      source_of(images[first + i], d);
+      resized_to(d, g[0], g[1]);
+      // an offset beyond [-q, S] shows nothing of Q, exactly like the bound itself: clamped so that the kernel's int arithmetic cannot wrap
+      const int qw = (g[4] & 4) ? g[1] : g[0], qh = (g[4] & 4) ? g[0] : g[1];
+      Placement& p = pl.p[i];
+      p.off_x = g[2] < -qw ? -qw : (g[2] > img_size ? img_size : g[2]);
+      p.off_y = g[3] < -qh ? -qh : (g[3] > img_size ? img_size : g[3]);
+      p.orient = g[4];
+      p.reserved = 0;
+    }
+    const unsigned gx = (unsigned)((plane / 4 + 255) / 256);
+    hipLaunchKernelGGL(augment_kernel, dim3(gx, (unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b, pl, img_size,
+                       lut ? lut + (long)first * 768 : nullptr, out_images + (long)first * 3 * plane,
+                       out_masks ? out_masks + (long)first * plane : nullptr);
     MTBT_LAUNCH_CHECK();
   }
   return MTBT_OK;

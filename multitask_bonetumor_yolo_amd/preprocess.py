@@ -4,31 +4,34 @@
 `letterbox_batch` is the image work (one HIP launch per <= 32 images, no CPU path); `transform_yolo_labels` and
 `collate_boxes` are the label arithmetic, which is a handful of Python-float operations per box and stays on the host
 exactly as the reference writes it.
+
+Training augmentation (`augment_batch` and the functions after it) is NOT in the reference, whose dataset class augments
+nothing: scale / aspect jitter, shift / crop, the eight dihedral orientations and an intensity table are this project's own
+definition (include/mtbt_hip.h `mtbt_augment_batch`).  The image work is the letterbox's launch with the sampling place
+chosen by the caller; the parameters are drawn and the labels moved on the host.
 """
 import ctypes as C
+import math
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib as L
 
 
-def letterbox_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]] = None, img_size: int = 640):
-    """images: decoded BGR uint8 [H0, W0, 3] CUDA tensors (any sizes); masks: uint8 [H0, W0] CUDA tensors or None.
-    Returns (imgs [B,3,S,S] f32 RGB in [0,1], masks [B,1,S,S] f32 {0,1}, scales list[float]) -- `img_t`, `mask_t` and
-    `scale` of dataset_btxrdv2.py:153-166 for every sample, stacked like `collate_fn` (:264-265)."""
-    lib = L.load()
+def _descriptors(images, masks, who: str):
+    """Validate raw images / masks and describe them for the library.  Returns (descs, tensors to keep alive, device)."""
     B = len(images)
     if B == 0:
-        raise ValueError("letterbox_batch: empty batch")
-    dev = images[0].device
+        raise ValueError(f"{who}: empty batch")
     descs = (L.RawImage * B)()
     keep = []
     for i, im in enumerate(images):
         if not im.is_cuda:
-            raise RuntimeError("letterbox_batch: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+            raise RuntimeError(f"{who}: expected CUDA/HIP tensors on an MI355X (no CPU path)")
         if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3:
-            raise ValueError("letterbox_batch: images must be uint8 [H, W, 3] (BGR, as cv2.imread returns them)")
+            raise ValueError(f"{who}: images must be uint8 [H, W, 3] (BGR, as cv2.imread returns them)")
         if im.stride(2) != 1 or im.stride(1) != 3:
             im = im.contiguous()
         keep.append(im)
@@ -37,13 +40,23 @@ def letterbox_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Opt
         mk = masks[i] if masks is not None else None
         if mk is not None:
             if mk.dtype != torch.uint8 or tuple(mk.shape) != tuple(im.shape[:2]) or not mk.is_cuda:
-                raise ValueError("letterbox_batch: mask must be a CUDA uint8 [H, W] tensor of the image's size")
+                raise ValueError(f"{who}: mask must be a CUDA uint8 [H, W] tensor of the image's size")
             if mk.stride(1) != 1:
                 mk = mk.contiguous()
             keep.append(mk)
             d.mask, d.mask_row_stride = mk.data_ptr(), mk.stride(0)
         else:
             d.mask, d.mask_row_stride = None, 0
+    return descs, keep, images[0].device
+
+
+def letterbox_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]] = None, img_size: int = 640):
+    """images: decoded BGR uint8 [H0, W0, 3] CUDA tensors (any sizes); masks: uint8 [H0, W0] CUDA tensors or None.
+    Returns (imgs [B,3,S,S] f32 RGB in [0,1], masks [B,1,S,S] f32 {0,1}, scales list[float]) -- `img_t`, `mask_t` and
+    `scale` of dataset_btxrdv2.py:153-166 for every sample, stacked like `collate_fn` (:264-265)."""
+    lib = L.load()
+    descs, keep, dev = _descriptors(images, masks, "letterbox_batch")
+    B = len(images)
     out = torch.empty(B, 3, img_size, img_size, device=dev, dtype=torch.float32)
     out_m = torch.empty(B, 1, img_size, img_size, device=dev, dtype=torch.float32)
     scales = (C.c_double * B)()
@@ -89,3 +102,151 @@ def collate_boxes(per_sample_rows: Sequence[Sequence[Sequence[float]]], device=N
             rows.append([float(i)] + [float(v) for v in r[1:6]])
     t = torch.tensor(rows, dtype=torch.float32) if rows else torch.zeros((0, 6), dtype=torch.float32)
     return t.to(device) if device is not None else t
+
+
+# ---- training augmentation (the project's own definition: the reference has none) ------------------------------------------
+GEOM_FIELDS = 8   # new_w, new_h, off_x, off_y, orient (bit 0 flip x, bit 1 flip y, bit 2 transpose), 3 reserved zeros
+
+
+def augment_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]], geom, lut: Optional[torch.Tensor] = None,
+                  img_size: int = 640):
+    """`letterbox_batch` with the geometry given per image: geom int [B, 8] rows (new_w, new_h, off_x, off_y, orient, 0, 0, 0) as
+    `letterbox_geometry` / `sample_geometry` return them, lut an optional CUDA uint8 [B, 3, 256] table (BGR order, `photometric_lut`).
+    Returns (imgs [B,3,S,S] f32 RGB in [0,1], masks [B,1,S,S] f32 {0,1}); one launch per <= 32 images, no CPU path."""
+    lib = L.load()
+    descs, keep, dev = _descriptors(images, masks, "augment_batch")
+    B = len(images)
+    g = np.asarray(geom.cpu() if isinstance(geom, torch.Tensor) else geom)
+    if g.dtype.kind not in "iu" or g.shape != (B, GEOM_FIELDS):
+        raise ValueError(f"augment_batch: geom must be an integer array of shape [{B}, {GEOM_FIELDS}]")
+    if g.size and (g.min() < -2 ** 31 or g.max() >= 2 ** 31):
+        raise ValueError("augment_batch: geom values must fit int32")
+    g = np.ascontiguousarray(g, dtype=np.int32)
+    if lut is not None:
+        if not isinstance(lut, torch.Tensor) or not lut.is_cuda or lut.dtype != torch.uint8 or tuple(lut.shape) != (B, 3, 256) or lut.device != dev:
+            raise ValueError(f"augment_batch: lut must be a CUDA uint8 [{B}, 3, 256] tensor on the images' device")
+        lut = lut.contiguous()
+        keep.append(lut)
+    out = torch.empty(B, 3, img_size, img_size, device=dev, dtype=torch.float32)
+    out_m = torch.empty(B, 1, img_size, img_size, device=dev, dtype=torch.float32)
+    L.check(lib.mtbt_augment_batch(descs, B, img_size, g.ctypes.data_as(C.POINTER(C.c_int32)), GEOM_FIELDS,
+                                   None if lut is None else lut.data_ptr(), out.data_ptr(), out_m.data_ptr(),
+                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_augment_batch")
+    for t in keep:   # the launch is asynchronous: keep the sources alive until the stream has consumed them
+        t.record_stream(torch.cuda.current_stream(dev))
+    return out, out_m
+
+
+def letterbox_geometry(sizes: Sequence[Sequence[int]], img_size: int) -> np.ndarray:
+    """sizes: (H0, W0) per image.  The identity parameters: the reference's new_w / new_h (dataset_btxrdv2.py:114-117), zero
+    offsets, orient 0 -- `augment_batch` with them and no table is `letterbox_batch`."""
+    geom = np.zeros((len(sizes), GEOM_FIELDS), dtype=np.int32)
+    for i, (H0, W0) in enumerate(sizes):
+        s = img_size / max(H0, W0)
+        geom[i, 0], geom[i, 1] = max(1, int(W0 * s)), max(1, int(H0 * s))
+    return geom
+
+
+def sample_geometry(sizes: Sequence[Sequence[int]], img_size: int, rng: np.random.Generator, *, scale=(0.5, 1.5), aspect: float = 0.0,
+                    fliplr: float = 0.5, flipud: float = 0.0, transpose: float = 0.0, place: str = "random") -> np.ndarray:
+    """Draw one geometry row per image.  new_w = max(1, int(W0 * s * g * a)), new_h = max(1, int(H0 * s * g / a)) with
+    s = S / max(H0, W0), g ~ U(scale), a = exp(U(-aspect, aspect)); each orientation bit is set with its probability;
+    place "topleft" puts the oriented image at (0, 0), "random" at floor(u * (S - q)) per axis, u ~ U[0, 1): a random position while
+    the canvas has padding on that axis, a random crop window once the image is larger than the canvas.  The draws come in a fixed
+    order (g, a, the three bits, the two offsets; one vector of B each), so a seeded generator gives the same array again."""
+    if place not in ("random", "topleft"):
+        raise ValueError("sample_geometry: place must be 'random' or 'topleft'")
+    B = len(sizes)
+    g = rng.uniform(scale[0], scale[1], B)
+    a = np.exp(rng.uniform(-aspect, aspect, B))
+    bits = [rng.random(B) < p for p in (fliplr, flipud, transpose)]
+    u = rng.random((B, 2))
+    geom = np.zeros((B, GEOM_FIELDS), dtype=np.int32)
+    for i, (H0, W0) in enumerate(sizes):
+        s = img_size / max(H0, W0)
+        new_w = min(max(1, int(W0 * s * float(g[i]) * float(a[i]))), 32768)
+        new_h = min(max(1, int(H0 * s * float(g[i]) / float(a[i]))), 32768)
+        orient = int(bits[0][i]) | int(bits[1][i]) << 1 | int(bits[2][i]) << 2
+        qw, qh = (new_h, new_w) if orient & 4 else (new_w, new_h)
+        off_x = off_y = 0
+        if place == "random":
+            off_x, off_y = math.floor(float(u[i, 0]) * (img_size - qw)), math.floor(float(u[i, 1]) * (img_size - qh))
+        geom[i, :5] = new_w, new_h, off_x, off_y, orient
+    return geom
+
+
+def photometric_lut(brightness, contrast, gamma) -> np.ndarray:
+    """Per-image scalars [B] -> uint8 [B, 3, 256]: row v -> rint(255 * (contrast * ((v / 255) ** gamma - 0.5) + 0.5 + brightness))
+    clipped to 0..255, in float64, the same row for the three channels.  (0, 1, 1) is the identity table."""
+    b, c, g = (np.atleast_1d(np.asarray(v, dtype=np.float64)) for v in (brightness, contrast, gamma))
+    v = np.arange(256, dtype=np.float64) / 255.0
+    row = np.rint(255.0 * (c[:, None] * (v[None, :] ** g[:, None] - 0.5) + 0.5 + b[:, None]))
+    row = np.clip(row, 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(np.repeat(row[:, None, :], 3, axis=1))
+
+
+def sample_photometric(B: int, rng: np.random.Generator, *, brightness: float = 0.2, contrast: float = 0.2, gamma: float = 0.2) -> np.ndarray:
+    """Draw brightness ~ U(+-brightness), contrast ~ U(1 +- contrast), gamma = exp(U(+-gamma)) per image -> `photometric_lut`."""
+    b = rng.uniform(-brightness, brightness, B)
+    c = rng.uniform(1.0 - contrast, 1.0 + contrast, B)
+    g = np.exp(rng.uniform(-gamma, gamma, B))
+    return photometric_lut(b, c, g)
+
+
+def augment_yolo_labels(rows: Sequence[Sequence[float]], W0: int, H0: int, geom_row, img_size: int, *, min_px: float = 2.0,
+                        min_area_ratio: float = 0.1, max_aspect: float = 100.0) -> List[List[float]]:
+    """YOLO-txt rows (cls, xc, yc, w, h normalised to the ORIGINAL image) -> [0.0, cls, cx, cy, w, h] normalised to the augmented
+    S x S canvas of `augment_batch` under geom_row.  Corners in source pixels, times new / old per axis, through the orientation (the
+    pixel map Q -> R of the kernel, inverted: transpose swap, then x -> qw - x, y -> qh - y), plus the offsets, clipped to [0, S].
+    A box is dropped when a clipped side is < min_px, when clipped area / unclipped area <= min_area_ratio (mostly cropped away), or
+    when its side ratio is >= max_aspect.  Python floats, like `transform_yolo_labels`."""
+    new_w, new_h, off_x, off_y, orient = (int(v) for v in geom_row[:5])
+    qw, qh = (new_h, new_w) if orient & 4 else (new_w, new_h)
+    kx, ky, S = new_w / W0, new_h / H0, float(img_size)
+    clip = lambda v: min(max(v, 0.0), S)
+    out = []
+    for r in rows:
+        if len(r) < 5:
+            continue
+        cls, xc, yc, w, h = (float(v) for v in r[:5])
+        if w <= 0 or h <= 0:
+            continue
+        x1, y1, x2, y2 = (xc - w / 2) * W0 * kx, (yc - h / 2) * H0 * ky, (xc + w / 2) * W0 * kx, (yc + h / 2) * H0 * ky
+        if orient & 4:
+            x1, y1, x2, y2 = y1, x1, y2, x2
+        if orient & 1:
+            x1, x2 = qw - x2, qw - x1
+        if orient & 2:
+            y1, y2 = qh - y2, qh - y1
+        x1, y1, x2, y2 = x1 + off_x, y1 + off_y, x2 + off_x, y2 + off_y
+        area = (x2 - x1) * (y2 - y1)
+        cx1, cy1, cx2, cy2 = clip(x1), clip(y1), clip(x2), clip(y2)
+        cw, ch = cx2 - cx1, cy2 - cy1
+        if cw < min_px or ch < min_px or cw <= 0.0 or ch <= 0.0:
+            continue
+        if cw * ch / area <= min_area_ratio:
+            continue
+        if max(cw / ch, ch / cw) >= max_aspect:
+            continue
+        out.append([0.0, cls, (cx1 + cx2) / 2 / S, (cy1 + cy2) / 2 / S, cw / S, ch / S])
+    return out
+
+
+def augment_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]],
+                    rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int, rng: np.random.Generator, **ranges):
+    """Draw geometry and intensity, run `augment_batch`, move the labels: (imgs [B,3,S,S], masks [B,1,S,S], gt_rows [M,6] on the
+    device, batch index in column 0) -- what `TrainStep.step` takes.  `ranges` are the keyword arguments of `sample_geometry`,
+    `sample_photometric` and `augment_yolo_labels`; anything else is an error."""
+    geo = {k: ranges.pop(k) for k in ("scale", "aspect", "fliplr", "flipud", "transpose", "place") if k in ranges}
+    pho = {k: ranges.pop(k) for k in ("brightness", "contrast", "gamma") if k in ranges}
+    lab = {k: ranges.pop(k) for k in ("min_px", "min_area_ratio", "max_aspect") if k in ranges}
+    if ranges:
+        raise TypeError(f"augment_samples: unknown arguments {sorted(ranges)}")
+    if len(rows_per_image) != len(images):
+        raise ValueError("augment_samples: one list of label rows per image")
+    sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+    geom = sample_geometry(sizes, img_size, rng, **geo)
+    lut = torch.from_numpy(sample_photometric(len(images), rng, **pho)).to(images[0].device)
+    imgs, out_masks = augment_batch(images, masks, geom, lut, img_size)
+    rows = [augment_yolo_labels(r, W0, H0, geom[i], img_size, **lab) for i, (r, (H0, W0)) in enumerate(zip(rows_per_image, sizes))]
+    return imgs, out_masks, collate_boxes(rows, device=imgs.device)
