@@ -552,6 +552,26 @@ int mtbt_letterbox_batch(const mtbt_raw_image* images, int count, int img_size, 
 int mtbt_augment_batch(const mtbt_raw_image* images, int count, int img_size, const int32_t* geom, int geom_stride,
                        const uint8_t* lut, float* out_images, float* out_masks, void* stream);
 
+/* Four-image mosaic on the same arithmetic (the project's own definition as well; tests/mosaic_reference.py restates it from
+ * tests/augment_reference.py).  A canvas is S x S with a centre (cx, cy), 0 <= cx <= S, cx % 4 == 0, 0 <= cy <= S, which cuts it into four
+ * half-open rectangles, x then y:
+ *   tile 0 [0,cx) x [0,cy)    tile 1 [cx,S) x [0,cy)    tile 2 [0,cx) x [cy,S)    tile 3 [cx,S) x [cy,S)
+ * Tile t of canvas i has its own source descriptor tiles[4*i + t] and its own geometry row geom[4*i + t] = (new_w, new_h, off_x, off_y,
+ * orient, 0, 0, 0), which means exactly what it means in mtbt_augment_batch, its offsets in CANVAS coordinates: inside its rectangle the
+ * canvas equals what mtbt_augment_batch would draw for that source and row on a whole S x S canvas (image, 114/255 pad and mask); outside
+ * its rectangle a tile draws nothing.  lut: one optional table per CANVAS (DEVICE uint8 [count][3][256], BGR order) that remaps the resized
+ * bytes of all four tiles, never the pad.  A tile whose descriptor has no mask contributes zeros to its rectangle.  An empty rectangle (cx
+ * or cy at 0 or S) is legal; with the centre at (S, S) tile 0 is the whole canvas and the result is mtbt_augment_batch of tile 0, bit for
+ * bit, so a batch that mixes mosaic and plain canvases is one call.  Descriptors may repeat.  One launch per <= 8 canvases (32 descriptors);
+ * every output byte is written exactly once; every source index is clamped to its source.  Outputs as mtbt_letterbox_batch.
+ * MTBT_EINVAL before any launch, every canvas checked first: NULL tiles / geom / centres / out_images, geom_stride != 8, count < 0,
+ * img_size <= 0 or % 4, cx outside [0, S] or % 4, cy outside [0, S], any of a canvas's four rows or descriptors that mtbt_augment_batch
+ * would refuse (also those of an empty tile).  MTBT_EALIGN, after those, for outputs not 16-byte aligned.  count == 0 is MTBT_OK. */
+int mtbt_mosaic_batch(const mtbt_raw_image* tiles /* HOST [4*count], canvas-major, repeats allowed */, int count, int img_size,
+                      const int32_t* geom /* HOST [4*count][geom_stride], geom_stride == 8 */, int geom_stride,
+                      const int32_t* centres /* HOST [count][2] = cx, cy */, const uint8_t* lut /* DEVICE [count][3][256] or NULL */,
+                      float* out_images, float* out_masks /* NULL = skip */, void* stream);
+
 /* Segmentation metric accumulators (running_main_v3.py:466-498 feeding the torchmetrics objects of :198-203), SURVEY §8f N3.
  * logits, gt: [B][n_per_image] f32 (n % 4 == 0); prediction = sigmoid(logit) > 0.5, target = int(gt) >= 1.
  * counts [B][4] int64 = TP, FP, FN, TN per image; prob_sum [B] = sum of sigmoid(logit) over predicted-foreground pixels

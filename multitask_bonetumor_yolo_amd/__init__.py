@@ -4,6 +4,7 @@
     from multitask_bonetumor_yolo_amd import postprocess                 # decode / NMS / masks on the GPU
     from multitask_bonetumor_yolo_amd import preprocess                  # letterbox / BGR->RGB / /255 of a batch on the GPU
     from multitask_bonetumor_yolo_amd import augment_samples             # training augmentation fused into that launch (the reference has none)
+    from multitask_bonetumor_yolo_amd import mosaic_samples              # the same with four images per canvas
     from multitask_bonetumor_yolo_amd import multitask_loss              # == MultiTaskLitModel._multitask_loss (value)
     from multitask_bonetumor_yolo_amd import instance_mask_loss          # YOLOv8-seg instance-mask loss + gradients (opt-in extension)
     from multitask_bonetumor_yolo_amd import ValidationStep              # == validation_step + the epoch-end metrics, on the device
@@ -12,8 +13,8 @@ The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
 """
 from . import postprocess, preprocess  # noqa: F401
-from .preprocess import (augment_batch, augment_samples, augment_yolo_labels, letterbox_geometry, photometric_lut,  # noqa: F401
-                         sample_geometry, sample_photometric)
+from .preprocess import (augment_batch, augment_samples, augment_yolo_labels, letterbox_geometry, mosaic_batch, mosaic_samples,  # noqa: F401
+                         mosaic_yolo_labels, photometric_lut, sample_geometry, sample_mosaic, sample_photometric)
 from .loss import InstanceMaskLoss, instance_mask_loss, multitask_loss  # noqa: F401
 from .checkpoints import load_pretrained_heads, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401

@@ -181,6 +181,7 @@ SYMBOLS = {
     "mtbt_bbox_iou_pairwise": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "mtbt_letterbox_batch": (C.c_int, [C.POINTER(RawImage), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "mtbt_augment_batch": (C.c_int, [C.POINTER(RawImage), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtbt_mosaic_batch": (C.c_int, [C.POINTER(RawImage), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtbt_seg_confusion_workspace_bytes": (C.c_int64, [C.c_int]),
     "mtbt_seg_confusion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mtbt_conv_wgrad_workspace_bytes": (C.c_int64, [C.c_int] * 7),

@@ -24,6 +24,10 @@
 // geometry is the project's own definition, include/mtbt_hip.h mtbt_augment_batch).  R = the source resized to new_w x new_h
 // by the arithmetic above (never materialised); Q = R under one of the eight dihedral orientations; the canvas shows Q at
 // (off_x, off_y), pad elsewhere; an optional 256-entry table per channel remaps the resized byte before the /255.
+//
+// mosaic_kernel is augment_kernel's pixel with the source picked per canvas region (include/mtbt_hip.h mtbt_mosaic_batch): a centre
+// (cx, cy) cuts the canvas into four rectangles, each of which shows its own source under its own geometry row.  cx % 4 == 0, so the
+// four pixels of a thread share a rectangle; one blockIdx.y per (canvas, rectangle) keeps descriptor and placement scalar.
 #include "common.h"
 
 namespace {
@@ -40,6 +44,8 @@ struct RawImage {
 struct Batch { RawImage im[MAX_IMAGES]; };
 struct Placement { int off_x, off_y, orient, reserved; };   // of the oriented image Q on the canvas
 struct Placements { Placement p[MAX_IMAGES]; };              // 2048 + 512 bytes of kernel arguments with Batch
+constexpr int MAX_CANVASES = MAX_IMAGES / 4;                 // mosaic canvases per launch: four descriptors each
+struct Centres { int cx[MAX_CANVASES], cy[MAX_CANVASES]; };
 
 __device__ __forceinline__ void linear_tap(int d, double scale, int size, int& s0, int& s1, int& c0, int& c1) {
   float f = (float)((d + 0.5) * scale - 0.5);
@@ -169,7 +175,78 @@ __global__ __launch_bounds__(256) void augment_kernel(const Batch b, const Place
   if (out_mask) *reinterpret_cast<float4*>(out_mask + (long)blockIdx.y * plane + (long)dy * S + dx0) = make_float4(m[0], m[1], m[2], m[3]);
 }
 
-// the descriptor checks both entry points make; fills everything but the resized size
+// blockIdx.y = canvas * 4 + tile; blockIdx.x runs over the quads of that tile's rectangle [x0, x1) x [y0, y1) of the canvas (x0, x1 are
+// multiples of 4) and workgroups beyond it leave at once.  The four rectangles partition the canvas, so every output byte is written by
+// exactly one thread.  Inside the rectangle the pixel is augment_kernel's for descriptor / placement blockIdx.y (offsets in canvas
+// coordinates); the table is the canvas's.  Source indices as there: out of linear_tap / the clamped nearest index only.
+__global__ __launch_bounds__(256) void mosaic_kernel(const Batch b, const Placements pl, const Centres ce, int S, const uint8_t* __restrict__ lut,
+                                                     float* __restrict__ out_img, float* __restrict__ out_mask) {
+  const int canvas = blockIdx.y >> 2, tile = blockIdx.y & 3;
+  const int cx = ce.cx[canvas], cy = ce.cy[canvas];
+  const int x0 = (tile & 1) ? cx : 0, x1 = (tile & 1) ? S : cx, y0 = (tile & 2) ? cy : 0, y1 = (tile & 2) ? S : cy;
+  const int quads = (x1 - x0) >> 2;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= (y1 - y0) * quads) return;   // also the empty rectangle
+  const int ty = q / quads;
+  const int dy = y0 + ty, dx0 = x0 + ((q - ty * quads) << 2);
+  const RawImage& im = b.im[blockIdx.y];
+  const Placement& g = pl.p[blockIdx.y];
+  const bool flip_x = g.orient & 1, flip_y = g.orient & 2, transposed = g.orient & 4;
+  const int qw = transposed ? im.new_h : im.new_w, qh = transposed ? im.new_w : im.new_h;
+  const double scale_p = transposed ? im.scale_y : im.scale_x, scale_s = transposed ? im.scale_x : im.scale_y;
+  const int size_p = transposed ? im.H0 : im.W0, size_s = transposed ? im.W0 : im.H0;
+  const uint8_t* table = lut ? lut + (long)canvas * 768 : nullptr;
+  float r[4], gr[4], bl[4], m[4];
+  const float pad = __fdiv_rn(114.f, 255.f);
+  const int qy = dy - g.off_y;
+  const bool row_in = qy >= 0 && qy < qh;
+  int s0 = 0, s1 = 0, cs0 = 0, cs1 = 0, ms = 0;
+  if (row_in) {
+    const int u = flip_y ? qh - 1 - qy : qy;
+    linear_tap(u, scale_s, size_s, s0, s1, cs0, cs1);
+    ms = max(min((int)floor(u * scale_s), size_s - 1), 0);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int qx = dx0 + i - g.off_x;
+    r[i] = gr[i] = bl[i] = pad;
+    m[i] = 0.f;
+    if (row_in && qx >= 0 && qx < qw) {
+      const int v = flip_x ? qw - 1 - qx : qx;
+      int p0, p1, cp0, cp1;
+      linear_tap(v, scale_p, size_p, p0, p1, cp0, cp1);
+      const int sx0 = transposed ? s0 : p0, sx1 = transposed ? s1 : p1, a0 = transposed ? cs0 : cp0, a1 = transposed ? cs1 : cp1;
+      const int sy0 = transposed ? p0 : s0, sy1 = transposed ? p1 : s1, b0 = transposed ? cp0 : cs0, b1 = transposed ? cp1 : cs1;
+      const uint8_t* row0 = im.bgr + sy0 * im.row_stride;
+      const uint8_t* row1 = im.bgr + sy1 * im.row_stride;
+      int o[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int r0 = row0[sx0 * 3 + c] * a0 + row0[sx1 * 3 + c] * a1;
+        const int r1 = row1[sx0 * 3 + c] * a0 + row1[sx1 * 3 + c] * a1;
+        const int t = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
+        o[c] = min(max(t, 0), 255);
+        if (table) o[c] = table[c * 256 + o[c]];
+      }
+      bl[i] = __fdiv_rn((float)o[0], 255.f);
+      gr[i] = __fdiv_rn((float)o[1], 255.f);
+      r[i] = __fdiv_rn((float)o[2], 255.f);
+      if (im.mask) {
+        const int mp = max(min((int)floor(v * scale_p), size_p - 1), 0);
+        const int mx = transposed ? ms : mp, my = transposed ? mp : ms;
+        m[i] = im.mask[my * im.mask_stride + mx] >= 128 ? 1.f : 0.f;
+      }
+    }
+  }
+  const long plane = (long)S * S;
+  float* o = out_img + (long)canvas * 3 * plane + (long)dy * S + dx0;
+  *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
+  *reinterpret_cast<float4*>(o + plane) = make_float4(gr[0], gr[1], gr[2], gr[3]);
+  *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(bl[0], bl[1], bl[2], bl[3]);
+  if (out_mask) *reinterpret_cast<float4*>(out_mask + (long)canvas * plane + (long)dy * S + dx0) = make_float4(m[0], m[1], m[2], m[3]);
+}
+
+// the descriptor checks all entry points make; fills everything but the resized size
 bool source_of(const mtbt_raw_image& s, RawImage& d) {
   if (!s.bgr || s.height <= 0 || s.width <= 0 || s.row_stride < (int64_t)s.width * 3 || (s.mask && s.mask_row_stride < s.width) ||
       (long)s.height * s.row_stride >= 0x7fffffffL)
@@ -183,6 +260,22 @@ void resized_to(RawImage& d, int new_w, int new_h) {
   d.new_w = new_w; d.new_h = new_h;
   d.scale_x = 1.0 / ((double)new_w / (double)d.W0);
   d.scale_y = 1.0 / ((double)new_h / (double)d.H0);
+}
+
+// the geometry-row checks of mtbt_augment_batch and mtbt_mosaic_batch
+bool geom_ok(const int32_t* g) {
+  return g[0] >= 1 && g[0] <= 32768 && g[1] >= 1 && g[1] <= 32768 && g[4] >= 0 && g[4] <= 7 && !g[5] && !g[6] && !g[7];
+}
+
+// an offset beyond [-q, S] shows nothing of Q, exactly like the bound itself: clamped so that the kernel's int arithmetic cannot wrap
+Placement placed(const int32_t* g, int img_size) {
+  const int qw = (g[4] & 4) ? g[1] : g[0], qh = (g[4] & 4) ? g[0] : g[1];
+  Placement p;
+  p.off_x = g[2] < -qw ? -qw : (g[2] > img_size ? img_size : g[2]);
+  p.off_y = g[3] < -qh ? -qh : (g[3] > img_size ? img_size : g[3]);
+  p.orient = g[4];
+  p.reserved = 0;
+  return p;
 }
 
 }  // namespace
@@ -222,7 +315,7 @@ extern "C" int mtbt_augment_batch(const mtbt_raw_image* images, int count, int i
   for (int i = 0; i < count; ++i) {   // every image is checked before the first launch
     const int32_t* g = geom + (long)i * geom_stride;
     if (!source_of(images[i], probe)) return MTBT_EINVAL;
-    if (g[0] < 1 || g[0] > 32768 || g[1] < 1 || g[1] > 32768 || g[4] < 0 || g[4] > 7 || g[5] || g[6] || g[7]) return MTBT_EINVAL;
+    if (!geom_ok(g)) return MTBT_EINVAL;
   }
   const long plane = (long)img_size * img_size;
   for (int first = 0; first < count; first += MAX_IMAGES) {
@@ -234,17 +327,49 @@ extern "C" int mtbt_augment_batch(const mtbt_raw_image* images, int count, int i
       RawImage& d = b.im[i];
       source_of(images[first + i], d);
       resized_to(d, g[0], g[1]);
-      // an offset beyond [-q, S] shows nothing of Q, exactly like the bound itself: clamped so that the kernel's int arithmetic cannot wrap
-      const int qw = (g[4] & 4) ? g[1] : g[0], qh = (g[4] & 4) ? g[0] : g[1];
-      Placement& p = pl.p[i];
-      p.off_x = g[2] < -qw ? -qw : (g[2] > img_size ? img_size : g[2]);
-      p.off_y = g[3] < -qh ? -qh : (g[3] > img_size ? img_size : g[3]);
-      p.orient = g[4];
-      p.reserved = 0;
+      pl.p[i] = placed(g, img_size);
     }
     const unsigned gx = (unsigned)((plane / 4 + 255) / 256);
     hipLaunchKernelGGL(augment_kernel, dim3(gx, (unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b, pl, img_size,
                        lut ? lut + (long)first * 768 : nullptr, out_images + (long)first * 3 * plane,
+                       out_masks ? out_masks + (long)first * plane : nullptr);
+    MTBT_LAUNCH_CHECK();
+  }
+  return MTBT_OK;
+}
+
+extern "C" int mtbt_mosaic_batch(const mtbt_raw_image* tiles, int count, int img_size, const int32_t* geom, int geom_stride,
+                                 const int32_t* centres, const uint8_t* lut, float* out_images, float* out_masks, void* stream) {
+  if (!tiles || !geom || !centres || !out_images || count < 0 || img_size <= 0 || img_size % 4 || geom_stride != 8) return MTBT_EINVAL;
+  RawImage probe;
+  for (int i = 0; i < count; ++i) {   // every canvas is checked before the first launch, empty tiles included
+    const int cx = centres[2 * i], cy = centres[2 * i + 1];
+    if (cx < 0 || cx > img_size || cx % 4 || cy < 0 || cy > img_size) return MTBT_EINVAL;
+    for (int t = 0; t < 4; ++t)
+      if (!source_of(tiles[4L * i + t], probe) || !geom_ok(geom + (4L * i + t) * geom_stride)) return MTBT_EINVAL;
+  }
+  if (!aligned16(out_images) || (out_masks && !aligned16(out_masks))) return MTBT_EALIGN;
+  const long plane = (long)img_size * img_size;
+  for (int first = 0; first < count; first += MAX_CANVASES) {
+    const int nb = count - first < MAX_CANVASES ? count - first : MAX_CANVASES;
+    Batch b;
+    Placements pl;
+    Centres ce;
+    long most = 0;   // quads of the largest rectangle of this chunk: the grid's x extent
+    for (int i = 0; i < nb; ++i) {
+      const int cx = ce.cx[i] = centres[2 * (first + i)], cy = ce.cy[i] = centres[2 * (first + i) + 1];
+      for (int t = 0; t < 4; ++t) {
+        const long k = 4L * (first + i) + t;
+        RawImage& d = b.im[4 * i + t];
+        source_of(tiles[k], d);
+        resized_to(d, geom[k * geom_stride], geom[k * geom_stride + 1]);
+        pl.p[4 * i + t] = placed(geom + k * geom_stride, img_size);
+        const long quads = (long)(((t & 1) ? img_size - cx : cx) >> 2) * ((t & 2) ? img_size - cy : cy);
+        if (quads > most) most = quads;
+      }
+    }
+    hipLaunchKernelGGL(mosaic_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)(4 * nb)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b,
+                       pl, ce, img_size, lut ? lut + (long)first * 768 : nullptr, out_images + (long)first * 3 * plane,
                        out_masks ? out_masks + (long)first * plane : nullptr);
     MTBT_LAUNCH_CHECK();
   }

@@ -9,6 +9,10 @@ Training augmentation (`augment_batch` and the functions after it) is NOT in the
 nothing: scale / aspect jitter, shift / crop, the eight dihedral orientations and an intensity table are this project's own
 definition (include/mtbt_hip.h `mtbt_augment_batch`).  The image work is the letterbox's launch with the sampling place
 chosen by the caller; the parameters are drawn and the labels moved on the host.
+
+The four-image mosaic (`mosaic_batch` and the functions after it, include/mtbt_hip.h `mtbt_mosaic_batch`) is the same arithmetic
+with the source picked per canvas region: a centre cuts the canvas into four rectangles, each showing its own image under its own
+geometry row; with the centre at (S, S) a canvas is the plain augmentation of its first tile.
 """
 import ctypes as C
 import math
@@ -194,16 +198,19 @@ def sample_photometric(B: int, rng: np.random.Generator, *, brightness: float = 
 
 
 def augment_yolo_labels(rows: Sequence[Sequence[float]], W0: int, H0: int, geom_row, img_size: int, *, min_px: float = 2.0,
-                        min_area_ratio: float = 0.1, max_aspect: float = 100.0) -> List[List[float]]:
+                        min_area_ratio: float = 0.1, max_aspect: float = 100.0, clip_rect=None) -> List[List[float]]:
     """YOLO-txt rows (cls, xc, yc, w, h normalised to the ORIGINAL image) -> [0.0, cls, cx, cy, w, h] normalised to the augmented
     S x S canvas of `augment_batch` under geom_row.  Corners in source pixels, times new / old per axis, through the orientation (the
     pixel map Q -> R of the kernel, inverted: transpose swap, then x -> qw - x, y -> qh - y), plus the offsets, clipped to [0, S].
     A box is dropped when a clipped side is < min_px, when clipped area / unclipped area <= min_area_ratio (mostly cropped away), or
-    when its side ratio is >= max_aspect.  Python floats, like `transform_yolo_labels`."""
+    when its side ratio is >= max_aspect.  Python floats, like `transform_yolo_labels`.  clip_rect = (x0, y0, x1, y1) in canvas pixels
+    replaces the clip to [0, S] by the clip to that rectangle (a mosaic tile, `mosaic_yolo_labels`); None is the whole canvas."""
     new_w, new_h, off_x, off_y, orient = (int(v) for v in geom_row[:5])
     qw, qh = (new_h, new_w) if orient & 4 else (new_w, new_h)
     kx, ky, S = new_w / W0, new_h / H0, float(img_size)
-    clip = lambda v: min(max(v, 0.0), S)
+    rx0, ry0, rx1, ry1 = (0.0, 0.0, S, S) if clip_rect is None else (float(v) for v in clip_rect)
+    clip_x = lambda v: min(max(v, rx0), rx1)
+    clip_y = lambda v: min(max(v, ry0), ry1)
     out = []
     for r in rows:
         if len(r) < 5:
@@ -220,7 +227,7 @@ def augment_yolo_labels(rows: Sequence[Sequence[float]], W0: int, H0: int, geom_
             y1, y2 = qh - y2, qh - y1
         x1, y1, x2, y2 = x1 + off_x, y1 + off_y, x2 + off_x, y2 + off_y
         area = (x2 - x1) * (y2 - y1)
-        cx1, cy1, cx2, cy2 = clip(x1), clip(y1), clip(x2), clip(y2)
+        cx1, cy1, cx2, cy2 = clip_x(x1), clip_y(y1), clip_x(x2), clip_y(y2)
         cw, ch = cx2 - cx1, cy2 - cy1
         if cw < min_px or ch < min_px or cw <= 0.0 or ch <= 0.0:
             continue
@@ -249,4 +256,126 @@ def augment_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Opt
     lut = torch.from_numpy(sample_photometric(len(images), rng, **pho)).to(images[0].device)
     imgs, out_masks = augment_batch(images, masks, geom, lut, img_size)
     rows = [augment_yolo_labels(r, W0, H0, geom[i], img_size, **lab) for i, (r, (H0, W0)) in enumerate(zip(rows_per_image, sizes))]
+    return imgs, out_masks, collate_boxes(rows, device=imgs.device)
+
+
+# ---- four-image mosaic (the project's own definition as well) ------------------------------------------------------------------
+def tile_rects(centre, img_size: int):
+    """The four half-open rectangles (x0, y0, x1, y1) a centre (cx, cy) cuts an S x S canvas into, tile 0..3 (x then y)."""
+    cx, cy, S = int(centre[0]), int(centre[1]), int(img_size)
+    return [(0, 0, cx, cy), (cx, 0, S, cy), (0, cy, cx, S), (cx, cy, S, S)]
+
+
+def mosaic_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]], index, geom, centres,
+                 lut: Optional[torch.Tensor] = None, img_size: int = 640):
+    """B canvases of four tiles each: index int [B, 4] into `images` (repeats allowed), geom int [B, 4, 8] rows as for `augment_batch`
+    with the offsets in canvas coordinates, centres int [B, 2] = (cx, cy) with 0 <= cx <= S, cx % 4 == 0, 0 <= cy <= S, lut an optional
+    CUDA uint8 [B, 3, 256] table per CANVAS.  Tile t of a canvas shows, inside its rectangle (`tile_rects`), what `augment_batch` would
+    draw for images[index[b, t]] under geom[b, t]; a centre of (S, S) makes the canvas `augment_batch` of tile 0.
+    Returns (imgs [B,3,S,S] f32 RGB in [0,1], masks [B,1,S,S] f32 {0,1}); one launch per <= 8 canvases, no CPU path."""
+    lib = L.load()
+    descs, keep, dev = _descriptors(images, masks, "mosaic_batch")
+    idx = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
+    if idx.dtype.kind not in "iu" or idx.ndim != 2 or idx.shape[1] != 4:
+        raise ValueError("mosaic_batch: index must be an integer array of shape [B, 4]")
+    B = idx.shape[0]
+    if B == 0:
+        raise ValueError("mosaic_batch: empty batch")
+    if idx.min() < 0 or idx.max() >= len(images):
+        raise ValueError(f"mosaic_batch: index values must lie in [0, {len(images)})")
+    g = np.asarray(geom.cpu() if isinstance(geom, torch.Tensor) else geom)
+    if g.dtype.kind not in "iu" or g.shape != (B, 4, GEOM_FIELDS):
+        raise ValueError(f"mosaic_batch: geom must be an integer array of shape [{B}, 4, {GEOM_FIELDS}]")
+    c = np.asarray(centres.cpu() if isinstance(centres, torch.Tensor) else centres)
+    if c.dtype.kind not in "iu" or c.shape != (B, 2):
+        raise ValueError(f"mosaic_batch: centres must be an integer array of shape [{B}, 2]")
+    for a in (g, c):
+        if a.min() < -2 ** 31 or a.max() >= 2 ** 31:
+            raise ValueError("mosaic_batch: geom and centres values must fit int32")
+    g, c = np.ascontiguousarray(g, dtype=np.int32), np.ascontiguousarray(c, dtype=np.int32)
+    if lut is not None:
+        if not isinstance(lut, torch.Tensor) or not lut.is_cuda or lut.dtype != torch.uint8 or tuple(lut.shape) != (B, 3, 256) or lut.device != dev:
+            raise ValueError(f"mosaic_batch: lut must be a CUDA uint8 [{B}, 3, 256] tensor on the images' device")
+        lut = lut.contiguous()
+        keep.append(lut)
+    # the four descriptors of every canvas, gathered in one step (the library reads them before it returns)
+    tiles = np.ascontiguousarray(np.frombuffer(descs, dtype=np.uint8).reshape(len(images), C.sizeof(L.RawImage))[idx.reshape(-1)])
+    out = torch.empty(B, 3, img_size, img_size, device=dev, dtype=torch.float32)
+    out_m = torch.empty(B, 1, img_size, img_size, device=dev, dtype=torch.float32)
+    L.check(lib.mtbt_mosaic_batch(tiles.ctypes.data_as(C.POINTER(L.RawImage)), B, img_size, g.ctypes.data_as(C.POINTER(C.c_int32)), GEOM_FIELDS, c.ctypes.data_as(C.POINTER(C.c_int32)),
+                                  None if lut is None else lut.data_ptr(), out.data_ptr(), out_m.data_ptr(),
+                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_mosaic_batch")
+    for t in keep:   # the launch is asynchronous: keep the sources alive until the stream has consumed them
+        t.record_stream(torch.cuda.current_stream(dev))
+    return out, out_m
+
+
+def sample_mosaic(sizes: Sequence[Sequence[int]], img_size: int, rng: np.random.Generator, *, prob: float = 1.0, centre=(0.25, 0.75),
+                  scale=(0.5, 1.0), aspect: float = 0.0, fliplr: float = 0.5, flipud: float = 0.0, transpose: float = 0.0):
+    """Draw one canvas per entry of sizes ((H0, W0) per image): (index int64 [B, 4], geom int32 [B, 4, 8], centres int32 [B, 2]) for
+    `mosaic_batch`.  Canvas i is a mosaic with probability prob: image i sits in a tile drawn from 0..3, the three other tiles show images
+    drawn uniformly from all B with replacement, cx = 4 * floor(u * S / 4) and cy = floor(u * S) with u ~ U(centre) each, every tile's
+    new_w / new_h / orientation follow `sample_geometry`'s formula for its own image, and the oriented image (qw x qh) is placed so that
+    the corner facing the centre touches it: offsets (cx - qw, cy - qh), (cx, cy - qh), (cx - qw, cy), (cx, cy) for tiles 0..3.
+    Otherwise the centre is (S, S), tile 0 is image i under a `sample_geometry(place="random")` row and tiles 1..3 are image i under the
+    letterbox row (drawn nowhere): `mosaic_batch` then gives `augment_batch` of tile 0.
+    The draws come in a fixed order whatever prob is -- the mosaic decision (B), the own tile position (B), the other sources (B x 3),
+    the centres (B x 2: x, y), then ONE `sample_geometry(place="random")` call over the 4 B tiles in canvas-major order -- so a seeded
+    generator gives the same arrays again."""
+    B, S = len(sizes), int(img_size)
+    is_mosaic = rng.random(B) < prob
+    own = rng.integers(0, 4, B)
+    others = rng.integers(0, max(B, 1), (B, 3))
+    u = rng.uniform(centre[0], centre[1], (B, 2))
+    index = np.repeat(np.arange(B, dtype=np.int64)[:, None], 4, axis=1)
+    for i in range(B):
+        if is_mosaic[i]:
+            index[i, [t for t in range(4) if t != own[i]]] = others[i]
+    geom = sample_geometry([sizes[k] for k in index.reshape(-1)], S, rng, scale=scale, aspect=aspect, fliplr=fliplr, flipud=flipud,
+                           transpose=transpose, place="random").reshape(B, 4, GEOM_FIELDS)
+    centres = np.full((B, 2), S, dtype=np.int32)
+    for i in range(B):
+        if is_mosaic[i]:
+            cx, cy = 4 * math.floor(float(u[i, 0]) * S / 4), math.floor(float(u[i, 1]) * S)
+            centres[i] = cx, cy
+            for t in range(4):
+                new_w, new_h, orient = (int(v) for v in geom[i, t, [0, 1, 4]])
+                qw, qh = (new_h, new_w) if orient & 4 else (new_w, new_h)
+                geom[i, t, 2], geom[i, t, 3] = (cx if t & 1 else cx - qw), (cy if t & 2 else cy - qh)
+        else:
+            geom[i, 1:] = letterbox_geometry([sizes[i]], S)[0]
+    return index, geom, centres
+
+
+def mosaic_yolo_labels(rows_per_tile: Sequence[Sequence[Sequence[float]]], sizes_per_tile: Sequence[Sequence[int]], geom4, centre, img_size: int, *,
+                       min_px: float = 2.0, min_area_ratio: float = 0.1, max_aspect: float = 100.0) -> List[List[float]]:
+    """The label rows of one mosaic canvas: `augment_yolo_labels` per tile (rows and (H0, W0) of the tile's image, geom4[t]) with the clip
+    to [0, S] replaced by the clip to the tile's rectangle, the same drop rules, the four tiles' rows concatenated in tile order."""
+    if not (len(rows_per_tile) == len(sizes_per_tile) == len(geom4) == 4):
+        raise ValueError("mosaic_yolo_labels: four tiles per canvas")
+    out = []
+    for rows, (H0, W0), g, rect in zip(rows_per_tile, sizes_per_tile, geom4, tile_rects(centre, img_size)):
+        out += augment_yolo_labels(rows, W0, H0, g, img_size, min_px=min_px, min_area_ratio=min_area_ratio, max_aspect=max_aspect, clip_rect=rect)
+    return out
+
+
+def mosaic_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]],
+                   rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int, rng: np.random.Generator, **ranges):
+    """`augment_samples` with four images per canvas: draw `sample_mosaic`, then `sample_photometric` (one table per canvas) from the one
+    generator, run `mosaic_batch`, move the labels with `mosaic_yolo_labels`: (imgs [B,3,S,S], masks [B,1,S,S], gt_rows [M,6] on the
+    device, batch index = canvas in column 0) -- what `TrainStep.step` takes.  `ranges` are the keyword arguments of those three functions;
+    anything else is an error."""
+    geo = {k: ranges.pop(k) for k in ("prob", "centre", "scale", "aspect", "fliplr", "flipud", "transpose") if k in ranges}
+    pho = {k: ranges.pop(k) for k in ("brightness", "contrast", "gamma") if k in ranges}
+    lab = {k: ranges.pop(k) for k in ("min_px", "min_area_ratio", "max_aspect") if k in ranges}
+    if ranges:
+        raise TypeError(f"mosaic_samples: unknown arguments {sorted(ranges)}")
+    if len(rows_per_image) != len(images):
+        raise ValueError("mosaic_samples: one list of label rows per image")
+    sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+    index, geom, centres = sample_mosaic(sizes, img_size, rng, **geo)
+    lut = torch.from_numpy(sample_photometric(len(images), rng, **pho)).to(images[0].device)
+    imgs, out_masks = mosaic_batch(images, masks, index, geom, centres, lut, img_size)
+    rows = [mosaic_yolo_labels([rows_per_image[k] for k in index[i]], [sizes[k] for k in index[i]], geom[i], centres[i], img_size, **lab)
+            for i in range(len(images))]
     return imgs, out_masks, collate_boxes(rows, device=imgs.device)
