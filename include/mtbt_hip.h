@@ -787,6 +787,22 @@ int mtbt_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_
 int mtbt_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
                   float weight_decay, int nesterov, int64_t step, const float* grad_scale, void* stream);
 
+/* Weight EMA (exponential moving average of the weights; the reference trainer has none -- this is the project's own definition).
+ * Per element, after the optimiser has produced the new p:
+ *     d   = (float)ema_decay        omd = (float)(1.0 - ema_decay)      host, in double, then rounded once
+ *     e   = e * d                                                         one rounding
+ *     e   = e + omd * p                                                   product rounded, then the sum rounded: no contraction
+ * which is torch's CPU `e.mul_(d); e.add_((1 - d) * p)` bit for bit.  mtbt_adamw_step_ema / mtbt_sgd_step_ema are the steps above with
+ * that update applied, in the same pass, to the p about to be stored: param and the moments come out exactly as from the plain entry
+ * points, and the EMA costs one 4-byte read and one 4-byte write per parameter and no launch.  mtbt_ema_update is the same update for
+ * values no optimiser steps (BatchNorm running statistics); ema and src 16-byte aligned, as mtbt_adamw_step(_ema) asks of its buffers.
+ * MTBT_EINVAL for a null ema / src, n < 0 or ema_decay outside [0, 1] (NaN included); n == 0 is MTBT_OK without a launch. */
+int mtbt_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr, float beta1,
+                        float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale, double ema_decay, void* stream);
+int mtbt_sgd_step_ema(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n, float lr, float momentum, float dampening,
+                      float weight_decay, int nesterov, int64_t step, const float* grad_scale, double ema_decay, void* stream);
+int mtbt_ema_update(float* ema, const float* src, int64_t n, double ema_decay, void* stream);
+
 /* Gradient clipping by global norm (Trainer(gradient_clip_val=10), running_main_v3.py:826 -> torch.nn.utils.clip_grad_norm_):
  * mtbt_sumsq adds the sum of squares of one flat bucket to *out (deterministic two-level reduction; workspace >=
  * mtbt_sumsq_workspace_bytes()); after an all-reduce-free sum over the buckets, mtbt_clip_coef writes

@@ -205,6 +205,9 @@ SYMBOLS = {
     "mtbt_dwconv_wgrad_bias": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 7 + [C.c_void_p, C.c_int64, C.c_void_p]),
     "mtbt_adamw_step": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_float] * 5 + [C.c_int64, C.c_void_p, C.c_void_p]),
     "mtbt_sgd_step": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_float] * 4 + [C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "mtbt_adamw_step_ema": (C.c_int, [C.c_void_p] * 5 + [C.c_int64] + [C.c_float] * 5 + [C.c_int64, C.c_void_p, C.c_double, C.c_void_p]),
+    "mtbt_sgd_step_ema": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_float] * 4 + [C.c_int, C.c_int64, C.c_void_p, C.c_double, C.c_void_p]),
+    "mtbt_ema_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p]),
     "mtbt_sumsq_workspace_bytes": (C.c_int64, []),
     "mtbt_sumsq": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "mtbt_clip_coef": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -12,7 +12,11 @@ file, or a file `torch.load(..., weights_only=True)` accepts -- with the checkpo
 highest-numbered `model.<N>.` block that owns the head's parameter names, as the reference takes the LAST Detect / Segment
 module of the layer list.
 
-`strip_lightning_prefix` maps a Lightning checkpoint's `state_dict` (`net.` prefix, `running_main_v3.py:181`) onto the model."""
+`strip_lightning_prefix` maps a Lightning checkpoint's `state_dict` (`net.` prefix, `running_main_v3.py:181`) onto the model.
+
+`save_train_state` / `load_train_state` write and read `trainstep.TrainStep.state_dict()` -- model, projector, optimiser moments, step
+counters, rate and (when kept) the averaged weights -- the native step's counterpart of the save / resume the reference trainer gets
+from Lightning's `ModelCheckpoint` (`running_main_v3.py:799-806`).  Its `"state_dict"` carries a Lightning checkpoint's names."""
 import re
 from typing import Dict, Optional, Union
 
@@ -115,3 +119,16 @@ def load_pretrained_heads(model, detect_ckpt_path: StateSource = None, segment_c
 def strip_lightning_prefix(state_dict: Dict[str, torch.Tensor], prefix: str = "net.") -> Dict[str, torch.Tensor]:
     """Lightning `.ckpt['state_dict']` -> model state_dict (drops the trainer's own entries such as `seg_proto_projector.*`)."""
     return {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+
+
+def save_train_state(path, ts) -> None:
+    """`ts.state_dict()` (a `trainstep.TrainStep`) to `path`: plain tensors, numbers and strings only."""
+    torch.save(ts.state_dict(), str(path))
+
+
+def load_train_state(path, ts) -> dict:
+    """Read a file written by `save_train_state` (`weights_only=True`: no pickled objects) into `ts`, in place; returns what was read.
+    `ts` must have been constructed like the step that wrote it: same model, optimiser and `ema` on / off (ValueError otherwise)."""
+    state = torch.load(str(path), map_location="cpu", weights_only=True)
+    ts.load_state_dict(state)
+    return state

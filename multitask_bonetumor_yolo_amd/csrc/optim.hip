@@ -10,11 +10,36 @@
 // contraction (-ffp-contract=off) so that the result follows torch's CPU rounding step by step (checked to 1e-6 relative over several
 // steps, not bit for bit: torch's CUDA / foreach paths round differently from its CPU path as well).  The bias corrections are
 // computed on the host in double like torch does (Python floats) and passed as fp32 scalars exactly where torch uses them.
+// The `_ema` entry points update an averaged copy of the weights from the `p` this pass is about to store: +4 B read, +4 B written.
 #include <cmath>
 
 #include "common.h"
 
 namespace {
+
+// Weight EMA riding on the optimiser pass (include/mtbt_hip.h, "Weight EMA"): e = e * d, then e = e + omd * p with the product and the sum
+// rounded separately (-ffp-contract=off) -- torch's CPU `e.mul_(d); e.add_((1 - d) * p)`.  d and omd are rounded once on the host.
+struct EmaP {
+  float* e;           // null: no EMA, the step kernels behave as they did before the field existed
+  float d, omd;       // (float)decay, (float)(1.0 - decay)
+};
+
+__device__ __forceinline__ void ema1(float& e, float p, const EmaP& a) {
+  e = e * a.d;
+  e = e + a.omd * p;
+}
+
+__device__ __forceinline__ void ema4(float4& e, const float4& p, const EmaP& a) {
+  ema1(e.x, p.x, a); ema1(e.y, p.y, a); ema1(e.z, p.z, a); ema1(e.w, p.w, a);
+}
+
+inline bool ema_decay_ok(double d) { return d >= 0.0 && d <= 1.0; }   // false for NaN
+
+inline EmaP make_ema(float* e, double decay) {
+  EmaP a;
+  a.e = e; a.d = (float)decay; a.omd = (float)(1.0 - decay);
+  return a;
+}
 
 struct AdamP {
   float* p; const float* g; float* m; float* v;
@@ -26,6 +51,7 @@ struct AdamP {
   float step_size;    // lr / (1 - beta1^t)
   float eps;
   const float* gscale; // optional device scalar multiplied into every gradient first (the clip coefficient of clip_grad_norm_)
+  EmaP ema;
 };
 
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamP& q) {
@@ -45,10 +71,16 @@ __global__ __launch_bounds__(256) void adamw_kernel(const AdamP q) {
     if (q.gscale) { g.x *= gs; g.y *= gs; g.z *= gs; g.w *= gs; }
     adam1(p.x, g.x, m.x, v.x, q); adam1(p.y, g.y, m.y, v.y, q); adam1(p.z, g.z, m.z, v.z, q); adam1(p.w, g.w, m.w, v.w, q);
     reinterpret_cast<float4*>(q.p)[i] = p; reinterpret_cast<float4*>(q.m)[i] = m; reinterpret_cast<float4*>(q.v)[i] = v;
+    if (q.ema.e) {
+      float4 e = reinterpret_cast<float4*>(q.ema.e)[i];
+      ema4(e, p, q.ema);
+      reinterpret_cast<float4*>(q.ema.e)[i] = e;
+    }
   }
   if (blockIdx.x == 0 && threadIdx.x < (q.n & 3)) {   // tail
     const long i = (n4 << 2) + threadIdx.x;
     adam1(q.p[i], q.gscale ? q.g[i] * gs : q.g[i], q.m[i], q.v[i], q);
+    if (q.ema.e) ema1(q.ema.e[i], q.p[i], q.ema);
   }
 }
 
@@ -58,6 +90,7 @@ struct SgdP {
   float* p; const float* g; float* buf; long n;
   float lr, momentum, dampening, wd; int nesterov, first;
   const float* gscale;
+  EmaP ema;
 };
 
 __device__ __forceinline__ void sgd1(float& p, float g, float* buf, const SgdP& q) {
@@ -76,6 +109,21 @@ __global__ __launch_bounds__(256) void sgd_kernel(const SgdP q) {
     float p = q.p[i];
     sgd1(p, q.gscale ? q.g[i] * gs : q.g[i], q.buf ? q.buf + i : nullptr, q);
     q.p[i] = p;
+    if (q.ema.e) ema1(q.ema.e[i], p, q.ema);
+  }
+}
+
+// the EMA of a buffer the optimiser does not step (BatchNorm running statistics): the same three lines as a pass of its own
+__global__ __launch_bounds__(256) void ema_kernel(const float* __restrict__ src, long n, const EmaP a) {
+  const long n4 = n >> 2;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    float4 e = reinterpret_cast<float4*>(a.e)[i];
+    ema4(e, reinterpret_cast<const float4*>(src)[i], a);
+    reinterpret_cast<float4*>(a.e)[i] = e;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail
+    const long i = (n4 << 2) + threadIdx.x;
+    ema1(a.e[i], src[i], a);
   }
 }
 
@@ -115,13 +163,12 @@ __global__ void clip_coef_kernel(const float* __restrict__ sumsq, float max_norm
   if (norm_out) *norm_out = norm;
 }
 
-}  // namespace
-
-extern "C" int mtbt_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                               float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale, void* stream) {
+// the step entry points with and without an EMA share one host path: `ema` null = the plain step
+int adamw_launch(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, double ema_decay, int64_t n, float lr, float beta1,
+                 float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale, void* stream) {
   if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || step < 1 || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return MTBT_EINVAL;
   if (n == 0) return MTBT_OK;
-  if (!aligned16(param) || !aligned16(grad) || !aligned16(exp_avg) || !aligned16(exp_avg_sq)) return MTBT_EALIGN;
+  if (!aligned16(param) || !aligned16(grad) || !aligned16(exp_avg) || !aligned16(exp_avg_sq) || !aligned16(ema)) return MTBT_EALIGN;
   AdamP q;
   q.p = param; q.g = grad; q.m = exp_avg; q.v = exp_avg_sq; q.n = n;
   // torch computes these in Python floats (double) and hands the results to fp32 tensor ops
@@ -134,6 +181,7 @@ extern "C" int mtbt_adamw_step(float* param, const float* grad, float* exp_avg, 
   q.step_size = (float)(l / (1.0 - std::pow(b1, (double)step)));
   q.eps = eps;
   q.gscale = grad_scale;
+  q.ema = make_ema(ema, ema_decay);
   long blocks = ((n >> 2) + 255) / 256;
   blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), q);
@@ -141,17 +189,55 @@ extern "C" int mtbt_adamw_step(float* param, const float* grad, float* exp_avg, 
   return MTBT_OK;
 }
 
-extern "C" int mtbt_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
-                             float weight_decay, int nesterov, int64_t step, const float* grad_scale, void* stream) {
+int sgd_launch(float* param, const float* grad, float* momentum_buf, float* ema, double ema_decay, int64_t n, float lr, float momentum,
+               float dampening, float weight_decay, int nesterov, int64_t step, const float* grad_scale, void* stream) {
   if (!param || !grad || n < 0 || step < 1 || (momentum != 0.f && !momentum_buf)) return MTBT_EINVAL;
   if (nesterov && (momentum <= 0.f || dampening != 0.f)) return MTBT_EINVAL;
   if (n == 0) return MTBT_OK;
   SgdP q;
   q.p = param; q.g = grad; q.buf = momentum_buf; q.n = n; q.lr = lr; q.momentum = momentum; q.dampening = dampening; q.wd = weight_decay;
   q.nesterov = nesterov; q.first = step == 1; q.gscale = grad_scale;
+  q.ema = make_ema(ema, ema_decay);
   long blocks = (n + 255) / 256;
   blocks = blocks > 4096 ? 4096 : blocks;
   hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), q);
+  MTBT_LAUNCH_CHECK();
+  return MTBT_OK;
+}
+
+}  // namespace
+
+extern "C" int mtbt_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                               float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale, void* stream) {
+  return adamw_launch(param, grad, exp_avg, exp_avg_sq, nullptr, 0.0, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream);
+}
+
+extern "C" int mtbt_adamw_step_ema(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, float lr, float beta1,
+                                   float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale, double ema_decay,
+                                   void* stream) {
+  if (!ema || !ema_decay_ok(ema_decay)) return MTBT_EINVAL;
+  return adamw_launch(param, grad, exp_avg, exp_avg_sq, ema, ema_decay, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream);
+}
+
+extern "C" int mtbt_sgd_step(float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
+                             float weight_decay, int nesterov, int64_t step, const float* grad_scale, void* stream) {
+  return sgd_launch(param, grad, momentum_buf, nullptr, 0.0, n, lr, momentum, dampening, weight_decay, nesterov, step, grad_scale, stream);
+}
+
+extern "C" int mtbt_sgd_step_ema(float* param, const float* grad, float* momentum_buf, float* ema, int64_t n, float lr, float momentum,
+                                 float dampening, float weight_decay, int nesterov, int64_t step, const float* grad_scale, double ema_decay,
+                                 void* stream) {
+  if (!ema || !ema_decay_ok(ema_decay)) return MTBT_EINVAL;
+  return sgd_launch(param, grad, momentum_buf, ema, ema_decay, n, lr, momentum, dampening, weight_decay, nesterov, step, grad_scale, stream);
+}
+
+extern "C" int mtbt_ema_update(float* ema, const float* src, int64_t n, double ema_decay, void* stream) {
+  if (!ema || !src || n < 0 || !ema_decay_ok(ema_decay)) return MTBT_EINVAL;
+  if (n == 0) return MTBT_OK;
+  if (!aligned16(ema) || !aligned16(src)) return MTBT_EALIGN;
+  long blocks = ((n >> 2) + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks);
+  hipLaunchKernelGGL(ema_kernel, dim3((unsigned)blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, (long)n, make_ema(ema, ema_decay));
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }
