@@ -520,7 +520,12 @@ int mtbt_bbox_iou_pairwise(const float* boxes1, int n, const float* boxes2, int 
  * image resized like cv2.resize(INTER_LINEAR) (OpenCV's 8-bit fixed-point path), mask like INTER_NEAREST, both placed
  * top-left; image padded with 114, mask with 0.  out_images [count][3][S][S] f32 RGB in [0,1]; out_masks
  * [count][1][S][S] f32 in {0,1} (NULL = skip; a NULL descriptor mask gives zeros); out_scales HOST [count] (NULL = skip):
- * the letterbox scale the caller applies to its YOLO-txt boxes (:200-203).  S % 4 == 0. */
+ * the letterbox scale the caller applies to its YOLO-txt boxes (:200-203).  S % 4 == 0.
+ * Order of the checks, the same in the three entry points of this pipeline: (1) MTBT_EINVAL with every item checked, so before any
+ * launch and before out_scales is written: NULL images / out_images, count < 0, img_size <= 0 or % 4, a descriptor with a NULL bgr, a
+ * height or width <= 0, row_stride < 3 * width, a mask with mask_row_stride < width, height * row_stride >= 2^31 - 1, or a resized side
+ * beyond 32768 (only an img_size beyond 32768 gives one); (2) then MTBT_EALIGN for outputs not 16-byte aligned; (3) then the first
+ * launch, one per <= 32 images.  count == 0 is MTBT_OK with nothing launched. */
 typedef struct {
   const uint8_t* bgr;
   const uint8_t* mask;
@@ -546,9 +551,10 @@ int mtbt_letterbox_batch(const mtbt_raw_image* images, int count, int img_size, 
  * each resized 8-bit channel value before the one correctly rounded /255; pad pixels are not remapped.  Outputs as
  * mtbt_letterbox_batch.  With the letterbox's new_w / new_h, zero offsets, orient 0 and no table the output equals
  * mtbt_letterbox_batch bit for bit.  Every source index is clamped to the source: no geometry addresses outside it.
- * MTBT_EINVAL before any launch: NULL images / geom / out_images, geom_stride != 8, img_size <= 0 or % 4, count < 0, new_w or new_h
- * outside [1, 32768], orient outside 0..7, a non-zero reserved field, a descriptor mtbt_letterbox_batch refuses.  MTBT_EALIGN for
- * outputs not 16-byte aligned. */
+ * Order of the checks as in mtbt_letterbox_batch: (1) MTBT_EINVAL with every image checked, so before any launch: NULL images / geom /
+ * out_images, geom_stride != 8, img_size <= 0 or % 4, count < 0, new_w or new_h outside [1, 32768], orient outside 0..7, a non-zero
+ * reserved field, a descriptor mtbt_letterbox_batch refuses; (2) then MTBT_EALIGN for outputs not 16-byte aligned (a call that is both
+ * invalid and misaligned is MTBT_EINVAL); (3) then the first launch.  count == 0 is MTBT_OK with nothing launched. */
 int mtbt_augment_batch(const mtbt_raw_image* images, int count, int img_size, const int32_t* geom, int geom_stride,
                        const uint8_t* lut, float* out_images, float* out_masks, void* stream);
 
@@ -564,9 +570,10 @@ int mtbt_augment_batch(const mtbt_raw_image* images, int count, int img_size, co
  * or cy at 0 or S) is legal; with the centre at (S, S) tile 0 is the whole canvas and the result is mtbt_augment_batch of tile 0, bit for
  * bit, so a batch that mixes mosaic and plain canvases is one call.  Descriptors may repeat.  One launch per <= 8 canvases (32 descriptors);
  * every output byte is written exactly once; every source index is clamped to its source.  Outputs as mtbt_letterbox_batch.
- * MTBT_EINVAL before any launch, every canvas checked first: NULL tiles / geom / centres / out_images, geom_stride != 8, count < 0,
- * img_size <= 0 or % 4, cx outside [0, S] or % 4, cy outside [0, S], any of a canvas's four rows or descriptors that mtbt_augment_batch
- * would refuse (also those of an empty tile).  MTBT_EALIGN, after those, for outputs not 16-byte aligned.  count == 0 is MTBT_OK. */
+ * Order of the checks as in mtbt_letterbox_batch: (1) MTBT_EINVAL with every canvas checked, so before any launch: NULL tiles / geom /
+ * centres / out_images, geom_stride != 8, count < 0, img_size <= 0 or % 4, cx outside [0, S] or % 4, cy outside [0, S], any of a canvas's
+ * four rows or descriptors that mtbt_augment_batch would refuse (also those of an empty tile); (2) then MTBT_EALIGN for outputs not
+ * 16-byte aligned; (3) then the first launch.  count == 0 is MTBT_OK with nothing launched. */
 int mtbt_mosaic_batch(const mtbt_raw_image* tiles /* HOST [4*count], canvas-major, repeats allowed */, int count, int img_size,
                       const int32_t* geom /* HOST [4*count][geom_stride], geom_stride == 8 */, int geom_stride,
                       const int32_t* centres /* HOST [count][2] = cx, cy */, const uint8_t* lut /* DEVICE [count][3][256] or NULL */,

@@ -20,14 +20,14 @@
 // float4 store (the output, 16 B per pixel, is the HBM traffic that bounds the kernel); the <= 12 source bytes per pixel
 // are gathered through L2.
 //
-// augment_kernel is the same work with the sampling place chosen by the caller (the reference has NO augmentation: this
-// geometry is the project's own definition, include/mtbt_hip.h mtbt_augment_batch).  R = the source resized to new_w x new_h
-// by the arithmetic above (never materialised); Q = R under one of the eight dihedral orientations; the canvas shows Q at
-// (off_x, off_y), pad elsewhere; an optional 256-entry table per channel remaps the resized byte before the /255.
-//
-// mosaic_kernel is augment_kernel's pixel with the source picked per canvas region (include/mtbt_hip.h mtbt_mosaic_batch): a centre
-// (cx, cy) cuts the canvas into four rectangles, each of which shows its own source under its own geometry row.  cx % 4 == 0, so the
-// four pixels of a thread share a rectangle; one blockIdx.y per (canvas, rectangle) keeps descriptor and placement scalar.
+// That pixel is written once, in quad_pixels, for a source under a placement (the reference has NO augmentation: the placement
+// is the project's own definition, include/mtbt_hip.h mtbt_augment_batch).  R = the source resized to new_w x new_h by the
+// arithmetic above (never materialised); Q = R under one of the eight dihedral orientations; the canvas shows Q at (off_x, off_y),
+// pad elsewhere; an optional 256-entry table per channel remaps the resized byte before the /255.  The three kernels only say
+// which (canvas, dy, dx0, source, placement, table) a thread has, then call quad_pixels and store_quad:
+//   letterbox_kernel  blockIdx.y = image = canvas; offsets 0, orient 0 and no table as compile-time constants (PLACED = false)
+//   augment_kernel    blockIdx.y = image = canvas; the caller's placement and table
+//   mosaic_kernel     blockIdx.y = canvas * 4 + tile, the source picked per canvas region (include/mtbt_hip.h mtbt_mosaic_batch)
 #include "common.h"
 
 namespace {
@@ -46,6 +46,7 @@ struct Placement { int off_x, off_y, orient, reserved; };   // of the oriented i
 struct Placements { Placement p[MAX_IMAGES]; };              // 2048 + 512 bytes of kernel arguments with Batch
 constexpr int MAX_CANVASES = MAX_IMAGES / 4;                 // mosaic canvases per launch: four descriptors each
 struct Centres { int cx[MAX_CANVASES], cy[MAX_CANVASES]; };
+struct Quad { float r[4], g[4], b[4], m[4]; };               // four adjacent canvas pixels: RGB in [0,1] and the mask
 
 __device__ __forceinline__ void linear_tap(int d, double scale, int size, int& s0, int& s1, int& c0, int& c1) {
   float f = (float)((d + 0.5) * scale - 0.5);
@@ -59,75 +60,21 @@ __device__ __forceinline__ void linear_tap(int d, double scale, int size, int& s
   c1 = __float2int_rn(f * 2048.f);
 }
 
-__global__ __launch_bounds__(256) void letterbox_kernel(const Batch b, int S, float* __restrict__ out_img, float* __restrict__ out_mask) {
-  const RawImage& im = b.im[blockIdx.y];
-  const int quads = S >> 2;
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= S * quads) return;
-  const int dy = q / quads, dx0 = (q - dy * quads) << 2;
-  float r[4], g[4], bl[4], m[4];
-  const float pad = __fdiv_rn(114.f, 255.f);
-  const bool row_in = dy < im.new_h;
-  int sy0 = 0, sy1 = 0, b0 = 0, b1 = 0, my = 0;
-  if (row_in) {
-    linear_tap(dy, im.scale_y, im.H0, sy0, sy1, b0, b1);
-    my = min((int)floor(dy * im.scale_y), im.H0 - 1);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int dx = dx0 + i;
-    r[i] = g[i] = bl[i] = pad;
-    m[i] = 0.f;
-    if (row_in && dx < im.new_w) {
-      int sx0, sx1, a0, a1;
-      linear_tap(dx, im.scale_x, im.W0, sx0, sx1, a0, a1);
-      const uint8_t* p0 = im.bgr + sy0 * im.row_stride;
-      const uint8_t* p1 = im.bgr + sy1 * im.row_stride;
-      int v[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int r0 = p0[sx0 * 3 + c] * a0 + p0[sx1 * 3 + c] * a1;
-        const int r1 = p1[sx0 * 3 + c] * a0 + p1[sx1 * 3 + c] * a1;
-        const int o = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-        v[c] = min(max(o, 0), 255);
-      }
-      bl[i] = __fdiv_rn((float)v[0], 255.f);
-      g[i] = __fdiv_rn((float)v[1], 255.f);
-      r[i] = __fdiv_rn((float)v[2], 255.f);
-      if (im.mask) {
-        const int mx = min((int)floor(dx * im.scale_x), im.W0 - 1);
-        m[i] = im.mask[my * im.mask_stride + mx] >= 128 ? 1.f : 0.f;   // v / 255 > 0.5  <=>  v >= 128
-      }
-    }
-  }
-  const long plane = (long)S * S;
-  float* o = out_img + (long)blockIdx.y * 3 * plane + (long)dy * S + dx0;
-  *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
-  *reinterpret_cast<float4*>(o + plane) = make_float4(g[0], g[1], g[2], g[3]);
-  *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(bl[0], bl[1], bl[2], bl[3]);
-  if (out_mask) *reinterpret_cast<float4*>(out_mask + (long)blockIdx.y * plane + (long)dy * S + dx0) = make_float4(m[0], m[1], m[2], m[3]);
-}
-
-// One thread = 4 horizontally adjacent canvas pixels, as above.  They lie on one row of Q, which is one row of R (a shared
-// vertical tap) or, transposed, one column of R (a shared horizontal tap); the other tap is per pixel.  Every source index
-// comes out of linear_tap / the clamped nearest index, so it lies in [0, size-1] whatever the geometry is.
-__global__ __launch_bounds__(256) void augment_kernel(const Batch b, const Placements pl, int S, const uint8_t* __restrict__ lut,
-                                                      float* __restrict__ out_img, float* __restrict__ out_mask) {
-  const RawImage& im = b.im[blockIdx.y];
-  const Placement& g = pl.p[blockIdx.y];
-  const int quads = S >> 2;
-  const int q = blockIdx.x * 256 + threadIdx.x;
-  if (q >= S * quads) return;
-  const int dy = q / quads, dx0 = (q - dy * quads) << 2;
-  const bool flip_x = g.orient & 1, flip_y = g.orient & 2, transposed = g.orient & 4;
+// The canvas pixels (dy, dx0 .. dx0+3) of source im under placement g and an optional table.  They lie on one row of Q, which is
+// one row of R (a shared vertical tap) or, transposed, one column of R (a shared horizontal tap); the other tap is per pixel.
+// Every source index comes out of linear_tap / the clamped nearest index, so it lies in [0, size-1] whatever the geometry is.
+// PLACED = false is the letterbox: g and table are not read, the orientation selects fold away at compile time.
+template <bool PLACED>
+__device__ __forceinline__ void quad_pixels(const RawImage& im, const Placement& g, const uint8_t* table, int dy, int dx0, Quad& out) {
+  const int off_x = PLACED ? g.off_x : 0, off_y = PLACED ? g.off_y : 0, orient = PLACED ? g.orient : 0;
+  if (!PLACED) table = nullptr;
+  const bool flip_x = orient & 1, flip_y = orient & 2, transposed = orient & 4;
   const int qw = transposed ? im.new_h : im.new_w, qh = transposed ? im.new_w : im.new_h;
   // the axis of R that runs along a row of Q (per pixel) and the one across it (shared)
   const double scale_p = transposed ? im.scale_y : im.scale_x, scale_s = transposed ? im.scale_x : im.scale_y;
   const int size_p = transposed ? im.H0 : im.W0, size_s = transposed ? im.W0 : im.H0;
-  const uint8_t* table = lut ? lut + (long)blockIdx.y * 768 : nullptr;
-  float r[4], gr[4], bl[4], m[4];
   const float pad = __fdiv_rn(114.f, 255.f);
-  const int qy = dy - g.off_y;
+  const int qy = dy - off_y;
   const bool row_in = qy >= 0 && qy < qh;
   int s0 = 0, s1 = 0, cs0 = 0, cs1 = 0, ms = 0;
   if (row_in) {
@@ -137,9 +84,9 @@ __global__ __launch_bounds__(256) void augment_kernel(const Batch b, const Place
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int qx = dx0 + i - g.off_x;
-    r[i] = gr[i] = bl[i] = pad;
-    m[i] = 0.f;
+    const int qx = dx0 + i - off_x;
+    out.r[i] = out.g[i] = out.b[i] = pad;
+    out.m[i] = 0.f;
     if (row_in && qx >= 0 && qx < qw) {
       const int v = flip_x ? qw - 1 - qx : qx;
       int p0, p1, cp0, cp1;
@@ -157,28 +104,52 @@ __global__ __launch_bounds__(256) void augment_kernel(const Batch b, const Place
         o[c] = min(max(t, 0), 255);
         if (table) o[c] = table[c * 256 + o[c]];
       }
-      bl[i] = __fdiv_rn((float)o[0], 255.f);
-      gr[i] = __fdiv_rn((float)o[1], 255.f);
-      r[i] = __fdiv_rn((float)o[2], 255.f);
+      out.b[i] = __fdiv_rn((float)o[0], 255.f);
+      out.g[i] = __fdiv_rn((float)o[1], 255.f);
+      out.r[i] = __fdiv_rn((float)o[2], 255.f);
       if (im.mask) {
         const int mp = max(min((int)floor(v * scale_p), size_p - 1), 0);
         const int mx = transposed ? ms : mp, my = transposed ? mp : ms;
-        m[i] = im.mask[my * im.mask_stride + mx] >= 128 ? 1.f : 0.f;
+        out.m[i] = im.mask[my * im.mask_stride + mx] >= 128 ? 1.f : 0.f;   // v / 255 > 0.5  <=>  v >= 128
       }
     }
   }
+}
+
+__device__ __forceinline__ void store_quad(const Quad& q, int S, int canvas, int dy, int dx0, float* __restrict__ out_img, float* __restrict__ out_mask) {
   const long plane = (long)S * S;
-  float* o = out_img + (long)blockIdx.y * 3 * plane + (long)dy * S + dx0;
-  *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
-  *reinterpret_cast<float4*>(o + plane) = make_float4(gr[0], gr[1], gr[2], gr[3]);
-  *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(bl[0], bl[1], bl[2], bl[3]);
-  if (out_mask) *reinterpret_cast<float4*>(out_mask + (long)blockIdx.y * plane + (long)dy * S + dx0) = make_float4(m[0], m[1], m[2], m[3]);
+  float* o = out_img + (long)canvas * 3 * plane + (long)dy * S + dx0;
+  *reinterpret_cast<float4*>(o) = make_float4(q.r[0], q.r[1], q.r[2], q.r[3]);
+  *reinterpret_cast<float4*>(o + plane) = make_float4(q.g[0], q.g[1], q.g[2], q.g[3]);
+  *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(q.b[0], q.b[1], q.b[2], q.b[3]);
+  if (out_mask) *reinterpret_cast<float4*>(out_mask + (long)canvas * plane + (long)dy * S + dx0) = make_float4(q.m[0], q.m[1], q.m[2], q.m[3]);
+}
+
+__global__ __launch_bounds__(256) void letterbox_kernel(const Batch b, int S, float* __restrict__ out_img, float* __restrict__ out_mask) {
+  const int quads = S >> 2;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= S * quads) return;
+  const int dy = q / quads, dx0 = (q - dy * quads) << 2;
+  Quad px;
+  quad_pixels<false>(b.im[blockIdx.y], Placement{}, nullptr, dy, dx0, px);
+  store_quad(px, S, blockIdx.y, dy, dx0, out_img, out_mask);
+}
+
+__global__ __launch_bounds__(256) void augment_kernel(const Batch b, const Placements pl, int S, const uint8_t* __restrict__ lut,
+                                                      float* __restrict__ out_img, float* __restrict__ out_mask) {
+  const int quads = S >> 2;
+  const int q = blockIdx.x * 256 + threadIdx.x;
+  if (q >= S * quads) return;
+  const int dy = q / quads, dx0 = (q - dy * quads) << 2;
+  Quad px;
+  quad_pixels<true>(b.im[blockIdx.y], pl.p[blockIdx.y], lut ? lut + (long)blockIdx.y * 768 : nullptr, dy, dx0, px);
+  store_quad(px, S, blockIdx.y, dy, dx0, out_img, out_mask);
 }
 
 // blockIdx.y = canvas * 4 + tile; blockIdx.x runs over the quads of that tile's rectangle [x0, x1) x [y0, y1) of the canvas (x0, x1 are
-// multiples of 4) and workgroups beyond it leave at once.  The four rectangles partition the canvas, so every output byte is written by
-// exactly one thread.  Inside the rectangle the pixel is augment_kernel's for descriptor / placement blockIdx.y (offsets in canvas
-// coordinates); the table is the canvas's.  Source indices as there: out of linear_tap / the clamped nearest index only.
+// multiples of 4, so the four pixels of a thread share a rectangle) and workgroups beyond it leave at once.  The four rectangles partition
+// the canvas, so every output byte is written by exactly one thread.  One blockIdx.y per (canvas, rectangle) keeps descriptor and placement
+// scalar; the offsets are in canvas coordinates and the table is the canvas's.
 __global__ __launch_bounds__(256) void mosaic_kernel(const Batch b, const Placements pl, const Centres ce, int S, const uint8_t* __restrict__ lut,
                                                      float* __restrict__ out_img, float* __restrict__ out_mask) {
   const int canvas = blockIdx.y >> 2, tile = blockIdx.y & 3;
@@ -189,118 +160,70 @@ __global__ __launch_bounds__(256) void mosaic_kernel(const Batch b, const Placem
   if (q >= (y1 - y0) * quads) return;   // also the empty rectangle
   const int ty = q / quads;
   const int dy = y0 + ty, dx0 = x0 + ((q - ty * quads) << 2);
-  const RawImage& im = b.im[blockIdx.y];
-  const Placement& g = pl.p[blockIdx.y];
-  const bool flip_x = g.orient & 1, flip_y = g.orient & 2, transposed = g.orient & 4;
-  const int qw = transposed ? im.new_h : im.new_w, qh = transposed ? im.new_w : im.new_h;
-  const double scale_p = transposed ? im.scale_y : im.scale_x, scale_s = transposed ? im.scale_x : im.scale_y;
-  const int size_p = transposed ? im.H0 : im.W0, size_s = transposed ? im.W0 : im.H0;
-  const uint8_t* table = lut ? lut + (long)canvas * 768 : nullptr;
-  float r[4], gr[4], bl[4], m[4];
-  const float pad = __fdiv_rn(114.f, 255.f);
-  const int qy = dy - g.off_y;
-  const bool row_in = qy >= 0 && qy < qh;
-  int s0 = 0, s1 = 0, cs0 = 0, cs1 = 0, ms = 0;
-  if (row_in) {
-    const int u = flip_y ? qh - 1 - qy : qy;
-    linear_tap(u, scale_s, size_s, s0, s1, cs0, cs1);
-    ms = max(min((int)floor(u * scale_s), size_s - 1), 0);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int qx = dx0 + i - g.off_x;
-    r[i] = gr[i] = bl[i] = pad;
-    m[i] = 0.f;
-    if (row_in && qx >= 0 && qx < qw) {
-      const int v = flip_x ? qw - 1 - qx : qx;
-      int p0, p1, cp0, cp1;
-      linear_tap(v, scale_p, size_p, p0, p1, cp0, cp1);
-      const int sx0 = transposed ? s0 : p0, sx1 = transposed ? s1 : p1, a0 = transposed ? cs0 : cp0, a1 = transposed ? cs1 : cp1;
-      const int sy0 = transposed ? p0 : s0, sy1 = transposed ? p1 : s1, b0 = transposed ? cp0 : cs0, b1 = transposed ? cp1 : cs1;
-      const uint8_t* row0 = im.bgr + sy0 * im.row_stride;
-      const uint8_t* row1 = im.bgr + sy1 * im.row_stride;
-      int o[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int r0 = row0[sx0 * 3 + c] * a0 + row0[sx1 * 3 + c] * a1;
-        const int r1 = row1[sx0 * 3 + c] * a0 + row1[sx1 * 3 + c] * a1;
-        const int t = (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2;
-        o[c] = min(max(t, 0), 255);
-        if (table) o[c] = table[c * 256 + o[c]];
-      }
-      bl[i] = __fdiv_rn((float)o[0], 255.f);
-      gr[i] = __fdiv_rn((float)o[1], 255.f);
-      r[i] = __fdiv_rn((float)o[2], 255.f);
-      if (im.mask) {
-        const int mp = max(min((int)floor(v * scale_p), size_p - 1), 0);
-        const int mx = transposed ? ms : mp, my = transposed ? mp : ms;
-        m[i] = im.mask[my * im.mask_stride + mx] >= 128 ? 1.f : 0.f;
-      }
-    }
-  }
-  const long plane = (long)S * S;
-  float* o = out_img + (long)canvas * 3 * plane + (long)dy * S + dx0;
-  *reinterpret_cast<float4*>(o) = make_float4(r[0], r[1], r[2], r[3]);
-  *reinterpret_cast<float4*>(o + plane) = make_float4(gr[0], gr[1], gr[2], gr[3]);
-  *reinterpret_cast<float4*>(o + 2 * plane) = make_float4(bl[0], bl[1], bl[2], bl[3]);
-  if (out_mask) *reinterpret_cast<float4*>(out_mask + (long)canvas * plane + (long)dy * S + dx0) = make_float4(m[0], m[1], m[2], m[3]);
+  Quad px;
+  quad_pixels<true>(b.im[blockIdx.y], pl.p[blockIdx.y], lut ? lut + (long)canvas * 768 : nullptr, dy, dx0, px);
+  store_quad(px, S, canvas, dy, dx0, out_img, out_mask);
 }
 
-// the descriptor checks all entry points make; fills everything but the resized size
-bool source_of(const mtbt_raw_image& s, RawImage& d) {
+// ---- host: every entry point checks all of its items, then the alignment, then launches ----------------------------------------
+// One source and its geometry row (new_w, new_h, off_x, off_y, orient, 0, 0, 0) -> what the kernel reads; false = MTBT_EINVAL.
+bool describe(const mtbt_raw_image& s, const int32_t* g, int img_size, RawImage& d, Placement& p) {
   if (!s.bgr || s.height <= 0 || s.width <= 0 || s.row_stride < (int64_t)s.width * 3 || (s.mask && s.mask_row_stride < s.width) ||
       (long)s.height * s.row_stride >= 0x7fffffffL)
     return false;
+  if (g[0] < 1 || g[0] > 32768 || g[1] < 1 || g[1] > 32768 || g[4] < 0 || g[4] > 7 || g[5] || g[6] || g[7]) return false;
   d.bgr = s.bgr; d.mask = s.mask; d.row_stride = s.row_stride; d.mask_stride = s.mask_row_stride;
-  d.H0 = s.height; d.W0 = s.width;
-  return true;
-}
-
-void resized_to(RawImage& d, int new_w, int new_h) {
-  d.new_w = new_w; d.new_h = new_h;
-  d.scale_x = 1.0 / ((double)new_w / (double)d.W0);
-  d.scale_y = 1.0 / ((double)new_h / (double)d.H0);
-}
-
-// the geometry-row checks of mtbt_augment_batch and mtbt_mosaic_batch
-bool geom_ok(const int32_t* g) {
-  return g[0] >= 1 && g[0] <= 32768 && g[1] >= 1 && g[1] <= 32768 && g[4] >= 0 && g[4] <= 7 && !g[5] && !g[6] && !g[7];
-}
-
-// an offset beyond [-q, S] shows nothing of Q, exactly like the bound itself: clamped so that the kernel's int arithmetic cannot wrap
-Placement placed(const int32_t* g, int img_size) {
+  d.H0 = s.height; d.W0 = s.width; d.new_w = g[0]; d.new_h = g[1];
+  d.scale_x = 1.0 / ((double)d.new_w / (double)d.W0);
+  d.scale_y = 1.0 / ((double)d.new_h / (double)d.H0);
+  // an offset beyond [-q, S] shows nothing of Q, exactly like the bound itself: clamped so that the kernel's int arithmetic cannot wrap
   const int qw = (g[4] & 4) ? g[1] : g[0], qh = (g[4] & 4) ? g[0] : g[1];
-  Placement p;
   p.off_x = g[2] < -qw ? -qw : (g[2] > img_size ? img_size : g[2]);
   p.off_y = g[3] < -qh ? -qh : (g[3] > img_size ? img_size : g[3]);
   p.orient = g[4];
   p.reserved = 0;
-  return p;
+  return true;
 }
+
+// the row of the plain letterbox, dataset_btxrdv2.py:114-117 in the same double arithmetic as Python's floats; returns its scale
+// (a descriptor without a positive size gets scale 0: describe refuses it, and no out-of-range double is converted to int)
+double letterbox_row(const mtbt_raw_image& s, int img_size, int32_t* g) {
+  const double scale = s.height > 0 && s.width > 0 ? (double)img_size / (double)(s.height > s.width ? s.height : s.width) : 0.0;
+  const int nw = (int)((double)s.width * scale), nh = (int)((double)s.height * scale);
+  g[0] = nw < 1 ? 1 : nw; g[1] = nh < 1 ? 1 : nh;
+  g[2] = g[3] = g[4] = g[5] = g[6] = g[7] = 0;
+  return scale;
+}
+
+bool call_ok(const void* items, const void* out_images, int count, int img_size) {
+  return items && out_images && count >= 0 && img_size > 0 && img_size % 4 == 0;
+}
+bool outputs_aligned(const float* out_images, const float* out_masks) { return aligned16(out_images) && (!out_masks || aligned16(out_masks)); }
+unsigned blocks_of(long quads) { return (unsigned)((quads + 255) / 256); }
 
 }  // namespace
 
 extern "C" int mtbt_letterbox_batch(const mtbt_raw_image* images, int count, int img_size, float* out_images, float* out_masks,
                                     double* out_scales, void* stream) {
-  if (!images || count < 0 || img_size <= 0 || img_size % 4 || !out_images) return MTBT_EINVAL;
-  if (!aligned16(out_images) || (out_masks && !aligned16(out_masks))) return MTBT_EALIGN;
+  if (!call_ok(images, out_images, count, img_size)) return MTBT_EINVAL;
+  RawImage probe;
+  Placement unused;
+  int32_t row[8];
+  for (int i = 0; i < count; ++i) {   // every image is checked before the first launch
+    letterbox_row(images[i], img_size, row);
+    if (!describe(images[i], row, img_size, probe, unused)) return MTBT_EINVAL;
+  }
+  if (!outputs_aligned(out_images, out_masks)) return MTBT_EALIGN;
   const long plane = (long)img_size * img_size;
   for (int first = 0; first < count; first += MAX_IMAGES) {
     const int nb = count - first < MAX_IMAGES ? count - first : MAX_IMAGES;
     Batch b;
     for (int i = 0; i < nb; ++i) {
-      const mtbt_raw_image& s = images[first + i];
-      RawImage& d = b.im[i];
-      if (!source_of(s, d)) return MTBT_EINVAL;
-      // dataset_btxrdv2.py:114-117 in the same double arithmetic as Python's floats
-      const double scale = (double)img_size / (double)(s.height > s.width ? s.height : s.width);
-      const int nw = (int)((double)s.width * scale), nh = (int)((double)s.height * scale);
-      resized_to(d, nw < 1 ? 1 : nw, nh < 1 ? 1 : nh);
-      if (d.new_w > img_size || d.new_h > img_size) return MTBT_EINVAL;   // cannot happen for scale = S / max(H0, W0)
+      const double scale = letterbox_row(images[first + i], img_size, row);
+      describe(images[first + i], row, img_size, b.im[i], unused);
       if (out_scales) out_scales[first + i] = scale;
     }
-    const unsigned gx = (unsigned)((plane / 4 + 255) / 256);
-    hipLaunchKernelGGL(letterbox_kernel, dim3(gx, (unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b, img_size,
+    hipLaunchKernelGGL(letterbox_kernel, dim3(blocks_of(plane / 4), (unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b, img_size,
                        out_images + (long)first * 3 * plane, out_masks ? out_masks + (long)first * plane : nullptr);
     MTBT_LAUNCH_CHECK();
   }
@@ -309,28 +232,19 @@ extern "C" int mtbt_letterbox_batch(const mtbt_raw_image* images, int count, int
 
 extern "C" int mtbt_augment_batch(const mtbt_raw_image* images, int count, int img_size, const int32_t* geom, int geom_stride,
                                   const uint8_t* lut, float* out_images, float* out_masks, void* stream) {
-  if (!images || !geom || !out_images || count < 0 || img_size <= 0 || img_size % 4 || geom_stride != 8) return MTBT_EINVAL;
-  if (!aligned16(out_images) || (out_masks && !aligned16(out_masks))) return MTBT_EALIGN;
+  if (!call_ok(images, out_images, count, img_size) || !geom || geom_stride != 8) return MTBT_EINVAL;
   RawImage probe;
-  for (int i = 0; i < count; ++i) {   // every image is checked before the first launch
-    const int32_t* g = geom + (long)i * geom_stride;
-    if (!source_of(images[i], probe)) return MTBT_EINVAL;
-    if (!geom_ok(g)) return MTBT_EINVAL;
-  }
+  Placement unused;
+  for (int i = 0; i < count; ++i)   // every image is checked before the first launch
+    if (!describe(images[i], geom + 8L * i, img_size, probe, unused)) return MTBT_EINVAL;
+  if (!outputs_aligned(out_images, out_masks)) return MTBT_EALIGN;
   const long plane = (long)img_size * img_size;
   for (int first = 0; first < count; first += MAX_IMAGES) {
     const int nb = count - first < MAX_IMAGES ? count - first : MAX_IMAGES;
     Batch b;
     Placements pl;
-    for (int i = 0; i < nb; ++i) {
-      const int32_t* g = geom + (long)(first + i) * geom_stride;
-      RawImage& d = b.im[i];
-      source_of(images[first + i], d);
-      resized_to(d, g[0], g[1]);
-      pl.p[i] = placed(g, img_size);
-    }
-    const unsigned gx = (unsigned)((plane / 4 + 255) / 256);
-    hipLaunchKernelGGL(augment_kernel, dim3(gx, (unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b, pl, img_size,
+    for (int i = 0; i < nb; ++i) describe(images[first + i], geom + 8L * (first + i), img_size, b.im[i], pl.p[i]);
+    hipLaunchKernelGGL(augment_kernel, dim3(blocks_of(plane / 4), (unsigned)nb), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b, pl, img_size,
                        lut ? lut + (long)first * 768 : nullptr, out_images + (long)first * 3 * plane,
                        out_masks ? out_masks + (long)first * plane : nullptr);
     MTBT_LAUNCH_CHECK();
@@ -340,15 +254,16 @@ extern "C" int mtbt_augment_batch(const mtbt_raw_image* images, int count, int i
 
 extern "C" int mtbt_mosaic_batch(const mtbt_raw_image* tiles, int count, int img_size, const int32_t* geom, int geom_stride,
                                  const int32_t* centres, const uint8_t* lut, float* out_images, float* out_masks, void* stream) {
-  if (!tiles || !geom || !centres || !out_images || count < 0 || img_size <= 0 || img_size % 4 || geom_stride != 8) return MTBT_EINVAL;
+  if (!call_ok(tiles, out_images, count, img_size) || !geom || !centres || geom_stride != 8) return MTBT_EINVAL;
   RawImage probe;
+  Placement unused;
   for (int i = 0; i < count; ++i) {   // every canvas is checked before the first launch, empty tiles included
     const int cx = centres[2 * i], cy = centres[2 * i + 1];
     if (cx < 0 || cx > img_size || cx % 4 || cy < 0 || cy > img_size) return MTBT_EINVAL;
-    for (int t = 0; t < 4; ++t)
-      if (!source_of(tiles[4L * i + t], probe) || !geom_ok(geom + (4L * i + t) * geom_stride)) return MTBT_EINVAL;
+    for (long k = 4L * i; k < 4L * i + 4; ++k)
+      if (!describe(tiles[k], geom + 8 * k, img_size, probe, unused)) return MTBT_EINVAL;
   }
-  if (!aligned16(out_images) || (out_masks && !aligned16(out_masks))) return MTBT_EALIGN;
+  if (!outputs_aligned(out_images, out_masks)) return MTBT_EALIGN;
   const long plane = (long)img_size * img_size;
   for (int first = 0; first < count; first += MAX_CANVASES) {
     const int nb = count - first < MAX_CANVASES ? count - first : MAX_CANVASES;
@@ -360,16 +275,13 @@ extern "C" int mtbt_mosaic_batch(const mtbt_raw_image* tiles, int count, int img
       const int cx = ce.cx[i] = centres[2 * (first + i)], cy = ce.cy[i] = centres[2 * (first + i) + 1];
       for (int t = 0; t < 4; ++t) {
         const long k = 4L * (first + i) + t;
-        RawImage& d = b.im[4 * i + t];
-        source_of(tiles[k], d);
-        resized_to(d, geom[k * geom_stride], geom[k * geom_stride + 1]);
-        pl.p[4 * i + t] = placed(geom + k * geom_stride, img_size);
+        describe(tiles[k], geom + 8 * k, img_size, b.im[4 * i + t], pl.p[4 * i + t]);
         const long quads = (long)(((t & 1) ? img_size - cx : cx) >> 2) * ((t & 2) ? img_size - cy : cy);
         if (quads > most) most = quads;
       }
     }
-    hipLaunchKernelGGL(mosaic_kernel, dim3((unsigned)((most + 255) / 256), (unsigned)(4 * nb)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b,
-                       pl, ce, img_size, lut ? lut + (long)first * 768 : nullptr, out_images + (long)first * 3 * plane,
+    hipLaunchKernelGGL(mosaic_kernel, dim3(blocks_of(most), (unsigned)(4 * nb)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), b, pl, ce, img_size,
+                       lut ? lut + (long)first * 768 : nullptr, out_images + (long)first * 3 * plane,
                        out_masks ? out_masks + (long)first * plane : nullptr);
     MTBT_LAUNCH_CHECK();
   }

@@ -54,6 +54,49 @@ def _descriptors(images, masks, who: str):
     return descs, keep, images[0].device
 
 
+def _int_array(a, shape, who: str, what: str) -> np.ndarray:
+    """An integer array or tensor of exactly `shape` (None = any length) whose values fit int32 -> contiguous int32 numpy."""
+    a = np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a)
+    if a.dtype.kind not in "iu" or a.ndim != len(shape) or any(n is not None and n != m for n, m in zip(shape, a.shape)):
+        raise ValueError(f"{who}: {what} must be an integer array of shape [{', '.join('B' if n is None else str(n) for n in shape)}]")
+    if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+        raise ValueError(f"{who}: {what} values must fit int32")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _table(lut, B: int, dev, keep, who: str):
+    """The optional CUDA uint8 [B, 3, 256] table -> its device address or None; the tensor joins `keep`."""
+    if lut is None:
+        return None
+    if not isinstance(lut, torch.Tensor) or not lut.is_cuda or lut.dtype != torch.uint8 or tuple(lut.shape) != (B, 3, 256) or lut.device != dev:
+        raise ValueError(f"{who}: lut must be a CUDA uint8 [{B}, 3, 256] tensor on the images' device")
+    keep.append(lut.contiguous())
+    return keep[-1].data_ptr()
+
+
+def _run(B: int, img_size: int, dev, keep, launch, name: str):
+    """Allocate (imgs [B,3,S,S], masks [B,1,S,S]), call launch(image address, mask address, stream) -> status of entry point `name`."""
+    out = torch.empty(B, 3, img_size, img_size, device=dev, dtype=torch.float32)
+    out_m = torch.empty(B, 1, img_size, img_size, device=dev, dtype=torch.float32)
+    stream = torch.cuda.current_stream(dev)
+    L.check(launch(out.data_ptr(), out_m.data_ptr(), C.c_void_p(stream.cuda_stream)), name)
+    for t in keep:   # the launch is asynchronous: keep the sources alive until the stream has consumed them
+        t.record_stream(stream)
+    return out, out_m
+
+
+def _split(ranges: dict, who: str, geo_keys):
+    """The keyword arguments of `*_samples` -> those of the geometry draw, `sample_photometric` and the label move; others are an error."""
+    parts = [{k: ranges.pop(k) for k in keys if k in ranges}
+             for keys in (geo_keys, ("brightness", "contrast", "gamma"), ("min_px", "min_area_ratio", "max_aspect"))]
+    if ranges:
+        raise TypeError(f"{who}: unknown arguments {sorted(ranges)}")
+    return parts
+
+
+_INT32_P = C.POINTER(C.c_int32)
+
+
 def letterbox_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]] = None, img_size: int = 640):
     """images: decoded BGR uint8 [H0, W0, 3] CUDA tensors (any sizes); masks: uint8 [H0, W0] CUDA tensors or None.
     Returns (imgs [B,3,S,S] f32 RGB in [0,1], masks [B,1,S,S] f32 {0,1}, scales list[float]) -- `img_t`, `mask_t` and
@@ -61,13 +104,8 @@ def letterbox_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Opt
     lib = L.load()
     descs, keep, dev = _descriptors(images, masks, "letterbox_batch")
     B = len(images)
-    out = torch.empty(B, 3, img_size, img_size, device=dev, dtype=torch.float32)
-    out_m = torch.empty(B, 1, img_size, img_size, device=dev, dtype=torch.float32)
     scales = (C.c_double * B)()
-    L.check(lib.mtbt_letterbox_batch(descs, B, img_size, out.data_ptr(), out_m.data_ptr(), scales,
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_letterbox_batch")
-    for t in keep:   # the launch is asynchronous: keep the sources alive until the stream has consumed them
-        t.record_stream(torch.cuda.current_stream(dev))
+    out, out_m = _run(B, img_size, dev, keep, lambda x, m, st: lib.mtbt_letterbox_batch(descs, B, img_size, x, m, scales, st), "mtbt_letterbox_batch")
     return out, out_m, [float(s) for s in scales]
 
 
@@ -120,25 +158,10 @@ def augment_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optio
     lib = L.load()
     descs, keep, dev = _descriptors(images, masks, "augment_batch")
     B = len(images)
-    g = np.asarray(geom.cpu() if isinstance(geom, torch.Tensor) else geom)
-    if g.dtype.kind not in "iu" or g.shape != (B, GEOM_FIELDS):
-        raise ValueError(f"augment_batch: geom must be an integer array of shape [{B}, {GEOM_FIELDS}]")
-    if g.size and (g.min() < -2 ** 31 or g.max() >= 2 ** 31):
-        raise ValueError("augment_batch: geom values must fit int32")
-    g = np.ascontiguousarray(g, dtype=np.int32)
-    if lut is not None:
-        if not isinstance(lut, torch.Tensor) or not lut.is_cuda or lut.dtype != torch.uint8 or tuple(lut.shape) != (B, 3, 256) or lut.device != dev:
-            raise ValueError(f"augment_batch: lut must be a CUDA uint8 [{B}, 3, 256] tensor on the images' device")
-        lut = lut.contiguous()
-        keep.append(lut)
-    out = torch.empty(B, 3, img_size, img_size, device=dev, dtype=torch.float32)
-    out_m = torch.empty(B, 1, img_size, img_size, device=dev, dtype=torch.float32)
-    L.check(lib.mtbt_augment_batch(descs, B, img_size, g.ctypes.data_as(C.POINTER(C.c_int32)), GEOM_FIELDS,
-                                   None if lut is None else lut.data_ptr(), out.data_ptr(), out_m.data_ptr(),
-                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_augment_batch")
-    for t in keep:   # the launch is asynchronous: keep the sources alive until the stream has consumed them
-        t.record_stream(torch.cuda.current_stream(dev))
-    return out, out_m
+    g = _int_array(geom, (B, GEOM_FIELDS), "augment_batch", "geom")
+    table = _table(lut, B, dev, keep, "augment_batch")
+    return _run(B, img_size, dev, keep, lambda x, m, st: lib.mtbt_augment_batch(descs, B, img_size, g.ctypes.data_as(_INT32_P), GEOM_FIELDS, table, x, m, st),
+                "mtbt_augment_batch")
 
 
 def letterbox_geometry(sizes: Sequence[Sequence[int]], img_size: int) -> np.ndarray:
@@ -244,11 +267,7 @@ def augment_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Opt
     """Draw geometry and intensity, run `augment_batch`, move the labels: (imgs [B,3,S,S], masks [B,1,S,S], gt_rows [M,6] on the
     device, batch index in column 0) -- what `TrainStep.step` takes.  `ranges` are the keyword arguments of `sample_geometry`,
     `sample_photometric` and `augment_yolo_labels`; anything else is an error."""
-    geo = {k: ranges.pop(k) for k in ("scale", "aspect", "fliplr", "flipud", "transpose", "place") if k in ranges}
-    pho = {k: ranges.pop(k) for k in ("brightness", "contrast", "gamma") if k in ranges}
-    lab = {k: ranges.pop(k) for k in ("min_px", "min_area_ratio", "max_aspect") if k in ranges}
-    if ranges:
-        raise TypeError(f"augment_samples: unknown arguments {sorted(ranges)}")
+    geo, pho, lab = _split(ranges, "augment_samples", ("scale", "aspect", "fliplr", "flipud", "transpose", "place"))
     if len(rows_per_image) != len(images):
         raise ValueError("augment_samples: one list of label rows per image")
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
@@ -275,39 +294,19 @@ def mosaic_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Option
     Returns (imgs [B,3,S,S] f32 RGB in [0,1], masks [B,1,S,S] f32 {0,1}); one launch per <= 8 canvases, no CPU path."""
     lib = L.load()
     descs, keep, dev = _descriptors(images, masks, "mosaic_batch")
-    idx = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
-    if idx.dtype.kind not in "iu" or idx.ndim != 2 or idx.shape[1] != 4:
-        raise ValueError("mosaic_batch: index must be an integer array of shape [B, 4]")
+    idx = _int_array(index, (None, 4), "mosaic_batch", "index")
     B = idx.shape[0]
     if B == 0:
         raise ValueError("mosaic_batch: empty batch")
     if idx.min() < 0 or idx.max() >= len(images):
         raise ValueError(f"mosaic_batch: index values must lie in [0, {len(images)})")
-    g = np.asarray(geom.cpu() if isinstance(geom, torch.Tensor) else geom)
-    if g.dtype.kind not in "iu" or g.shape != (B, 4, GEOM_FIELDS):
-        raise ValueError(f"mosaic_batch: geom must be an integer array of shape [{B}, 4, {GEOM_FIELDS}]")
-    c = np.asarray(centres.cpu() if isinstance(centres, torch.Tensor) else centres)
-    if c.dtype.kind not in "iu" or c.shape != (B, 2):
-        raise ValueError(f"mosaic_batch: centres must be an integer array of shape [{B}, 2]")
-    for a in (g, c):
-        if a.min() < -2 ** 31 or a.max() >= 2 ** 31:
-            raise ValueError("mosaic_batch: geom and centres values must fit int32")
-    g, c = np.ascontiguousarray(g, dtype=np.int32), np.ascontiguousarray(c, dtype=np.int32)
-    if lut is not None:
-        if not isinstance(lut, torch.Tensor) or not lut.is_cuda or lut.dtype != torch.uint8 or tuple(lut.shape) != (B, 3, 256) or lut.device != dev:
-            raise ValueError(f"mosaic_batch: lut must be a CUDA uint8 [{B}, 3, 256] tensor on the images' device")
-        lut = lut.contiguous()
-        keep.append(lut)
+    g = _int_array(geom, (B, 4, GEOM_FIELDS), "mosaic_batch", "geom")
+    c = _int_array(centres, (B, 2), "mosaic_batch", "centres")
+    table = _table(lut, B, dev, keep, "mosaic_batch")
     # the four descriptors of every canvas, gathered in one step (the library reads them before it returns)
     tiles = np.ascontiguousarray(np.frombuffer(descs, dtype=np.uint8).reshape(len(images), C.sizeof(L.RawImage))[idx.reshape(-1)])
-    out = torch.empty(B, 3, img_size, img_size, device=dev, dtype=torch.float32)
-    out_m = torch.empty(B, 1, img_size, img_size, device=dev, dtype=torch.float32)
-    L.check(lib.mtbt_mosaic_batch(tiles.ctypes.data_as(C.POINTER(L.RawImage)), B, img_size, g.ctypes.data_as(C.POINTER(C.c_int32)), GEOM_FIELDS, c.ctypes.data_as(C.POINTER(C.c_int32)),
-                                  None if lut is None else lut.data_ptr(), out.data_ptr(), out_m.data_ptr(),
-                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_mosaic_batch")
-    for t in keep:   # the launch is asynchronous: keep the sources alive until the stream has consumed them
-        t.record_stream(torch.cuda.current_stream(dev))
-    return out, out_m
+    return _run(B, img_size, dev, keep, lambda x, m, st: lib.mtbt_mosaic_batch(tiles.ctypes.data_as(C.POINTER(L.RawImage)), B, img_size, g.ctypes.data_as(_INT32_P),
+                                                                                GEOM_FIELDS, c.ctypes.data_as(_INT32_P), table, x, m, st), "mtbt_mosaic_batch")
 
 
 def sample_mosaic(sizes: Sequence[Sequence[int]], img_size: int, rng: np.random.Generator, *, prob: float = 1.0, centre=(0.25, 0.75),
@@ -365,11 +364,7 @@ def mosaic_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Opti
     generator, run `mosaic_batch`, move the labels with `mosaic_yolo_labels`: (imgs [B,3,S,S], masks [B,1,S,S], gt_rows [M,6] on the
     device, batch index = canvas in column 0) -- what `TrainStep.step` takes.  `ranges` are the keyword arguments of those three functions;
     anything else is an error."""
-    geo = {k: ranges.pop(k) for k in ("prob", "centre", "scale", "aspect", "fliplr", "flipud", "transpose") if k in ranges}
-    pho = {k: ranges.pop(k) for k in ("brightness", "contrast", "gamma") if k in ranges}
-    lab = {k: ranges.pop(k) for k in ("min_px", "min_area_ratio", "max_aspect") if k in ranges}
-    if ranges:
-        raise TypeError(f"mosaic_samples: unknown arguments {sorted(ranges)}")
+    geo, pho, lab = _split(ranges, "mosaic_samples", ("prob", "centre", "scale", "aspect", "fliplr", "flipud", "transpose"))
     if len(rows_per_image) != len(images):
         raise ValueError("mosaic_samples: one list of label rows per image")
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]

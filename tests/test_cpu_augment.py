@@ -1,6 +1,6 @@
 """Training augmentation without a GPU: the numpy restatement (tests/augment_reference.py) against the letterbox oracle, the host
 side of `preprocess` (geometry and table sampling, label arithmetic, pixel / label consistency) and the argument checks of
-`mtbt_augment_batch`, which refuse a bad call before any launch.  The reference project has no augmentation: the arithmetic is
+`mtbt_augment_batch` and `mtbt_letterbox_batch`, which refuse a bad call before any launch.  The reference project has no augmentation: the arithmetic is
 the project's own definition (include/mtbt_hip.h)."""
 import ctypes as C
 
@@ -256,3 +256,46 @@ def test_bad_arguments_are_refused_before_any_launch(lib):
     assert _call(lib, out=PTR + 4) == EALIGN
     assert _call(lib, out_m=PTR + 8) == EALIGN
     assert _call(lib, S=62, out=PTR + 4) == EINVAL                                  # the argument checks come first
+
+
+def _letterbox_call(lib, n=1, S=64, images=True, out=PTR, out_m=PTR, edit=None):
+    descs = (L.RawImage * max(n, 1))()
+    for d in descs:
+        d.bgr, d.mask, d.height, d.width, d.row_stride, d.mask_row_stride = PTR, PTR, 10, 20, 60, 20
+    if edit:
+        edit(descs)
+    return lib.mtbt_letterbox_batch(descs if images else None, n, S, out, out_m, None, None)
+
+
+def test_letterbox_bad_arguments_are_refused_before_any_launch(lib):
+    """The letterbox follows the order of the two newer entry points: every descriptor first (also one in the second launch chunk, which
+    used to be refused only after the first chunk had been launched), then the alignment."""
+    assert _letterbox_call(lib, n=0) == 0
+    assert _letterbox_call(lib, images=False) == EINVAL
+    assert _letterbox_call(lib, out=None) == EINVAL
+    assert _letterbox_call(lib, n=-1) == EINVAL
+    for S in (62, 0, -64):
+        assert _letterbox_call(lib, S=S) == EINVAL
+
+    def bad(index, **kw):
+        def edit(descs):
+            for k, v in kw.items():
+                setattr(descs[index], k, v)
+        return edit
+    for kw in (dict(bgr=None), dict(height=0), dict(width=-3), dict(row_stride=59), dict(mask_row_stride=19), dict(height=1 << 20, row_stride=1 << 11),
+               dict(width=-2 ** 31)):
+        assert _letterbox_call(lib, edit=bad(0, **kw)) == EINVAL, kw
+        assert _letterbox_call(lib, n=40, edit=bad(39, **kw)) == EINVAL, kw             # second chunk of 32: still before the first launch
+        assert _letterbox_call(lib, n=40, out=PTR + 4, edit=bad(39, **kw)) == EINVAL, kw
+    assert _letterbox_call(lib, out=PTR + 4) == EALIGN
+    assert _letterbox_call(lib, out_m=PTR + 8) == EALIGN
+    assert _letterbox_call(lib, S=62, out=PTR + 4) == EINVAL
+    assert _letterbox_call(lib, out_m=PTR + 8, edit=bad(0, width=0)) == EINVAL
+
+
+def test_invalid_and_misaligned_is_invalid(lib):
+    bad_row = [32, 16, 0, 0, 8, 0, 0, 0]
+    assert _call(lib, geom=[bad_row], out=PTR + 4) == EINVAL
+    assert _call(lib, geom=[bad_row], out_m=PTR + 8) == EINVAL
+    assert _call(lib, n=40, geom=[[32, 16, 0, 0, 0, 0, 0, 0]] * 39 + [bad_row], out=PTR + 4) == EINVAL
+    assert _call(lib, out=PTR + 4) == EALIGN

@@ -129,3 +129,48 @@ def test_augment_rejects_bad_input():
         P.augment_batch([ok], None, good.astype(np.float32), None, 64)                              # not integers
     with pytest.raises(ValueError):
         P.augment_batch([ok], None, good, torch.zeros(1, 3, 256, dtype=torch.uint8), 64)            # table on the host
+
+
+def test_null_mask_output_of_the_three_entry_points():
+    """out_masks == NULL (and, for the letterbox, out_scales == NULL) through the C entry points themselves -- the Python wrappers always
+    pass a mask buffer: the images are bit-equal to the wrappers'."""
+    import ctypes as C
+    from multitask_bonetumor_yolo_amd import _lib as L
+    from multitask_bonetumor_yolo_amd import preprocess as P
+    S, n = 64, 8
+    lib = L.load()
+    imgs, masks = zip(*[_sample(h, w, seed=h * 131 + w) for h, w in SOURCES])
+    di, dm = [torch.from_numpy(a).to(DEV) for a in imgs], [torch.from_numpy(a).to(DEV) for a in masks]
+    src = [i % len(SOURCES) for i in range(n)]
+    bi, bm = [di[k] for k in src], [dm[k] for k in src]
+    sizes = [(S - 20, S - 30), (int(2.3 * S), S - 30), (S, S), (1, S - 24), (S - 1, int(2.3 * S)), (S - 20, S - 30), (S, S), (int(2.3 * S), int(2.3 * S))]
+    offsets = [(0, 0), (-10, 5), (7, -3), (3, 2), (-9, -70), (30, 40), (-1, -1), (-40, -50)]
+    geom = np.array([[nw, nh, ox, oy, orient, 0, 0, 0] for orient, ((nw, nh), (ox, oy)) in enumerate(zip(sizes, offsets))], dtype=np.int32)
+    assert set(geom[:, 4].tolist()) == set(range(8))
+    lut = torch.from_numpy(np.random.default_rng(7).integers(0, 256, size=(n, 3, 256), dtype=np.uint8)).to(DEV)
+    index = np.array([[0, 1, 2, 3], [4, 5, 0, 1], [3, 4, 5, 2]])
+    mgeom = np.stack([geom[[0, 1, 2, 3]], geom[[4, 5, 6, 7]], geom[[7, 2, 5, 0]]])
+    centres = np.array([[32, 17], [0, 0], [64, 64]], dtype=np.int32)
+
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32).ctypes.data_as(C.POINTER(C.c_int32))
+    descs, keep, _ = P._descriptors(bi, bm, "test")
+    got = {k: torch.full((b, 3, S, S), -1.0, device=DEV) for k, b in (("letterbox", n), ("augment", n), ("augment+table", n), ("mosaic", 3), ("mosaic+table", 3))}
+    assert lib.mtbt_letterbox_batch(descs, n, S, got["letterbox"].data_ptr(), None, None, stream) == 0
+    g = i32(geom)
+    assert lib.mtbt_augment_batch(descs, n, S, g, 8, None, got["augment"].data_ptr(), None, stream) == 0
+    assert lib.mtbt_augment_batch(descs, n, S, g, 8, lut.data_ptr(), got["augment+table"].data_ptr(), None, stream) == 0
+    sdescs, skeep, _ = P._descriptors(di, dm, "test")
+    tiles = (L.RawImage * 12)()
+    for k, s in enumerate(index.reshape(-1)):
+        tiles[k] = sdescs[int(s)]
+    mg, mc = i32(mgeom), i32(centres)
+    assert lib.mtbt_mosaic_batch(tiles, 3, S, mg, 8, mc, None, got["mosaic"].data_ptr(), None, stream) == 0
+    assert lib.mtbt_mosaic_batch(tiles, 3, S, mg, 8, mc, lut.data_ptr(), got["mosaic+table"].data_ptr(), None, stream) == 0
+    torch.cuda.synchronize()
+    want = {"letterbox": P.letterbox_batch(bi, bm, S)[0], "augment": P.augment_batch(bi, bm, geom, None, S)[0],
+            "augment+table": P.augment_batch(bi, bm, geom, lut, S)[0], "mosaic": P.mosaic_batch(di, dm, index, mgeom, centres, None, S)[0],
+            "mosaic+table": P.mosaic_batch(di, dm, index, mgeom, centres, lut[:3], S)[0]}
+    torch.cuda.synchronize()
+    for k in got:
+        assert torch.equal(got[k], want[k]), k

@@ -5,9 +5,10 @@ geometry (same output, same source bytes), the identity geometry with an intensi
 row gathers down a column of the source), and `preprocess.mosaic_batch` on B canvases of four of the same sources each: once with random
 centres in the middle half of the canvas (corner placement, the resized sizes of the identity geometry) and once with the degenerate
 centre (S, S), where a canvas is the identity augmentation of its first tile.  Device events around 20 calls per variant after warm-up,
-the variants alternating, 5 rounds; the median per variant, the ratio to the letterbox and, for the mosaic, the ratio to the augmentation
-at the identity geometry are printed.  usage: python tools/bench_augment.py [B] [H0] [W0] [S]"""
-import os, sys, statistics
+the variants alternating, 5 rounds; the median and the rounds per variant, the ratio to the letterbox and, for the mosaic, the ratio to the augmentation
+at the identity geometry are printed, after a sha256 of each variant's output (image and mask tensors), so that two builds can be compared at
+the size that is timed.  usage: python tools/bench_augment.py [B] [H0] [W0] [S]"""
+import hashlib, os, sys, statistics
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from multitask_bonetumor_yolo_amd import preprocess as P
@@ -37,6 +38,8 @@ variants = {
 }
 assert torch.equal(variants["letterbox_batch"]()[0], variants["augment identity"]()[0])
 assert torch.equal(variants["mosaic centre (S, S)"]()[0], variants["augment identity"]()[0])
+for k, f in variants.items():
+    print(f"{k:26s} sha256 {hashlib.sha256(b''.join(t.cpu().numpy().tobytes() for t in f()[:2])).hexdigest()}")
 for f in variants.values():
     for _ in range(5):
         f()
@@ -54,5 +57,5 @@ base, aug = statistics.median(times["letterbox_batch"]), statistics.median(times
 out_bytes = B * 4 * S * S * 4
 for k, t in times.items():
     us = statistics.median(t)
-    print(f"{k:26s} {us:8.1f} us / batch of {B} (min {min(t):.1f}, max {max(t):.1f}; {out_bytes / us / 1e3:.0f} GB/s of output)  x{us / base:.3f} of letterbox_batch"
+    print(f"{k:26s} {us:8.1f} us / batch of {B} (min {min(t):.1f}, max {max(t):.1f}, rounds {' '.join(f'{v:.1f}' for v in t)}; {out_bytes / us / 1e3:.0f} GB/s of output)  x{us / base:.3f} of letterbox_batch"
           + (f", x{us / aug:.3f} of augment identity" if k.startswith("mosaic") else ""))
