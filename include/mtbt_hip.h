@@ -466,6 +466,73 @@ int mtbt_instance_mask_loss(const mtbt_mask_loss_args* a, void* stream);
 int mtbt_sizeof_mask_loss_args(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * Task-aligned detection loss (the loss ultralytics' `Detect` head is trained with: TaskAlignedAssigner + CIoU + DFL + BCE over all
+ * anchors, `v8DetectionLoss`; an opt-in sibling of mtbt_multitask_loss's detection terms, whose positives need a predicted box that
+ * already overlaps a GT box) and its gradient with respect to the raw Detect maps.  The definition, restated (nothing is copied):
+ *   decode      as mtbt_multitask_loss: softmax expectation per side, anchor point (x + .5, y + .5) * stride, stride = img_size / w,
+ *               boxes xyxy in pixels.  GT rows: every row its own box in pixels, grouped by image with gt_off [N+1]; rows at or beyond
+ *               gt_off[N] belong to no image.  A row whose class lies outside [0, nc) takes part with score 0 and no class target.
+ *   ciou(p, g)  eps = 1e-7; w = x2 - x1, h = y2 - y1 + eps; inter = clamp(min(x2) - max(x1), 0) * clamp(min(y2) - max(y1), 0);
+ *               iou = inter / (w_p h_p + w_g h_g - inter + eps); cw, ch = extent of the enclosing box;
+ *               rho2 = ((g.x1 + g.x2 - p.x1 - p.x2)^2 + (g.y1 + g.y2 - p.y1 - p.y2)^2) / 4;
+ *               v = 4 / pi^2 * (atan(w_g / h_g) - atan(w_p / h_p))^2; alpha = v / (v - iou + (1 + eps)), a constant in the gradient;
+ *               ciou = iou - (rho2 / (cw^2 + ch^2 + eps) + v * alpha)
+ *   assignment  (no gradient) per image, GT row g, anchor a:
+ *               inside(g, a) = min(ax - x1, ay - y1, x2 - ax, y2 - ay) > 1e-9;  ov(g, a) = max(ciou(pred_a, gt_g), 0) where inside, else 0;
+ *               metric(g, a) = sigmoid(class logit[a][cls_g])^alpha * ov(g, a)^beta  (fp32 powf);
+ *               g selects its `topk` anchors of largest metric among ALL anchors of the image, ties (zeros included) to the lower
+ *               anchor index; selected anchors that are not inside are dropped; an anchor selected by several rows goes to the one
+ *               with the largest ov (the first maximum in row order); such an anchor is foreground (fg) with row g(a).
+ *               M_g = max metric, O_g = max ov over g's fg anchors; target score t_a = metric(g(a), a) * O_g / (M_g + 1e-9);
+ *               class target = t_a at class cls_g(a), 0 elsewhere; background anchors have all-zero targets.
+ *   loss        T = max(sum_a t_a over the batch, 1)
+ *               out[2] cls = sum over EVERY anchor and class of bce_with_logits(logit, target) / T
+ *               out[0] box = sum_fg (1 - ciou(pred_a, gt_g(a))) * t_a / T
+ *               out[1] dfl = sum_fg t_a * mean over the 4 sides of [ce(side, tl) * wl + ce(side, tr) * wr] / T, side target =
+ *                            clamp(distance from the anchor point to the GT side / stride, 0, reg_max - 1 - 0.01), tl = floor, tr = tl + 1,
+ *                            wl = tr - target, wr = 1 - wl
+ *               out[3] = #fg (an exact integer), out[4] = mean ov(g(a), a) over fg (0 without fg), out[5] = T,
+ *               out[6] = w_box * box + w_dfl * dfl + w_cls * cls, out[7] = 0
+ *   gradient    of out[6] with respect to every channel of every anchor's map row (T, t_a and the assignment are constants):
+ *               class channels w_cls * (sigmoid(x) - target) / T for ALL anchors; the 4 * reg_max distribution channels of fg anchors
+ *               through the corners (d dist / d raw_j = p_j (j - dist)) plus the DFL term; exact zeros for background anchors.
+ * map / h / w / map_pixel_stride / n_levels / N / nc / reg_max / img_size: as in mtbt_loss_args.  n_gt rows in gt_xyxy (16-byte
+ * aligned) / gt_cls.  topk in [1, 64].  d_map (all NULL, or one per level, pixel stride >= 4 * reg_max + nc): fp32 NHWC rows,
+ * every row written whole, or added to when `accumulate` is set.  assigned (optional) int32 [N][A]: g(a) as a row of gt_xyxy, -1 for
+ * background; target_score (optional) fp32 [N][A].  Deterministic (fixed-order sums, no floating-point atomics); no host
+ * synchronisation.  MTBT_EINVAL before any launch: NULL args / maps / gt_xyxy / gt_cls / gt_off / out / workspace, bad sizes, topk
+ * outside [1, 64], n_gt < 0, some but not all d_map given; MTBT_EALIGN for a misaligned gt_xyxy / workspace; MTBT_EWORKSPACE for
+ * workspace_bytes below mtbt_tal_loss_workspace_bytes(N, A, n_gt).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mtbt_tal_loss_args {
+  const float* map[3];
+  int32_t h[3], w[3];
+  int32_t map_pixel_stride[3];
+  int32_t n_levels, N, nc, reg_max;
+  float img_size;
+  int32_t n_gt;
+  const float* gt_xyxy;   /* [n_gt][4] pixels */
+  const int32_t* gt_cls;  /* [n_gt] */
+  const int32_t* gt_off;  /* [N+1] */
+  int32_t topk;
+  float alpha, beta;
+  float w_box, w_dfl, w_cls;
+  int32_t accumulate;
+  int32_t reserved;
+  float* d_map[3];
+  int32_t d_map_pixel_stride[3];
+  int32_t reserved2;
+  int32_t* assigned;
+  float* target_score;
+  void* workspace;
+  int64_t workspace_bytes;
+  float* out; /* [8] */
+} mtbt_tal_loss_args;
+int64_t mtbt_tal_loss_workspace_bytes(int N, int A, int G);
+int mtbt_tal_det_loss(const mtbt_tal_loss_args* a, void* stream);
+int mtbt_sizeof_tal_loss_args(void);
+
+/* ---------------------------------------------------------------------------------------------
  * ConvTranspose2d(C, Cm, 2, stride 2, bias) -> Conv 3x3 (Cm -> K, pad 1) + per-channel shift + activation as ONE direct convolution
  * over the LOW-resolution map (inference).  Replaces ultralytics `Proto.upsample` followed by `Proto.cv2` (conv + folded BatchNorm +
  * SiLU): main_model.py:326-328 [ultralytics Proto], SURVEY 8a row 10.  Both operators are linear with nothing in between: per output

@@ -151,6 +151,16 @@ class MaskLossArgs(C.Structure):  # mtbt_mask_loss_args
                 ("out", C.c_void_p)]
 
 
+class TalLossArgs(C.Structure):  # mtbt_tal_loss_args
+    _fields_ = [("map", C.c_void_p * 3), ("h", C.c_int32 * 3), ("w", C.c_int32 * 3), ("map_pixel_stride", C.c_int32 * 3),
+                ("n_levels", C.c_int32), ("N", C.c_int32), ("nc", C.c_int32), ("reg_max", C.c_int32), ("img_size", C.c_float),
+                ("n_gt", C.c_int32), ("gt_xyxy", C.c_void_p), ("gt_cls", C.c_void_p), ("gt_off", C.c_void_p),
+                ("topk", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float), ("w_box", C.c_float), ("w_dfl", C.c_float), ("w_cls", C.c_float),
+                ("accumulate", C.c_int32), ("reserved", C.c_int32), ("d_map", C.c_void_p * 3), ("d_map_pixel_stride", C.c_int32 * 3),
+                ("reserved2", C.c_int32), ("assigned", C.c_void_p), ("target_score", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("out", C.c_void_p)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -262,6 +272,9 @@ SYMBOLS = {
     "mtbt_mask_loss_workspace_bytes": (C.c_int64, [C.c_int] * 5),
     "mtbt_instance_mask_loss": (C.c_int, [C.POINTER(MaskLossArgs), C.c_void_p]),
     "mtbt_sizeof_mask_loss_args": (C.c_int, []),
+    "mtbt_tal_loss_workspace_bytes": (C.c_int64, [C.c_int] * 3),
+    "mtbt_tal_det_loss": (C.c_int, [C.POINTER(TalLossArgs), C.c_void_p]),
+    "mtbt_sizeof_tal_loss_args": (C.c_int, []),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -293,9 +306,10 @@ def load():
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "
                                        f"out in {C.sizeof(st)} bytes: stale library, rebuild")
-        if lib.mtbt_sizeof_mask_loss_args() != C.sizeof(MaskLossArgs):
-            raise RuntimeError(f"libmtbt_hip.so was built with sizeof(MaskLossArgs) = {lib.mtbt_sizeof_mask_loss_args()}, this binding lays it "
-                               f"out in {C.sizeof(MaskLossArgs)} bytes: stale library, rebuild")
+        for sizeof, st in ((lib.mtbt_sizeof_mask_loss_args, MaskLossArgs), (lib.mtbt_sizeof_tal_loss_args, TalLossArgs)):
+            if sizeof() != C.sizeof(st):
+                raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof()}, this binding lays it "
+                                   f"out in {C.sizeof(st)} bytes: stale library, rebuild")
         _lib = lib
     return _lib
 

@@ -242,3 +242,115 @@ class InstanceMaskLoss(torch.autograd.Function):
     def backward(ctx, g_loss, _g_npos):
         d_mc, d_pr = ctx.saved_tensors
         return ((d_mc * g_loss).to(ctx.dtypes[0]), (d_pr * g_loss).to(ctx.dtypes[1])) + (None,) * (7 + ctx.n_maps)
+
+
+# ---- task-aligned detection loss (TaskAlignedAssigner + CIoU + DFL + BCE over all anchors): csrc/det_loss_tal.hip ---------------
+def group_gt_rows_cls(gt_boxes: torch.Tensor, n_images: int, img_size: float):
+    """`group_gt_rows` with the rows' classes: -> (xyxy [G,4] pixels, cls [G] int32, off [N+1] int32), every row its own box, rows grouped
+    by image in stable order, rows with a non-positive side or an image index outside the batch behind `off[N]`.  Device-side tensor
+    ops only."""
+    dev = gt_boxes.device
+    G = gt_boxes.shape[0]
+    off = torch.zeros(n_images + 1, dtype=torch.int32, device=dev)
+    if G == 0:
+        return torch.zeros((1, 4), dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), off
+    g = gt_boxes.float()
+    bidx = g[:, 0].long()
+    skip = (g[:, 4] <= 0) | (g[:, 5] <= 0) | (bidx < 0) | (bidx >= n_images)
+    bidx = torch.where(skip, torch.full_like(bidx, n_images), bidx)
+    order = torch.argsort(bidx, stable=True)
+    g, bidx = g[order], bidx[order]
+    counts = torch.zeros(n_images + 1, dtype=torch.long, device=dev).scatter_add_(0, bidx, torch.ones_like(bidx))
+    off[1:] = torch.cumsum(counts[:n_images], 0).int()
+    xyxy = torch.stack([(g[:, 2] - g[:, 4] / 2) * img_size, (g[:, 3] - g[:, 5] / 2) * img_size,
+                        (g[:, 2] + g[:, 4] / 2) * img_size, (g[:, 3] + g[:, 5] / 2) * img_size], 1)
+    return xyxy.contiguous(), g[:, 1].int().contiguous(), off
+
+
+def task_aligned_det_loss(det_maps: Sequence[torch.Tensor], gt_boxes: torch.Tensor, *, img_size: int, nc_det: int, reg_max: int = 16,
+                          topk: int = 10, alpha: float = 0.5, beta: float = 6.0, weights=(7.5, 1.5, 0.5), with_grads: bool = False,
+                          grad_out=None, accumulate: bool = False, want_assignment: bool = False):
+    """The task-aligned (YOLOv8) detection loss on the device (definition: include/mtbt_hip.h, `mtbt_tal_loss_args`).  An opt-in
+    extension beyond the reference's `_multitask_loss`, whose positives need a predicted box that already overlaps a GT box.
+
+    det_maps: the raw Detect maps (<= 3 x [B, 4*reg_max+nc, h, w]); gt_boxes [G, 6] = (batch_idx, cls, cx, cy, w, h) normalised, every
+    row its own box (`group_gt_rows_cls`).  Returns (box, dfl, cls, n_fg, mean overlap of the foreground anchors) as 0-d fp32 device
+    tensors without autograd history.  `with_grads=True` also returns the gradient of `weights . (box, dfl, cls)` with respect to the
+    maps, a list of [B, no, h, w] views of NHWC fp32 memory; `grad_out=[NHWC fp32 buffers]` writes it straight into a training plan's
+    input buffers, `accumulate=True` adds to the buffers.  `want_assignment=True` also returns `assigned` int32 [B, A] (the row of the
+    grouped GT an anchor is assigned to, -1 = background) and `target_score` [B, A].  The extras follow the values in that order.  No
+    host synchronisation."""
+    lib = L.load()
+    _need_cuda(det_maps[0], "task_aligned_det_loss")
+    dev = det_maps[0].device
+    B = det_maps[0].shape[0]
+    no = 4 * reg_max + nc_det
+    A = sum(m.shape[2] * m.shape[3] for m in det_maps)
+    a = L.TalLossArgs()
+    keep = []
+    for i, m in enumerate(det_maps):
+        if m.shape[1] != no:
+            raise ValueError(f"task_aligned_det_loss: map {i} has {m.shape[1]} channels, expected 4 * reg_max + nc_det = {no}")
+        t, ld = _nhwc_rows(m.detach())
+        keep.append(t)
+        a.map[i], a.h[i], a.w[i], a.map_pixel_stride[i] = t.data_ptr(), m.shape[2], m.shape[3], ld
+    a.n_levels, a.N, a.nc, a.reg_max, a.img_size = len(det_maps), B, nc_det, reg_max, float(img_size)
+    xyxy, gcls, off = group_gt_rows_cls(gt_boxes.to(dev), B, float(img_size))
+    keep += [xyxy, gcls, off]
+    G = int(gt_boxes.shape[0])
+    a.n_gt, a.gt_xyxy, a.gt_cls, a.gt_off = G, xyxy.data_ptr(), gcls.data_ptr(), off.data_ptr()
+    a.topk, a.alpha, a.beta = int(topk), float(alpha), float(beta)
+    a.w_box, a.w_dfl, a.w_cls = (float(v) for v in weights)
+    d_maps = None
+    if with_grads or grad_out is not None:
+        if grad_out is not None:
+            d_maps = list(grad_out)
+            for t, m in zip(d_maps, det_maps):
+                if t.dtype != torch.float32 or t.numel() != B * m.shape[2] * m.shape[3] * no or not t.is_contiguous():
+                    raise ValueError("task_aligned_det_loss: grad_out must hold one contiguous fp32 [B, h, w, no] buffer per map")
+            if len(d_maps) != len(det_maps):
+                raise ValueError("task_aligned_det_loss: grad_out must hold one buffer per map")
+        else:
+            mk = torch.zeros if accumulate else torch.empty
+            d_maps = [mk(B, m.shape[2], m.shape[3], no, dtype=torch.float32, device=dev) for m in det_maps]
+        for i, t in enumerate(d_maps):
+            a.d_map[i], a.d_map_pixel_stride[i] = t.data_ptr(), no
+        a.accumulate = int(accumulate)
+    assigned = tscore = None
+    if want_assignment:
+        assigned = torch.empty(B, A, dtype=torch.int32, device=dev)
+        tscore = torch.empty(B, A, dtype=torch.float32, device=dev)
+        a.assigned, a.target_score = assigned.data_ptr(), tscore.data_ptr()
+    nbytes = lib.mtbt_tal_loss_workspace_bytes(B, A, G)
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
+    L.check(lib.mtbt_tal_det_loss(C.byref(a), _stream(dev)), "mtbt_tal_det_loss")
+    del keep
+    res = [tuple(out[i] for i in range(5))]
+    if d_maps is not None:
+        res.append([t.view(B, m.shape[2], m.shape[3], no).permute(0, 3, 1, 2) for t, m in zip(d_maps, det_maps)])
+    if want_assignment:
+        res += [assigned, tscore]
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+class TaskAlignedDetLoss(torch.autograd.Function):
+    """`w_box * box + w_dfl * dfl + w_cls * cls` of the task-aligned detection loss as an autograd node for the drop-in route: a trainer
+    uses it in place of the detection terms it computes on the maps of `model(x, "train")`.
+        TaskAlignedDetLoss.apply(gt_boxes, img_size, reg_max, nc, topk, alpha, beta, w_box, w_dfl, w_cls, *det_maps)
+    -> (weighted loss, n_fg).  Forward runs the value and the gradient; backward scales the gradient by the incoming one and hands it
+    out in the maps' dtypes.  The assignment carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, gt_boxes, img_size, reg_max, nc, topk, alpha, beta, w_box, w_dfl, w_cls, *det_maps):
+        (box, dfl, cls, n_fg, _), g = task_aligned_det_loss([m.detach() for m in det_maps], gt_boxes, img_size=img_size, nc_det=nc, reg_max=reg_max,
+                                                            topk=topk, alpha=alpha, beta=beta, weights=(w_box, w_dfl, w_cls), with_grads=True)
+        ctx.save_for_backward(*g)
+        ctx.dtypes = tuple(m.dtype for m in det_maps)
+        ctx.mark_non_differentiable(n_fg)
+        return w_box * box + w_dfl * dfl + w_cls * cls, n_fg
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_nfg):
+        return (None,) * 10 + tuple((g * g_loss).to(dt) for g, dt in zip(ctx.saved_tensors, ctx.dtypes))

@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import code_of, reserved_stream
-from .loss import instance_mask_loss, multitask_loss
+from .loss import instance_mask_loss, multitask_loss, task_aligned_det_loss
 from .dist_train import FlatBuckets
 from .train import TrainPlan, make_arena
 
@@ -99,7 +99,8 @@ class TrainStep:
     def __init__(self, model, batch_shape: Sequence[int], *, optimizer: str = "adamw", lr: float = 1e-4, weight_decay: float = 5e-4,
                  betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.9, nesterov: bool = False, clip_norm: Optional[float] = 10.0,
                  iou_match_thresh: float = 0.5, label_smoothing: float = 0.1, loss_weights=(1.0, 2.0, 1.5, 0.5, 1.0),
-                 projector: Optional[nn.Conv2d] = None, process_group=None, overlap: bool = True, instance_mask_weight: float = 0.0, ema=None):
+                 projector: Optional[nn.Conv2d] = None, process_group=None, overlap: bool = True, instance_mask_weight: float = 0.0, ema=None,
+                 det_loss: str = "reference", tal=None):
         """batch_shape [B,3,S,S] per rank.  `projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1),
         running_main_v3.py:186); created (seeded default init) when not given.  A live `torch.distributed` process group with more than
         one rank turns on the gradient exchange; parameters are broadcast from rank 0 first (what DDP does at construction).
@@ -108,7 +109,19 @@ class TrainStep:
         `ema` = dict(decay=0.9999, tau=2000.0) (or True for those values) keeps averaged weights: `self.ema` (buckets laid out like
         `self.params`), `self.pj_ema`, `self.ema_model` / `self.ema_projector` (eval-mode modules over that storage, for validation
         and export); update u uses `ema_decay_at(u, decay, tau)`.  The model's floating-point buffers are then re-homed into one flat
-        buffer so that one launch averages them all.  None (default): no launch, no storage and no buffer moves."""
+        buffer so that one launch averages them all.  None (default): no launch, no storage and no buffer moves.
+        `det_loss="tal"` replaces the detection terms of the reference's loss by the task-aligned detection loss (csrc/det_loss_tal.hip,
+        `tal` = dict(topk=10, alpha=0.5, beta=6.0)): box / dfl / cls_det, #positives and the mean matched IoU of the returned tuple then
+        hold its terms, its #foreground anchors and their mean overlap, weighted by the same `loss_weights` slots; `iou_match_thresh` then
+        governs only the instance-mask term.  "reference" (default): nothing changes."""
+        if det_loss not in ("reference", "tal"):
+            raise ValueError(f"det_loss: 'reference' (the reference trainer's _multitask_loss) or 'tal' (task-aligned), not {det_loss!r}")
+        self.det_loss = det_loss
+        self.tal_kw = dict(topk=10, alpha=0.5, beta=6.0)
+        if tal is not None:
+            if det_loss != "tal" or set(tal) - set(self.tal_kw):
+                raise ValueError("tal: dict(topk=, alpha=, beta=), only with det_loss='tal'")
+            self.tal_kw.update(tal)
         if not hasattr(model, "detect"):
             raise NotImplementedError("TrainStep drives the canonical model (running_main_v3.py needs .detect, SURVEY F4)")
         self.m = model
@@ -176,6 +189,10 @@ class TrainStep:
         self.sq_ws = torch.empty(self.lib.mtbt_sumsq_workspace_bytes() // 4, device=dev)
         self.loss_kw = dict(img_size=self.S, nc_det=model.nc_det, reg_max=model.detect.reg_max, iou_match_thresh=iou_match_thresh,
                             label_smoothing=label_smoothing, training=True, weights=loss_weights)
+        if det_loss == "tal":        # the detection terms come from the task-aligned operator: the reference's get weight 0
+            w = tuple(float(v) for v in loss_weights)
+            self.tal_w = w[1:4]
+            self.loss_kw["weights"] = (w[0], 0.0, 0.0, 0.0, w[4])
         # ---- gradient exchange: bucket b is complete once EVERY backward launch in writers[b] has run ----
         self.comm = reserved_stream(dev, "grad_exchange") if (self.world > 1 and overlap) else None
         self.writers = bucket_writers(self.bwd.launches, self.grads.buckets)
@@ -258,6 +275,11 @@ class TrainStep:
                                 self.projector.bias, with_grads=True,
                                 grad_out={"det_maps": [d.buf for d in tp.d_in["det"]], "img_logits": tp.d_in["logits"]}, **self.loss_kw)
         dseg = g["seg_logits"]
+        if self.det_loss == "tal":   # overwrites d_in["det"] whole
+            tal, _ = task_aligned_det_loss([m.nchw() for m in tp.det_maps], gt_boxes, img_size=self.S, nc_det=self.loss_kw["nc_det"],
+                                           reg_max=self.loss_kw["reg_max"], weights=self.tal_w, grad_out=[d.buf for d in tp.d_in["det"]], **self.tal_kw)
+            wb, wd, wc = self.tal_w
+            res = (res[0] + (wb * tal[0] + wd * tal[1] + wc * tal[2]), res[1], tal[0], tal[1], tal[2], res[5], tal[3], tal[4])
         mask = None
         if self.mask_w > 0:          # writes d_in["mc"] and d_in["protos"] whole; the projector's share is then ADDED to the latter
             mask = instance_mask_loss([m.nchw() for m in tp.det_maps], tp.mc, tp.protos.nchw(), gt_boxes, gt_masks, img_size=self.S,
@@ -427,7 +449,7 @@ class TrainStep:
                             (`checkpoints.strip_lightning_prefix` reads it);
           "ema_state_dict"  the same names without the `net.` prefix, from the averaged weights (only with `ema=`);
           "optimizer"       {name: {"exp_avg", "exp_avg_sq"}} or {name: {"momentum_buffer"}}, the names of "state_dict";
-          "steps", "ema_updates", "lr", "optimizer_name".
+          "steps", "ema_updates", "lr", "optimizer_name", "det_loss".
         Every tensor is keyed by parameter name and has the parameter's own shape, so the file does not depend on the bucket layout."""
         sd, esd = self._live_tensors()
         out = {"state_dict": {k: _cpu(v) for k, v in sd.items()}}
@@ -437,17 +459,20 @@ class TrainStep:
         for slot, views in self._moments().items():
             for name, v in views.items():
                 opt.setdefault(name, {})[slot] = _cpu(v)
-        out.update(optimizer=opt, steps=int(self.steps), ema_updates=int(self.ema_updates), lr=float(self.lr), optimizer_name=str(self.opt))
+        out.update(optimizer=opt, steps=int(self.steps), ema_updates=int(self.ema_updates), lr=float(self.lr), optimizer_name=str(self.opt),
+                   det_loss=str(self.det_loss))
         return out
 
     @torch.no_grad()
     def load_state_dict(self, state: dict):
         """Write a `state_dict()` into the existing storage, in place (the plans keep their pointers).  ValueError, before anything is
-        written, for another optimiser, names or shapes that do not match, or an EMA on one side only."""
+        written, for another optimiser or detection loss, names or shapes that do not match, or an EMA on one side only."""
         if not isinstance(state, dict) or "state_dict" not in state or "optimizer" not in state:
             raise ValueError("load_state_dict: not a TrainStep state (expected the keys of TrainStep.state_dict())")
         if state.get("optimizer_name") != self.opt:
             raise ValueError(f"load_state_dict: the state was saved by optimizer {state.get('optimizer_name')!r}, this step runs {self.opt!r}")
+        if state.get("det_loss", "reference") != self.det_loss:
+            raise ValueError(f"load_state_dict: the state was trained with det_loss {state.get('det_loss', 'reference')!r}, this step runs {self.det_loss!r}")
         if ("ema_state_dict" in state) != (self.ema is not None):
             raise ValueError("load_state_dict: the state holds an EMA and this step keeps none (construct it with ema=...)" if self.ema is None
                              else "load_state_dict: this step keeps an EMA and the state holds none")
