@@ -437,6 +437,14 @@ int mtbt_cls_confusion(const float* logits, const int64_t* target, int N, int nc
  * MTBT_EINVAL before any launch: NULL args / maps / gt_xyxy / gt_off / mc / protos / gt_masks / out / workspace, a non-integral
  * img_size or one that hp or wp does not divide, nm != 32, n_gt < 0 or > N * A, workspace_bytes below
  * mtbt_mask_loss_workspace_bytes(N, A, hp, wp, nm), an unknown dprotos_dtype.  MTBT_EALIGN for misaligned gt_xyxy / protos / d_mc / d_protos.
+ *
+ * mtbt_instance_mask_loss_assigned: the same loss with the positives GIVEN (ultralytics `v8SegmentationLoss`: the mask term runs on
+ * the task-aligned assigner's foreground anchors and their assigned GT rows).  assigned: int32 [N][A] dense, in the anchor order of
+ * the maps -- what mtbt_tal_det_loss writes; element (b, a) is a row of gt_xyxy or -1.  A value v is foreground only if
+ * gt_off[b] <= v < min(gt_off[b + 1], n_gt); any other value (another image's row, at or beyond n_gt, below -1) is background and is
+ * never used as an index.  map / h / w / n_levels are read for the anchor count A only: the map pointers may be NULL, and
+ * map_pixel_stride, reg_max and iou_thresh are ignored.  Target, crop, area, norm, out, both gradients with their accumulate flags and
+ * dtypes, the workspace size, determinism and the error codes are those above; MTBT_EINVAL also for a NULL `assigned`, before any launch.
  * ------------------------------------------------------------------------------------------- */
 typedef struct mtbt_mask_loss_args {
   const float* map[3];
@@ -463,6 +471,7 @@ typedef struct mtbt_mask_loss_args {
 } mtbt_mask_loss_args;
 int64_t mtbt_mask_loss_workspace_bytes(int N, int A, int hp, int wp, int nm);
 int mtbt_instance_mask_loss(const mtbt_mask_loss_args* a, void* stream);
+int mtbt_instance_mask_loss_assigned(const mtbt_mask_loss_args* a, const int32_t* assigned, void* stream);
 int mtbt_sizeof_mask_loss_args(void);
 
 /* ---------------------------------------------------------------------------------------------

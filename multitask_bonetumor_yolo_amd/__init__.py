@@ -8,6 +8,7 @@
     from multitask_bonetumor_yolo_amd import multitask_loss              # == MultiTaskLitModel._multitask_loss (value)
     from multitask_bonetumor_yolo_amd import instance_mask_loss          # YOLOv8-seg instance-mask loss + gradients (opt-in extension)
     from multitask_bonetumor_yolo_amd import task_aligned_det_loss       # task-aligned (YOLOv8) detection loss + gradients (opt-in extension)
+    from multitask_bonetumor_yolo_amd import TaskAlignedSegLoss          # both in one autograd node: the mask term on the task-aligned assignment
     from multitask_bonetumor_yolo_amd import ValidationStep              # == validation_step + the epoch-end metrics, on the device
     from multitask_bonetumor_yolo_amd import TrainStep, ema_decay_at     # the native training step (ema=: averaged weights in the optimiser pass)
     from multitask_bonetumor_yolo_amd import save_train_state, load_train_state   # stop a TrainStep and continue it
@@ -18,7 +19,7 @@ The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 from . import postprocess, preprocess  # noqa: F401
 from .preprocess import (augment_batch, augment_samples, augment_yolo_labels, letterbox_geometry, mosaic_batch, mosaic_samples,  # noqa: F401
                          mosaic_yolo_labels, photometric_lut, sample_geometry, sample_mosaic, sample_photometric)
-from .loss import InstanceMaskLoss, TaskAlignedDetLoss, instance_mask_loss, multitask_loss, task_aligned_det_loss  # noqa: F401
+from .loss import InstanceMaskLoss, TaskAlignedDetLoss, TaskAlignedSegLoss, instance_mask_loss, multitask_loss, task_aligned_det_loss  # noqa: F401
 from .checkpoints import load_pretrained_heads, load_train_state, save_train_state, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision,  # noqa: F401

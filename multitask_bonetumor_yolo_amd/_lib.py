@@ -271,6 +271,7 @@ SYMBOLS = {
     "mtbt_sizeof_mask_eval_args": (C.c_int, [C.c_int]),
     "mtbt_mask_loss_workspace_bytes": (C.c_int64, [C.c_int] * 5),
     "mtbt_instance_mask_loss": (C.c_int, [C.POINTER(MaskLossArgs), C.c_void_p]),
+    "mtbt_instance_mask_loss_assigned": (C.c_int, [C.POINTER(MaskLossArgs), C.c_void_p, C.c_void_p]),
     "mtbt_sizeof_mask_loss_args": (C.c_int, []),
     "mtbt_tal_loss_workspace_bytes": (C.c_int64, [C.c_int] * 3),
     "mtbt_tal_det_loss": (C.c_int, [C.POINTER(TalLossArgs), C.c_void_p]),

@@ -1,8 +1,11 @@
 // Instance-mask loss (YOLOv8-seg single_mask_loss / crop_mask) and its gradient with respect to the mask coefficients and the
 // prototypes: the operator that lets training reach Segment.cv4 and use the prototypes as a per-instance basis.  Definition:
-// include/mtbt_hip.h (mtbt_mask_loss_args).  Positives come from the detection loss's own prologue (match_anchor, loss_match.h).
+// include/mtbt_hip.h (mtbt_mask_loss_args).  Positives come from the detection loss's own prologue (match_anchor, loss_match.h), or,
+// through mtbt_instance_mask_loss_assigned, from an assignment the caller hands in (the task-aligned assigner's, det_loss_tal.hip).
 //
 //   ml_match_kernel     4 lanes per (image, anchor): match[b][a] = matched GT row or -1; zero rows of d_mc for non-positives
+//   ml_assigned_kernel  its sibling for a given assignment: match[b][a] = assigned[b][a] if it is a row of image b, else -1; the same
+//                       zeroing; reads no detection map.  Everything below reads match[b][a] only and is shared by both entry points
 //   ml_list_kernel      one workgroup per GT row g: the anchors matched to g, ascending, compacted into the image's positive list
 //                       (list[b][start_g .. start_g + cnt_g), GT rows of an image in order) -- sized for all A anchors
 //   ml_count_kernel     #positives of the batch (integer sum of cnt)
@@ -85,6 +88,25 @@ __global__ __launch_bounds__(256) void ml_match_kernel(const MaskLossP p) {
   if (!am.live) return;
   if (side == 0) p.match[g] = am.pos ? am.bi : -1;
   if (p.d_mc && !p.acc_dmc && !am.pos) {
+    f32x4* d = reinterpret_cast<f32x4*>(p.d_mc + g * NM + side * 8);
+    d[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    d[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+// The match from a given assignment: 4 lanes per (image, anchor) like ml_match_kernel, so that a non-foreground anchor's d_mc row is
+// zeroed by the same 16-byte stores.  An entry is foreground only if it is a row of its own image below n_gt; anything else is
+// background and is never used as an index.
+__global__ __launch_bounds__(256) void ml_assigned_kernel(const MaskLossP p, const int* __restrict__ assigned) {
+  const long g = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
+  const int side = threadIdx.x & 3;
+  if (g >= (long)p.l.N * p.l.A) return;
+  const int n = (int)(g / p.l.A);
+  const int v = assigned[g];
+  const int g0 = max(p.l.gt_off[n], 0), g1 = min(p.l.gt_off[n + 1], p.G);
+  const bool pos = v >= g0 && v < g1;
+  if (side == 0) p.match[g] = pos ? v : -1;
+  if (p.d_mc && !p.acc_dmc && !pos) {
     f32x4* d = reinterpret_cast<f32x4*>(p.d_mc + g * NM + side * 8);
     d[0] = f32x4{0.f, 0.f, 0.f, 0.f};
     d[1] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -414,9 +436,13 @@ extern "C" int64_t mtbt_mask_loss_workspace_bytes(int N, int A, int hp, int wp, 
 
 extern "C" int mtbt_sizeof_mask_loss_args(void) { return (int)sizeof(mtbt_mask_loss_args); }
 
-extern "C" int mtbt_instance_mask_loss(const mtbt_mask_loss_args* a, void* stream) {
+// One body for both entry points: without `by_assignment` it decodes and matches (ml_match_kernel), with it the match is taken from the
+// assignment (ml_assigned_kernel; the maps give the anchor count only).  Everything behind the match is the same launch sequence.
+static int run_mask_loss(const mtbt_mask_loss_args* a, const int32_t* assigned, bool by_assignment, void* stream) {
   if (!a || !a->gt_xyxy || !a->gt_off || !a->mc || !a->protos || !a->gt_masks || !a->out || !a->workspace) return MTBT_EINVAL;
-  if (a->n_levels < 1 || a->n_levels > 3 || a->N <= 0 || a->reg_max <= 0 || a->reg_max > 64 || a->hp <= 0 || a->wp <= 0) return MTBT_EINVAL;
+  if (by_assignment && !assigned) return MTBT_EINVAL;
+  if (a->n_levels < 1 || a->n_levels > 3 || a->N <= 0 || a->hp <= 0 || a->wp <= 0) return MTBT_EINVAL;
+  if (!by_assignment && (a->reg_max <= 0 || a->reg_max > 64)) return MTBT_EINVAL;
   if (a->nm != NM || a->n_gt < 0) return MTBT_EINVAL;
   const int S = (int)a->img_size;
   if (S <= 0 || (float)S != a->img_size || S % a->hp || S % a->wp) return MTBT_EINVAL;
@@ -426,8 +452,9 @@ extern "C" int mtbt_instance_mask_loss(const mtbt_mask_loss_args* a, void* strea
   for (int l = 0; l < 3; ++l) {
     p.l.off[l] = (int)A;
     if (l < a->n_levels) {
-      if (!a->map[l] || a->h[l] <= 0 || a->w[l] <= 0 || a->map_pixel_stride[l] < 4 * a->reg_max) return MTBT_EINVAL;
-      p.l.map[l] = a->map[l]; p.l.h[l] = a->h[l]; p.l.w[l] = a->w[l]; p.l.ld[l] = a->map_pixel_stride[l];
+      if (a->h[l] <= 0 || a->w[l] <= 0) return MTBT_EINVAL;
+      if (!by_assignment && (!a->map[l] || a->map_pixel_stride[l] < 4 * a->reg_max)) return MTBT_EINVAL;
+      p.l.map[l] = by_assignment ? nullptr : a->map[l]; p.l.h[l] = a->h[l]; p.l.w[l] = a->w[l]; p.l.ld[l] = a->map_pixel_stride[l];
       p.l.stride[l] = a->img_size / (float)a->w[l];
       A += (long)a->h[l] * a->w[l];
     } else { p.l.map[l] = nullptr; p.l.h[l] = p.l.w[l] = 1; p.l.ld[l] = 0; p.l.stride[l] = 0.f; }
@@ -456,7 +483,8 @@ extern "C" int mtbt_instance_mask_loss(const mtbt_mask_loss_args* a, void* strea
   p.out = a->out;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long mb = (NA + 63) / 64;
-  hipLaunchKernelGGL(ml_match_kernel, dim3((unsigned)mb), dim3(256), 0, s, p);
+  if (by_assignment) hipLaunchKernelGGL(ml_assigned_kernel, dim3((unsigned)mb), dim3(256), 0, s, p, assigned);
+  else hipLaunchKernelGGL(ml_match_kernel, dim3((unsigned)mb), dim3(256), 0, s, p);
   if (p.G > 0) hipLaunchKernelGGL(ml_list_kernel, dim3((unsigned)p.G), dim3(256), 0, s, p);
   hipLaunchKernelGGL(ml_count_kernel, dim3(1), dim3(256), 0, s, p);
   if (p.G > 0) {
@@ -473,4 +501,10 @@ extern "C" int mtbt_instance_mask_loss(const mtbt_mask_loss_args* a, void* strea
   hipLaunchKernelGGL(ml_finalize_kernel, dim3(1), dim3(256), 0, s, p);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
+}
+
+extern "C" int mtbt_instance_mask_loss(const mtbt_mask_loss_args* a, void* stream) { return run_mask_loss(a, nullptr, false, stream); }
+
+extern "C" int mtbt_instance_mask_loss_assigned(const mtbt_mask_loss_args* a, const int32_t* assigned, void* stream) {
+  return run_mask_loss(a, assigned, true, stream);
 }

@@ -124,29 +124,16 @@ def group_gt_rows(gt_boxes: torch.Tensor, n_images: int, img_size: float):
     (x1 = (cx - w / 2) * S, ...), rows grouped by image in stable order.  Unlike `group_gt_boxes` this is not the reference's
     column-concatenated layout, which mixes coordinates of different boxes of an image: a mask target cropped to such a box means
     nothing.  Rows with a non-positive width or height (or an image index outside the batch) are moved behind `off[N]`: they belong
-    to no image and are never matched.  Device-side tensor ops only, no host synchronisation."""
-    dev = gt_boxes.device
-    G = gt_boxes.shape[0]
-    off = torch.zeros(n_images + 1, dtype=torch.int32, device=dev)
-    if G == 0:
-        return torch.zeros((1, 4), dtype=torch.float32, device=dev), off
-    g = gt_boxes.float()
-    bidx = g[:, 0].long()
-    skip = (g[:, 4] <= 0) | (g[:, 5] <= 0) | (bidx < 0) | (bidx >= n_images)
-    bidx = torch.where(skip, torch.full_like(bidx, n_images), bidx)
-    order = torch.argsort(bidx, stable=True)
-    g, bidx = g[order], bidx[order]
-    counts = torch.zeros(n_images + 1, dtype=torch.long, device=dev).scatter_add_(0, bidx, torch.ones_like(bidx))
-    off[1:] = torch.cumsum(counts[:n_images], 0).int()
-    xyxy = torch.stack([(g[:, 2] - g[:, 4] / 2) * img_size, (g[:, 3] - g[:, 5] / 2) * img_size,
-                        (g[:, 2] + g[:, 4] / 2) * img_size, (g[:, 3] + g[:, 5] / 2) * img_size], 1)
-    return xyxy.contiguous(), off
+    to no image and are never matched.  Device-side tensor ops only, no host synchronisation.  It IS `group_gt_rows_cls` without the
+    classes: one definition of the row order, which an assignment handed from the task-aligned loss to the mask loss relies on."""
+    xyxy, _, off = group_gt_rows_cls(gt_boxes, n_images, img_size, want_cls=False)
+    return xyxy, off
 
 
 def instance_mask_loss(box_maps: Sequence[torch.Tensor], mc: torch.Tensor, protos: torch.Tensor, gt_boxes: torch.Tensor,
                        gt_masks: torch.Tensor, *, img_size: int, reg_max: int = 16, iou_match_thresh: float = 0.5, weight: float = 1.0,
                        with_grads: bool = False, grad_out=None, accumulate: bool = False, protos_grad_dtype=torch.float32,
-                       mc_layout: Optional[str] = None):
+                       mc_layout: Optional[str] = None, assigned: Optional[torch.Tensor] = None):
     """The YOLOv8-seg instance-mask loss on the device (definition: include/mtbt_hip.h, `mtbt_mask_loss_args`).  An extension beyond the
     reference's `_multitask_loss`, whose only use of the prototypes is the 1x1 projector.
 
@@ -156,7 +143,10 @@ def instance_mask_loss(box_maps: Sequence[torch.Tensor], mc: torch.Tensor, proto
     Returns (mask_loss, n_pos) as 0-d fp32 device tensors without autograd history.  `with_grads=True` returns
     `((mask_loss, n_pos), {"mc": [B, A, nm] fp32, "protos": [B, nm, hp, wp] view of channels-last memory in protos_grad_dtype})`,
     the gradient of `weight * mask_loss`.  `grad_out={"mc": [B, A, nm] fp32, "protos": NHWC buffer (fp32 / bf16 / fp16)}` writes them
-    straight into a training plan's input buffers; `accumulate=True` adds to the buffers instead of overwriting them."""
+    straight into a training plan's input buffers; `accumulate=True` adds to the buffers instead of overwriting them.
+    `assigned` = int32 [B, A] on the device (`task_aligned_det_loss(want_assignment=True)`: a row of the grouped GT, or -1) takes the
+    positives from that assignment instead of the IoU match (`mtbt_instance_mask_loss_assigned`): `box_maps` is then used for its
+    shapes only, `reg_max` and `iou_match_thresh` are not read, and n_pos is the number of foreground anchors."""
     lib = L.load()
     _need_cuda(box_maps[0], "instance_mask_loss")
     _need_cuda(mc, "instance_mask_loss")
@@ -167,10 +157,18 @@ def instance_mask_loss(box_maps: Sequence[torch.Tensor], mc: torch.Tensor, proto
     S = int(img_size)
     a = L.MaskLossArgs()
     keep = []
+    if assigned is not None:
+        _need_cuda(assigned, "instance_mask_loss")
+        if assigned.dtype != torch.int32 or tuple(assigned.shape) != (B, A):
+            raise ValueError(f"instance_mask_loss: assigned must be an int32 [B, A] = {(B, A)} tensor, not {assigned.dtype} {tuple(assigned.shape)}")
+        assigned = assigned.contiguous()
+        keep.append(assigned)
     for i, m in enumerate(box_maps):
-        t, ld = _nhwc_rows(m)
-        keep.append(t)
-        a.map[i], a.h[i], a.w[i], a.map_pixel_stride[i] = t.data_ptr(), m.shape[2], m.shape[3], ld
+        a.h[i], a.w[i] = m.shape[2], m.shape[3]
+        if assigned is None:
+            t, ld = _nhwc_rows(m)
+            keep.append(t)
+            a.map[i], a.map_pixel_stride[i] = t.data_ptr(), ld
     a.n_levels, a.N, a.reg_max, a.img_size, a.iou_thresh = len(box_maps), B, reg_max, float(img_size), float(iou_match_thresh)
     xyxy, off = group_gt_rows(gt_boxes.to(dev), B, float(img_size))
     a.n_gt, a.gt_xyxy, a.gt_off = int(gt_boxes.shape[0]), xyxy.data_ptr(), off.data_ptr()
@@ -214,7 +212,10 @@ def instance_mask_loss(box_maps: Sequence[torch.Tensor], mc: torch.Tensor, proto
     ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
     out = torch.empty(2, dtype=torch.float32, device=dev)
     a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
-    L.check(lib.mtbt_instance_mask_loss(C.byref(a), _stream(dev)), "mtbt_instance_mask_loss")
+    if assigned is None:
+        L.check(lib.mtbt_instance_mask_loss(C.byref(a), _stream(dev)), "mtbt_instance_mask_loss")
+    else:
+        L.check(lib.mtbt_instance_mask_loss_assigned(C.byref(a), assigned.data_ptr(), _stream(dev)), "mtbt_instance_mask_loss_assigned")
     del keep
     res = (out[0], out[1])
     return (res, grads) if grads is not None else res
@@ -245,15 +246,15 @@ class InstanceMaskLoss(torch.autograd.Function):
 
 
 # ---- task-aligned detection loss (TaskAlignedAssigner + CIoU + DFL + BCE over all anchors): csrc/det_loss_tal.hip ---------------
-def group_gt_rows_cls(gt_boxes: torch.Tensor, n_images: int, img_size: float):
+def group_gt_rows_cls(gt_boxes: torch.Tensor, n_images: int, img_size: float, want_cls: bool = True):
     """`group_gt_rows` with the rows' classes: -> (xyxy [G,4] pixels, cls [G] int32, off [N+1] int32), every row its own box, rows grouped
     by image in stable order, rows with a non-positive side or an image index outside the batch behind `off[N]`.  Device-side tensor
-    ops only."""
+    ops only.  `want_cls=False` (what `group_gt_rows` passes) returns None in place of the classes and launches nothing for them."""
     dev = gt_boxes.device
     G = gt_boxes.shape[0]
     off = torch.zeros(n_images + 1, dtype=torch.int32, device=dev)
     if G == 0:
-        return torch.zeros((1, 4), dtype=torch.float32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), off
+        return torch.zeros((1, 4), dtype=torch.float32, device=dev), (torch.zeros(1, dtype=torch.int32, device=dev) if want_cls else None), off
     g = gt_boxes.float()
     bidx = g[:, 0].long()
     skip = (g[:, 4] <= 0) | (g[:, 5] <= 0) | (bidx < 0) | (bidx >= n_images)
@@ -264,7 +265,7 @@ def group_gt_rows_cls(gt_boxes: torch.Tensor, n_images: int, img_size: float):
     off[1:] = torch.cumsum(counts[:n_images], 0).int()
     xyxy = torch.stack([(g[:, 2] - g[:, 4] / 2) * img_size, (g[:, 3] - g[:, 5] / 2) * img_size,
                         (g[:, 2] + g[:, 4] / 2) * img_size, (g[:, 3] + g[:, 5] / 2) * img_size], 1)
-    return xyxy.contiguous(), g[:, 1].int().contiguous(), off
+    return xyxy.contiguous(), (g[:, 1].int().contiguous() if want_cls else None), off
 
 
 def task_aligned_det_loss(det_maps: Sequence[torch.Tensor], gt_boxes: torch.Tensor, *, img_size: int, nc_det: int, reg_max: int = 16,
@@ -354,3 +355,32 @@ class TaskAlignedDetLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_nfg):
         return (None,) * 10 + tuple((g * g_loss).to(dt) for g, dt in zip(ctx.saved_tensors, ctx.dtypes))
+
+
+class TaskAlignedSegLoss(torch.autograd.Function):
+    """The detection and mask terms of ultralytics' `v8SegmentationLoss` in one autograd node for the drop-in route: the task-aligned
+    detection loss, and the instance-mask loss on ITS foreground anchors and assigned GT rows.
+        TaskAlignedSegLoss.apply(mc, protos, gt_boxes, gt_masks, img_size, reg_max, nc, topk, alpha, beta, w_box, w_dfl, w_cls, w_mask,
+                                 mc_layout, *det_maps)
+    -> (w_box * box + w_dfl * dfl + w_cls * cls + w_mask * mask, n_fg).  Forward runs `task_aligned_det_loss(want_assignment=True,
+    with_grads=True)`, then `instance_mask_loss(assigned=...)`; backward scales the stored gradients by the incoming one and hands them
+    out in the inputs' dtypes.  The assignment is a constant: the maps get the task-aligned loss's gradient only."""
+
+    @staticmethod
+    def forward(ctx, mc, protos, gt_boxes, gt_masks, img_size, reg_max, nc, topk, alpha, beta, w_box, w_dfl, w_cls, w_mask, mc_layout, *det_maps):
+        maps = [m.detach() for m in det_maps]
+        (box, dfl, cls, n_fg, _), g_maps, assigned, _ = task_aligned_det_loss(maps, gt_boxes, img_size=img_size, nc_det=nc, reg_max=reg_max, topk=topk,
+                                                                             alpha=alpha, beta=beta, weights=(w_box, w_dfl, w_cls), with_grads=True,
+                                                                             want_assignment=True)
+        (mask, _), g = instance_mask_loss(maps, mc, protos, gt_boxes, gt_masks, img_size=img_size, reg_max=reg_max, weight=w_mask, with_grads=True,
+                                          mc_layout=mc_layout, assigned=assigned)
+        d_mc = g["mc"] if mc_layout == "bAn" else g["mc"].permute(0, 2, 1)
+        ctx.save_for_backward(d_mc, g["protos"], *g_maps)
+        ctx.dtypes = (mc.dtype, protos.dtype) + tuple(m.dtype for m in det_maps)
+        ctx.mark_non_differentiable(n_fg)
+        return w_box * box + w_dfl * dfl + w_cls * cls + w_mask * mask, n_fg
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_nfg):
+        grads = tuple((g * g_loss).to(dt) for g, dt in zip(ctx.saved_tensors, ctx.dtypes))
+        return grads[:2] + (None,) * 13 + grads[2:]

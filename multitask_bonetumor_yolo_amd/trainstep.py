@@ -100,7 +100,7 @@ class TrainStep:
                  betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.9, nesterov: bool = False, clip_norm: Optional[float] = 10.0,
                  iou_match_thresh: float = 0.5, label_smoothing: float = 0.1, loss_weights=(1.0, 2.0, 1.5, 0.5, 1.0),
                  projector: Optional[nn.Conv2d] = None, process_group=None, overlap: bool = True, instance_mask_weight: float = 0.0, ema=None,
-                 det_loss: str = "reference", tal=None):
+                 det_loss: str = "reference", tal=None, mask_assign: str = "iou"):
         """batch_shape [B,3,S,S] per rank.  `projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1),
         running_main_v3.py:186); created (seeded default init) when not given.  A live `torch.distributed` process group with more than
         one rank turns on the gradient exchange; parameters are broadcast from rank 0 first (what DDP does at construction).
@@ -113,7 +113,11 @@ class TrainStep:
         `det_loss="tal"` replaces the detection terms of the reference's loss by the task-aligned detection loss (csrc/det_loss_tal.hip,
         `tal` = dict(topk=10, alpha=0.5, beta=6.0)): box / dfl / cls_det, #positives and the mean matched IoU of the returned tuple then
         hold its terms, its #foreground anchors and their mean overlap, weighted by the same `loss_weights` slots; `iou_match_thresh` then
-        governs only the instance-mask term.  "reference" (default): nothing changes."""
+        governs only the instance-mask term.  "reference" (default): nothing changes.
+        `mask_assign="tal"` (needs `det_loss="tal"` and `instance_mask_weight` > 0) gives the instance-mask term the task-aligned
+        assignment's foreground anchors and their assigned GT rows in place of its own IoU match (`v8SegmentationLoss`): the mask
+        positives' count (element 9) then equals the number of foreground anchors (element 6) and `iou_match_thresh` is not read.
+        "iou" (default): nothing changes."""
         if det_loss not in ("reference", "tal"):
             raise ValueError(f"det_loss: 'reference' (the reference trainer's _multitask_loss) or 'tal' (task-aligned), not {det_loss!r}")
         self.det_loss = det_loss
@@ -122,6 +126,11 @@ class TrainStep:
             if det_loss != "tal" or set(tal) - set(self.tal_kw):
                 raise ValueError("tal: dict(topk=, alpha=, beta=), only with det_loss='tal'")
             self.tal_kw.update(tal)
+        if mask_assign not in ("iou", "tal"):
+            raise ValueError(f"mask_assign: 'iou' (the mask loss's own IoU match) or 'tal' (the task-aligned assignment), not {mask_assign!r}")
+        if mask_assign == "tal" and (det_loss != "tal" or not float(instance_mask_weight) > 0):
+            raise ValueError("mask_assign='tal' needs det_loss='tal' and instance_mask_weight > 0")
+        self.mask_assign = mask_assign
         if not hasattr(model, "detect"):
             raise NotImplementedError("TrainStep drives the canonical model (running_main_v3.py needs .detect, SURVEY F4)")
         self.m = model
@@ -275,16 +284,21 @@ class TrainStep:
                                 self.projector.bias, with_grads=True,
                                 grad_out={"det_maps": [d.buf for d in tp.d_in["det"]], "img_logits": tp.d_in["logits"]}, **self.loss_kw)
         dseg = g["seg_logits"]
+        assigned = None
         if self.det_loss == "tal":   # overwrites d_in["det"] whole
-            tal, _ = task_aligned_det_loss([m.nchw() for m in tp.det_maps], gt_boxes, img_size=self.S, nc_det=self.loss_kw["nc_det"],
-                                           reg_max=self.loss_kw["reg_max"], weights=self.tal_w, grad_out=[d.buf for d in tp.d_in["det"]], **self.tal_kw)
+            r = task_aligned_det_loss([m.nchw() for m in tp.det_maps], gt_boxes, img_size=self.S, nc_det=self.loss_kw["nc_det"],
+                                      reg_max=self.loss_kw["reg_max"], weights=self.tal_w, grad_out=[d.buf for d in tp.d_in["det"]],
+                                      want_assignment=self.mask_assign == "tal", **self.tal_kw)
+            tal = r[0]
+            if self.mask_assign == "tal":
+                assigned = r[2]
             wb, wd, wc = self.tal_w
             res = (res[0] + (wb * tal[0] + wd * tal[1] + wc * tal[2]), res[1], tal[0], tal[1], tal[2], res[5], tal[3], tal[4])
         mask = None
         if self.mask_w > 0:          # writes d_in["mc"] and d_in["protos"] whole; the projector's share is then ADDED to the latter
             mask = instance_mask_loss([m.nchw() for m in tp.det_maps], tp.mc, tp.protos.nchw(), gt_boxes, gt_masks, img_size=self.S,
                                       reg_max=self.loss_kw["reg_max"], iou_match_thresh=self.loss_kw["iou_match_thresh"], weight=self.mask_w,
-                                      mc_layout="bAn", grad_out={"mc": tp.d_in["mc"], "protos": tp.d_in["protos"]})[0]
+                                      mc_layout="bAn", grad_out={"mc": tp.d_in["mc"], "protos": tp.d_in["protos"]}, assigned=assigned)[0]
         L.check(lib.mtbt_projector_backward(dseg.data_ptr(), tp.protos.ptr, self.pj.data_ptr(), tp.d_in["protos"].data_ptr(), tp.code, int(mask is not None),
                                             self.pj_grad.data_ptr(), self.pj_grad.data_ptr() + 4 * nm, 0, self.B, self.S // 4, self.S // 4, nm, self.S, self.S,
                                             self.pj_ws.data_ptr(), self.pj_ws.numel() * 4, _s(dev)), "mtbt_projector_backward")
@@ -449,7 +463,7 @@ class TrainStep:
                             (`checkpoints.strip_lightning_prefix` reads it);
           "ema_state_dict"  the same names without the `net.` prefix, from the averaged weights (only with `ema=`);
           "optimizer"       {name: {"exp_avg", "exp_avg_sq"}} or {name: {"momentum_buffer"}}, the names of "state_dict";
-          "steps", "ema_updates", "lr", "optimizer_name", "det_loss".
+          "steps", "ema_updates", "lr", "optimizer_name", "det_loss", "mask_assign".
         Every tensor is keyed by parameter name and has the parameter's own shape, so the file does not depend on the bucket layout."""
         sd, esd = self._live_tensors()
         out = {"state_dict": {k: _cpu(v) for k, v in sd.items()}}
@@ -460,19 +474,21 @@ class TrainStep:
             for name, v in views.items():
                 opt.setdefault(name, {})[slot] = _cpu(v)
         out.update(optimizer=opt, steps=int(self.steps), ema_updates=int(self.ema_updates), lr=float(self.lr), optimizer_name=str(self.opt),
-                   det_loss=str(self.det_loss))
+                   det_loss=str(self.det_loss), mask_assign=str(self.mask_assign))
         return out
 
     @torch.no_grad()
     def load_state_dict(self, state: dict):
         """Write a `state_dict()` into the existing storage, in place (the plans keep their pointers).  ValueError, before anything is
-        written, for another optimiser or detection loss, names or shapes that do not match, or an EMA on one side only."""
+        written, for another optimiser, detection loss or mask assignment, names or shapes that do not match, or an EMA on one side only."""
         if not isinstance(state, dict) or "state_dict" not in state or "optimizer" not in state:
             raise ValueError("load_state_dict: not a TrainStep state (expected the keys of TrainStep.state_dict())")
         if state.get("optimizer_name") != self.opt:
             raise ValueError(f"load_state_dict: the state was saved by optimizer {state.get('optimizer_name')!r}, this step runs {self.opt!r}")
         if state.get("det_loss", "reference") != self.det_loss:
             raise ValueError(f"load_state_dict: the state was trained with det_loss {state.get('det_loss', 'reference')!r}, this step runs {self.det_loss!r}")
+        if state.get("mask_assign", "iou") != self.mask_assign:
+            raise ValueError(f"load_state_dict: the state was trained with mask_assign {state.get('mask_assign', 'iou')!r}, this step runs {self.mask_assign!r}")
         if ("ema_state_dict" in state) != (self.ema is not None):
             raise ValueError("load_state_dict: the state holds an EMA and this step keeps none (construct it with ema=...)" if self.ema is None
                              else "load_state_dict: this step keeps an EMA and the state holds none")

@@ -17,12 +17,13 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .loss import multitask_loss
+from .loss import instance_mask_loss, multitask_loss, task_aligned_det_loss
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision, ImageClassificationMetrics,
                       SegmentationMetrics, _sum_over_ranks)
 from .postprocess import CONF_TH, NMS_IOU, TOP_K, decode_boxes, masks_to_frames, nms_batched, pack_masks, proto_projector_logits
 
 LOSS_NAMES = ("total", "seg", "box_iou", "dfl", "det_cls", "img_cls")       # running_main_v3.py:578-582
+MASK_LOSS_NAME = "mask"                                                      # appended with instance_mask_weight > 0
 
 
 class BatchWeightedMeans:
@@ -56,7 +57,8 @@ class ValidationStep:
     def __init__(self, model, *, projector: Optional[nn.Conv2d] = None, img_size: int = 640, iou_match_thresh: float = 0.5,
                  label_smoothing: float = 0.1, loss_weights=(1.0, 2.0, 1.5, 0.5, 1.0), conf_th: float = CONF_TH, nms_iou: float = NMS_IOU,
                  top_k: int = TOP_K, map_max_detections: int = 100, dist_sync: bool = True, process_group=None,
-                 instance_masks: bool = False, mask_crop: bool = True):
+                 instance_masks: bool = False, mask_crop: bool = True, det_loss: str = "reference", tal=None,
+                 instance_mask_weight: float = 0.0, mask_assign: str = "iou"):
         """`projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1), running_main_v3.py:186); created with torch's default
         init when not given.  The loss hyper-parameters default to the reference's (and TrainStep's); `label_smoothing` is accepted for
         symmetry with TrainStep but the eval-mode loss never smooths (:337).  conf_th / nms_iou / top_k: `:54-56`;
@@ -64,7 +66,29 @@ class ValidationStep:
         `instance_masks`: also score the Segment head's INSTANCE masks (COCO mask mAP next to the box mAP; nothing in the reference
         computes it): the kept boxes' masks at S x S, bit-packed (`masks_to_frames` with identity frames, cropped to their boxes with
         `mask_crop`), against per-box ground truth cut out of the image's one mask by its box rows (`pack_masks`).  Off: `step`
-        launches nothing more and `compute()` returns the reference's keys only."""
+        launches nothing more and `compute()` returns the reference's keys only.
+        `det_loss`, `tal`, `instance_mask_weight`, `mask_assign`: as in `TrainStep`, so that a run trained with them monitors the loss it
+        optimises.  `det_loss="tal"`: the box / dfl / det_cls elements and the total hold the task-aligned terms, weighted by the same
+        `loss_weights` slots; seg and img_cls still come from the eval-mode `multitask_loss` with detection weights 0.
+        `instance_mask_weight` > 0: the total includes `weight * mask_loss`, the tuple gains mask_loss and its positive count (8 elements)
+        and `compute()` gains `val_epoch/loss_mask`; `mask_assign="tal"` takes its positives from the task-aligned assignment.  No
+        gradient is computed.  The detection confusion matrix keeps the reference's matching.  At the defaults nothing changes."""
+        if det_loss not in ("reference", "tal"):
+            raise ValueError(f"det_loss: 'reference' (the reference trainer's _multitask_loss) or 'tal' (task-aligned), not {det_loss!r}")
+        self.det_loss = det_loss
+        self.tal_kw = dict(topk=10, alpha=0.5, beta=6.0)
+        if tal is not None:
+            if det_loss != "tal" or set(tal) - set(self.tal_kw):
+                raise ValueError("tal: dict(topk=, alpha=, beta=), only with det_loss='tal'")
+            self.tal_kw.update(tal)
+        self.mask_w = float(instance_mask_weight)
+        if self.mask_w < 0:
+            raise ValueError("instance_mask_weight must be >= 0")
+        if mask_assign not in ("iou", "tal"):
+            raise ValueError(f"mask_assign: 'iou' (the mask loss's own IoU match) or 'tal' (the task-aligned assignment), not {mask_assign!r}")
+        if mask_assign == "tal" and (det_loss != "tal" or not self.mask_w > 0):
+            raise ValueError("mask_assign='tal' needs det_loss='tal' and instance_mask_weight > 0")
+        self.mask_assign = mask_assign
         if not hasattr(model, "detect"):
             raise NotImplementedError("ValidationStep drives the canonical model (running_main_v3.py needs .detect, SURVEY F4)")
         dev = next(model.parameters()).device
@@ -75,9 +99,14 @@ class ValidationStep:
         self.nc_det, self.reg_max = model.nc_det, model.detect.reg_max
         self.loss_kw = dict(img_size=self.S, nc_det=self.nc_det, reg_max=self.reg_max, iou_match_thresh=iou_match_thresh,
                             label_smoothing=label_smoothing, training=False, weights=loss_weights)
+        if det_loss == "tal":        # the detection terms come from the task-aligned operator: the reference's get weight 0
+            w = tuple(float(v) for v in loss_weights)
+            self.tal_w = w[1:4]
+            self.loss_kw["weights"] = (w[0], 0.0, 0.0, 0.0, w[4])
         self.nms_kw = dict(conf_th=conf_th, iou_th=nms_iou, top_k=top_k)
         sync = dict(dist_sync=dist_sync, process_group=process_group)
-        self.losses = BatchWeightedMeans(len(LOSS_NAMES), **sync)
+        self.loss_names = LOSS_NAMES + ((MASK_LOSS_NAME,) if self.mask_w > 0 else ())
+        self.losses = BatchWeightedMeans(len(self.loss_names), **sync)
         self.seg = SegmentationMetrics(**sync)
         self.img = ImageClassificationMetrics(model.nc_img, **sync)
         self.det_cm = DetectionConfusionMatrix(self.nc_det, self.S, iou_match_thresh, self.reg_max, **sync)
@@ -109,6 +138,7 @@ class ValidationStep:
     def step(self, imgs: torch.Tensor, det_gt: torch.Tensor, masks_gt: torch.Tensor, cls_gt: torch.Tensor):
         """One validation batch: imgs [B,3,S,S], det_gt [M,6] collated rows, masks_gt [B,1,S,S], cls_gt [B], all on the model's device.
         Returns the eval-mode loss tuple (total, seg, box, dfl, cls_det, img_cls) as 0-d device tensors; no host synchronisation.
+        With `instance_mask_weight` > 0 two elements follow: mask_loss and its positive count.
         With `instance_masks`, masks_gt must be bool, uint8 or float32 (what `pack_masks` takes; anything else raises ValueError)."""
         if not all(t.is_cuda for t in (imgs, det_gt, masks_gt, cls_gt)):
             raise RuntimeError("ValidationStep.step: expected CUDA/HIP tensors on an MI355X (no CPU path)")
@@ -117,6 +147,19 @@ class ValidationStep:
         protos = seg_out[2]
         pj = self.projector
         losses = multitask_loss(det, protos, logits, det_gt, masks_gt, cls_gt, pj.weight, pj.bias, **self.loss_kw)
+        assigned = None
+        if self.det_loss == "tal":
+            r = task_aligned_det_loss(det, det_gt, img_size=self.S, nc_det=self.nc_det, reg_max=self.reg_max, weights=self.tal_w,
+                                      want_assignment=self.mask_assign == "tal", **self.tal_kw)
+            tal = r[0] if self.mask_assign == "tal" else r
+            if self.mask_assign == "tal":
+                assigned = r[1]
+            wb, wd, wc = self.tal_w
+            losses = (losses[0] + (wb * tal[0] + wd * tal[1] + wc * tal[2]), losses[1], tal[0], tal[1], tal[2], losses[5])
+        if self.mask_w > 0:
+            mask = instance_mask_loss(det, seg_out[1], protos, det_gt, masks_gt, img_size=self.S, reg_max=self.reg_max,
+                                      iou_match_thresh=self.loss_kw["iou_match_thresh"], weight=self.mask_w, mc_layout="bnA", assigned=assigned)
+            losses = (losses[0] + self.mask_w * mask[0],) + tuple(losses[1:]) + (mask[0], mask[1])
         self.losses.update(losses, B)
         self.seg.update(proto_projector_logits(protos, pj.weight, pj.bias, self.S), masks_gt)
         self.img.update(logits, cls_gt)
@@ -153,7 +196,7 @@ class ValidationStep:
         macro image scores), plus the alias `val_epoch_map_iou50/map` that the checkpoint callback monitors (:803).  Confusion matrices
         are row-normalised numpy arrays.  With a live process group: over every rank's batches (a collective, every rank must call it)."""
         out: Dict[str, object] = {}
-        for name, v in zip(LOSS_NAMES, self.losses.compute()):
+        for name, v in zip(self.loss_names, self.losses.compute()):
             out[f"val_epoch/loss_{name}"] = float(v)
         img = self.img.compute()
         out["val_epoch/img_accuracy_epoch"] = img["accuracy"]
