@@ -167,13 +167,18 @@ __global__ __launch_bounds__(256) void scalar_final(const float* __restrict__ pa
 __global__ __launch_bounds__(256) void proj_bwd_low(const float* __restrict__ dseg, float* __restrict__ dlow, int N, int hp, int wp, int Ho, int Wo) {
   const long total = (long)N * hp * wp;
   const float sy = (float)hp / (float)Ho, sx = (float)wp / (float)Wo;   // torch: scale = in / out (size given, no scale_factor)
-  const int ry = (Ho + hp - 1) / hp, rx = (Wo + wp - 1) / wp;
+  // The gather window is the inverse of the forward mapping: output Y reaches input y only if its source coordinate (Y + .5) * sy - .5
+  // lies in (y - 1, y + 1), i.e. Y in ((y - .5) / sy - .5, (y + 1.5) / sy - .5); the coordinates the forward clamps (below 0: input 0;
+  // i1 past the last row: the last row) lie inside the window of the row they are clamped to, and the window is cut to the map.  One pixel
+  // of slack per side covers the rounding of these float expressions; bil_weight gives the slack pixels weight 0 (skipped below).  Any
+  // Ho / hp >= 1 is served, integer or not (a window stepped by ceil(Ho / hp) drifts above its true lower edge as y grows).
+  const float iy = (float)Ho / (float)hp, ix = (float)Wo / (float)wp;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int x = (int)(i % wp);
     const long ny = i / wp;
     const int y = (int)(ny % hp), n = (int)(ny / hp);
-    const int Y0 = max(0, (y - 1) * ry - 1), Y1 = min(Ho - 1, (y + 2) * ry + 1);
-    const int X0 = max(0, (x - 1) * rx - 1), X1 = min(Wo - 1, (x + 2) * rx + 1);
+    const int Y0 = max(0, (int)floorf((y - 0.5f) * iy - 0.5f) - 1), Y1 = min(Ho - 1, (int)ceilf((y + 1.5f) * iy - 0.5f) + 1);
+    const int X0 = max(0, (int)floorf((x - 0.5f) * ix - 0.5f) - 1), X1 = min(Wo - 1, (int)ceilf((x + 1.5f) * ix - 0.5f) + 1);
     float acc = 0.f;
     for (int Y = Y0; Y <= Y1; ++Y) {
       const float wy = bil_weight(Y, y, sy, hp);
