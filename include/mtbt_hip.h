@@ -214,6 +214,44 @@ typedef struct mtbt_node_args {
 int mtbt_bifpn_node_nhwc(const mtbt_node_args* a, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Two back-to-back 1x1 convolutions on the same pixels as ONE launch (pw_chain.hip; inference, 16-bit storage):
+ *   t[p][m] = round16( act1( (sum_c w1[m][c] * x[p][c]) * scale1[m] + shift1[m] ) )       m < 256, C = 256
+ *   y[p][k] =          act2( (sum_m w2[k][m] * t[p][m]) * scale2[k] + shift2[k] )
+ * t never reaches memory: it is rounded to the storage type exactly as mtbt_conv2d_nhwc stores it and becomes the second GEMM's operand in
+ * LDS.  Every output element goes through the reduction order and the epilogue arithmetic of mtbt_conv2d_nhwc, so the result is BIT-IDENTICAL
+ * to the two launches (tests/test_gpu_pw_chain.py).  Two families:
+ *   out_dtype == dtype:    K = 256, act2 any of MTBT_ACT_NONE | SILU | ELU                      (BiFPN node conv -> C2f cv1)
+ *   out_dtype == MTBT_F32: K <= 32, act2 = MTBT_ACT_NONE, scale2 = NULL (bias only)             (class branch cv3[i][1][1] -> cv3[i][2])
+ * act1 is MTBT_ACT_SILU or MTBT_ACT_ELU.  x [pixels][256] dense; y: pixel p at y + p * y_pixel_stride (elements of out_dtype), K channels -- a
+ * channel slice of a wider buffer is fine.  scale1 / scale2 may be NULL (= 1), shift1 / shift2 may be NULL (= 0).  Anything else returns
+ * MTBT_EINVAL / MTBT_EALIGN before a launch. */
+typedef struct mtbt_pw_chain_args {
+  const void* x;        /* [pixels][256] dtype */
+  const void* w1;       /* [256][256] dtype */
+  const float* scale1;  /* [256] or NULL */
+  const float* shift1;  /* [256] or NULL */
+  const void* w2;       /* [K][256] dtype */
+  const float* scale2;  /* [K] or NULL */
+  const float* shift2;  /* [K] or NULL */
+  void* y;
+  int64_t pixels;
+  int32_t y_pixel_stride;
+  int32_t C;            /* 256 */
+  int32_t M;            /* 256: width of the intermediate tensor */
+  int32_t K;
+  int32_t dtype;        /* MTBT_BF16 | MTBT_F16 */
+  int32_t out_dtype;    /* dtype | MTBT_F32 */
+  int32_t act1;
+  int32_t act2;
+} mtbt_pw_chain_args;
+int mtbt_pw_chain_nhwc(const mtbt_pw_chain_args* a, void* stream);
+/* What mtbt_pw_chain_nhwc would do with these arguments; nothing is launched, no pointer is dereferenced.  0: it has no kernel for them (the
+ * entry point returns an error).  1: it has one and the fused launch is the faster form.  2: it has one, but at this pixel count the two
+ * launches measured faster (a pixel-count rule; the entry point still runs the call).  A lowering asks this before it fuses a site. */
+int mtbt_pw_chain_supported(const mtbt_pw_chain_args* a);
+int mtbt_sizeof_pw_chain_args(void);
+
+/* ---------------------------------------------------------------------------------------------
  * BatchNorm2d forward with BATCH statistics + activation (module in train mode): the reference flips the
  * Detect/Segment heads to train mode inside forward(mode="train") (main_model.py:358-359), so their
  * BatchNorms use batch statistics and update running_mean/var (momentum, unbiased variance) -- SURVEY F14.

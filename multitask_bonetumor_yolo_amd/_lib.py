@@ -45,6 +45,12 @@ class NodeArgs(C.Structure):  # mtbt_node_args
                 ("act", C.c_int32)]
 
 
+class PwChainArgs(C.Structure):  # mtbt_pw_chain_args
+    _fields_ = [("x", C.c_void_p), ("w1", C.c_void_p), ("scale1", C.c_void_p), ("shift1", C.c_void_p), ("w2", C.c_void_p), ("scale2", C.c_void_p),
+                ("shift2", C.c_void_p), ("y", C.c_void_p), ("pixels", C.c_int64), ("y_pixel_stride", C.c_int32), ("C", C.c_int32), ("M", C.c_int32),
+                ("K", C.c_int32), ("dtype", C.c_int32), ("out_dtype", C.c_int32), ("act1", C.c_int32), ("act2", C.c_int32)]
+
+
 class UpconvArgs(C.Structure):  # mtbt_upconv_args
     _fields_ = [("x", C.c_void_p), ("w", C.c_void_p), ("y", C.c_void_p), ("shift", C.c_void_p),
                 ("x_batch_stride", C.c_int64), ("y_batch_stride", C.c_int64), ("x_pixel_stride", C.c_int32), ("y_pixel_stride", C.c_int32),
@@ -173,6 +179,9 @@ SYMBOLS = {
     "mtbt_layernorm_nhwc": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "mtbt_bifpn_fuse": (C.c_int, [C.POINTER(FuseArgs), C.c_void_p]),
     "mtbt_bifpn_node_nhwc": (C.c_int, [C.POINTER(NodeArgs), C.c_void_p]),
+    "mtbt_pw_chain_nhwc": (C.c_int, [C.POINTER(PwChainArgs), C.c_void_p]),
+    "mtbt_pw_chain_supported": (C.c_int, [C.POINTER(PwChainArgs)]),
+    "mtbt_sizeof_pw_chain_args": (C.c_int, []),
     "mtbt_bn_train_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),
     "mtbt_bn_train_nhwc": (C.c_int, [C.c_void_p] * 6 + [C.c_float, C.c_float, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p,
                                       C.c_int64, C.c_void_p]),
@@ -307,7 +316,8 @@ def load():
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "
                                        f"out in {C.sizeof(st)} bytes: stale library, rebuild")
-        for sizeof, st in ((lib.mtbt_sizeof_mask_loss_args, MaskLossArgs), (lib.mtbt_sizeof_tal_loss_args, TalLossArgs)):
+        for sizeof, st in ((lib.mtbt_sizeof_mask_loss_args, MaskLossArgs), (lib.mtbt_sizeof_tal_loss_args, TalLossArgs),
+                           (lib.mtbt_sizeof_pw_chain_args, PwChainArgs)):
             if sizeof() != C.sizeof(st):
                 raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof()}, this binding lays it "
                                    f"out in {C.sizeof(st)} bytes: stale library, rebuild")

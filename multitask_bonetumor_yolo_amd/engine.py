@@ -616,6 +616,33 @@ class Plan:
         self._io(list(inputs) + [w, shift], [y])
         return a
 
+    def pw_chain_args(self, x: Act, w1: torch.Tensor, shift1, act1, w2: torch.Tensor, shift2, act2, y: Act, any_size=False):
+        """The argument block of `pw_chain`, or None where the library has no fused kernel for the site or, unless `any_size`, advises the two
+        launches at this pixel count (`mtbt_pw_chain_supported`: nothing is launched) -- the caller then lowers the two convolutions as
+        launches of their own."""
+        if not (x.dense and y.bs == y.H * y.W * y.ld and (x.N, x.H, x.W) == (y.N, y.H, y.W)) or x.code not in (L.BF16, L.F16):
+            return None
+        a = L.PwChainArgs()
+        a.x, a.w1, a.w2, a.y = x.ptr, w1.data_ptr(), w2.data_ptr(), y.ptr
+        a.shift1 = shift1.data_ptr() if shift1 is not None else None
+        a.shift2 = shift2.data_ptr() if shift2 is not None else None
+        a.pixels, a.y_pixel_stride = x.N * x.H * x.W, y.ld
+        a.C, a.M, a.K = x.C, w1.shape[0], w2.shape[0]
+        a.dtype, a.out_dtype, a.act1, a.act2 = x.code, y.code, act1, act2
+        if w1.shape[1] != x.C or w2.shape[1] != w1.shape[0] or y.C != w2.shape[0]:
+            return None
+        return a if self.lib.mtbt_pw_chain_supported(C.byref(a)) in ((1, 2) if any_size else (1,)) else None
+
+    def pw_chain(self, a, x: Act, w1, shift1, w2, shift2, y: Act, name="pw_chain"):
+        """Two chained 1x1 convolutions in one launch (pw_chain.hip), bit-identical to the pair; `a` from `pw_chain_args`.  Reads x, writes
+        y's slice: the dependencies of the pair without its intermediate tensor.  FLOPs / bytes: both GEMMs, x once, y once, the weights once."""
+        n = x.N * x.H * x.W
+        Cin, M, K = x.C, w1.shape[0], w2.shape[0]
+        self.launches.append(Launch(self.lib.mtbt_pw_chain_nhwc, (C.byref(a),), name, (a, x.buf, w1, shift1, w2, shift2, y.buf),
+                                    2.0 * n * (M * Cin + K * M), (n * Cin + M * Cin + K * M) * ESIZE[x.code] + n * K * ESIZE[y.code]))
+        self._io([x, w1, shift1, w2, shift2], [y])
+        return a
+
     def upconv(self, x: Act, w: torch.Tensor, shift9: torch.Tensor, y: Act, act=L.ACT_SILU, name="upconv"):
         """ConvTranspose2d(2, 2) -> Conv 3x3 + shift + activation as one direct conv on the low-resolution map (upconv_fused.hip).
         w [4*K, 4*C] composed weights, shift9 [9, K] fp32 (model.compose_upconv)."""

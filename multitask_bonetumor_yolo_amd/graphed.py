@@ -12,7 +12,7 @@ from . import postprocess as pp
 
 
 # Schedule candidates of `autotune`: (plan option, values).  Coordinate search from the defaults: one knob at a time, keep what is faster.
-AUTOTUNE_KNOBS = (("NODE_FUSED", ("1",)), ("SEG_GATE", ("1", "2")), ("LANE_WIDE_US", ("200",)), ("LANES", ("3",)), ("ADAPTOR_EARLY", ("1",)),
+AUTOTUNE_KNOBS = (("PW_CHAIN", ("1",)), ("NODE_FUSED", ("1",)), ("SEG_GATE", ("1", "2")), ("LANE_WIDE_US", ("200",)), ("LANES", ("3",)), ("ADAPTOR_EARLY", ("1",)),
                   ("HEADS_EARLY", ("1",)))
 
 

@@ -280,7 +280,7 @@ def pack_dwblocks(mods):
     return torch.cat(ws, 1).contiguous(), torch.cat(scs, 0), torch.cat(shs, 0)
 
 
-PLAN_OPTION_DEFAULTS = {"NODE_FUSED": "0", "ADAPTOR_EARLY": "0", "HEADS_EARLY": "0", "SEG_GATE": "0", "HEADS_MERGED": "0", "LANES": None, "LANE_WIDE_US": None}
+PLAN_OPTION_DEFAULTS = {"NODE_FUSED": "0", "ADAPTOR_EARLY": "0", "HEADS_EARLY": "0", "SEG_GATE": "0", "HEADS_MERGED": "0", "PW_CHAIN": "0", "LANES": None, "LANE_WIDE_US": None}
 
 
 def plan_option(model, name: str):
@@ -289,7 +289,13 @@ def plan_option(model, name: str):
     computes the same values up to the fused kernels' accumulation order; only the launch schedule differs.
     HEADS_MERGED=1 lowers the eval-mode Detect / Segment branches of a pyramid level as shared launches (`_Lowering.heads_level_merged`:
     19 -> 9 per level); Segment's box / class chain then has no launches of its own, so SEG_GATE is ignored with it, and HEADS_EARLY marks the
-    shared launches `side` as it does the separate ones.  Not an autotune knob: off unless asked for."""
+    shared launches `side` as it does the separate ones.  Not an autotune knob: off unless asked for.
+    PW_CHAIN=1 lowers two back-to-back 1x1 convolutions on the same pixels as ONE launch (`mtbt_pw_chain_nhwc`, bit-identical to the pair): the
+    BiFPN nodes' `X_conv` + `X_cf.cv1` (launch `X_conv+cf.cv1`; not with NODE_FUSED=1) and the class branches' `cv3[i][1][1]` + `cv3[i][2]`
+    (launch `cv3.i.1.1+2`; not with HEADS_MERGED=1).  16-bit compute dtypes and eval-mode BatchNorms only; a site the library declines
+    (`mtbt_pw_chain_supported`: no kernel for the shape, or a pixel count at which the two launches measured faster -- the 256 -> 256 -> 256
+    form below 16 384 pixels) lowers as the two launches.  PW_CHAIN=2 fuses every site the library has a kernel for, whatever its size
+    (tests, A/B of the pixel-count rule)."""
     v = model.__dict__.get("plan_options", {}).get(name)
     if v is None:
         v = os.environ.get("MTBT_" + name, PLAN_OPTION_DEFAULTS[name])
@@ -370,11 +376,34 @@ class _Lowering:
         self.p.dwconv(x, w, y, 3, scale=self.F(scale), shift=self.F(shift), act=L.ACT_SILU, name=name)
         return y
 
-    def c2f(self, x: Act, mod: C2f, name=""):
-        """Concat-free C2f: every branch writes its channel slice of one [.., (2+n)c] buffer."""
+    def pw_pair(self, x: Act, first, second, y: Act, name) -> bool:
+        """Two chained 1x1 convolutions as ONE launch (plan option PW_CHAIN; pw_chain.hip, bit-identical to the two launches).  first / second:
+        (weights [K, C] fp32, shift fp32 or None, activation).  False -- and nothing recorded -- where the library has no fused kernel for
+        the site: the caller lowers the pair as it always did."""
+        n0 = len(self.p.consts)
+        (w1, s1, a1), (w2, s2, a2) = first, second
+        w1, w2 = self.W(w1), self.W(w2)
+        s1, s2 = (self.F(s1) if s1 is not None else None), (self.F(s2) if s2 is not None else None)
+        a = self.p.pw_chain_args(x, w1, s1, a1, w2, s2, a2, y, any_size=plan_option(self.m, "PW_CHAIN") == "2")
+        if a is None:
+            del self.p.consts[n0:]
+            return False
+        self.p.pw_chain(a, x, w1, s1, w2, s2, y, name=name)
+        return True
+
+    def pw_chain_on(self, *bns) -> bool:
+        """Plan option PW_CHAIN at a site whose BatchNorms are `bns`: 16-bit compute dtype, every BatchNorm folded (eval mode)."""
+        return plan_option(self.m, "PW_CHAIN") in ("1", "2") and self.code in (L.BF16, L.F16) and not any(bn.training for bn in bns)
+
+    def c2f(self, x: Act, mod: C2f, name="", cv1=None):
+        """Concat-free C2f: every branch writes its channel slice of one [.., (2+n)c] buffer.  `cv1(dst)`: issues cv1's output into `dst`
+        itself (a launch fused with the producer of x) instead of `convblock(x, mod.cv1, dst)`; x then only gives the shape."""
         c, n = mod.c, len(mod.m)
         cat = self.p.new(x.N, x.H, x.W, (2 + n) * c, self.code)
-        self.convblock(x, mod.cv1, cat.slice(0, 2 * c), name + ".cv1")
+        if cv1 is not None:
+            cv1(cat.slice(0, 2 * c))
+        else:
+            self.convblock(x, mod.cv1, cat.slice(0, 2 * c), name + ".cv1")
         prev = cat.slice(c, c)
         for i, b in enumerate(mod.m):
             if b.add:
@@ -549,6 +578,20 @@ class _Lowering:
                 else:
                     s = self.p.new(like.N, like.H, like.W, like.C, self.code)
                     self.p.fuse(inputs, [float(v) for v in weights], modes, s, name=f"{nm}.{tag}.fuse")
+                    c1 = cf.cv1.conv
+                    if self.pw_chain_on(conv.bn, cf.cv1.bn) and c1.kernel_size == (1, 1) and K == like.C:
+                        # X_conv (1x1 + BN + ELU) and X_cf.cv1 (1x1 + BN + SiLU) in ONE launch: the tensor between them has this one reader
+                        def cv1(dst):
+                            sc, sh = _bn_fold(cf.cv1.bn, c1.bias)
+                            if self.pw_pair(s, fold_dwblock(conv) + (L.ACT_ELU,), (_krsc(c1.weight).float() * sc[:, None], sh, L.ACT_SILU), dst,
+                                            f"{nm}.{tag}_conv+cf.cv1"):
+                                return
+                            d = self.dw_pointwise(s, conv, f"{nm}.{tag}_conv")
+                            self.convblock(d, cf.cv1, dst, f"{nm}.{tag}_cf.cv1")
+                            self.p.release(d)
+                        o = self.c2f(s, cf, f"{nm}.{tag}_cf", cv1=cv1)
+                        self.p.release(s)
+                        return o
                     d = self.dw_pointwise(s, conv, f"{nm}.{tag}_conv")
                     self.p.release(s)
                 o = self.c2f(d, cf, f"{nm}.{tag}_cf")
@@ -594,6 +637,15 @@ class _Lowering:
         self.p.release(d1)
         d2 = self.dwblock(t1, s[1][0], f"{tag}.cv3.{i}.1.0")
         self.p.release(t1)
+        c1, c2 = s[1][1].conv, s[2]
+        if (self.pw_chain_on(s[1][1].bn) and not self.merged and c1.kernel_size == (1, 1) and c2.kernel_size == (1, 1) and c2.stride == (1, 1)
+                and c2.padding == (0, 0)):
+            # cv3[i][1][1] (1x1 + BN + SiLU) and the output conv (1x1 + bias into the fp32 map) in ONE launch
+            sc, sh = _bn_fold(s[1][1].bn, c1.bias)
+            if self.pw_pair(d2, (_krsc(c1.weight).float() * sc[:, None], sh, L.ACT_SILU), (_krsc(c2.weight), c2.bias, L.ACT_NONE), dst,
+                            f"{tag}.cv3.{i}.1.1+2"):
+                self.p.release(d2)
+                return
         t2 = self.convblock(d2, s[1][1], None, f"{tag}.cv3.{i}.1.1")
         self.p.release(d2)
         self.conv_plain(t2, s[2], dst, f"{tag}.cv3.{i}.2")
