@@ -390,6 +390,70 @@ int mtbt_masks_to_frames(const mtbt_frame_mask_args* a, const mtbt_frame* frames
 int mtbt_sizeof_frame_args(int which);
 
 /* ---------------------------------------------------------------------------------------------
+ * Weighted boxes fusion (Solovyev, Wang, Gabruseva 2021, "avg" confidence with the count correction) of M detection lists of the same
+ * N images: the views of test-time augmentation, the models of an ensemble.  The reference has NO counterpart; this arithmetic is the
+ * project's own definition (tests/fuse_reference.py restates it in numpy).  One launch, one workgroup per image, no host
+ * synchronisation, deterministic; every fp32 operation is a separate correctly rounded one (no FMA contraction), in the order written.
+ * Source m (0 <= m < n_sources = M <= 8) is exactly what mtbt_nms_batched writes, never modified: boxes[m] [N,K,4] xyxy in the img_size
+ * frame of that source's VIEW, scores[m] [N,K], labels[m] int64 [N,K], counts[m] int32 [N], anchors[m] int32 [N,K] or NULL;
+ * orient[m] is the view's code as in mtbt_augment_batch (bit 0 flips x, bit 1 flips y, bit 2 transposes), weight[m] > 0.
+ * N, K are the same for every source, M * K <= 4096.  For image n, S = img_size:
+ *   1. candidates, m ascending then k ascending below min(counts[m][n], K):  s = scores[m][n,k] * weight[m], kept iff s > skip_thr;
+ *      index c = m K + k.  The box is un-oriented as two corner points (the continuous form of the augmentation's pixel rule):
+ *      x <- S - x on both x if bit 0; y <- S - y on both y if bit 1; then x <-> y if bit 2; then each axis re-sorted to (min, max).
+ *   2. order: ascending 64-bit keys ~orderable(s) << 32 | c  (the NMS key: stable descending s, ties to ascending c).
+ *   3. greedy clustering in that order.  For candidate j and every existing cluster of the same label, in ascending cluster index:
+ *      ovr = inter / (area_i + area_j - inter) of the NMS, i = the cluster's current fused box, j = the candidate's box.  The winner is
+ *      the largest ovr (best starts at -inf, a cluster wins iff ovr > best: a NaN never wins, ties stay with the lowest index).
+ *      best > iou_thr: j JOINS the winner:  Ss += s;  Sx1 += s * x1 (multiply, then add; the same for y1, x2, y2);  n += 1;
+ *                      fused = (Sx1 / Ss, Sy1 / Ss, Sx2 / Ss, Sy2 / Ss).
+ *      otherwise j OPENS the next cluster:  Ss = s;  Sx1 = s * x1, ...;  n = 1;  fused = the box itself (copied, not divided);
+ *                      label = j's label;  lead = c  (the leader is the highest-scoring member).  No cap on the clusters below M K.
+ *   4. cluster score = ((Ss / (float)n) * (float)min(n, M)) / W,  W = weight[0] + weight[1] + ... (m ascending, fp32).  Members of
+ *      one source may share a cluster, hence the min.
+ *   5. output order: ascending keys ~orderable(score) << 32 | cluster index (stable descending score); the first top_k, row stride
+ *      top_k:  out_boxes [N,top_k,4] (fused), out_scores, out_labels (int64), n_members (n), lead_source = lead / K, lead_slot =
+ *      lead % K, lead_anchor = anchors[lead_source][n, lead_slot] (optional: NULL, and it must be NULL when any anchors[m] is NULL);
+ *      out_counts[n] = min(#clusters, top_k), n_clusters[n] = #clusters before the cut.  Padded slots as mtbt_nms_batched pads:
+ *      boxes and scores 0, labels -1; lead_source / lead_slot / lead_anchor -1; n_members 0.
+ * workspace: >= mtbt_fuse_workspace_bytes(M, N, K) bytes, 16-byte aligned (0 is returned for arguments the launch would refuse).
+ * Order of the checks: MTBT_EINVAL before any launch for NULL a, M outside 1..8, N < 0, K < 1, M K > 4096, top_k < 1, img_size not > 0,
+ * an orient outside 0..7, a weight not > 0 (NaN included); then N == 0 is MTBT_OK with nothing launched; then MTBT_EINVAL for a NULL
+ * required pointer (every source array but anchors, every output but lead_anchor, workspace), lead_anchor without every anchors[m], a
+ * workspace that is too small; then MTBT_EALIGN for boxes[m] / out_boxes / workspace not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define MTBT_FUSE_MAX_SOURCES 8
+#define MTBT_FUSE_MAX_CANDIDATES 4096
+typedef struct mtbt_box_fuse_args {
+  const float* boxes[MTBT_FUSE_MAX_SOURCES];
+  const float* scores[MTBT_FUSE_MAX_SOURCES];
+  const int64_t* labels[MTBT_FUSE_MAX_SOURCES];
+  const int32_t* counts[MTBT_FUSE_MAX_SOURCES];
+  const int32_t* anchors[MTBT_FUSE_MAX_SOURCES]; /* each [N,K] or NULL */
+  int32_t orient[MTBT_FUSE_MAX_SOURCES];
+  float weight[MTBT_FUSE_MAX_SOURCES];
+  int32_t n_sources, N, K, top_k;
+  float img_size, iou_thr, skip_thr;
+  int32_t reserved;
+  float* out_boxes;
+  float* out_scores;
+  int64_t* out_labels;
+  int32_t* out_counts;
+  int32_t* n_clusters;
+  int32_t* n_members;
+  int32_t* lead_source;
+  int32_t* lead_slot;
+  int32_t* lead_anchor; /* [N,top_k] or NULL */
+  void* workspace;
+  int64_t workspace_bytes;
+} mtbt_box_fuse_args;
+
+int64_t mtbt_fuse_workspace_bytes(int n_sources, int N, int K);
+int mtbt_fuse_detections(const mtbt_box_fuse_args* a, void* stream);
+/* sizeof(mtbt_box_fuse_args) as the library was compiled (mtbt_fuse_args is the BiFPN fusion node's struct, above) */
+int mtbt_sizeof_box_fuse_args(void);
+
+/* ---------------------------------------------------------------------------------------------
  * Multitask loss VALUE (forward only), MultiTaskLitModel._multitask_loss, running_main_v3.py:232-387:
  *   per (image, anchor): trainer decode (:268-290), IoU against the image's GT boxes (:316), positives = max IoU >
  *   iou_thresh (:319-321), sum(1 - IoU) (:331), BCE-with-logits(sum) of the class logits against one-hot /

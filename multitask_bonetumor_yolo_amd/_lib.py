@@ -167,6 +167,16 @@ class TalLossArgs(C.Structure):  # mtbt_tal_loss_args
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("out", C.c_void_p)]
 
 
+class BoxFuseArgs(C.Structure):  # mtbt_box_fuse_args (FuseArgs / mtbt_fuse_args is the BiFPN fusion node's)
+    _fields_ = [("boxes", C.c_void_p * 8), ("scores", C.c_void_p * 8), ("labels", C.c_void_p * 8), ("counts", C.c_void_p * 8),
+                ("anchors", C.c_void_p * 8), ("orient", C.c_int32 * 8), ("weight", C.c_float * 8),
+                ("n_sources", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("top_k", C.c_int32),
+                ("img_size", C.c_float), ("iou_thr", C.c_float), ("skip_thr", C.c_float), ("reserved", C.c_int32),
+                ("out_boxes", C.c_void_p), ("out_scores", C.c_void_p), ("out_labels", C.c_void_p), ("out_counts", C.c_void_p),
+                ("n_clusters", C.c_void_p), ("n_members", C.c_void_p), ("lead_source", C.c_void_p), ("lead_slot", C.c_void_p),
+                ("lead_anchor", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -285,6 +295,9 @@ SYMBOLS = {
     "mtbt_tal_loss_workspace_bytes": (C.c_int64, [C.c_int] * 3),
     "mtbt_tal_det_loss": (C.c_int, [C.POINTER(TalLossArgs), C.c_void_p]),
     "mtbt_sizeof_tal_loss_args": (C.c_int, []),
+    "mtbt_fuse_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mtbt_fuse_detections": (C.c_int, [C.POINTER(BoxFuseArgs), C.c_void_p]),
+    "mtbt_sizeof_box_fuse_args": (C.c_int, []),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -317,7 +330,7 @@ def load():
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "
                                        f"out in {C.sizeof(st)} bytes: stale library, rebuild")
         for sizeof, st in ((lib.mtbt_sizeof_mask_loss_args, MaskLossArgs), (lib.mtbt_sizeof_tal_loss_args, TalLossArgs),
-                           (lib.mtbt_sizeof_pw_chain_args, PwChainArgs)):
+                           (lib.mtbt_sizeof_pw_chain_args, PwChainArgs), (lib.mtbt_sizeof_box_fuse_args, BoxFuseArgs)):
             if sizeof() != C.sizeof(st):
                 raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof()}, this binding lays it "
                                    f"out in {C.sizeof(st)} bytes: stale library, rebuild")

@@ -1,0 +1,305 @@
+// Weighted box fusion of several detection lists of the same images (test-time augmentation views, model ensembles):
+// mtbt_fuse_detections.  The arithmetic is the project's own definition (include/mtbt_hip.h; tests/fuse_reference.py restates it in
+// numpy) and the results are bit-exact restatements of it: no FMA contraction, IEEE division, stable ordering, no floating-point atomics.
+#include "common.h"
+
+// No FMA contraction in this file (built with -ffp-contract=off, see build.py), as in postprocess.hip.
+
+namespace {
+
+constexpr int FUSE_NT = 256;               // one workgroup per image
+constexpr int FUSE_LDS_BUDGET = 144 * 1024; // dynamic LDS this kernel ever asks for (160 KiB per CU less the static part)
+
+struct FuseP {
+  const float* boxes[MTBT_FUSE_MAX_SOURCES];
+  const float* scores[MTBT_FUSE_MAX_SOURCES];
+  const long long* labels[MTBT_FUSE_MAX_SOURCES];
+  const int* counts[MTBT_FUSE_MAX_SOURCES];
+  const int* anchors[MTBT_FUSE_MAX_SOURCES];
+  float weight[MTBT_FUSE_MAX_SOURCES];
+  int orient[MTBT_FUSE_MAX_SOURCES];
+  int M, K, top_k, C, P2, acc_in_lds;
+  float S, iou_thr, skip_thr, wsum;
+  float* out_boxes;
+  float* out_scores;
+  long long* out_labels;
+  int* out_counts;
+  int* n_clusters;
+  int* n_members;
+  int* lead_source;
+  int* lead_slot;
+  int* lead_anchor;
+  char* ws;
+  long ws_per_image;
+};
+
+// running sums of one cluster: touched by lane 0 of wave 0 only while the greedy pass runs
+struct Acc {
+  float ss, x1, y1, x2, y2;
+  int n, lead, pad;
+};
+
+__device__ __forceinline__ unsigned orderable(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// iou_gt's arithmetic of postprocess.hip (torchvision nms_kernel.cpp), i = the cluster's fused box, j = the candidate
+__device__ __forceinline__ float overlap(const float4 bi, const float4 bj) {
+  const float iarea = __fmul_rn(__fsub_rn(bi.z, bi.x), __fsub_rn(bi.w, bi.y));
+  const float jarea = __fmul_rn(__fsub_rn(bj.z, bj.x), __fsub_rn(bj.w, bj.y));
+  const float xx1 = fmaxf(bi.x, bj.x), yy1 = fmaxf(bi.y, bj.y);
+  const float xx2 = fminf(bi.z, bj.z), yy2 = fminf(bi.w, bj.w);
+  const float w = fmaxf(0.f, __fsub_rn(xx2, xx1)), h = fmaxf(0.f, __fsub_rn(yy2, yy1));
+  const float inter = __fmul_rn(w, h);
+  return __fdiv_rn(inter, __fsub_rn(__fadd_rn(iarea, jarea), inter));
+}
+
+// ascending bitonic sort of keys[0, P), P a power of two, whole workgroup
+__device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int P, int tid) {
+  for (int k = 2; k <= P; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (P >> 1); t += FUSE_NT) {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+        const int hi = lo | j;
+        const bool up = (lo & k) == 0;
+        const unsigned long long x = keys[lo], y = keys[hi];
+        if ((x > y) == up) { keys[lo] = y; keys[hi] = x; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__device__ __forceinline__ float cluster_score(const Acc& a, int M, float wsum) {
+  return __fdiv_rn(__fmul_rn(__fdiv_rn(a.ss, (float)a.n), (float)min(a.n, M)), wsum);
+}
+
+// One 256-thread workgroup per image.
+//  1. candidates: key[c] = ~orderable(s) << 32 | c for every kept (m, k), c = m K + k; bitonic sort == stable descending s, ascending c
+//  2. the sorted candidates (un-oriented box, s, label, c) go to the workspace
+//  3. greedy clustering by wave 0: 64 sorted candidates per step live in registers (lane = candidate) and are broadcast one at a time;
+//     each lane scans clusters lane, lane + 64, ... in LDS, a butterfly (value, index) arg-max picks the winner, lane 0 applies the update.
+//     No workgroup barrier inside the loop: LDS operations of one wave complete in order, the fence keeps the compiler from moving them.
+//  4. cluster scores -> keys, bitonic sort, write-out by the whole workgroup
+__global__ __launch_bounds__(FUSE_NT) void fuse_kernel(const FuseP p) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  __shared__ int s_cnt, s_ncl;
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int C = p.C, K = p.K, M = p.M;
+  // LDS: fused boxes [C] | cluster labels [C] | keys [P2] | (running sums [C])
+  float4* fused = reinterpret_cast<float4*>(smem);
+  long long* clabel = reinterpret_cast<long long*>(smem + (long)C * 16);
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(smem + (long)C * 24);
+  // workspace: sorted candidate boxes [C] | labels [C] | scores [C] | indices [C] | (running sums [C])
+  char* wsi = p.ws + (long)n * p.ws_per_image;
+  float4* cbox = reinterpret_cast<float4*>(wsi);
+  long long* clab = reinterpret_cast<long long*>(wsi + (long)C * 16);
+  float* cs = reinterpret_cast<float*>(wsi + (long)C * 24);
+  int* cc = reinterpret_cast<int*>(wsi + (long)C * 28);
+  Acc* acc = p.acc_in_lds ? reinterpret_cast<Acc*>(smem + (long)C * 24 + (long)p.P2 * 8) : reinterpret_cast<Acc*>(wsi + (long)C * 32);
+
+  // ---- 1. keys of the candidates ----
+  if (tid == 0) { s_cnt = 0; s_ncl = 0; }
+  __syncthreads();
+  int mine = 0;
+  for (int c = tid; c < p.P2; c += FUSE_NT) {
+    unsigned long long key = ~0ull;
+    if (c < C) {
+      const int m = c / K, k = c - m * K;
+      if (k < min(p.counts[m][n], K)) {
+        const float s = __fmul_rn(p.scores[m][(long)n * K + k], p.weight[m]);
+        if (s > p.skip_thr) { key = ((unsigned long long)(~orderable(s)) << 32) | (unsigned)c; ++mine; }
+      }
+    }
+    keys[c] = key;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+  if (lane == 0 && mine) atomicAdd(&s_cnt, mine);
+  __syncthreads();
+  const int nc = s_cnt;
+  bitonic_sort(keys, p.P2, tid);   // (the dropped slots carry the largest key: the nc candidates come first)
+
+  // ---- 2. sorted candidates, un-oriented ----
+  for (int i = tid; i < nc; i += FUSE_NT) {
+    const int c = (int)(keys[i] & 0xffffffffu);
+    const int m = c / K, k = c - m * K;
+    const long at = (long)n * K + k;
+    float4 b = reinterpret_cast<const float4*>(p.boxes[m])[at];
+    const int o = p.orient[m];
+    if (o & 1) { b.x = __fsub_rn(p.S, b.x); b.z = __fsub_rn(p.S, b.z); }
+    if (o & 2) { b.y = __fsub_rn(p.S, b.y); b.w = __fsub_rn(p.S, b.w); }
+    if (o & 4) { float t = b.x; b.x = b.y; b.y = t; t = b.z; b.z = b.w; b.w = t; }
+    float4 r;
+    r.x = fminf(b.x, b.z); r.z = fmaxf(b.x, b.z); r.y = fminf(b.y, b.w); r.w = fmaxf(b.y, b.w);
+    cbox[i] = r;
+    clab[i] = p.labels[m][at];
+    cs[i] = __fmul_rn(p.scores[m][at], p.weight[m]);
+    cc[i] = c;
+  }
+  __threadfence_block();
+  __syncthreads();
+
+  // ---- 3. greedy clustering, wave 0 ----
+  if (wave == 0) {
+    int ncl = 0;
+    for (int j0 = 0; j0 < nc; j0 += 64) {
+      const int j = min(j0 + lane, nc - 1);
+      const float4 mb = cbox[j];
+      const float ms = cs[j];
+      const long long ml = clab[j];
+      const int mc = cc[j];
+      const int steps = min(64, nc - j0);
+      for (int t = 0; t < steps; ++t) {
+        float4 bj;
+        bj.x = __shfl(mb.x, t, 64); bj.y = __shfl(mb.y, t, 64); bj.z = __shfl(mb.z, t, 64); bj.w = __shfl(mb.w, t, 64);
+        const float s = __shfl(ms, t, 64);
+        const long long lab = ((long long)__shfl((int)(ml >> 32), t, 64) << 32) | (unsigned)__shfl((int)ml, t, 64);
+        const int c = __shfl(mc, t, 64);
+        float best = -INFINITY;
+        int bi = 0x7fffffff;
+        for (int k = lane; k < ncl; k += 64) {
+          if (clabel[k] == lab) {
+            const float ovr = overlap(fused[k], bj);
+            if (ovr > best) { best = ovr; bi = k; }          // (a NaN never wins; ascending k: ties stay with the lowest index)
+          }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const float ob = __shfl_xor(best, o, 64);
+          const int oi = __shfl_xor(bi, o, 64);
+          if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+        }
+        const bool join = best > p.iou_thr;                   // (uniform: every lane holds the same winner)
+        if (lane == 0) {
+          if (join) {
+            Acc a = acc[bi];
+            a.ss = __fadd_rn(a.ss, s);
+            a.x1 = __fadd_rn(a.x1, __fmul_rn(s, bj.x)); a.y1 = __fadd_rn(a.y1, __fmul_rn(s, bj.y));
+            a.x2 = __fadd_rn(a.x2, __fmul_rn(s, bj.z)); a.y2 = __fadd_rn(a.y2, __fmul_rn(s, bj.w));
+            a.n += 1;
+            acc[bi] = a;
+            fused[bi] = make_float4(__fdiv_rn(a.x1, a.ss), __fdiv_rn(a.y1, a.ss), __fdiv_rn(a.x2, a.ss), __fdiv_rn(a.y2, a.ss));
+          } else {
+            Acc a;
+            a.ss = s;
+            a.x1 = __fmul_rn(s, bj.x); a.y1 = __fmul_rn(s, bj.y); a.x2 = __fmul_rn(s, bj.z); a.y2 = __fmul_rn(s, bj.w);
+            a.n = 1; a.lead = c; a.pad = 0;
+            acc[ncl] = a;
+            fused[ncl] = bj;
+            clabel[ncl] = lab;
+          }
+        }
+        if (!join) ++ncl;
+        __threadfence_block();                                // the update is in LDS before the next candidate's scan reads it
+        __builtin_amdgcn_wave_barrier();
+      }
+    }
+    if (lane == 0) s_ncl = ncl;
+  }
+  __threadfence_block();
+  __syncthreads();
+
+  // ---- 4. cluster order and write-out ----
+  const int ncl = s_ncl;
+  int Pc = 1;
+  while (Pc < ncl) Pc <<= 1;
+  for (int i = tid; i < Pc; i += FUSE_NT)
+    keys[i] = i < ncl ? ((unsigned long long)(~orderable(cluster_score(acc[i], M, p.wsum))) << 32) | (unsigned)i : ~0ull;
+  __syncthreads();
+  bitonic_sort(keys, Pc, tid);
+  const int top_k = p.top_k, nout = min(ncl, top_k);
+  const long row = (long)n * top_k;
+  for (int r = tid; r < top_k; r += FUSE_NT) {
+    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+    float sc = 0.f;
+    long long lab = -1;
+    int nm = 0, ls = -1, lk = -1, la = -1;
+    if (r < nout) {
+      const int i = (int)(keys[r] & 0xffffffffu);
+      const Acc a = acc[i];
+      b = fused[i];
+      sc = cluster_score(a, M, p.wsum);
+      lab = clabel[i];
+      nm = a.n;
+      ls = a.lead / K;
+      lk = a.lead - ls * K;
+      if (p.lead_anchor) la = p.anchors[ls][(long)n * K + lk];
+    }
+    reinterpret_cast<float4*>(p.out_boxes)[row + r] = b;
+    p.out_scores[row + r] = sc;
+    p.out_labels[row + r] = lab;
+    p.n_members[row + r] = nm;
+    p.lead_source[row + r] = ls;
+    p.lead_slot[row + r] = lk;
+    if (p.lead_anchor) p.lead_anchor[row + r] = la;
+  }
+  if (tid == 0) { p.out_counts[n] = nout; p.n_clusters[n] = ncl; }
+}
+
+inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+inline long fuse_ws_per_image(int C) { return ((long)C * 64 + 255) / 256 * 256; }
+
+}  // namespace
+
+extern "C" int64_t mtbt_fuse_workspace_bytes(int n_sources, int N, int K) {
+  if (n_sources < 1 || n_sources > MTBT_FUSE_MAX_SOURCES || N <= 0 || K <= 0 || (long)n_sources * K > MTBT_FUSE_MAX_CANDIDATES) return 0;
+  return (int64_t)N * fuse_ws_per_image(n_sources * K);
+}
+
+extern "C" int mtbt_sizeof_box_fuse_args(void) { return (int)sizeof(mtbt_box_fuse_args); }
+
+extern "C" int mtbt_fuse_detections(const mtbt_box_fuse_args* a, void* stream) {
+  if (!a) return MTBT_EINVAL;
+  const int M = a->n_sources;
+  if (M < 1 || M > MTBT_FUSE_MAX_SOURCES || a->N < 0 || a->K < 1 || (long)M * a->K > MTBT_FUSE_MAX_CANDIDATES || a->top_k < 1) return MTBT_EINVAL;
+  if (!(a->img_size > 0.f)) return MTBT_EINVAL;
+  float wsum = 0.f;
+  for (int m = 0; m < M; ++m) {
+    if (a->orient[m] < 0 || a->orient[m] > 7 || !(a->weight[m] > 0.f)) return MTBT_EINVAL;
+    wsum = m ? wsum + a->weight[m] : a->weight[m];
+  }
+  if (a->N == 0) return MTBT_OK;
+  bool all_anchors = true;
+  for (int m = 0; m < M; ++m) {
+    if (!a->boxes[m] || !a->scores[m] || !a->labels[m] || !a->counts[m]) return MTBT_EINVAL;
+    if (!a->anchors[m]) all_anchors = false;
+  }
+  if (!a->out_boxes || !a->out_scores || !a->out_labels || !a->out_counts || !a->n_clusters || !a->n_members || !a->lead_source ||
+      !a->lead_slot || !a->workspace)
+    return MTBT_EINVAL;
+  if (a->lead_anchor && !all_anchors) return MTBT_EINVAL;
+  const int C = M * a->K;
+  const long per = fuse_ws_per_image(C);
+  if (a->workspace_bytes < (int64_t)a->N * per) return MTBT_EINVAL;
+  for (int m = 0; m < M; ++m)
+    if (!aligned16(a->boxes[m])) return MTBT_EALIGN;
+  if (!aligned16(a->out_boxes) || !aligned16(a->workspace)) return MTBT_EALIGN;
+
+  FuseP p;
+  for (int m = 0; m < MTBT_FUSE_MAX_SOURCES; ++m) {
+    const bool on = m < M;
+    p.boxes[m] = on ? a->boxes[m] : nullptr;
+    p.scores[m] = on ? a->scores[m] : nullptr;
+    p.labels[m] = on ? reinterpret_cast<const long long*>(a->labels[m]) : nullptr;
+    p.counts[m] = on ? a->counts[m] : nullptr;
+    p.anchors[m] = on ? a->anchors[m] : nullptr;
+    p.weight[m] = on ? a->weight[m] : 0.f;
+    p.orient[m] = on ? a->orient[m] : 0;
+  }
+  p.M = M; p.K = a->K; p.top_k = a->top_k; p.C = C; p.P2 = pow2ceil(C);
+  const long lds_small = (long)C * 24 + (long)p.P2 * 8, lds_acc = lds_small + (long)C * (long)sizeof(Acc);
+  p.acc_in_lds = lds_acc <= FUSE_LDS_BUDGET ? 1 : 0;
+  p.S = a->img_size; p.iou_thr = a->iou_thr; p.skip_thr = a->skip_thr; p.wsum = wsum;
+  p.out_boxes = a->out_boxes; p.out_scores = a->out_scores; p.out_labels = reinterpret_cast<long long*>(a->out_labels);
+  p.out_counts = a->out_counts; p.n_clusters = a->n_clusters; p.n_members = a->n_members;
+  p.lead_source = a->lead_source; p.lead_slot = a->lead_slot; p.lead_anchor = a->lead_anchor;
+  p.ws = reinterpret_cast<char*>(a->workspace); p.ws_per_image = per;
+  const size_t lds = (size_t)(p.acc_in_lds ? lds_acc : lds_small);
+  // one-time (per device) opt-in to the LARGEST dynamic LDS this kernel ever asks for
+  if (int rc = mtbt_allow_lds(fuse_kernel, FUSE_LDS_BUDGET)) return rc;
+  hipLaunchKernelGGL(fuse_kernel, dim3(a->N), dim3(FUSE_NT), lds, reinterpret_cast<hipStream_t>(stream), p);
+  MTBT_LAUNCH_CHECK();
+  return MTBT_OK;
+}

@@ -344,3 +344,114 @@ def detect_and_segment(det_maps: List[torch.Tensor], mc: torch.Tensor, protos: t
     elif masks:
         out["masks"], _ = assemble_masks(protos, mc, k["keep_anchor"], k["counts"], (img_size, img_size))
     return out
+
+
+FUSE_MAX_SOURCES, FUSE_MAX_CANDIDATES = 8, 4096   # include/mtbt_hip.h MTBT_FUSE_MAX_SOURCES / MTBT_FUSE_MAX_CANDIDATES
+
+
+def _fuse_args(dets, img_size, orients, weights, iou_thr, skip_thr, top_k):
+    """The checked `mtbt_box_fuse_args` of a `fuse_detections` call, its output dict (which keeps every tensor the struct points to
+    alive under "_keep") and the device."""
+    lib = L.load()
+    dets = list(dets)
+    M = len(dets)
+    if not 1 <= M <= FUSE_MAX_SOURCES:
+        raise ValueError(f"fuse_detections: {M} sources (1..{FUSE_MAX_SOURCES})")
+    for d in dets:
+        for key in ("boxes", "scores", "labels", "counts"):
+            _need_cuda(d[key], "fuse_detections")
+    B, K = dets[0]["scores"].shape
+    dev = dets[0]["scores"].device
+    for m, d in enumerate(dets):
+        if tuple(d["scores"].shape) != (B, K) or tuple(d["boxes"].shape) != (B, K, 4) or tuple(d["labels"].shape) != (B, K) or tuple(d["counts"].shape) != (B,):
+            raise ValueError(f"fuse_detections: source {m} has boxes {tuple(d['boxes'].shape)}, scores {tuple(d['scores'].shape)}, counts "
+                             f"{tuple(d['counts'].shape)}; source 0 has B = {B}, K = {K}")
+    if K < 1 or M * K > FUSE_MAX_CANDIDATES:
+        raise ValueError(f"fuse_detections: {M} sources of K = {K} slots ({FUSE_MAX_CANDIDATES} slots at most, K >= 1)")
+    orients = [0] * M if orients is None else [int(o) for o in orients]
+    weights = [1.0] * M if weights is None else [float(w) for w in weights]
+    if len(orients) != M or len(weights) != M:
+        raise ValueError(f"fuse_detections: {len(orients)} orients and {len(weights)} weights for {M} sources")
+    top_k = K if top_k is None else int(top_k)
+    with_anchor = all("keep_anchor" in d for d in dets)
+    a = L.BoxFuseArgs()
+    keep = []
+    for m, d in enumerate(dets):
+        src = [d["boxes"].contiguous().float(), d["scores"].contiguous().float(), d["labels"].contiguous().to(torch.int64),
+               d["counts"].contiguous().to(torch.int32)]
+        if with_anchor:
+            src.append(d["keep_anchor"].contiguous().to(torch.int32))
+            a.anchors[m] = src[4].data_ptr()
+        a.boxes[m], a.scores[m], a.labels[m], a.counts[m] = (t.data_ptr() for t in src[:4])
+        a.orient[m], a.weight[m] = orients[m], weights[m]
+        keep.append(src)
+    o = {
+        "boxes": torch.empty((B, top_k, 4), dtype=torch.float32, device=dev),
+        "scores": torch.empty((B, top_k), dtype=torch.float32, device=dev),
+        "labels": torch.empty((B, top_k), dtype=torch.int64, device=dev),
+        "counts": torch.empty((B,), dtype=torch.int32, device=dev),
+        "n_clusters": torch.empty((B,), dtype=torch.int32, device=dev),
+        "n_members": torch.empty((B, top_k), dtype=torch.int32, device=dev),
+        "lead_source": torch.empty((B, top_k), dtype=torch.int32, device=dev),
+        "lead_slot": torch.empty((B, top_k), dtype=torch.int32, device=dev),
+    }
+    if with_anchor:
+        o["lead_anchor"] = torch.empty((B, top_k), dtype=torch.int32, device=dev)
+        a.lead_anchor = o["lead_anchor"].data_ptr()
+    wsb = lib.mtbt_fuse_workspace_bytes(M, B, K)
+    ws = torch.empty((max(wsb, 16),), dtype=torch.uint8, device=dev)
+    a.n_sources, a.N, a.K, a.top_k = M, B, K, top_k
+    a.img_size, a.iou_thr, a.skip_thr = float(img_size), float(iou_thr), float(skip_thr)
+    a.out_boxes, a.out_scores, a.out_labels, a.out_counts = o["boxes"].data_ptr(), o["scores"].data_ptr(), o["labels"].data_ptr(), o["counts"].data_ptr()
+    a.n_clusters, a.n_members, a.lead_source, a.lead_slot = (o[k].data_ptr() for k in ("n_clusters", "n_members", "lead_source", "lead_slot"))
+    a.workspace, a.workspace_bytes = ws.data_ptr(), wsb
+    o["_keep"] = (keep, ws)
+    return a, o, dev
+
+
+def fuse_detections(dets: Sequence[dict], *, img_size: float, orients: Optional[Sequence[int]] = None,
+                    weights: Optional[Sequence[float]] = None, iou_thr: float = 0.55, skip_thr: float = 0.0, top_k: Optional[int] = None):
+    """Weighted boxes fusion (`mtbt_fuse_detections`) of several detection lists of the same batch: the views of test-time
+    augmentation, the models of an ensemble.  One launch, no host synchronisation, deterministic.
+
+    `dets`: 1..8 result dicts of `nms_batched` / `detect_and_segment` (boxes [B,K,4], scores, labels, counts; the same B and K, at most
+    4096 slots together).  `orients[m]`: the dihedral code of the view source m saw (`orient_batch`; bit 0 flips x, bit 1 flips y, bit 2
+    transposes; default 0), its boxes are turned back to the upright `img_size` frame.  `weights[m]` > 0 scales its scores (default 1).
+    Candidates with score * weight <= skip_thr are dropped; a candidate joins the same-label cluster whose fused box it overlaps most when
+    that IoU > iou_thr, else it opens a cluster; a cluster's box is the score-weighted mean of its members and its score
+    mean(member scores) * min(members, sources) / sum(weights).  `top_k` defaults to K.
+
+    Returns dict(boxes [B,top_k,4], scores, labels int64, counts int32 [B] -- what `update_batched` and the mask-mAP classes read --,
+    n_clusters int32 [B] (before the cut), n_members int32 [B,top_k], lead_source / lead_slot int32 [B,top_k] (source and slot of each
+    cluster's highest-scoring member, -1 padded) and, when every input has `keep_anchor`, lead_anchor int32 [B,top_k])."""
+    a, o, dev = _fuse_args(dets, img_size, orients, weights, iou_thr, skip_thr, top_k)
+    with torch.cuda.device(dev):
+        L.check(L.load().mtbt_fuse_detections(C.byref(a), _stream(dev)), "mtbt_fuse_detections")
+    return o
+
+
+def _square(x: torch.Tensor, orient: int, what: str):
+    if x.dim() != 4 or x.shape[2] != x.shape[3]:
+        raise ValueError(f"{what}: expected [B, C, S, S] (square views only), got {tuple(x.shape)}")
+    if not 0 <= int(orient) <= 7:
+        raise ValueError(f"{what}: orient {orient} outside 0..7")
+
+
+def orient_batch(x: torch.Tensor, orient: int) -> torch.Tensor:
+    """The view Q of a [B, C, S, S] batch under one of the eight dihedral codes, by the pixel rule of `mtbt_augment_batch`:
+    Q = flips(transpose(x)) -- the last two dimensions transposed if bit 2 is set, then x flipped if bit 0, then y flipped if bit 1.
+    Plain torch indexing (not a hot path)."""
+    _square(x, orient, "orient_batch")
+    q = x.transpose(2, 3) if orient & 4 else x
+    dims = [d for bit, d in ((1, 3), (2, 2)) if orient & bit]
+    if dims:
+        q = q.flip(dims)
+    return q.contiguous()
+
+
+def unorient_batch(q: torch.Tensor, orient: int) -> torch.Tensor:
+    """The inverse of `orient_batch`, e.g. for dense [B, K, S, S] masks of a view: the flips undone, then the transpose."""
+    _square(q, orient, "unorient_batch")
+    dims = [d for bit, d in ((1, 3), (2, 2)) if orient & bit]
+    x = q.flip(dims) if dims else q
+    return (x.transpose(2, 3) if orient & 4 else x).contiguous()

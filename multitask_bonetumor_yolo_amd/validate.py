@@ -20,7 +20,8 @@ import torch.nn as nn
 from .loss import instance_mask_loss, multitask_loss, task_aligned_det_loss
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision, ImageClassificationMetrics,
                       SegmentationMetrics, _sum_over_ranks)
-from .postprocess import CONF_TH, NMS_IOU, TOP_K, decode_boxes, masks_to_frames, nms_batched, pack_masks, proto_projector_logits
+from .postprocess import (CONF_TH, NMS_IOU, TOP_K, decode_boxes, fuse_detections, masks_to_frames, nms_batched, orient_batch, pack_masks,
+                          proto_projector_logits)
 
 LOSS_NAMES = ("total", "seg", "box_iou", "dfl", "det_cls", "img_cls")       # running_main_v3.py:578-582
 MASK_LOSS_NAME = "mask"                                                      # appended with instance_mask_weight > 0
@@ -58,7 +59,7 @@ class ValidationStep:
                  label_smoothing: float = 0.1, loss_weights=(1.0, 2.0, 1.5, 0.5, 1.0), conf_th: float = CONF_TH, nms_iou: float = NMS_IOU,
                  top_k: int = TOP_K, map_max_detections: int = 100, dist_sync: bool = True, process_group=None,
                  instance_masks: bool = False, mask_crop: bool = True, det_loss: str = "reference", tal=None,
-                 instance_mask_weight: float = 0.0, mask_assign: str = "iou"):
+                 instance_mask_weight: float = 0.0, mask_assign: str = "iou", views: Optional[Sequence[int]] = None, wbf_iou: float = 0.55):
         """`projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1), running_main_v3.py:186); created with torch's default
         init when not given.  The loss hyper-parameters default to the reference's (and TrainStep's); `label_smoothing` is accepted for
         symmetry with TrainStep but the eval-mode loss never smooths (:337).  conf_th / nms_iou / top_k: `:54-56`;
@@ -72,7 +73,21 @@ class ValidationStep:
         `loss_weights` slots; seg and img_cls still come from the eval-mode `multitask_loss` with detection weights 0.
         `instance_mask_weight` > 0: the total includes `weight * mask_loss`, the tuple gains mask_loss and its positive count (8 elements)
         and `compute()` gains `val_epoch/loss_mask`; `mask_assign="tal"` takes its positives from the task-aligned assignment.  No
-        gradient is computed.  The detection confusion matrix keeps the reference's matching.  At the defaults nothing changes."""
+        gradient is computed.  The detection confusion matrix keeps the reference's matching.  At the defaults nothing changes.
+        `views` (orient codes 0..7 of `orient_batch`, at most 8): test-time augmentation of the BOX mAP only.  map_iou50 / map_iou50_95
+        are updated from the weighted-boxes fusion (`fuse_detections`, IoU `wbf_iou`) of one detection list per view: view 0 is the
+        step's own identity pass (the same maps the losses see), every other view one more forward of the oriented batch with the whole
+        module in eval mode (`model(x, "infer")`), decoded and filtered like the identity pass.  The losses, the confusion matrices and
+        the segmentation metrics stay on the identity pass, and `compute()` keeps its keys.  Not with `instance_masks` (fused instance
+        masks: `detect_fused(masks=True)`).  `views=None`: not one launch changes."""
+        self.views = None if views is None else tuple(int(v) for v in views)
+        self.wbf_iou = float(wbf_iou)
+        if self.views is not None:
+            if instance_masks:
+                raise NotImplementedError("ValidationStep: views with instance_masks=True is not implemented; fused instance masks come from "
+                                          "detect_fused(masks=True)")
+            if not 1 <= len(self.views) <= 8 or any(not 0 <= v <= 7 for v in self.views):
+                raise ValueError(f"views: 1..8 orient codes in 0..7, not {views!r}")
         if det_loss not in ("reference", "tal"):
             raise ValueError(f"det_loss: 'reference' (the reference trainer's _multitask_loss) or 'tal' (task-aligned), not {det_loss!r}")
         self.det_loss = det_loss
@@ -166,11 +181,28 @@ class ValidationStep:
         self.det_cm.update(det, det_gt)
         d = decode_boxes(det, self.S, reg_max=self.reg_max, want_scores=False)
         k = nms_batched(d["boxes"], d["best_score"], d["best_label"], float(self.S), **self.nms_kw)
+        if self.views is not None:
+            k = fuse_detections([k if v == 0 else self._view_detections(imgs, v) for v in self.views], img_size=self.S, orients=self.views,
+                                iou_thr=self.wbf_iou, top_k=self.nms_kw["top_k"])
         self.map50.update_batched(k, det_gt, self.S)
         self.map50_95.update_batched(k, det_gt, self.S)
         if self.instance_masks:
             self._mask_update(seg_out[1], protos, k, det_gt, masks_gt)
         return losses
+
+    def _view_detections(self, imgs, view: int):
+        """The detection list of one more view: `model(orient_batch(imgs, view), "infer")` with every module in eval mode (flags restored
+        afterwards), decoded and filtered like the identity pass.  Boxes in the view's frame: `fuse_detections` turns them back."""
+        flags = [(mod, mod.training) for mod in self.m.modules()]
+        self.m.eval()
+        try:
+            with torch.no_grad():
+                det = self.m(orient_batch(imgs, view), "infer")["detect_features"]
+        finally:
+            for mod, f in flags:
+                mod.training = f
+        d = decode_boxes(det, self.S, reg_max=self.reg_max, want_scores=False)
+        return nms_batched(d["boxes"], d["best_score"], d["best_label"], float(self.S), **self.nms_kw)
 
     def _mask_update(self, mc, protos, k, det_gt, masks_gt):
         """The instance-mask mAP's share of a step: detections' masks and per-box ground truth as packed S x S planes, one pair-count
