@@ -452,6 +452,60 @@ int64_t mtbt_fuse_workspace_bytes(int n_sources, int N, int K);
 int mtbt_fuse_detections(const mtbt_box_fuse_args* a, void* stream);
 /* sizeof(mtbt_box_fuse_args) as the library was compiled (mtbt_fuse_args is the BiFPN fusion node's struct, above) */
 int mtbt_sizeof_box_fuse_args(void);
+/* mtbt_fuse_detections plus the MEMBERSHIP of the clusters: the same kernel, the same checks in the same order, every output above
+ * bit-identical (mtbt_fuse_detections is the member_slot == NULL path of this code; the struct, its sizeof and the workspace do not
+ * change).  member_slot int32 [N, M*K]: for candidate c = m K + k the output row r < out_counts[n] of the cluster it opened or joined;
+ * -1 for a slot that is no candidate (k >= counts[m][n], s <= skip_thr) and for a member of a cluster that top_k cut.  Every element is
+ * written.  A NULL member_slot is MTBT_EINVAL (checked with the required pointers, after the N == 0 return). */
+int mtbt_fuse_detections_members(const mtbt_box_fuse_args* a, int32_t* member_slot, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Instance masks of FUSED detections, voted over the members of each cluster (test-time augmentation, ensembles): the sign of the
+ * score-weighted mean logit of the members at prototype resolution, upright, then sampled as mtbt_masks_to_frames samples.  The
+ * reference has NO counterpart; this is the project's own definition (tests/vote_reference.py restates it).  Sources m < n_sources = M
+ * <= 8 are the ones mtbt_fuse_detections_members fused: scores[m] [N,K], anchors[m] int32 [N,K] (the NMS keep_anchor), weight[m],
+ * orient[m]; mc[m] the source's mask coefficients, element (n, channel c, anchor a) at mc[m][n * mc_batch_stride[m] + a *
+ * mc_k_stride[m] + c * mc_c_stride[m]]; protos[m] [N,G,G,32] fp32 NHWC in the frame of the source's VIEW (hp == wp == G, nm == 32);
+ * member_slot int32 [N, M*K] as mtbt_fuse_detections_members writes it; counts [N], boxes [N,top_k,4] the FUSED list (upright).
+ * For image n and fused row r < min(counts[n], top_k), members c = m K + k with member_slot[n,c] == r, s_c = scores[m][n,k] * weight[m]:
+ *   Ss[n,r]      = sum of s_c over the members, m ascending then k ascending (starting from the first member's s_c)
+ *   W[n,r,m,:]   = (sum over the members c of source m, k ascending, of s_c * coeff_c[:]) / Ss[n,r],  coeff_c = mc[m][n, :, anchors[m][n,k]]
+ *                  fp32; multiply, then add (the sum starts at 0); ONE true division at the end; no FMA contraction
+ *   low[n,r,y,x] = sum over m ascending, c ascending of W[n,r,m,c] * U_m[n,y,x,c]                  (fp32 MFMA, 4 terms per step)
+ *   U_m          = protos[m] turned upright (postprocess.unorient_batch at the G x G grid):
+ *                  U_m[y,x] = P_m[fy(a), fx(b)],  (a,b) = (x,y) if orient bit 2 else (y,x),  fy(a) = G-1-a if bit 1,  fx(b) = G-1-b if bit 0
+ *   bit(n,r,Y,X) = bilinear tap of low at the frame pixel > 0 (and inside boxes_frame[n,r] with `crop`)
+ * Rows r >= counts[n] of W and Ss and (row, source) pairs without a member are zeros.  W float [N,top_k,M,32] and Ss float [N,top_k] are
+ * caller-provided and fully written (one small deterministic launch), then one mask launch reads W.  Everything from the bilinear tap
+ * on -- frame descriptors, step range, boxes_frame = clamp(boxes / scale), the crop rule, the packed layout with K = top_k planes per
+ * image, zero planes for r >= counts[n], zero padding bits, every byte written -- is mtbt_masks_to_frames' contract, above.
+ * Linear up to W: one vote costs one coefficient row per (row, source), not one mask per member.
+ * MTBT_EINVAL before any launch: NULL a / frames / out / member_slot / counts / W / Ss, M outside 1..8, n_frames outside 1..32 or != N,
+ * nm != 32, K < 1, M K > 4096, top_k outside 1..65535, hp < 1, hp != wp, out_bytes < 0, an orient outside 0..7, a NULL protos[m] / mc[m]
+ * / anchors[m] / scores[m] for m < M, crop or boxes_frame without boxes, then the frame descriptor checks of mtbt_masks_to_frames.
+ * MTBT_EALIGN for a protos[m] / out not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mtbt_vote_mask_args {
+  const float* protos[MTBT_FUSE_MAX_SOURCES];
+  const float* mc[MTBT_FUSE_MAX_SOURCES];
+  int64_t mc_batch_stride[MTBT_FUSE_MAX_SOURCES], mc_k_stride[MTBT_FUSE_MAX_SOURCES], mc_c_stride[MTBT_FUSE_MAX_SOURCES];
+  const int32_t* anchors[MTBT_FUSE_MAX_SOURCES];
+  const float* scores[MTBT_FUSE_MAX_SOURCES];
+  float weight[MTBT_FUSE_MAX_SOURCES];
+  int32_t orient[MTBT_FUSE_MAX_SOURCES];
+  const int32_t* member_slot; /* [N, M*K] */
+  const int32_t* counts;      /* [N] fused */
+  const float* boxes;         /* [N,top_k,4] fused, letterboxed upright xyxy, or NULL */
+  float* boxes_frame;         /* [N,top_k,4] or NULL */
+  float* W;                   /* [N,top_k,M,32] */
+  float* Ss;                  /* [N,top_k] */
+  uint8_t* out;               /* packed planes of all images, top_k per image */
+  int64_t out_bytes;
+  int32_t n_sources, N, K, top_k, nm, hp, wp, crop;
+} mtbt_vote_mask_args;
+
+int mtbt_vote_masks(const mtbt_vote_mask_args* a, const mtbt_frame* frames, int n_frames, void* stream);
+int mtbt_sizeof_vote_mask_args(void);
 
 /* ---------------------------------------------------------------------------------------------
  * Multitask loss VALUE (forward only), MultiTaskLitModel._multitask_loss, running_main_v3.py:232-387:

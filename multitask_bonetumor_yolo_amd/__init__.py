@@ -13,6 +13,7 @@
     from multitask_bonetumor_yolo_amd import TrainStep, ema_decay_at     # the native training step (ema=: averaged weights in the optimiser pass)
     from multitask_bonetumor_yolo_amd import save_train_state, load_train_state   # stop a TrainStep and continue it
     from multitask_bonetumor_yolo_amd import detect_fused                # test-time augmentation / ensembles: weighted boxes fusion on the device
+    from multitask_bonetumor_yolo_amd import vote_masks                  # instance masks of a fused list, voted over each cluster's members
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
@@ -27,5 +28,6 @@ from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, 
                       ImageClassificationMetrics, MeanAveragePrecision, SegmentationMetrics)
 from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
+from .postprocess import vote_masks  # noqa: F401
 from .trainstep import TrainStep, ema_decay_at  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

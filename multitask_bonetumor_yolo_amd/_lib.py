@@ -177,6 +177,16 @@ class BoxFuseArgs(C.Structure):  # mtbt_box_fuse_args (FuseArgs / mtbt_fuse_args
                 ("lead_anchor", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class VoteMaskArgs(C.Structure):  # mtbt_vote_mask_args
+    _fields_ = [("protos", C.c_void_p * 8), ("mc", C.c_void_p * 8),
+                ("mc_batch_stride", C.c_int64 * 8), ("mc_k_stride", C.c_int64 * 8), ("mc_c_stride", C.c_int64 * 8),
+                ("anchors", C.c_void_p * 8), ("scores", C.c_void_p * 8), ("weight", C.c_float * 8), ("orient", C.c_int32 * 8),
+                ("member_slot", C.c_void_p), ("counts", C.c_void_p), ("boxes", C.c_void_p), ("boxes_frame", C.c_void_p),
+                ("W", C.c_void_p), ("Ss", C.c_void_p), ("out", C.c_void_p), ("out_bytes", C.c_int64),
+                ("n_sources", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("top_k", C.c_int32),
+                ("nm", C.c_int32), ("hp", C.c_int32), ("wp", C.c_int32), ("crop", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -298,6 +308,9 @@ SYMBOLS = {
     "mtbt_fuse_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mtbt_fuse_detections": (C.c_int, [C.POINTER(BoxFuseArgs), C.c_void_p]),
     "mtbt_sizeof_box_fuse_args": (C.c_int, []),
+    "mtbt_fuse_detections_members": (C.c_int, [C.POINTER(BoxFuseArgs), C.c_void_p, C.c_void_p]),
+    "mtbt_vote_masks": (C.c_int, [C.POINTER(VoteMaskArgs), C.POINTER(Frame), C.c_int, C.c_void_p]),
+    "mtbt_sizeof_vote_mask_args": (C.c_int, []),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -330,7 +343,8 @@ def load():
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "
                                        f"out in {C.sizeof(st)} bytes: stale library, rebuild")
         for sizeof, st in ((lib.mtbt_sizeof_mask_loss_args, MaskLossArgs), (lib.mtbt_sizeof_tal_loss_args, TalLossArgs),
-                           (lib.mtbt_sizeof_pw_chain_args, PwChainArgs), (lib.mtbt_sizeof_box_fuse_args, BoxFuseArgs)):
+                           (lib.mtbt_sizeof_pw_chain_args, PwChainArgs), (lib.mtbt_sizeof_box_fuse_args, BoxFuseArgs),
+                           (lib.mtbt_sizeof_vote_mask_args, VoteMaskArgs)):
             if sizeof() != C.sizeof(st):
                 raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof()}, this binding lays it "
                                    f"out in {C.sizeof(st)} bytes: stale library, rebuild")

@@ -29,6 +29,7 @@ struct FuseP {
   int* lead_source;
   int* lead_slot;
   int* lead_anchor;
+  int* member_slot;   // [N, C] or nullptr: the cluster index during the greedy pass, the output row after the write-out
   char* ws;
   long ws_per_image;
 };
@@ -82,6 +83,8 @@ __device__ __forceinline__ float cluster_score(const Acc& a, int M, float wsum) 
 //     each lane scans clusters lane, lane + 64, ... in LDS, a butterfly (value, index) arg-max picks the winner, lane 0 applies the update.
 //     No workgroup barrier inside the loop: LDS operations of one wave complete in order, the fence keeps the compiler from moving them.
 //  4. cluster scores -> keys, bitonic sort, write-out by the whole workgroup
+// With member_slot (mtbt_fuse_detections_members) every candidate's cluster index is kept by the greedy pass and turned into its output
+// row at the end; nothing else changes.
 __global__ __launch_bounds__(FUSE_NT) void fuse_kernel(const FuseP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ int s_cnt, s_ncl;
@@ -101,6 +104,9 @@ __global__ __launch_bounds__(FUSE_NT) void fuse_kernel(const FuseP p) {
 
   // ---- 1. keys of the candidates ----
   if (tid == 0) { s_cnt = 0; s_ncl = 0; }
+  int* mslot = p.member_slot ? p.member_slot + (long)n * C : nullptr;
+  if (mslot)
+    for (int c = tid; c < C; c += FUSE_NT) mslot[c] = -1;
   __syncthreads();
   int mine = 0;
   for (int c = tid; c < p.P2; c += FUSE_NT) {
@@ -190,6 +196,7 @@ __global__ __launch_bounds__(FUSE_NT) void fuse_kernel(const FuseP p) {
             fused[ncl] = bj;
             clabel[ncl] = lab;
           }
+          if (mslot) mslot[c] = join ? bi : ncl;
         }
         if (!join) ++ncl;
         __threadfence_block();                                // the update is in LDS before the next candidate's scan reads it
@@ -236,6 +243,17 @@ __global__ __launch_bounds__(FUSE_NT) void fuse_kernel(const FuseP p) {
     if (p.lead_anchor) p.lead_anchor[row + r] = la;
   }
   if (tid == 0) { p.out_counts[n] = nout; p.n_clusters[n] = ncl; }
+  if (mslot) {
+    // cluster index -> output row (-1 past the cut), through the sorted candidates' score array: the greedy pass was its last reader
+    int* row_of = reinterpret_cast<int*>(cs);
+    for (int r = tid; r < ncl; r += FUSE_NT) row_of[(int)(keys[r] & 0xffffffffu)] = r < nout ? r : -1;
+    __threadfence_block();
+    __syncthreads();
+    for (int c = tid; c < C; c += FUSE_NT) {
+      const int i = mslot[c];
+      if (i >= 0) mslot[c] = row_of[i];
+    }
+  }
 }
 
 inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
@@ -250,7 +268,7 @@ extern "C" int64_t mtbt_fuse_workspace_bytes(int n_sources, int N, int K) {
 
 extern "C" int mtbt_sizeof_box_fuse_args(void) { return (int)sizeof(mtbt_box_fuse_args); }
 
-extern "C" int mtbt_fuse_detections(const mtbt_box_fuse_args* a, void* stream) {
+static int fuse_launch(const mtbt_box_fuse_args* a, int32_t* member_slot, bool want_members, void* stream) {
   if (!a) return MTBT_EINVAL;
   const int M = a->n_sources;
   if (M < 1 || M > MTBT_FUSE_MAX_SOURCES || a->N < 0 || a->K < 1 || (long)M * a->K > MTBT_FUSE_MAX_CANDIDATES || a->top_k < 1) return MTBT_EINVAL;
@@ -267,7 +285,7 @@ extern "C" int mtbt_fuse_detections(const mtbt_box_fuse_args* a, void* stream) {
     if (!a->anchors[m]) all_anchors = false;
   }
   if (!a->out_boxes || !a->out_scores || !a->out_labels || !a->out_counts || !a->n_clusters || !a->n_members || !a->lead_source ||
-      !a->lead_slot || !a->workspace)
+      !a->lead_slot || !a->workspace || (want_members && !member_slot))
     return MTBT_EINVAL;
   if (a->lead_anchor && !all_anchors) return MTBT_EINVAL;
   const int C = M * a->K;
@@ -295,6 +313,7 @@ extern "C" int mtbt_fuse_detections(const mtbt_box_fuse_args* a, void* stream) {
   p.out_boxes = a->out_boxes; p.out_scores = a->out_scores; p.out_labels = reinterpret_cast<long long*>(a->out_labels);
   p.out_counts = a->out_counts; p.n_clusters = a->n_clusters; p.n_members = a->n_members;
   p.lead_source = a->lead_source; p.lead_slot = a->lead_slot; p.lead_anchor = a->lead_anchor;
+  p.member_slot = want_members ? member_slot : nullptr;
   p.ws = reinterpret_cast<char*>(a->workspace); p.ws_per_image = per;
   const size_t lds = (size_t)(p.acc_in_lds ? lds_acc : lds_small);
   // one-time (per device) opt-in to the LARGEST dynamic LDS this kernel ever asks for
@@ -302,4 +321,10 @@ extern "C" int mtbt_fuse_detections(const mtbt_box_fuse_args* a, void* stream) {
   hipLaunchKernelGGL(fuse_kernel, dim3(a->N), dim3(FUSE_NT), lds, reinterpret_cast<hipStream_t>(stream), p);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
+}
+
+extern "C" int mtbt_fuse_detections(const mtbt_box_fuse_args* a, void* stream) { return fuse_launch(a, nullptr, false, stream); }
+
+extern "C" int mtbt_fuse_detections_members(const mtbt_box_fuse_args* a, int32_t* member_slot, void* stream) {
+  return fuse_launch(a, member_slot, true, stream);
 }

@@ -6,14 +6,15 @@
 
 A source is a (model, view) pair; a view is one of the eight dihedral codes of `mtbt_augment_batch` (bit 0 flips x, bit 1 flips y, bit 2
 transposes).  Every source is `orient_batch` -> `model(x, "infer")` -> `detect_and_segment`; one `fuse_detections` launch merges them
-(`mtbt_fuse_detections`, include/mtbt_hip.h).  No host synchronisation.
+(`mtbt_fuse_detections`, include/mtbt_hip.h).  Instance masks of the fused list are its leaders' (`masks=True`) or voted over every
+cluster's members (`masks="vote"`, `mtbt_vote_masks`).  No host synchronisation.
 """
 from typing import Optional, Sequence
 
 import torch
 
 from .postprocess import (CONF_TH, NMS_IOU, TOP_K, FUSE_MAX_SOURCES, assemble_masks, detect_and_segment, fuse_detections, orient_batch,
-                          unorient_batch)
+                          unorient_batch, unpack_masks, vote_masks)
 
 
 def _leader_masks(fused, outs, views, S: int) -> torch.Tensor:
@@ -38,7 +39,7 @@ def _leader_masks(fused, outs, views, S: int) -> torch.Tensor:
 @torch.no_grad()
 def detect_fused(models, images: torch.Tensor, img_size: int, *, views: Sequence[int] = (0,), weights: Optional[Sequence[float]] = None,
                  conf_th: float = CONF_TH, iou_th: float = NMS_IOU, top_k: int = TOP_K, wbf_iou: float = 0.55, skip_thr: float = 0.0,
-                 masks: bool = False):
+                 masks=False, frames=None, crop: bool = False):
     """Detections of `images` [B,3,S,S] (S = img_size) fused over models x views.
 
     `models`: one eval-mode model or a list of them (the k models of a k-fold run; the raw and the EMA weights of a `TrainStep`).
@@ -49,7 +50,18 @@ def detect_fused(models, images: torch.Tensor, img_size: int, *, views: Sequence
 
     `masks=True` adds `masks`, uint8 [B,top_k,S,S] in the upright frame: each fused detection's mask is its LEADER's (the highest-scoring
     member): the leader's coefficients against its own source's prototypes, turned back by the inverse of that source's view.  Transient
-    memory: B * top_k * S^2 bytes per source on top of the result.  Voting over the members' masks is not implemented."""
+    memory: B * top_k * S^2 bytes per source on top of the result.
+
+    `masks="vote"` votes instead (`postprocess.vote_masks`): the sign of the score-weighted mean of the MEMBERS' prototype-resolution
+    logits, every source turned upright, so that the mask belongs to the same members as the averaged box.  The result gains
+    `member_slot`, `vote_coeff` and, without `frames`, `masks` uint8 [B,top_k,S,S] (identity frames (S, S, 1.0), unpacked); with `frames`
+    ([(H0, W0, scale)] per image, `frames_of`) it gains `boxes_frame` [B,top_k,4] and the bit-packed `masks_frame` instead, as
+    `detect_and_segment` returns them, cropped to the fused boxes with `crop`.  `frames` / `crop` need `masks="vote"`."""
+    if masks not in (False, True, "vote"):
+        raise ValueError(f"detect_fused: masks is False, True (the leaders' masks) or 'vote', not {masks!r}")
+    vote = isinstance(masks, str)
+    if (frames is not None or crop) and not vote:
+        raise ValueError("detect_fused: frames / crop come with masks='vote'")
     models = list(models) if isinstance(models, (list, tuple)) else [models]
     views = [int(v) for v in views]
     weights = [1.0] * len(models) if weights is None else [float(w) for w in weights]
@@ -71,7 +83,17 @@ def detect_fused(models, images: torch.Tensor, img_size: int, *, views: Sequence
             outs.append(out)
             src_views.append(v)
             src_weights.append(w)
-    fused = fuse_detections(dets, img_size=S, orients=src_views, weights=src_weights, iou_thr=wbf_iou, skip_thr=skip_thr, top_k=top_k)
-    if masks:
+    fused = fuse_detections(dets, img_size=S, orients=src_views, weights=src_weights, iou_thr=wbf_iou, skip_thr=skip_thr, top_k=top_k,
+                            want_members=vote)
+    if vote:
+        B = images.shape[0]
+        r = vote_masks(fused, outs, src_views, src_weights, [(S, S, 1.0)] * B if frames is None else frames, crop=crop,
+                       up=S / outs[0]["segment_protos"][2].shape[3])
+        fused["vote_coeff"] = r["vote_coeff"]
+        if frames is None:
+            fused["masks"] = torch.stack([unpack_masks(p, S) for p in r["masks"]]).view(torch.uint8)
+        else:
+            fused["boxes_frame"], fused["masks_frame"] = r["boxes"], r["masks"]
+    elif masks:
         fused["masks"] = _leader_masks(fused, outs, src_views, S)
     return fused

@@ -410,7 +410,8 @@ def _fuse_args(dets, img_size, orients, weights, iou_thr, skip_thr, top_k):
 
 
 def fuse_detections(dets: Sequence[dict], *, img_size: float, orients: Optional[Sequence[int]] = None,
-                    weights: Optional[Sequence[float]] = None, iou_thr: float = 0.55, skip_thr: float = 0.0, top_k: Optional[int] = None):
+                    weights: Optional[Sequence[float]] = None, iou_thr: float = 0.55, skip_thr: float = 0.0, top_k: Optional[int] = None,
+                    want_members: bool = False):
     """Weighted boxes fusion (`mtbt_fuse_detections`) of several detection lists of the same batch: the views of test-time
     augmentation, the models of an ensemble.  One launch, no host synchronisation, deterministic.
 
@@ -423,11 +424,98 @@ def fuse_detections(dets: Sequence[dict], *, img_size: float, orients: Optional[
 
     Returns dict(boxes [B,top_k,4], scores, labels int64, counts int32 [B] -- what `update_batched` and the mask-mAP classes read --,
     n_clusters int32 [B] (before the cut), n_members int32 [B,top_k], lead_source / lead_slot int32 [B,top_k] (source and slot of each
-    cluster's highest-scoring member, -1 padded) and, when every input has `keep_anchor`, lead_anchor int32 [B,top_k])."""
+    cluster's highest-scoring member, -1 padded) and, when every input has `keep_anchor`, lead_anchor int32 [B,top_k]).
+
+    `want_members=True` (`mtbt_fuse_detections_members`: the same launch, every other entry bit-identical) adds `member_slot` int32
+    [B, M*K]: for slot k of source m, at m * K + k, the output row of the cluster it opened or joined; -1 for a slot that was no candidate
+    and for a member of a cluster that `top_k` cut.  `vote_masks` reads it."""
     a, o, dev = _fuse_args(dets, img_size, orients, weights, iou_thr, skip_thr, top_k)
     with torch.cuda.device(dev):
-        L.check(L.load().mtbt_fuse_detections(C.byref(a), _stream(dev)), "mtbt_fuse_detections")
+        if want_members:
+            o["member_slot"] = torch.empty((a.N, a.n_sources * a.K), dtype=torch.int32, device=dev)
+            L.check(L.load().mtbt_fuse_detections_members(C.byref(a), o["member_slot"].data_ptr(), _stream(dev)), "mtbt_fuse_detections_members")
+        else:
+            L.check(L.load().mtbt_fuse_detections(C.byref(a), _stream(dev)), "mtbt_fuse_detections")
     return o
+
+
+def vote_masks(fused: dict, sources: Sequence, orients: Optional[Sequence[int]], weights: Optional[Sequence[float]], frames,
+               crop: bool = False, out: Optional[torch.Tensor] = None, up: Optional[float] = None):
+    """Instance masks of fused detections, voted over the members of each cluster (`mtbt_vote_masks`): the sign of the score-weighted
+    mean of the members' prototype-resolution logits, every source turned upright first, sampled at the pixels of `frames`.
+
+    `fused`: the result of `fuse_detections(dets, ..., want_members=True)` of detection lists that carry `keep_anchor`.  `sources[m]`:
+    source m's model output (a dict with `segment_protos`) or its `(mc, protos)` pair -- mc [B,32,A] fp32, protos [B,32,G,G] in the frame
+    of the view that source saw.  `orients` / `weights`: the ones the fusion was given (None: 0 / 1).  `frames`, `up`, `crop`, `out` and the
+    packed layout: as in `masks_to_frames`, with the fused boxes and `top_k` planes per image.
+
+      W[b,r,m,:] = sum over source m's members of row r of (score * weight_m) * coefficients, divided by the row's sum of score * weight
+      mask bit   = bilinear tap of sum_m W[b,r,m,:] . upright protos_m at the frame pixel > 0 (and inside the fused frame box with `crop`)
+
+    One coefficient row per (fused row, source) instead of one mask per member: the vote is linear up to the sign.  Returns what
+    `masks_to_frames` returns ("boxes" [B,top_k,4] in the frames, "masks" views, "buffer") plus "vote_coeff" (W, float32 [B,top_k,M,32])
+    and "vote_weight" (the rows' sums, float32 [B,top_k]).  No host synchronisation."""
+    lib = L.load()
+    if "member_slot" not in fused:
+        raise ValueError("vote_masks: `fused` has no member_slot; call fuse_detections(..., want_members=True)")
+    srcs = fused["_keep"][0]
+    M = len(srcs)
+    if len(sources) != M or any(len(s) < 5 for s in srcs):
+        raise ValueError(f"vote_masks: {len(sources)} sources for a fusion of {M}, each of which must carry keep_anchor")
+    orients = [0] * M if orients is None else [int(o) for o in orients]
+    weights = [1.0] * M if weights is None else [float(w) for w in weights]
+    if len(orients) != M or len(weights) != M or any(not 0 <= o <= 7 for o in orients):
+        raise ValueError(f"vote_masks: {len(orients)} orients (0..7) and {len(weights)} weights for {M} sources")
+    member_slot, counts, boxes = fused["member_slot"], fused["counts"], fused["boxes"]
+    _need_cuda(member_slot, "vote_masks")
+    dev = member_slot.device
+    B, top_k = fused["scores"].shape
+    K = srcs[0][1].shape[1]
+    if len(frames) != B:
+        raise ValueError(f"vote_masks: {len(frames)} frames for a batch of {B}")
+    keep = []
+    for m, src in enumerate(sources):
+        mc, protos = src["segment_protos"][1:3] if isinstance(src, dict) else src
+        _need_cuda(protos, "vote_masks")
+        pr, ld = _nhwc_rows(protos)
+        nm, hp, wp = protos.shape[1:]
+        if ld != nm:
+            pr = pr.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+        mc = mc.float()
+        if protos.shape[0] != B or mc.shape[0] != B or mc.shape[1] != nm or nm != 32 or hp != wp or (keep and (hp, wp) != tuple(keep[0][0].shape[2:])):
+            raise ValueError(f"vote_masks: source {m} has protos {tuple(protos.shape)} and mc {tuple(mc.shape)}; expected [{B}, 32, G, G] and "
+                             f"[{B}, 32, A] with the same square G for every source")
+        keep.append((pr, mc))
+    G = keep[0][0].shape[2]
+    rows, total = _frame_layout(frames, top_k, 4.0 if up is None else float(up))
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total or out.device != dev:
+        raise ValueError(f"vote_masks: out must be a contiguous flat uint8 buffer of at least {total} bytes on {dev}")
+    boxes = boxes.contiguous().float()
+    boxes_frame = torch.empty((B, top_k, 4), dtype=torch.float32, device=dev)
+    W = torch.empty((B, top_k, M, 32), dtype=torch.float32, device=dev)
+    Ss = torch.empty((B, top_k), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        for c0 in range(0, B, MAX_FRAMES):
+            nb = min(MAX_FRAMES, B - c0)
+            a = L.VoteMaskArgs()
+            for m, ((pr, mc), src) in enumerate(zip(keep, srcs)):
+                a.protos[m], a.mc[m] = pr[c0:].data_ptr(), mc[c0:].data_ptr()
+                a.mc_batch_stride[m], a.mc_k_stride[m], a.mc_c_stride[m] = mc.stride(0), mc.stride(2), mc.stride(1)
+                a.scores[m], a.anchors[m] = src[1][c0:].data_ptr(), src[4][c0:].data_ptr()
+                a.weight[m], a.orient[m] = weights[m], orients[m]
+            a.member_slot, a.counts = member_slot[c0:].data_ptr(), counts[c0:].data_ptr()
+            a.boxes, a.boxes_frame = boxes[c0:].data_ptr(), boxes_frame[c0:].data_ptr()
+            a.W, a.Ss = W[c0:].data_ptr(), Ss[c0:].data_ptr()
+            a.out, a.out_bytes = out.data_ptr(), out.numel()
+            a.n_sources, a.N, a.K, a.top_k, a.nm, a.hp, a.wp, a.crop = M, nb, K, top_k, 32, G, G, int(bool(crop))
+            fr = (L.Frame * nb)()
+            for i, (H0, W0, step, scale, pitch, off) in enumerate(rows[c0:c0 + nb]):
+                fr[i].height, fr[i].width, fr[i].step, fr[i].scale, fr[i].pitch, fr[i].offset = H0, W0, step, scale, pitch, off
+            L.check(lib.mtbt_vote_masks(C.byref(a), fr, nb, _stream(dev)), "mtbt_vote_masks")
+    views = [out[off:off + top_k * H0 * pitch].view(top_k, H0, pitch) for H0, W0, step, scale, pitch, off in rows]
+    return {"boxes": boxes_frame, "masks": views, "buffer": out, "vote_coeff": W, "vote_weight": Ss}
 
 
 def _square(x: torch.Tensor, orient: int, what: str):

@@ -21,7 +21,7 @@ from .loss import instance_mask_loss, multitask_loss, task_aligned_det_loss
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision, ImageClassificationMetrics,
                       SegmentationMetrics, _sum_over_ranks)
 from .postprocess import (CONF_TH, NMS_IOU, TOP_K, decode_boxes, fuse_detections, masks_to_frames, nms_batched, orient_batch, pack_masks,
-                          proto_projector_logits)
+                          proto_projector_logits, vote_masks)
 
 LOSS_NAMES = ("total", "seg", "box_iou", "dfl", "det_cls", "img_cls")       # running_main_v3.py:578-582
 MASK_LOSS_NAME = "mask"                                                      # appended with instance_mask_weight > 0
@@ -59,7 +59,8 @@ class ValidationStep:
                  label_smoothing: float = 0.1, loss_weights=(1.0, 2.0, 1.5, 0.5, 1.0), conf_th: float = CONF_TH, nms_iou: float = NMS_IOU,
                  top_k: int = TOP_K, map_max_detections: int = 100, dist_sync: bool = True, process_group=None,
                  instance_masks: bool = False, mask_crop: bool = True, det_loss: str = "reference", tal=None,
-                 instance_mask_weight: float = 0.0, mask_assign: str = "iou", views: Optional[Sequence[int]] = None, wbf_iou: float = 0.55):
+                 instance_mask_weight: float = 0.0, mask_assign: str = "iou", views: Optional[Sequence[int]] = None, wbf_iou: float = 0.55,
+                 fused_masks: Optional[str] = None):
         """`projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1), running_main_v3.py:186); created with torch's default
         init when not given.  The loss hyper-parameters default to the reference's (and TrainStep's); `label_smoothing` is accepted for
         symmetry with TrainStep but the eval-mode loss never smooths (:337).  conf_th / nms_iou / top_k: `:54-56`;
@@ -78,14 +79,21 @@ class ValidationStep:
         are updated from the weighted-boxes fusion (`fuse_detections`, IoU `wbf_iou`) of one detection list per view: view 0 is the
         step's own identity pass (the same maps the losses see), every other view one more forward of the oriented batch with the whole
         module in eval mode (`model(x, "infer")`), decoded and filtered like the identity pass.  The losses, the confusion matrices and
-        the segmentation metrics stay on the identity pass, and `compute()` keeps its keys.  Not with `instance_masks` (fused instance
-        masks: `detect_fused(masks=True)`).  `views=None`: not one launch changes."""
+        the segmentation metrics stay on the identity pass, and `compute()` keeps its keys.  `views=None`: not one launch changes.
+        `fused_masks="vote"` (with `views` and `instance_masks`): the instance-mask mAP is fed from the fused list too -- every view's pass
+        keeps its mask coefficients and prototypes, and the packed planes are voted over each cluster's members (`vote_masks`, as
+        `detect_fused(masks="vote")`).  `views` with `instance_masks` needs it: there is no other fused mask to score."""
         self.views = None if views is None else tuple(int(v) for v in views)
         self.wbf_iou = float(wbf_iou)
+        if fused_masks not in (None, "vote"):
+            raise ValueError(f"fused_masks: None or 'vote', not {fused_masks!r}")
+        if fused_masks is not None and (self.views is None or not instance_masks):
+            raise ValueError("fused_masks='vote' scores the voted masks of the fused list: it needs views and instance_masks=True")
+        self.fused_masks = fused_masks
         if self.views is not None:
-            if instance_masks:
-                raise NotImplementedError("ValidationStep: views with instance_masks=True is not implemented; fused instance masks come from "
-                                          "detect_fused(masks=True)")
+            if instance_masks and fused_masks is None:
+                raise NotImplementedError("ValidationStep: views with instance_masks=True needs fused_masks='vote' (the voted masks of "
+                                          "detect_fused(masks='vote')); the leaders' masks are not scored")
             if not 1 <= len(self.views) <= 8 or any(not 0 <= v <= 7 for v in self.views):
                 raise ValueError(f"views: 1..8 orient codes in 0..7, not {views!r}")
         if det_loss not in ("reference", "tal"):
@@ -181,34 +189,44 @@ class ValidationStep:
         self.det_cm.update(det, det_gt)
         d = decode_boxes(det, self.S, reg_max=self.reg_max, want_scores=False)
         k = nms_batched(d["boxes"], d["best_score"], d["best_label"], float(self.S), **self.nms_kw)
+        sources = None
         if self.views is not None:
-            k = fuse_detections([k if v == 0 else self._view_detections(imgs, v) for v in self.views], img_size=self.S, orients=self.views,
-                                iou_thr=self.wbf_iou, top_k=self.nms_kw["top_k"])
+            vote = self.fused_masks is not None
+            per_view = [(k, (seg_out[1], protos)) if v == 0 else self._view_detections(imgs, v) for v in self.views]
+            k = fuse_detections([d for d, _ in per_view], img_size=self.S, orients=self.views, iou_thr=self.wbf_iou, top_k=self.nms_kw["top_k"],
+                                want_members=vote)
+            sources = [s for _, s in per_view] if vote else None
         self.map50.update_batched(k, det_gt, self.S)
         self.map50_95.update_batched(k, det_gt, self.S)
         if self.instance_masks:
-            self._mask_update(seg_out[1], protos, k, det_gt, masks_gt)
+            self._mask_update(seg_out[1], protos, k, det_gt, masks_gt, sources)
         return losses
 
     def _view_detections(self, imgs, view: int):
         """The detection list of one more view: `model(orient_batch(imgs, view), "infer")` with every module in eval mode (flags restored
-        afterwards), decoded and filtered like the identity pass.  Boxes in the view's frame: `fuse_detections` turns them back."""
+        afterwards), decoded and filtered like the identity pass.  Boxes in the view's frame: `fuse_detections` turns them back.  Returns
+        (the list, (mc, protos) of that pass, in the view's frame: what `vote_masks` takes)."""
         flags = [(mod, mod.training) for mod in self.m.modules()]
         self.m.eval()
         try:
             with torch.no_grad():
-                det = self.m(orient_batch(imgs, view), "infer")["detect_features"]
+                out = self.m(orient_batch(imgs, view), "infer")
         finally:
             for mod, f in flags:
                 mod.training = f
-        d = decode_boxes(det, self.S, reg_max=self.reg_max, want_scores=False)
-        return nms_batched(d["boxes"], d["best_score"], d["best_label"], float(self.S), **self.nms_kw)
+        d = decode_boxes(out["detect_features"], self.S, reg_max=self.reg_max, want_scores=False)
+        return nms_batched(d["boxes"], d["best_score"], d["best_label"], float(self.S), **self.nms_kw), tuple(out["segment_protos"][1:3])
 
-    def _mask_update(self, mc, protos, k, det_gt, masks_gt):
+    def _mask_update(self, mc, protos, k, det_gt, masks_gt, sources=None):
         """The instance-mask mAP's share of a step: detections' masks and per-box ground truth as packed S x S planes, one pair-count
-        pass for both threshold sets.  Device work only."""
+        pass for both threshold sets.  Device work only.  With `sources` ((mc, protos) per view) `k` is the fused list and its planes
+        are voted."""
         S, B, K = self.S, protos.shape[0], k["scores"].shape[1]
-        r = masks_to_frames(protos, mc.float(), k["keep_anchor"], k["counts"], k["boxes"], [(S, S, 1.0)] * B, up=S / protos.shape[3], crop=self.mask_crop)
+        frames = [(S, S, 1.0)] * B
+        if sources is not None:
+            r = vote_masks(k, sources, self.views, None, frames, crop=self.mask_crop, up=S / protos.shape[3])
+        else:
+            r = masks_to_frames(protos, mc.float(), k["keep_anchor"], k["counts"], k["boxes"], frames, up=S / protos.shape[3], crop=self.mask_crop)
         pitch = r["masks"][0].shape[2]
         plane = K * S * pitch
         # masks_to_frames starts every image on a 16-byte boundary (`_frame_layout`): the images are back to back, and the buffer is one
