@@ -508,6 +508,141 @@ int mtbt_vote_masks(const mtbt_vote_mask_args* a, const mtbt_frame* frames, int 
 int mtbt_sizeof_vote_mask_args(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * Sliced inference: the model runs on overlapping S x S windows (tiles) of a large image at or near native resolution, plus the whole
+ * image once, and the per-tile results are merged in the image's own pixel frame.  The reference has NO counterpart; this arithmetic is
+ * the project's own definition (tests/slice_reference.py restates it).  Every fp32 operation below is one correctly rounded operation in
+ * the order written (no FMA contraction).
+ *
+ * TILES.  A pass over image (H0, W0) at zoom z resizes it to R with new = max(1, (int)(dim * z)) per axis (the letterbox's rule; R is
+ * never materialised).  A tile is the S x S canvas showing R[oy:oy+S, ox:ox+S], 114/255 pad beyond R: mtbt_augment_batch with the
+ * geometry row (new_w, new_h, -ox, -oy, 0, 0, 0, 0) and no table.  ox, oy are multiples of up = S / G (4 for the models), so the tile's
+ * prototype grid sits at the integer offset (pox, poy) = (ox / up, oy / up) of R's virtual prototype grid.  Its descriptor:
+ *   image            index of the image (within the call) the tile belongs to; the tiles of an image are consecutive
+ *   pox, poy         >= 0
+ *   wx0,wy0,wx1,wy1  the frame WINDOW, half-open, clamped to the image: the frame pixels X whose centre (X + 0.5) * z lies in
+ *                    [ox, min(ox + S, new_w)), the same in y (computed by the host in double); the tile that reaches the end of the
+ *                    resized axis (ox + S >= new_w) takes the pixels up to the image's edge, since (int)(dim * z) may cut the last centre off
+ *   height, width    H0, W0 of the image
+ *   step, scale      step = (float)(z / up), 0 < step <= 1 prototype pixels per frame pixel;  scale = (float)z
+ *   fox, foy         (float)ox, (float)oy
+ * The whole-image pass is the tile z = S / max(H0, W0), ox = oy = 0, window = the image: for it everything below reduces to
+ * mtbt_masks_to_frames / its boxes_frame bit for bit.
+ *
+ * MERGING (mtbt_merge_tiles): one launch, one workgroup per image, no host synchronisation, deterministic.  Sources are exactly what
+ * mtbt_nms_batched writes for a batch of NT tiles: boxes [NT,K,4] xyxy in each tile's canvas, scores [NT,K], labels int64 [NT,K],
+ * counts int32 [NT], anchors int32 [NT,K] or NULL.  Image n owns tiles [first[n], first[n+1]), T_n = first[n+1] - first[n] <= 64 and
+ * T_n K <= 4096; first[0] = 0, first[N] = NT.
+ *   1. candidates: (tile t, slot k < min(counts[t], K)) with score s > skip_thr; index within the image c = (t - first[n]) K + k.
+ *      Component v of its FRAME box is clamp((v + off) / scale_t, 0, hi): one add, then one true division; off = fox_t | foy_t,
+ *      hi = W0 | H0.
+ *   2. order: ascending keys ~orderable(s) << 32 | c (the NMS / fusion key: stable descending s, ties to ascending c).
+ *   3. greedy non-maximum MERGING in that order.  A candidate i not yet absorbed opens the next row; every later, not yet absorbed
+ *      candidate j with the same label (any label with class_agnostic) and metric(box_i, box_j) > thr is absorbed into it.  box_i is i's
+ *      OWN frame box, never the growing union.  With area_x = (x2 - x1) * (y2 - y1), inter = max(0, min(x2) - max(x1)) * max(0, min(y2) -
+ *      max(y1)) as the NMS computes them:
+ *        metric 0 (IoU)  inter / ((area_i + area_j) - inter)
+ *        metric 1 (IoS)  inter / fminf(area_i, area_j)          (intersection over the smaller: a part is absorbed by the whole)
+ *      A NaN never matches.  The row's box is the union of its members' frame boxes (min / max), its score and label the leader's.
+ *      The loop stops after top_k rows.
+ *   4. outputs, row stride top_k, padded as mtbt_nms_batched pads (boxes and scores 0, labels -1, lead_* -1, n_members 0):
+ *      out_boxes [N,top_k,4] in FRAME pixels, out_scores, out_labels int64, out_counts [N], n_members, lead_tile (index into the tile
+ *      table), lead_slot, lead_anchor (optional; needs anchors), member_slot int32 [NT,K] (the row the slot opened or joined, -1
+ *      otherwise; every element is written), n_left [N] (candidates neither leading nor absorbed when the loop stopped: > 0 iff top_k cut).
+ * `tiles` is a HOST copy of the tile table (validated, never dereferenced on the device), `tiles_dev` the caller's DEVICE copy of the
+ * same NT descriptors (read by the kernels); `first` is a host array.  No allocation and no synchronisation inside the library.
+ * Order of the checks: MTBT_EINVAL before any launch for NULL a, N < 0, K < 1, top_k < 1, a metric outside 0..1, a NaN thr or skip_thr;
+ * then N == 0 is MTBT_OK with nothing launched; then MTBT_EINVAL for a NULL required pointer (boxes, scores, labels, counts, tiles,
+ * tiles_dev, first, every output but lead_anchor), lead_anchor without anchors, a bad `first` (first[0] != 0, decreasing, T_n > 64,
+ * T_n K > 4096, first[N] != n_tiles), a bad descriptor (image != n, negative pox / poy, an empty or out-of-image window, step outside
+ * (0, 1], scale not > 0, a NaN or negative fox / foy, height or width < 1 or not the same for every tile of the image, reserved != 0);
+ * then MTBT_EALIGN for boxes / out_boxes not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define MTBT_TILE_MAX_PER_IMAGE 64
+#define MTBT_MERGE_IOU 0
+#define MTBT_MERGE_IOS 1
+typedef struct mtbt_tile {
+  int32_t image;
+  int32_t pox, poy;
+  int32_t wx0, wy0, wx1, wy1;
+  int32_t height, width;
+  int32_t reserved;
+  float step, scale;
+  float fox, foy;
+} mtbt_tile;
+
+typedef struct mtbt_tile_merge_args {
+  const float* boxes;       /* [NT,K,4] */
+  const float* scores;      /* [NT,K] */
+  const int64_t* labels;    /* [NT,K] */
+  const int32_t* counts;    /* [NT] */
+  const int32_t* anchors;   /* [NT,K] or NULL */
+  const mtbt_tile* tiles;     /* HOST [NT] */
+  const mtbt_tile* tiles_dev; /* DEVICE [NT] */
+  const int32_t* first;     /* HOST [N+1] */
+  int32_t N, n_tiles, K, top_k;
+  int32_t metric, class_agnostic;
+  float thr, skip_thr;
+  float* out_boxes;
+  float* out_scores;
+  int64_t* out_labels;
+  int32_t* out_counts;
+  int32_t* n_members;
+  int32_t* lead_tile;
+  int32_t* lead_slot;
+  int32_t* lead_anchor;     /* [N,top_k] or NULL */
+  int32_t* member_slot;     /* [NT,K] */
+  int32_t* n_left;          /* [N] */
+} mtbt_tile_merge_args;
+
+int mtbt_merge_tiles(const mtbt_tile_merge_args* a, void* stream);
+
+/* Instance masks of MERGED rows, voted across the tiles of their members straight into the bit-packed frame planes
+ * (mtbt_vote_tile_masks).  For merged row r < min(counts[n], top_k) of image n, members c = (tile t, slot k) with member_slot[t,k] == r,
+ * s_c = scores[t,k], tl = t - first[n]:
+ *   Ss[n,r]      = sum of s_c over the members, c ascending (fp32 adds from 0)
+ *   W[n,r,tl,:]  = (sum over row r's members in tile t, k ascending, of s_c * coeff_c[:]) / Ss[n,r]      coeff_c = mc[t, :, anchors[t,k]];
+ *                  multiply, then add from 0, ONE true division; (row, tile) pairs without a member, rows r >= counts[n] and tl >= T_n: 0
+ *   low_t        = W[n,r,tl,:] . P_t            (fp32 MFMA, 4 terms per step; P_t = protos[t] [G,G,32], tile-major NHWC)
+ *   tap_t(Y,X)   : sx = max(((float)X + 0.5f) * step_t - 0.5f - (float)pox_t, 0), then exactly mtbt_masks_to_frames' rule against G:
+ *                  x0 = min((int)sx, G-1); x1 = min(x0+1, G-1); lx = clamp(sx - x0, 0, 1); the same in y with poy_t; its bilinear form
+ *   v(Y,X)       = sum, tiles t ascending, over the tiles with a member in r whose window holds (X, Y), of tap_t   (fp32 adds from 0)
+ *   bit          = v > 0, and with `crop` also x1 <= X < x2 && y1 <= Y < y2 of boxes[n,r] (the merged union box, frame pixels)
+ * Pixels that no member tile sees are 0.  The packed layout, the mtbt_frame descriptors (<= 32 images per call; their height, width,
+ * pitch and offset are read, step and scale are ignored), K = top_k planes per image, zero planes for r >= counts[n], zero padding bits
+ * and "every byte written exactly once" are mtbt_masks_to_frames' contract.  No atomics, no memset.  W float [N,top_k,Tmax,32] and Ss
+ * float [N,top_k] are caller-provided and fully written by one small launch (serial sums in the stated order); Tmax >= every T_n.
+ * `tiles` (HOST) / `tiles_dev` (DEVICE) / `first` (HOST [N+1], absolute indices into the tile table; first[0] may be > 0 here) as above.
+ * MTBT_EINVAL before any launch: NULL a / frames / out / member_slot / counts / W / Ss / protos / mc / anchors / scores / tiles /
+ * tiles_dev / first, n_frames outside 1..32 or != N, nm != 32, K < 1, top_k outside 1..65535, hp < 1, hp != wp, Tmax outside 1..64,
+ * out_bytes < 0, crop without boxes, a bad `first` (first[0] < 0, decreasing, T_n > Tmax, T_n K > 4096, first[N] > n_tiles), a bad
+ * descriptor (as above, except `image`; height / width must equal the frame's), then the frame descriptor checks of
+ * mtbt_masks_to_frames.  MTBT_EALIGN for protos / out not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct mtbt_tile_mask_args {
+  const float* protos;        /* [NT,G,G,32] */
+  const float* mc;            /* element (t, channel c, anchor a) at mc[t * mc_batch_stride + a * mc_k_stride + c * mc_c_stride] */
+  int64_t mc_batch_stride, mc_k_stride, mc_c_stride;
+  const int32_t* anchors;     /* [NT,K] */
+  const float* scores;        /* [NT,K] */
+  const int32_t* member_slot; /* [NT,K] */
+  const int32_t* counts;      /* [N] merged */
+  const float* boxes;         /* [N,top_k,4] merged, frame pixels, or NULL */
+  const mtbt_tile* tiles;     /* HOST [n_tiles] */
+  const mtbt_tile* tiles_dev; /* DEVICE [n_tiles] */
+  const int32_t* first;       /* HOST [N+1] */
+  float* W;                   /* [N,top_k,Tmax,32] */
+  float* Ss;                  /* [N,top_k] */
+  uint8_t* out;               /* packed planes of all images, top_k per image */
+  int64_t out_bytes;
+  int32_t N, n_tiles, K, top_k, Tmax, nm, hp, wp, crop, reserved;
+} mtbt_tile_mask_args;
+
+int mtbt_vote_tile_masks(const mtbt_tile_mask_args* a, const mtbt_frame* frames, int n_frames, void* stream);
+/* sizeof() of the three structs above as the library was compiled: which = 0 mtbt_tile, 1 mtbt_tile_merge_args, 2 mtbt_tile_mask_args;
+ * -1 otherwise */
+int mtbt_sizeof_tile_args(int which);
+
+/* ---------------------------------------------------------------------------------------------
  * Multitask loss VALUE (forward only), MultiTaskLitModel._multitask_loss, running_main_v3.py:232-387:
  *   per (image, anchor): trainer decode (:268-290), IoU against the image's GT boxes (:316), positives = max IoU >
  *   iou_thresh (:319-321), sum(1 - IoU) (:331), BCE-with-logits(sum) of the class logits against one-hot /

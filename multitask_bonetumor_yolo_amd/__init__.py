@@ -14,13 +14,14 @@
     from multitask_bonetumor_yolo_amd import save_train_state, load_train_state   # stop a TrainStep and continue it
     from multitask_bonetumor_yolo_amd import detect_fused                # test-time augmentation / ensembles: weighted boxes fusion on the device
     from multitask_bonetumor_yolo_amd import vote_masks                  # instance masks of a fused list, voted over each cluster's members
+    from multitask_bonetumor_yolo_amd import detect_sliced               # sliced inference: tiles of a large image, merged and voted on the device
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
 """
 from . import postprocess, preprocess  # noqa: F401
 from .preprocess import (augment_batch, augment_samples, augment_yolo_labels, letterbox_geometry, mosaic_batch, mosaic_samples,  # noqa: F401
-                         mosaic_yolo_labels, photometric_lut, sample_geometry, sample_mosaic, sample_photometric)
+                         mosaic_yolo_labels, photometric_lut, sample_geometry, sample_mosaic, sample_photometric, slice_batch, slice_geometry)
 from .loss import InstanceMaskLoss, TaskAlignedDetLoss, TaskAlignedSegLoss, instance_mask_loss, multitask_loss, task_aligned_det_loss  # noqa: F401
 from .checkpoints import load_pretrained_heads, load_train_state, save_train_state, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401
@@ -28,6 +29,7 @@ from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, 
                       ImageClassificationMetrics, MeanAveragePrecision, SegmentationMetrics)
 from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
-from .postprocess import vote_masks  # noqa: F401
+from .postprocess import merge_tiles, vote_masks, vote_tile_masks  # noqa: F401
+from .sliced import detect_sliced  # noqa: F401
 from .trainstep import TrainStep, ema_decay_at  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

@@ -187,6 +187,33 @@ class VoteMaskArgs(C.Structure):  # mtbt_vote_mask_args
                 ("nm", C.c_int32), ("hp", C.c_int32), ("wp", C.c_int32), ("crop", C.c_int32)]
 
 
+class Tile(C.Structure):  # mtbt_tile
+    _fields_ = [("image", C.c_int32), ("pox", C.c_int32), ("poy", C.c_int32),
+                ("wx0", C.c_int32), ("wy0", C.c_int32), ("wx1", C.c_int32), ("wy1", C.c_int32),
+                ("height", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
+                ("step", C.c_float), ("scale", C.c_float), ("fox", C.c_float), ("foy", C.c_float)]
+
+
+class TileMergeArgs(C.Structure):  # mtbt_tile_merge_args
+    _fields_ = [("boxes", C.c_void_p), ("scores", C.c_void_p), ("labels", C.c_void_p), ("counts", C.c_void_p), ("anchors", C.c_void_p),
+                ("tiles", C.POINTER(Tile)), ("tiles_dev", C.c_void_p), ("first", C.POINTER(C.c_int32)),
+                ("N", C.c_int32), ("n_tiles", C.c_int32), ("K", C.c_int32), ("top_k", C.c_int32),
+                ("metric", C.c_int32), ("class_agnostic", C.c_int32), ("thr", C.c_float), ("skip_thr", C.c_float),
+                ("out_boxes", C.c_void_p), ("out_scores", C.c_void_p), ("out_labels", C.c_void_p), ("out_counts", C.c_void_p),
+                ("n_members", C.c_void_p), ("lead_tile", C.c_void_p), ("lead_slot", C.c_void_p), ("lead_anchor", C.c_void_p),
+                ("member_slot", C.c_void_p), ("n_left", C.c_void_p)]
+
+
+class TileMaskArgs(C.Structure):  # mtbt_tile_mask_args
+    _fields_ = [("protos", C.c_void_p), ("mc", C.c_void_p),
+                ("mc_batch_stride", C.c_int64), ("mc_k_stride", C.c_int64), ("mc_c_stride", C.c_int64),
+                ("anchors", C.c_void_p), ("scores", C.c_void_p), ("member_slot", C.c_void_p), ("counts", C.c_void_p), ("boxes", C.c_void_p),
+                ("tiles", C.POINTER(Tile)), ("tiles_dev", C.c_void_p), ("first", C.POINTER(C.c_int32)),
+                ("W", C.c_void_p), ("Ss", C.c_void_p), ("out", C.c_void_p), ("out_bytes", C.c_int64),
+                ("N", C.c_int32), ("n_tiles", C.c_int32), ("K", C.c_int32), ("top_k", C.c_int32), ("Tmax", C.c_int32),
+                ("nm", C.c_int32), ("hp", C.c_int32), ("wp", C.c_int32), ("crop", C.c_int32), ("reserved", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -311,11 +338,15 @@ SYMBOLS = {
     "mtbt_fuse_detections_members": (C.c_int, [C.POINTER(BoxFuseArgs), C.c_void_p, C.c_void_p]),
     "mtbt_vote_masks": (C.c_int, [C.POINTER(VoteMaskArgs), C.POINTER(Frame), C.c_int, C.c_void_p]),
     "mtbt_sizeof_vote_mask_args": (C.c_int, []),
+    "mtbt_merge_tiles": (C.c_int, [C.POINTER(TileMergeArgs), C.c_void_p]),
+    "mtbt_vote_tile_masks": (C.c_int, [C.POINTER(TileMaskArgs), C.POINTER(Frame), C.c_int, C.c_void_p]),
+    "mtbt_sizeof_tile_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
 FRAME_STRUCTS = (Frame, FrameMaskArgs)   # order of mtbt_sizeof_frame_args(which)
 MASK_EVAL_STRUCTS = (PackMasksArgs, MaskImage, MaskPairArgs, MaskEvalArgs)   # order of mtbt_sizeof_mask_eval_args(which)
+TILE_STRUCTS = (Tile, TileMergeArgs, TileMaskArgs)   # order of mtbt_sizeof_tile_args(which)
 _lib = None
 
 
@@ -337,7 +368,8 @@ def load():
             if lib.mtbt_sizeof_args(which) != C.sizeof(st):
                 raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {lib.mtbt_sizeof_args(which)}, this binding lays it out in "
                                    f"{C.sizeof(st)} bytes: stale library, rebuild")
-        for sizeof, structs in ((lib.mtbt_sizeof_frame_args, FRAME_STRUCTS), (lib.mtbt_sizeof_mask_eval_args, MASK_EVAL_STRUCTS)):
+        for sizeof, structs in ((lib.mtbt_sizeof_frame_args, FRAME_STRUCTS), (lib.mtbt_sizeof_mask_eval_args, MASK_EVAL_STRUCTS),
+                                (lib.mtbt_sizeof_tile_args, TILE_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

@@ -543,3 +543,159 @@ def unorient_batch(q: torch.Tensor, orient: int) -> torch.Tensor:
     dims = [d for bit, d in ((1, 3), (2, 2)) if orient & bit]
     x = q.flip(dims) if dims else q
     return (x.transpose(2, 3) if orient & 4 else x).contiguous()
+
+
+# ---- sliced inference: merge the detection lists of an image's tiles, vote the masks across them (include/mtbt_hip.h `mtbt_tile`) ----
+TILE_MAX_PER_IMAGE = 64
+MERGE_METRICS = {"iou": 0, "ios": 1}
+_TILE_FIELDS = ("image", "pox", "poy", "wx0", "wy0", "wx1", "wy1", "height", "width", "step", "scale", "fox", "foy")
+
+
+def tile_table(tiles: Sequence[Sequence[dict]], dev=None):
+    """`slice_geometry`'s per-image tile lists -> (host `mtbt_tile` array [NT], `first` int32 [N+1] (ctypes), device copy of the array
+    (uint8 tensor, or None without `dev`))."""
+    flat = [t for per in tiles for t in per]
+    table = (L.Tile * max(len(flat), 1))()
+    for d, t in zip(table, flat):
+        for k in _TILE_FIELDS:
+            setattr(d, k, t[k])
+    first = (C.c_int32 * (len(tiles) + 1))()
+    for n, per in enumerate(tiles):
+        first[n + 1] = first[n] + len(per)
+    dev_copy = None
+    if dev is not None:
+        dev_copy = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+    return table, first, dev_copy
+
+
+def merge_tiles(det: dict, tiles: Sequence[Sequence[dict]], frames, *, metric: str = "ios", thr: float = 0.5, skip_thr: float = 0.0,
+                top_k: int = TOP_K, class_agnostic: bool = False):
+    """The detection lists of an image's tiles merged in the image's own pixel frame (`mtbt_merge_tiles`): one launch, one workgroup per
+    image, no host synchronisation, deterministic.
+
+    `det`: the result of `nms_batched` / `detect_and_segment` over the NT tile canvases of `slice_batch` (boxes [NT,K,4] in each tile's
+    canvas, scores, labels, counts and, for masks, keep_anchor).  `tiles`: `slice_geometry`'s lists.  `frames`: one (H0, W0, ...) per image.
+    A candidate (score > skip_thr) is moved to the frame, clamp((v + tile offset) / tile scale, 0, (W0, H0)); in descending score a
+    candidate that is still free opens a row and absorbs every later free candidate of its label (any label with `class_agnostic`) whose
+    `metric` with the leader's own box exceeds `thr`: "ios" = intersection over the smaller area (a part cut by a tile border is absorbed
+    by the whole), "iou" = the NMS overlap.  A row's box is the union of its members', its score and label the leader's; at most top_k rows.
+
+    Returns dict(boxes_frame [N,top_k,4] (also under "boxes"), scores, labels int64, counts int32 [N], n_members, lead_tile (index into
+    the flat tile table), lead_slot, lead_anchor (with keep_anchor), member_slot int32 [NT,K] (the row a slot opened or joined, else -1),
+    n_left int32 [N] (candidates that were still free when top_k rows were full), tiles)."""
+    lib = L.load()
+    if metric not in MERGE_METRICS:
+        raise ValueError(f"merge_tiles: metric {metric!r} (one of {sorted(MERGE_METRICS)})")
+    for key in ("boxes", "scores", "labels", "counts"):
+        _need_cuda(det[key], "merge_tiles")
+    NT, K = det["scores"].shape
+    N = len(tiles)
+    dev = det["scores"].device
+    if len(frames) != N or sum(len(per) for per in tiles) != NT:
+        raise ValueError(f"merge_tiles: {len(frames)} frames and {sum(len(per) for per in tiles)} tiles for {N} images and {NT} detection lists")
+    for n, (per, fr) in enumerate(zip(tiles, frames)):
+        if len(per) > TILE_MAX_PER_IMAGE or len(per) * K > FUSE_MAX_CANDIDATES or any((t["height"], t["width"]) != (int(fr[0]), int(fr[1])) for t in per):
+            raise ValueError(f"merge_tiles: image {n} has {len(per)} tiles of K = {K} slots ({TILE_MAX_PER_IMAGE} tiles and {FUSE_MAX_CANDIDATES} slots "
+                             f"at most), all of them of its frame {tuple(fr[:2])}")
+    top_k = int(top_k)
+    table, first, table_dev = tile_table(tiles, dev)
+    src = [det["boxes"].contiguous().float(), det["scores"].contiguous().float(), det["labels"].contiguous().to(torch.int64),
+           det["counts"].contiguous().to(torch.int32)]
+    o = {
+        "boxes_frame": torch.empty((N, top_k, 4), dtype=torch.float32, device=dev),
+        "scores": torch.empty((N, top_k), dtype=torch.float32, device=dev),
+        "labels": torch.empty((N, top_k), dtype=torch.int64, device=dev),
+        "counts": torch.empty((N,), dtype=torch.int32, device=dev),
+        "n_members": torch.empty((N, top_k), dtype=torch.int32, device=dev),
+        "lead_tile": torch.empty((N, top_k), dtype=torch.int32, device=dev),
+        "lead_slot": torch.empty((N, top_k), dtype=torch.int32, device=dev),
+        "member_slot": torch.empty((NT, K), dtype=torch.int32, device=dev),
+        "n_left": torch.empty((N,), dtype=torch.int32, device=dev),
+    }
+    a = L.TileMergeArgs()
+    a.boxes, a.scores, a.labels, a.counts = (t.data_ptr() for t in src)
+    if "keep_anchor" in det:
+        src.append(det["keep_anchor"].contiguous().to(torch.int32))
+        o["lead_anchor"] = torch.empty((N, top_k), dtype=torch.int32, device=dev)
+        a.anchors, a.lead_anchor = src[4].data_ptr(), o["lead_anchor"].data_ptr()
+    a.tiles, a.tiles_dev, a.first = table, table_dev.data_ptr(), first
+    a.N, a.n_tiles, a.K, a.top_k = N, NT, K, top_k
+    a.metric, a.class_agnostic, a.thr, a.skip_thr = MERGE_METRICS[metric], int(bool(class_agnostic)), float(thr), float(skip_thr)
+    a.out_boxes, a.out_scores, a.out_labels, a.out_counts = o["boxes_frame"].data_ptr(), o["scores"].data_ptr(), o["labels"].data_ptr(), o["counts"].data_ptr()
+    a.n_members, a.lead_tile, a.lead_slot = o["n_members"].data_ptr(), o["lead_tile"].data_ptr(), o["lead_slot"].data_ptr()
+    a.member_slot, a.n_left = o["member_slot"].data_ptr(), o["n_left"].data_ptr()
+    with torch.cuda.device(dev):
+        L.check(lib.mtbt_merge_tiles(C.byref(a), _stream(dev)), "mtbt_merge_tiles")
+    o["boxes"] = o["boxes_frame"]
+    o["tiles"] = tiles
+    o["_keep"] = (src, table, first, table_dev)
+    return o
+
+
+def vote_tile_masks(merged: dict, det: dict, mc: torch.Tensor, protos: torch.Tensor, tiles: Sequence[Sequence[dict]], frames,
+                    crop: bool = False, out: Optional[torch.Tensor] = None):
+    """Instance masks of merged rows, voted across the tiles of their members straight into the bit-packed frame planes
+    (`mtbt_vote_tile_masks`).  `merged`: the result of `merge_tiles(det, tiles, frames)` of a `det` with keep_anchor; mc [NT,32,A] fp32
+    and protos [NT,32,G,G] are the tiles' mask coefficients and prototypes, tile-major as `det`.
+
+      W[n,r,t,:] = sum over row r's members in tile t of score * coefficients, divided by the row's sum of scores
+      mask bit   = sum over the tiles with a window over the pixel, ascending, of the bilinear tap of W[n,r,t,:] . protos_t at the
+                   pixel's place in that tile > 0 (and inside the merged box with `crop`); pixels no member tile sees are 0
+
+    Returns what `masks_to_frames` returns ("boxes": the merged frame boxes, "masks": uint8 [top_k, H0_n, pitch_n] views, "buffer") plus
+    "vote_coeff" (W, float32 [N,top_k,Tmax,32]) and "vote_weight" (float32 [N,top_k]).  No host synchronisation."""
+    lib = L.load()
+    if "keep_anchor" not in det:
+        raise ValueError("vote_tile_masks: `det` has no keep_anchor")
+    member_slot, counts, boxes = merged["member_slot"], merged["counts"], merged["boxes_frame"]
+    _need_cuda(protos, "vote_tile_masks")
+    dev = member_slot.device
+    N, top_k = merged["scores"].shape
+    NT, K = member_slot.shape
+    pr, ld = _nhwc_rows(protos)
+    nm, hp, wp = protos.shape[1:]
+    if ld != nm:
+        pr = pr.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    mc = mc.float()
+    if protos.shape[0] != NT or mc.shape[0] != NT or mc.shape[1] != nm or nm != 32 or hp != wp:
+        raise ValueError(f"vote_tile_masks: protos {tuple(protos.shape)} and mc {tuple(mc.shape)}; expected [{NT}, 32, G, G] and [{NT}, 32, A]")
+    if len(frames) != N or len(tiles) != N or sum(len(per) for per in tiles) != NT:
+        raise ValueError(f"vote_tile_masks: {len(frames)} frames and {len(tiles)} tile lists for {N} images, {NT} tiles")
+    Tmax = max(1, max(len(per) for per in tiles))
+    rows, total = [], 0
+    for fr in frames:
+        H0, W0 = int(fr[0]), int(fr[1])
+        pitch = 8 * ((W0 + 63) // 64)
+        rows.append((H0, W0, pitch, total))
+        total = (total + top_k * H0 * pitch + 15) // 16 * 16
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total or out.device != dev:
+        raise ValueError(f"vote_tile_masks: out must be a contiguous flat uint8 buffer of at least {total} bytes on {dev}")
+    if merged.get("tiles") is tiles and "_keep" in merged:
+        table, first, table_dev = merged["_keep"][1:4]           # the table `merge_tiles` built and uploaded
+    else:
+        table, first, table_dev = tile_table(tiles, dev)
+    scores, anchors = det["scores"].contiguous().float(), det["keep_anchor"].contiguous().to(torch.int32)
+    boxes = boxes.contiguous().float()
+    W = torch.empty((N, top_k, Tmax, 32), dtype=torch.float32, device=dev)
+    Ss = torch.empty((N, top_k), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        for c0 in range(0, N, MAX_FRAMES):
+            nb = min(MAX_FRAMES, N - c0)
+            a = L.TileMaskArgs()
+            a.protos, a.mc = pr.data_ptr(), mc.data_ptr()
+            a.mc_batch_stride, a.mc_k_stride, a.mc_c_stride = mc.stride(0), mc.stride(2), mc.stride(1)
+            a.anchors, a.scores, a.member_slot = anchors.data_ptr(), scores.data_ptr(), member_slot.data_ptr()
+            a.counts, a.boxes = counts[c0:].data_ptr(), boxes[c0:].data_ptr()
+            a.tiles, a.tiles_dev = table, table_dev.data_ptr()
+            a.first = C.cast(C.byref(first, 4 * c0), C.POINTER(C.c_int32))
+            a.W, a.Ss = W[c0:].data_ptr(), Ss[c0:].data_ptr()
+            a.out, a.out_bytes = out.data_ptr(), out.numel()
+            a.N, a.n_tiles, a.K, a.top_k, a.Tmax, a.nm, a.hp, a.wp, a.crop = nb, NT, K, top_k, Tmax, 32, hp, wp, int(bool(crop))
+            fr = (L.Frame * nb)()
+            for i, (H0, W0, pitch, off) in enumerate(rows[c0:c0 + nb]):
+                fr[i].height, fr[i].width, fr[i].step, fr[i].scale, fr[i].pitch, fr[i].offset = H0, W0, 1.0, 1.0, pitch, off
+            L.check(lib.mtbt_vote_tile_masks(C.byref(a), fr, nb, _stream(dev)), "mtbt_vote_tile_masks")
+    views = [out[off:off + top_k * H0 * pitch].view(top_k, H0, pitch) for H0, W0, pitch, off in rows]
+    return {"boxes": boxes, "masks": views, "buffer": out, "vote_coeff": W, "vote_weight": Ss, "_keep": (table, first, table_dev, pr, mc, scores, anchors)}

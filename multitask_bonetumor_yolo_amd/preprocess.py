@@ -374,3 +374,70 @@ def mosaic_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Opti
     rows = [mosaic_yolo_labels([rows_per_image[k] for k in index[i]], [sizes[k] for k in index[i]], geom[i], centres[i], img_size, **lab)
             for i in range(len(images))]
     return imgs, out_masks, collate_boxes(rows, device=imgs.device)
+
+
+# ---- sliced inference: overlapping tiles of a large image (the project's own definition: include/mtbt_hip.h `mtbt_tile`) ----
+def _axis_origins(L: int, S: int, overlap: float, up: int) -> List[int]:
+    """Tile origins along an axis of resized length L: one at 0 if L <= S, else ceil((L - S overlap) / (S (1 - overlap))) spread evenly
+    from 0 to L - S, each rounded down to a multiple of `up`, the last one rounded up (the end is covered, the overhang is pad)."""
+    if L <= S:
+        return [0]
+    n = max(2, math.ceil((L - S * overlap) / (S * (1.0 - overlap))))
+    out = [int(i * (L - S) / (n - 1)) // up * up for i in range(n - 1)]
+    return out + [-(-(L - S) // up) * up]
+
+
+def _window(o: int, S: int, new: int, z: float, extent: int):
+    """The frame pixels X whose centre (X + 0.5) z lies in [o, min(o + S, new)), half-open, clamped to the image; the tile that reaches the
+    end of the resized axis takes the pixels up to the image's edge (int(extent z) may cut the last centre off)."""
+    lo = max(0, math.ceil(o / z - 0.5))
+    hi = extent if o + S >= new else min(extent, math.ceil(min(o + S, new) / z - 0.5))
+    return lo, max(hi, lo)
+
+
+def _tile(image: int, H0: int, W0: int, z: float, ox: int, oy: int, S: int, up: int) -> dict:
+    new_w, new_h = max(1, int(W0 * z)), max(1, int(H0 * z))
+    wx0, wx1 = _window(ox, S, new_w, z, W0)
+    wy0, wy1 = _window(oy, S, new_h, z, H0)
+    return {"image": image, "pox": ox // up, "poy": oy // up, "wx0": wx0, "wy0": wy0, "wx1": wx1, "wy1": wy1, "height": H0, "width": W0,
+            "step": C.c_float(z / up).value, "scale": C.c_float(z).value, "fox": float(ox), "foy": float(oy), "zoom": z, "ox": ox, "oy": oy,
+            "geom": [new_w, new_h, -ox, -oy, 0, 0, 0, 0]}
+
+
+def slice_geometry(sizes: Sequence[Sequence[int]], img_size: int, zoom: float = 1.0, overlap: float = 0.2, full_view: bool = True,
+                   up: int = 4) -> List[List[dict]]:
+    """The tiles of sliced inference.  sizes: (H0, W0) per image.  A pass at `zoom` resizes the image by the letterbox's rule
+    (new = max(1, int(dim * zoom)); never materialised) and cuts it into S x S tiles (S = img_size) that overlap by about `overlap` of
+    S, row-major, origins multiples of `up` (letterboxed pixels per prototype pixel, S / G); with `full_view` the whole image at
+    S / max(H0, W0) -- the plain letterbox -- comes last, unless the pass is one tile already.  Returns per image the list of its tiles:
+    dicts of the `mtbt_tile` fields (image, pox, poy, window wx0 wy0 wx1 wy1 half-open in image pixels, height, width, step =
+    float32(zoom / up) which must lie in (0, 1], scale = float32(zoom), fox, foy) plus `geom`, the `augment_batch` row (new_w, new_h,
+    -ox, -oy, 0, 0, 0, 0) that draws the tile, and zoom / ox / oy."""
+    S, up = int(img_size), int(up)
+    if not 0.0 <= overlap < 1.0 or zoom <= 0 or S % up:
+        raise ValueError(f"slice_geometry: overlap {overlap} (0 <= overlap < 1), zoom {zoom} (> 0), img_size {S} (a multiple of up = {up})")
+    out = []
+    for n, (H0, W0) in enumerate(sizes):
+        H0, W0 = int(H0), int(W0)
+        new_w, new_h = max(1, int(W0 * zoom)), max(1, int(H0 * zoom))
+        tiles = [_tile(n, H0, W0, float(zoom), ox, oy, S, up) for oy in _axis_origins(new_h, S, overlap, up) for ox in _axis_origins(new_w, S, overlap, up)]
+        if full_view and len(tiles) > 1:
+            tiles.append(_tile(n, H0, W0, S / max(H0, W0), 0, 0, S, up))
+        for t in tiles:
+            if not 0.0 < t["step"] <= 1.0:
+                raise ValueError(f"slice_geometry: image {n} ({H0} x {W0}) at zoom {t['zoom']} gives {t['step']} prototype pixels per image pixel; "
+                                 "the supported range is 0 < zoom / up <= 1")
+        if len(tiles) > 64:
+            raise ValueError(f"slice_geometry: image {n} ({H0} x {W0}) needs {len(tiles)} tiles (64 at most): lower zoom or raise img_size")
+        out.append(tiles)
+    return out
+
+
+def slice_batch(images: Sequence[torch.Tensor], tiles: Sequence[Sequence[dict]], img_size: int = 640) -> torch.Tensor:
+    """The canvases of `slice_geometry`'s tiles, [NT,3,S,S] f32 RGB in [0,1], tile-major in the order of `tiles`: `augment_batch` with each
+    tile's geometry row and its image's descriptor repeated (no new pixel kernel, no table)."""
+    if len(tiles) != len(images):
+        raise ValueError(f"slice_batch: {len(tiles)} tile lists for {len(images)} images")
+    flat = [t for per in tiles for t in per]
+    geom = np.asarray([t["geom"] for t in flat], dtype=np.int32).reshape(len(flat), GEOM_FIELDS)
+    return augment_batch([images[t["image"]] for t in flat], None, geom, None, img_size)[0]
