@@ -1089,6 +1089,52 @@ int mtbt_mask_eval(const mtbt_mask_eval_args* args, void* stream);
  * 2 mtbt_mask_pair_args, 3 mtbt_mask_eval_args; -1 otherwise */
 int mtbt_sizeof_mask_eval_args(int which);
 
+/* ---------------------------------------------------------------------------------------------
+ * Surface distances between pairs of bit-packed planes (csrc/surface_dist.hip): the records from which the host forms the
+ * Hausdorff distance, its percentile, the average symmetric surface distance and the normalised surface Dice (MedPy's
+ * definitions; `metrics.SurfaceDistanceMetrics`).  Packed layout and alignment as in the section above (planes 8-byte aligned,
+ * 8-byte accesses only); bits X >= W never count, whatever they hold.
+ * For a plane M its EDGE SET dM holds the set pixels with at least one of their four neighbours unset or outside the image
+ * (M ^ binary_erosion(M, 4-connected cross, border_value = 0)).  For a pair (A, B) the directed list A->B holds, for every pixel
+ * of dA in row-major order, d2 = min over dB of (dy^2 + dx^2), an exact integer below 2^29; B->A likewise; the pooled list is A->B
+ * followed by B->A.  A pair with dA or dB empty is UNDEFINED: all its records are zero, n_edge apart.
+ *   a, b      [n][H][pitch] packed planes
+ *   tol2      squared tolerance in pixels: n_within counts d2 <= tol2
+ *   Q, q[]    0..4 quantiles, each in [0, 1]
+ *   n_edge    uint32 [n][2]        |dA|, |dB|
+ *   max_d2    uint32 [n][2]        largest d2 of A->B, of B->A
+ *   n_within  uint32 [n][2]        items with d2 <= tol2 of A->B, of B->A
+ *   sum_d     double [n][2]        sum of sqrt(d2) in a fixed order: the same inputs give the same bits on every run
+ *   rank_d2   uint32 [n][Q][3][2]  for the segments A->B, B->A, pooled of length m: the order statistics (0-based, ascending) at
+ *                                  lo = floor(q * (m - 1)) and min(lo + 1, m - 1), q * (m - 1) being ONE IEEE double product (the
+ *                                  host recomputes it for the interpolation weight); zeros for m == 0.  May be NULL when Q == 0.
+ * Every output word is defined after the call: the caller does not pre-zero.  Asynchronous on `stream`, no host synchronisation,
+ * no global atomics, deterministic, graph-capturable.  The pairs are taken in groups that share `workspace`
+ * (>= mtbt_surface_distances_workspace_bytes(n, H, W), 16-byte aligned; the query returns MTBT_EINVAL for a shape refused below).
+ * MTBT_EINVAL before any launch: NULL a or a NULL pointer member (rank_d2 only with Q > 0, workspace only when the query is > 0),
+ * n < 0, H or W outside [1, 16384], pitch != 8 * ceil(W / 64), Q outside [0, 4], a q outside [0, 1] or NaN, workspace_bytes below
+ * the query.  MTBT_EALIGN: a / b / sum_d not 8-byte, workspace not 16-byte, the other outputs not 4-byte aligned.  n == 0 launches
+ * nothing. */
+typedef struct mtbt_surface_args {
+  const uint8_t* a;        /* [n][H][pitch] */
+  const uint8_t* b;        /* [n][H][pitch] */
+  void* workspace;
+  int64_t workspace_bytes;
+  uint32_t* n_edge;        /* [n][2] */
+  uint32_t* max_d2;        /* [n][2] */
+  uint32_t* n_within;      /* [n][2] */
+  double* sum_d;           /* [n][2] */
+  uint32_t* rank_d2;       /* [n][Q][3][2] */
+  double q[4];
+  int32_t n, H, W, pitch;
+  uint32_t tol2;
+  int32_t Q;
+} mtbt_surface_args;
+int64_t mtbt_surface_distances_workspace_bytes(int n, int H, int W);
+int mtbt_surface_distances(const mtbt_surface_args* a, void* stream);
+/* sizeof() of the struct above as the library was compiled: which = 0 mtbt_surface_args; -1 otherwise */
+int mtbt_sizeof_surface_args(int which);
+
 /* Weight gradient of a k x k convolution (any stride / padding; 1x1 and the 2x2 stride-2 downsample included), bf16 (MFMA) or fp32 operands:
  *   dw[k][r][s][c] (fp32, packed [K][R*S*C] like the forward weight) (+)= sum_p dy[p][k] * x[n][y*stride + r - pad][x*stride + s - pad][c]
  * x [N,H,W,C], dy [N,Ho,Wo,K] (Ho = (H + 2 pad - R) / stride + 1) NHWC with pixel / batch strides in elements (multiples of 8; C % 8 == K % 8 == 0;

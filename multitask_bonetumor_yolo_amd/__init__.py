@@ -15,6 +15,7 @@
     from multitask_bonetumor_yolo_amd import detect_fused                # test-time augmentation / ensembles: weighted boxes fusion on the device
     from multitask_bonetumor_yolo_amd import vote_masks                  # instance masks of a fused list, voted over each cluster's members
     from multitask_bonetumor_yolo_amd import detect_sliced               # sliced inference: tiles of a large image, merged and voted on the device
+    from multitask_bonetumor_yolo_amd import SurfaceDistanceMetrics      # Hausdorff / HD95 / ASSD / surface Dice from packed masks, on the device
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
@@ -26,7 +27,8 @@ from .loss import InstanceMaskLoss, TaskAlignedDetLoss, TaskAlignedSegLoss, inst
 from .checkpoints import load_pretrained_heads, load_train_state, save_train_state, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision,  # noqa: F401
-                      ImageClassificationMetrics, MeanAveragePrecision, SegmentationMetrics)
+                      ImageClassificationMetrics, MeanAveragePrecision, SegmentationMetrics, SurfaceDistanceMetrics, surface_distances,
+                      surface_metrics)
 from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
 from .postprocess import merge_tiles, vote_masks, vote_tile_masks  # noqa: F401

@@ -214,6 +214,13 @@ class TileMaskArgs(C.Structure):  # mtbt_tile_mask_args
                 ("nm", C.c_int32), ("hp", C.c_int32), ("wp", C.c_int32), ("crop", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SurfaceArgs(C.Structure):  # mtbt_surface_args
+    _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("n_edge", C.c_void_p), ("max_d2", C.c_void_p), ("n_within", C.c_void_p), ("sum_d", C.c_void_p), ("rank_d2", C.c_void_p),
+                ("q", C.c_double * 4), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32),
+                ("tol2", C.c_uint32), ("Q", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -341,12 +348,16 @@ SYMBOLS = {
     "mtbt_merge_tiles": (C.c_int, [C.POINTER(TileMergeArgs), C.c_void_p]),
     "mtbt_vote_tile_masks": (C.c_int, [C.POINTER(TileMaskArgs), C.POINTER(Frame), C.c_int, C.c_void_p]),
     "mtbt_sizeof_tile_args": (C.c_int, [C.c_int]),
+    "mtbt_surface_distances_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mtbt_surface_distances": (C.c_int, [C.POINTER(SurfaceArgs), C.c_void_p]),
+    "mtbt_sizeof_surface_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
 FRAME_STRUCTS = (Frame, FrameMaskArgs)   # order of mtbt_sizeof_frame_args(which)
 MASK_EVAL_STRUCTS = (PackMasksArgs, MaskImage, MaskPairArgs, MaskEvalArgs)   # order of mtbt_sizeof_mask_eval_args(which)
 TILE_STRUCTS = (Tile, TileMergeArgs, TileMaskArgs)   # order of mtbt_sizeof_tile_args(which)
+SURFACE_STRUCTS = (SurfaceArgs,)   # order of mtbt_sizeof_surface_args(which)
 _lib = None
 
 
@@ -369,7 +380,7 @@ def load():
                 raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {lib.mtbt_sizeof_args(which)}, this binding lays it out in "
                                    f"{C.sizeof(st)} bytes: stale library, rebuild")
         for sizeof, structs in ((lib.mtbt_sizeof_frame_args, FRAME_STRUCTS), (lib.mtbt_sizeof_mask_eval_args, MASK_EVAL_STRUCTS),
-                                (lib.mtbt_sizeof_tile_args, TILE_STRUCTS)):
+                                (lib.mtbt_sizeof_tile_args, TILE_STRUCTS), (lib.mtbt_sizeof_surface_args, SURFACE_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

@@ -25,6 +25,10 @@ torchmetrics' binary stat-score definitions.
                           the confusion matrix of the eval-mode loss's matched anchors (:218, :349-350, :710-722), counted on the
                           device by the loss's own decode and match (`mtbt_det_confusion`).
 
+  SurfaceDistanceMetrics  boundary metrics of binary segmentation -- Hausdorff distance, HD95, average symmetric surface distance, normalised
+                          surface Dice (MedPy's definitions; nothing in the reference computes them) -- from device-side records of
+                          bit-packed masks (`mtbt_surface_distances`: edge sets, exact integer squared distances, order statistics).
+
 The two box classes and the segmentation mAP differ only in how they match; all three accumulate and summarise (pycocotools
 `accumulate` / `summarize`) through one vectorised numpy function, `_accumulate`, once per epoch.
 
@@ -903,3 +907,200 @@ class DetectionConfusionMatrix(_ConfusionCounts):
     def compute(self) -> Dict[str, object]:
         cm = self.counts()
         return {"confusion_matrix": _normalize_rows(cm), "confusion_counts": cm}
+
+
+# ---- surface distances ------------------------------------------------------------------------------------------------------------
+SURFACE_MAX_DIM = 16384          # H and W of mtbt_surface_distances (squared distances stay below 2^29)
+SURFACE_MAX_QUANTILES = 4
+
+
+def surface_tol2(tolerance: float, spacing: float = 1.0) -> int:
+    """The integer the device compares squared pixel distances with: d <= tolerance  <=>  d^2 <= floor((tolerance / spacing)^2)."""
+    if not (spacing > 0) or not (tolerance >= 0):
+        raise ValueError("surface_tol2: spacing must be > 0 and tolerance >= 0")
+    return int(min(np.floor((float(tolerance) / float(spacing)) ** 2), 2.0 ** 32 - 1))
+
+
+def surface_distances(a_packed: torch.Tensor, b_packed: torch.Tensor, W: int, *, quantiles: Sequence[float] = (0.95,), tol2: int = 0):
+    """Surface-distance records of n pairs of bit-packed planes, on the device (`mtbt_surface_distances`; definitions in
+    include/mtbt_hip.h: 4-neighbour edge sets, exact integer squared distances from every edge pixel of one plane to the other's edge set).
+
+    a_packed, b_packed: uint8 [n, H, pitch] with pitch = 8 * ceil(W / 64) (`pack_masks`, `masks_to_frames`); bits X >= W never count.
+    Returns a dict of device tensors -- n_edge, max_d2, n_within int32 [n, 2] (A->B, B->A; the values are below 2^31), sum_d float64
+    [n, 2], rank_d2 int32 [n, Q, 3, 2] (A->B, B->A, pooled; the order statistics at floor(q (m - 1)) and the next) -- plus the host
+    values `quantiles`, `tol2` and `shape` = (H, W) that `surface_metrics` needs.  Asynchronous: no host synchronisation."""
+    for t in (a_packed, b_packed):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError("surface_distances: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+    W = int(W)
+    if a_packed.dim() != 3 or a_packed.dtype != torch.uint8 or b_packed.dtype != torch.uint8 or a_packed.shape != b_packed.shape:
+        raise ValueError("surface_distances: a_packed and b_packed must be uint8 [n, H, pitch] of the same shape")
+    if a_packed.device != b_packed.device:
+        raise ValueError("surface_distances: the two sides are on different devices")
+    n, H, pitch = (int(v) for v in a_packed.shape)
+    if not (1 <= H <= SURFACE_MAX_DIM and 1 <= W <= SURFACE_MAX_DIM):
+        raise ValueError(f"surface_distances: planes of {H} x {W} pixels (1 <= H, W <= {SURFACE_MAX_DIM})")
+    if pitch != _mask_pitch(W):
+        raise ValueError(f"surface_distances: packed planes of width {W} are uint8 [n, H, {_mask_pitch(W)}]")
+    q = tuple(float(v) for v in quantiles)
+    if len(q) > SURFACE_MAX_QUANTILES or any(not 0.0 <= v <= 1.0 for v in q):
+        raise ValueError(f"surface_distances: at most {SURFACE_MAX_QUANTILES} quantiles, each in [0, 1]")
+    tol2 = int(tol2)
+    if not 0 <= tol2 < 2 ** 32:
+        raise ValueError("surface_distances: tol2 must fit an unsigned 32-bit integer")
+    dev = a_packed.device
+    Q = len(q)
+    out = {"n_edge": torch.empty((n, 2), dtype=torch.int32, device=dev), "max_d2": torch.empty((n, 2), dtype=torch.int32, device=dev),
+           "n_within": torch.empty((n, 2), dtype=torch.int32, device=dev), "sum_d": torch.empty((n, 2), dtype=torch.float64, device=dev),
+           "rank_d2": torch.empty((n, Q, 3, 2), dtype=torch.int32, device=dev), "quantiles": q, "tol2": tol2, "shape": (H, W)}
+    if n == 0:
+        return out
+    lib = L.load()
+    planes = []
+    for t in (a_packed, b_packed):
+        t = t.contiguous()
+        planes.append(t if t.data_ptr() % 8 == 0 else t.clone())
+    ws_bytes = int(lib.mtbt_surface_distances_workspace_bytes(n, H, W))
+    if ws_bytes < 0:
+        L.check(ws_bytes, "mtbt_surface_distances_workspace_bytes")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    a = L.SurfaceArgs()
+    a.a, a.b, a.workspace, a.workspace_bytes = planes[0].data_ptr(), planes[1].data_ptr(), ws.data_ptr(), ws_bytes
+    a.n_edge, a.max_d2, a.n_within, a.sum_d = (out[k].data_ptr() for k in ("n_edge", "max_d2", "n_within", "sum_d"))
+    a.rank_d2 = out["rank_d2"].data_ptr() if Q else None
+    for i, v in enumerate(q):
+        a.q[i] = v
+    a.n, a.H, a.W, a.pitch, a.tol2, a.Q = n, H, W, pitch, tol2, Q
+    with torch.cuda.device(dev):
+        L.check(lib.mtbt_surface_distances(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_surface_distances")
+    return out
+
+
+SURFACE_KEYS = ("hd", "hd95", "assd", "nsd")
+
+
+def surface_metrics(records: Dict[str, object], *, spacing: float = 1.0, tolerance: float = 2.0, percentile_mode: str = "pooled",
+                    undefined: str = "skip", quantile_index: int = 0) -> Dict[str, np.ndarray]:
+    """Per-pair hd, hd95, assd, nsd and `defined` from the records of `surface_distances` (host arrays or tensors); pure host code.
+
+    With d = spacing * sqrt(d2): hd = the largest d of both directed lists; hd95 = the `quantiles[quantile_index]` percentile with
+    linear interpolation (numpy's default) of the pooled list (`percentile_mode="pooled"`, MedPy's hd95) or the larger of the two
+    directed percentiles ("max", MONAI's); assd = (mean(A->B) + mean(B->A)) / 2; nsd = the share of both lists with
+    d2 <= floor((tolerance / spacing)^2), which must be the `tol2` the records were made with.
+    A pair with an empty edge set is undefined: `defined` is False and its four values are NaN (`undefined="skip"`); under
+    `undefined="diagonal"` a pair with exactly ONE empty side gets spacing * sqrt(H^2 + W^2) for hd, hd95 and assd and 0 for nsd
+    (`defined` stays False; a pair with both sides empty stays NaN)."""
+    if percentile_mode not in ("pooled", "max"):
+        raise ValueError(f"percentile_mode: 'pooled' (MedPy) or 'max' (MONAI), not {percentile_mode!r}")
+    if undefined not in ("skip", "diagonal"):
+        raise ValueError(f"undefined: 'skip' or 'diagonal', not {undefined!r}")
+    if surface_tol2(tolerance, spacing) != int(records["tol2"]):
+        raise ValueError(f"surface_metrics: tolerance {tolerance} at spacing {spacing} is tol2 = {surface_tol2(tolerance, spacing)}, "
+                         f"the records were made with tol2 = {records['tol2']}")
+    np_ = lambda k, dt: MeanAveragePrecision._np(records[k], dt)
+    n_edge = np_("n_edge", np.int64).reshape(-1, 2)
+    n = len(n_edge)
+    max_d2, within, sum_d = np_("max_d2", np.int64).reshape(n, 2), np_("n_within", np.int64).reshape(n, 2), np_("sum_d", np.float64).reshape(n, 2)
+    spacing = float(spacing)
+    nA, nB = n_edge[:, 0], n_edge[:, 1]
+    defined = (nA > 0) & (nB > 0)
+    one = np.maximum(n_edge, 1).astype(np.float64)
+    out = {"hd": spacing * np.sqrt(max_d2.max(axis=1).astype(np.float64)),
+           "assd": spacing * 0.5 * (sum_d[:, 0] / one[:, 0] + sum_d[:, 1] / one[:, 1]),
+           "nsd": within.sum(axis=1) / np.maximum(nA + nB, 1).astype(np.float64)}
+    if len(records["quantiles"]):
+        q = float(records["quantiles"][quantile_index])
+        rank = spacing * np.sqrt(np_("rank_d2", np.float64).reshape(n, len(records["quantiles"]), 3, 2)[:, quantile_index])   # [n, 3, 2]
+        m = np.stack([nA, nB, nA + nB], 1)
+        pos = q * np.maximum(m - 1, 0).astype(np.float64)                        # the product the kernel formed
+        t = pos - np.floor(pos)
+        diff = rank[:, :, 1] - rank[:, :, 0]
+        pct = np.where(t >= 0.5, rank[:, :, 1] - diff * (1 - t), rank[:, :, 0] + diff * t)        # numpy's _lerp
+        out["hd95"] = pct[:, 2] if percentile_mode == "pooled" else pct[:, :2].max(axis=1)
+    else:
+        out["hd95"] = np.full(n, np.nan)
+    H, W = records["shape"]
+    diag = spacing * float(np.sqrt(float(H) ** 2 + float(W) ** 2))
+    one_empty = (nA > 0) ^ (nB > 0)
+    for k in SURFACE_KEYS:
+        v = np.where(defined, out[k], np.nan)
+        if undefined == "diagonal":
+            v = np.where(one_empty, 0.0 if k == "nsd" else diag, v)
+        out[k] = v
+    out["defined"] = defined
+    return out
+
+
+class SurfaceDistanceMetrics:
+    """Boundary metrics of binary segmentation -- Hausdorff distance, its `quantile` percentile (HD95), average symmetric surface
+    distance and normalised surface Dice at `tolerance` -- with MedPy's definitions (`surface_metrics`) from device-side records
+    (`surface_distances`: 4-neighbour edge sets, exact integer squared distances).  Isotropic `spacing` only.
+
+    `update(seg_logits, masks_gt)`: [B,1,S,S] or [B,S,S] device tensors.  Prediction bit = logit > 0, target bit = masks_gt >= 1 (the
+    rule of `mtbt_seg_confusion`); both sides are packed by `pack_masks`.  logit > 0 differs from sigmoid(logit) > 0.5 in fp32 only
+    for 0 < logit <~ 6e-8, where the sigmoid rounds to exactly 0.5.  Asynchronous: the records stay on the device.
+    `update_packed(a, b, W)`: pairs of packed planes uint8 [n, H, pitch], e.g. `masks_frame` against packed ground truth for pairs
+    the caller has matched.
+    `per_image(sync=False)` -> per-pair arrays hd, hd95, assd, nsd (NaN where a pair does not contribute) and `defined`.
+    `compute()` -> the means of hd, hd95, assd, nsd over the contributing pairs (-1.0 when there is none), n_pairs and n_undefined
+    (pairs with an empty edge set, whatever `undefined` does with them).  With a live process group (and `dist_sync`): over the
+    pairs of ALL ranks in rank order -- a collective, every rank must call it."""
+
+    def __init__(self, quantile: float = 0.95, tolerance: float = 2.0, spacing: float = 1.0, percentile_mode: str = "pooled",
+                 undefined: str = "skip", dist_sync: bool = True, process_group=None):
+        if not 0.0 <= float(quantile) <= 1.0:
+            raise ValueError(f"SurfaceDistanceMetrics: quantile {quantile!r} is not in [0, 1]")
+        if percentile_mode not in ("pooled", "max"):
+            raise ValueError(f"SurfaceDistanceMetrics: percentile_mode 'pooled' (MedPy) or 'max' (MONAI), not {percentile_mode!r}")
+        if undefined not in ("skip", "diagonal"):
+            raise ValueError(f"SurfaceDistanceMetrics: undefined 'skip' or 'diagonal', not {undefined!r}")
+        self.quantile, self.tolerance, self.spacing = float(quantile), float(tolerance), float(spacing)
+        self.tol2 = surface_tol2(self.tolerance, self.spacing)
+        self.percentile_mode, self.undefined = percentile_mode, undefined
+        self.dist_sync, self.group = dist_sync, process_group
+        self.reset()
+
+    def reset(self):
+        self._records: List[Dict[str, object]] = []
+
+    def update_packed(self, a: torch.Tensor, b: torch.Tensor, W: int):
+        """Asynchronous: launches on the current stream and keeps its records on the device."""
+        rec = surface_distances(a, b, W, quantiles=(self.quantile,), tol2=self.tol2)
+        if rec["n_edge"].shape[0]:
+            self._records.append(rec)
+
+    def update(self, seg_logits: torch.Tensor, masks_gt: torch.Tensor):
+        from .postprocess import pack_masks
+        if not (isinstance(seg_logits, torch.Tensor) and isinstance(masks_gt, torch.Tensor) and seg_logits.is_cuda and masks_gt.is_cuda):
+            raise RuntimeError("SurfaceDistanceMetrics.update: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+        if seg_logits.shape != masks_gt.shape:
+            raise ValueError("SurfaceDistanceMetrics.update: logits and masks differ in shape")
+        if seg_logits.dim() == 4 and seg_logits.shape[1] == 1:
+            seg_logits, masks_gt = seg_logits[:, 0], masks_gt[:, 0]
+        if seg_logits.dim() != 3:
+            raise ValueError("SurfaceDistanceMetrics.update: logits and masks must be [B,1,S,S] or [B,S,S]")
+        if seg_logits.shape[0] == 0:
+            return
+        self.update_packed(pack_masks(seg_logits.float()), pack_masks(masks_gt >= 1), seg_logits.shape[2])
+
+    def per_image(self, sync: bool = False) -> Dict[str, np.ndarray]:
+        parts = []
+        for rec in self._records:
+            host = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else v) for k, v in rec.items()}
+            parts.append(surface_metrics(host, spacing=self.spacing, tolerance=self.tolerance, percentile_mode=self.percentile_mode,
+                                         undefined=self.undefined))
+        keys = SURFACE_KEYS + ("defined",)
+        out = {k: np.concatenate([np.zeros(0, bool if k == "defined" else np.float64)] + [p[k] for p in parts]) for k in keys}
+        if sync and _world(self.group) > 1:
+            recs = _all_gather_records([out], self.group)
+            out = {k: np.concatenate([r[k] for r in recs]) for k in keys}
+        return out
+
+    def compute(self) -> Dict[str, float]:
+        per = self.per_image(sync=self.dist_sync)
+        out: Dict[str, float] = {}
+        for k in SURFACE_KEYS:
+            v = per[k][~np.isnan(per[k])]
+            out[k] = float(v.mean()) if v.size else -1.0
+        out["n_pairs"], out["n_undefined"] = int(len(per["defined"])), int(np.count_nonzero(~per["defined"]))
+        return out

@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .loss import instance_mask_loss, multitask_loss, task_aligned_det_loss
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision, ImageClassificationMetrics,
-                      SegmentationMetrics, _sum_over_ranks)
+                      SegmentationMetrics, SurfaceDistanceMetrics, _sum_over_ranks)
 from .postprocess import (CONF_TH, NMS_IOU, TOP_K, decode_boxes, fuse_detections, masks_to_frames, nms_batched, orient_batch, pack_masks,
                           proto_projector_logits, vote_masks)
 
@@ -60,7 +60,7 @@ class ValidationStep:
                  top_k: int = TOP_K, map_max_detections: int = 100, dist_sync: bool = True, process_group=None,
                  instance_masks: bool = False, mask_crop: bool = True, det_loss: str = "reference", tal=None,
                  instance_mask_weight: float = 0.0, mask_assign: str = "iou", views: Optional[Sequence[int]] = None, wbf_iou: float = 0.55,
-                 fused_masks: Optional[str] = None):
+                 fused_masks: Optional[str] = None, surface=None):
         """`projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1), running_main_v3.py:186); created with torch's default
         init when not given.  The loss hyper-parameters default to the reference's (and TrainStep's); `label_smoothing` is accepted for
         symmetry with TrainStep but the eval-mode loss never smooths (:337).  conf_th / nms_iou / top_k: `:54-56`;
@@ -82,7 +82,12 @@ class ValidationStep:
         the segmentation metrics stay on the identity pass, and `compute()` keeps its keys.  `views=None`: not one launch changes.
         `fused_masks="vote"` (with `views` and `instance_masks`): the instance-mask mAP is fed from the fused list too -- every view's pass
         keeps its mask coefficients and prototypes, and the packed planes are voted over each cluster's members (`vote_masks`, as
-        `detect_fused(masks="vote")`).  `views` with `instance_masks` needs it: there is no other fused mask to score."""
+        `detect_fused(masks="vote")`).  `views` with `instance_masks` needs it: there is no other fused mask to score.
+        `surface` (True, or a dict of `SurfaceDistanceMetrics`' options quantile / tolerance / spacing / percentile_mode / undefined):
+        also the boundary metrics of the semantic mask -- one `SurfaceDistanceMetrics.update` on the projector logits `self.seg` sees;
+        `compute()` gains seg_hd_epoch, seg_hd95_epoch, seg_assd_epoch, seg_nsd_epoch and seg_surface_undefined.  None: not one
+        launch and not one key changes."""
+        self.surface_kw = self._surface_options(surface)
         self.views = None if views is None else tuple(int(v) for v in views)
         self.wbf_iou = float(wbf_iou)
         if fused_masks not in (None, "vote"):
@@ -139,9 +144,23 @@ class ValidationStep:
         self.instance_masks, self.mask_crop = bool(instance_masks), bool(mask_crop)
         self.mask_map50 = DeviceMaskMeanAveragePrecision([0.5], max_dets, **sync) if self.instance_masks else None
         self.mask_map50_95 = DeviceMaskMeanAveragePrecision(None, max_dets, **sync) if self.instance_masks else None
+        self.surface = SurfaceDistanceMetrics(**self.surface_kw, **sync) if self.surface_kw is not None else None
+
+    @staticmethod
+    def _surface_options(surface):
+        """`surface=` of the constructor -> None (off) or the keyword arguments of `SurfaceDistanceMetrics`."""
+        if surface is None or surface is False:
+            return None
+        if surface is True:
+            return {}
+        allowed = ("quantile", "tolerance", "spacing", "percentile_mode", "undefined")
+        if not isinstance(surface, dict) or set(surface) - set(allowed):
+            raise ValueError(f"surface: None, True or a dict with keys among {allowed}, not {surface!r}")
+        SurfaceDistanceMetrics(**surface)          # its own checks of the values; needs no device
+        return dict(surface)
 
     def reset(self):
-        for m in (self.losses, self.seg, self.img, self.det_cm, self.map50, self.map50_95, self.mask_map50, self.mask_map50_95):
+        for m in (self.losses, self.seg, self.img, self.det_cm, self.map50, self.map50_95, self.mask_map50, self.mask_map50_95, self.surface):
             if m is not None:
                 m.reset()
 
@@ -184,7 +203,10 @@ class ValidationStep:
                                       iou_match_thresh=self.loss_kw["iou_match_thresh"], weight=self.mask_w, mc_layout="bnA", assigned=assigned)
             losses = (losses[0] + self.mask_w * mask[0],) + tuple(losses[1:]) + (mask[0], mask[1])
         self.losses.update(losses, B)
-        self.seg.update(proto_projector_logits(protos, pj.weight, pj.bias, self.S), masks_gt)
+        seg_logits = proto_projector_logits(protos, pj.weight, pj.bias, self.S)
+        self.seg.update(seg_logits, masks_gt)
+        if self.surface is not None:
+            self.surface.update(seg_logits, masks_gt)
         self.img.update(logits, cls_gt)
         self.det_cm.update(det, det_gt)
         d = decode_boxes(det, self.S, reg_max=self.reg_max, want_scores=False)
@@ -267,4 +289,9 @@ class ValidationStep:
             for prefix, m in (("val_epoch/mask_map_iou50_95", self.mask_map50_95), ("val_epoch/mask_map_iou50", self.mask_map50)):
                 for k, v in m.compute().items():
                     out[f"{prefix}_{k}"] = v
+        if self.surface is not None:
+            sd = self.surface.compute()
+            for k in ("hd", "hd95", "assd", "nsd"):
+                out[f"val_epoch/seg_{k}_epoch"] = sd[k]
+            out["val_epoch/seg_surface_undefined"] = sd["n_undefined"]
         return out
