@@ -420,7 +420,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvP& p, f32x4 (&acc)[FC][F
       case MTBT_ACT_DGELU_POLY: if (TRAIN) { MTBT_FAST(MTBT_ACT_DGELU_POLY, 2); return; } break;
       default: break;
     }
-  } else if (TRAIN && fast) {   // second output = the pre-activation (training forward of fc1)
+  } else if (TRAIN && fast && !(p.cs_part && srow >= 0)) {   // second output = the pre-activation (training forward of fc1)
+    // (y2 WITH column sums: the general body below -- these MODE 1 bodies have no SUMS form and left the partial rows unwritten)
     switch (p.act) {
       case MTBT_ACT_NONE: MTBT_FAST(MTBT_ACT_NONE, 1); return;
       case MTBT_ACT_GELU: MTBT_FAST(MTBT_ACT_GELU, 1); return;

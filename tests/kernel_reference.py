@@ -11,7 +11,13 @@ Bounds are per element and built from stated terms, never from one "relative to 
   * fp32 accumulation: ACC * sum |x * w| (ACC = 2^-22: the order 2^-23 of an fp32 sum, with a factor 2 for the products of the fp32 mode);
   * fp32 epilogue arithmetic (affine, residual add): 2^-23 of the magnitude of its operands;
   * the activation's fp32 evaluation with the hardware exp2 / rcp (common.h act_apply): 2^-20 (1 + |v|);
-  * a fixed term only where an approximation is documented: the polynomial GELU (ACT_GELU_POLY, common.h gelu_poly) has |err| <= 2.3e-4.
+  * a fixed term only where an approximation is documented: the polynomial GELU (ACT_GELU_POLY, common.h gelu_poly) has |err| <= 2.3e-4,
+    the Abramowitz-Stegun erf of ACT_DGELU (common.h fast_erf) has |err| <= 1.5e-7;
+  * the polynomial GELU derivative (ACT_DGELU_POLY, common.h gelu_poly_grad): 2^-23 of the absolute terms of its Horner chain
+    (gelu_poly_grad_condition), which cancel to a small result near |z| = 4.
+
+The training face of the conv kernels (second output y2, the derivative epilogues MTBT_ACT_D*, a residual that IS the output) has its own
+references (preact_ref, deriv_ref, act_grad64) and its own table, TRAIN_VARIANTS; tests/test_gpu_conv_train_epilogue.py runs it.
 """
 import math
 from dataclasses import dataclass, field
@@ -22,7 +28,9 @@ import torch.nn.functional as F
 
 # activation codes of include/mtbt_hip.h (MTBT_ACT_*)
 ACT_NONE, ACT_SILU, ACT_ELU, ACT_GELU, ACT_GELU_POLY = 0, 1, 2, 3, 4
+ACT_DSILU, ACT_DELU, ACT_DGELU, ACT_DGELU_POLY = 5, 6, 7, 8       # y = affine * act'(res): the backward epilogues
 GELU_POLY_ERR = 2.3e-4
+ERF_AS_ERR = 1.5e-7              # common.h fast_erf: Abramowitz-Stegun 7.1.26
 ACC = 2.0 ** -22
 EPI = 2.0 ** -23
 ACT_EVAL = 2.0 ** -20
@@ -47,10 +55,14 @@ def output_rounding(ref: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
     return a * 2.0 ** -24
 
 
+# the fp32 coefficients of P in common.h gelu_poly, highest power of s = xc^2 first
+GELU_POLY_C = [float(torch.tensor(v, dtype=torch.float32)) for v in
+               (2.1609857e-08, -1.5335673e-06, 4.6542096e-05, -7.9887325e-04, 8.6900834e-03, -6.4366050e-02, 3.9770728e-01)]
+
+
 def gelu_poly64(x: torch.Tensor) -> torch.Tensor:
     """common.h gelu_poly in fp64, from the same fp32 coefficients: x * (1/2 + xc P(xc^2)), xc = clamp(x, -4, 4)."""
-    c = [float(torch.tensor(v, dtype=torch.float32)) for v in
-         (2.1609857e-08, -1.5335673e-06, 4.6542096e-05, -7.9887325e-04, 8.6900834e-03, -6.4366050e-02, 3.9770728e-01)]
+    c = GELU_POLY_C
     xc = x.clamp(-4.0, 4.0)
     s = xc * xc
     p = torch.full_like(s, c[0])
@@ -93,6 +105,82 @@ def affine_act_ref(acc: torch.Tensor, mag: torch.Tensor, scale, shift, act: int,
         y = y + res
         bnd = bnd + EPI * res.abs()
     return y, bnd + output_rounding(y, out_dtype)
+
+
+def act_grad64(z: torch.Tensor, act: int) -> torch.Tensor:
+    """act'(z) in fp64 (common.h act_grad; the D* codes and their forward codes mean the same derivative).  SiLU', ELU' and the erf GELU'
+    in closed form.  ACT_DGELU_POLY: the derivative of gelu_poly64 by autograd on the fp64 forward polynomial (the kernel's gelu_poly_grad
+    claims to be the exact derivative of what the forward computed, clamp region included), so no derivative coefficient is typed here.
+    At |z| == 4 exactly the forward has a kink (autograd takes the inner side, the kernel the outer): the reference refuses such a z."""
+    if act in (ACT_SILU, ACT_DSILU):
+        s = torch.sigmoid(z)
+        return s * (1.0 + z * (1.0 - s))
+    if act in (ACT_ELU, ACT_DELU):
+        return torch.where(z > 0, torch.ones_like(z), torch.exp(z))
+    if act in (ACT_GELU, ACT_DGELU):
+        return 0.5 * (1.0 + torch.erf(z / math.sqrt(2.0))) + z * torch.exp(-0.5 * z * z) / math.sqrt(2.0 * math.pi)
+    if act in (ACT_GELU_POLY, ACT_DGELU_POLY):
+        assert not (z.abs() == 4.0).any(), "gelu_poly is not differentiable at |z| == 4"
+        with torch.enable_grad():
+            zz = z.detach().clone().requires_grad_()
+            (g,) = torch.autograd.grad(gelu_poly64(zz).sum(), zz)
+        return g.detach()
+    raise ValueError(act)
+
+
+def act_grad_error(z: torch.Tensor, act: int) -> torch.Tensor:
+    """fp32 evaluation error of act'(z) with the hardware exp2 / rcp, like act_error; ACT_DGELU adds the one fixed term: its Phi(z) =
+    (1 + erf) / 2 uses the Abramowitz-Stegun erf (common.h fast_erf, |error| <= 1.5e-7).  ACT_DGELU_POLY adds the conditioning of its
+    Horner chain (gelu_poly_grad_condition): without it a faithful fp32 evaluation of the kernel's own formula misses the bound near
+    |z| = 4 (tests/test_cpu_kernel_reference.py shows both)."""
+    e = ACT_EVAL * (1.0 + z.abs())
+    if act == ACT_DGELU_POLY:
+        e = e + 2.0 ** -23 * gelu_poly_grad_condition(z)
+    return e + 0.5 * ERF_AS_ERR if act == ACT_DGELU else e
+
+
+def gelu_poly_grad_condition(z: torch.Tensor) -> torch.Tensor:
+    """The magnitude the fp32 roundings of common.h gelu_poly_grad act on.  Inside |z| < 4 it returns fmaf(2 xc, Q(s), 1/2) with Q(s) =
+    sum_j (j + 1) c_j s^j evaluated by Horner in fp32: the coefficient products (j + 1) c_j, s = xc * xc and each of the six FMAs round
+    once, each on the scale of the ABSOLUTE terms sum_j (j + 1) |c_j| s^j -- which alternate in sign and reach 15 at s = 16, where Q itself
+    is 0.08.  So the error is of the order 2^-24 |2 xc| sum_j (j + 1) |c_j| s^j (taken as 2^-23, like ACC), not of the order of the result:
+    near |z| = 4 that is 4e-5, ten times ACT_EVAL (1 + |z|).  Outside, fmaf(xc, P16, 1/2) with the constant P16 = P(16) folded in fp32:
+    |xc| sum_j |c_j| 16^j.  The weights (j + 1) come from differentiating the forward polynomial, its coefficients from GELU_POLY_C."""
+    xc = z.clamp(-4.0, 4.0)
+    s = xc * xc
+    n = len(GELU_POLY_C)
+    inside = sum((n - i) * abs(c) * s ** (n - 1 - i) for i, c in enumerate(GELU_POLY_C)) * (2.0 * xc).abs()
+    outside = sum(abs(c) * 16.0 ** (n - 1 - i) for i, c in enumerate(GELU_POLY_C)) * xc.abs()
+    return torch.where(z.abs() < 4.0, inside, outside)
+
+
+def _affine(acc, scale, shift):
+    shp = (1, -1) + (1,) * (acc.dim() - 2)
+    sc = scale.double().view(shp) if scale is not None else torch.ones(1, dtype=torch.float64)
+    sh = shift.double().view(shp) if shift is not None else torch.zeros(1, dtype=torch.float64)
+    return sc, sh, acc * sc + sh
+
+
+def deriv_ref(acc: torch.Tensor, mag: torch.Tensor, scale, shift, act: int, z: torch.Tensor, out_dtype):
+    """The backward epilogues MTBT_ACT_D* (conv_epilogue.h MODE 2): y = (acc * scale + shift) * act'(z), rounded once; z is the residual
+    operand in storage precision, so it is exact.  Bound: the affine's error through |act'(z)|, the derivative's fp32 evaluation error
+    times |pre|, the product's rounding and the output rounding.  Returns (ref, bound)."""
+    sc, sh, pre = _affine(acc, scale, shift)
+    d = act_grad64(z, act)
+    ref = pre * d
+    bnd = d.abs() * (ACC * sc.abs() * mag + EPI * (pre.abs() + sh.abs())) + pre.abs() * act_grad_error(z, act) + EPI * ref.abs()
+    return ref, bnd + output_rounding(ref, out_dtype)
+
+
+def preact_ref(acc: torch.Tensor, mag: torch.Tensor, scale, shift, out_dtype):
+    """The second output y2 of the training forward (conv_epilogue.h MODE 1): the pre-activation acc * scale + shift rounded once."""
+    sc, sh, pre = _affine(acc, scale, shift)
+    return pre, ACC * sc.abs() * mag + EPI * (pre.abs() + sh.abs()) + output_rounding(pre, out_dtype)
+
+
+def conv_sums(x, w, stride, pad):
+    """(sum x*w, sum |x*w|) of an NCHW fp64 conv: what the epilogue references start from."""
+    return F.conv2d(x, w, None, stride, pad), F.conv2d(x.abs(), w.abs(), None, stride, pad)
 
 
 def conv_ref(x, w, stride, pad, scale, shift, act, res, out_dtype, groups=1):
@@ -258,3 +346,184 @@ def kernel_choice(L, lib, a) -> Tuple[int, int, int, int]:
     rc = lib.mtbt_conv_kernel_choice(C.byref(a), out)
     assert rc == 0, rc
     return tuple(out)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Exact operands: small integers, a power-of-two scale and a dyadic shift make every product and partial sum exact in fp32, so a
+# kernel's result does not depend on its accumulation order and must equal the exact result rounded ONCE.
+# ------------------------------------------------------------------------------------------------------------------------------------
+def exact_operands(row, dtype, g, target=4000.0, scale_pow=None, shift_step=0.25):
+    """Integer x in [-8, 8] ([-64, 64] for rows without a scale vector), w in [-8, 8] (exact in every storage type), a per-channel
+    power-of-two scale putting the outputs near `target`, a shift in quarter steps and an integer residual rounded to the storage type.
+    Returns the operands and the exact fp64 result."""
+    xr = 8 if row.scale else 64
+    x = torch.randint(-xr, xr + 1, (row.N, row.C, row.H, row.W), generator=g).double()
+    w = torch.randint(-8, 9, (row.K, row.C, row.k, row.k), generator=g).double()
+    if scale_pow is None:
+        scale_pow = round(math.log2(target / (24.0 * math.sqrt(row.C * row.k * row.k))))
+    scale = (2.0 ** (scale_pow + torch.randint(0, 2, (row.K,), generator=g))).float() if row.scale else None
+    shift = torch.randint(-64, 65, (row.K,), generator=g).float() * shift_step
+    res = storage(torch.randint(-1000, 1001, (row.N, row.K, row.Ho, row.Wo), generator=g).double(), dtype) if row.res else None
+    acc = F.conv2d(x, w, None, row.stride, row.pad)
+    exact = acc * (scale.double().view(1, -1, 1, 1) if scale is not None else 1.0) + shift.double().view(1, -1, 1, 1)
+    if res is not None:
+        exact = exact + res
+    assert torch.equal(exact.float().double(), exact), "the exact result must be an fp32 value"
+    return x, w, scale, shift, res, exact
+
+
+def rounded_once(exact, out_dt):
+    """The exact fp32 result rounded once into the output type (from fp32, as the kernel does); fp16 saturates at +-65504 (common.h)."""
+    e = exact.float()
+    if out_dt == torch.float16:
+        e = e.clamp(-65504.0, 65504.0)
+    return e.to(out_dt).double()
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Training variant table: the same kernels with the training epilogue bodies of conv_epilogue.h.
+#   mode "y2":    the pre-activation as a second output next to y = act(.) (+ res)              (MODE 1 of the fast body)
+#   mode "deriv": y = affine * act'(res), act one of the D* codes; the residual is the pre-activation z  (MODE 2)
+#   mode "accum": the residual IS the output buffer (a gradient accumulating in place)           (MODE 0 with res == y)
+# colsum: per-channel sums of the stored output from the same launch (the SUMS bodies: ACT_NONE and ACT_DGELU_POLY; everything else the
+# general body; not on the 96-channel tiles).
+# Layouts: where y / y2 / res live, as (extra channels of the buffer, first channel of the view, extra pixel rows per image).  y2 has no
+# strides of its own in mtbt_conv_args: it shares y's pitch and batch stride.
+#   dense     plain NHWC tensors;
+#   slice16   16-byte-aligned channel slices of wider buffers, res with ANOTHER pitch than y: still the fast bodies;
+#   batchgap  a gap after every image (y_batch_stride > Ho * Wo * pitch; res with another gap): y_linear is false, the general body;
+#   slice2    y at channel offset 2 of a K + 2 wide buffer (misaligned: the scalar body), y2 aligned in its own buffer of that pitch;
+#   f32       fp32 y and y2 from 16-bit operands (the general body).
+# ------------------------------------------------------------------------------------------------------------------------------------
+LAYOUTS = {
+    "dense": dict(y=(0, 0, 0), y2=(0, 0, 0), res=(0, 0, 0)),
+    "slice16": dict(y=(24, 8, 0), y2=(24, 16, 0), res=(40, 24, 0)),
+    "batchgap": dict(y=(0, 0, 3), y2=(0, 0, 3), res=(0, 0, 5)),
+    "slice2": dict(y=(2, 2, 0), y2=(2, 0, 0), res=(0, 0, 0)),
+    "f32": dict(y=(0, 0, 0), y2=(0, 0, 0), res=(0, 0, 0)),
+}
+
+
+@dataclass(frozen=True)
+class TrainRow(Row):
+    mode: str = "y2"         # "y2" | "deriv" | "accum"
+    colsum: bool = False
+    layout: str = "dense"
+
+    def view(self, which):
+        """(buffer width in channels, first channel, pixel rows per image) of "y" / "y2" / "res"."""
+        wpad, c0, gap = LAYOUTS[self.layout]["y" if which == "res" and self.mode == "accum" else which]
+        return self.K + wpad, c0, self.Ho * self.Wo + gap
+
+
+def _t(name, N, H, W, C, K, k, stride, pad, act, res, hint_, expect, mode, layout="dense", colsum=False, policy=0):
+    return TrainRow(name, N, H, W, C, K, k, stride, pad, act, res, "f32" if layout == "f32" else "same", hint_, policy, expect,
+                    mode=mode, colsum=colsum, layout=layout)
+
+
+DS, DE, DG, DP = ACT_DSILU, ACT_DELU, ACT_DGELU, ACT_DGELU_POLY
+CS_TILES = [(128, 128), (128, 64), (64, 128), (64, 64), (32, 128), (32, 64)]       # the tiles that allow column sums
+TRAIN_VARIANTS = [
+    # ---- y2: every tile; 2 x 9 x 7 = 126 pixels is ragged for both pixel tiles and leaves 14 rows in the last slab; K = TC + 8 a second,
+    # nearly empty channel tile.  NONE / GELU / GELU_POLY: the fast body; SILU / ELU: the general one.
+    _t("y2_128x128w", 2, 9, 7, 64, 128, 1, 1, 0, GP, False, hint(128, 128), (0, 128, 128, 1), "y2"),
+    _t("y2_128x64n", 2, 9, 7, 128, 136, 1, 1, 0, G, True, hint(128, 64, True), (0, 128, 64, 0), "y2"),
+    _t("y2_96x128n", 1, 10, 10, 64, 96, 3, 1, 1, ACT_NONE, True, hint(96, 128, True), (0, 96, 128, 0), "y2"),
+    _t("y2_96x64w", 2, 9, 7, 64, 104, 1, 1, 0, GP, False, hint(96, 64), (0, 96, 64, 1), "y2"),
+    _t("y2_64x128w", 2, 9, 7, 128, 64, 1, 1, 0, S, False, hint(64, 128), (0, 64, 128, 1), "y2"),
+    _t("y2_64x64n_3x3", 1, 16, 16, 64, 64, 3, 1, 1, GP, False, hint(64, 64, True), (0, 64, 64, 0), "y2"),   # 16-aligned map: not direct
+    _t("y2_32x128n", 1, 3, 5, 64, 32, 1, 1, 0, G, False, hint(32, 128, True), (0, 32, 128, 0), "y2"),      # 15 pixels in all
+    _t("y2_32x64w", 2, 9, 7, 64, 40, 1, 1, 0, E, True, hint(32, 64), (0, 32, 64, 1), "y2"),
+    _t("y2_slice16", 2, 9, 7, 64, 128, 1, 1, 0, GP, True, hint(128, 64), (0, 128, 64, 1), "y2", "slice16"),
+    _t("y2_batchgap", 2, 9, 7, 64, 64, 1, 1, 0, G, True, hint(64, 64), (0, 64, 64, 1), "y2", "batchgap"),
+    _t("y2_slice2", 2, 6, 5, 64, 64, 1, 1, 0, GP, True, hint(64, 128), (0, 64, 128, 1), "y2", "slice2"),
+    _t("y2_f32", 2, 9, 7, 64, 96, 1, 1, 0, G, False, hint(96, 64, True), (0, 96, 64, 0), "y2", "f32"),
+    # ---- deriv: every tile; DSILU / DELU / DGELU_POLY: the fast body; DGELU: the general one; each on a PERM tile and on 96x64
+    _t("d_128x128n", 2, 9, 7, 64, 128, 1, 1, 0, DP, True, hint(128, 128, True), (0, 128, 128, 0), "deriv"),
+    _t("d_128x64w", 2, 9, 7, 128, 136, 1, 1, 0, DS, True, hint(128, 64), (0, 128, 64, 1), "deriv"),
+    _t("d_96x128w", 2, 9, 7, 128, 96, 1, 1, 0, DE, True, hint(96, 128), (0, 96, 128, 1), "deriv"),
+    _t("d_96x64n_dp", 2, 9, 7, 64, 96, 1, 1, 0, DP, True, hint(96, 64, True), (0, 96, 64, 0), "deriv"),
+    _t("d_96x64w_ds", 1, 7, 9, 64, 104, 1, 1, 0, DS, True, hint(96, 64), (0, 96, 64, 1), "deriv"),
+    _t("d_96x64w_de", 2, 9, 7, 64, 96, 1, 1, 0, DE, True, hint(96, 64), (0, 96, 64, 1), "deriv"),
+    _t("d_96x64n_dg", 1, 3, 5, 64, 96, 1, 1, 0, DG, True, hint(96, 64, True), (0, 96, 64, 0), "deriv"),     # 15 pixels in all
+    _t("d_64x128n", 2, 9, 7, 128, 72, 1, 1, 0, DG, True, hint(64, 128, True), (0, 64, 128, 0), "deriv"),
+    _t("d_64x64w_3x3", 1, 16, 16, 64, 64, 3, 1, 1, DP, True, hint(64, 64), (0, 64, 64, 1), "deriv"),        # 16-aligned map: not direct
+    _t("d_32x128w", 2, 9, 7, 64, 32, 1, 1, 0, DE, True, hint(32, 128), (0, 32, 128, 1), "deriv"),
+    _t("d_32x64n", 2, 9, 7, 64, 40, 1, 1, 0, DS, True, hint(32, 64, True), (0, 32, 64, 0), "deriv"),
+    _t("d_slice16", 2, 9, 7, 64, 128, 1, 1, 0, DP, True, hint(128, 128), (0, 128, 128, 1), "deriv", "slice16"),
+    _t("d_batchgap", 2, 9, 7, 64, 64, 1, 1, 0, DS, True, hint(64, 64), (0, 64, 64, 1), "deriv", "batchgap"),
+    _t("d_slice2", 2, 6, 5, 64, 64, 1, 1, 0, DE, True, hint(64, 128), (0, 64, 128, 1), "deriv", "slice2"),
+    _t("d_f32", 2, 9, 7, 64, 128, 1, 1, 0, DP, True, hint(128, 64), (0, 128, 64, 1), "deriv", "f32"),
+    # column sums from the DGELU_POLY launch (d fc1.bias): the SUMS body on every tile that allows them; DGELU once (the general body)
+    *[_t(f"d_cs_{tc}x{tp}", 2, 9, 7, 64, tc, 1, 1, 0, DP, True, hint(tc, tp, narrow=(i % 2 == 1)), (0, tc, tp, 1 - i % 2), "deriv",
+         colsum=True) for i, (tc, tp) in enumerate(CS_TILES)],
+    _t("d_cs_dgelu", 2, 9, 7, 64, 128, 1, 1, 0, DG, True, hint(128, 64), (0, 128, 64, 1), "deriv", colsum=True),
+    # ---- accum: res is y.  A wide and a narrow implicit-GEMM tile per TC 128 / 64 / 32, 96x64, the 2x2 / stride-2 dgrad form, both direct
+    # formulations at TC 64 / 128 (4 and 8 slabs per wave).  The smallest shapes that have that: the fp32 rows rest on ACC * mag alone, the order
+    # of a random walk and no worst case -- over the 131072 outputs of a 2 x 32 x 16 map with a 1152-term reduction one output reached 1.03 of its
+    # bound on the direct kernel, and a plain sequential fp32 sum of the same operands 1.02 (forwards) and 1.07 (backwards).
+    _t("a_128x128w", 2, 9, 7, 64, 128, 1, 1, 0, ACT_NONE, True, hint(128, 128), (0, 128, 128, 1), "accum"),
+    _t("a_128x64n", 2, 9, 7, 128, 136, 1, 1, 0, ACT_NONE, True, hint(128, 64, True), (0, 128, 64, 0), "accum"),
+    _t("a_64x128n", 2, 9, 7, 64, 64, 1, 1, 0, ACT_NONE, True, hint(64, 128, True), (0, 64, 128, 0), "accum"),
+    _t("a_64x64w_3x3", 1, 10, 10, 64, 72, 3, 1, 1, ACT_NONE, True, hint(64, 64), (0, 64, 64, 1), "accum"),
+    _t("a_32x128w", 2, 9, 7, 128, 32, 1, 1, 0, ACT_NONE, True, hint(32, 128), (0, 32, 128, 1), "accum"),
+    _t("a_32x64n", 1, 3, 5, 64, 40, 1, 1, 0, ACT_NONE, True, hint(32, 64, True), (0, 32, 64, 0), "accum"),
+    _t("a_96x64w", 2, 9, 7, 64, 96, 1, 1, 0, ACT_NONE, True, hint(96, 64), (0, 96, 64, 1), "accum"),
+    _t("a_down2x2", 2, 10, 6, 64, 128, 2, 2, 0, ACT_NONE, True, hint(128, 64), (0, 128, 64, 1), "accum"),
+    _t("a_direct64", 1, 16, 32, 64, 64, 3, 1, 1, ACT_NONE, True, 0, (1, 64, 256, 1), "accum", policy=DIRECT_FIRST),
+    _t("a_direct128", 2, 16, 16, 64, 128, 3, 1, 1, ACT_NONE, True, 0, (1, 128, 256, 1), "accum", policy=DIRECT_FIRST),
+    _t("a_rowreuse64", 1, 16, 16, 64, 48, 3, 1, 1, ACT_NONE, True, ROW_REUSE, (1, 64, 256, 0), "accum"),
+    _t("a_rowreuse128", 1, 48, 16, 128, 96, 3, 1, 1, ACT_NONE, True, ROW_REUSE, (1, 128, 256, 0), "accum"),
+    # column sums of the raw conv (the ACT_NONE SUMS body), accumulating in place
+    *[_t(f"a_cs_{tc}x{tp}", 2, 9, 7, 64, tc, 1, 1, 0, ACT_NONE, True, hint(tc, tp, narrow=(i % 2 == 0)), (0, tc, tp, i % 2), "accum",
+         colsum=True) for i, (tc, tp) in enumerate(CS_TILES)],
+    # the same on the direct kernels: the only road to the fast slab body there (with column sums; without, MODE 0 stores straight from the
+    # accumulators), whose residual prefetch runs one slab ahead of the aliasing stores
+    _t("a_cs_direct64", 1, 16, 32, 64, 64, 3, 1, 1, ACT_NONE, True, 0, (1, 64, 256, 1), "accum", colsum=True, policy=DIRECT_FIRST),
+    _t("a_cs_direct128", 2, 16, 16, 64, 128, 3, 1, 1, ACT_NONE, True, 0, (1, 128, 256, 1), "accum", colsum=True, policy=DIRECT_FIRST),
+    _t("a_cs_rowreuse64", 1, 16, 16, 64, 48, 3, 1, 1, ACT_NONE, True, ROW_REUSE, (1, 64, 256, 0), "accum", colsum=True),
+    _t("a_cs_rowreuse128", 2, 16, 16, 64, 96, 3, 1, 1, ACT_NONE, True, ROW_REUSE, (1, 128, 256, 0), "accum", colsum=True),
+]
+TRAIN_ROWS = {r.name: r for r in TRAIN_VARIANTS}
+
+
+def train_conv_args(L, row: TrainRow, dtype: torch.dtype):
+    """The mtbt_conv_args of a training row with fake pointers (never dereferenced by mtbt_conv_kernel_choice), offset, pitched and
+    strided like the real views; the GPU tests fill theirs through engine.Plan.conv from the same TrainRow.view."""
+    code = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}[dtype]
+    out_code = L.F32 if row.layout == "f32" else code
+    oes, es = (4 if out_code == L.F32 else 2), (4 if code == L.F32 else 2)
+    a = conv_args(L, row, dtype, ptrs=dict(x=0x100000, w=0x200000, y=0, scale=0x400000 if row.scale else None, shift=0x500000, res=None))
+    yw, yc, yr = row.view("y")
+    a.y, a.y_pixel_stride, a.y_batch_stride = 0x300000 + yc * oes, yw, yr * yw
+    if row.mode == "y2":
+        assert row.view("y2")[0] == yw and row.view("y2")[2] == yr, "y2 shares y's pitch and batch stride"
+        a.y2 = 0x700000 + row.view("y2")[1] * oes
+    if row.res:
+        rw, rc, rr = row.view("res")
+        a.res = a.y if row.mode == "accum" else 0x600000 + rc * es
+        a.res_pixel_stride, a.res_batch_stride = rw, rr * rw
+    if row.colsum:
+        a.colsum, a.colsum_ws, a.colsum_ws_bytes = 0x800000, 0x900000, 1 << 30
+    return a
+
+
+def train_row_reference(row, dtype, seed=0):
+    """A training row as the parity tests build it: storage-precision operands, fp32 scale / shift.  Returns the
+    operands and {"y": (ref, bound), "y2": (ref, bound)} (y2 only in mode "y2").  Mode "accum": res is what y holds before the launch."""
+    g = torch.Generator().manual_seed(seed + sum(map(ord, row.name)))
+    x = storage(torch.randn(row.N, row.C, row.H, row.W, generator=g), dtype)
+    w = storage(torch.randn(row.K, row.C, row.k, row.k, generator=g) / (row.C * row.k * row.k) ** 0.5, dtype)
+    scale = torch.rand(row.K, generator=g) + 0.5
+    shift = torch.randn(row.K, generator=g) * 0.1
+    res = storage(torch.randn(row.N, row.K, row.Ho, row.Wo, generator=g), dtype) if row.res else None
+    out_dt = torch.float32 if row.layout == "f32" else dtype
+    acc, mag = conv_sums(x, w, row.stride, row.pad)
+    refs = {}
+    if row.mode == "deriv":
+        refs["y"] = deriv_ref(acc, mag, scale, shift, row.act, res, out_dt)
+    else:
+        refs["y"] = affine_act_ref(acc, mag, scale, shift, row.act, res, out_dt)
+    if row.mode == "y2":
+        refs["y2"] = preact_ref(acc, mag, scale, shift, out_dt)
+    return (x, w, scale, shift, res), refs

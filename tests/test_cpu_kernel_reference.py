@@ -84,3 +84,152 @@ def test_variant_table_covers_every_variant():
 def test_variant_table_kernel_choice(row, dtype):
     from multitask_bonetumor_yolo_amd import _lib as L
     assert R.kernel_choice(L, L.load(), R.conv_args(L, row, dtype)) == row.expect
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The training face: references, bounds and the training variant table
+# ---------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,which", [("d_128x128n", "y"), ("d_96x64w_ds", "y"), ("y2_128x64n", "y2")])
+def test_train_bound_accepts_one_fp16_rounding_and_rejects_bf16_and_4_ulps(name, which):
+    _, refs = R.train_row_reference(R.TRAIN_ROWS[name], torch.float16)
+    ref, bnd = refs[which]
+    R.check(ref.half(), ref, bnd, "correctly rounded fp16")
+    assert not R.within(ref.bfloat16(), ref, bnd), "bf16 rounding passed the fp16 bound"
+    flat = ref.flatten()
+    order = flat.abs().argsort()
+    for i in (int(order[-1]), int(order[flat.numel() // 2]), int(order[flat.numel() // 4])):
+        bad = ref.half().flatten().clone()
+        ulp = (bad[i].float().abs().to(torch.float16).view(torch.int16) + 1).view(torch.float16).float() - bad[i].float().abs()
+        bad[i] = bad[i].float() + 4 * ulp
+        assert not R.within(bad.view_as(ref), ref, bnd), f"a 4-ulp error at element {i} passed"
+
+
+def test_act_grad64_closed_forms_match_autograd():
+    z = torch.linspace(-9, 9, 20001, dtype=torch.float64)
+    for act, fwd in ((R.ACT_DSILU, torch.nn.functional.silu), (R.ACT_DELU, torch.nn.functional.elu), (R.ACT_DGELU, torch.nn.functional.gelu)):
+        zz = z.clone().requires_grad_()
+        (g,) = torch.autograd.grad(fwd(zz).sum(), zz)
+        assert (R.act_grad64(z, act) - g).abs().max().item() <= 1e-14, act
+    assert torch.equal(R.act_grad64(torch.tensor([3.0, -200.0], dtype=torch.float64), R.ACT_DELU)[:1], torch.ones(1, dtype=torch.float64))
+    assert R.act_grad64(torch.tensor([-200.0], dtype=torch.float64), R.ACT_DELU).item() < 2.0 ** -280
+
+
+def test_act_grad64_gelu_poly_equals_central_difference():
+    """g = gelu_poly64 is a polynomial of degree 14 inside |x| < 4 and linear outside.  Central difference with h = 2^-14: truncation
+    h^2 / 6 max |g'''| <= 6.3e-10 * 8; fp64 rounding of the two forward values, whose Horner terms reach |x xc| * 12 <= 600 at
+    |x| = 12: 2 * 4 * 2^-53 * 600 / (2 h) <= 4.4e-9.  Tolerance 1e-8; points within h of the kinks at |x| = 4 are left out."""
+    h = 2.0 ** -14
+    x = torch.linspace(-12, 12, 48001, dtype=torch.float64) + 1e-3
+    x = x[((x.abs() - 4.0).abs() > 2 * h)]
+    cd = (R.gelu_poly64(x + h) - R.gelu_poly64(x - h)) / (2 * h)
+    assert (R.act_grad64(x, R.ACT_DGELU_POLY) - cd).abs().max().item() <= 1e-8
+
+
+def _gelu_poly_grad_fp32(x):
+    """common.h gelu_poly_grad step by step in fp32 (numpy float32; an FMA = the fp64 product and sum rounded once, exact for fp32 operands
+    up to the double rounding no test below depends on).  Derivative coefficients: (j + 1) c_j rounded to fp32, as the kernel's constants."""
+    import numpy as np
+    f32, f64 = np.float32, np.float64
+    c = [f32(v) for v in R.GELU_POLY_C]
+    n = len(c)
+    fma = lambda a, b, d: (np.asarray(a, f64) * np.asarray(b, f64) + np.asarray(d, f64)).astype(f32)
+    xc = np.clip(x, f32(-4), f32(4))
+    s = (xc * xc).astype(f32)
+    k = [f32(f32(n - i) * c[i]) for i in range(n)]
+    q = fma(k[0], s, k[1])
+    for kk in k[2:]:
+        q = fma(q, s, kk)
+    p16 = c[0]
+    for cc in c[1:]:
+        p16 = f32(f32(p16 * f32(16)) + cc)
+    return np.where(np.abs(x) < 4, fma(f32(2) * xc, q, 0.5), fma(xc, p16, 0.5))
+
+
+def test_gelu_poly_grad_bound_covers_a_faithful_fp32_evaluation_and_needs_its_horner_term():
+    import numpy as np
+    x = np.linspace(-8, 8, 400001).astype(np.float32)
+    x = x[np.abs(x) != 4]
+    z = torch.from_numpy(x.astype(np.float64))
+    err = (torch.from_numpy(_gelu_poly_grad_fp32(x).astype(np.float64)) - R.act_grad64(z, R.ACT_DGELU_POLY)).abs()
+    assert (err <= R.act_grad_error(z, R.ACT_DGELU_POLY)).all()
+    plain = R.ACT_EVAL * (1.0 + z.abs())
+    assert (err > 2 * plain).any() and not (err > plain)[z.abs() < 3].any(), "the Horner term is needed near |z| = 4 only"
+    # the term stays a small part of the derivative's scale away from the clamp: below ACT_EVAL (1 + |z|) for |z| <= 2
+    assert (2.0 ** -23 * R.gelu_poly_grad_condition(z) <= plain)[z.abs() <= 2].all()
+
+
+PERM_TILES = {(128, 128), (128, 64), (96, 128), (64, 128), (64, 64), (32, 128), (32, 64)}      # even fragment count per wave; 96x64: 3
+
+
+def test_train_variant_table_covers_every_training_epilogue():
+    """What TRAIN_VARIANTS has to contain (the issue's list): tiles x modes x K-step widths, activations per body, column sums, pixel and
+    channel tails, layouts, the 3x3 rows the chooser keeps off the direct kernels, and the in-place accumulation on every kernel."""
+    V = R.TRAIN_VARIANTS
+    assert len({r.name for r in V}) == len(V)
+    tiles = [(tc, tp) for tc in (128, 96, 64, 32) for tp in (128, 64)]
+    for dt in (torch.float16, torch.bfloat16):
+        for mode in ("y2", "deriv"):
+            rows = [r for r in V if r.mode == mode and dt in r.dtypes]
+            assert {r.expect[1:3] for r in rows if r.expect[0] == 0} >= set(tiles), (dt, mode)
+            assert {r.expect[3] for r in rows} == {0, 1}
+    assert all(set(r.dtypes) == set(R.DTYPES) for r in V)
+    y2, dv, ac = ([r for r in V if r.mode == m] for m in ("y2", "deriv", "accum"))
+    # y2: the fast body's three activations and the general body's two; a residual next to y2
+    assert {r.act for r in y2} >= {R.ACT_NONE, R.ACT_GELU, R.ACT_GELU_POLY, R.ACT_SILU, R.ACT_ELU}
+    assert any(r.res for r in y2) and all(r.act < R.ACT_DSILU for r in y2)
+    # deriv: each D* code on a PERM tile and on the one non-PERM tile
+    assert all(r.res for r in dv)
+    for act in (R.ACT_DSILU, R.ACT_DELU, R.ACT_DGELU, R.ACT_DGELU_POLY):
+        assert any(r.act == act and r.expect[1:3] in PERM_TILES for r in dv), act
+        assert any(r.act == act and r.expect[1:3] == (96, 64) for r in dv), act
+    # column sums: ACT_NONE and DGELU_POLY on every tile that allows them, DGELU once, never on a 96-channel tile
+    for act in (R.ACT_NONE, R.ACT_DGELU_POLY):
+        assert {r.expect[1:3] for r in V if r.colsum and r.act == act and r.expect[0] == 0} == set(R.CS_TILES), act
+    assert sum(1 for r in V if r.colsum and r.act == R.ACT_DGELU) == 1
+    assert set(R.CS_TILES) == {t for t in tiles if t[0] != 96} and not any(r.colsum and r.expect[1] == 96 for r in V)
+    # pixel tails: 126 pixels (ragged for both pixel tiles, 14 rows in the last slab), fewer than 16 pixels in all
+    for mode_rows in (y2, dv, ac):
+        assert any(r.N * r.Ho * r.Wo == 126 and r.expect[2] == 128 for r in mode_rows) and any(r.N * r.Ho * r.Wo == 126 and r.expect[2] == 64 for r in mode_rows)
+        assert any(r.N * r.Ho * r.Wo < 16 for r in mode_rows)
+    assert 126 % 16 == 14
+    # channel tails: K = TC + 8
+    for mode_rows in (y2, dv, ac):
+        assert any(r.K == r.expect[1] + 8 and r.expect[0] == 0 and r.layout == "dense" for r in mode_rows)
+    # layouts, for both training outputs; the layouts are what they say
+    for mode_rows in (y2, dv):
+        assert {r.layout for r in mode_rows} == set(R.LAYOUTS)
+    for r in V:
+        (yw, yc, yr), (rw, rc, rr) = r.view("y"), r.view("res")
+        assert r.view("y2")[0] == yw and r.view("y2")[2] == yr
+        if r.layout == "slice16":
+            assert yc % 8 == 0 and yw % 8 == 0 and r.view("y2")[1] % 8 == 0 and rc % 8 == 0 and rw % 8 == 0 and rw != yw and yw > r.K
+        if r.layout == "batchgap":
+            assert yr > r.Ho * r.Wo and r.N > 1
+        if r.layout == "slice2":
+            assert yc == 2 and yw == r.K + 2 and r.view("y2")[1] == 0
+        if r.mode == "accum":
+            assert r.res and r.view("res") == r.view("y")
+    # 3x3 / stride 1 / pad 1 on a 16-aligned map stays on the implicit GEMM with y2 and with a D* act
+    for mode_rows in (y2, dv):
+        assert any(r.k == 3 and r.stride == 1 and r.pad == 1 and r.H % 16 == 0 and r.W % 16 == 0 and (r.hint >> 26) & 1 == 0 and r.expect[0] == 0
+                   for r in mode_rows)
+    # accum: a wide and a narrow tile per TC 128 / 64 / 32, 96x64, the 2x2 / stride-2 form, both direct formulations at both TC
+    plain = [r for r in ac if not r.colsum]
+    for tc in (128, 64, 32):
+        assert {r.expect[3] for r in plain if r.expect[0] == 0 and r.expect[1] == tc} == {0, 1}, tc
+        assert {r.expect[2] for r in plain if r.expect[0] == 0 and r.expect[1] == tc} == {128, 64}, tc
+    assert any(r.expect[:3] == (0, 96, 64) for r in plain)
+    assert any(r.k == 2 and r.stride == 2 for r in plain)
+    assert {r.expect for r in ac if r.colsum and r.expect[0] == 1} == {(1, tc, 256, f) for tc in (64, 128) for f in (0, 1)}
+    for tc in (64, 128):
+        for first in (0, 1):
+            assert any(r.expect == (1, tc, 256, first) and r.H * r.W // 256 * (4 if first else 8) > 1 for r in plain), (tc, first)
+
+
+TRAIN_PARAMS = [(r, d) for r in R.TRAIN_VARIANTS for d in r.dtypes]
+
+
+@pytest.mark.parametrize("row,dtype", TRAIN_PARAMS, ids=[f"{r.name}-{R.DNAME[d]}" for r, d in TRAIN_PARAMS])
+def test_train_variant_table_kernel_choice(row, dtype):
+    from multitask_bonetumor_yolo_amd import _lib as L
+    assert R.kernel_choice(L, L.load(), R.train_conv_args(L, row, dtype)) == row.expect

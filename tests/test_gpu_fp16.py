@@ -8,7 +8,6 @@ Exact-rounding tests use small-integer operands, a power-of-two scale and a dyad
 the result does not depend on accumulation order and the kernel output must equal, bit for bit, the exact fp32 result rounded ONCE."""
 import ctypes as C
 import dataclasses
-import math
 
 import pytest
 import torch
@@ -89,32 +88,7 @@ EXACT_ROWS = ["g128x128w", "g128x128n", "g96x128w", "g32x64n", "g64x64w_slice", 
 EXACT_PARAMS = [(n, d) for n in EXACT_ROWS for d in R.ROWS[n].dtypes]
 
 
-def exact_operands(row, dtype, g, target=4000.0, scale_pow=None, shift_step=0.25):
-    """Integer x in [-8, 8] ([-64, 64] for rows without a scale vector), w in [-8, 8] (exact in every storage type), a per-channel
-    power-of-two scale putting the outputs near `target`, a shift in quarter steps and an integer residual rounded to the storage type.
-    Returns the operands and the exact fp64 result."""
-    xr = 8 if row.scale else 64
-    x = torch.randint(-xr, xr + 1, (row.N, row.C, row.H, row.W), generator=g).double()
-    w = torch.randint(-8, 9, (row.K, row.C, row.k, row.k), generator=g).double()
-    if scale_pow is None:
-        scale_pow = round(math.log2(target / (24.0 * math.sqrt(row.C * row.k * row.k))))
-    scale = (2.0 ** (scale_pow + torch.randint(0, 2, (row.K,), generator=g))).float() if row.scale else None
-    shift = torch.randint(-64, 65, (row.K,), generator=g).float() * shift_step
-    res = R.storage(torch.randint(-1000, 1001, (row.N, row.K, row.Ho, row.Wo), generator=g).double(), dtype) if row.res else None
-    acc = F.conv2d(x, w, None, row.stride, row.pad)
-    exact = acc * (scale.double().view(1, -1, 1, 1) if scale is not None else 1.0) + shift.double().view(1, -1, 1, 1)
-    if res is not None:
-        exact = exact + res
-    assert torch.equal(exact.float().double(), exact), "the exact result must be an fp32 value"
-    return x, w, scale, shift, res, exact
-
-
-def rounded_once(exact, out_dt):
-    """The exact fp32 result rounded once into the output type (from fp32, as the kernel does); fp16 saturates at +-65504 (common.h)."""
-    e = exact.float()
-    if out_dt == F16:
-        e = e.clamp(-65504.0, 65504.0)
-    return e.to(out_dt).double()
+exact_operands, rounded_once = R.exact_operands, R.rounded_once     # shared with tests/test_gpu_conv_train_epilogue.py
 
 
 @pytest.mark.parametrize("name,dtype", EXACT_PARAMS, ids=[f"{n}-{R.DNAME[d]}" for n, d in EXACT_PARAMS])

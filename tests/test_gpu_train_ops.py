@@ -598,7 +598,8 @@ def test_conv_column_sums(dtype, cfg):
     xa = Act.of(nhwc(x, dtype))
     y = Act.of(torch.empty(N, H, W, K, dtype=dtype, device=DEV))
     wp = w.permute(0, 2, 3, 1).reshape(K, -1).contiguous().to(DEV, dtype)
-    res = Act.of(nhwc(torch.randn(N, K, H, W), dtype)) if deriv else None
+    z = torch.randn(N, K, H, W).to(dtype).float() if deriv else None
+    res = Act.of(nhwc(z, dtype)) if deriv else None
     a = p.conv(xa, wp, y, R=k, S=k, pad=k // 2, shift=b.to(DEV), act=act, res=res)
     sums = torch.full((2 * K,), 7.0, device=DEV)
     sh = shift.to(DEV)
@@ -612,6 +613,10 @@ def test_conv_column_sums(dtype, cfg):
     want1 = (stored - shift.double()).sum(0)
     want2 = ((stored - shift.double()) ** 2).sum(0)
     got = sums.cpu().double()
+    if deriv:     # the stored output itself: (conv + b) * GELU'(z), at the tolerance of test_conv_epilogue_second_output_and_derivative_mode
+        zz = z.clone().requires_grad_()
+        (gelu_grad,) = torch.autograd.grad(F.gelu(zz), zz, torch.ones_like(zz))
+        close(back(y.buf), F.conv2d(x, w, b, padding=k // 2) * gelu_grad, 2e-5 if dtype == torch.float32 else 2e-2, "stored derivative epilogue")
     tol = 2e-5 if dtype == torch.float32 else 2e-4        # (fp32 accumulation order only: the summed values are the stored ones)
     assert (got[:K] - want1).abs().max() <= tol * (stored - shift.double()).abs().sum(0).max() + 1e-6
     assert (got[K:] - want2).abs().max() <= tol * want2.max() + 1e-6
