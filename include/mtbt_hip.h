@@ -167,6 +167,15 @@ int mtbt_dwconv_nhwc(const void* x, const void* w, const float* bias, const floa
  * w / scale / shift: two depthwise branches off one tensor as one launch.  C % 128 == 0, M * C <= 768. */
 int mtbt_dwconv3x3_mult_nhwc(const void* x, const void* w, const float* scale, const float* shift, int act, void* y,
                              int N, int H, int W, int C, int M, int dtype, void* stream);
+/* Which kernel, tile and grid mtbt_dwconv_nhwc (and mtbt_dwconv_nhwc_train: its extra outputs do not take part) would launch for this
+ * shape; ln != 0 = the LayerNorm form.  Nothing is launched and there is no pointer to dereference: the launch code itself runs and
+ * reports in place of the launch.  choice[0] tile height; [1] tile width; [2] outputs per lane row (8, or 4 on the half-width tile);
+ * [3] chunks of 128 channels the kernel holds in registers (1, 2, 3, 6; 1 with C > 128 = the chunks as grid rows); [4] 1 = the full-tile
+ * instantiation without bounds checks around the stores; [5] the activation compiled in (MTBT_ACT_*; -1 = the runtime argument);
+ * [6] tiles; [7] gridDim.x = persistent workgroups per grid row; [8] gridDim.y.  The shape errors of mtbt_dwconv_nhwc.  For tests. */
+int mtbt_dwconv_kernel_choice(int N, int H, int W, int C, int ksize, int ln, int act, int dtype, int32_t* choice);
+/* The same for mtbt_dwconv3x3_mult_nhwc. */
+int mtbt_dwconv3x3_mult_kernel_choice(int N, int H, int W, int C, int M, int act, int dtype, int32_t* choice);
 
 /* LayerNorm over C of an NHWC dense tensor (timm LayerNorm2d in `stages_i.downsample.0`). */
 int mtbt_layernorm_nhwc(const void* x, const float* w, const float* b, float eps, void* y,

@@ -297,6 +297,8 @@ SYMBOLS = {
     "mtbt_conv2d_nhwc_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mtbt_conv_batch_kernel_choice": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "mtbt_dwconv3x3_mult_nhwc": (C.c_int, [C.c_void_p] * 4 + [C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "mtbt_dwconv_kernel_choice": (C.c_int, [C.c_int] * 8 + [C.c_void_p]),
+    "mtbt_dwconv3x3_mult_kernel_choice": (C.c_int, [C.c_int] * 7 + [C.c_void_p]),
     "mtbt_bn_forward_partials_nhwc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4 + [C.c_float, C.c_float, C.c_int, C.c_int64, C.c_int, C.c_int,
                                                 C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtbt_bn_backward_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int]),

@@ -87,6 +87,13 @@ template <> struct Pair<f16_t> {
 
 constexpr int CC = 128;  // channels per chunk = 64 lanes x 2
 
+// mtbt_dwconv_kernel_choice: what the launch functions below are about to launch, written where they would launch it (DwArgs::choice)
+inline int dw_report(int32_t* choice, int th, int tw, int xb, int maxch, bool full, int act, long tiles, long blocks, int ygrid) {
+  const int32_t v[9] = {th, tw, xb, maxch, full ? 1 : 0, act, (int32_t)tiles, (int32_t)blocks, ygrid};
+  for (int i = 0; i < 9; ++i) choice[i] = v[i];
+  return MTBT_OK;
+}
+
 
 // MAXCH = ceil(C / 128) chunks held in registers.  Workgroups are PERSISTENT: each walks a strided list of tiles
 // (XCD-contiguous ranges, so neighbouring tiles' halos meet in one L2); with a single chunk (C <= 128) the taps stay
@@ -128,7 +135,8 @@ __global__ __launch_bounds__((TH / 2) * (TW / 8) * 64, 2) void dwconv_mult_kerne
 }
 
 template <typename T, int TH, int TW, int ACT, bool FULL>
-int launch_dw_mult(const void* x, const void* w, const float* scale, const float* shift, int act, void* y, int N, int H, int W, int C, int Cx, hipStream_t s) {
+int launch_dw_mult(const void* x, const void* w, const float* scale, const float* shift, int act, void* y, int N, int H, int W, int C, int Cx, int32_t* choice,
+                   hipStream_t s) {
   constexpr int NT = (TH / 2) * (TW / 8) * 64;
   constexpr int PARTS = CC * (int)sizeof(T) / 16, PXI = 64 / PARTS, IWP = ((TW + 2 + PXI - 1) / PXI) * PXI;
   constexpr int lds = (TH + 2) * IWP * CC * (int)sizeof(T);
@@ -142,6 +150,7 @@ int launch_dw_mult(const void* x, const void* w, const float* scale, const float
   blocks = (blocks + 7) / 8 * 8;
   const int ygrid = C / CC;
   if (ygrid > 1) { blocks = (blocks / ygrid + 7) / 8 * 8; if (blocks < 8) blocks = 8; }
+  if (choice) return dw_report(choice, TH, TW, 8, 1, FULL, ACT, tiles, blocks, ygrid);
   auto kern = dwconv_mult_kernel<T, TH, TW, ACT, FULL>;
   if (int rc = mtbt_allow_lds(kern, lds)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)ygrid), dim3(NT), lds, s, (const T*)x, (const T*)w, scale, shift, act, (T*)y, N, H, W, C, Cx);
@@ -153,7 +162,7 @@ int launch_dw_mult(const void* x, const void* w, const float* scale, const float
 // form runs the code a plain call on that block runs
 template <typename T, int TW, bool VARIANTS>
 int dw_run_mult(const DwArgs& a, int Cx, hipStream_t s) {
-#define DW_M(ACTV, FULLV) launch_dw_mult<T, 4, TW, ACTV, FULLV>(a.x, a.w, a.scale, a.shift, a.act, a.y, a.N, a.H, a.W, a.C, Cx, s)
+#define DW_M(ACTV, FULLV) launch_dw_mult<T, 4, TW, ACTV, FULLV>(a.x, a.w, a.scale, a.shift, a.act, a.y, a.N, a.H, a.W, a.C, Cx, a.choice, s)
   if constexpr (VARIANTS) {
     const bool full = a.H % 4 == 0 && a.W % TW == 0;
     if (a.act == MTBT_ACT_NONE) return full ? DW_M(MTBT_ACT_NONE, true) : DW_M(MTBT_ACT_NONE, false);
@@ -167,7 +176,8 @@ int dw_run_mult(const DwArgs& a, int Cx, hipStream_t s) {
 
 template <typename T, int KS, bool LN, int TH, int TW, int MAXCH, int XB = 8, int ACT = -1, bool FULL = false, int OCC = 2, bool REGT = (MAXCH == 1)>
 int launch_dw(const void* x, const void* w, const float* bias, const float* lnw, const float* lnb, float eps,
-              const float* scale, const float* shift, int act, void* y, void* raw, const void* res, int N, int H, int W, int C, hipStream_t s) {
+              const float* scale, const float* shift, int act, void* y, void* raw, const void* res, int N, int H, int W, int C, int32_t* choice,
+              hipStream_t s) {
   constexpr int NT = (TH / 2) * (TW / XB) * 64;
   constexpr int PARTS = CC * (int)sizeof(T) / 16, PXI = 64 / PARTS, IWP = ((TW + KS - 1 + PXI - 1) / PXI) * PXI;
   constexpr int lds_tile = (TH + KS - 1) * IWP * CC * (int)sizeof(T), lds_red = LN ? (NT / 64) * (16 * 64 + 16) * 4 : 0;
@@ -184,10 +194,11 @@ int launch_dw(const void* x, const void* w, const float* bias, const float* lnw,
   const long resident = 256L * (160 * 1024 / lds > cap ? cap : 160 * 1024 / lds);
   long blocks = tiles < resident ? tiles : resident;
   blocks = (blocks + 7) / 8 * 8;
-  auto kern = dwconv_kernel<T, KS, LN, TH, TW, MAXCH, XB, OCC, REGT, ACT, FULL>;
-  if (int rc = mtbt_allow_lds(kern, lds)) return rc;
   const int ygrid = MAXCH == 1 ? (C + CC - 1) / CC : 1;      // one-chunk kernel on a wider tensor: the chunks are grid rows
   if (ygrid > 1) { blocks = (blocks / ygrid + 7) / 8 * 8; if (blocks < 8) blocks = 8; }
+  if (choice) return dw_report(choice, TH, TW, XB, MAXCH, FULL, ACT, tiles, blocks, ygrid);
+  auto kern = dwconv_kernel<T, KS, LN, TH, TW, MAXCH, XB, OCC, REGT, ACT, FULL>;
+  if (int rc = mtbt_allow_lds(kern, lds)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks, (unsigned)ygrid), dim3(NT), lds, s, (const T*)x, (const T*)w, bias, lnw, lnb, eps, scale, shift,
                      act, (T*)y, (T*)raw, (const T*)res, N, H, W, C, 0 /* ablation bits: development builds only */);
   MTBT_LAUNCH_CHECK();
@@ -197,22 +208,22 @@ int launch_dw(const void* x, const void* w, const float* bias, const float* lnw,
 template <typename T, int KS, bool LN, int TH, int TW, int ACT, bool FULL>
 int dispatch_chunks(const void* x, const void* w, const float* bias, const float* lnw, const float* lnb, float eps,
                     const float* scale, const float* shift, int act, void* y, void* raw, const void* res, int N, int H, int W, int C, bool half,
-                    hipStream_t s) {
+                    int32_t* choice, hipStream_t s) {
   // (An earlier separate kernel for two / three chunks -- taps of a chunk in registers, one tile per workgroup -- was
   // 10-25 % faster on those layers but restaged its LDS tile behind a plain __syncthreads(): DESIGN.md 4 has the root cause.)
   // `half` = the TH x TW/2 tile with 4 outputs per lane row (twice the waves per tile, half the accumulators): see dw_run.
   const int nch = (C + CC - 1) / CC;
   if constexpr (!LN) {   // no cross-channel step: the one-chunk kernel, chunks as grid rows
     if constexpr (KS == 7) {
-      if (half) return launch_dw<T, KS, LN, TH, TW / 2, 1, 4, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, s);
+      if (half) return launch_dw<T, KS, LN, TH, TW / 2, 1, 4, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, choice, s);
     }
-    return launch_dw<T, KS, LN, TH, TW, 1, 8, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, s);
+    return launch_dw<T, KS, LN, TH, TW, 1, 8, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, choice, s);
   } else {
-  if (nch <= 1) return launch_dw<T, KS, LN, TH, TW, 1, 8, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, s);
-  if (nch <= 2) return launch_dw<T, KS, LN, TH, TW, 2, 8, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, s);
-  if (nch <= 3) return launch_dw<T, KS, LN, TH, TW / 2, 3, 4, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, s);
+  if (nch <= 1) return launch_dw<T, KS, LN, TH, TW, 1, 8, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, choice, s);
+  if (nch <= 2) return launch_dw<T, KS, LN, TH, TW, 2, 8, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, choice, s);
+  if (nch <= 3) return launch_dw<T, KS, LN, TH, TW / 2, 3, 4, ACT, FULL>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, choice, s);
   // (six chunks: ONE wave per SIMD -- at two the 48 accumulator pairs + taps + LayerNorm vectors spilled 344 bytes per lane; 40 -> 25 us on stage 3)
-  if (nch <= 6) return launch_dw<T, KS, LN, TH, TW / 2, 6, 4, ACT, FULL, 1>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, s);
+  if (nch <= 6) return launch_dw<T, KS, LN, TH, TW / 2, 6, 4, ACT, FULL, 1>(x, w, bias, lnw, lnb, eps, scale, shift, act, y, raw, res, N, H, W, C, choice, s);
   return MTBT_EINVAL;
   }
 }
@@ -221,7 +232,7 @@ int dispatch_chunks(const void* x, const void* w, const float* bias, const float
 // path) builds only the runtime-activation bounds-checked kernels.
 template <typename T, int TW, bool VARIANTS>
 int dw_run(const DwArgs& a, hipStream_t s) {
-#define DW_ARGS a.x, a.w, a.bias, a.ln_w, a.ln_b, a.ln_eps, a.scale, a.shift, a.act, a.y, a.raw, a.res, a.N, a.H, a.W, a.C, half, s
+#define DW_ARGS a.x, a.w, a.bias, a.ln_w, a.ln_b, a.ln_eps, a.scale, a.shift, a.act, a.y, a.raw, a.res, a.N, a.H, a.W, a.C, half, a.choice, s
   const bool ln = a.ln_w != nullptr;
   // the half-width tile (4 x TW/2, 4 outputs per lane row): LayerNorm form from three chunks on (stage 2 of the 640x640 forward, 40x40 maps:
   // 48.5 -> 33 us; twice the waves per tile hide what the 96-register accumulator tile of three chunks could not), scale / shift 7x7 form

@@ -6,6 +6,7 @@ struct DwArgs {
   const void* x; const void* w; const float* bias; const float* ln_w; const float* ln_b; float ln_eps;
   const float* scale; const float* shift; int act; void* y; void* raw; const void* res;
   int N, H, W, C, ksize;
+  int32_t* choice;   // non-null (mtbt_dwconv_kernel_choice): the launch function reports what it would launch, here, and launches nothing
 };
 
 int mtbt_dw_run_bf16(const DwArgs& a, hipStream_t s);

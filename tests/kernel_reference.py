@@ -18,6 +18,11 @@ Bounds are per element and built from stated terms, never from one "relative to 
 
 The training face of the conv kernels (second output y2, the derivative epilogues MTBT_ACT_D*, a residual that IS the output) has its own
 references (preact_ref, deriv_ref, act_grad64) and its own table, TRAIN_VARIANTS; tests/test_gpu_conv_train_epilogue.py runs it.
+
+The depthwise kernels (LayerNorm form, scale / shift form, training outputs, depth multiplier) have the table DW_VARIANTS and the references
+dw_sums / dw_ln_ref / dw_row_reference; tests/test_gpu_dwconv_variants.py runs it.  They add no term to the list above: the scale / shift
+form is affine_act_ref on the depthwise sums, the LayerNorm form ln_bound with an input error of ACC * sum |x * w| + EPI * |bias|, and the
+LayerNorm input kept for training (raw) preact_ref with the bias as the shift: conv + bias rounded once.
 """
 import math
 from dataclasses import dataclass, field
@@ -527,3 +532,268 @@ def train_row_reference(row, dtype, seed=0):
     if row.mode == "y2":
         refs["y2"] = preact_ref(acc, mag, scale, shift, out_dt)
     return (x, w, scale, shift, res), refs
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# Depthwise variant table (csrc/dwconv.inc: mtbt_dwconv_nhwc, mtbt_dwconv_nhwc_train, mtbt_dwconv3x3_mult_nhwc);
+# tests/test_gpu_dwconv_variants.py runs it.  Each row: shape (C = the channels of x), kernel size, form (LayerNorm or scale / shift + act),
+# the training extras (raw = the LayerNorm input as a second output; res = "buf" a residual tensor / "y" the residual IS the output), the
+# depth multiplier M (0 = the plain entry) and, per storage width, the mtbt_dwconv_kernel_choice tuple it must reach:
+#   (tile height, tile width, outputs per lane row, MAXCH, FULL, compiled activation (-1 = runtime), tiles, gridDim.x, gridDim.y).
+# e16 holds for f16 and bf16 (16-wide tiles, activation constants, FULL instantiations), e32 for f32 (8-wide tiles, bounds-checked,
+# runtime activation); None = the row does not run in that width (the walk rows are sized per width).
+# walk: the persistent workgroups take further tiles (one chunk: some workgroup runs a first, a middle and a last tile).
+# No tolerance of its own: the scale / shift form uses affine_act_ref, the LayerNorm form ln_bound with v_err = ACC sum |x w| + EPI |bias|
+# (as test_fp16_dwconv7_layernorm), raw the bound of conv + bias rounded once (preact_ref with the bias as shift).
+# ------------------------------------------------------------------------------------------------------------------------------------
+DW_EPS = 1e-6
+DW_FIELDS = ("th", "tw", "xb", "maxch", "full", "act", "tiles", "gx", "gy")
+
+
+@dataclass(frozen=True)
+class DwRow:
+    name: str
+    N: int
+    C: int
+    H: int
+    W: int
+    k: int
+    ln: bool
+    act: int
+    e16: Optional[Tuple[int, ...]]
+    e32: Optional[Tuple[int, ...]]
+    raw: bool = False
+    res: str = ""            # "" | "buf" | "y"
+    M: int = 0
+    walk: bool = False
+
+    @property
+    def Co(self):
+        return self.C * max(self.M, 1)
+
+    @property
+    def dtypes(self):
+        return tuple(d for d in DTYPES if self.expect(d) is not None)
+
+    def expect(self, dtype):
+        return self.e32 if dtype == torch.float32 else self.e16
+
+    def field(self, dtype, name):
+        return self.expect(dtype)[DW_FIELDS.index(name)]
+
+
+def _ln(name, shape, k, e16, e32, raw=False, walk=False):
+    return DwRow(name, *shape, k, True, ACT_NONE, e16, e32, raw=raw, walk=walk)
+
+
+def _af(name, shape, k, act, e16, e32, res="", walk=False):
+    return DwRow(name, *shape, k, False, act, e16, e32, res=res, walk=walk)
+
+
+def _mu(name, shape, M, act, e16, e32):
+    return DwRow(name, *shape, 3, False, act, e16, e32, M=M)
+
+
+N_, SI = ACT_NONE, ACT_SILU
+DW_VARIANTS = [
+    # ---- LayerNorm form, 7x7: MAXCH 1 / 2 / 3 / 6, each ragged (_r) and in whole tiles (_f: the FULL instantiation of the 16-bit types); a last
+    # chunk of 8 channels at C = 8, 136, 264, 392, 520, 648; the six-chunk kernel with 4 (392), 5 (520) and 6 (648, 768) live chunks
+    _ln("ln7_c96_r", (2, 96, 9, 11), 7, (4, 16, 8, 1, 0, 0, 6, 8, 1), (4, 8, 8, 1, 0, 0, 12, 16, 1), raw=True),
+    _ln("ln7_c8_f", (2, 8, 8, 16), 7, (4, 16, 8, 1, 1, 0, 4, 8, 1), (4, 8, 8, 1, 0, 0, 8, 8, 1)),
+    _ln("ln7_c136_r", (2, 136, 7, 18), 7, (4, 16, 8, 2, 0, 0, 8, 8, 1), (4, 8, 8, 2, 0, 0, 12, 16, 1), raw=True),
+    _ln("ln7_c256_f", (2, 256, 8, 32), 7, (4, 16, 8, 2, 1, 0, 8, 8, 1), (4, 8, 8, 2, 0, 0, 16, 16, 1)),
+    _ln("ln7_c264_r", (2, 264, 5, 9), 7, (4, 8, 4, 3, 0, 0, 8, 8, 1), (4, 4, 4, 3, 0, 0, 12, 16, 1)),
+    _ln("ln7_c384_f", (2, 384, 8, 8), 7, (4, 8, 4, 3, 1, 0, 4, 8, 1), (4, 4, 4, 3, 0, 0, 8, 8, 1), raw=True),
+    _ln("ln7_c392_r", (2, 392, 6, 7), 7, (4, 8, 4, 6, 0, 0, 4, 8, 1), (4, 4, 4, 6, 0, 0, 8, 8, 1), raw=True),
+    _ln("ln7_c520_f", (2, 520, 4, 16), 7, (4, 8, 4, 6, 1, 0, 4, 8, 1), (4, 4, 4, 6, 0, 0, 8, 8, 1)),
+    _ln("ln7_c648_r", (1, 648, 3, 15), 7, (4, 8, 4, 6, 0, 0, 2, 8, 1), (4, 4, 4, 6, 0, 0, 4, 8, 1)),
+    _ln("ln7_c768_f", (2, 768, 4, 8), 7, (4, 8, 4, 6, 1, 0, 2, 8, 1), (4, 4, 4, 6, 0, 0, 4, 8, 1), raw=True),
+    _ln("ln7_c96_1x1", (2, 96, 1, 1), 7, (4, 16, 8, 1, 0, 0, 2, 8, 1), (4, 8, 8, 1, 0, 0, 2, 8, 1), raw=True),
+    # ---- LayerNorm form, 3x3: the same cells; H = W = 2, H = 3 = tile - 1, W = 15 / 7 / 3 = tile - 1 of the 16 / 8 / 4 wide tiles
+    _ln("ln3_c8_r", (2, 8, 5, 17), 3, (4, 16, 8, 1, 0, 0, 8, 8, 1), (4, 8, 8, 1, 0, 0, 12, 16, 1), raw=True),
+    _ln("ln3_c96_f", (2, 96, 4, 32), 3, (4, 16, 8, 1, 1, 0, 4, 8, 1), (4, 8, 8, 1, 0, 0, 8, 8, 1)),
+    _ln("ln3_c136_f", (2, 136, 8, 16), 3, (4, 16, 8, 2, 1, 0, 4, 8, 1), (4, 8, 8, 2, 0, 0, 8, 8, 1)),
+    _ln("ln3_c192_r", (2, 192, 3, 15), 3, (4, 16, 8, 2, 0, 0, 2, 8, 1), (4, 8, 8, 2, 0, 0, 4, 8, 1), raw=True),
+    _ln("ln3_c264_f", (2, 264, 4, 24), 3, (4, 8, 4, 3, 1, 0, 6, 8, 1), (4, 4, 4, 3, 0, 0, 12, 16, 1), raw=True),
+    _ln("ln3_c320_r", (2, 320, 3, 3), 3, (4, 8, 4, 3, 0, 0, 2, 8, 1), (4, 4, 4, 3, 0, 0, 2, 8, 1)),
+    _ln("ln3_c448_f", (2, 448, 8, 8), 3, (4, 8, 4, 6, 1, 0, 4, 8, 1), (4, 4, 4, 6, 0, 0, 8, 8, 1)),
+    _ln("ln3_c640_r", (2, 640, 2, 2), 3, (4, 8, 4, 6, 0, 0, 2, 8, 1), (4, 4, 4, 6, 0, 0, 2, 8, 1), raw=True),
+    _ln("ln3_c648_f", (1, 648, 4, 16), 3, (4, 8, 4, 6, 1, 0, 2, 8, 1), (4, 4, 4, 6, 0, 0, 4, 8, 1), raw=True),
+    _ln("ln3_c768_r", (2, 768, 5, 6), 3, (4, 8, 4, 6, 0, 0, 4, 8, 1), (4, 4, 4, 6, 0, 0, 8, 8, 1)),
+    # ---- LayerNorm form, walk rows of the 16-bit types: 1040 tiles on 512 workgroups (one chunk: first, middle and last tile), 529 on 512
+    # (two, three chunks), 289 on 256 (six-chunk kernel, five live); 3x3 with one chunk (every type) and three
+    _ln("w16_ln7_c96", (1, 96, 103, 635), 7, (4, 16, 8, 1, 0, 0, 1040, 512, 1), None, raw=True, walk=True),
+    _ln("w16_ln7_c192", (1, 192, 92, 361), 7, (4, 16, 8, 2, 0, 0, 529, 512, 1), None, walk=True),
+    _ln("w16_ln7_c384", (1, 384, 90, 181), 7, (4, 8, 4, 3, 0, 0, 529, 512, 1), None, raw=True, walk=True),
+    _ln("w16_ln7_c520", (1, 520, 66, 131), 7, (4, 8, 4, 6, 0, 0, 289, 256, 1), None, walk=True),
+    _ln("w_ln3_c96", (1, 96, 103, 635), 3, (4, 16, 8, 1, 0, 0, 1040, 512, 1), (4, 8, 8, 1, 0, 0, 2080, 1024, 1), walk=True),
+    _ln("w16_ln3_c384", (1, 384, 90, 181), 3, (4, 8, 4, 3, 0, 0, 529, 512, 1), None, raw=True, walk=True),
+    # ---- LayerNorm form, walk rows of fp32 (4 x 8 and 4 x 4 tiles)
+    _ln("w32_ln7_c96", (1, 96, 103, 315), 7, None, (4, 8, 8, 1, 0, 0, 1040, 512, 1), walk=True),
+    _ln("w32_ln7_c192", (1, 192, 66, 131), 7, None, (4, 8, 8, 2, 0, 0, 289, 256, 1), raw=True, walk=True),
+    _ln("w32_ln7_c384", (1, 384, 90, 90), 7, None, (4, 4, 4, 3, 0, 0, 529, 512, 1), walk=True),
+    _ln("w32_ln7_c768", (1, 768, 90, 90), 7, None, (4, 4, 4, 6, 0, 0, 529, 512, 1), raw=True, walk=True),
+    # ---- scale / shift form, 7x7: C <= 128 and the chunks as 2 / 3 grid rows with a ragged last chunk; full-width tiles (W a multiple of the
+    # tile width) and half-width ones; the activation as the NONE / SILU constant and at run time (ELU); no residual, a residual tensor, res is y
+    _af("af7_c96_f", (2, 96, 8, 32), 7, N_, (4, 16, 8, 1, 1, 0, 8, 8, 1), (4, 8, 8, 1, 0, -1, 16, 16, 1)),
+    _af("af7_c128_r", (2, 128, 9, 21), 7, SI, (4, 8, 4, 1, 0, 1, 18, 24, 1), (4, 4, 4, 1, 0, -1, 36, 40, 1), res="buf"),
+    _af("af7_c192_hf", (2, 192, 8, 24), 7, E, (4, 8, 4, 1, 1, -1, 12, 8, 2), (4, 8, 8, 1, 0, -1, 12, 8, 2)),
+    _af("af7_c264_r", (2, 264, 7, 19), 7, N_, (4, 8, 4, 1, 0, 0, 12, 8, 3), (4, 4, 4, 1, 0, -1, 20, 8, 3), res="y"),
+    _af("af7_c328_f", (1, 328, 12, 16), 7, SI, (4, 16, 8, 1, 1, 1, 3, 8, 3), (4, 8, 8, 1, 0, -1, 6, 8, 3)),
+    _af("af7_c8_r", (2, 8, 3, 15), 7, N_, (4, 8, 4, 1, 0, 0, 4, 8, 1), (4, 4, 4, 1, 0, -1, 8, 8, 1), res="buf"),
+    _af("af7_c64_r16", (2, 64, 6, 32), 7, E, (4, 16, 8, 1, 0, -1, 8, 8, 1), (4, 8, 8, 1, 0, -1, 16, 16, 1), res="y"),
+    # ---- scale / shift form, 3x3 (always the full-width tile); a 1 x 2 image
+    _af("af3_c64_r", (2, 64, 3, 7), 3, E, (4, 16, 8, 1, 0, -1, 2, 8, 1), (4, 8, 8, 1, 0, -1, 2, 8, 1)),
+    _af("af3_c128_f", (2, 128, 8, 16), 3, N_, (4, 16, 8, 1, 1, 0, 4, 8, 1), (4, 8, 8, 1, 0, -1, 8, 8, 1), res="y"),
+    _af("af3_c192_r", (2, 192, 6, 17), 3, SI, (4, 16, 8, 1, 0, 1, 8, 8, 2), (4, 8, 8, 1, 0, -1, 12, 8, 2), res="buf"),
+    _af("af3_c264_f", (2, 264, 4, 32), 3, N_, (4, 16, 8, 1, 1, 0, 4, 8, 3), (4, 8, 8, 1, 0, -1, 8, 8, 3), res="buf"),
+    _af("af3_c256_1x2", (3, 256, 1, 2), 3, SI, (4, 16, 8, 1, 0, 1, 3, 8, 2), (4, 8, 8, 1, 0, -1, 3, 8, 2)),
+    _af("af3_c392_f", (1, 392, 8, 16), 3, E, (4, 16, 8, 1, 1, -1, 2, 8, 4), (4, 8, 8, 1, 0, -1, 4, 8, 4), res="y"),
+    # ---- scale / shift form at C <= 128, walk rows: act none, so that the bit-exact check runs the very kernel of the parity check
+    _af("w16_af7_full", (1, 72, 103, 640), 7, N_, (4, 16, 8, 1, 0, 0, 1040, 512, 1), None, walk=True),
+    _af("w16_af7_half", (1, 72, 103, 315), 7, N_, (4, 8, 4, 1, 0, 0, 1040, 512, 1), None, res="y", walk=True),
+    _af("w16_af3", (1, 72, 103, 635), 3, N_, (4, 16, 8, 1, 0, 0, 1040, 512, 1), None, res="buf", walk=True),
+    _af("w32_af7_full", (1, 72, 103, 320), 7, N_, None, (4, 8, 8, 1, 0, -1, 1040, 512, 1), walk=True),
+    _af("w32_af7_half", (1, 72, 103, 237), 7, N_, None, (4, 4, 4, 1, 0, -1, 1560, 768, 1), res="y", walk=True),
+    _af("w32_af3", (1, 72, 103, 635), 3, N_, None, (4, 8, 8, 1, 0, -1, 2080, 1024, 1), res="buf", walk=True),
+    # ---- depth multiplier: M = 1 / 2, C = 128 / 256, ragged and whole tiles, every activation choice
+    _mu("mu1_c128_r", (2, 128, 5, 9), 1, SI, (4, 16, 8, 1, 0, 1, 4, 8, 1), (4, 8, 8, 1, 0, -1, 8, 8, 1)),
+    _mu("mu2_c128_f", (2, 128, 8, 16), 2, N_, (4, 16, 8, 1, 1, 0, 4, 8, 2), (4, 8, 8, 1, 0, -1, 8, 8, 2)),
+    _mu("mu1_c256_f", (1, 256, 4, 32), 1, E, (4, 16, 8, 1, 1, -1, 2, 8, 2), (4, 8, 8, 1, 0, -1, 4, 8, 2)),
+    _mu("mu2_c256_r", (2, 256, 7, 10), 2, SI, (4, 16, 8, 1, 0, 1, 4, 8, 4), (4, 8, 8, 1, 0, -1, 8, 8, 4)),
+    _mu("mu2_c128_n", (2, 128, 6, 11), 2, N_, (4, 16, 8, 1, 0, 0, 4, 8, 2), (4, 8, 8, 1, 0, -1, 8, 8, 2)),
+]
+DW_ROWS = {r.name: r for r in DW_VARIANTS}
+
+
+def dw_choice(L, lib, row: DwRow, dtype) -> Tuple[int, ...]:
+    """What the entry point of this row would launch (host-only query)."""
+    import ctypes as C
+    code = {torch.float32: L.F32, torch.bfloat16: L.BF16, torch.float16: L.F16}[dtype]
+    out = (C.c_int32 * 9)()
+    if row.M:
+        rc = lib.mtbt_dwconv3x3_mult_kernel_choice(row.N, row.H, row.W, row.C, row.M, row.act, code, out)
+    else:
+        rc = lib.mtbt_dwconv_kernel_choice(row.N, row.H, row.W, row.C, row.k, int(row.ln), row.act, code, out)
+    assert rc == 0, rc
+    return tuple(out)
+
+
+def storage16(t: torch.Tensor) -> torch.Tensor:
+    """t rounded so that it is exact in bf16 AND in fp16 (bf16's 8 significant bits; below fp16's normal range the fp16 subnormal grid, which
+    leaves at most 7): the big walk rows share one reference between the two 16-bit types."""
+    s = t.to(torch.bfloat16).to(torch.float16)
+    assert torch.equal(s.double(), s.to(torch.bfloat16).double())
+    return s.double()
+
+
+def dw_sums(x: torch.Tensor, w: torch.Tensor):
+    """(sum x*w, sum |x*w|) of a depthwise k x k conv (stride 1, pad k/2) in fp64, by shift-and-add over the taps.  x [N,C,H,W], w [Co,k,k]
+    with Co = M * C: output channel j reads input channel j mod C (M = 1: the plain depthwise conv)."""
+    (N, C, H, W), k = x.shape, w.shape[-1]
+    if w.shape[0] != C:
+        x = x.repeat(1, w.shape[0] // C, 1, 1)
+    xp = F.pad(x, (k // 2,) * 4)
+    xa, wa = xp.abs(), w.abs()
+    acc, mag = torch.zeros_like(x), torch.zeros_like(x)
+    for ky in range(k):
+        for kx in range(k):
+            acc.addcmul_(xp[:, :, ky:ky + H, kx:kx + W], w[:, ky, kx].view(1, -1, 1, 1))
+            mag.addcmul_(xa[:, :, ky:ky + H, kx:kx + W], wa[:, ky, kx].view(1, -1, 1, 1))
+    return acc, mag
+
+
+def dw_ln_ref(acc, mag, bias, lw, lb, out_dtype, stat_channels=None):
+    """LayerNorm form from the conv sums (NCHW): {"y": LayerNorm over C of v = conv + bias, "raw": v rounded once}, each (ref, bound), NCHW.
+    stat_channels: a DEFECT for the sensitivity tests -- the statistics taken over that many leading channels only."""
+    N, C, H, W = acc.shape
+    b = bias.double().view(1, -1, 1, 1)
+    v = (acc + b).permute(0, 2, 3, 1).reshape(-1, C)
+    verr = (ACC * mag + EPI * b.abs()).permute(0, 2, 3, 1).reshape(-1, C).amax(-1, keepdim=True)
+    if stat_channels is None:
+        y = F.layer_norm(v, (C,), lw.double(), lb.double(), DW_EPS)
+    else:
+        m = v[:, :stat_channels].mean(-1, keepdim=True)
+        var = ((v[:, :stat_channels] - m) ** 2).mean(-1, keepdim=True)
+        y = (v - m) / torch.sqrt(var + DW_EPS) * lw.double() + lb.double()
+    bnd = ln_bound(y, v, lw, lb, DW_EPS, verr, out_dtype)
+    back = lambda t: t.reshape(N, H, W, C).permute(0, 3, 1, 2)
+    return {"y": (back(y), back(bnd)), "raw": preact_ref(acc, mag, None, bias, out_dtype)}
+
+
+def dw_operands(row: DwRow, dtype, seed=0):
+    """Random operands of a row as the kernel reads them: x / w / res in storage precision (the 16-bit walk rows: exact in both 16-bit types),
+    the per-channel vectors fp32.  Returns a dict; v0 / v1 / v2 are bias, ln weight, ln bias (LayerNorm form) or scale, shift, None."""
+    g = torch.Generator().manual_seed(seed + sum(map(ord, row.name)))
+    st = (lambda t: storage(t, dtype)) if not (row.walk and dtype != torch.float32) else storage16
+    Co, k = row.Co, row.k
+    o = dict(x=st(torch.randn(row.N, row.C, row.H, row.W, generator=g)), w=st(torch.randn(Co, k, k, generator=g) / k))
+    if row.ln:
+        o.update(v0=torch.randn(Co, generator=g) * 0.1, v1=torch.rand(Co, generator=g) + 0.5, v2=torch.randn(Co, generator=g) * 0.1)
+    else:
+        o.update(v0=torch.rand(Co, generator=g) + 0.5, v1=torch.randn(Co, generator=g) * 0.1, v2=None)
+    o["res"] = st(torch.randn(row.N, Co, row.H, row.W, generator=g)) if row.res else None
+    return o
+
+
+_dw_cache = {}
+
+
+def dw_row_sums(row: DwRow, dtype, seed=0):
+    """(operands, conv sums) of a row; the last row's are kept (the fp64 conv is the cost of a walk row: once per row and storage)."""
+    key = (row.name, "16" if row.walk and dtype != torch.float32 else DNAME[dtype], seed)
+    if key not in _dw_cache:
+        _dw_cache.clear()
+        o = dw_operands(row, dtype, seed)
+        _dw_cache[key] = (o, dw_sums(o["x"], o["w"]))
+    return _dw_cache[key]
+
+
+def dw_row_reference(row: DwRow, dtype, seed=0):
+    """Operands and {"y": (ref, bound)[, "raw": (ref, bound)]} of a row, NCHW fp64: what the GPU parity test checks with `check`."""
+    o, (acc, mag) = dw_row_sums(row, dtype, seed)
+    if row.ln:
+        refs = dw_ln_ref(acc, mag, o["v0"], o["v1"], o["v2"], dtype)
+        if not row.raw:
+            del refs["raw"]
+        return o, refs
+    return o, {"y": affine_act_ref(acc, mag, o["v0"], o["v1"], row.act, o["res"], dtype)}
+
+
+def dw_exact_operands(row: DwRow, dtype, seed=0, target=4000.0):
+    """Integer operands of a row: x, w in [-8, 8] (exact in every storage type); every product and partial sum is exact in fp32.
+    LayerNorm form: a bias in quarter steps up to +-2000 (so that conv + bias needs rounding in the 16-bit types), LayerNorm vectors as in
+    dw_operands; exact["raw"] = conv + bias.  Scale / shift form: a power-of-two scale putting the outputs near `target`, a shift in quarter
+    steps, an integer residual; exact["conv"] = conv * scale + shift, exact["y"] = that + res."""
+    key = (row.name, "exact", seed)
+    if key not in _dw_cache:      # (x, w and their conv do not depend on the storage type: once per row)
+        _dw_cache.clear()
+        g = torch.Generator().manual_seed(seed + 1 + sum(map(ord, row.name)))
+        x, w = torch.randint(-8, 9, (row.N, row.C, row.H, row.W), generator=g).double(), torch.randint(-8, 9, (row.Co, row.k, row.k), generator=g).double()
+        _dw_cache[key] = (x, w, dw_sums(x, w)[0])
+    x, w, acc = _dw_cache[key]
+    g = torch.Generator().manual_seed(seed + 2 + sum(map(ord, row.name)))
+    Co, k = row.Co, row.k
+    o = dict(x=x, w=w, res=None)
+    if row.ln:
+        o.update(v0=torch.randint(-8000, 8001, (Co,), generator=g).float() * 0.25, v1=torch.rand(Co, generator=g) + 0.5, v2=torch.randn(Co, generator=g) * 0.1)
+        exact = {"raw": acc + o["v0"].double().view(1, -1, 1, 1)}
+    else:
+        p = round(math.log2(target / (24.0 * k)))
+        o.update(v0=(2.0 ** (p + torch.randint(0, 2, (Co,), generator=g))).float(), v1=torch.randint(-64, 65, (Co,), generator=g).float() * 0.25, v2=None)
+        conv = acc * o["v0"].double().view(1, -1, 1, 1) + o["v1"].double().view(1, -1, 1, 1)
+        exact = {"conv": conv, "y": conv}
+        if row.res:
+            o["res"] = storage(torch.randint(-1000, 1001, tuple(acc.shape), generator=g).double(), dtype)
+            exact["y"] = conv + o["res"]
+    for e in exact.values():
+        assert torch.equal(e.float().double(), e), "the exact result must be an fp32 value"
+    return o, exact
+
+
+def dw_tile_of(row: DwRow, dtype, n, y, x):
+    """(tile index in the kernel's walk order, image, tile row, tile column) of output pixel (n, y, x)."""
+    th, tw = row.field(dtype, "th"), row.field(dtype, "tw")
+    ty, tx = y // th, x // tw
+    tiles_x, tiles_y = (row.W + tw - 1) // tw, (row.H + th - 1) // th
+    return (n * tiles_y + ty) * tiles_x + tx, n, ty, tx

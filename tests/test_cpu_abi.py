@@ -77,6 +77,18 @@ def test_entry_points_reject_bad_arguments_without_launching(lib):
     assert lib.mtbt_mask_assemble(None, None) == -1
     assert lib.mtbt_stem_conv4x4_ln(None, None, None, None, None, 1e-6, None, 1, 8, 8, 96, 0, None) == -1
     assert lib.mtbt_dwconv_nhwc(None, None, None, None, None, 0.0, None, None, 0, None, 1, 8, 8, 96, 7, 0, None) == -1
+    # an activation code outside MTBT_ACT_*: refused with every pointer set (16: aligned, never dereferenced), by the shape rules the
+    # host-only choice query shares with the entry points -- which accepts the last code and refuses the next
+    for act in (-1, 9):
+        assert lib.mtbt_dwconv_nhwc(16, 16, None, None, None, 0.0, 16, 16, act, 16, 1, 8, 8, 96, 7, L.BF16, None) == -1
+        assert lib.mtbt_dwconv_nhwc_train(16, 16, None, None, None, 0.0, 16, 16, act, 16, None, 16, 1, 8, 8, 96, 7, L.BF16, None) == -1
+        assert lib.mtbt_dwconv_kernel_choice(1, 8, 8, 96, 7, 0, act, L.BF16, (C.c_int32 * 9)()) == -1
+        assert lib.mtbt_dwconv3x3_mult_kernel_choice(1, 8, 8, 128, 2, act, L.BF16, (C.c_int32 * 9)()) == -1
+    choice = (C.c_int32 * 9)()
+    assert lib.mtbt_dwconv_kernel_choice(1, 8, 8, 96, 7, 0, 8, L.BF16, choice) == 0 and tuple(choice) == (4, 8, 4, 1, 1, -1, 2, 8, 1)
+    assert lib.mtbt_dwconv3x3_mult_kernel_choice(1, 8, 8, 128, 2, 8, L.BF16, choice) == 0 and tuple(choice) == (4, 16, 8, 1, 0, -1, 2, 8, 2)
+    assert lib.mtbt_dwconv_kernel_choice(1, 8, 8, 96, 7, 0, 0, L.BF16, None) == -1
+    assert lib.mtbt_dwconv3x3_mult_kernel_choice(1, 8, 8, 128, 2, 0, L.BF16, None) == -1
     assert lib.mtbt_layernorm_nhwc(None, None, None, 0.0, None, 1, 96, 0, None) == -1
     assert lib.mtbt_gap_fc(None, None, None, None, 1, 1, 8, 1, 0, None) == -1
     assert lib.mtbt_cast(None, None, 1, 0, 1, None) == -1

@@ -1,5 +1,7 @@
 """CPU checks of tests/kernel_reference.py: the per-element bounds are tight enough to mean something, and every row of the conv variant
 table reaches the kernel it names (mtbt_conv_kernel_choice: no launch, no GPU)."""
+import dataclasses
+
 import pytest
 import torch
 
@@ -233,3 +235,184 @@ TRAIN_PARAMS = [(r, d) for r in R.TRAIN_VARIANTS for d in r.dtypes]
 def test_train_variant_table_kernel_choice(row, dtype):
     from multitask_bonetumor_yolo_amd import _lib as L
     assert R.kernel_choice(L, L.load(), R.train_conv_args(L, row, dtype)) == row.expect
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The depthwise kernels: variant table, choice query, and what the parity check of tests/test_gpu_dwconv_variants.py can see
+# ---------------------------------------------------------------------------------------------------------------------------------------
+F16, BF16, F32 = torch.float16, torch.bfloat16, torch.float32
+
+
+def _dw(rows, dt, **want):
+    """Rows that run in dt and whose choice fields / attributes have the wanted values."""
+    out = []
+    for r in rows:
+        if dt not in r.dtypes:
+            continue
+        if all((r.field(dt, k) if k in R.DW_FIELDS else getattr(r, k)) == v for k, v in want.items()):
+            out.append(r)
+    return out
+
+
+def test_dw_variant_table_covers_every_instantiation_and_the_tile_walk():
+    V = R.DW_VARIANTS
+    assert len({r.name for r in V}) == len(V)
+    for r in V:
+        assert r.C % 8 == 0 and r.Co <= 768 and r.k in (3, 7) and not (r.ln and (r.res or r.M)) and not (r.raw and not r.ln)
+        for dt in r.dtypes:
+            th, tw = r.field(dt, "th"), r.field(dt, "tw")
+            assert r.field(dt, "tiles") == r.N * -(-r.H // th) * -(-r.W // tw), r.name
+            assert r.field(dt, "full") == int(dt != F32 and r.H % th == 0 and r.W % tw == 0), r.name
+            assert r.field(dt, "gx") % 8 == 0
+            assert (r.e16 is not None and r.e32 is not None) or r.walk, r.name
+    plain = [r for r in V if not r.M]
+    for dt in R.DTYPES:
+        fulls = (0, 1) if dt != F32 else (0,)
+        ln, af = [r for r in plain if r.ln], [r for r in plain if not r.ln]
+        # LayerNorm form: 7x7 and 3x3 x MAXCH 1, 2, 3, 6 (x FULL / bounds-checked for the 16-bit types); the six-chunk kernel at 4, 5 and 6 live
+        # chunks; a last chunk of 8 channels in a one-chunk and in a multi-chunk kernel
+        for k in (7, 3):
+            for maxch in (1, 2, 3, 6):
+                for full in fulls:
+                    assert _dw(ln, dt, k=k, maxch=maxch, full=full, walk=False), (dt, k, maxch, full)
+            live = {-(-r.C // 128) for r in _dw(ln, dt, k=k, maxch=6)}
+            assert live >= {4, 5, 6}, (dt, k, live)
+            assert _dw(ln, dt, k=k, maxch=1, walk=True), (dt, k)
+        assert _dw(ln, dt, C=8, maxch=1)
+        assert any(r.C % 128 == 8 and r.field(dt, "maxch") > 1 for r in _dw(ln, dt))
+        assert {r.field(dt, "maxch") for r in _dw(ln, dt) if r.C % 128 == 8} >= {2, 3, 6}
+        assert any(r.raw for r in _dw(ln, dt, k=3)) and any(r.raw for r in _dw(ln, dt, k=7)) and any(not r.raw for r in _dw(ln, dt))
+        for maxch in (2, 3, 6):
+            assert _dw(ln, dt, k=7, maxch=maxch, walk=True), (dt, maxch)
+        # scale / shift form: 3x3 and 7x7; one grid row, two, three or more with a ragged last chunk; full- and half-width tiles; FULL and
+        # bounds-checked; the activation as the NONE constant, the SILU constant and at run time
+        for k in (7, 3):
+            assert _dw(af, dt, k=k, gy=1) and any(r.C % 128 for r in _dw(af, dt, k=k, gy=2))
+            assert any(r.C % 128 for r in af if dt in r.dtypes and r.k == k and r.field(dt, "gy") >= 3)
+            for full in fulls:
+                assert _dw(af, dt, k=k, full=full, walk=False), (dt, k, full)
+            assert {r.res for r in _dw(af, dt, k=k)} == {"", "buf", "y"}
+            assert any(r.res for r in af if dt in r.dtypes and r.k == k and r.field(dt, "gy") > 1)
+        for xb in (8, 4):
+            assert _dw(af, dt, k=7, xb=xb, walk=False) and _dw(af, dt, k=7, xb=xb, walk=True, gy=1), (dt, xb)
+            assert any(r.res for r in _dw(af, dt, k=7, xb=xb))
+        assert _dw(af, dt, k=3, walk=True, gy=1)
+        if dt != F32:
+            for k in (7, 3):
+                assert {r.field(dt, "act") for r in _dw(af, dt, k=k)} >= {R.ACT_NONE, R.ACT_SILU, -1}, (dt, k)
+            assert _dw(af, dt, k=7, xb=4, full=1) and _dw(af, dt, k=7, xb=4, full=0)
+        else:
+            assert {r.field(dt, "act") for r in _dw(af, dt)} == {-1}
+        assert {r.act for r in _dw(af, dt)} >= {R.ACT_NONE, R.ACT_SILU, R.ACT_ELU}
+        # multiplier form: M = 1 and 2, C = 128 and 256, ragged and full tiles
+        mu = [r for r in V if r.M and dt in r.dtypes]
+        assert {(r.M, r.C) for r in mu} == {(1, 128), (2, 128), (1, 256), (2, 256)}
+        assert {r.H % 4 == 0 and r.W % r.field(dt, "tw") == 0 for r in mu} == {True, False}
+        assert all(r.field(dt, "gy") == r.M * r.C // 128 for r in mu)
+        # image edges
+        rows = _dw(V, dt)
+        assert sum(r.N >= 2 for r in rows if not r.walk) > 0.8 * sum(not r.walk for r in rows)
+        for n in (1, 2):
+            assert any(r.H == n for r in rows) and any(r.W == n for r in rows), (dt, n)
+        assert any(r.H == 3 for r in rows)
+        for tw in {r.field(dt, "tw") for r in rows}:
+            assert any(r.W == tw - 1 for r in _dw(rows, dt, tw=tw)), (dt, tw)
+        # the walk: one chunk -- some workgroup runs a first, a middle and a last tile; several chunks -- some workgroup takes a second tile
+        for r in _dw(V, dt, walk=True):
+            tiles, gx = r.field(dt, "tiles"), r.field(dt, "gx")
+            assert r.field(dt, "gy") == 1
+            assert tiles >= 2 * gx + 1 if r.field(dt, "maxch") == 1 else tiles > gx, (r.name, tiles, gx)
+    # 3x3 LayerNorm walk rows in bf16 for MAXCH 1 and 3
+    assert _dw(V, BF16, k=3, ln=True, walk=True, maxch=1) and _dw(V, BF16, k=3, ln=True, walk=True, maxch=3)
+
+
+DW_PARAMS = [(r, d) for r in R.DW_VARIANTS for d in r.dtypes]
+DW_IDS = [f"{r.name}-{R.DNAME[d]}" for r, d in DW_PARAMS]
+
+
+@pytest.mark.parametrize("row,dtype", DW_PARAMS, ids=DW_IDS)
+def test_dw_variant_table_kernel_choice(row, dtype):
+    from multitask_bonetumor_yolo_amd import _lib as L
+    assert R.dw_choice(L, L.load(), row, dtype) == row.expect(dtype)
+
+
+def test_dw_choice_is_the_launch_rule_not_a_copy():
+    """The query's tile count and grid follow the shape: the tiles of a 16-bit 4 x 16 tiling, a grid capped at the resident workgroups
+    (a multiple of the 8 XCDs), grid rows for the scale / shift form only; and the errors of the entry point."""
+    import ctypes as C
+    from multitask_bonetumor_yolo_amd import _lib as L
+    lib = L.load()
+    out = (C.c_int32 * 9)()
+    assert lib.mtbt_dwconv_kernel_choice(1, 400, 4096, 96, 7, 1, 0, L.BF16, out) == 0
+    assert tuple(out)[:7] == (4, 16, 8, 1, 1, 0, 100 * 256) and out[7] % 256 == 0 and out[7] <= 1024 and out[8] == 1
+    assert lib.mtbt_dwconv_kernel_choice(1, 8, 16, 384, 7, 0, 0, L.BF16, out) == 0 and out[8] == 3 and out[3] == 1
+    assert lib.mtbt_dwconv_kernel_choice(1, 8, 16, 384, 7, 1, 0, L.BF16, out) == 0 and out[8] == 1 and out[3] == 3
+    for bad in ((0, 8, 8, 96, 7, 1, 0, L.BF16), (1, 8, 8, 100, 7, 1, 0, L.BF16), (1, 8, 8, 776, 7, 1, 0, L.BF16), (1, 8, 8, 96, 5, 1, 0, L.BF16),
+                (1, 8, 8, 96, 7, 0, 9, L.BF16), (1, 8, 8, 96, 7, 0, -1, L.BF16), (1, 8, 8, 96, 7, 1, 0, 3)):
+        assert lib.mtbt_dwconv_kernel_choice(*bad, out) == -1, bad
+    assert lib.mtbt_dwconv_kernel_choice(1, 8, 8, 96, 7, 1, 0, L.BF16, None) == -1
+    for bad in ((1, 8, 8, 96, 1, 0, L.BF16), (1, 8, 8, 128, 3, 0, L.BF16), (1, 8, 8, 512, 2, 0, L.BF16), (1, 8, 8, 128, 2, 9, L.BF16), (1, 8, 8, 128, 2, 0, 3)):
+        assert lib.mtbt_dwconv3x3_mult_kernel_choice(*bad, out) == -1, bad
+
+
+def _rounded(ref, dtype):
+    return ref.to(dtype).double()
+
+
+def _swap_first_tiles(out, row, dtype):
+    """The output with tile 0's pixels replaced by its right neighbour's (a stale or mis-indexed tile)."""
+    th, tw = row.field(dtype, "th"), row.field(dtype, "tw")
+    bad = out.clone()
+    wn = min(tw, row.W - tw)
+    bad[:, :, :th, :wn] = out[:, :, :th, tw:tw + wn]
+    return bad
+
+
+@pytest.mark.parametrize("dtype", [F16, BF16, F32], ids=lambda d: R.DNAME[d])
+def test_dw_parity_check_rejects_defective_layernorm_kernels(dtype):
+    row = R.DW_ROWS["ln7_c264_r"]
+    o, refs = R.dw_row_reference(dataclasses.replace(row, raw=True), dtype)
+    for which, (ref, bnd) in refs.items():
+        R.check(_rounded(ref, dtype), ref, bnd, f"correctly rounded {which}")
+    w = o["w"].clone()
+    w[:, 2, 5] = 0                                                                            # one tap dropped
+    acc, mag = R.dw_sums(o["x"], w)
+    bad = R.dw_ln_ref(acc, mag, o["v0"], o["v1"], o["v2"], dtype)
+    assert not R.within(_rounded(bad["y"][0], dtype), *refs["y"]) and not R.within(_rounded(bad["raw"][0], dtype), *refs["raw"])
+    acc, mag = R.dw_sums(o["x"], o["w"])
+    bad = R.dw_ln_ref(acc, mag, o["v0"], o["v1"], o["v2"], dtype, stat_channels=128)          # statistics over the first chunk only
+    assert not R.within(_rounded(bad["y"][0], dtype), *refs["y"])
+    for which, (ref, bnd) in refs.items():                                                    # a tile's output replaced by its neighbour's
+        assert not R.within(_swap_first_tiles(_rounded(ref, dtype), row, dtype), ref, bnd), which
+
+
+@pytest.mark.parametrize("dtype", [F16, BF16, F32], ids=lambda d: R.DNAME[d])
+def test_dw_parity_check_rejects_defective_affine_kernels(dtype):
+    row = R.DW_ROWS["af7_c128_r"]
+    assert row.act == R.ACT_SILU and row.res == "buf"
+    o, refs = R.dw_row_reference(row, dtype)
+    ref, bnd = refs["y"]
+    R.check(_rounded(ref, dtype), ref, bnd, "correctly rounded")
+    w = o["w"].clone()
+    w[:, 6, 0] = 0                                                                            # one tap dropped
+    bad, _ = R.affine_act_ref(*R.dw_sums(o["x"], w), o["v0"], o["v1"], row.act, o["res"], dtype)
+    assert not R.within(_rounded(bad, dtype), ref, bnd)
+    assert not R.within(_swap_first_tiles(_rounded(ref, dtype), row, dtype), ref, bnd)        # a tile's output replaced by its neighbour's
+    acc, _ = R.dw_sums(o["x"], o["w"])                                                        # the residual added before the activation
+    pre = acc * o["v0"].double().view(1, -1, 1, 1) + o["v1"].double().view(1, -1, 1, 1)
+    assert not R.within(_rounded(R.act64(pre + o["res"], row.act), dtype), ref, bnd)
+
+
+def test_dw_exact_operands_need_rounding_and_see_a_stale_tile():
+    """The integer operands of the bit-exact tests: the LayerNorm input and the scale / shift output need rounding in the 16-bit types, and
+    a tile replaced by its neighbour's differs bit for bit, at a pixel dw_tile_of places in tile 0."""
+    for name in ("ln7_c264_r", "af7_c264_r"):
+        row = R.DW_ROWS[name]
+        for dtype in (F16, BF16):
+            _, exact = R.dw_exact_operands(row, dtype)
+            e = exact["raw" if row.ln else "y"]
+            want = R.rounded_once(e, dtype)
+            assert (want != e).float().mean().item() > 0.3
+            diff = _swap_first_tiles(want, row, dtype) != want
+            n, _, y, x = (int(v) for v in diff.nonzero()[0])
+            assert R.dw_tile_of(row, dtype, n, y, x) == (0, 0, 0, 0)
