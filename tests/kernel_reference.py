@@ -23,6 +23,10 @@ The depthwise kernels (LayerNorm form, scale / shift form, training outputs, dep
 dw_sums / dw_ln_ref / dw_row_reference; tests/test_gpu_dwconv_variants.py runs it.  They add no term to the list above: the scale / shift
 form is affine_act_ref on the depthwise sums, the LayerNorm form ln_bound with an input error of ACC * sum |x * w| + EPI * |bias|, and the
 LayerNorm input kept for training (raw) preact_ref with the bias as the shift: conv + bias rounded once.
+
+The fused inference kernels (ConvT 2x2 -> conv 3x3 as one direct conv, the BiFPN node, the ConvNeXt MLP) have the tables UPCONV_VARIANTS,
+NODE_VARIANTS and MLP_VARIANTS and the references upconv_ref / node_ref / mlp_ref; tests/test_gpu_fused_variants.py runs them.  They add no
+term either; an intermediate that a kernel rounds to the storage type is rounded at the same point (round_flips).
 """
 import math
 from dataclasses import dataclass, field
@@ -797,3 +801,347 @@ def dw_tile_of(row: DwRow, dtype, n, y, x):
     ty, tx = y // th, x // tw
     tiles_x, tiles_y = (row.W + tw - 1) // tw, (row.H + th - 1) // th
     return (n * tiles_y + ty) * tiles_x + tx, n, ty, tx
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# The fused inference kernels: upconv_fused.hip (mtbt_convt2x2_conv3x3_nhwc), node_gemm.hip (mtbt_bifpn_node_nhwc) and mlp_fused.hip
+# (mtbt_convnext_mlp_fused_dt / _train); tests/test_gpu_fused_variants.py runs the tables UPCONV_VARIANTS, NODE_VARIANTS, MLP_VARIANTS.
+# No term of their own.  Two of the kernels round an INTERMEDIATE to the storage type (the fused map of the node, the hidden activations of
+# the MLP) from an fp32 value: the reference rounds the fp64 value at the same point, and where that value lies within the fp32 error of a
+# rounding midpoint the kernel may land on the other neighbour (round_flips): such an element may be off by one spacing of the storage
+# type, carried to the outputs through the absolute weights of the GEMM behind it.
+# ------------------------------------------------------------------------------------------------------------------------------------
+def spacing_below(v: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """Distance from |v| (a value of the 16-bit `dtype`, fp64 tensor) down to the next smaller magnitude of `dtype` (at zero: the smallest
+    subnormal)."""
+    a = v.abs().to(dtype)
+    prev = (a.view(torch.int16) - 1).clamp(min=0).view(dtype).double()
+    tiny = 2.0 ** -24 if dtype == torch.float16 else 2.0 ** -133
+    return torch.where(a == 0, torch.full_like(v, tiny), a.double() - prev)
+
+
+def spacing_above(v: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """Distance from |v| up to the next larger magnitude of `dtype`."""
+    return spacing_below(v.abs().to(dtype).view(torch.int16).add(1).view(dtype).double(), dtype)
+
+
+def round_flips(v: torch.Tensor, dtype: torch.dtype, delta: torch.Tensor):
+    """v (fp64) rounded to `dtype`, the elements whose fp32 counterpart (|error| <= delta) may round to the other neighbour, and the width
+    such a flip adds (the larger neighbouring spacing, 0 elsewhere)."""
+    r = v.to(dtype).double()
+    below, above = spacing_below(r, dtype), spacing_above(r, dtype)
+    flip = (v - r).abs() >= 0.5 * torch.minimum(below, above) - delta
+    return r, flip, flip.double() * torch.maximum(below, above)
+
+
+# ---- upconv_fused.hip ---------------------------------------------------------------------------------------------------------------
+def upconv_sums(x: torch.Tensor, wc: torch.Tensor):
+    """(sum, sum of magnitudes) of the composed 2 x 2-tap convolution of include/mtbt_hip.h, NCHW fp64 [N, K, 2H, 2W]: output (2i + a, 2j + b)
+    = sum over (rho, sigma, ci) of wc[2a + b][k][rho][sigma][ci] * x[i + a - 1 + rho][j + b - 1 + sigma][ci], zero outside the source map.
+    x [N, C, H, W], wc [4, K, 2, 2, C]."""
+    (N, C, H, W), K = x.shape, wc.shape[1]
+    xp = F.pad(x, (1, 1, 1, 1))                                  # source pixel (r, c) at xp[r + 1][c + 1]
+    acc = torch.zeros(N, K, 2 * H, 2 * W, dtype=torch.float64)
+    mag = torch.zeros_like(acc)
+    for a in range(2):
+        for b in range(2):
+            for rho in range(2):
+                for sig in range(2):
+                    src = xp[:, :, a + rho:a + rho + H, b + sig:b + sig + W]
+                    wt = wc[2 * a + b, :, rho, sig, :]
+                    acc[:, :, a::2, b::2] += torch.einsum("kc,nchw->nkhw", wt, src)
+                    mag[:, :, a::2, b::2] += torch.einsum("kc,nchw->nkhw", wt.abs(), src.abs())
+    return acc, mag
+
+
+def upconv_shift(shift9: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """shift9 [9, K] as the per-pixel shift [1, K, 2H, 2W]: class rc * 3 + cc, rc / cc = 0 first, 2 last, 1 interior OUTPUT row / column."""
+    cls = lambda n: torch.tensor([0] + [1] * (n - 2) + [2])
+    idx = cls(2 * H)[:, None] * 3 + cls(2 * W)[None, :]
+    return shift9.double()[idx].permute(2, 0, 1).unsqueeze(0)
+
+
+def upconv_bound(acc, mag, sh, act, out_dtype):
+    """act(acc + sh) rounded once; the terms of affine_act_ref with a unit scale and a per-pixel shift.  Returns (ref, bound)."""
+    pre = acc + sh
+    y = act64(pre, act)
+    bnd = ACT_LIPSCHITZ[act] * (ACC * mag + EPI * (pre.abs() + sh.abs())) + act_error(pre, act) + EPI * y.abs()
+    return y, bnd + output_rounding(y, out_dtype)
+
+
+def upconv_ref(x, wc, shift9, act, out_dtype):
+    """mtbt_convt2x2_conv3x3_nhwc from the formula of its header: x [N, C, H, W] and wc [4, K, 2, 2, C] in storage precision (the composed
+    weights ALREADY rounded), shift9 [9, K] fp32.  Returns (ref, bound, sum of magnitudes), NCHW fp64 [N, K, 2H, 2W]."""
+    acc, mag = upconv_sums(x, wc)
+    ref, bnd = upconv_bound(acc, mag, upconv_shift(shift9, x.shape[2], x.shape[3]), act, out_dtype)
+    return ref, bnd, mag
+
+
+# Rows: N, H, W, C (16-bit types), K, C32 (the channels of the fp32 run: one slab is 64 bytes, 32 / 16 channels), the activations it runs with,
+# the layout and whether the exact-rounding test runs it.  A workgroup owns a 16 x 16 source tile x 128 virtual channels q * K + k (one
+# parity q; K = 256: two channel tiles per parity, cbase = 0 / 128); launch: ceil(tiles / 8) slots on each of 8 XCDs, the surplus returns.
+#   layout "slice": x = channels 16 .. 16 + C of a C + 32 wide NaN-filled buffer, y = channels 8 .. 8 + K of a K + 16 wide sentinel-filled
+#   one, both with a gap of pixel rows after every image (UP_SLICE).
+UP_SLICE = dict(xpad=32, xc0=16, xgap=5, ypad=16, yc0=8, ygap=3)
+
+
+@dataclass(frozen=True)
+class UpRow:
+    name: str
+    N: int
+    H: int
+    W: int
+    C: int               # 0: the row does not run in the 16-bit types
+    K: int
+    C32: int             # 0: the row does not run in fp32
+    acts: Tuple[int, ...] = (ACT_SILU,)
+    layout: str = "dense"
+    exact: bool = False
+
+    @property
+    def dtypes(self):
+        return tuple(d for d in DTYPES if self.channels(d))
+
+    def channels(self, dtype):
+        return self.C32 if dtype == torch.float32 else self.C
+
+    @property
+    def tiles(self):
+        return self.N * (self.H // 16) * (self.W // 16)
+
+
+UPCONV_VARIANTS = [
+    UpRow("tile1", 1, 16, 16, 32, 128, 16, acts=(ACT_NONE, ACT_SILU), exact=True),     # one tile: all nine classes in a workgroup; one slab
+    UpRow("seam_w", 1, 16, 32, 96, 128, 48),                                           # tile seam in a row; three slabs
+    UpRow("seam_h", 1, 32, 16, 96, 128, 48),                                           # tile seam in a column
+    UpRow("k256", 2, 16, 16, 64, 256, 64, acts=(ACT_NONE, ACT_SILU), exact=True),      # cbase = 128: two channel tiles per parity
+    UpRow("xcd3", 3, 16, 16, 64, 128, 64),                                             # 3 tiles: one slot per XCD, 5 of 8 empty
+    UpRow("xcd9", 1, 48, 48, 32, 128, 16),                                             # 9 tiles: two slots per XCD, 7 of 16 empty
+    UpRow("model", 1, 16, 16, 256, 256, 0),                                            # the model's channel counts on one tile
+    UpRow("slice", 2, 16, 16, 64, 256, 64, layout="slice"),                            # strided x and y, gaps between the images
+]
+UP_ROWS = {r.name: r for r in UPCONV_VARIANTS}
+
+
+def up_operands(row: UpRow, dtype, seed=0):
+    """Random operands of a row as the kernel reads them: x [N, C, H, W] and wc [4, K, 2, 2, C] in storage precision, shift9 [9, K] fp32 with
+    nine different class vectors."""
+    g = torch.Generator().manual_seed(seed + sum(map(ord, row.name)))
+    C = row.channels(dtype)
+    x = storage(torch.randn(row.N, C, row.H, row.W, generator=g), dtype)
+    wc = storage(torch.randn(4, row.K, 2, 2, C, generator=g) / (4 * C) ** 0.5, dtype)
+    shift9 = torch.randn(9, row.K, generator=g) * 0.3
+    return x, wc, shift9
+
+
+def up_exact_operands(row: UpRow, dtype, seed=0):
+    """Integer x and wc in [-8, 8] (exact in every storage type; |sum| <= 64 * 4 C <= 2^16) and a shift9 in steps of 1/64 up to +-64 whose nine
+    class vectors differ pairwise: every product, partial sum and the shifted result (at most 17 + 6 bits) is exact in fp32, and a result
+    beyond 32 mostly needs rounding in fp16 (11 bits), nearly every one in bf16.  Returns the operands and the exact fp64 result (act none)."""
+    g = torch.Generator().manual_seed(seed + 1 + sum(map(ord, row.name)))
+    C = row.channels(dtype)
+    x = torch.randint(-8, 9, (row.N, C, row.H, row.W), generator=g).double()
+    wc = torch.randint(-8, 9, (4, row.K, 2, 2, C), generator=g).double()
+    shift9 = torch.randint(-4096, 4097, (9, row.K), generator=g).float() / 64.0
+    assert all(not torch.equal(shift9[i], shift9[j]) for i in range(9) for j in range(i))
+    exact = upconv_sums(x, wc)[0] + upconv_shift(shift9, row.H, row.W)
+    assert torch.equal(exact.float().double(), exact), "the exact result must be an fp32 value"
+    return x, wc, shift9, exact
+
+
+# ---- node_gemm.hip ------------------------------------------------------------------------------------------------------------------
+RES_ID, RES_UP_BILINEAR, RES_DOWN_MEAN = 0, 1, 2          # resampling modes of include/mtbt_hip.h that a node takes
+
+
+def bilinear_up2(x: torch.Tensor, clamp_early: int = 0) -> torch.Tensor:
+    """Bilinear x2 with align_corners=False, written out (fp64, NCHW): source coordinate (dst + 1/2) / 2 - 1/2 clamped at 0, the neighbour
+    i0 + 1 clamped at the last row / column.  clamp_early: a DEFECT for the sensitivity tests -- the ROW neighbour clamped that many rows
+    before the last one."""
+    def taps(n_src, early):
+        s = ((torch.arange(2 * n_src, dtype=torch.float64) + 0.5) / 2 - 0.5).clamp(min=0)
+        i0 = s.floor().long()
+        i1 = torch.where(i0 < n_src - 1 - early, i0 + 1, i0)
+        return i0, i1, s - i0
+    y0, y1, ly = taps(x.shape[2], clamp_early)
+    x0, x1, lx = taps(x.shape[3], 0)
+    ly, lx = ly.view(-1, 1), lx.view(1, -1)
+    top = (1 - lx) * x[:, :, y0][:, :, :, x0] + lx * x[:, :, y0][:, :, :, x1]
+    bot = (1 - lx) * x[:, :, y1][:, :, :, x0] + lx * x[:, :, y1][:, :, :, x1]
+    return (1 - ly) * top + ly * bot
+
+
+def mean2x2(x: torch.Tensor) -> torch.Tensor:
+    return 0.25 * (x[:, :, 0::2, 0::2] + x[:, :, 0::2, 1::2] + x[:, :, 1::2, 0::2] + x[:, :, 1::2, 1::2])
+
+
+def node_resample(x, mode, clamp_early=0):
+    return x if mode == RES_ID else bilinear_up2(x, clamp_early) if mode == RES_UP_BILINEAR else mean2x2(x)
+
+
+def f32_values(wgts):
+    """The fusion weights as the kernel reads them: fp32."""
+    return [float(v) for v in torch.tensor(list(wgts), dtype=torch.float32).double()]
+
+
+def node_fused(inputs, wgts, modes, clamp_early=0):
+    """(s, sum of magnitudes) of the fused map s = sum_i wgt_i * resample_i(x_i), fp64 NCHW."""
+    wv = f32_values(wgts)
+    s = sum(w * node_resample(x, m, clamp_early) for w, x, m in zip(wv, inputs, modes))
+    mag = sum(abs(w) * node_resample(x.abs(), m, clamp_early) for w, x, m in zip(wv, inputs, modes))
+    return s, mag
+
+
+def node_output(s, smag, w, shift, act, dtype):
+    """act(W round_T(s) + shift) from the exact fused map.  The kernel forms s in fp32: at most 7 roundings of 2^-24 lie on any path from an
+    input to s (the bilinear form's two products and two sums, the weight product, two sums of the weighted terms), taken as 4 EPI of the
+    summed magnitudes; an element of s within that of a rounding midpoint may be one spacing off (round_flips), which reaches an output
+    through |W| and the activation's Lipschitz constant.  Returns (ref, bound, flip mask)."""
+    sT, flip, width = round_flips(s, dtype, 4 * EPI * smag)
+    w4 = w[:, :, None, None]
+    ref, bnd = affine_act_ref(F.conv2d(sT, w4), F.conv2d(sT.abs(), w4.abs()), None, shift, act, None, dtype)
+    return ref, bnd + ACT_LIPSCHITZ[act] * F.conv2d(width, w4.abs()), flip
+
+
+def node_ref(inputs, wgts, modes, w, shift, act, dtype):
+    """mtbt_bifpn_node_nhwc: inputs NCHW fp64 in storage precision, wgts the fusion weights, modes the resampling modes, w [K, C] in storage
+    precision, shift [K] fp32.  Returns (ref, bound, flip mask of the fused map)."""
+    return node_output(*node_fused(inputs, wgts, modes), w, shift, act, dtype)
+
+
+# Rows: kind "td" (top-down: identity + bilinear x2) on N, H, W = 3, 6, 10 -- 60 pixels per image, so the 64-pixel workgroups 0 .. 2 each span
+# two images -- or "out" (output: identity + identity + 2x2 mean) on 2, 5, 7 -- 70 pixels, an odd map, the third input 10 x 14; C = K;
+# wdev: the weights come from device memory and wgt[] holds other values; slice: y = channels 8 .. 8 + K of a K + 8 wide sentinel-filled buffer.
+NODE_WGT = {"td": (0.55, 0.45), "out": (0.31, 0.42, 0.27)}
+NODE_WGT_OTHER = {"td": (0.2, 0.8), "out": (0.5, 0.1, 0.4)}
+NODE_MODES = {"td": (RES_ID, RES_UP_BILINEAR), "out": (RES_ID, RES_ID, RES_DOWN_MEAN)}
+NODE_SHAPE = {"td": (3, 6, 10), "out": (2, 5, 7)}
+NODE_DTYPES = (torch.bfloat16, torch.float16)
+
+
+@dataclass(frozen=True)
+class NodeRow:
+    name: str
+    kind: str
+    C: int
+    act: int = ACT_ELU
+    wdev: bool = False
+    slice: bool = False
+    dtypes: Tuple[torch.dtype, ...] = NODE_DTYPES
+
+    @property
+    def shape(self):
+        return NODE_SHAPE[self.kind]
+
+    @property
+    def modes(self):
+        return NODE_MODES[self.kind]
+
+    @property
+    def pitch(self):
+        return self.C + 8 if self.slice else self.C
+
+    @property
+    def c0(self):
+        return 8 if self.slice else 0
+
+
+NODE_VARIANTS = [
+    NodeRow("td128", "td", 128), NodeRow("td256", "td", 256), NodeRow("out128", "out", 128), NodeRow("out256", "out", 256),
+    NodeRow("td256_wdev", "td", 256, wdev=True), NodeRow("out128_wdev", "out", 128, wdev=True),
+    NodeRow("td128_slice", "td", 128, slice=True), NodeRow("out256_slice", "out", 256, slice=True),
+    NodeRow("td256_none", "td", 256, act=ACT_NONE), NodeRow("out128_none", "out", 128, act=ACT_NONE),
+]
+NODE_ROWS = {r.name: r for r in NODE_VARIANTS}
+
+
+def node_operands(row: NodeRow, dtype, seed=0):
+    """(inputs NCHW fp64 in storage precision, w [K, C] in storage precision, shift [K] fp32) of a row."""
+    g = torch.Generator().manual_seed(seed + sum(map(ord, row.name)))
+    N, H, W = row.shape
+    sizes = {RES_ID: (H, W), RES_UP_BILINEAR: (H // 2, W // 2), RES_DOWN_MEAN: (2 * H, 2 * W)}
+    inputs = [storage(torch.randn(N, row.C, *sizes[m], generator=g), dtype) for m in row.modes]
+    w = storage(torch.randn(row.C, row.C, generator=g) / row.C ** 0.5, dtype)
+    return inputs, w, torch.randn(row.C, generator=g) * 0.3
+
+
+def node_row_reference(row: NodeRow, dtype, seed=0):
+    """Operands and (ref, bound, flip mask) of a row; the weights that count are NODE_WGT (wdev rows: those in device memory)."""
+    inputs, w, shift = node_operands(row, dtype, seed)
+    return (inputs, w, shift), node_ref(inputs, NODE_WGT[row.kind], row.modes, w, shift, row.act, dtype)
+
+
+# ---- mlp_fused.hip ------------------------------------------------------------------------------------------------------------------
+def mlp_ref(t, res, w1, b1, w2, b2, dtype, round_h=True):
+    """y = res + W2 h + b2, h = round_T(gelu_poly(W1 t + b1)): t [M, D], res [M, D] or None, w1 [4D, D], w2 [D, 4D] in storage precision and
+    NATURAL hidden order, b1 / b2 fp32.  The kernel's own polynomial GELU in fp64 (gelu_poly64), not erf + 2.3e-4: a fixed 2.3e-4 on each of
+    the 4D hidden units, summed through W2, would be looser than the hidden rounding it has to see.  fc1's fp32 accumulation (ACC of the
+    magnitudes) and the fp32 polynomial (half ACT_EVAL) can move a hidden value across a rounding midpoint: round_flips.
+    round_h=False: h is NOT rounded (the plain MLP; a defect for the sensitivity tests).
+    Returns (ref, bound, pre = W1 t + b1, bound of pre rounded once to T, flip mask of the hidden units)."""
+    pre = t @ w1.t() + b1.double()
+    pre_err = ACC * (t.abs() @ w1.abs().t() + b1.double().abs())
+    h64 = gelu_poly64(pre)
+    h, flip, width = round_flips(h64, dtype, ACT_LIPSCHITZ[ACT_GELU_POLY] * pre_err + 0.5 * ACT_EVAL * (1 + h64.abs()))
+    if not round_h:
+        h = h64
+    r = res if res is not None else torch.zeros_like(t)
+    ref = r + h @ w2.t() + b2.double()
+    bnd = output_rounding(ref, dtype) + ACC * (h.abs() @ w2.abs().t() + r.abs() + b2.double().abs()) + width @ w2.abs().t()
+    return ref, bnd, pre, output_rounding(pre, dtype) + pre_err, flip
+
+
+def mlp_hidden_order():
+    """Column order of the inference entry's fc2 weight inside a group of 32 hidden units (include/mtbt_hip.h): slot 8 g + j holds hidden
+    4 g + j (j < 4) or 16 + 4 g + (j - 4)."""
+    kk = torch.arange(32)
+    g, j = kk // 8, kk % 8
+    return torch.where(j < 4, 4 * g + j, 16 + 4 * g + (j - 4))
+
+
+def mlp_permute_w2(w2: torch.Tensor) -> torch.Tensor:
+    idx = (torch.arange(w2.shape[1] // 32)[:, None] * 32 + mlp_hidden_order()[None, :]).reshape(-1)
+    return w2[:, idx].contiguous()
+
+
+def mlp_train_rows(n4d: int) -> torch.Tensor:
+    """Row order of the training entry's fc1 weight / bias (include/mtbt_hip.h): row 16 b + 4 g + e of a group of 32 holds hidden 8 g + 4 b + e."""
+    return torch.arange(n4d).view(-1, 4, 2, 4).permute(0, 2, 1, 3).reshape(-1)
+
+
+# Rows: D, M, res, train.  A workgroup owns 128 pixels, a wave 32 (two 16-pixel fragments).  M = 1: one pixel; 17: less than a fragment pair;
+# 33: the second wave holds one pixel; 127 / 129: one workgroup -+ 1; 300: three workgroups.  D = 96 the streaming kernel, 192 the pipelined
+# one, 384 the pair kernel; train: the two HP forms (bf16, D = 96 / 192) with the fc1 pre-activation as a second output.
+MLP_DTYPES = (torch.bfloat16, torch.float16)
+
+
+@dataclass(frozen=True)
+class MlpRow:
+    name: str
+    D: int
+    M: int
+    res: bool = True
+    train: bool = False
+    dtypes: Tuple[torch.dtype, ...] = MLP_DTYPES
+
+
+MLP_VARIANTS = ([MlpRow(f"d{D}_m{M}", D, M) for D in (96, 192, 384) for M in (1, 17, 33, 127, 129, 300)]
+                + [MlpRow(f"d{D}_m129_nores", D, 129, res=False) for D in (96, 192, 384)]
+                + [MlpRow(f"train_d{D}_m{M}", D, M, train=True, dtypes=(torch.bfloat16,)) for D in (96, 192) for M in (17, 129, 300)])
+MLP_ROWS = {r.name: r for r in MLP_VARIANTS}
+
+
+def mlp_operands(row: MlpRow, dtype, seed=0):
+    """(t, res or None, w1, b1, w2, b2) of a row: storage precision, natural hidden order, the scales of the fp16 test before the table."""
+    g = torch.Generator().manual_seed(seed + sum(map(ord, row.name)))
+    D, M = row.D, row.M
+    t = storage(torch.randn(M, D, generator=g), dtype)
+    res = storage(torch.randn(M, D, generator=g) * 0.1, dtype)
+    w1 = storage(torch.randn(4 * D, D, generator=g) / D ** 0.5, dtype)
+    w2 = storage(torch.randn(D, 4 * D, generator=g) / (4 * D) ** 0.5, dtype)
+    b1, b2 = torch.randn(4 * D, generator=g) * 0.1, torch.randn(D, generator=g) * 0.1
+    return t, (res if row.res else None), w1, b1, w2, b2
+
+
+def mlp_row_reference(row: MlpRow, dtype, seed=0):
+    o = mlp_operands(row, dtype, seed)
+    return o, mlp_ref(*o, dtype)

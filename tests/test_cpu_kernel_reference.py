@@ -416,3 +416,180 @@ def test_dw_exact_operands_need_rounding_and_see_a_stale_tile():
             diff = _swap_first_tiles(want, row, dtype) != want
             n, _, y, x = (int(v) for v in diff.nonzero()[0])
             assert R.dw_tile_of(row, dtype, n, y, x) == (0, 0, 0, 0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The fused inference kernels (UPCONV_VARIANTS, NODE_VARIANTS, MLP_VARIANTS): the references against torch, the conditions on the inputs
+# (flip shares), and for every row that the correctly rounded reference passes its bound while each defective kernel fails it.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+FLIP_CAP = 0.2        # share of rounded intermediates that may be flagged as possible rounding flips (the cap of test_fp16_convnext_mlp_fused)
+UP_PARAMS = [(r, d) for r in R.UPCONV_VARIANTS for d in r.dtypes]
+NODE_PARAMS = [(r, d) for r in R.NODE_VARIANTS for d in r.dtypes]
+MLP_PARAMS = [(r, d) for r in R.MLP_VARIANTS for d in r.dtypes]
+_row_ids = lambda params: [f"{r.name}-{R.DNAME[d]}" for r, d in params]
+
+
+def test_fused_tables_cover_every_instantiation_and_path():
+    up = {(d, a) for r, d in UP_PARAMS for a in r.acts}
+    assert up == {(d, a) for d in R.DTYPES for a in (R.ACT_NONE, R.ACT_SILU)}                        # upconv_fused_kernel<T, ACT>
+    for d in R.DTYPES:
+        rows = [r for r, dd in UP_PARAMS if dd == d]
+        slab = 16 if d == F32 else 32
+        assert any(r.tiles == 1 and r.channels(d) == slab for r in rows), "one tile, one slab"
+        assert any((r.channels(d) // slab) % 2 == 1 and r.channels(d) > slab for r in rows), "an odd slab count above one"
+        assert any(r.W > 16 for r in rows) and any(r.H > 16 for r in rows), "tile seams"
+        assert any(r.K == 256 and set(r.acts) == {R.ACT_NONE, R.ACT_SILU} and r.exact for r in rows), "cbase = 128"
+        assert {3, 9} <= {r.tiles for r in rows}, "two fill levels of the XCD walk"
+        assert any(r.layout == "slice" and r.N > 1 for r in rows)
+    assert any(r.C == 256 and r.K == 256 for r in R.UPCONV_VARIANTS), "the model's channel counts"
+    assert {(d, r.C, r.kind) for r, d in NODE_PARAMS} == {(d, c, k) for d in R.NODE_DTYPES for c in (128, 256) for k in ("td", "out")}
+    for kind in ("td", "out"):
+        rows = [r for r in R.NODE_VARIANTS if r.kind == kind]
+        assert any(r.wdev for r in rows) and any(r.slice for r in rows) and {r.act for r in rows} >= {R.ACT_NONE, R.ACT_ELU}
+    N, H, W = R.NODE_SHAPE["td"]
+    assert (H * W) % 64 and N * H * W > 128 and H % 2 == 0 and W % 2 == 0, "workgroups that span two images"
+    N, H, W = R.NODE_SHAPE["out"]
+    assert (H * W) % 64 and N * H * W > 64 and H % 2 and W % 2, "an odd map"
+    inf = {(d, r.D, r.M, r.res) for r, d in MLP_PARAMS if not r.train}
+    assert inf >= {(d, D, M, True) for d in R.MLP_DTYPES for D in (96, 192, 384) for M in (1, 17, 33, 127, 129, 300)}
+    assert inf >= {(d, D, 129, False) for d in R.MLP_DTYPES for D in (96, 192, 384)}
+    assert {(d, r.D, r.M) for r, d in MLP_PARAMS if r.train} == {(BF16, D, M) for D in (96, 192) for M in (17, 129, 300)}
+
+
+@pytest.mark.parametrize("H,W", [(16, 16), (16, 32)])
+@pytest.mark.parametrize("act", [R.ACT_NONE, R.ACT_SILU])
+def test_upconv_ref_equals_convtranspose_then_conv3x3(H, W, act):
+    """upconv_ref (written from the header's formula) on model.compose_upconv's weights against fp64 conv_transpose2d -> conv2d -> affine -> act
+    of the uncomposed operands, every pixel: all nine border classes.  compose_upconv returns fp32: 2^-24 of the summed magnitudes."""
+    import torch.nn.functional as F
+    from multitask_bonetumor_yolo_amd.model import compose_upconv
+    g = torch.Generator().manual_seed(H + W + act)
+    N, C, K = 2, 8, 16
+    wt, bt = torch.randn(C, C, 2, 2, generator=g).double() * 0.3, torch.randn(C, generator=g).double() * 0.5
+    w3 = torch.randn(K, C, 3, 3, generator=g).double() * 0.2
+    sc, sh = torch.rand(K, generator=g).double() + 0.5, torch.randn(K, generator=g).double() * 0.2
+    x = torch.randn(N, C, H, W, generator=g).double()
+    pair = R.act64(F.conv2d(F.conv_transpose2d(x, wt, bt, stride=2), w3, padding=1) * sc.view(1, -1, 1, 1) + sh.view(1, -1, 1, 1), act)
+    wc, s9 = compose_upconv(wt, bt, w3, sc, sh)
+    assert all(not torch.equal(s9[i], s9[j]) for i in range(9) for j in range(i)), "nine different class vectors"
+    ref, _, mag = R.upconv_ref(x, wc.double().view(4, K, 2, 2, C), s9, act, F32)
+    tol = R.ACT_LIPSCHITZ[act] * 2.0 ** -24 * (mag + R.upconv_shift(s9, H, W).abs()) + 1e-13
+    assert bool(((ref - pair).abs() <= tol).all()), ((ref - pair).abs() / tol).max().item()
+    border = (ref - pair).abs()[:, :, [0, -1]].max().item(), (ref - pair).abs()[:, :, :, [0, -1]].max().item()
+    assert max(border) < 1e-6
+
+
+def test_node_resampling_equals_torch():
+    import torch.nn.functional as F
+    g = torch.Generator().manual_seed(4)
+    for shape in ((2, 3, 3, 5), (1, 2, 1, 1), (2, 2, 4, 2)):
+        x = torch.randn(*shape, generator=g).double()
+        assert torch.allclose(R.bilinear_up2(x), F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False), rtol=0, atol=1e-14)
+    x = torch.randn(2, 3, 10, 14, generator=g).double()
+    assert torch.allclose(R.mean2x2(x), F.avg_pool2d(x, 2), rtol=0, atol=1e-15)
+    a, b, c = torch.randn(2, 3, 5, 7, generator=g).double(), torch.randn(2, 3, 5, 7, generator=g).double(), x
+    s, mag = R.node_fused([a, b, c], (0.5, 0.25, 2.0), R.NODE_MODES["out"])
+    assert torch.allclose(s, 0.5 * a + 0.25 * b + 2.0 * F.avg_pool2d(c, 2), rtol=0, atol=1e-14) and bool((mag >= s.abs() - 1e-14).all())
+    assert R.f32_values([0.55])[0] != 0.55 and R.f32_values([0.5])[0] == 0.5                        # the weights are fp32 values
+
+
+def test_mlp_ref_without_hidden_rounding_is_the_plain_mlp():
+    import torch.nn.functional as F
+    t, res, w1, b1, w2, b2 = R.mlp_operands(R.MLP_ROWS["d96_m33"], BF16)
+    ref = R.mlp_ref(t, res, w1, b1, w2, b2, BF16, round_h=False)[0]
+    pre = t @ w1.t() + b1.double()
+    assert torch.allclose(ref, res + R.gelu_poly64(pre) @ w2.t() + b2.double(), rtol=0, atol=1e-13)
+    assert bool(((ref - (res + F.gelu(pre) @ w2.t() + b2.double())).abs() <= R.GELU_POLY_ERR * w2.abs().sum(1) + 1e-13).all())
+    nores = R.mlp_ref(t, None, w1, b1, w2, b2, BF16, round_h=False)[0]
+    assert torch.allclose(nores, ref - res, rtol=0, atol=1e-13)
+    for dt in (BF16, F16):                                                   # the spacing helpers on both 16-bit grids
+        v = torch.tensor([1.0, 1.5, 2.0, 0.0], dtype=torch.float64)
+        eps = 2.0 ** (-7 if dt == BF16 else -10)
+        assert R.spacing_below(v, dt).tolist()[:3] == [eps / 2, eps, eps] and R.spacing_above(v, dt).tolist()[:3] == [eps, eps, 2 * eps]
+        assert R.spacing_below(v, dt)[3].item() > 0
+
+
+@pytest.mark.parametrize("row,dtype", UP_PARAMS, ids=_row_ids(UP_PARAMS))
+def test_upconv_check_rejects_defective_kernels(row, dtype):
+    x, wc, s9 = R.up_operands(row, dtype)
+    acc, mag = R.upconv_sums(x, wc)
+    sh = R.upconv_shift(s9, row.H, row.W)
+    acc1 = R.upconv_sums(torch.roll(x, 1, dims=3 if row.W > 16 else 2), wc)[0] if row.tiles > row.N else None
+    for act in row.acts:
+        ref, bnd = R.upconv_bound(acc, mag, sh, act, dtype)
+        assert torch.equal(ref, R.upconv_ref(x, wc, s9, act, dtype)[0])
+        R.check(_rounded(ref, dtype), ref, bnd, "correctly rounded")
+        bad = lambda a, s: not R.within(_rounded(R.act64(a + s, act), dtype), ref, bnd)
+        m = sh.clone()
+        m[:, :, 0] = sh[:, :, 1]                                             # the interior row class on the first output row
+        assert bad(acc, m), "interior shift on a border row"
+        m = acc.clone()
+        m[..., 0::2], m[..., 1::2] = acc[..., 1::2], acc[..., 0::2]          # the two column parities swapped
+        assert bad(m, sh), "column parities swapped"
+        if acc1 is not None:                                                 # the second tile reads its source one pixel off
+            m = acc.clone()
+            if row.W > 16:
+                m[..., 32:] = acc1[..., 32:]
+            else:
+                m[..., 32:, :] = acc1[..., 32:, :]
+            assert bad(m, sh), "source shifted at a tile seam"
+        if row.K > 128:                                                      # channel tile 1 with the shifts of channel tile 0
+            m = sh.clone()
+            m[:, 128:256] = sh[:, 0:128]
+            assert bad(acc, m), "shift of channel tile 0 on channel tile 1"
+
+
+@pytest.mark.parametrize("row,dtype", [(r, d) for r, d in UP_PARAMS if r.exact], ids=_row_ids([(r, d) for r, d in UP_PARAMS if r.exact]))
+def test_upconv_exact_operands_need_rounding(row, dtype):
+    _, _, _, exact = R.up_exact_operands(row, dtype)
+    want = R.rounded_once(exact, dtype)
+    if dtype != F32:
+        assert (want != exact).float().mean().item() > 0.3
+    else:
+        assert torch.equal(want, exact)
+
+
+@pytest.mark.parametrize("row,dtype", NODE_PARAMS, ids=_row_ids(NODE_PARAMS))
+def test_node_check_rejects_defective_kernels(row, dtype):
+    (inputs, w, shift), (ref, bnd, flip) = R.node_row_reference(row, dtype)
+    assert flip.double().mean().item() <= FLIP_CAP, "a condition on the inputs"
+    R.check(_rounded(ref, dtype), ref, bnd, "correctly rounded")
+    wg = R.NODE_WGT[row.kind]
+    assert row.shape[0] >= 2, "a second image"
+    out = lambda s, mag: _rounded(R.node_output(s, mag, w, shift, row.act, dtype)[0], dtype)
+    s, mag = R.node_fused(inputs, wg, row.modes)
+    if row.kind == "td":                                                     # bilinear source rows clamped one row early
+        assert not R.within(out(*R.node_fused(inputs, wg, row.modes, clamp_early=1)), ref, bnd), "clamped early"
+    # the pixel index not reduced modulo H * W from the second image on: the row index runs past the map -- the bilinear rows clamp to the
+    # last source row, the 2 x 2 mean reads the next image
+    wrong = list(inputs)
+    wrong[-1] = inputs[-1][:, :, -1:, :].expand_as(inputs[-1]) if row.kind == "td" else torch.roll(inputs[-1], -1, dims=0)
+    s2 = s.clone()
+    s2[1:] = R.node_fused(wrong, wg, row.modes)[0][1:]
+    assert not R.within(out(s2, mag), ref, bnd), "pixel index not reduced"
+    if row.wdev:                                                             # wgt[] (other values) instead of wgt_dev
+        assert not R.within(out(*R.node_fused(inputs, R.NODE_WGT_OTHER[row.kind], row.modes)), ref, bnd), "wgt[] used"
+
+
+@pytest.mark.parametrize("row,dtype", MLP_PARAMS, ids=_row_ids(MLP_PARAMS))
+def test_mlp_check_rejects_defective_kernels(row, dtype):
+    (t, res, w1, b1, w2, b2), (ref, bnd, pre, pbnd, flip) = R.mlp_row_reference(row, dtype)
+    assert flip.double().mean().item() <= FLIP_CAP, "a condition on the inputs"
+    R.check(_rounded(ref, dtype), ref, bnd, "correctly rounded y")
+    R.check(_rounded(pre, dtype), pre, pbnd, "correctly rounded pre-activation")
+    D, M = row.D, row.M
+    if row.train:                                                            # one chunk of fc1 rows left in natural order under the staged permutation
+        rows = torch.arange(4 * D)
+        rows[:32] = R.mlp_train_rows(32)
+        y, _, p, _, _ = R.mlp_ref(t, res, w1[rows], b1[rows], w2, b2, dtype)
+        assert not R.within(_rounded(y, dtype), ref, bnd) and not R.within(_rounded(p, dtype), pre, pbnd), "chunk 0 left natural"
+    else:                                                                    # one chunk of fc2 columns left in natural order
+        cols = torch.arange(4 * D)
+        cols[:32] = R.mlp_hidden_order()
+        assert not R.within(_rounded(R.mlp_ref(t, res, w1, b1, w2[:, cols], b2, dtype)[0], dtype), ref, bnd), "chunk 0 left natural"
+    if res is not None:                                                      # the residual dropped for the last partial fragment
+        assert M % 16
+        y = ref.clone()
+        y[M - M % 16:] -= res[M - M % 16:]
+        assert not R.within(_rounded(y, dtype), ref, bnd), "residual dropped"
+    assert not R.within(_rounded(R.mlp_ref(t, res, w1, b1, w2, b2, dtype, round_h=False)[0], dtype), ref, bnd), "h not rounded"
