@@ -1144,6 +1144,65 @@ int mtbt_surface_distances(const mtbt_surface_args* a, void* stream);
 /* sizeof() of the struct above as the library was compiled: which = 0 mtbt_surface_args; -1 otherwise */
 int mtbt_sizeof_surface_args(int which);
 
+/* ---------------------------------------------------------------------------------------------
+ * Connected components of bit-packed planes (csrc/components.hip; `postprocess.label_components`, `filter_components`,
+ * `metrics.LesionMetrics`).  Packed layout and alignment as in the two sections above (planes 8-byte aligned, 8-byte accesses only);
+ * bits X >= W never count, whatever they hold.
+ * mtbt_label_components: two set pixels belong together when a path of set pixels joins them, a step going to one of the 4
+ * (connectivity 4) or 8 (connectivity 8) neighbours.  The components of a plane are numbered 1 .. n_components in row-major order of
+ * their FIRST pixel, the one with the smallest flat index y * W + x (the numbering of scipy.ndimage.label); 0 is background.
+ *   packed        [n][H][pitch]
+ *   other         [n][H][pitch] a second stack, or NULL (then inter is NULL too)
+ *   labels        int32  [n][H][W] the label map; NULL: not written (the workspace still holds it for mtbt_select_components)
+ *   n_components  int32  [n]       the true count, never capped
+ *   area          uint32 [n][C]    pixels of id i at [i - 1], for i <= min(n_components, C), C = max_components in [1, 65536]
+ *   box           int32  [n][C][4] x1, y1, x2, y2 with exclusive maxima: x1 <= X < x2 (the crop rule of mtbt_pack_masks)
+ *   first         int32  [n][C]    flat index of the first pixel
+ *   inter         uint32 [n][C]    popcount(component & other's plane)
+ * The rows of the four tables beyond n_components are zero.  Every output word is defined after the call: the caller does not pre-zero.
+ * The result is a pure function of the input (union by minimum index: the root of a component is its first pixel; integer atomics only).
+ * mtbt_select_components: `packed` and `workspace` as given to (and left by) the LAST mtbt_label_components call with the same n, H, W.
+ * A component is kept when area >= min_area and, with keep_largest = k > 0, it is among the k largest of its plane by area, ties going
+ * to the lower id; exact for every component, also ids above max_components (the workspace holds the area of every id).
+ *   out     [n][H][pitch] the kept components; every byte is written, padding bits zero
+ *   n_kept  int32 [n]
+ * Both: asynchronous on `stream`, no host synchronisation, no workgroup waits on another, graph-capturable.  `workspace`:
+ * >= mtbt_components_workspace_bytes(n, H, W) bytes, 16-byte aligned (about 6 bytes per pixel; the query returns MTBT_EINVAL for a shape
+ * refused below).  MTBT_EINVAL before any launch: NULL args or a NULL pointer member (labels may be NULL; other and inter only together;
+ * workspace only when the query is 0), n < 0, H or W outside [1, 16384], H * W >= 2^31, pitch != 8 * ceil(W / 64), a connectivity other
+ * than 4 or 8, max_components outside [1, 65536], keep_largest < 0, workspace_bytes below the query.  MTBT_EALIGN: packed / other / out
+ * not 8-byte, workspace not 16-byte, the other pointers not 4-byte aligned.  n == 0 launches nothing. */
+typedef struct mtbt_components_args {
+  const uint8_t* packed;   /* [n][H][pitch] */
+  const uint8_t* other;    /* [n][H][pitch] or NULL */
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t* labels;         /* [n][H][W] or NULL */
+  int32_t* n_components;   /* [n] */
+  uint32_t* area;          /* [n][C] */
+  int32_t* box;            /* [n][C][4] */
+  int32_t* first;          /* [n][C] */
+  uint32_t* inter;         /* [n][C] or NULL */
+  int32_t n, H, W, pitch;
+  int32_t connectivity;    /* 4 or 8 */
+  int32_t max_components;  /* C */
+} mtbt_components_args;
+typedef struct mtbt_select_components_args {
+  const uint8_t* packed;   /* [n][H][pitch] */
+  void* workspace;
+  int64_t workspace_bytes;
+  uint8_t* out;            /* [n][H][pitch] */
+  int32_t* n_kept;         /* [n] */
+  int32_t n, H, W, pitch;
+  uint32_t min_area;
+  int32_t keep_largest;    /* 0: no limit */
+} mtbt_select_components_args;
+int64_t mtbt_components_workspace_bytes(int n, int H, int W);
+int mtbt_label_components(const mtbt_components_args* a, void* stream);
+int mtbt_select_components(const mtbt_select_components_args* a, void* stream);
+/* sizeof() of the structs above as the library was compiled: which = 0 mtbt_components_args, 1 mtbt_select_components_args; -1 otherwise */
+int mtbt_sizeof_components_args(int which);
+
 /* Weight gradient of a k x k convolution (any stride / padding; 1x1 and the 2x2 stride-2 downsample included), bf16 (MFMA) or fp32 operands:
  *   dw[k][r][s][c] (fp32, packed [K][R*S*C] like the forward weight) (+)= sum_p dy[p][k] * x[n][y*stride + r - pad][x*stride + s - pad][c]
  * x [N,H,W,C], dy [N,Ho,Wo,K] (Ho = (H + 2 pad - R) / stride + 1) NHWC with pixel / batch strides in elements (multiples of 8; C % 8 == K % 8 == 0;

@@ -16,6 +16,7 @@
     from multitask_bonetumor_yolo_amd import vote_masks                  # instance masks of a fused list, voted over each cluster's members
     from multitask_bonetumor_yolo_amd import detect_sliced               # sliced inference: tiles of a large image, merged and voted on the device
     from multitask_bonetumor_yolo_amd import SurfaceDistanceMetrics      # Hausdorff / HD95 / ASSD / surface Dice from packed masks, on the device
+    from multitask_bonetumor_yolo_amd import label_components, LesionMetrics   # connected components of packed masks; lesion-wise recall / precision
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
@@ -27,11 +28,11 @@ from .loss import InstanceMaskLoss, TaskAlignedDetLoss, TaskAlignedSegLoss, inst
 from .checkpoints import load_pretrained_heads, load_train_state, save_train_state, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision,  # noqa: F401
-                      ImageClassificationMetrics, MeanAveragePrecision, SegmentationMetrics, SurfaceDistanceMetrics, surface_distances,
-                      surface_metrics)
+                      ImageClassificationMetrics, LesionMetrics, MeanAveragePrecision, SegmentationMetrics, SurfaceDistanceMetrics,
+                      lesion_hits, surface_distances, surface_metrics)
 from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
-from .postprocess import merge_tiles, vote_masks, vote_tile_masks  # noqa: F401
+from .postprocess import components_to_instances, filter_components, label_components, merge_tiles, vote_masks, vote_tile_masks  # noqa: F401
 from .sliced import detect_sliced  # noqa: F401
 from .trainstep import TrainStep, ema_decay_at  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

@@ -221,6 +221,19 @@ class SurfaceArgs(C.Structure):  # mtbt_surface_args
                 ("tol2", C.c_uint32), ("Q", C.c_int32)]
 
 
+class ComponentsArgs(C.Structure):  # mtbt_components_args
+    _fields_ = [("packed", C.c_void_p), ("other", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("labels", C.c_void_p), ("n_components", C.c_void_p), ("area", C.c_void_p), ("box", C.c_void_p), ("first", C.c_void_p),
+                ("inter", C.c_void_p), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32),
+                ("connectivity", C.c_int32), ("max_components", C.c_int32)]
+
+
+class SelectComponentsArgs(C.Structure):  # mtbt_select_components_args
+    _fields_ = [("packed", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("out", C.c_void_p),
+                ("n_kept", C.c_void_p), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32),
+                ("min_area", C.c_uint32), ("keep_largest", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -353,6 +366,10 @@ SYMBOLS = {
     "mtbt_surface_distances_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mtbt_surface_distances": (C.c_int, [C.POINTER(SurfaceArgs), C.c_void_p]),
     "mtbt_sizeof_surface_args": (C.c_int, [C.c_int]),
+    "mtbt_components_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mtbt_label_components": (C.c_int, [C.POINTER(ComponentsArgs), C.c_void_p]),
+    "mtbt_select_components": (C.c_int, [C.POINTER(SelectComponentsArgs), C.c_void_p]),
+    "mtbt_sizeof_components_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -360,6 +377,7 @@ FRAME_STRUCTS = (Frame, FrameMaskArgs)   # order of mtbt_sizeof_frame_args(which
 MASK_EVAL_STRUCTS = (PackMasksArgs, MaskImage, MaskPairArgs, MaskEvalArgs)   # order of mtbt_sizeof_mask_eval_args(which)
 TILE_STRUCTS = (Tile, TileMergeArgs, TileMaskArgs)   # order of mtbt_sizeof_tile_args(which)
 SURFACE_STRUCTS = (SurfaceArgs,)   # order of mtbt_sizeof_surface_args(which)
+COMPONENTS_STRUCTS = (ComponentsArgs, SelectComponentsArgs)   # order of mtbt_sizeof_components_args(which)
 _lib = None
 
 
@@ -382,7 +400,8 @@ def load():
                 raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {lib.mtbt_sizeof_args(which)}, this binding lays it out in "
                                    f"{C.sizeof(st)} bytes: stale library, rebuild")
         for sizeof, structs in ((lib.mtbt_sizeof_frame_args, FRAME_STRUCTS), (lib.mtbt_sizeof_mask_eval_args, MASK_EVAL_STRUCTS),
-                                (lib.mtbt_sizeof_tile_args, TILE_STRUCTS), (lib.mtbt_sizeof_surface_args, SURFACE_STRUCTS)):
+                                (lib.mtbt_sizeof_tile_args, TILE_STRUCTS), (lib.mtbt_sizeof_surface_args, SURFACE_STRUCTS),
+                                (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

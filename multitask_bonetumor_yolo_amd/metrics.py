@@ -28,6 +28,9 @@ torchmetrics' binary stat-score definitions.
   SurfaceDistanceMetrics  boundary metrics of binary segmentation -- Hausdorff distance, HD95, average symmetric surface distance, normalised
                           surface Dice (MedPy's definitions; nothing in the reference computes them) -- from device-side records of
                           bit-packed masks (`mtbt_surface_distances`: edge sets, exact integer squared distances, order statistics).
+  LesionMetrics           lesion-wise detection from the semantic mask -- ground-truth components found, predicted components that are
+                          true, false-positive components per image (nothing in the reference computes them) -- from device-side
+                          connected-component records of bit-packed masks (`mtbt_label_components`: areas and overlaps per component).
 
 The two box classes and the segmentation mAP differ only in how they match; all three accumulate and summarise (pycocotools
 `accumulate` / `summarize`) through one vectorised numpy function, `_accumulate`, once per epoch.
@@ -1104,3 +1107,95 @@ class SurfaceDistanceMetrics:
             out[k] = float(v.mean()) if v.size else -1.0
         out["n_pairs"], out["n_undefined"] = int(len(per["defined"])), int(np.count_nonzero(~per["defined"]))
         return out
+
+
+# ---- lesion-wise detection from the semantic mask ------------------------------------------------------------------------------------
+def lesion_hits(n_components, area, inter, overlap: float = 0.0):
+    """Which components of `label_components(..., other=)` records are hit by the other side; pure host code.
+
+    n_components [n], area and inter [n, C] (id i in row i - 1).  A component is hit when inter >= 1 and inter >= overlap * area, the
+    product being one float64 multiplication.  Returns (hits int64 [n], truncated bool [n]): a plane with more than C components is
+    truncated, and its components beyond the table count as not hit."""
+    n_comp = np.asarray(n_components, np.int64).reshape(-1)
+    area, inter = np.asarray(area, np.int64), np.asarray(inter, np.int64)
+    n, C_ = len(n_comp), area.shape[1] if area.ndim == 2 else 0
+    area, inter = area.reshape(n, C_), inter.reshape(n, C_)
+    listed = np.arange(C_)[None, :] < np.minimum(n_comp, C_)[:, None]
+    hit = listed & (inter >= 1) & (inter.astype(np.float64) >= np.float64(overlap) * area.astype(np.float64))
+    return hit.sum(axis=1).astype(np.int64), n_comp > C_
+
+
+class LesionMetrics:
+    """Lesion-wise detection of binary segmentation: the connected components of the ground truth that the prediction finds and the
+    components of the prediction that are true, from device-side records (`postprocess.label_components` with `other=`).
+
+    A ground-truth component is FOUND when the prediction covers at least one of its pixels and at least `overlap` of its area
+    (`lesion_hits`); a predicted component is TRUE by the same test against the ground truth.  With `min_area` > 0 predicted components
+    below it are removed first (`filter_components`); the ground truth is never filtered.
+    `update(seg_logits, masks_gt)`: [B,1,S,S] or [B,S,S] device tensors, prediction bit = logit > 0, target bit = masks_gt >= 1 (the
+    rule of `SurfaceDistanceMetrics.update`).  `update_packed(pred, gt, W)`: packed uint8 [n, H, pitch] stacks.  Two labelling calls
+    per batch; the records stay on the device until `compute()`.
+    `compute()` -> lesion_recall = found / ground-truth components, lesion_precision = true / predicted components (pooled over the
+    data set, each 0 when its denominator is 0), lesion_f1, fp_per_image (false predicted components per image), n_gt, n_pred,
+    n_images, and n_truncated: the images with more than `max_components` components on a side, whose excess components count as not
+    found / false.  With a live process group (and `dist_sync`): over ALL ranks -- a collective, every rank must call it."""
+
+    def __init__(self, overlap: float = 0.0, min_area: int = 0, connectivity: int = 4, max_components: int = 1024,
+                 dist_sync: bool = True, process_group=None):
+        if not 0.0 <= float(overlap) <= 1.0:
+            raise ValueError(f"LesionMetrics: overlap {overlap!r} is not in [0, 1]")
+        if int(min_area) < 0 or int(min_area) != min_area:
+            raise ValueError(f"LesionMetrics: min_area {min_area!r} is not an integer >= 0")
+        if connectivity not in (4, 8):
+            raise ValueError(f"LesionMetrics: connectivity 4 or 8, not {connectivity!r}")
+        if not 1 <= int(max_components) <= 65536:
+            raise ValueError(f"LesionMetrics: max_components {max_components!r} is outside [1, 65536]")
+        self.overlap, self.min_area, self.connectivity, self.max_components = float(overlap), int(min_area), int(connectivity), int(max_components)
+        self.dist_sync, self.group = dist_sync, process_group
+        self.reset()
+
+    def reset(self):
+        self._records: List[Dict[str, torch.Tensor]] = []
+
+    def update_packed(self, pred: torch.Tensor, gt: torch.Tensor, W: int):
+        """Asynchronous: launches on the current stream and keeps its records on the device."""
+        from .postprocess import filter_components, label_components
+        kw = dict(connectivity=self.connectivity, max_components=self.max_components, want_labels=False)
+        if self.min_area > 0:
+            pred =filter_components(pred, W, min_area=self.min_area, connectivity=self.connectivity)[0]
+        p, g = label_components(pred, W, other=gt, **kw), label_components(gt, W, other=pred, **kw)
+        if p["n_components"].shape[0]:
+            self._records.append({f"{s}_{k}": r[k] for s, r in (("pred", p), ("gt", g)) for k in ("n_components", "area", "inter")})
+
+    def update(self, seg_logits: torch.Tensor, masks_gt: torch.Tensor):
+        from .postprocess import pack_masks
+        if not (isinstance(seg_logits, torch.Tensor) and isinstance(masks_gt, torch.Tensor) and seg_logits.is_cuda and masks_gt.is_cuda):
+            raise RuntimeError("LesionMetrics.update: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+        if seg_logits.shape != masks_gt.shape:
+            raise ValueError("LesionMetrics.update: logits and masks differ in shape")
+        if seg_logits.dim() == 4 and seg_logits.shape[1] == 1:
+            seg_logits, masks_gt = seg_logits[:, 0], masks_gt[:, 0]
+        if seg_logits.dim() != 3:
+            raise ValueError("LesionMetrics.update: logits and masks must be [B,1,S,S] or [B,S,S]")
+        if seg_logits.shape[0] == 0:
+            return
+        self.update_packed(pack_masks(seg_logits.float()), pack_masks(masks_gt >= 1), seg_logits.shape[2])
+
+    def counts(self, sync: bool = False) -> np.ndarray:
+        """int64 [6]: ground-truth components, found ones, predicted components, true ones, images, truncated images."""
+        tot = np.zeros(6, np.int64)
+        for rec in self._records:
+            h = {k: v.cpu().numpy() for k, v in rec.items()}
+            found, cut_g = lesion_hits(h["gt_n_components"], h["gt_area"], h["gt_inter"], self.overlap)
+            true, cut_p = lesion_hits(h["pred_n_components"], h["pred_area"], h["pred_inter"], self.overlap)
+            tot += np.array([h["gt_n_components"].sum(), found.sum(), h["pred_n_components"].sum(), true.sum(), len(found),
+                             np.count_nonzero(cut_g | cut_p)], np.int64)
+        return _sum_over_ranks(tot, self.group) if sync else tot
+
+    def compute(self) -> Dict[str, float]:
+        n_gt, n_found, n_pred, n_true, n_images, n_cut = (int(v) for v in self.counts(sync=self.dist_sync))
+        rec = n_found / n_gt if n_gt else 0.0
+        prec = n_true / n_pred if n_pred else 0.0
+        return {"lesion_recall": rec, "lesion_precision": prec, "lesion_f1": 2 * prec * rec / (prec + rec) if prec + rec > 0 else 0.0,
+                "fp_per_image": (n_pred - n_true) / n_images if n_images else 0.0, "n_gt": n_gt, "n_pred": n_pred, "n_images": n_images,
+                "n_truncated": n_cut}

@@ -699,3 +699,125 @@ def vote_tile_masks(merged: dict, det: dict, mc: torch.Tensor, protos: torch.Ten
             L.check(lib.mtbt_vote_tile_masks(C.byref(a), fr, nb, _stream(dev)), "mtbt_vote_tile_masks")
     views = [out[off:off + top_k * H0 * pitch].view(top_k, H0, pitch) for H0, W0, pitch, off in rows]
     return {"boxes": boxes, "masks": views, "buffer": out, "vote_coeff": W, "vote_weight": Ss, "_keep": (table, first, table_dev, pr, mc, scores, anchors)}
+
+
+# ---- connected components of packed planes ----------------------------------------------------------------------------------------
+COMPONENTS_MAX_DIM = 16384       # H and W of mtbt_label_components
+COMPONENTS_MAX_TABLE = 65536     # max_components
+
+
+def _component_planes(what: str, packed: torch.Tensor, W: int, other: Optional[torch.Tensor] = None):
+    """The checks both component operators share -> (n, H, pitch, planes made contiguous and 8-byte aligned)."""
+    for t in (packed,) + (() if other is None else (other,)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"{what}: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+    if packed.dim() != 3 or packed.dtype != torch.uint8:
+        raise ValueError(f"{what}: packed must be uint8 [n, H, pitch]")
+    if other is not None and (other.dtype != torch.uint8 or other.shape != packed.shape or other.device != packed.device):
+        raise ValueError(f"{what}: other must be uint8 of packed's shape {tuple(packed.shape)}, on its device")
+    n, H, pitch = (int(v) for v in packed.shape)
+    if not (1 <= H <= COMPONENTS_MAX_DIM and 1 <= W <= COMPONENTS_MAX_DIM):
+        raise ValueError(f"{what}: planes of {H} x {W} pixels (1 <= H, W <= {COMPONENTS_MAX_DIM})")
+    if pitch != 8 * ((W + 63) // 64):
+        raise ValueError(f"{what}: packed planes of width {W} are uint8 [n, H, {8 * ((W + 63) // 64)}]")
+    planes = []
+    for t in (packed, other):
+        if t is not None:
+            t = t.contiguous()
+            t = t if t.data_ptr() % 8 == 0 else t.clone()
+        planes.append(t)
+    return n, H, pitch, planes[0], planes[1]
+
+
+def label_components(packed: torch.Tensor, W: int, *, connectivity: int = 4, max_components: int = 1024,
+                     other: Optional[torch.Tensor] = None, want_labels: bool = True):
+    """Connected components of n bit-packed planes, on the device (`mtbt_label_components`; definitions in include/mtbt_hip.h).
+
+    packed: uint8 [n, H, pitch] with pitch = 8 * ceil(W / 64) (`pack_masks`, `masks_to_frames`); bits X >= W never count.
+    `connectivity` 4 or 8.  The components of a plane are numbered 1 .. n_components in row-major order of their first pixel (the
+    numbering of `scipy.ndimage.label`); 0 is background.  Returns a dict of device tensors: `labels` int32 [n, H, W] (None with
+    want_labels=False), `n_components` int32 [n] (the true count), and for the ids 1 .. min(n_components, max_components), id i in
+    row i - 1, `area` int32 [n, C], `boxes` float32 [n, C, 4] xyxy with exclusive maxima (usable as `pack_masks(boxes=)`), `first`
+    int32 [n, C] (flat index of the first pixel) and, with a second stack `other` of the same shape, `inter` int32 [n, C] =
+    popcount(component & other's plane) (None without).  Rows beyond n_components are zero.  `shape` = (H, W).  Asynchronous: no
+    host synchronisation; the result is a pure function of the input."""
+    W, connectivity, C_ = int(W), int(connectivity), int(max_components)
+    n, H, pitch, planes, oth = _component_planes("label_components", packed, W, other)
+    if connectivity not in (4, 8):
+        raise ValueError(f"label_components: connectivity 4 or 8, not {connectivity}")
+    if not 1 <= C_ <= COMPONENTS_MAX_TABLE:
+        raise ValueError(f"label_components: max_components {C_} is outside [1, {COMPONENTS_MAX_TABLE}]")
+    dev = packed.device
+    out = {"labels": torch.empty((n, H, W), dtype=torch.int32, device=dev) if want_labels else None,
+           "n_components": torch.empty((n,), dtype=torch.int32, device=dev), "area": torch.empty((n, C_), dtype=torch.int32, device=dev),
+           "first": torch.empty((n, C_), dtype=torch.int32, device=dev),
+           "inter": torch.empty((n, C_), dtype=torch.int32, device=dev) if oth is not None else None, "shape": (H, W)}
+    box = torch.empty((n, C_, 4), dtype=torch.int32, device=dev)
+    if n == 0:
+        out["boxes"] = box.float()
+        return out
+    lib = L.load()
+    ws_bytes = int(lib.mtbt_components_workspace_bytes(n, H, W))
+    if ws_bytes < 0:
+        L.check(ws_bytes, "mtbt_components_workspace_bytes")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    a = L.ComponentsArgs()
+    a.packed, a.other, a.workspace, a.workspace_bytes = planes.data_ptr(), oth.data_ptr() if oth is not None else None, ws.data_ptr(), ws_bytes
+    a.labels = out["labels"].data_ptr() if want_labels else None
+    a.n_components, a.area, a.box, a.first = out["n_components"].data_ptr(), out["area"].data_ptr(), box.data_ptr(), out["first"].data_ptr()
+    a.inter = out["inter"].data_ptr() if oth is not None else None
+    a.n, a.H, a.W, a.pitch, a.connectivity, a.max_components = n, H, W, pitch, connectivity, C_
+    with torch.cuda.device(dev):
+        L.check(lib.mtbt_label_components(C.byref(a), _stream(dev)), "mtbt_label_components")
+    out["boxes"] = box.float()
+    out["_keep"] = (planes, ws, ws_bytes)                     # what `mtbt_select_components` continues from
+    return out
+
+
+def filter_components(packed: torch.Tensor, W: int, *, min_area: int = 0, keep_largest: Optional[int] = None, connectivity: int = 4):
+    """Remove components of n bit-packed planes, on the device (`mtbt_label_components` then `mtbt_select_components`).
+
+    A component stays when its area is at least `min_area` and, with `keep_largest` = k > 0, it is among the k largest of its plane
+    (equal areas: the lower id, i.e. the earlier first pixel); exact however many components a plane has.  Returns (packed uint8
+    [n, H, pitch] with zero padding bits, n_kept int32 [n]).  Asynchronous."""
+    W, min_area, k = int(W), int(min_area), int(keep_largest or 0)
+    if not 0 <= min_area < 2 ** 32 or not 0 <= k < 2 ** 31:
+        raise ValueError("filter_components: min_area and keep_largest must be >= 0 (and fit 32 bits)")
+    rec = label_components(packed, W, connectivity=connectivity, max_components=1, want_labels=False)
+    n, H, pitch = (int(v) for v in packed.shape)
+    dev = packed.device
+    out = torch.empty((n, H, pitch), dtype=torch.uint8, device=dev)
+    n_kept = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return out, n_kept
+    planes, ws, ws_bytes = rec["_keep"]
+    a = L.SelectComponentsArgs()
+    a.packed, a.workspace, a.workspace_bytes, a.out, a.n_kept = planes.data_ptr(), ws.data_ptr(), ws_bytes, out.data_ptr(), n_kept.data_ptr()
+    a.n, a.H, a.W, a.pitch, a.min_area, a.keep_largest = n, H, W, pitch, min_area, k
+    with torch.cuda.device(dev):
+        L.check(L.load().mtbt_select_components(C.byref(a), _stream(dev)), "mtbt_select_components")
+    return out, n_kept
+
+
+def components_to_instances(packed: torch.Tensor, W: int, *, max_instances: int = 100, min_area: int = 0, connectivity: int = 4):
+    """The largest components of each of n bit-packed planes as instance planes: a semantic mask in the layout the instance consumers
+    read (`det["masks_frame"][b]`, `DeviceMaskMeanAveragePrecision`, `SurfaceDistanceMetrics.update_packed`).
+
+    Per plane the up to K = `max_instances` largest components of at least `min_area` pixels, largest first (equal areas: the earlier
+    first pixel).  Returns a dict: `masks` uint8 [n, K, H, pitch] (masks[b] is [K, H, pitch]; the slots from counts[b] on are zero),
+    `boxes` float32 [n, K, 4] xyxy, `areas` int32 [n, K], `counts` int32 [n].  `filter_components`, `label_components` and
+    `pack_masks` with torch indexing between them; no host synchronisation."""
+    K = int(max_instances)
+    if not 1 <= K <= COMPONENTS_MAX_TABLE:
+        raise ValueError(f"components_to_instances: max_instances {K} is outside [1, {COMPONENTS_MAX_TABLE}]")
+    kept, counts = filter_components(packed, W, min_area=min_area, keep_largest=K, connectivity=connectivity)
+    rec = label_components(kept, W, connectivity=connectivity, max_components=K)      # at most K components are left: the tables hold all
+    n, H, pitch = (int(v) for v in kept.shape)
+    areas, order = torch.sort(rec["area"], dim=1, descending=True, stable=True)
+    slot = torch.arange(K, device=kept.device)[None, :]
+    ids = torch.where(slot < counts[:, None], order + 1, -1).to(torch.int32)            # -1: no pixel carries it
+    boxes = torch.gather(rec["boxes"], 1, order[:, :, None].expand(n, K, 4))
+    masks = torch.empty((n, K, H, pitch), dtype=torch.uint8, device=kept.device)
+    for b in range(n):
+        pack_masks(rec["labels"][b][None] == ids[b][:, None, None], out=masks[b])
+    return {"masks": masks, "boxes": boxes, "areas": areas, "counts": counts}

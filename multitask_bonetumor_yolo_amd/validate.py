@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .loss import instance_mask_loss, multitask_loss, task_aligned_det_loss
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision, ImageClassificationMetrics,
-                      SegmentationMetrics, SurfaceDistanceMetrics, _sum_over_ranks)
+                      LesionMetrics, SegmentationMetrics, SurfaceDistanceMetrics, _sum_over_ranks)
 from .postprocess import (CONF_TH, NMS_IOU, TOP_K, decode_boxes, fuse_detections, masks_to_frames, nms_batched, orient_batch, pack_masks,
                           proto_projector_logits, vote_masks)
 
@@ -60,7 +60,7 @@ class ValidationStep:
                  top_k: int = TOP_K, map_max_detections: int = 100, dist_sync: bool = True, process_group=None,
                  instance_masks: bool = False, mask_crop: bool = True, det_loss: str = "reference", tal=None,
                  instance_mask_weight: float = 0.0, mask_assign: str = "iou", views: Optional[Sequence[int]] = None, wbf_iou: float = 0.55,
-                 fused_masks: Optional[str] = None, surface=None):
+                 fused_masks: Optional[str] = None, surface=None, lesions=None):
         """`projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1), running_main_v3.py:186); created with torch's default
         init when not given.  The loss hyper-parameters default to the reference's (and TrainStep's); `label_smoothing` is accepted for
         symmetry with TrainStep but the eval-mode loss never smooths (:337).  conf_th / nms_iou / top_k: `:54-56`;
@@ -86,8 +86,12 @@ class ValidationStep:
         `surface` (True, or a dict of `SurfaceDistanceMetrics`' options quantile / tolerance / spacing / percentile_mode / undefined):
         also the boundary metrics of the semantic mask -- one `SurfaceDistanceMetrics.update` on the projector logits `self.seg` sees;
         `compute()` gains seg_hd_epoch, seg_hd95_epoch, seg_assd_epoch, seg_nsd_epoch and seg_surface_undefined.  None: not one
-        launch and not one key changes."""
+        launch and not one key changes.
+        `lesions` (True, or a dict of `LesionMetrics`' options overlap / min_area / connectivity / max_components): also lesion-wise
+        detection from the semantic mask -- one `LesionMetrics.update` on the same logits; `compute()` gains seg_lesion_recall,
+        seg_lesion_precision, seg_lesion_f1 and seg_lesion_fp_per_image.  None: not one launch and not one key changes."""
         self.surface_kw = self._surface_options(surface)
+        self.lesion_kw = self._lesion_options(lesions)
         self.views = None if views is None else tuple(int(v) for v in views)
         self.wbf_iou = float(wbf_iou)
         if fused_masks not in (None, "vote"):
@@ -145,6 +149,7 @@ class ValidationStep:
         self.mask_map50 = DeviceMaskMeanAveragePrecision([0.5], max_dets, **sync) if self.instance_masks else None
         self.mask_map50_95 = DeviceMaskMeanAveragePrecision(None, max_dets, **sync) if self.instance_masks else None
         self.surface = SurfaceDistanceMetrics(**self.surface_kw, **sync) if self.surface_kw is not None else None
+        self.lesions = LesionMetrics(**self.lesion_kw, **sync) if self.lesion_kw is not None else None
 
     @staticmethod
     def _surface_options(surface):
@@ -159,8 +164,22 @@ class ValidationStep:
         SurfaceDistanceMetrics(**surface)          # its own checks of the values; needs no device
         return dict(surface)
 
+    @staticmethod
+    def _lesion_options(lesions):
+        """`lesions=` of the constructor -> None (off) or the keyword arguments of `LesionMetrics`."""
+        if lesions is None or lesions is False:
+            return None
+        if lesions is True:
+            return {}
+        allowed = ("overlap", "min_area", "connectivity", "max_components")
+        if not isinstance(lesions, dict) or set(lesions) - set(allowed):
+            raise ValueError(f"lesions: None, True or a dict with keys among {allowed}, not {lesions!r}")
+        LesionMetrics(**lesions)                   # its own checks of the values; needs no device
+        return dict(lesions)
+
     def reset(self):
-        for m in (self.losses, self.seg, self.img, self.det_cm, self.map50, self.map50_95, self.mask_map50, self.mask_map50_95, self.surface):
+        for m in (self.losses, self.seg, self.img, self.det_cm, self.map50, self.map50_95, self.mask_map50, self.mask_map50_95, self.surface,
+                  self.lesions):
             if m is not None:
                 m.reset()
 
@@ -207,6 +226,8 @@ class ValidationStep:
         self.seg.update(seg_logits, masks_gt)
         if self.surface is not None:
             self.surface.update(seg_logits, masks_gt)
+        if self.lesions is not None:
+            self.lesions.update(seg_logits, masks_gt)
         self.img.update(logits, cls_gt)
         self.det_cm.update(det, det_gt)
         d = decode_boxes(det, self.S, reg_max=self.reg_max, want_scores=False)
@@ -294,4 +315,9 @@ class ValidationStep:
             for k in ("hd", "hd95", "assd", "nsd"):
                 out[f"val_epoch/seg_{k}_epoch"] = sd[k]
             out["val_epoch/seg_surface_undefined"] = sd["n_undefined"]
+        if self.lesions is not None:
+            lm = self.lesions.compute()
+            for k in ("recall", "precision", "f1"):
+                out[f"val_epoch/seg_lesion_{k}"] = lm[f"lesion_{k}"]
+            out["val_epoch/seg_lesion_fp_per_image"] = lm["fp_per_image"]
         return out
