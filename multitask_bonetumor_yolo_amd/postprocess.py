@@ -34,6 +34,15 @@ def _nhwc_rows(t: torch.Tensor):
     return t, t.stride(3)
 
 
+def _proto_rows(protos: torch.Tensor) -> torch.Tensor:
+    """[N,nm,hp,wp] prototypes -> the fp32 tensor the mask kernels read: dense NHWC rows, a pixel's nm channels side by side
+    (`_nhwc_rows`, and one more copy when the channels-last tensor is a view with a wider pixel stride)."""
+    pr, ld = _nhwc_rows(protos)
+    if ld != protos.shape[1]:
+        pr = pr.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+    return pr
+
+
 def decode_boxes(det_maps: Sequence[torch.Tensor], img_size: Optional[float] = None, reg_max: int = 16, xywh: bool = False,
                  strides: Optional[Sequence[float]] = None, preds_cat: Optional[torch.Tensor] = None, want_scores: bool = True):
     """Decode raw Detect maps (per level [B, 4*reg_max+nc, h, w]).
@@ -138,10 +147,8 @@ def nms_batched(boxes: torch.Tensor, best_score: torch.Tensor, best_label: Optio
 def _mask_call(protos, coeff, cbs, cks, ccs, gather, counts, bias, K, out_hw, want_logits, want_masks):
     lib = L.load()
     _need_cuda(protos, "mask assembly")
-    pr, ld = _nhwc_rows(protos)
+    pr = _proto_rows(protos)
     B, nm, hp, wp = protos.shape
-    if ld != nm:
-        pr = pr.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
     dev = protos.device
     H, W = out_hw
     a = L.MaskArgs()
@@ -205,6 +212,32 @@ def _frame_layout(frames, K: int, up: float):
     return rows, total
 
 
+class _PackedFrames:
+    """The packed buffer of one call of a frame operator `who` (K planes per image): its layout (`_frame_layout`), the checked or new
+    `out`, the launches of at most MAX_FRAMES images with their `mtbt_frame` arrays, and the views that are returned."""
+
+    def __init__(self, who: str, frames, K: int, up: float, out: Optional[torch.Tensor], dev):
+        self.K = K
+        self.rows, total = _frame_layout(frames, K, up)
+        if out is None:
+            out = torch.empty((total,), dtype=torch.uint8, device=dev)
+        elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total or out.device != dev:
+            raise ValueError(f"{who}: out must be a contiguous flat uint8 buffer of at least {total} bytes on {dev}")
+        self.out = out
+
+    def chunks(self):
+        """(c0, nb, `mtbt_frame` array) of every launch: images c0 .. c0 + nb - 1."""
+        for c0 in range(0, len(self.rows), MAX_FRAMES):
+            rows = self.rows[c0:c0 + MAX_FRAMES]
+            fr = (L.Frame * len(rows))()
+            for i, (H0, W0, step, scale, pitch, off) in enumerate(rows):
+                fr[i].height, fr[i].width, fr[i].step, fr[i].scale, fr[i].pitch, fr[i].offset = H0, W0, step, scale, pitch, off
+            yield c0, len(rows), fr
+
+    def views(self):
+        return [self.out[off:off + self.K * H0 * pitch].view(self.K, H0, pitch) for H0, W0, step, scale, pitch, off in self.rows]
+
+
 def masks_to_frames(protos: torch.Tensor, mc: torch.Tensor, keep_anchor: torch.Tensor, counts: Optional[torch.Tensor],
                     boxes: Optional[torch.Tensor], frames, up: Optional[float] = None, crop: bool = False, out: Optional[torch.Tensor] = None):
     """Kept boxes and their instance masks in the coordinates of the ORIGINAL images, masks one bit per pixel.
@@ -226,10 +259,8 @@ def masks_to_frames(protos: torch.Tensor, mc: torch.Tensor, keep_anchor: torch.T
     lib = L.load()
     _need_cuda(protos, "masks_to_frames")
     assert mc.dtype == torch.float32
-    pr, ld = _nhwc_rows(protos)
+    pr = _proto_rows(protos)
     B, nm, hp, wp = protos.shape
-    if ld != nm:
-        pr = pr.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
     dev = protos.device
     keep_anchor = keep_anchor.contiguous().to(torch.int32)
     K = keep_anchor.shape[1]
@@ -237,19 +268,15 @@ def masks_to_frames(protos: torch.Tensor, mc: torch.Tensor, keep_anchor: torch.T
         raise ValueError(f"masks_to_frames: {len(frames)} frames for a batch of {B}")
     if crop and boxes is None:
         raise ValueError("masks_to_frames: crop=True needs the boxes")
-    rows, total = _frame_layout(frames, K, 4.0 if up is None else float(up))
-    if out is None:
-        out = torch.empty((total,), dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total or out.device != dev:
-        raise ValueError(f"masks_to_frames: out must be a contiguous flat uint8 buffer of at least {total} bytes on {dev}")
+    packed = _PackedFrames("masks_to_frames", frames, K, 4.0 if up is None else float(up), out, dev)
+    out = packed.out
     if counts is not None:
         counts = counts.contiguous().to(torch.int32)
     boxes_frame = None
     if boxes is not None:
         boxes = boxes.contiguous().float()
         boxes_frame = torch.empty((B, K, 4), dtype=torch.float32, device=dev)
-    for c0 in range(0, B, MAX_FRAMES):
-        nb = min(MAX_FRAMES, B - c0)
+    for c0, nb, fr in packed.chunks():
         a = L.FrameMaskArgs()
         a.protos, a.coeff = pr[c0:].data_ptr(), mc[c0:].data_ptr()
         a.coeff_batch_stride, a.coeff_k_stride, a.coeff_c_stride = mc.stride(0), mc.stride(2), mc.stride(1)
@@ -259,15 +286,11 @@ def masks_to_frames(protos: torch.Tensor, mc: torch.Tensor, keep_anchor: torch.T
         a.boxes_frame = boxes_frame[c0:].data_ptr() if boxes_frame is not None else None
         a.out, a.out_bytes = out.data_ptr(), out.numel()
         a.N, a.K, a.nm, a.hp, a.wp, a.crop = nb, K, nm, hp, wp, int(bool(crop))
-        fr = (L.Frame * nb)()
-        for i, (H0, W0, step, scale, pitch, off) in enumerate(rows[c0:c0 + nb]):
-            fr[i].height, fr[i].width, fr[i].step, fr[i].scale, fr[i].pitch, fr[i].offset = H0, W0, step, scale, pitch, off
         rc = lib.mtbt_masks_to_frames(C.byref(a), fr, nb, _stream(dev))
         if rc == -1 and nm != 32:
             raise ValueError(f"masks_to_frames: {nm} prototype channels; the kernel supports 32")
         L.check(rc, "mtbt_masks_to_frames")
-    views = [out[off:off + K * H0 * pitch].view(K, H0, pitch) for H0, W0, step, scale, pitch, off in rows]
-    return {"boxes": boxes_frame, "masks": views, "buffer": out}
+    return {"boxes": boxes_frame, "masks": packed.views(), "buffer": out}
 
 
 def unpack_masks(packed: torch.Tensor, W0: int) -> torch.Tensor:
@@ -349,6 +372,15 @@ def detect_and_segment(det_maps: List[torch.Tensor], mc: torch.Tensor, protos: t
 FUSE_MAX_SOURCES, FUSE_MAX_CANDIDATES = 8, 4096   # include/mtbt_hip.h MTBT_FUSE_MAX_SOURCES / MTBT_FUSE_MAX_CANDIDATES
 
 
+def _det_tensors(d: dict, with_anchor: bool):
+    """[boxes, scores, labels, counts(, keep_anchor)] of a detection dict, typed and contiguous as the fusion and merge kernels read them."""
+    src = [d["boxes"].contiguous().float(), d["scores"].contiguous().float(), d["labels"].contiguous().to(torch.int64),
+           d["counts"].contiguous().to(torch.int32)]
+    if with_anchor:
+        src.append(d["keep_anchor"].contiguous().to(torch.int32))
+    return src
+
+
 def _fuse_args(dets, img_size, orients, weights, iou_thr, skip_thr, top_k):
     """The checked `mtbt_box_fuse_args` of a `fuse_detections` call, its output dict (which keeps every tensor the struct points to
     alive under "_keep") and the device."""
@@ -377,10 +409,8 @@ def _fuse_args(dets, img_size, orients, weights, iou_thr, skip_thr, top_k):
     a = L.BoxFuseArgs()
     keep = []
     for m, d in enumerate(dets):
-        src = [d["boxes"].contiguous().float(), d["scores"].contiguous().float(), d["labels"].contiguous().to(torch.int64),
-               d["counts"].contiguous().to(torch.int32)]
+        src = _det_tensors(d, with_anchor)
         if with_anchor:
-            src.append(d["keep_anchor"].contiguous().to(torch.int32))
             a.anchors[m] = src[4].data_ptr()
         a.boxes[m], a.scores[m], a.labels[m], a.counts[m] = (t.data_ptr() for t in src[:4])
         a.orient[m], a.weight[m] = orients[m], weights[m]
@@ -477,28 +507,22 @@ def vote_masks(fused: dict, sources: Sequence, orients: Optional[Sequence[int]],
     for m, src in enumerate(sources):
         mc, protos = src["segment_protos"][1:3] if isinstance(src, dict) else src
         _need_cuda(protos, "vote_masks")
-        pr, ld = _nhwc_rows(protos)
+        pr = _proto_rows(protos)
         nm, hp, wp = protos.shape[1:]
-        if ld != nm:
-            pr = pr.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
         mc = mc.float()
         if protos.shape[0] != B or mc.shape[0] != B or mc.shape[1] != nm or nm != 32 or hp != wp or (keep and (hp, wp) != tuple(keep[0][0].shape[2:])):
             raise ValueError(f"vote_masks: source {m} has protos {tuple(protos.shape)} and mc {tuple(mc.shape)}; expected [{B}, 32, G, G] and "
                              f"[{B}, 32, A] with the same square G for every source")
         keep.append((pr, mc))
     G = keep[0][0].shape[2]
-    rows, total = _frame_layout(frames, top_k, 4.0 if up is None else float(up))
-    if out is None:
-        out = torch.empty((total,), dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total or out.device != dev:
-        raise ValueError(f"vote_masks: out must be a contiguous flat uint8 buffer of at least {total} bytes on {dev}")
+    packed = _PackedFrames("vote_masks", frames, top_k, 4.0 if up is None else float(up), out, dev)
+    out = packed.out
     boxes = boxes.contiguous().float()
     boxes_frame = torch.empty((B, top_k, 4), dtype=torch.float32, device=dev)
     W = torch.empty((B, top_k, M, 32), dtype=torch.float32, device=dev)
     Ss = torch.empty((B, top_k), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        for c0 in range(0, B, MAX_FRAMES):
-            nb = min(MAX_FRAMES, B - c0)
+        for c0, nb, fr in packed.chunks():
             a = L.VoteMaskArgs()
             for m, ((pr, mc), src) in enumerate(zip(keep, srcs)):
                 a.protos[m], a.mc[m] = pr[c0:].data_ptr(), mc[c0:].data_ptr()
@@ -510,12 +534,8 @@ def vote_masks(fused: dict, sources: Sequence, orients: Optional[Sequence[int]],
             a.W, a.Ss = W[c0:].data_ptr(), Ss[c0:].data_ptr()
             a.out, a.out_bytes = out.data_ptr(), out.numel()
             a.n_sources, a.N, a.K, a.top_k, a.nm, a.hp, a.wp, a.crop = M, nb, K, top_k, 32, G, G, int(bool(crop))
-            fr = (L.Frame * nb)()
-            for i, (H0, W0, step, scale, pitch, off) in enumerate(rows[c0:c0 + nb]):
-                fr[i].height, fr[i].width, fr[i].step, fr[i].scale, fr[i].pitch, fr[i].offset = H0, W0, step, scale, pitch, off
             L.check(lib.mtbt_vote_masks(C.byref(a), fr, nb, _stream(dev)), "mtbt_vote_masks")
-    views = [out[off:off + top_k * H0 * pitch].view(top_k, H0, pitch) for H0, W0, step, scale, pitch, off in rows]
-    return {"boxes": boxes_frame, "masks": views, "buffer": out, "vote_coeff": W, "vote_weight": Ss}
+    return {"boxes": boxes_frame, "masks": packed.views(), "buffer": out, "vote_coeff": W, "vote_weight": Ss}
 
 
 def _square(x: torch.Tensor, orient: int, what: str):
@@ -599,8 +619,7 @@ def merge_tiles(det: dict, tiles: Sequence[Sequence[dict]], frames, *, metric: s
                              f"at most), all of them of its frame {tuple(fr[:2])}")
     top_k = int(top_k)
     table, first, table_dev = tile_table(tiles, dev)
-    src = [det["boxes"].contiguous().float(), det["scores"].contiguous().float(), det["labels"].contiguous().to(torch.int64),
-           det["counts"].contiguous().to(torch.int32)]
+    src = _det_tensors(det, "keep_anchor" in det)
     o = {
         "boxes_frame": torch.empty((N, top_k, 4), dtype=torch.float32, device=dev),
         "scores": torch.empty((N, top_k), dtype=torch.float32, device=dev),
@@ -613,9 +632,8 @@ def merge_tiles(det: dict, tiles: Sequence[Sequence[dict]], frames, *, metric: s
         "n_left": torch.empty((N,), dtype=torch.int32, device=dev),
     }
     a = L.TileMergeArgs()
-    a.boxes, a.scores, a.labels, a.counts = (t.data_ptr() for t in src)
+    a.boxes, a.scores, a.labels, a.counts = (t.data_ptr() for t in src[:4])
     if "keep_anchor" in det:
-        src.append(det["keep_anchor"].contiguous().to(torch.int32))
         o["lead_anchor"] = torch.empty((N, top_k), dtype=torch.int32, device=dev)
         a.anchors, a.lead_anchor = src[4].data_ptr(), o["lead_anchor"].data_ptr()
     a.tiles, a.tiles_dev, a.first = table, table_dev.data_ptr(), first
@@ -652,26 +670,17 @@ def vote_tile_masks(merged: dict, det: dict, mc: torch.Tensor, protos: torch.Ten
     dev = member_slot.device
     N, top_k = merged["scores"].shape
     NT, K = member_slot.shape
-    pr, ld = _nhwc_rows(protos)
+    pr = _proto_rows(protos)
     nm, hp, wp = protos.shape[1:]
-    if ld != nm:
-        pr = pr.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
     mc = mc.float()
     if protos.shape[0] != NT or mc.shape[0] != NT or mc.shape[1] != nm or nm != 32 or hp != wp:
         raise ValueError(f"vote_tile_masks: protos {tuple(protos.shape)} and mc {tuple(mc.shape)}; expected [{NT}, 32, G, G] and [{NT}, 32, A]")
     if len(frames) != N or len(tiles) != N or sum(len(per) for per in tiles) != NT:
         raise ValueError(f"vote_tile_masks: {len(frames)} frames and {len(tiles)} tile lists for {N} images, {NT} tiles")
     Tmax = max(1, max(len(per) for per in tiles))
-    rows, total = [], 0
-    for fr in frames:
-        H0, W0 = int(fr[0]), int(fr[1])
-        pitch = 8 * ((W0 + 63) // 64)
-        rows.append((H0, W0, pitch, total))
-        total = (total + top_k * H0 * pitch + 15) // 16 * 16
-    if out is None:
-        out = torch.empty((total,), dtype=torch.uint8, device=dev)
-    elif out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous() or out.numel() < total or out.device != dev:
-        raise ValueError(f"vote_tile_masks: out must be a contiguous flat uint8 buffer of at least {total} bytes on {dev}")
+    # the frame's own step and scale are not used (1 here): every tile carries its own
+    packed = _PackedFrames("vote_tile_masks", [(fr[0], fr[1], 1.0) for fr in frames], top_k, 1.0, out, dev)
+    out = packed.out
     if merged.get("tiles") is tiles and "_keep" in merged:
         table, first, table_dev = merged["_keep"][1:4]           # the table `merge_tiles` built and uploaded
     else:
@@ -681,8 +690,7 @@ def vote_tile_masks(merged: dict, det: dict, mc: torch.Tensor, protos: torch.Ten
     W = torch.empty((N, top_k, Tmax, 32), dtype=torch.float32, device=dev)
     Ss = torch.empty((N, top_k), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        for c0 in range(0, N, MAX_FRAMES):
-            nb = min(MAX_FRAMES, N - c0)
+        for c0, nb, fr in packed.chunks():
             a = L.TileMaskArgs()
             a.protos, a.mc = pr.data_ptr(), mc.data_ptr()
             a.mc_batch_stride, a.mc_k_stride, a.mc_c_stride = mc.stride(0), mc.stride(2), mc.stride(1)
@@ -693,12 +701,8 @@ def vote_tile_masks(merged: dict, det: dict, mc: torch.Tensor, protos: torch.Ten
             a.W, a.Ss = W[c0:].data_ptr(), Ss[c0:].data_ptr()
             a.out, a.out_bytes = out.data_ptr(), out.numel()
             a.N, a.n_tiles, a.K, a.top_k, a.Tmax, a.nm, a.hp, a.wp, a.crop = nb, NT, K, top_k, Tmax, 32, hp, wp, int(bool(crop))
-            fr = (L.Frame * nb)()
-            for i, (H0, W0, pitch, off) in enumerate(rows[c0:c0 + nb]):
-                fr[i].height, fr[i].width, fr[i].step, fr[i].scale, fr[i].pitch, fr[i].offset = H0, W0, 1.0, 1.0, pitch, off
             L.check(lib.mtbt_vote_tile_masks(C.byref(a), fr, nb, _stream(dev)), "mtbt_vote_tile_masks")
-    views = [out[off:off + top_k * H0 * pitch].view(top_k, H0, pitch) for H0, W0, pitch, off in rows]
-    return {"boxes": boxes, "masks": views, "buffer": out, "vote_coeff": W, "vote_weight": Ss, "_keep": (table, first, table_dev, pr, mc, scores, anchors)}
+    return {"boxes": boxes, "masks": packed.views(), "buffer": out, "vote_coeff": W, "vote_weight": Ss, "_keep": (table, first, table_dev, pr, mc, scores, anchors)}
 
 
 # ---- connected components of packed planes ----------------------------------------------------------------------------------------

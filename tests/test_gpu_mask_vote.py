@@ -174,6 +174,68 @@ def test_one_source_equals_masks_to_frames(crop):
         assert not (diff & ~(ref[b]["logits"][single[b]].abs() < BAND)).any()
 
 
+# ---- more images than one launch takes (32 frames): the chunks of `vote_masks` ------------------------------------------------------
+CH_B, CH_G, CH_S, CH_K, CH_ORIENTS = 33, 16, 64.0, 5, (0, 5)
+CH_FRAMES = [(H0, W0, CH_S / max(H0, W0)) for H0, W0 in [(20, 30), (30, 20)] * 17][:CH_B]
+
+
+@functools.lru_cache(maxsize=None)
+def _chunk_inputs(seed=7):
+    counts = np.random.default_rng(seed).integers(0, CH_K + 1, size=(2, CH_B))
+    counts[:, 5], counts[:, CH_B - 1] = 0, (CH_K, 3)                 # an image without detections; the last image has fused rows
+    dets = FU.clustered_lists(2, CH_B, CH_K, counts.tolist(), seed, S=CH_S, orients=CH_ORIENTS)
+    mcs, protos = VR.vote_inputs(dets, CH_B, CH_G, seed, CH_ORIENTS, S=CH_S, A=A)
+    return dets, mcs, protos
+
+
+def _chunk_call(lo, hi, crop):
+    """The public calls on images lo .. hi - 1 alone: fusion with membership, then the vote into a buffer pre-filled with 0xFF."""
+    dets, mcs, protos = _chunk_inputs()
+    fused = pp.fuse_detections(_device_dets([{k: v[lo:hi] for k, v in d.items()} for d in dets]), img_size=CH_S, orients=CH_ORIENTS,
+                               want_members=True)
+    frames = CH_FRAMES[lo:hi]
+    buf = torch.full((_total_bytes(frames, CH_K),), 0xFF, dtype=torch.uint8, device=DEV)
+    r = pp.vote_masks(fused, _device_sources([mc[lo:hi] for mc in mcs], [p[lo:hi] for p in protos]), CH_ORIENTS, None, frames, crop=crop,
+                      out=buf, up=CH_S / CH_G)
+    assert r["buffer"].data_ptr() == buf.data_ptr()
+    return r
+
+
+@pytest.mark.parametrize("crop", [False, True])
+def test_more_than_32_images_are_chunked(crop):
+    """33 images, M = 2 (orients 0 and 5), G = 16, S = 64, K = 5, frames 20 x 30 and 30 x 20 in turn: the second launch (image 32 alone)
+    writes what a call on that image alone writes, byte for byte, and its planes are the CPU restatement's outside BAND * M."""
+    last = CH_B - 1
+    whole, head, tail = _chunk_call(0, CH_B, crop), _chunk_call(0, last, crop), _chunk_call(last, CH_B, crop)
+    torch.cuda.synchronize()
+    at = head["buffer"].numel()                                      # image 32's planes start where 32 images end (16-byte aligned)
+    assert whole["buffer"].numel() == at + tail["buffer"].numel()
+    assert torch.equal(whole["buffer"][:at], head["buffer"]) and torch.equal(whole["buffer"][at:], tail["buffer"])
+    for k in ("boxes", "vote_coeff", "vote_weight"):
+        assert torch.equal(whole[k][:last].view(torch.int32), head[k].view(torch.int32)), k
+        assert torch.equal(whole[k][last:].view(torch.int32), tail[k].view(torch.int32)), k
+    # image 32 against the CPU
+    dets, mcs, protos = _chunk_inputs()
+    d1 = [{k: v[last:] for k, v in d.items()} for d in dets]
+    fused = VR.fuse_members(d1, CH_S, CH_ORIENTS, None, top_k=CH_K)
+    W, Ss = VR.vote_coefficients(d1, [mc[last:] for mc in mcs], fused["member_slot"], fused["counts"], (1.0, 1.0), CH_K)
+    ref = VR.vote_reference(W, fused["counts"], fused["boxes"], [p[last:] for p in protos], CH_ORIENTS, CH_FRAMES[last:], CH_S / CH_G, crop)[0]
+    H0, W0, _ = CH_FRAMES[last]
+    n = int(fused["counts"][0])
+    packed = whole["masks"][last]
+    assert packed.dtype == torch.uint8 and tuple(packed.shape) == (CH_K, H0, FR.pitch_of(W0))
+    allbits = FR.unpack_bits(packed, W0)
+    got = allbits[:, :, :W0]
+    assert not allbits[:, :, W0:].any(), "padding bits"
+    assert 0 < n and not got[n:].any(), "planes r >= counts"
+    near = ref["logits"].abs() < BAND * 2
+    diff = got != ref["bits"]
+    print(f"crop={crop} image {last} {H0}x{W0}: differing bits {int(diff.sum())}, in-band pixels {int(near[:n].sum())} of {near[:n].numel()}")
+    assert not (diff & ~near).any(), "bits differ outside the sign-ambiguous band"
+    assert got.any() and torch.equal(whole["boxes"][last].cpu(), ref["boxes"])
+    assert not whole["masks"][5].any(), "an image without detections has zero planes"
+
+
 # ---- the public routes on the synthetic model of test_gpu_ensemble.py ----------------------------------------------------------------
 MS, MB, TOP_K = 128, 3, 50
 NMS = dict(conf_th=0.05, iou_th=0.6, top_k=TOP_K)

@@ -173,6 +173,79 @@ def test_single_full_view_tile_is_masks_to_frames():
         assert allbits.any()
 
 
+# ---- more images than one launch takes (32 frames): the chunks of `vote_tile_masks` -------------------------------------------------
+CH_N, CH_S, CH_K = 33, 64, 5                                          # G = 16
+CH_SIZES = ([(40, 50), (70, 100)] * 17)[:CH_N]                        # one tile; 2 x 2 tiles plus the full view
+
+
+@functools.lru_cache(maxsize=None)
+def _chunk_inputs():
+    tiles = pre.slice_geometry(CH_SIZES, CH_S)
+    assert [len(per) for per in tiles[:2]] == [1, 5]
+    return (tiles,) + SR.tile_lists(tiles, CH_K, SEED, CH_S, A=A, empty=(4,))
+
+
+def _chunk_call(lo, hi, crop):
+    """The public calls on images lo .. hi - 1 alone: their tiles renumbered from image 0, the merge, then the vote into a buffer
+    pre-filled with 0xFF."""
+    tiles, det, mc, protos = _chunk_inputs()
+    t0, t1 = sum(len(per) for per in tiles[:lo]), sum(len(per) for per in tiles[:hi])
+    sub = [[dict(t, image=n) for t in per] for n, per in enumerate(tiles[lo:hi])]
+    d = _dev({k: v[t0:t1] for k, v in det.items()})
+    sizes = CH_SIZES[lo:hi]
+    frames = [(H0, W0, CH_S / max(H0, W0)) for H0, W0 in sizes]
+    merged = pp.merge_tiles(d, sub, frames, top_k=CH_K)
+    buf = torch.full((_total_bytes(sizes, CH_K),), 0xFF, dtype=torch.uint8, device=DEV)
+    r = pp.vote_tile_masks(merged, d, mc[t0:t1].to(DEV), protos[t0:t1].to(DEV).contiguous(memory_format=torch.channels_last), sub, frames,
+                           crop=crop, out=buf)
+    assert r["buffer"].data_ptr() == buf.data_ptr()
+    return r
+
+
+@pytest.mark.parametrize("crop", [False, True])
+def test_more_than_32_images_are_chunked(crop):
+    """33 images of 40 x 50 (one tile) and 70 x 100 (five) in turn at S = 64, K = 5: the second launch (image 32 alone, whose tile is
+    number 96 of the table) writes what a call on that image alone writes, byte for byte, and its planes are the CPU restatement's
+    outside BAND * (tiles added)."""
+    last = CH_N - 1
+    whole, head, tail = _chunk_call(0, CH_N, crop), _chunk_call(0, last, crop), _chunk_call(last, CH_N, crop)
+    torch.cuda.synchronize()
+    at = head["buffer"].numel()                                      # image 32's planes start where 32 images end (16-byte aligned)
+    assert whole["buffer"].numel() == at + tail["buffer"].numel()
+    assert torch.equal(whole["buffer"][:at], head["buffer"]) and torch.equal(whole["buffer"][at:], tail["buffer"])
+    for k in ("boxes", "vote_weight"):
+        assert torch.equal(whole[k][:last].view(torch.int32), head[k].view(torch.int32)), k
+        assert torch.equal(whole[k][last:].view(torch.int32), tail[k].view(torch.int32)), k
+    W, tmax = whole["vote_coeff"].view(torch.int32), tail["vote_coeff"].shape[2]   # W's third dimension is the batch's largest tile count
+    assert tuple(W.shape) == (CH_N, CH_K, 5, 32) and tmax == 1
+    assert torch.equal(W[:last], head["vote_coeff"].view(torch.int32))
+    assert torch.equal(W[last:, :, :tmax], tail["vote_coeff"].view(torch.int32)) and not W[last:, :, tmax:].any()
+    # image 32 against the CPU
+    tiles, det, mc, protos = _chunk_inputs()
+    t0 = sum(len(per) for per in tiles[:last])
+    assert t0 == 96 and len(tiles[last]) == 1
+    d1, per = {k: v[t0:] for k, v in det.items()}, [tiles[last]]
+    merged = SR.merge_tiles(d1, per, top_k=CH_K)
+    Wr, _ = SR.vote_coefficients(d1, mc[t0:], merged, per, CH_K)
+    ref = SR.vote_reference(Wr, merged, protos[t0:], per, crop)[0]
+    H0, W0 = CH_SIZES[last]
+    cnt = int(merged["counts"][0])
+    packed = whole["masks"][last]
+    assert packed.dtype == torch.uint8 and tuple(packed.shape) == (CH_K, H0, FR.pitch_of(W0))
+    allbits = FR.unpack_bits(packed, W0)
+    got = allbits[:, :, :W0]
+    assert not allbits[:, :, W0:].any(), "padding bits"
+    assert 0 < cnt and not got[cnt:].any(), "planes r >= counts"
+    voted = ref["contrib"] > 0
+    near = (ref["logits"].abs() < BAND * ref["contrib"]) & voted
+    diff = got != ref["bits"]
+    print(f"crop={crop} image {last} {H0}x{W0}: differing bits {int(diff.sum())}, in-band pixels {int(near.sum())} of {int(voted.sum())}")
+    assert not (diff & ~near).any(), "bits differ outside the sign-ambiguous band"
+    assert got.any() and not (got & ~voted).any()
+    assert torch.equal(whole["boxes"][last].cpu().view(torch.int32), torch.from_numpy(merged["boxes_frame"][0]).view(torch.int32))
+    assert not whole["masks"][4].any(), "an image without detections has zero planes"
+
+
 # ---- the public route on the synthetic model of the vote tests ---------------------------------------------------------------------
 MS, TILE_K, TOP = 128, 50, 60
 

@@ -1,10 +1,12 @@
 """Timing probe of the frame operator (GPU box): `postprocess.masks_to_frames` (bit-packed masks in the original image frame, crop off
 and crop on) beside the dense `assemble_masks`, in one process, on the kept boxes of one calibrated synthetic step
 (batch 16, 640 x 640, K = 100, identity frames).  Device events around 20 launches per variant after warm-up, the variants
-alternating, 6 rounds; prints the per-launch mean of every round and the bytes each variant writes.
+alternating, 6 rounds; prints a sha256 of each frame variant's planes and boxes (so that two builds can be compared byte for byte at the
+size that is timed), then the per-launch mean of every round and the bytes each variant writes.
 
   python tools/frame_mask_probe.py [--batch 16] [--img 640]"""
 import argparse
+import hashlib
 import os
 import sys
 
@@ -19,6 +21,17 @@ ap.add_argument("--img", type=int, default=640)
 ap.add_argument("--launches", type=int, default=20)
 ap.add_argument("--rounds", type=int, default=6)
 args = ap.parse_args()
+
+
+def digest(r):
+    """sha256 of a frame operator's result: the packed planes, the boxes and, where they exist, vote_coeff and vote_weight."""
+    h = hashlib.sha256()
+    for t in list(r["masks"]) + [r.get(k) for k in ("boxes", "vote_coeff", "vote_weight")]:
+        if t is not None:
+            h.update(t.contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
 dev = torch.device("cuda", 0)
 B, S = args.batch, args.img
 
@@ -46,6 +59,8 @@ variants = {
     "dense assemble_masks": lambda: pp.assemble_masks(protos, mc, keep, counts, (S, S)),
 }
 bytes_written = {"frames crop=off": buf.numel(), "frames crop=on": buf.numel(), "dense assemble_masks": B * K * S * S}
+for name in ("frames crop=off", "frames crop=on"):
+    print(f"{name:22s} sha256 {digest(variants[name]())}", flush=True)
 for f in variants.values():
     for _ in range(5):
         f()

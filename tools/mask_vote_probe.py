@@ -1,6 +1,7 @@
 """Timing probe of the mask vote over fused detections (GPU box) on the benchmark's calibrated synthetic model (batch 16, 640 x 640, bf16,
 top_k = 100), M = 2 (views 0, 1) and M = 8 (views 0 - 7) sources.  One process, warm; device events around `--reps` back-to-back calls, the
-variants alternating, `--rounds` rounds; prints every reading and the median per call.
+variants alternating, `--rounds` rounds; prints every reading and the median per call and, before the `launch` timings, a sha256 of each of
+their results (planes, boxes, vote_coeff, vote_weight), so that two builds can be compared byte for byte at the size that is timed.
 
   whole    detect_fused(masks="vote") against detect_fused(masks=True) (the leaders' masks): M forwards + NMS + fusion + masks
   masks    the mask half alone on kept forward results: ensemble._leader_masks against vote_masks + unpack (identity frames, dense uint8)
@@ -9,6 +10,7 @@ variants alternating, `--rounds` rounds; prints every reading and the median per
 
   python tools/mask_vote_probe.py [--batch 16] [--img 640]"""
 import argparse
+import hashlib
 import os
 import statistics
 import sys
@@ -24,6 +26,17 @@ ap.add_argument("--img", type=int, default=640)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--rounds", type=int, default=7)
 args = ap.parse_args()
+
+
+def digest(r):
+    """sha256 of a frame operator's result: the packed planes, the boxes and, where they exist, vote_coeff and vote_weight."""
+    h = hashlib.sha256()
+    for t in list(r["masks"]) + [r.get(k) for k in ("boxes", "vote_coeff", "vote_weight")]:
+        if t is not None:
+            h.update(t.contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
 dev = torch.device("cuda", 0)
 B, S = args.batch, args.img
 
@@ -75,5 +88,9 @@ for M in (2, 8):
             pp.masks_to_frames(protos, mc, d["keep_anchor"], d["counts"], d["boxes"], frames, up=up, crop=crop, out=buf)
 
     for crop in (False, True):
+        print(f"  vote_masks M={M} crop={crop!s:5} sha256 {digest(pp.vote_masks(fused, pairs, views, None, frames, crop=crop, out=buf, up=up))}", flush=True)
+        for m, ((protos, mc), d) in enumerate(zip(srcs, dets)):
+            r = pp.masks_to_frames(protos, mc, d["keep_anchor"], d["counts"], d["boxes"], frames, up=up, crop=crop, out=buf)
+            print(f"  masks_to_frames source {m} of {M} crop={crop!s:5} sha256 {digest(r)}", flush=True)
         timed({f"launch, vote_masks crop={crop!s:5}           ": lambda: pp.vote_masks(fused, pairs, views, None, frames, crop=crop, out=buf, up=up),
                f"launch, {M} x masks_to_frames crop={crop!s:5}": lambda: per_source(crop)})

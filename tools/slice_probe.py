@@ -1,7 +1,9 @@
 """Timing probe of sliced inference's merge and mask launches (GPU box) on one 2048 x 1536 image at S = 640: 12 tiles plus the full view,
 K = 100 slots per tile, top_k = 100 merged rows, on the planted detection lists of tests/slice_reference.py (no model).  One process,
 warm; device events around `--reps` back-to-back calls of the Python wrappers (so the host's share -- the tile table, its upload, the
-frame tile choice -- is inside every reading), the variants alternating, `--rounds` rounds; prints every reading and the median per call.
+frame tile choice -- is inside every reading), the variants alternating, `--rounds` rounds; prints every reading and the median per call
+and, before the mask timings, a sha256 of each of their results (planes, boxes, vote_coeff, vote_weight), so that two builds can be
+compared byte for byte at the size that is timed.
 
   merge    postprocess.merge_tiles (mtbt_merge_tiles: one workgroup for the image's 1300 slots)
   vote     postprocess.vote_tile_masks (mtbt_vote_tile_masks: coefficient launch + mask launch, 100 packed planes of 1536 x 2048)
@@ -10,6 +12,7 @@ frame tile choice -- is inside every reading), the variants alternating, `--roun
 
   python tools/slice_probe.py [--height 1536] [--width 2048]"""
 import argparse
+import hashlib
 import os
 import statistics
 import sys
@@ -32,6 +35,17 @@ ap.add_argument("--objects", type=int, default=150)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--rounds", type=int, default=7)
 args = ap.parse_args()
+
+
+def digest(r):
+    """sha256 of a frame operator's result: the packed planes, the boxes and, where they exist, vote_coeff and vote_weight."""
+    h = hashlib.sha256()
+    for t in list(r["masks"]) + [r.get(k) for k in ("boxes", "vote_coeff", "vote_weight")]:
+        if t is not None:
+            h.update(t.contiguous().cpu().numpy().tobytes())
+    return h.hexdigest()
+
+
 dev = torch.device("cuda", 0)
 S, K, H0, W0 = args.img, args.k, args.height, args.width
 
@@ -70,6 +84,9 @@ def timed(variants):
 timed({"merge, merge_tiles (ios 0.5)      ": lambda: pp.merge_tiles(det, tiles, frames, top_k=K),
        "merge, merge_tiles (iou 0.5)      ": lambda: pp.merge_tiles(det, tiles, frames, metric="iou", top_k=K)})
 for crop in (False, True):
+    print(f"  vote_tile_masks crop={crop!s:5} sha256 {digest(pp.vote_tile_masks(merged, det, mc, protos, tiles, frames, crop=crop, out=buf))}", flush=True)
+    r = pp.masks_to_frames(protos[full:], mc[full:], det["keep_anchor"][full:], det["counts"][full:], det["boxes"][full:], frames, up=4.0, crop=crop, out=buf)
+    print(f"  masks_to_frames crop={crop!s:5} sha256 {digest(r)}", flush=True)
     timed({f"vote,  vote_tile_masks crop={crop!s:5} ": lambda: pp.vote_tile_masks(merged, det, mc, protos, tiles, frames, crop=crop, out=buf),
            f"frame, masks_to_frames crop={crop!s:5} ": lambda: pp.masks_to_frames(protos[full:], mc[full:], det["keep_anchor"][full:], det["counts"][full:],
                                                                              det["boxes"][full:], frames, up=4.0, crop=crop, out=buf)})
