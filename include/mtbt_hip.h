@@ -1203,6 +1203,52 @@ int mtbt_select_components(const mtbt_select_components_args* a, void* stream);
 /* sizeof() of the structs above as the library was compiled: which = 0 mtbt_components_args, 1 mtbt_select_components_args; -1 otherwise */
 int mtbt_sizeof_components_args(int which);
 
+/* ---------------------------------------------------------------------------------------------
+ * Polygons -> bit-packed planes (csrc/polygon_fill.hip; `postprocess.fill_polygons`, `yolo_seg_planes`,
+ * `preprocess.augment_samples_seg`).  Packed layout and alignment as in the sections above (planes 8-byte aligned, 8-byte accesses only).
+ * THE FILL RULE is this project's own and exact in integers (tests/polygon_reference.py restates it):
+ *   Quantisation  a vertex coordinate v, in pixels of the target plane, is given as fixed point q = rint(float32(v) * 16), round half
+ *                 to even, int32 (the caller quantises).  Pixel (X, Y) has its centre at (16 X + 8, 16 Y + 8).
+ *   Crossing      an edge a -> b of the closed polygon (the last vertex joins the first) crosses the scanline yc = 16 Y + 8 when
+ *                 (ay <= yc) != (by <= yc); a horizontal edge never crosses.
+ *   Left          with the crossing edge oriented so that ay < by, the pixel is left of it when
+ *                 (bx - ax) * (yc - ay) - (xc - ax) * (by - ay) > 0, in int64.
+ *   Even-odd      the pixel is inside the polygon when the number of crossing edges it is left of is odd.
+ *   Planes        a plane is the union (OR) of its polygons, each filled on its own; a polygon of fewer than 3 vertices fills nothing.
+ *   Clip          an optional rectangle (x0, y0, x1, y1) per plane, int32, half-open in pixel indices, zeroes everything outside it.
+ * The result does not depend on the starting vertex or the winding; two polygons that share an edge tile the pixels without overlap or
+ * gap; a rectangle sets exactly q(x1) <= 16 X + 8 < q(x2), q(y1) <= 16 Y + 8 < q(y2).
+ *   vertices       int32 [n_vertices][2] x, y
+ *   poly_offsets   int32 [n_polys + 1]: polygon p owns the vertices poly_offsets[p] .. poly_offsets[p + 1] - 1
+ *   plane_offsets  int32 [n + 1]: plane j owns the polygons plane_offsets[j] .. plane_offsets[j + 1] - 1
+ *   clip           int32 [n][4] or NULL
+ *   out            [n][H][pitch]; EVERY byte is written, padding bits X >= W are zero: the caller never pre-zeroes
+ *   area           uint32 [n] or NULL: the popcount of the plane
+ *   box            int32 [n][4] or NULL: the tight x1, y1, x2, y2 with exclusive maxima (the convention of mtbt_label_components);
+ *                  all zero for an empty plane
+ * area and box are fully defined after the call (the entry point clears them on the stream before the launch).  Integer arithmetic
+ * and integer atomics only: the result is a pure function of the input.
+ * CLAMPING: the tables live on the device, so the library cannot validate them.  The kernel clamps every offset it reads into
+ * [0, n_polys] or [0, n_vertices] (a decreasing pair is an empty range) and every coordinate into [-2^24, 2^24], so that the products
+ * fit int64; its loop bounds then come from the host-side counts, and no table can make it read outside `vertices` or spin.
+ * Asynchronous on `stream`, no host synchronisation, no workspace, graph-capturable.
+ * MTBT_EINVAL before any launch: NULL a / out / poly_offsets / plane_offsets, NULL vertices with n_vertices > 0, n < 0, n_polys < 0,
+ * n_vertices < 0, H < 1, W < 1, H * W >= 2^31, pitch != 8 * ceil(W / 64).  MTBT_EALIGN: out not 8-byte aligned, an int32 / uint32 pointer
+ * not 4-byte aligned.  n == 0 launches nothing. */
+typedef struct mtbt_fill_polygons_args {
+  const int32_t* vertices;       /* [n_vertices][2] x, y, fixed point 1/16 px */
+  const int32_t* poly_offsets;   /* [n_polys + 1] into vertices */
+  const int32_t* plane_offsets;  /* [n + 1] into polygons */
+  const int32_t* clip;           /* [n][4] x0, y0, x1, y1, or NULL */
+  uint8_t* out;                  /* [n][H][pitch] */
+  uint32_t* area;                /* [n] or NULL */
+  int32_t* box;                  /* [n][4] or NULL */
+  int32_t n, n_polys, n_vertices, H, W, pitch;
+} mtbt_fill_polygons_args;
+int mtbt_fill_polygons(const mtbt_fill_polygons_args* a, void* stream);
+/* sizeof() of the struct above as the library was compiled: which = 0 mtbt_fill_polygons_args; -1 otherwise */
+int mtbt_sizeof_fill_polygons_args(int which);
+
 /* Weight gradient of a k x k convolution (any stride / padding; 1x1 and the 2x2 stride-2 downsample included), bf16 (MFMA) or fp32 operands:
  *   dw[k][r][s][c] (fp32, packed [K][R*S*C] like the forward weight) (+)= sum_p dy[p][k] * x[n][y*stride + r - pad][x*stride + s - pad][c]
  * x [N,H,W,C], dy [N,Ho,Wo,K] (Ho = (H + 2 pad - R) / stride + 1) NHWC with pixel / batch strides in elements (multiples of 8; C % 8 == K % 8 == 0;

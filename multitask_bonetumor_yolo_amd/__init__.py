@@ -17,13 +17,15 @@
     from multitask_bonetumor_yolo_amd import detect_sliced               # sliced inference: tiles of a large image, merged and voted on the device
     from multitask_bonetumor_yolo_amd import SurfaceDistanceMetrics      # Hausdorff / HD95 / ASSD / surface Dice from packed masks, on the device
     from multitask_bonetumor_yolo_amd import label_components, LesionMetrics   # connected components of packed masks; lesion-wise recall / precision
+    from multitask_bonetumor_yolo_amd import fill_polygons, yolo_seg_planes, augment_samples_seg   # polygon labels -> packed instance masks
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
 """
 from . import postprocess, preprocess  # noqa: F401
-from .preprocess import (augment_batch, augment_samples, augment_yolo_labels, letterbox_geometry, mosaic_batch, mosaic_samples,  # noqa: F401
-                         mosaic_yolo_labels, photometric_lut, sample_geometry, sample_mosaic, sample_photometric, slice_batch, slice_geometry)
+from .preprocess import (augment_batch, augment_polygons, augment_samples, augment_samples_seg, augment_yolo_labels, letterbox_geometry,  # noqa: F401
+                         mosaic_batch, mosaic_polygons, mosaic_samples, mosaic_samples_seg, mosaic_yolo_labels, photometric_lut,
+                         sample_geometry, sample_mosaic, sample_photometric, slice_batch, slice_geometry)
 from .loss import InstanceMaskLoss, TaskAlignedDetLoss, TaskAlignedSegLoss, instance_mask_loss, multitask_loss, task_aligned_det_loss  # noqa: F401
 from .checkpoints import load_pretrained_heads, load_train_state, save_train_state, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401
@@ -32,7 +34,8 @@ from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, 
                       lesion_hits, surface_distances, surface_metrics)
 from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
-from .postprocess import components_to_instances, filter_components, label_components, merge_tiles, vote_masks, vote_tile_masks  # noqa: F401
+from .postprocess import (components_to_instances, fill_polygons, filter_components, label_components, merge_tiles, vote_masks,  # noqa: F401
+                          vote_tile_masks, yolo_seg_planes)
 from .sliced import detect_sliced  # noqa: F401
 from .trainstep import TrainStep, ema_decay_at  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

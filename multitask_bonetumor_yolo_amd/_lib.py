@@ -234,6 +234,12 @@ class SelectComponentsArgs(C.Structure):  # mtbt_select_components_args
                 ("min_area", C.c_uint32), ("keep_largest", C.c_int32)]
 
 
+class FillPolygonsArgs(C.Structure):  # mtbt_fill_polygons_args
+    _fields_ = [("vertices", C.c_void_p), ("poly_offsets", C.c_void_p), ("plane_offsets", C.c_void_p), ("clip", C.c_void_p),
+                ("out", C.c_void_p), ("area", C.c_void_p), ("box", C.c_void_p),
+                ("n", C.c_int32), ("n_polys", C.c_int32), ("n_vertices", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -370,6 +376,8 @@ SYMBOLS = {
     "mtbt_label_components": (C.c_int, [C.POINTER(ComponentsArgs), C.c_void_p]),
     "mtbt_select_components": (C.c_int, [C.POINTER(SelectComponentsArgs), C.c_void_p]),
     "mtbt_sizeof_components_args": (C.c_int, [C.c_int]),
+    "mtbt_fill_polygons": (C.c_int, [C.POINTER(FillPolygonsArgs), C.c_void_p]),
+    "mtbt_sizeof_fill_polygons_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -378,6 +386,7 @@ MASK_EVAL_STRUCTS = (PackMasksArgs, MaskImage, MaskPairArgs, MaskEvalArgs)   # o
 TILE_STRUCTS = (Tile, TileMergeArgs, TileMaskArgs)   # order of mtbt_sizeof_tile_args(which)
 SURFACE_STRUCTS = (SurfaceArgs,)   # order of mtbt_sizeof_surface_args(which)
 COMPONENTS_STRUCTS = (ComponentsArgs, SelectComponentsArgs)   # order of mtbt_sizeof_components_args(which)
+POLYGON_STRUCTS = (FillPolygonsArgs,)   # order of mtbt_sizeof_fill_polygons_args(which)
 _lib = None
 
 
@@ -401,7 +410,7 @@ def load():
                                    f"{C.sizeof(st)} bytes: stale library, rebuild")
         for sizeof, structs in ((lib.mtbt_sizeof_frame_args, FRAME_STRUCTS), (lib.mtbt_sizeof_mask_eval_args, MASK_EVAL_STRUCTS),
                                 (lib.mtbt_sizeof_tile_args, TILE_STRUCTS), (lib.mtbt_sizeof_surface_args, SURFACE_STRUCTS),
-                                (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS)):
+                                (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS), (lib.mtbt_sizeof_fill_polygons_args, POLYGON_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

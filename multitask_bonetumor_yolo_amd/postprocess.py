@@ -7,6 +7,7 @@ batched on the GPU with no per-image Python loop and no host synchronisation.  N
 import ctypes as C
 from typing import List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -825,3 +826,123 @@ def components_to_instances(packed: torch.Tensor, W: int, *, max_instances: int 
     for b in range(n):
         pack_masks(rec["labels"][b][None] == ids[b][:, None, None], out=masks[b])
     return {"masks": masks, "boxes": boxes, "areas": areas, "counts": counts}
+
+
+# ---- polygons -> bit-packed planes (the project's own fill rule: include/mtbt_hip.h `mtbt_fill_polygons`) ---------------------------
+POLYGON_MAX_COORD = 32768.0      # |v| in pixels: 16 v fits int32 with room, and stays inside the kernel's clamp
+
+
+def _polygons_of(entry, who: str):
+    """One entry of `fill_polygons(planes)` -> its list of float64 [n_i, 2] arrays: an [n, 2] array-like is one polygon, a sequence of
+    them their union."""
+    as_np = lambda v: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+    if isinstance(entry, (torch.Tensor, np.ndarray)) and getattr(entry, "dtype", None) != object:
+        a = as_np(entry)
+        if a.ndim == 2 and a.shape[1] == 2:
+            return [a]
+        if a.ndim == 3 and a.shape[2] == 2:
+            return list(a)
+        if a.size == 0:
+            return []
+        raise ValueError(f"{who}: a polygon must be an [n, 2] array of pixel coordinates, not {tuple(a.shape)}")
+    items = list(entry)
+    if items and (items[0].dim() if isinstance(items[0], torch.Tensor) else np.ndim(items[0])) == 1:   # a list of (x, y) pairs
+        items = [items]
+    polys = []
+    for it in items:
+        a = as_np(it)
+        if a.size == 0:
+            a = a.reshape(0, 2)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError(f"{who}: a polygon must be an [n, 2] array of pixel coordinates, not {tuple(a.shape)}")
+        polys.append(a)
+    return polys
+
+
+def fill_polygons(planes: Sequence, H: int, W: int, *, clip=None, out: Optional[torch.Tensor] = None, records: bool = False, device=None):
+    """Rasterise polygons into bit-packed planes on the device (`mtbt_fill_polygons`; the fill rule is in include/mtbt_hip.h: vertices
+    in 1/16 pixel, pixel centres, even-odd per polygon, a plane the union of its polygons).
+
+    `planes` has one entry per output plane: an [n_i, 2] array-like of pixel coordinates (one polygon), or a sequence of such arrays
+    (their union; an empty sequence is an empty plane).  A polygon of fewer than 3 vertices fills nothing.  `clip`: an optional int
+    [n, 4] of half-open pixel rectangles (x0, y0, x1, y1), one per plane (a mosaic tile).  Coordinates must be finite with
+    |v| <= 32768 (ValueError).  They are quantised on the host, q = rint(float32(v) * 16), packed with the offset tables and the
+    rectangles into one buffer that goes up in one asynchronous copy, and one call fills every plane.  Returns uint8 [n, H, pitch],
+    pitch = 8 * ceil(W / 64), padding bits zero; with records=True also `area` int32 [n] and `boxes` float32 [n, 4] xyxy with
+    exclusive maxima (zeros for an empty plane), as `label_components` returns them.  `out=` as in `pack_masks`.  Asynchronous; there
+    is no CPU path."""
+    lib = L.load()
+    H, W = int(H), int(W)
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError(f"fill_polygons: planes of {H} x {W} pixels (1 <= H * W < 2^31)")
+    polys_of = [_polygons_of(e, "fill_polygons") for e in planes]
+    n = len(polys_of)
+    flat = [p for ps in polys_of for p in ps]
+    verts = np.concatenate(flat, axis=0) if flat else np.zeros((0, 2), dtype=np.float64)
+    if verts.size and not (np.isfinite(verts).all() and np.abs(verts).max() <= POLYGON_MAX_COORD):
+        raise ValueError(f"fill_polygons: coordinates must be finite and within +-{int(POLYGON_MAX_COORD)} pixels")
+    n_polys, n_vertices = len(flat), verts.shape[0]
+    if n_vertices >= 2 ** 30:
+        raise ValueError("fill_polygons: too many vertices")
+    rects = None
+    if clip is not None:
+        rects = np.asarray(clip.cpu() if isinstance(clip, torch.Tensor) else clip)
+        if rects.dtype.kind not in "iu" and rects.size:
+            raise ValueError("fill_polygons: clip must be integer pixel rectangles")
+        rects = rects.reshape(-1, 4) if rects.size or n == 0 else rects
+        if rects.shape != (n, 4):
+            raise ValueError(f"fill_polygons: clip must be [{n}, 4] (x0, y0, x1, y1), one row per plane")
+        rects = np.clip(rects.astype(np.int64), -2 ** 31, 2 ** 31 - 1)
+    dev = torch.device(device) if device is not None else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+    if dev.type != "cuda":
+        raise RuntimeError("fill_polygons: expected a CUDA/HIP device (an MI355X; no CPU path)")
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    pitch = 8 * ((W + 63) // 64)
+    if out is None:
+        out = torch.empty((n, H, pitch), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n, H, pitch) or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"fill_polygons: out must be a contiguous uint8 [{n}, {H}, {pitch}] tensor on {dev}")
+    area = torch.empty((n,), dtype=torch.int32, device=dev) if records else None
+    box = torch.empty((n, 4), dtype=torch.int32, device=dev) if records else None
+    if n:
+        # one host buffer: vertices | polygon offsets | plane offsets | clip rectangles, all int32
+        o_poly, o_plane, o_clip = 2 * n_vertices, 2 * n_vertices + n_polys + 1, 2 * n_vertices + n_polys + 1 + n + 1
+        host = torch.empty(o_clip + (4 * n if rects is not None else 0), dtype=torch.int32).pin_memory()
+        h = host.numpy()
+        h[:o_poly] = np.rint(verts.astype(np.float32) * np.float32(16.0)).astype(np.int32).reshape(-1)
+        h[o_poly] = 0
+        np.cumsum([p.shape[0] for p in flat], dtype=np.int32, out=h[o_poly + 1:o_plane])
+        h[o_plane] = 0
+        np.cumsum([len(ps) for ps in polys_of], dtype=np.int32, out=h[o_plane + 1:o_clip])
+        if rects is not None:
+            h[o_clip:] = rects.reshape(-1)
+        buf = host.to(dev, non_blocking=True)
+        a = L.FillPolygonsArgs()
+        base = buf.data_ptr()
+        a.vertices, a.poly_offsets, a.plane_offsets = base, base + 4 * o_poly, base + 4 * o_plane
+        a.clip = base + 4 * o_clip if rects is not None else None
+        a.out, a.area, a.box = out.data_ptr(), area.data_ptr() if records else None, box.data_ptr() if records else None
+        a.n, a.n_polys, a.n_vertices, a.H, a.W, a.pitch = n, n_polys, n_vertices, H, W, pitch
+        with torch.cuda.device(dev):
+            L.check(lib.mtbt_fill_polygons(C.byref(a), _stream(dev)), "mtbt_fill_polygons")   # buf is freed in stream order, after the launch
+    return (out, area, box.float()) if records else out
+
+
+def yolo_seg_planes(rows: Sequence[Sequence[float]], H0: int, W0: int, device=None):
+    """YOLO-seg label rows (cls, x1, y1, x2, y2, ... normalised to the ORIGINAL image) -> (packed uint8 [G, H0, pitch], labels int64
+    [G]) on the device: one plane per row in the image's own pixels, vertices at (x * W0, y * H0), filled by `fill_polygons`.  Rows of
+    fewer than 3 points are skipped.  The per-image ground truth `DeviceMaskMeanAveragePrecision.update_batched` and
+    `SurfaceDistanceMetrics.update_packed` take."""
+    polys, labels = [], []
+    for r in rows:
+        pts = [float(v) for v in r[1:]]
+        k = len(pts) // 2
+        if k < 3:
+            continue
+        v = np.asarray(pts[:2 * k], dtype=np.float64).reshape(k, 2)
+        polys.append(v * np.asarray([float(W0), float(H0)]))
+        labels.append(int(r[0]))
+    packed = fill_polygons(polys, H0, W0, device=device)
+    labels = torch.tensor(labels, dtype=torch.int64)
+    return packed, (labels.pin_memory().to(packed.device, non_blocking=True) if labels.numel() else labels.to(packed.device))

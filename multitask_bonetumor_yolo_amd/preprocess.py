@@ -376,6 +376,160 @@ def mosaic_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Opti
     return imgs, out_masks, collate_boxes(rows, device=imgs.device)
 
 
+# ---- polygon labels (YOLO-seg rows) under the same augmentation: vertices moved on the host, rasterised at the canvas resolution ----
+def _shoelace(pts) -> float:
+    """Signed area of a closed polygon given as a list of (x, y)."""
+    a = 0.0
+    for i in range(len(pts)):
+        (x1, y1), (x2, y2) = pts[i], pts[(i + 1) % len(pts)]
+        a += x1 * y2 - x2 * y1
+    return a / 2
+
+
+def _clip_polygon(pts, rect):
+    """Sutherland-Hodgman: the polygon (list of (x, y)) clipped to the rectangle (x0, y0, x1, y1); a point put on a clip line carries
+    that line's coordinate exactly."""
+    rx0, ry0, rx1, ry1 = rect
+    for axis, bound, keep_ge in ((0, rx0, True), (0, rx1, False), (1, ry0, True), (1, ry1, False)):
+        if not pts:
+            break
+        inside = (lambda q: q[axis] >= bound) if keep_ge else (lambda q: q[axis] <= bound)
+        out = []
+        for i in range(len(pts)):
+            a, b = pts[i - 1], pts[i]
+            if inside(a) != inside(b):
+                t = (bound - a[axis]) / (b[axis] - a[axis])
+                other = a[1 - axis] + (b[1 - axis] - a[1 - axis]) * t
+                out.append((bound, other) if axis == 0 else (other, bound))
+            if inside(b):
+                out.append(b)
+        pts = out
+    return pts
+
+
+def augment_polygons(rows: Sequence[Sequence[float]], W0: int, H0: int, geom_row, img_size: int, *, min_px: float = 2.0,
+                     min_area_ratio: float = 0.1, max_aspect: float = 100.0, clip_rect=None):
+    """YOLO-seg rows (cls, x1, y1, x2, y2, ... normalised to the ORIGINAL image) -> a list of (row6, vertices) on the augmented S x S
+    canvas of `augment_batch` under geom_row.  Every vertex goes through exactly the map `augment_yolo_labels` applies to box corners
+    (times new / old per axis, transpose swap, x -> qw - x, y -> qh - y, plus the offsets; Python floats).  `vertices` is float64
+    [n, 2] in canvas pixels, NOT clipped: the rasteriser clips (`postprocess.fill_polygons`).  row6 = [0.0, cls, cx, cy, w, h],
+    normalised by S, is the bounding box of the polygon clipped (Sutherland-Hodgman) to clip_rect, or to [0, S]^2 when that is None.
+    A polygon is dropped when it has fewer than 3 vertices or zero area, when a clipped box side is < min_px, when
+    |area of the clipped polygon| / |area of the polygon| <= min_area_ratio (shoelace), or when the box side ratio is >= max_aspect:
+    the rules of `augment_yolo_labels`, which a rectangle given as four vertices reproduces."""
+    new_w, new_h, off_x, off_y, orient = (int(v) for v in geom_row[:5])
+    qw, qh = (new_h, new_w) if orient & 4 else (new_w, new_h)
+    kx, ky, S = new_w / W0, new_h / H0, float(img_size)
+    rect = (0.0, 0.0, S, S) if clip_rect is None else tuple(float(v) for v in clip_rect)
+    out = []
+    for r in rows:
+        n = (len(r) - 1) // 2
+        if n < 3:
+            continue
+        cls = float(r[0])
+        pts = []
+        for i in range(n):
+            x, y = float(r[1 + 2 * i]) * W0 * kx, float(r[2 + 2 * i]) * H0 * ky
+            if orient & 4:
+                x, y = y, x
+            if orient & 1:
+                x = qw - x
+            if orient & 2:
+                y = qh - y
+            pts.append((x + off_x, y + off_y))
+        area = abs(_shoelace(pts))
+        if not area > 0.0:
+            continue
+        cl = _clip_polygon(pts, rect)
+        if len(cl) < 3:
+            continue
+        cx1, cx2 = min(q[0] for q in cl), max(q[0] for q in cl)
+        cy1, cy2 = min(q[1] for q in cl), max(q[1] for q in cl)
+        cw, ch = cx2 - cx1, cy2 - cy1
+        if cw < min_px or ch < min_px or cw <= 0.0 or ch <= 0.0:
+            continue
+        if abs(_shoelace(cl)) / area <= min_area_ratio:
+            continue
+        if max(cw / ch, ch / cw) >= max_aspect:
+            continue
+        out.append(([0.0, cls, (cx1 + cx2) / 2 / S, (cy1 + cy2) / 2 / S, cw / S, ch / S], np.asarray(pts, dtype=np.float64).reshape(n, 2)))
+    return out
+
+
+def mosaic_polygons(rows_per_tile: Sequence[Sequence[Sequence[float]]], sizes_per_tile: Sequence[Sequence[int]], geom4, centre, img_size: int, *,
+                    min_px: float = 2.0, min_area_ratio: float = 0.1, max_aspect: float = 100.0):
+    """The polygons of one mosaic canvas: `augment_polygons` per tile, clipped to the tile's rectangle (`tile_rects`), the four tiles
+    concatenated in tile order -> a list of (row6, vertices, rect); `rect` is what the rasteriser clips that polygon's plane to."""
+    if not (len(rows_per_tile) == len(sizes_per_tile) == len(geom4) == 4):
+        raise ValueError("mosaic_polygons: four tiles per canvas")
+    out = []
+    for rows, (H0, W0), g, rect in zip(rows_per_tile, sizes_per_tile, geom4, tile_rects(centre, img_size)):
+        out += [(row6, v, rect) for row6, v in augment_polygons(rows, W0, H0, g, img_size, min_px=min_px, min_area_ratio=min_area_ratio,
+                                                                max_aspect=max_aspect, clip_rect=rect)]
+    return out
+
+
+def _upload(t: torch.Tensor, dev) -> torch.Tensor:
+    """A host tensor -> the device through pinned memory, asynchronously: the host does not wait for the stream."""
+    return t.pin_memory().to(dev, non_blocking=True) if t.numel() else t.to(dev)
+
+
+def _seg_outputs(per_canvas, canvas_rects, img_size: int, dev):
+    """per_canvas: for every canvas its list of (row6, vertices, rect); canvas_rects: for every canvas the G rectangles its polygons are
+    clipped to (one for a plain canvas, the four tiles of a mosaic) -> (masks [B,1,S,S], gt_rows [M,6], inst) of the `*_samples_seg`
+    functions: one fill for the M instance planes, one for the B x G unions of the polygons that share a rectangle."""
+    from .postprocess import fill_polygons, unpack_masks
+    S, B, G = int(img_size), len(per_canvas), len(canvas_rects[0])
+    items = [(i, it) for i, canvas in enumerate(per_canvas) for it in canvas]
+    gt_rows = _upload(collate_boxes([[it[0] for it in canvas] for canvas in per_canvas]), dev)
+    planes = fill_polygons([it[1] for _, it in items], S, S, clip=np.asarray([it[2] for _, it in items], dtype=np.int32).reshape(-1, 4), device=dev)
+    inst = {"planes": planes, "image": _upload(torch.tensor([i for i, _ in items], dtype=torch.int64), dev),
+            "labels": _upload(torch.tensor([int(it[0][1]) for _, it in items], dtype=torch.int64), dev)}
+    groups = [[it[1] for it in canvas if tuple(it[2]) == tuple(rect)] for canvas, rects in zip(per_canvas, canvas_rects) for rect in rects]
+    union = fill_polygons(groups, S, S, clip=np.asarray(canvas_rects, dtype=np.int32).reshape(-1, 4), device=dev).view(B, G, S, -1)
+    merged = union[:, 0]
+    for g in range(1, G):
+        merged = merged | union[:, g]
+    return unpack_masks(merged, S).to(torch.float32).unsqueeze(1), gt_rows, inst
+
+
+def augment_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int,
+                        rng: np.random.Generator, **ranges):
+    """`augment_samples` for polygon labels: seg_rows_per_image holds YOLO-seg rows (cls, x1, y1, x2, y2, ...) per image.  The generator
+    is consumed exactly as `augment_samples` consumes it (the same seed gives the same `imgs`, bit for bit); the image work is
+    `augment_batch` without masks; the vertices are moved on the host (`augment_polygons`) and rasterised at the canvas resolution
+    (`postprocess.fill_polygons`).  Returns (imgs [B,3,S,S], masks [B,1,S,S] float32 {0,1}: the union of each canvas's surviving
+    polygons, gt_rows [M,6] on the device, inst = dict(planes uint8 [M,S,pitch], image int64 [M], labels int64 [M]), row for row with
+    gt_rows).  Nothing synchronises with the host."""
+    geo, pho, lab = _split(ranges, "augment_samples_seg", ("scale", "aspect", "fliplr", "flipud", "transpose", "place"))
+    if len(seg_rows_per_image) != len(images):
+        raise ValueError("augment_samples_seg: one list of label rows per image")
+    sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+    geom = sample_geometry(sizes, img_size, rng, **geo)
+    lut = _upload(torch.from_numpy(sample_photometric(len(images), rng, **pho)), images[0].device)
+    imgs, _ = augment_batch(images, None, geom, lut, img_size)
+    whole = (0, 0, int(img_size), int(img_size))
+    per_canvas = [[(row6, v, whole) for row6, v in augment_polygons(r, W0, H0, geom[i], img_size, **lab)]
+                  for i, (r, (H0, W0)) in enumerate(zip(seg_rows_per_image, sizes))]
+    return (imgs,) + _seg_outputs(per_canvas, [[whole]] * len(images), img_size, imgs.device)
+
+
+def mosaic_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int,
+                       rng: np.random.Generator, **ranges):
+    """`mosaic_samples` for polygon labels, as `augment_samples_seg` is to `augment_samples`: the same draws, `mosaic_batch` without
+    masks, `mosaic_polygons` per canvas.  Every instance plane is clipped to its tile, and so is its share of the canvas mask."""
+    geo, pho, lab = _split(ranges, "mosaic_samples_seg", ("prob", "centre", "scale", "aspect", "fliplr", "flipud", "transpose"))
+    if len(seg_rows_per_image) != len(images):
+        raise ValueError("mosaic_samples_seg: one list of label rows per image")
+    sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+    index, geom, centres = sample_mosaic(sizes, img_size, rng, **geo)
+    lut = _upload(torch.from_numpy(sample_photometric(len(images), rng, **pho)), images[0].device)
+    imgs, _ = mosaic_batch(images, None, index, geom, centres, lut, img_size)
+    per_canvas = [mosaic_polygons([seg_rows_per_image[k] for k in index[i]], [sizes[k] for k in index[i]], geom[i], centres[i], img_size, **lab)
+                  for i in range(len(images))]
+    return (imgs,) + _seg_outputs(per_canvas, [tile_rects(c, img_size) for c in centres], img_size, imgs.device)
+
+
 # ---- sliced inference: overlapping tiles of a large image (the project's own definition: include/mtbt_hip.h `mtbt_tile`) ----
 def _axis_origins(L: int, S: int, overlap: float, up: int) -> List[int]:
     """Tile origins along an axis of resized length L: one at 0 if L <= S, else ceil((L - S overlap) / (S (1 - overlap))) spread evenly
