@@ -955,6 +955,53 @@ int mtbt_mosaic_batch(const mtbt_raw_image* tiles /* HOST [4*count], canvas-majo
                       const int32_t* centres /* HOST [count][2] = cx, cy */, const uint8_t* lut /* DEVICE [count][3][256] or NULL */,
                       float* out_images, float* out_masks /* NULL = skip */, void* stream);
 
+/* Contrast-limited adaptive histogram equalisation of raw uint8 images on the device (csrc/clahe.hip; `preprocess.clahe_batch`, the
+ * `clahe=` option of the `*_samples` functions), ahead of the resampling entry points above and independent of them.  The reference
+ * equalises nothing; cv2 is absent here, so THE RULE below is this project's own definition, modelled step for step on cv2's CLAHE
+ * (modules/imgproc/src/clahe.cpp) and exact in integers (tests/clahe_reference.py restates it in numpy).  It differs from cv2 in two
+ * places, where cv2 rounds through float32 (the curve's scale 255 / area and the bilinear blend) and this rule rounds the exact rational:
+ * a difference from cv2 of at most one grey level at a few pixels is expected and has not been measured.
+ * Per image: H x W, channels 1 or 3 (interleaved, as cv2.imread returns them), a grid gx x gy, an integer clip >= 0.
+ *   Key            one channel: k = v.  Three channels: k = (c0 + 2 c1 + c2 + 2) >> 2.  ONE curve is built from k and applied to each
+ *                  channel value, so a grey image stored as three equal channels stays grey and equals the one-channel result.
+ *   Tiles          tw = ceil(W / gx), th = ceil(H / gy), area = tw th.  The image is extended on the right and bottom to gx tw x gy th by
+ *                  reflection without repeating the edge (index i >= n reads 2 (n - 1) - i); the extension is never materialised.  Tile
+ *                  (i, j) covers [i tw, (i + 1) tw) x [j th, (j + 1) th) of the extended image; hist[b] counts its keys and sums to area.
+ *   Clip           skipped when clip == 0.  excess = sum max(hist[b] - clip, 0); hist[b] = min(hist[b], clip); hist[b] += excess / 256
+ *                  for all b; r = excess % 256; if r > 0: step = max(256 / r, 1) and hist[j step] += 1 for j = 0 .. r - 1 (the closed
+ *                  form of cv2's loop).  The counts still sum to area.
+ *   Curve          cdf[b] = sum of hist[b'] over b' <= b; lut[b] = (510 cdf[b] + area) / (2 area), integer division: 255 cdf / area
+ *                  rounded half up, so lut[255] = 255.
+ *   Interpolation  column x: u = 2 x + 1 - tw, t1 = floor(u / 2 tw) (may be -1), a = u - t1 2 tw in [0, 2 tw); weights (2 tw - a, a)
+ *                  on tiles (clamp(t1), clamp(t1 + 1)), clamped to [0, gx - 1]; rows the same with th and gy.
+ *                  out = (sum over the four tiles of wy wx lut_tile[v] + 2 tw th) / (4 tw th): the exact rational of cv2's bilinear
+ *                  blend between tile centres, rounded half up.  With area <= 2^22 the sum fits uint32.
+ *   Host           clip = 0 if clip_limit <= 0 else max(1, int(clip_limit * area / 256)) in double arithmetic is cv2's formula
+ *                  (`preprocess.clahe_clip`); the library sees only the integer.
+ * images: HOST array of DEVICE buffers; sizes and channel counts may be mixed within a batch.  dst == src with equal strides is allowed
+ * (each output byte depends on the input only at its own place plus the finished curves).  Every byte of the width * channels bytes of
+ * each destination row is written; stride padding is never touched.  Workspace: mtbt_clahe_workspace_bytes(...) bytes of DEVICE memory,
+ * 16-byte aligned (int32 histograms, cleared on the stream by the entry point, then the curves); two calls on one stream may share it.
+ * Asynchronous on `stream`, no host synchronisation, graph-capturable; integer arithmetic and integer atomics only, so the result is a
+ * pure function of the input.  Three launches (histograms, curves, apply) per <= 32 images.
+ * Order of the checks as in mtbt_letterbox_batch: (1) MTBT_EINVAL with every item checked, so before any launch: NULL images / src /
+ * dst, count < 0, grid_x or grid_y outside [1, 16], channels not 1 or 3, height < grid_y or width < grid_x, clip < 0, a stride below
+ * width * channels, height * stride >= 2^31 - 1, area > 2^22, a workspace that is NULL or smaller than mtbt_clahe_workspace_bytes when
+ * that is positive, a destination that overlaps a source of the call other than exactly its own (dst == src, equal strides); (2) then
+ * MTBT_EALIGN for a workspace not 16-byte aligned; (3) then the first launch.  count == 0 is MTBT_OK with nothing launched.
+ * mtbt_clahe_workspace_bytes returns MTBT_EINVAL for count < 0, a grid outside [1, 16] or NULL images with count > 0. */
+typedef struct mtbt_clahe_image { /* HOST array, DEVICE buffers */
+  const uint8_t* src;
+  uint8_t* dst;
+  int32_t height, width, channels, clip;
+  int64_t src_row_stride, dst_row_stride; /* bytes, >= width * channels */
+} mtbt_clahe_image;
+int64_t mtbt_clahe_workspace_bytes(const mtbt_clahe_image* images, int count, int grid_x, int grid_y);
+int mtbt_clahe_batch(const mtbt_clahe_image* images, int count, int grid_x, int grid_y, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+/* sizeof() of the struct above as the library was compiled: which = 0 mtbt_clahe_image; -1 otherwise */
+int mtbt_sizeof_clahe_args(int which);
+
 /* Segmentation metric accumulators (running_main_v3.py:466-498 feeding the torchmetrics objects of :198-203), SURVEY §8f N3.
  * logits, gt: [B][n_per_image] f32 (n % 4 == 0); prediction = sigmoid(logit) > 0.5, target = int(gt) >= 1.
  * counts [B][4] int64 = TP, FP, FN, TN per image; prob_sum [B] = sum of sigmoid(logit) over predicted-foreground pixels

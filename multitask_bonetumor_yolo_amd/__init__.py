@@ -18,14 +18,15 @@
     from multitask_bonetumor_yolo_amd import SurfaceDistanceMetrics      # Hausdorff / HD95 / ASSD / surface Dice from packed masks, on the device
     from multitask_bonetumor_yolo_amd import label_components, LesionMetrics   # connected components of packed masks; lesion-wise recall / precision
     from multitask_bonetumor_yolo_amd import fill_polygons, yolo_seg_planes, augment_samples_seg   # polygon labels -> packed instance masks
+    from multitask_bonetumor_yolo_amd import clahe_batch                 # tile-wise contrast equalisation (CLAHE) of the raw uint8 images
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
 """
 from . import postprocess, preprocess  # noqa: F401
-from .preprocess import (augment_batch, augment_polygons, augment_samples, augment_samples_seg, augment_yolo_labels, letterbox_geometry,  # noqa: F401
-                         mosaic_batch, mosaic_polygons, mosaic_samples, mosaic_samples_seg, mosaic_yolo_labels, photometric_lut,
-                         sample_geometry, sample_mosaic, sample_photometric, slice_batch, slice_geometry)
+from .preprocess import (augment_batch, augment_polygons, augment_samples, augment_samples_seg, augment_yolo_labels, clahe_batch, clahe_clip,  # noqa: F401
+                         letterbox_geometry, mosaic_batch, mosaic_polygons, mosaic_samples, mosaic_samples_seg, mosaic_yolo_labels, photometric_lut,
+                         sample_clahe, sample_geometry, sample_mosaic, sample_photometric, slice_batch, slice_geometry)
 from .loss import InstanceMaskLoss, TaskAlignedDetLoss, TaskAlignedSegLoss, instance_mask_loss, multitask_loss, task_aligned_det_loss  # noqa: F401
 from .checkpoints import load_pretrained_heads, load_train_state, save_train_state, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401

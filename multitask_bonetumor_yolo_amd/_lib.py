@@ -240,6 +240,11 @@ class FillPolygonsArgs(C.Structure):  # mtbt_fill_polygons_args
                 ("n", C.c_int32), ("n_polys", C.c_int32), ("n_vertices", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32)]
 
 
+class ClaheImage(C.Structure):  # mtbt_clahe_image
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("clip", C.c_int32),
+                ("src_row_stride", C.c_int64), ("dst_row_stride", C.c_int64)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -378,6 +383,9 @@ SYMBOLS = {
     "mtbt_sizeof_components_args": (C.c_int, [C.c_int]),
     "mtbt_fill_polygons": (C.c_int, [C.POINTER(FillPolygonsArgs), C.c_void_p]),
     "mtbt_sizeof_fill_polygons_args": (C.c_int, [C.c_int]),
+    "mtbt_clahe_workspace_bytes": (C.c_int64, [C.POINTER(ClaheImage), C.c_int, C.c_int, C.c_int]),
+    "mtbt_clahe_batch": (C.c_int, [C.POINTER(ClaheImage), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "mtbt_sizeof_clahe_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -387,6 +395,7 @@ TILE_STRUCTS = (Tile, TileMergeArgs, TileMaskArgs)   # order of mtbt_sizeof_tile
 SURFACE_STRUCTS = (SurfaceArgs,)   # order of mtbt_sizeof_surface_args(which)
 COMPONENTS_STRUCTS = (ComponentsArgs, SelectComponentsArgs)   # order of mtbt_sizeof_components_args(which)
 POLYGON_STRUCTS = (FillPolygonsArgs,)   # order of mtbt_sizeof_fill_polygons_args(which)
+CLAHE_STRUCTS = (ClaheImage,)   # order of mtbt_sizeof_clahe_args(which)
 _lib = None
 
 
@@ -410,7 +419,8 @@ def load():
                                    f"{C.sizeof(st)} bytes: stale library, rebuild")
         for sizeof, structs in ((lib.mtbt_sizeof_frame_args, FRAME_STRUCTS), (lib.mtbt_sizeof_mask_eval_args, MASK_EVAL_STRUCTS),
                                 (lib.mtbt_sizeof_tile_args, TILE_STRUCTS), (lib.mtbt_sizeof_surface_args, SURFACE_STRUCTS),
-                                (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS), (lib.mtbt_sizeof_fill_polygons_args, POLYGON_STRUCTS)):
+                                (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS), (lib.mtbt_sizeof_fill_polygons_args, POLYGON_STRUCTS),
+                                (lib.mtbt_sizeof_clahe_args, CLAHE_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

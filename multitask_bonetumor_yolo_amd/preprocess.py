@@ -13,6 +13,9 @@ chosen by the caller; the parameters are drawn and the labels moved on the host.
 The four-image mosaic (`mosaic_batch` and the functions after it, include/mtbt_hip.h `mtbt_mosaic_batch`) is the same arithmetic
 with the source picked per canvas region: a centre cuts the canvas into four rectangles, each showing its own image under its own
 geometry row; with the centre at (S, S) a canvas is the plain augmentation of its first tile.
+
+`clahe_batch` (include/mtbt_hip.h `mtbt_clahe_batch`) equalises the raw uint8 images tile-wise at their own resolution before any of
+the above: the project's own integer rule, modelled on cv2's CLAHE, which the reference does not use either.
 """
 import ctypes as C
 import math
@@ -146,8 +149,105 @@ def collate_boxes(per_sample_rows: Sequence[Sequence[Sequence[float]]], device=N
     return t.to(device) if device is not None else t
 
 
+# ---- contrast-limited adaptive histogram equalisation of the raw images (the project's own definition, modelled on cv2's CLAHE) ----
+def _grid(grid, who: str):
+    gx, gy = (int(v) for v in grid)
+    if not (1 <= gx <= 16 and 1 <= gy <= 16):
+        raise ValueError(f"{who}: grid = (gx, gy) must lie in [1, 16] per axis")
+    return gx, gy
+
+
+def clahe_clip(clip_limit: float, H: int, W: int, grid=(8, 8)) -> int:
+    """cv2's integer clip of a `clipLimit` for an H x W image on a (gx, gy) grid: 0 (no clipping) if clip_limit <= 0, else
+    max(1, int(clip_limit * area / 256)) with area = ceil(W / gx) * ceil(H / gy), in Python floats.  This integer is all the library sees."""
+    gx, gy = _grid(grid, "clahe_clip")
+    area = -(-int(W) // gx) * -(-int(H) // gy)
+    return 0 if clip_limit <= 0 else max(1, int(float(clip_limit) * area / 256))
+
+
+def _row_strided(t: torch.Tensor) -> bool:
+    """Pixels of a row contiguous and the rows apart by at least a row: what the library addresses without a copy."""
+    ch = 1 if t.dim() == 2 else 3
+    inner = t.stride(1) == 1 if t.dim() == 2 else (t.stride(2) == 1 and t.stride(1) == 3)
+    return inner and (t.shape[0] == 1 or t.stride(0) >= t.shape[1] * ch)
+
+
+def clahe_batch(images: Sequence[torch.Tensor], clip_limit=2.0, grid=(8, 8), out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
+    """Contrast-limited adaptive histogram equalisation of raw images at their own resolution, on the device (include/mtbt_hip.h
+    `mtbt_clahe_batch` states the rule: this project's own, modelled step for step on cv2's `createCLAHE(clipLimit, tileGridSize)`).
+    images: uint8 [H, W] or [H, W, 3] CUDA tensors of any sizes, mixed freely, row-strided views included (anything else is copied);
+    a three-channel image gets ONE curve per tile, built from (c0 + 2 c1 + c2 + 2) >> 2 and applied to each channel.  clip_limit: a
+    scalar or one value per image (<= 0 equalises without clipping); None for an image returns that tensor itself, untouched.
+    grid = (gx, gy) tiles per axis, each in [1, 16] and no more than the image has pixels on that axis.  out: None (new tensors) or one
+    uint8 CUDA tensor per image of the image's shape, row-strided, written in its first W * channels bytes per row only; `out=images`
+    works in place.  Returns the list of equalised tensors.  Three launches per <= 32 images, asynchronous, no CPU path."""
+    lib = L.load()
+    B = len(images)
+    if B == 0:
+        raise ValueError("clahe_batch: empty batch")
+    gx, gy = _grid(grid, "clahe_batch")
+    limits = list(clip_limit) if isinstance(clip_limit, (list, tuple, np.ndarray)) else [clip_limit] * B
+    if len(limits) != B or (out is not None and len(out) != B):
+        raise ValueError("clahe_batch: one clip limit and one output per image")
+    result, keep, items = list(images), [], []
+    dev = images[0].device
+    for i, im in enumerate(images):
+        if limits[i] is None:
+            continue
+        if not isinstance(im, torch.Tensor) or not im.is_cuda or im.device != dev:
+            raise RuntimeError("clahe_batch: expected CUDA/HIP tensors on one MI355X (no CPU path)")
+        if im.dtype != torch.uint8 or not (im.dim() == 2 or (im.dim() == 3 and im.shape[2] == 3)):
+            raise ValueError("clahe_batch: images must be uint8 [H, W] or [H, W, 3]")
+        H, W = int(im.shape[0]), int(im.shape[1])
+        if H < gy or W < gx:
+            raise ValueError(f"clahe_batch: image {i} ({H} x {W}) has fewer pixels than the grid {gx} x {gy} has tiles")
+        dst = torch.empty(tuple(im.shape), device=dev, dtype=torch.uint8) if out is None else out[i]
+        if out is not None and (not isinstance(dst, torch.Tensor) or not dst.is_cuda or dst.device != dev or dst.dtype != torch.uint8
+                                or tuple(dst.shape) != tuple(im.shape) or not _row_strided(dst)):
+            raise ValueError(f"clahe_batch: out[{i}] must be a row-strided CUDA uint8 tensor of the image's shape")
+        src = im if _row_strided(im) else im.contiguous()
+        keep += [src, dst]
+        items.append((src, dst, clahe_clip(float(limits[i]), H, W, (gx, gy))))
+        result[i] = dst
+    if not items:
+        return result
+    n = len(items)
+    descs = (L.ClaheImage * n)()
+    for d, (src, dst, clip) in zip(descs, items):
+        d.src, d.dst, d.height, d.width, d.channels, d.clip = src.data_ptr(), dst.data_ptr(), src.shape[0], src.shape[1], 1 if src.dim() == 2 else 3, clip
+        d.src_row_stride = src.stride(0) if src.shape[0] > 1 else src.shape[1] * d.channels
+        d.dst_row_stride = dst.stride(0) if dst.shape[0] > 1 else dst.shape[1] * d.channels
+    nbytes = int(lib.mtbt_clahe_workspace_bytes(descs, n, gx, gy))
+    if nbytes < 0:
+        L.check(nbytes, "mtbt_clahe_workspace_bytes")
+    workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    stream = torch.cuda.current_stream(dev)
+    L.check(lib.mtbt_clahe_batch(descs, n, gx, gy, workspace.data_ptr(), nbytes, C.c_void_p(stream.cuda_stream)), "mtbt_clahe_batch")
+    for t in keep:   # the launches are asynchronous: keep the buffers alive until the stream has consumed them
+        t.record_stream(stream)
+    return result
+
+
+def sample_clahe(B: int, rng: np.random.Generator, *, prob: float = 0.5, clip=(1.0, 4.0)) -> list:
+    """Draw, per image, whether it is equalised (probability prob) and its clip limit ~ U(clip): a list of B floats or None, the
+    `clip_limit` of `clahe_batch`.  Two vectors of B draws in that order whatever prob is, so a seeded generator gives the same list again."""
+    on = rng.random(B) < prob
+    c = rng.uniform(clip[0], clip[1], B)
+    return [float(c[i]) if on[i] else None for i in range(B)]
+
+
+def _equalised(images, rng: np.random.Generator, clahe: Optional[dict]):
+    """The `clahe=dict(prob=, clip=, grid=)` option of the `*_samples` functions: every source image is equalised at most once, at its own
+    resolution, before any resampling; the draws (`sample_clahe`) are the last ones.  None draws nothing and returns the images."""
+    if clahe is None:
+        return images
+    opts = dict(clahe)
+    grid = opts.pop("grid", (8, 8))
+    return clahe_batch(images, sample_clahe(len(images), rng, **opts), grid)
+
+
 # ---- training augmentation (the project's own definition: the reference has none) ------------------------------------------
-GEOM_FIELDS = 8   # new_w, new_h, off_x, off_y, orient (bit 0 flip x, bit 1 flip y, bit 2 transpose), 3 reserved zeros
+GEOM_FIELDS = 8  # new_w, new_h, off_x, off_y, orient (bit 0 flip x, bit 1 flip y, bit 2 transpose), 3 reserved zeros
 
 
 def augment_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]], geom, lut: Optional[torch.Tensor] = None,
@@ -266,14 +366,17 @@ def augment_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Opt
                     rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int, rng: np.random.Generator, **ranges):
     """Draw geometry and intensity, run `augment_batch`, move the labels: (imgs [B,3,S,S], masks [B,1,S,S], gt_rows [M,6] on the
     device, batch index in column 0) -- what `TrainStep.step` takes.  `ranges` are the keyword arguments of `sample_geometry`,
-    `sample_photometric` and `augment_yolo_labels`; anything else is an error."""
+    `sample_photometric` and `augment_yolo_labels`, plus clahe=dict(prob=, clip=, grid=) (`sample_clahe`, `clahe_batch`: the sources are
+    equalised at their own resolution before the resample; its draws come last, so geometry, tables and labels are the same with and
+    without it, and None -- the default -- draws nothing); anything else is an error."""
+    clahe = ranges.pop("clahe", None)
     geo, pho, lab = _split(ranges, "augment_samples", ("scale", "aspect", "fliplr", "flipud", "transpose", "place"))
     if len(rows_per_image) != len(images):
         raise ValueError("augment_samples: one list of label rows per image")
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
     geom = sample_geometry(sizes, img_size, rng, **geo)
     lut = torch.from_numpy(sample_photometric(len(images), rng, **pho)).to(images[0].device)
-    imgs, out_masks = augment_batch(images, masks, geom, lut, img_size)
+    imgs, out_masks = augment_batch(_equalised(images, rng, clahe), masks, geom, lut, img_size)
     rows = [augment_yolo_labels(r, W0, H0, geom[i], img_size, **lab) for i, (r, (H0, W0)) in enumerate(zip(rows_per_image, sizes))]
     return imgs, out_masks, collate_boxes(rows, device=imgs.device)
 
@@ -362,15 +465,17 @@ def mosaic_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Opti
                    rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int, rng: np.random.Generator, **ranges):
     """`augment_samples` with four images per canvas: draw `sample_mosaic`, then `sample_photometric` (one table per canvas) from the one
     generator, run `mosaic_batch`, move the labels with `mosaic_yolo_labels`: (imgs [B,3,S,S], masks [B,1,S,S], gt_rows [M,6] on the
-    device, batch index = canvas in column 0) -- what `TrainStep.step` takes.  `ranges` are the keyword arguments of those three functions;
-    anything else is an error."""
+    device, batch index = canvas in column 0) -- what `TrainStep.step` takes.  `ranges` are the keyword arguments of those three functions,
+    plus clahe=dict(prob=, clip=, grid=) as in `augment_samples` (one draw per IMAGE, each equalised at most once however many tiles show
+    it); anything else is an error."""
+    clahe = ranges.pop("clahe", None)
     geo, pho, lab = _split(ranges, "mosaic_samples", ("prob", "centre", "scale", "aspect", "fliplr", "flipud", "transpose"))
     if len(rows_per_image) != len(images):
         raise ValueError("mosaic_samples: one list of label rows per image")
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
     index, geom, centres = sample_mosaic(sizes, img_size, rng, **geo)
     lut = torch.from_numpy(sample_photometric(len(images), rng, **pho)).to(images[0].device)
-    imgs, out_masks = mosaic_batch(images, masks, index, geom, centres, lut, img_size)
+    imgs, out_masks = mosaic_batch(_equalised(images, rng, clahe), masks, index, geom, centres, lut, img_size)
     rows = [mosaic_yolo_labels([rows_per_image[k] for k in index[i]], [sizes[k] for k in index[i]], geom[i], centres[i], img_size, **lab)
             for i in range(len(images))]
     return imgs, out_masks, collate_boxes(rows, device=imgs.device)
@@ -500,14 +605,15 @@ def augment_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Sequ
     `augment_batch` without masks; the vertices are moved on the host (`augment_polygons`) and rasterised at the canvas resolution
     (`postprocess.fill_polygons`).  Returns (imgs [B,3,S,S], masks [B,1,S,S] float32 {0,1}: the union of each canvas's surviving
     polygons, gt_rows [M,6] on the device, inst = dict(planes uint8 [M,S,pitch], image int64 [M], labels int64 [M]), row for row with
-    gt_rows).  Nothing synchronises with the host."""
+    gt_rows).  clahe=dict(prob=, clip=, grid=) as in `augment_samples`.  Nothing synchronises with the host."""
+    clahe = ranges.pop("clahe", None)
     geo, pho, lab = _split(ranges, "augment_samples_seg", ("scale", "aspect", "fliplr", "flipud", "transpose", "place"))
     if len(seg_rows_per_image) != len(images):
         raise ValueError("augment_samples_seg: one list of label rows per image")
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
     geom = sample_geometry(sizes, img_size, rng, **geo)
     lut = _upload(torch.from_numpy(sample_photometric(len(images), rng, **pho)), images[0].device)
-    imgs, _ = augment_batch(images, None, geom, lut, img_size)
+    imgs, _ = augment_batch(_equalised(images, rng, clahe), None, geom, lut, img_size)
     whole = (0, 0, int(img_size), int(img_size))
     per_canvas = [[(row6, v, whole) for row6, v in augment_polygons(r, W0, H0, geom[i], img_size, **lab)]
                   for i, (r, (H0, W0)) in enumerate(zip(seg_rows_per_image, sizes))]
@@ -517,14 +623,16 @@ def augment_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Sequ
 def mosaic_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int,
                        rng: np.random.Generator, **ranges):
     """`mosaic_samples` for polygon labels, as `augment_samples_seg` is to `augment_samples`: the same draws, `mosaic_batch` without
-    masks, `mosaic_polygons` per canvas.  Every instance plane is clipped to its tile, and so is its share of the canvas mask."""
+    masks, `mosaic_polygons` per canvas.  Every instance plane is clipped to its tile, and so is its share of the canvas mask.
+    clahe=dict(prob=, clip=, grid=) as in `mosaic_samples`."""
+    clahe = ranges.pop("clahe", None)
     geo, pho, lab = _split(ranges, "mosaic_samples_seg", ("prob", "centre", "scale", "aspect", "fliplr", "flipud", "transpose"))
     if len(seg_rows_per_image) != len(images):
         raise ValueError("mosaic_samples_seg: one list of label rows per image")
     sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
     index, geom, centres = sample_mosaic(sizes, img_size, rng, **geo)
     lut = _upload(torch.from_numpy(sample_photometric(len(images), rng, **pho)), images[0].device)
-    imgs, _ = mosaic_batch(images, None, index, geom, centres, lut, img_size)
+    imgs, _ = mosaic_batch(_equalised(images, rng, clahe), None, index, geom, centres, lut, img_size)
     per_canvas = [mosaic_polygons([seg_rows_per_image[k] for k in index[i]], [sizes[k] for k in index[i]], geom[i], centres[i], img_size, **lab)
                   for i in range(len(images))]
     return (imgs,) + _seg_outputs(per_canvas, [tile_rects(c, img_size) for c in centres], img_size, imgs.device)
