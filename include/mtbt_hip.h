@@ -955,6 +955,42 @@ int mtbt_mosaic_batch(const mtbt_raw_image* tiles /* HOST [4*count], canvas-majo
                       const int32_t* centres /* HOST [count][2] = cx, cy */, const uint8_t* lut /* DEVICE [count][3][256] or NULL */,
                       float* out_images, float* out_masks /* NULL = skip */, void* stream);
 
+/* Affine augmentation on the device (csrc/warp_affine.hip; `preprocess.warp_batch`, `affine_samples`): rotation by any angle, shear, and
+ * with them every 2 x 3 map, one canvas per source.  The reference augments nothing and cv2 is absent here, so THE RULE below is this
+ * project's own definition, modelled on cv2's warpAffine(INTER_LINEAR) -- an inverse map in fixed point, a position reduced to 1/32 pixel,
+ * 2 x 2 taps -- and exact in integers (tests/warp_reference.py restates it in numpy).  It has a kernel of its own: the two entry points above
+ * rest on separable taps (a canvas row is a row or a column of the source), and a rotated row is neither.
+ * Per canvas i: a source descriptor images[i] (H0 x W0) and a row coef[i] = (a, b, c, d, e, f, 0, 0) of HOST int64, coef_stride must be 8.
+ *   Position       of canvas pixel (dx, dy), in source pixel-index coordinates (an integer is a pixel centre), units of 1/65536 px, int64:
+ *                  X = a dx + b dy + c, Y = d dx + e dy + f;  Xs = (X + 1024) >> 11, Ys = (Y + 1024) >> 11 (arithmetic shift = floor):
+ *                  the position rounded to 1/32 px.
+ *   Inside         -16 <= Xs <= 32 W0 - 17 and -16 <= Ys <= 32 H0 - 17: the rounded position lies in the source's pixel footprint
+ *                  [-0.5, W0 - 0.5) x [-0.5, H0 - 0.5).  Compared in int64, before anything is narrowed.
+ *   Image, inside  sx = Xs >> 5 (may be -1), fx = Xs & 31, the same for y;  x0 = clamp(sx, 0, W0 - 1), x1 = clamp(sx + 1, 0, W0 - 1),
+ *                  y0, y1 likewise;  per channel
+ *                  v = ((32-fx)(32-fy) S[y0][x0] + fx (32-fy) S[y0][x1] + (32-fx) fy S[y1][x0] + fx fy S[y1][x1] + 512) >> 10.
+ *                  The weights sum to 1024, so v is in 0..255 without a clamp.  Then the optional table lut[i][c][v] (DEVICE uint8
+ *                  [count][3][256], the source's BGR order, as in mtbt_augment_batch), the one correctly rounded /255, BGR -> RGB planes.
+ *   Mask, inside   mx = clamp((Xs + 16) >> 5, 0, W0 - 1), my likewise: the nearest source pixel; 1.f when that byte is >= 128, else 0.f.
+ *                  A descriptor without a mask gives zeros.
+ *   Outside        image 114/255, not remapped by the table; mask 0.  A map that shows nothing of the source gives a pure pad canvas.
+ * Every source index is clamped, so no coefficients address outside the source.  Outputs as mtbt_letterbox_batch: out_images
+ * [count][3][S][S] f32 RGB in [0,1], out_masks [count][1][S][S] f32 in {0,1} or NULL.  There is NO area averaging: a map that shrinks the
+ * source by more than 2 aliases, as warpAffine does and as the INTER_LINEAR path of the entry points above does.  This rule is NOT
+ * bit-equal to mtbt_augment_batch at angle 0: that path is cv2's two-pass resize with 11-bit coefficients per axis, this one blends four
+ * taps with 5-bit fractions in one step; no equality between the two is claimed or tested.
+ * Limits: |a|, |b|, |d|, |e| <= 2^26 (1024 source px per canvas px), |c|, |f| <= 2^47, img_size <= 32768; with them |X|, |Y| < 2^48.
+ * The host side (`preprocess.affine_coefficients`) makes the row from a forward matrix in float64 and moves the labels by the exact
+ * inverse of the INTEGER map, so labels follow the pixels.
+ * One launch per <= 32 canvases, asynchronous on `stream`; every output byte is written exactly once; no LDS, no atomics.
+ * Order of the checks as in mtbt_letterbox_batch: (1) MTBT_EINVAL with every canvas checked, so before any launch: NULL images / coef /
+ * out_images, coef_stride != 8, count < 0, img_size <= 0, % 4 or > 32768, a coefficient outside the limits, a non-zero reserved field, a
+ * descriptor mtbt_letterbox_batch refuses; (2) then MTBT_EALIGN for outputs not 16-byte aligned (a call that is both invalid and
+ * misaligned is MTBT_EINVAL); (3) then the first launch.  count == 0 is MTBT_OK with nothing launched. */
+int mtbt_warp_batch(const mtbt_raw_image* images, int count, int img_size, const int64_t* coef /* HOST [count][coef_stride] */,
+                    int coef_stride, const uint8_t* lut /* DEVICE [count][3][256] or NULL */, float* out_images,
+                    float* out_masks /* NULL = skip */, void* stream);
+
 /* Contrast-limited adaptive histogram equalisation of raw uint8 images on the device (csrc/clahe.hip; `preprocess.clahe_batch`, the
  * `clahe=` option of the `*_samples` functions), ahead of the resampling entry points above and independent of them.  The reference
  * equalises nothing; cv2 is absent here, so THE RULE below is this project's own definition, modelled step for step on cv2's CLAHE

@@ -5,6 +5,7 @@
     from multitask_bonetumor_yolo_amd import preprocess                  # letterbox / BGR->RGB / /255 of a batch on the GPU
     from multitask_bonetumor_yolo_amd import augment_samples             # training augmentation fused into that launch (the reference has none)
     from multitask_bonetumor_yolo_amd import mosaic_samples              # the same with four images per canvas
+    from multitask_bonetumor_yolo_amd import affine_samples, affine_samples_seg   # rotation and shear: an affine map per canvas, labels moved with it
     from multitask_bonetumor_yolo_amd import multitask_loss              # == MultiTaskLitModel._multitask_loss (value)
     from multitask_bonetumor_yolo_amd import instance_mask_loss          # YOLOv8-seg instance-mask loss + gradients (opt-in extension)
     from multitask_bonetumor_yolo_amd import task_aligned_det_loss       # task-aligned (YOLOv8) detection loss + gradients (opt-in extension)
@@ -24,6 +25,8 @@ The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
 """
 from . import postprocess, preprocess  # noqa: F401
+from .preprocess import (affine_coefficients, affine_forward, affine_polygons, affine_samples, affine_samples_seg, affine_yolo_labels,  # noqa: F401
+                         sample_affine, warp_batch)
 from .preprocess import (augment_batch, augment_polygons, augment_samples, augment_samples_seg, augment_yolo_labels, clahe_batch, clahe_clip,  # noqa: F401
                          letterbox_geometry, mosaic_batch, mosaic_polygons, mosaic_samples, mosaic_samples_seg, mosaic_yolo_labels, photometric_lut,
                          sample_clahe, sample_geometry, sample_mosaic, sample_photometric, slice_batch, slice_geometry)

@@ -11,6 +11,8 @@ ACT_NONE, ACT_SILU, ACT_ELU, ACT_GELU, ACT_GELU_POLY, ACT_DSILU, ACT_DELU, ACT_D
 OUT_NHWC, OUT_CONVT2X2 = 0, 1
 RES_ID, RES_UP_BILINEAR, RES_DOWN_MEAN, RES_UP_NEAREST, RES_MAXPOOL = 0, 1, 2, 3, 4
 CONFUSION_MAX_NC = 64    # include/mtbt_hip.h MTBT_CONFUSION_MAX_NC: classes of mtbt_det_confusion / mtbt_cls_confusion
+WARP_CHUNK = 32          # csrc/warp_affine.hip MAX_CANVASES: canvases per launch of mtbt_warp_batch
+WARP_LIN_MAX, WARP_OFF_MAX = 1 << 26, 1 << 47   # include/mtbt_hip.h mtbt_warp_batch: |a|, |b|, |d|, |e| and |c|, |f|
 
 ERRORS = {-1: "MTBT_EINVAL (bad argument / unsupported shape)", -2: "MTBT_EALIGN (misaligned pointer or stride)",
           -3: "MTBT_ELAUNCH (kernel launch failed)", -4: "MTBT_EWORKSPACE (workspace too small)"}
@@ -279,6 +281,7 @@ SYMBOLS = {
     "mtbt_letterbox_batch": (C.c_int, [C.POINTER(RawImage), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]),
     "mtbt_augment_batch": (C.c_int, [C.POINTER(RawImage), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtbt_mosaic_batch": (C.c_int, [C.POINTER(RawImage), C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mtbt_warp_batch": (C.c_int, [C.POINTER(RawImage), C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mtbt_seg_confusion_workspace_bytes": (C.c_int64, [C.c_int]),
     "mtbt_seg_confusion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "mtbt_conv_wgrad_workspace_bytes": (C.c_int64, [C.c_int] * 7),

@@ -14,6 +14,10 @@ The four-image mosaic (`mosaic_batch` and the functions after it, include/mtbt_h
 with the source picked per canvas region: a centre cuts the canvas into four rectangles, each showing its own image under its own
 geometry row; with the centre at (S, S) a canvas is the plain augmentation of its first tile.
 
+`warp_batch` (include/mtbt_hip.h `mtbt_warp_batch`, and the `affine_*` functions after it) turns and shears: an affine map per canvas in
+fixed point, 2 x 2 taps, a kernel of its own because a rotated canvas row is neither a row nor a column of the source.  Its labels are
+moved by the exact inverse of the integer map the pixels use; polygon labels stay tight under rotation, box labels grow.
+
 `clahe_batch` (include/mtbt_hip.h `mtbt_clahe_batch`) equalises the raw uint8 images tile-wise at their own resolution before any of
 the above: the project's own integer rule, modelled on cv2's CLAHE, which the reference does not use either.
 """
@@ -512,6 +516,28 @@ def _clip_polygon(pts, rect):
     return pts
 
 
+def _polygon_row(cls: float, pts, rect, S: float, min_px: float, min_area_ratio: float, max_aspect: float):
+    """The label row of a moved polygon (list of (x, y) in canvas pixels), or None when it is dropped: clip to `rect` (Sutherland-Hodgman),
+    take the clipped polygon's box, apply the three drop rules.  The one tail of `augment_polygons`, `affine_polygons` and
+    `affine_yolo_labels`."""
+    area = abs(_shoelace(pts))
+    if not area > 0.0:
+        return None
+    cl = _clip_polygon(pts, rect)
+    if len(cl) < 3:
+        return None
+    cx1, cx2 = min(q[0] for q in cl), max(q[0] for q in cl)
+    cy1, cy2 = min(q[1] for q in cl), max(q[1] for q in cl)
+    cw, ch = cx2 - cx1, cy2 - cy1
+    if cw < min_px or ch < min_px or cw <= 0.0 or ch <= 0.0:
+        return None
+    if abs(_shoelace(cl)) / area <= min_area_ratio:
+        return None
+    if max(cw / ch, ch / cw) >= max_aspect:
+        return None
+    return [0.0, cls, (cx1 + cx2) / 2 / S, (cy1 + cy2) / 2 / S, cw / S, ch / S]
+
+
 def augment_polygons(rows: Sequence[Sequence[float]], W0: int, H0: int, geom_row, img_size: int, *, min_px: float = 2.0,
                      min_area_ratio: float = 0.1, max_aspect: float = 100.0, clip_rect=None):
     """YOLO-seg rows (cls, x1, y1, x2, y2, ... normalised to the ORIGINAL image) -> a list of (row6, vertices) on the augmented S x S
@@ -542,22 +568,9 @@ def augment_polygons(rows: Sequence[Sequence[float]], W0: int, H0: int, geom_row
             if orient & 2:
                 y = qh - y
             pts.append((x + off_x, y + off_y))
-        area = abs(_shoelace(pts))
-        if not area > 0.0:
-            continue
-        cl = _clip_polygon(pts, rect)
-        if len(cl) < 3:
-            continue
-        cx1, cx2 = min(q[0] for q in cl), max(q[0] for q in cl)
-        cy1, cy2 = min(q[1] for q in cl), max(q[1] for q in cl)
-        cw, ch = cx2 - cx1, cy2 - cy1
-        if cw < min_px or ch < min_px or cw <= 0.0 or ch <= 0.0:
-            continue
-        if abs(_shoelace(cl)) / area <= min_area_ratio:
-            continue
-        if max(cw / ch, ch / cw) >= max_aspect:
-            continue
-        out.append(([0.0, cls, (cx1 + cx2) / 2 / S, (cy1 + cy2) / 2 / S, cw / S, ch / S], np.asarray(pts, dtype=np.float64).reshape(n, 2)))
+        row6 = _polygon_row(cls, pts, rect, S, min_px, min_area_ratio, max_aspect)
+        if row6 is not None:
+            out.append((row6, np.asarray(pts, dtype=np.float64).reshape(n, 2)))
     return out
 
 
@@ -636,6 +649,193 @@ def mosaic_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Seque
     per_canvas = [mosaic_polygons([seg_rows_per_image[k] for k in index[i]], [sizes[k] for k in index[i]], geom[i], centres[i], img_size, **lab)
                   for i in range(len(images))]
     return (imgs,) + _seg_outputs(per_canvas, [tile_rects(c, img_size) for c in centres], img_size, imgs.device)
+
+
+# ---- affine augmentation: rotation and shear (the project's own definition: include/mtbt_hip.h `mtbt_warp_batch`) ----------------
+COEF_FIELDS = 8  # a, b, c, d, e, f (the inverse map in 1/65536 source px: X = a dx + b dy + c, Y = d dx + e dy + f), 2 reserved zeros
+_INT64_P = C.POINTER(C.c_int64)
+
+
+def _coef_array(coef, B: Optional[int], who: str) -> np.ndarray:
+    """An integer array or tensor of shape [B, 8] (None = any B) -> contiguous int64 numpy."""
+    a = np.asarray(coef.cpu() if isinstance(coef, torch.Tensor) else coef)
+    if a.dtype.kind not in "iu" or a.ndim != 2 or a.shape[1] != COEF_FIELDS or (B is not None and a.shape[0] != B):
+        raise ValueError(f"{who}: coef must be an integer array of shape [B, {COEF_FIELDS}]")
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def warp_batch(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]], coef, lut: Optional[torch.Tensor] = None,
+               img_size: int = 640):
+    """One canvas per image under an affine map: coef int64 [B, 8] rows (a, b, c, d, e, f, 0, 0) as `affine_coefficients` returns them --
+    the INVERSE map, canvas pixel -> source position in 1/65536 px -- lut an optional CUDA uint8 [B, 3, 256] table (BGR order,
+    `photometric_lut`).  The rule (fixed-point position reduced to 1/32 px, 2 x 2 taps, nearest mask, 114/255 and 0 outside the source)
+    is stated in include/mtbt_hip.h `mtbt_warp_batch`; it does not average areas, so a map that shrinks by more than 2 aliases.
+    Returns (imgs [B,3,S,S] f32 RGB in [0,1], masks [B,1,S,S] f32 {0,1}); one launch per <= 32 canvases, no CPU path."""
+    lib = L.load()
+    descs, keep, dev = _descriptors(images, masks, "warp_batch")
+    B = len(images)
+    k = _coef_array(coef, B, "warp_batch")
+    table = _table(lut, B, dev, keep, "warp_batch")
+    return _run(B, img_size, dev, keep, lambda x, m, st: lib.mtbt_warp_batch(descs, B, img_size, k.ctypes.data_as(_INT64_P), COEF_FIELDS, table, x, m, st),
+                "mtbt_warp_batch")
+
+
+def affine_coefficients(forward) -> np.ndarray:
+    """forward: float64 [B, 2, 3] (or one [2, 3]) matrices that take source EDGE coordinates (pixel x covers [x, x + 1): the coordinates of
+    the label rows times W0, H0) to canvas edge coordinates -> the int64 [B, 8] rows of `warp_batch`.  Each matrix is inverted in float64,
+    the pixel-centre convention is folded into the offsets (source_index = inv . (dx + 0.5, dy + 0.5) - 0.5), and the six numbers are
+    multiplied by 65536 and rounded (`np.rint`).  ValueError on a singular (or non-finite) matrix and on a coefficient outside the
+    library's limits (|a|, |b|, |d|, |e| <= 2^26, |c|, |f| <= 2^47)."""
+    F = np.asarray(forward, dtype=np.float64)
+    F = F.reshape(1, 2, 3) if F.ndim == 2 else F
+    if F.ndim != 3 or F.shape[1:] != (2, 3):
+        raise ValueError("affine_coefficients: forward must be float64 [B, 2, 3]")
+    coef = np.zeros((F.shape[0], COEF_FIELDS), dtype=np.int64)
+    for i, M in enumerate(F):
+        det = M[0, 0] * M[1, 1] - M[0, 1] * M[1, 0]
+        if not np.isfinite(M).all() or not np.isfinite(det) or det == 0.0:
+            raise ValueError(f"affine_coefficients: matrix {i} is singular")
+        ia, ib, id_, ie = M[1, 1] / det, -M[0, 1] / det, -M[1, 0] / det, M[0, 0] / det
+        ic, if_ = -(ia * M[0, 2] + ib * M[1, 2]), -(id_ * M[0, 2] + ie * M[1, 2])
+        row = np.array([ia, ib, ic + 0.5 * (ia + ib) - 0.5, id_, ie, if_ + 0.5 * (id_ + ie) - 0.5]) * 65536.0
+        if not np.isfinite(row).all() or np.abs(row[[0, 1, 3, 4]]).max() > L.WARP_LIN_MAX or np.abs(row[[2, 5]]).max() > L.WARP_OFF_MAX:
+            raise ValueError(f"affine_coefficients: matrix {i} gives coefficients {row.tolist()} outside the library's limits "
+                             f"(2^26 for a, b, d, e; 2^47 for c, f): the map shrinks the source too far or is nearly singular")
+        coef[i, :6] = np.rint(row).astype(np.int64)
+    return coef
+
+
+def affine_forward(coef) -> np.ndarray:
+    """int64 [B, 8] coefficient rows -> float64 [B, 2, 3]: the inverse of the INTEGER map the pixels use, back in edge coordinates (source
+    edge -> canvas edge).  Labels are moved by `affine_forward(affine_coefficients(F))`, not by F: they follow the pixels.  The two differ
+    by the 2^-17 rounding of each coefficient, a few 2^-16 S canvas pixels at most.  ValueError when the integer map is singular."""
+    k = _coef_array(coef, None, "affine_forward").astype(np.float64) / 65536.0
+    out = np.zeros((k.shape[0], 2, 3), dtype=np.float64)
+    for i, (a, b, c, d, e, f) in enumerate(k[:, :6]):
+        det = a * e - b * d
+        if det == 0.0:
+            raise ValueError(f"affine_forward: coefficient row {i} is a singular map")
+        # source_edge = A . canvas_edge + t with t = (c, f) + 0.5 - A . (0.5, 0.5); canvas_edge = A^-1 . (source_edge - t)
+        tx, ty = c + 0.5 - 0.5 * (a + b), f + 0.5 - 0.5 * (d + e)
+        fa, fb, fd, fe = e / det, -b / det, -d / det, a / det
+        out[i] = [[fa, fb, -(fa * tx + fb * ty)], [fd, fe, -(fd * tx + fe * ty)]]
+    return out
+
+
+def sample_affine(sizes: Sequence[Sequence[int]], img_size: int, rng: np.random.Generator, *, scale=(0.5, 1.5), aspect: float = 0.0,
+                  degrees: float = 10.0, shear: float = 0.0, translate: float = 0.1, fliplr: float = 0.5, flipud: float = 0.0) -> np.ndarray:
+    """Draw one forward matrix per image, float64 [B, 2, 3], source edge coordinates -> canvas edge coordinates:
+        F = T(S/2 + tx S, S/2 + ty S) . R(theta) . Sh(tan sx, tan sy) . diag(+-kx, +-ky) . T(-W0/2, -H0/2)
+    with kx = s g a, ky = s g / a, s = S / max(H0, W0), g ~ U(scale), a = exp(U(+-aspect)), theta ~ U(+-degrees), sx, sy ~ U(+-shear)
+    (degrees both), tx, ty ~ U(+-translate), kx negated with probability fliplr and ky with probability flipud;
+    R = [[cos, -sin], [sin, cos]], Sh = [[1, tan sx], [tan sy, 1]].  The image's centre lands on the canvas centre plus the translation.
+    The draws come in a fixed order, one vector of B each -- g, a, theta, sx, sy, tx, ty, the fliplr bits, the flipud bits -- so a seeded
+    generator gives the same array again."""
+    B, S = len(sizes), float(img_size)
+    g = rng.uniform(scale[0], scale[1], B)
+    a = np.exp(rng.uniform(-aspect, aspect, B))
+    theta = np.deg2rad(rng.uniform(-degrees, degrees, B))
+    sx, sy = np.deg2rad(rng.uniform(-shear, shear, B)), np.deg2rad(rng.uniform(-shear, shear, B))
+    tx, ty = rng.uniform(-translate, translate, B), rng.uniform(-translate, translate, B)
+    lr, ud = rng.random(B) < fliplr, rng.random(B) < flipud
+    out = np.zeros((B, 2, 3), dtype=np.float64)
+    for i, (H0, W0) in enumerate(sizes):
+        s = S / max(H0, W0)
+        kx, ky = s * g[i] * a[i] * (-1.0 if lr[i] else 1.0), s * g[i] / a[i] * (-1.0 if ud[i] else 1.0)
+        rot = np.array([[math.cos(theta[i]), -math.sin(theta[i])], [math.sin(theta[i]), math.cos(theta[i])]])
+        lin = rot @ np.array([[1.0, math.tan(sx[i])], [math.tan(sy[i]), 1.0]]) @ np.diag([kx, ky])
+        out[i, :, :2] = lin
+        out[i, :, 2] = np.array([S / 2 + tx[i] * S, S / 2 + ty[i] * S]) - lin @ np.array([W0 / 2, H0 / 2])
+    return out
+
+
+def affine_polygons(rows: Sequence[Sequence[float]], W0: int, H0: int, forward_row, img_size: int, *, min_px: float = 2.0,
+                    min_area_ratio: float = 0.1, max_aspect: float = 100.0, clip_rect=None):
+    """`augment_polygons` under an affine map: YOLO-seg rows (cls, x1, y1, x2, y2, ... normalised to the ORIGINAL image) -> a list of
+    (row6, vertices) on the S x S canvas of `warp_batch`.  forward_row is one float64 [2, 3] matrix of `affine_forward` (use that, not the
+    matrix the coefficients were made from: labels follow the integer map).  Every vertex (x W0, y H0) goes through the matrix exactly and
+    is NOT clipped -- the rasteriser clips; row6 is the box of the polygon clipped to clip_rect or [0, S]^2, under the drop rules of
+    `augment_polygons`.  The box of a rotated polygon is tight: polygon rows do not grow under rotation, box rows (`affine_yolo_labels`) do."""
+    M = np.asarray(forward_row, dtype=np.float64).reshape(2, 3)
+    (fa, fb, fc), (fd, fe, ff) = ((float(v) for v in r) for r in M)
+    S = float(img_size)
+    rect = (0.0, 0.0, S, S) if clip_rect is None else tuple(float(v) for v in clip_rect)
+    out = []
+    for r in rows:
+        n = (len(r) - 1) // 2
+        if n < 3:
+            continue
+        pts = []
+        for i in range(n):
+            x, y = float(r[1 + 2 * i]) * W0, float(r[2 + 2 * i]) * H0
+            pts.append((fa * x + fb * y + fc, fd * x + fe * y + ff))
+        row6 = _polygon_row(float(r[0]), pts, rect, S, min_px, min_area_ratio, max_aspect)
+        if row6 is not None:
+            out.append((row6, np.asarray(pts, dtype=np.float64).reshape(n, 2)))
+    return out
+
+
+def affine_yolo_labels(rows: Sequence[Sequence[float]], W0: int, H0: int, forward_row, img_size: int, *, min_px: float = 2.0,
+                       min_area_ratio: float = 0.1, max_aspect: float = 100.0, clip_rect=None) -> List[List[float]]:
+    """`augment_yolo_labels` under an affine map: YOLO-txt rows (cls, xc, yc, w, h) -> [0.0, cls, cx, cy, w, h] on the canvas of
+    `warp_batch`.  Each box goes through `affine_polygons` as its four corners, so its row is the axis-aligned hull of the rotated
+    rectangle, clipped, under the same drop rules.  Boxes therefore GROW under rotation (a w x h box turned by 45 degrees has sides
+    (w + h) / sqrt 2, and the hull of an already loose box is looser still); polygon rows do not -- prefer them when `degrees` is large."""
+    out = []
+    for r in rows:
+        if len(r) < 5:
+            continue
+        cls, xc, yc, w, h = (float(v) for v in r[:5])
+        if w <= 0 or h <= 0:
+            continue
+        x1, y1, x2, y2 = xc - w / 2, yc - h / 2, xc + w / 2, yc + h / 2
+        out += [row6 for row6, _ in affine_polygons([[cls, x1, y1, x2, y1, x2, y2, x1, y2]], W0, H0, forward_row, img_size, min_px=min_px,
+                                                    min_area_ratio=min_area_ratio, max_aspect=max_aspect, clip_rect=clip_rect)]
+    return out
+
+
+_AFFINE_KEYS = ("scale", "aspect", "degrees", "shear", "translate", "fliplr", "flipud")
+
+
+def affine_samples(images: Sequence[torch.Tensor], masks: Optional[Sequence[Optional[torch.Tensor]]],
+                   rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int, rng: np.random.Generator, **ranges):
+    """`augment_samples` with rotation and shear: draw `sample_affine`, then `sample_photometric` from the one generator, run `warp_batch`
+    on `affine_coefficients` of the draw, move the box rows with `affine_yolo_labels` under `affine_forward` of those coefficients:
+    (imgs [B,3,S,S], masks [B,1,S,S], gt_rows [M,6] on the device, batch index in column 0) -- what `TrainStep.step` takes.  `ranges` are
+    the keyword arguments of those three functions plus clahe=dict(prob=, clip=, grid=) as in `augment_samples` (its draws come last);
+    anything else is an error.  Box rows grow under rotation (`affine_yolo_labels`); `affine_samples_seg` keeps polygon labels tight."""
+    clahe = ranges.pop("clahe", None)
+    geo, pho, lab = _split(ranges, "affine_samples", _AFFINE_KEYS)
+    if len(rows_per_image) != len(images):
+        raise ValueError("affine_samples: one list of label rows per image")
+    sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+    coef = affine_coefficients(sample_affine(sizes, img_size, rng, **geo))
+    forward = affine_forward(coef)
+    lut = torch.from_numpy(sample_photometric(len(images), rng, **pho)).to(images[0].device)
+    imgs, out_masks = warp_batch(_equalised(images, rng, clahe), masks, coef, lut, img_size)
+    rows = [affine_yolo_labels(r, W0, H0, forward[i], img_size, **lab) for i, (r, (H0, W0)) in enumerate(zip(rows_per_image, sizes))]
+    return imgs, out_masks, collate_boxes(rows, device=imgs.device)
+
+
+def affine_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int,
+                       rng: np.random.Generator, **ranges):
+    """`affine_samples` for polygon labels, as `augment_samples_seg` is to `augment_samples`: the same draws (the same seed gives the same
+    `imgs`, bit for bit), `warp_batch` without masks, the vertices moved exactly on the host (`affine_polygons`) and rasterised at the
+    canvas resolution, so nothing is resampled and the boxes of the rotated polygons stay tight.  Returns (imgs, masks, gt_rows, inst) as
+    `augment_samples_seg` does.  Nothing synchronises with the host."""
+    clahe = ranges.pop("clahe", None)
+    geo, pho, lab = _split(ranges, "affine_samples_seg", _AFFINE_KEYS)
+    if len(seg_rows_per_image) != len(images):
+        raise ValueError("affine_samples_seg: one list of label rows per image")
+    sizes = [(int(im.shape[0]), int(im.shape[1])) for im in images]
+    coef = affine_coefficients(sample_affine(sizes, img_size, rng, **geo))
+    forward = affine_forward(coef)
+    lut = _upload(torch.from_numpy(sample_photometric(len(images), rng, **pho)), images[0].device)
+    imgs, _ = warp_batch(_equalised(images, rng, clahe), None, coef, lut, img_size)
+    whole = (0, 0, int(img_size), int(img_size))
+    per_canvas = [[(row6, v, whole) for row6, v in affine_polygons(r, W0, H0, forward[i], img_size, **lab)]
+                  for i, (r, (H0, W0)) in enumerate(zip(seg_rows_per_image, sizes))]
+    return (imgs,) + _seg_outputs(per_canvas, [[whole]] * len(images), img_size, imgs.device)
 
 
 # ---- sliced inference: overlapping tiles of a large image (the project's own definition: include/mtbt_hip.h `mtbt_tile`) ----
