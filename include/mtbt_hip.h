@@ -1038,6 +1038,73 @@ int mtbt_clahe_batch(const mtbt_clahe_image* images, int count, int grid_x, int 
 /* sizeof() of the struct above as the library was compiled: which = 0 mtbt_clahe_image; -1 otherwise */
 int mtbt_sizeof_clahe_args(int which);
 
+/* Copy-paste augmentation between the canvases of a batch on the device (csrc/copy_paste.hip; `preprocess.copy_paste_batch`, the
+ * `copy_paste=` option of the `*_samples_seg` functions): instances, given as bit-packed planes, are cut out of donor canvases and laid
+ * on destination canvases, pixels, planes and label rows together.  The reference augments nothing, so THE RULE below is this project's
+ * own, and exact: no float arithmetic touches a pixel (tests/copy_paste_reference.py restates it in numpy).
+ *   Inputs     B canvases images f32 [B][3][S][S]; M planes uint8 [M][S][pitch], pitch = 8 * ceil(S / 64), packed as everywhere in this
+ *              header, grouped by canvas through row_off[B + 1] (canvas i owns the rows row_off[i] .. row_off[i + 1] - 1); a label row per
+ *              plane, rows_in f32 [M][6] = (image, cls, xc, yc, w, h); P paste entries grouped by DESTINATION canvas through
+ *              paste_off[B + 1], each (src_row, dx, dy, flip, 0, 0, 0, 0) of int32, entry_stride must be 8.
+ *   Pasted     entry e of canvas i with donor row r = src_row, which lies on canvas j (row_off[j] <= r < row_off[j + 1]; j == i is
+ *              allowed):  T_e[y'][x'] = planes[r][y][x] with y = y' - dy, x = flip ? S - 1 - (x' - dx) : x' - dx, and 0 wherever (x, y) is
+ *              outside [0, S)^2: the donor canvas is mirrored first, then translated.
+ *   Layering   the entries of a canvas apply in table order, later above earlier: C_e = OR of T over the later entries of the canvas, the
+ *              visible plane V_e = T_e & ~C_e; U_i = OR of all T of canvas i; an old row m of canvas i becomes O_m = planes[m] & ~U_i.
+ *              Old planes that overlap each other are left as they are.
+ *   Pixels     out[i][c][y'][x'] = images[j][c][y][x] of the topmost entry with T_e[y'][x'] set (its j, x, y), else images[i][c][y'][x'].
+ *              Floats are copied, never recomputed.  The input is never modified, so mutual pastes (i from j and j from i) and
+ *              self-pastes read pristine pixels; outputs may not overlap inputs.
+ *   Planes     out_planes [M + P][S][pitch]: rows 0 .. M-1 are O_m, rows M .. M+P-1 are V_e in table order; every byte is written,
+ *              padding bits are zero (input bits at x >= S, which the layout forbids, are ignored).
+ *   Mask       out_masks (optional) [B][1][S][S] f32 in {0, 1}: the union of the canvas's output planes = old union | U_i.
+ *   Records    area_before uint32 [M + P]: popcount of planes[m], respectively of T_e; area uint32 [M + P]: popcount of the output plane;
+ *              box int32 [M + P][4]: tight x1, y1, x2, y2 of the output plane with exclusive maxima, all zero for an empty plane (the
+ *              convention of mtbt_fill_polygons).  All three are fully defined after the call.
+ *   Rows       rows_out (optional) f32 [M + P][6]; the first rule that applies:
+ *                (1) an old row with area == area_before is rows_in[m], bit for bit (so P == 0 returns rows_in);
+ *                (2) a row with area == 0 is (image, cls, 0, 0, 0, 0);
+ *                (3) every other row is (image, cls, xc, yc, w, h) from the box: xc = float(x1 + x2) / float(2 S),
+ *                    yc = float(y1 + y2) / float(2 S), w = float(x2 - x1) / float(S), h = float(y2 - y1) / float(S), each division
+ *                    correctly rounded in f32; the operands are exact integers, so the result is one defined float.
+ *              image and cls of an old row are rows_in[m][0], rows_in[m][1]; of a pasted row float(i) and rows_in[src_row][1].
+ *              A zero row is what an instance becomes that later pastes cover completely.  Downstream `loss.group_gt_rows_cls` moves a
+ *              row of zero width or height behind off[N], so the task-aligned loss and the mask loss skip it; in the reference's loss it
+ *              is a zero-area box whose IoU with everything is 0.  Rows are never dropped here: area and area_before are returned for
+ *              callers that filter.
+ * row_off, paste_off and entries are HOST arrays, validated in full before any launch and handed to the kernel by value, 8 canvases per
+ * launch; everything else is DEVICE memory.  Asynchronous on `stream`, no allocation, no workspace, no host synchronisation,
+ * graph-capturable.  Integer atomics gather the records only (cleared on the stream first), and one small finishing launch turns them into
+ * boxes and rows: the result is a pure function of the input.  Every output byte is written exactly once.
+ * Limits: S % 4 == 0, 4 <= S <= 32768, at most 16 entries per canvas, |dx|, |dy| <= S.
+ * Required pointers: a, row_off, paste_off; images and out_images when B > 0; planes when M > 0; entries when P > 0; out_planes,
+ * area_before, area and box when M + P > 0; rows_in when rows_out is given and M + P > 0.
+ * Order of the checks: (1) MTBT_EINVAL with every item checked, so before any launch: a NULL required pointer, B, M or P negative, S
+ * outside the limits, pitch != 8 * ceil(S / 64), entry_stride != 8, an offset table that does not start at 0, decreases or ends
+ * elsewhere than M respectively P, more than 16 entries on a canvas, src_row outside [0, M), flip outside {0, 1}, |dx| or |dy| > S, a
+ * non-zero reserved field, rows_out without rows_in, an output range that overlaps an input range; (2) then MTBT_EALIGN: images, out_images
+ * or out_masks not 16-byte aligned, planes or out_planes not 8-byte aligned, rows or records not 4-byte aligned; (3) then the launches.
+ * B == 0 launches nothing.  M == 0 or P == 0 is legal: the images are copied, the planes copied (P == 0) or absent (M == 0). */
+typedef struct mtbt_copy_paste_args {
+  const float* images;           /* [B][3][S][S] */
+  const uint8_t* planes;         /* [M][S][pitch] */
+  const float* rows_in;          /* [M][6], or NULL when rows_out is NULL */
+  const int32_t* row_off;        /* HOST [B + 1] into the planes */
+  const int32_t* paste_off;      /* HOST [B + 1] into the entries */
+  const int32_t* entries;        /* HOST [P][entry_stride] = src_row, dx, dy, flip, 0, 0, 0, 0 */
+  float* out_images;             /* [B][3][S][S] */
+  uint8_t* out_planes;           /* [M + P][S][pitch] */
+  float* out_masks;              /* [B][1][S][S] or NULL */
+  float* rows_out;               /* [M + P][6] or NULL */
+  uint32_t* area_before;         /* [M + P] */
+  uint32_t* area;                /* [M + P] */
+  int32_t* box;                  /* [M + P][4] */
+  int32_t B, M, P, S, pitch, entry_stride;
+} mtbt_copy_paste_args;
+int mtbt_copy_paste(const mtbt_copy_paste_args* a, void* stream);
+/* sizeof() of the struct above as the library was compiled: which = 0 mtbt_copy_paste_args; -1 otherwise */
+int mtbt_sizeof_copy_paste_args(int which);
+
 /* Segmentation metric accumulators (running_main_v3.py:466-498 feeding the torchmetrics objects of :198-203), SURVEY §8f N3.
  * logits, gt: [B][n_per_image] f32 (n % 4 == 0); prediction = sigmoid(logit) > 0.5, target = int(gt) >= 1.
  * counts [B][4] int64 = TP, FP, FN, TN per image; prob_sum [B] = sum of sigmoid(logit) over predicted-foreground pixels

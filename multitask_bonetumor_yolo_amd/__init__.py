@@ -20,6 +20,7 @@
     from multitask_bonetumor_yolo_amd import label_components, LesionMetrics   # connected components of packed masks; lesion-wise recall / precision
     from multitask_bonetumor_yolo_amd import fill_polygons, yolo_seg_planes, augment_samples_seg   # polygon labels -> packed instance masks
     from multitask_bonetumor_yolo_amd import clahe_batch                 # tile-wise contrast equalisation (CLAHE) of the raw uint8 images
+    from multitask_bonetumor_yolo_amd import copy_paste_batch, sample_copy_paste   # instances pasted between the canvases of a batch
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
@@ -27,6 +28,7 @@ The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 from . import postprocess, preprocess  # noqa: F401
 from .preprocess import (affine_coefficients, affine_forward, affine_polygons, affine_samples, affine_samples_seg, affine_yolo_labels,  # noqa: F401
                          sample_affine, warp_batch)
+from .preprocess import copy_paste_batch, sample_copy_paste  # noqa: F401
 from .preprocess import (augment_batch, augment_polygons, augment_samples, augment_samples_seg, augment_yolo_labels, clahe_batch, clahe_clip,  # noqa: F401
                          letterbox_geometry, mosaic_batch, mosaic_polygons, mosaic_samples, mosaic_samples_seg, mosaic_yolo_labels, photometric_lut,
                          sample_clahe, sample_geometry, sample_mosaic, sample_photometric, slice_batch, slice_geometry)

@@ -13,6 +13,8 @@ RES_ID, RES_UP_BILINEAR, RES_DOWN_MEAN, RES_UP_NEAREST, RES_MAXPOOL = 0, 1, 2, 3
 CONFUSION_MAX_NC = 64    # include/mtbt_hip.h MTBT_CONFUSION_MAX_NC: classes of mtbt_det_confusion / mtbt_cls_confusion
 WARP_CHUNK = 32          # csrc/warp_affine.hip MAX_CANVASES: canvases per launch of mtbt_warp_batch
 WARP_LIN_MAX, WARP_OFF_MAX = 1 << 26, 1 << 47   # include/mtbt_hip.h mtbt_warp_batch: |a|, |b|, |d|, |e| and |c|, |f|
+COPY_PASTE_CHUNK = 8     # csrc/copy_paste_check.h CHUNK: canvases per launch of mtbt_copy_paste
+COPY_PASTE_MAX_ENTRIES = 16   # csrc/copy_paste_check.h MAX_ENTRIES: paste entries per canvas
 
 ERRORS = {-1: "MTBT_EINVAL (bad argument / unsupported shape)", -2: "MTBT_EALIGN (misaligned pointer or stride)",
           -3: "MTBT_ELAUNCH (kernel launch failed)", -4: "MTBT_EWORKSPACE (workspace too small)"}
@@ -247,6 +249,14 @@ class ClaheImage(C.Structure):  # mtbt_clahe_image
                 ("src_row_stride", C.c_int64), ("dst_row_stride", C.c_int64)]
 
 
+class CopyPasteArgs(C.Structure):  # mtbt_copy_paste_args
+    _fields_ = [("images", C.c_void_p), ("planes", C.c_void_p), ("rows_in", C.c_void_p),
+                ("row_off", C.POINTER(C.c_int32)), ("paste_off", C.POINTER(C.c_int32)), ("entries", C.POINTER(C.c_int32)),
+                ("out_images", C.c_void_p), ("out_planes", C.c_void_p), ("out_masks", C.c_void_p), ("rows_out", C.c_void_p),
+                ("area_before", C.c_void_p), ("area", C.c_void_p), ("box", C.c_void_p),
+                ("B", C.c_int32), ("M", C.c_int32), ("P", C.c_int32), ("S", C.c_int32), ("pitch", C.c_int32), ("entry_stride", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -389,6 +399,8 @@ SYMBOLS = {
     "mtbt_clahe_workspace_bytes": (C.c_int64, [C.POINTER(ClaheImage), C.c_int, C.c_int, C.c_int]),
     "mtbt_clahe_batch": (C.c_int, [C.POINTER(ClaheImage), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "mtbt_sizeof_clahe_args": (C.c_int, [C.c_int]),
+    "mtbt_copy_paste": (C.c_int, [C.POINTER(CopyPasteArgs), C.c_void_p]),
+    "mtbt_sizeof_copy_paste_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -399,6 +411,7 @@ SURFACE_STRUCTS = (SurfaceArgs,)   # order of mtbt_sizeof_surface_args(which)
 COMPONENTS_STRUCTS = (ComponentsArgs, SelectComponentsArgs)   # order of mtbt_sizeof_components_args(which)
 POLYGON_STRUCTS = (FillPolygonsArgs,)   # order of mtbt_sizeof_fill_polygons_args(which)
 CLAHE_STRUCTS = (ClaheImage,)   # order of mtbt_sizeof_clahe_args(which)
+COPY_PASTE_STRUCTS = (CopyPasteArgs,)   # order of mtbt_sizeof_copy_paste_args(which)
 _lib = None
 
 
@@ -423,7 +436,7 @@ def load():
         for sizeof, structs in ((lib.mtbt_sizeof_frame_args, FRAME_STRUCTS), (lib.mtbt_sizeof_mask_eval_args, MASK_EVAL_STRUCTS),
                                 (lib.mtbt_sizeof_tile_args, TILE_STRUCTS), (lib.mtbt_sizeof_surface_args, SURFACE_STRUCTS),
                                 (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS), (lib.mtbt_sizeof_fill_polygons_args, POLYGON_STRUCTS),
-                                (lib.mtbt_sizeof_clahe_args, CLAHE_STRUCTS)):
+                                (lib.mtbt_sizeof_clahe_args, CLAHE_STRUCTS), (lib.mtbt_sizeof_copy_paste_args, COPY_PASTE_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

@@ -20,6 +20,10 @@ moved by the exact inverse of the integer map the pixels use; polygon labels sta
 
 `clahe_batch` (include/mtbt_hip.h `mtbt_clahe_batch`) equalises the raw uint8 images tile-wise at their own resolution before any of
 the above: the project's own integer rule, modelled on cv2's CLAHE, which the reference does not use either.
+
+`copy_paste_batch` (include/mtbt_hip.h `mtbt_copy_paste`) comes after all of them: it lays instances of other canvases of the batch, cut out
+by their bit-packed planes, on a canvas -- pixels, planes and label rows together, exact copies, nothing resampled.  `sample_copy_paste` draws
+its table from the host-side label rows; `copy_paste=dict(...)` of the `*_samples_seg` functions runs both.
 """
 import ctypes as C
 import math
@@ -618,8 +622,11 @@ def augment_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Sequ
     `augment_batch` without masks; the vertices are moved on the host (`augment_polygons`) and rasterised at the canvas resolution
     (`postprocess.fill_polygons`).  Returns (imgs [B,3,S,S], masks [B,1,S,S] float32 {0,1}: the union of each canvas's surviving
     polygons, gt_rows [M,6] on the device, inst = dict(planes uint8 [M,S,pitch], image int64 [M], labels int64 [M]), row for row with
-    gt_rows).  clahe=dict(prob=, clip=, grid=) as in `augment_samples`.  Nothing synchronises with the host."""
-    clahe = ranges.pop("clahe", None)
+    gt_rows).  clahe=dict(prob=, clip=, grid=) as in `augment_samples`.  copy_paste=dict(...) holds the keyword arguments of
+    `sample_copy_paste`: its draws come after every other draw, CLAHE's included, and `copy_paste_batch` then lays the drawn instances of
+    other canvases on each canvas -- the four outputs are then `copy_paste_batch`'s (M + P rows; inst gains area, area_before, boxes).
+    None -- the default -- draws nothing and changes nothing.  Nothing synchronises with the host."""
+    clahe, copy_paste = ranges.pop("clahe", None), ranges.pop("copy_paste", None)
     geo, pho, lab = _split(ranges, "augment_samples_seg", ("scale", "aspect", "fliplr", "flipud", "transpose", "place"))
     if len(seg_rows_per_image) != len(images):
         raise ValueError("augment_samples_seg: one list of label rows per image")
@@ -630,15 +637,15 @@ def augment_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Sequ
     whole = (0, 0, int(img_size), int(img_size))
     per_canvas = [[(row6, v, whole) for row6, v in augment_polygons(r, W0, H0, geom[i], img_size, **lab)]
                   for i, (r, (H0, W0)) in enumerate(zip(seg_rows_per_image, sizes))]
-    return (imgs,) + _seg_outputs(per_canvas, [[whole]] * len(images), img_size, imgs.device)
+    return _pasted((imgs,) + _seg_outputs(per_canvas, [[whole]] * len(images), img_size, imgs.device), per_canvas, img_size, rng, copy_paste)
 
 
 def mosaic_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Sequence[Sequence[Sequence[float]]], img_size: int,
                        rng: np.random.Generator, **ranges):
     """`mosaic_samples` for polygon labels, as `augment_samples_seg` is to `augment_samples`: the same draws, `mosaic_batch` without
     masks, `mosaic_polygons` per canvas.  Every instance plane is clipped to its tile, and so is its share of the canvas mask.
-    clahe=dict(prob=, clip=, grid=) as in `mosaic_samples`."""
-    clahe = ranges.pop("clahe", None)
+    clahe=dict(prob=, clip=, grid=) as in `mosaic_samples`; copy_paste=dict(...) as in `augment_samples_seg` (pastes are NOT clipped to a tile)."""
+    clahe, copy_paste = ranges.pop("clahe", None), ranges.pop("copy_paste", None)
     geo, pho, lab = _split(ranges, "mosaic_samples_seg", ("prob", "centre", "scale", "aspect", "fliplr", "flipud", "transpose"))
     if len(seg_rows_per_image) != len(images):
         raise ValueError("mosaic_samples_seg: one list of label rows per image")
@@ -648,7 +655,7 @@ def mosaic_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Seque
     imgs, _ = mosaic_batch(_equalised(images, rng, clahe), None, index, geom, centres, lut, img_size)
     per_canvas = [mosaic_polygons([seg_rows_per_image[k] for k in index[i]], [sizes[k] for k in index[i]], geom[i], centres[i], img_size, **lab)
                   for i in range(len(images))]
-    return (imgs,) + _seg_outputs(per_canvas, [tile_rects(c, img_size) for c in centres], img_size, imgs.device)
+    return _pasted((imgs,) + _seg_outputs(per_canvas, [tile_rects(c, img_size) for c in centres], img_size, imgs.device), per_canvas, img_size, rng, copy_paste)
 
 
 # ---- affine augmentation: rotation and shear (the project's own definition: include/mtbt_hip.h `mtbt_warp_batch`) ----------------
@@ -822,8 +829,8 @@ def affine_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Seque
     """`affine_samples` for polygon labels, as `augment_samples_seg` is to `augment_samples`: the same draws (the same seed gives the same
     `imgs`, bit for bit), `warp_batch` without masks, the vertices moved exactly on the host (`affine_polygons`) and rasterised at the
     canvas resolution, so nothing is resampled and the boxes of the rotated polygons stay tight.  Returns (imgs, masks, gt_rows, inst) as
-    `augment_samples_seg` does.  Nothing synchronises with the host."""
-    clahe = ranges.pop("clahe", None)
+    `augment_samples_seg` does; copy_paste=dict(...) as there.  Nothing synchronises with the host."""
+    clahe, copy_paste = ranges.pop("clahe", None), ranges.pop("copy_paste", None)
     geo, pho, lab = _split(ranges, "affine_samples_seg", _AFFINE_KEYS)
     if len(seg_rows_per_image) != len(images):
         raise ValueError("affine_samples_seg: one list of label rows per image")
@@ -835,7 +842,155 @@ def affine_samples_seg(images: Sequence[torch.Tensor], seg_rows_per_image: Seque
     whole = (0, 0, int(img_size), int(img_size))
     per_canvas = [[(row6, v, whole) for row6, v in affine_polygons(r, W0, H0, forward[i], img_size, **lab)]
                   for i, (r, (H0, W0)) in enumerate(zip(seg_rows_per_image, sizes))]
-    return (imgs,) + _seg_outputs(per_canvas, [[whole]] * len(images), img_size, imgs.device)
+    return _pasted((imgs,) + _seg_outputs(per_canvas, [[whole]] * len(images), img_size, imgs.device), per_canvas, img_size, rng, copy_paste)
+
+
+# ---- copy-paste of instances between the canvases of a batch (the project's own definition: include/mtbt_hip.h `mtbt_copy_paste`) ----
+PASTE_FIELDS = 8  # src_row, dx, dy, flip, 4 reserved zeros
+
+
+def copy_paste_batch(imgs: torch.Tensor, planes: torch.Tensor, row_off, gt_rows: torch.Tensor, table, *, masks: bool = True):
+    """Lay instances of the batch's canvases on its canvases.  imgs f32 [B,3,S,S], planes uint8 [M,S,pitch] (bit-packed, pitch =
+    8 ceil(S / 64), row for row with gt_rows f32 [M,6]) -- all three CUDA tensors, what a `*_samples_seg` function returns -- row_off int
+    [B + 1] on the HOST (canvas i owns the rows row_off[i] .. row_off[i + 1] - 1) and table = (paste_off int [B + 1], entries int [P, 8]) as
+    `sample_copy_paste` returns it: entry rows (src_row, dx, dy, flip, 0, 0, 0, 0) grouped by destination canvas, at most 16 per canvas,
+    later above earlier.  The rule is stated in include/mtbt_hip.h `mtbt_copy_paste`: the donor's pixels under its plane, mirrored first if
+    flip, then moved by (dx, dy); exact copies; covered parts of older planes removed; boxes tight around what stays visible.
+    Returns (imgs [B,3,S,S], masks [B,1,S,S] f32 {0,1} -- the union of each canvas's planes -- or None, gt_rows [M + P, 6], inst): the M old
+    rows first, then the P pasted ones in table order; inst = dict(planes uint8 [M+P,S,pitch], image int64 [M+P], labels int64 [M+P],
+    area int32 [M+P] visible pixels, area_before int32 [M+P] pixels before this call's layering, boxes int32 [M+P,4] x1 y1 x2 y2 with
+    exclusive maxima).  A row that later pastes cover completely stays, as (image, cls, 0, 0, 0, 0): `loss.group_gt_rows_cls` skips it.
+    The inputs are not modified.  One launch per <= 8 canvases plus a small one, no host synchronisation, no CPU path."""
+    lib = L.load()
+    for t, what in ((imgs, "imgs"), (planes, "planes"), (gt_rows, "gt_rows")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"copy_paste_batch: {what} must be a CUDA/HIP tensor on an MI355X (no CPU path)")
+    if imgs.dtype != torch.float32 or imgs.dim() != 4 or imgs.shape[1] != 3 or imgs.shape[2] != imgs.shape[3]:
+        raise ValueError("copy_paste_batch: imgs must be float32 [B, 3, S, S]")
+    B, S = int(imgs.shape[0]), int(imgs.shape[3])
+    pitch = 8 * ((S + 63) // 64)
+    if planes.dtype != torch.uint8 or planes.dim() != 3 or tuple(planes.shape[1:]) != (S, pitch):
+        raise ValueError(f"copy_paste_batch: planes must be uint8 [M, {S}, {pitch}]")
+    M = int(planes.shape[0])
+    if gt_rows.dtype != torch.float32 or tuple(gt_rows.shape) != (M, 6):
+        raise ValueError(f"copy_paste_batch: gt_rows must be float32 [{M}, 6], one row per plane")
+    ro = _int_array(row_off, (B + 1,), "copy_paste_batch", "row_off")
+    po = _int_array(table[0], (B + 1,), "copy_paste_batch", "table[0] (paste_off)")
+    ent = _int_array(np.asarray(table[1]).reshape(-1, PASTE_FIELDS), (None, PASTE_FIELDS), "copy_paste_batch", "table[1] (entries)")
+    P = int(ent.shape[0])
+    if ro[0] != 0 or po[0] != 0 or ro[-1] != M or po[-1] != P or (np.diff(ro) < 0).any() or (np.diff(po) < 0).any():
+        raise ValueError("copy_paste_batch: row_off / paste_off must start at 0, not decrease, and end at the number of planes / entries")
+    dev = imgs.device
+    imgs, planes, gt_rows = imgs.contiguous(), planes.contiguous(), gt_rows.contiguous()
+    N = M + P
+    out = torch.empty_like(imgs)
+    out_m = torch.empty(B, 1, S, S, device=dev, dtype=torch.float32) if masks else None
+    out_planes = torch.empty(N, S, pitch, device=dev, dtype=torch.uint8)
+    rows = torch.empty(N, 6, device=dev, dtype=torch.float32)
+    area_before, area = torch.empty(N, device=dev, dtype=torch.int32), torch.empty(N, device=dev, dtype=torch.int32)
+    boxes = torch.empty(N, 4, device=dev, dtype=torch.int32)
+    a = L.CopyPasteArgs()
+    a.images, a.planes, a.rows_in = imgs.data_ptr(), planes.data_ptr(), gt_rows.data_ptr()
+    a.row_off, a.paste_off, a.entries = ro.ctypes.data_as(_INT32_P), po.ctypes.data_as(_INT32_P), ent.ctypes.data_as(_INT32_P)
+    a.out_images, a.out_planes, a.out_masks, a.rows_out = out.data_ptr(), out_planes.data_ptr(), out_m.data_ptr() if masks else None, rows.data_ptr()
+    a.area_before, a.area, a.box = area_before.data_ptr(), area.data_ptr(), boxes.data_ptr()
+    a.B, a.M, a.P, a.S, a.pitch, a.entry_stride = B, M, P, S, pitch, PASTE_FIELDS
+    stream = torch.cuda.current_stream(dev)
+    L.check(lib.mtbt_copy_paste(C.byref(a), C.c_void_p(stream.cuda_stream)), "mtbt_copy_paste")
+    for t in (imgs, planes, gt_rows):   # the launches are asynchronous: keep the inputs alive until the stream has consumed them
+        t.record_stream(stream)
+    image = np.concatenate([np.repeat(np.arange(B, dtype=np.int64), np.diff(ro)), np.repeat(np.arange(B, dtype=np.int64), np.diff(po))])
+    inst = {"planes": out_planes, "image": _upload(torch.from_numpy(image), dev), "labels": rows[:, 1].to(torch.int64),
+            "area": area, "area_before": area_before, "boxes": boxes}
+    return out, out_m, rows, inst
+
+
+def _box_px(row6, S: float):
+    """A label row (image, cls, xc, yc, w, h), normalised -> (x1, y1, x2, y2) in canvas pixels, Python floats."""
+    xc, yc, w, h = (float(v) * S for v in row6[2:6])
+    return xc - w / 2, yc - h / 2, xc + w / 2, yc + h / 2
+
+
+def sample_copy_paste(boxes_per_canvas: Sequence[Sequence[Sequence[float]]], img_size: int, rng: np.random.Generator, *, prob: float = 0.5,
+                      fraction: float = 0.5, mode: str = "mix", translate: float = 0.0, max_ioa: float = 0.3, min_px: float = 2.0,
+                      max_per_canvas: int = 16):
+    """Draw the table of `copy_paste_batch` from the HOST-side label rows of the canvases, so nothing is read back from the device.
+    boxes_per_canvas: per canvas its rows (image, cls, xc, yc, w, h), normalised to the canvas, in the order of the planes; the donor row of
+    an entry is the row's index in the concatenation of all canvases.  Returns (paste_off int32 [B + 1], entries int32 [P, 8]).
+    A canvas receives pastes with probability prob.  mode "mix": its donor is one OTHER canvas drawn uniformly (none when B == 1), mirrored
+    with probability 0.5 and moved by integer offsets drawn uniformly from [-t, t], t = int(translate * S), per axis -- one donor, one flip
+    and one offset per receiving canvas, so the donor's instances keep their arrangement.  mode "flip" is the classic form: the donor is the
+    canvas itself, mirrored, not moved.  Every donor row, in row order, is a candidate with probability fraction; its box is mirrored
+    (x -> S - x) and moved like the pixels, then clipped to the canvas; it is rejected when a clipped side is below min_px, or when
+    inter(t, b) / area(b) >= max_ioa for any box b already on the canvas -- the canvas's own rows and the pastes accepted before it
+    (ultralytics' test, on boxes: it needs no plane).  At most max_per_canvas (<= 16) entries per canvas.  Donor boxes are always those of
+    the INPUT rows, as the pasted pixels are the input's.
+    The draws come in a fixed order whatever the mode -- the decisions (B), the donors (B, integers below max(B - 1, 1); a value >= the
+    canvas's own index names the next canvas), the flips (B), the offsets (B x 2: x, y; integers in [-t, t]), then, for each receiving
+    canvas with a donor in canvas order, one vector of the donor's row count for the candidates -- so a seeded generator gives the same
+    table again.  In mode "flip" the donor, flip and offset draws are made and not used."""
+    if mode not in ("mix", "flip"):
+        raise ValueError("sample_copy_paste: mode must be 'mix' or 'flip'")
+    if not 0 <= int(max_per_canvas) <= L.COPY_PASTE_MAX_ENTRIES:
+        raise ValueError(f"sample_copy_paste: max_per_canvas must lie in [0, {L.COPY_PASTE_MAX_ENTRIES}]")
+    B, S = len(boxes_per_canvas), float(img_size)
+    t = int(translate * S)
+    if not 0 <= t <= int(img_size):
+        raise ValueError("sample_copy_paste: translate must lie in [0, 1]")
+    on = rng.random(B) < prob
+    donors = rng.integers(0, max(B - 1, 1), B)
+    flips = rng.random(B) < 0.5
+    offsets = rng.integers(-t, t + 1, (B, 2))
+    first_row = np.concatenate([[0], np.cumsum([len(c) for c in boxes_per_canvas])]).astype(np.int64)
+    paste_off, entries = np.zeros(B + 1, dtype=np.int32), []
+    for i in range(B):
+        paste_off[i + 1] = paste_off[i]
+        if not on[i] or (mode == "mix" and B == 1):
+            continue
+        if mode == "mix":
+            j = int(donors[i]) + (int(donors[i]) >= i)
+            flip, dx, dy = int(flips[i]), int(offsets[i, 0]), int(offsets[i, 1])
+        else:
+            j, flip, dx, dy = i, 1, 0, 0
+        cand = rng.random(len(boxes_per_canvas[j])) < fraction
+        placed = [_box_px(r, S) for r in boxes_per_canvas[i]]
+        for k, r in enumerate(boxes_per_canvas[j]):
+            if paste_off[i + 1] - paste_off[i] >= max_per_canvas:
+                break
+            if not cand[k]:
+                continue
+            x1, y1, x2, y2 = _box_px(r, S)
+            if flip:
+                x1, x2 = S - x2, S - x1
+            x1, y1, x2, y2 = (min(max(v, 0.0), S) for v in (x1 + dx, y1 + dy, x2 + dx, y2 + dy))
+            if x2 - x1 < min_px or y2 - y1 < min_px:
+                continue
+            if any(_ioa((x1, y1, x2, y2), b) >= max_ioa for b in placed):
+                continue
+            placed.append((x1, y1, x2, y2))
+            entries.append([int(first_row[j]) + k, dx, dy, flip, 0, 0, 0, 0])
+            paste_off[i + 1] += 1
+    return paste_off, np.asarray(entries, dtype=np.int32).reshape(-1, PASTE_FIELDS)
+
+
+def _ioa(t, b) -> float:
+    """inter(t, b) / area(b) of two (x1, y1, x2, y2) boxes; 0 for a box b without area."""
+    area = (b[2] - b[0]) * (b[3] - b[1])
+    if not area > 0.0:
+        return 0.0
+    return max(min(t[2], b[2]) - max(t[0], b[0]), 0.0) * max(min(t[3], b[3]) - max(t[1], b[1]), 0.0) / area
+
+
+def _pasted(outputs, per_canvas, img_size: int, rng: np.random.Generator, copy_paste: Optional[dict]):
+    """The `copy_paste=dict(...)` option of the `*_samples_seg` functions: outputs = (imgs, masks, gt_rows, inst) of the canvases as drawn,
+    per_canvas their host-side items (label row first).  None draws nothing and returns the outputs; otherwise `sample_copy_paste` on the
+    label rows -- the last draws of the call -- then `copy_paste_batch`."""
+    if copy_paste is None:
+        return outputs
+    imgs, _, gt_rows, inst = outputs
+    row_off = np.concatenate([[0], np.cumsum([len(c) for c in per_canvas])]).astype(np.int32)
+    table = sample_copy_paste([[it[0] for it in c] for c in per_canvas], img_size, rng, **copy_paste)
+    return copy_paste_batch(imgs, inst["planes"], row_off, gt_rows, table)
 
 
 # ---- sliced inference: overlapping tiles of a large image (the project's own definition: include/mtbt_hip.h `mtbt_tile`) ----
