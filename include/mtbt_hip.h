@@ -1399,6 +1399,73 @@ int mtbt_fill_polygons(const mtbt_fill_polygons_args* a, void* stream);
 /* sizeof() of the struct above as the library was compiled: which = 0 mtbt_fill_polygons_args; -1 otherwise */
 int mtbt_sizeof_fill_polygons_args(int which);
 
+/* ---------------------------------------------------------------------------------------------
+ * Exact Euclidean distance transform of bit-packed planes (csrc/distance_transform.hip; `postprocess.distance_transform`,
+ * `signed_distance`).  Packed layout and alignment as in the surface and component sections above (planes 8-byte aligned, 8-byte
+ * accesses only, pitch = 8 * ceil(W / 64)); bits X >= W never count, whatever they hold.
+ * THE DISTANCE RULE, exact in integers (tests/edt_reference.py restates it):
+ *   d2_set    uint32 [n][H][W]  at pixel (x, y) the minimum of dy^2 + dx^2 over the SET pixels of the plane; 0 on a set pixel
+ *                               (scipy.ndimage.distance_transform_edt(~m) squared)
+ *   d2_unset  uint32 [n][H][W]  the same over the UNSET pixels inside the image; 0 on an unset pixel (distance_transform_edt(m) squared)
+ *   Sentinel  where no such pixel exists (d2_set of an empty plane, d2_unset of a full one) every word of that map is 0xFFFFFFFF.
+ *             Outside the image is neither set nor unset.
+ * Either output may be NULL (not both): the other map is still defined.  H, W in [1, 16384], so d2 < 2^29.  Every output word is
+ * defined after the call: the caller does not pre-zero.  Asynchronous on `stream`, no host synchronisation, no global atomics,
+ * deterministic, graph-capturable.  The planes are taken in chunks that share `workspace`
+ * (>= mtbt_distance_transform_workspace_bytes(n, H, W), 16-byte aligned; the query returns MTBT_EINVAL for a shape refused below).
+ * MTBT_EINVAL before any launch: NULL args or packed, both outputs NULL, workspace NULL when the query is > 0, n < 0, H or W outside
+ * [1, 16384], pitch != 8 * ceil(W / 64), workspace_bytes below the query.  MTBT_EALIGN: packed not 8-byte, workspace not 16-byte, an
+ * output not 4-byte aligned.  n == 0 launches nothing. */
+typedef struct mtbt_distance_transform_args {
+  const uint8_t* packed;   /* [n][H][pitch] */
+  void* workspace;
+  int64_t workspace_bytes;
+  uint32_t* d2_set;        /* [n][H][W] or NULL */
+  uint32_t* d2_unset;      /* [n][H][W] or NULL */
+  int32_t n, H, W, pitch;
+} mtbt_distance_transform_args;
+int64_t mtbt_distance_transform_workspace_bytes(int n, int H, int W);
+int mtbt_distance_transform(const mtbt_distance_transform_args* a, void* stream);
+
+/* The region terms of the segmentation loss over those maps (`loss.seg_region_loss`, `SegRegionLoss`, `TrainStep(seg_dice_weight=,
+ * seg_boundary_weight=)`); not terms of the reference's loss.  With z = logits + bias (bias: one float on the device, or NULL),
+ * p = sigmoid(z), t the target bit of the packed plane and N = H * W:
+ *   THE DICE RULE      per image I = sum p t, P = sum p, T = sum t; dice = mean over images of 1 - (2 I + smooth) / (P + T + smooth)
+ *                      (MONAI's DiceLoss(sigmoid=True) per sample: one `smooth` in numerator and denominator).
+ *   THE BOUNDARY RULE  phi = +sqrt(d2_set) on an unset pixel, -(sqrt(d2_unset) - 1) on a set pixel (Kervadec et al. 2019, one_hot2dist:
+ *                      edt(neg) * neg - (edt(pos) - 1) * pos); phi = 0 wherever the map it needs holds the sentinel, so an empty and a
+ *                      full plane contribute nothing; boundary = (1 / (B N)) sum phi p.
+ *   out[0..2]          dice, boundary, w_dice * dice + w_boundary * boundary (fp32)
+ *   d_logits           fp32 [B][H][W] or NULL: the gradient of out[2] with respect to the logits, written, or with accumulate = 1 ADDED
+ *                      to what the buffer holds
+ * Arithmetic: sigmoid in fp32; the per-image sums in fp64 in a fixed order (the same inputs give the same bits on every run); the Dice
+ * gradient's per-image factor -[2 t (P + T + smooth) - (2 I + smooth)] / (P + T + smooth)^2 * w_dice / B in fp64, cast once; sqrt of
+ * (double)d2, cast to fp32.  d2_set and d2_unset (the outputs of mtbt_distance_transform for `targets`) are given both or neither; they
+ * may be NULL only with w_boundary == 0 (phi is then 0).  Asynchronous on `stream`, no host synchronisation, no atomics, graph-capturable.
+ * `workspace`: >= mtbt_seg_region_loss_workspace_bytes(B, H, W) bytes, 16-byte aligned (the query returns MTBT_EINVAL for a shape refused
+ * below).  MTBT_EINVAL before any launch: NULL args / logits / targets / out / workspace, B outside [1, 65535], H or W outside [1, 16384],
+ * pitch != 8 * ceil(W / 64), smooth, w_dice or w_boundary negative, NaN or infinite, one map without the other, w_boundary != 0 without
+ * maps, accumulate other than 0 or 1, workspace_bytes below the query.  MTBT_EALIGN: targets not 8-byte, workspace not 16-byte, the
+ * other pointers not 4-byte aligned. */
+typedef struct mtbt_seg_region_args {
+  const float* logits;       /* [B][H][W] */
+  const float* bias;         /* 1 value on the device, or NULL */
+  const uint8_t* targets;    /* [B][H][pitch] */
+  const uint32_t* d2_set;    /* [B][H][W] or NULL */
+  const uint32_t* d2_unset;  /* [B][H][W] or NULL */
+  float* d_logits;           /* [B][H][W] or NULL */
+  void* workspace;
+  int64_t workspace_bytes;
+  float* out;                /* [3] */
+  int32_t B, H, W, pitch;
+  float smooth, w_dice, w_boundary;
+  int32_t accumulate;
+} mtbt_seg_region_args;
+int64_t mtbt_seg_region_loss_workspace_bytes(int B, int H, int W);
+int mtbt_seg_region_loss(const mtbt_seg_region_args* a, void* stream);
+/* sizeof() of the structs above as the library was compiled: which = 0 mtbt_distance_transform_args, 1 mtbt_seg_region_args; -1 otherwise */
+int mtbt_sizeof_distance_args(int which);
+
 /* Weight gradient of a k x k convolution (any stride / padding; 1x1 and the 2x2 stride-2 downsample included), bf16 (MFMA) or fp32 operands:
  *   dw[k][r][s][c] (fp32, packed [K][R*S*C] like the forward weight) (+)= sum_p dy[p][k] * x[n][y*stride + r - pad][x*stride + s - pad][c]
  * x [N,H,W,C], dy [N,Ho,Wo,K] (Ho = (H + 2 pad - R) / stride + 1) NHWC with pixel / batch strides in elements (multiples of 8; C % 8 == K % 8 == 0;

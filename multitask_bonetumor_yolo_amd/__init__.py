@@ -21,6 +21,8 @@
     from multitask_bonetumor_yolo_amd import fill_polygons, yolo_seg_planes, augment_samples_seg   # polygon labels -> packed instance masks
     from multitask_bonetumor_yolo_amd import clahe_batch                 # tile-wise contrast equalisation (CLAHE) of the raw uint8 images
     from multitask_bonetumor_yolo_amd import copy_paste_batch, sample_copy_paste   # instances pasted between the canvases of a batch
+    from multitask_bonetumor_yolo_amd import distance_transform, signed_distance   # exact Euclidean distance maps of packed masks
+    from multitask_bonetumor_yolo_amd import seg_region_loss, SegRegionLoss   # soft Dice + boundary terms of the segmentation loss
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
@@ -32,7 +34,8 @@ from .preprocess import copy_paste_batch, sample_copy_paste  # noqa: F401
 from .preprocess import (augment_batch, augment_polygons, augment_samples, augment_samples_seg, augment_yolo_labels, clahe_batch, clahe_clip,  # noqa: F401
                          letterbox_geometry, mosaic_batch, mosaic_polygons, mosaic_samples, mosaic_samples_seg, mosaic_yolo_labels, photometric_lut,
                          sample_clahe, sample_geometry, sample_mosaic, sample_photometric, slice_batch, slice_geometry)
-from .loss import InstanceMaskLoss, TaskAlignedDetLoss, TaskAlignedSegLoss, instance_mask_loss, multitask_loss, task_aligned_det_loss  # noqa: F401
+from .loss import (InstanceMaskLoss, SegRegionLoss, TaskAlignedDetLoss, TaskAlignedSegLoss, instance_mask_loss, multitask_loss,  # noqa: F401
+                   seg_region_loss, task_aligned_det_loss)
 from .checkpoints import load_pretrained_heads, load_train_state, save_train_state, strip_lightning_prefix  # noqa: F401
 from .graphed import GraphedInference  # noqa: F401
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision,  # noqa: F401
@@ -40,8 +43,8 @@ from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, 
                       lesion_hits, surface_distances, surface_metrics)
 from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
-from .postprocess import (components_to_instances, fill_polygons, filter_components, label_components, merge_tiles, vote_masks,  # noqa: F401
-                          vote_tile_masks, yolo_seg_planes)
+from .postprocess import (components_to_instances, distance_transform, fill_polygons, filter_components, label_components, merge_tiles, vote_masks,  # noqa: F401
+                          signed_distance, vote_tile_masks, yolo_seg_planes)
 from .sliced import detect_sliced  # noqa: F401
 from .trainstep import TrainStep, ema_decay_at  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

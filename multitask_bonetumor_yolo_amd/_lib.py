@@ -257,6 +257,18 @@ class CopyPasteArgs(C.Structure):  # mtbt_copy_paste_args
                 ("B", C.c_int32), ("M", C.c_int32), ("P", C.c_int32), ("S", C.c_int32), ("pitch", C.c_int32), ("entry_stride", C.c_int32)]
 
 
+class DistanceTransformArgs(C.Structure):  # mtbt_distance_transform_args
+    _fields_ = [("packed", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("d2_set", C.c_void_p),
+                ("d2_unset", C.c_void_p), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32)]
+
+
+class SegRegionArgs(C.Structure):  # mtbt_seg_region_args
+    _fields_ = [("logits", C.c_void_p), ("bias", C.c_void_p), ("targets", C.c_void_p), ("d2_set", C.c_void_p), ("d2_unset", C.c_void_p),
+                ("d_logits", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("out", C.c_void_p),
+                ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32),
+                ("smooth", C.c_float), ("w_dice", C.c_float), ("w_boundary", C.c_float), ("accumulate", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -401,6 +413,11 @@ SYMBOLS = {
     "mtbt_sizeof_clahe_args": (C.c_int, [C.c_int]),
     "mtbt_copy_paste": (C.c_int, [C.POINTER(CopyPasteArgs), C.c_void_p]),
     "mtbt_sizeof_copy_paste_args": (C.c_int, [C.c_int]),
+    "mtbt_distance_transform_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mtbt_distance_transform": (C.c_int, [C.POINTER(DistanceTransformArgs), C.c_void_p]),
+    "mtbt_seg_region_loss_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mtbt_seg_region_loss": (C.c_int, [C.POINTER(SegRegionArgs), C.c_void_p]),
+    "mtbt_sizeof_distance_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -412,6 +429,7 @@ COMPONENTS_STRUCTS = (ComponentsArgs, SelectComponentsArgs)   # order of mtbt_si
 POLYGON_STRUCTS = (FillPolygonsArgs,)   # order of mtbt_sizeof_fill_polygons_args(which)
 CLAHE_STRUCTS = (ClaheImage,)   # order of mtbt_sizeof_clahe_args(which)
 COPY_PASTE_STRUCTS = (CopyPasteArgs,)   # order of mtbt_sizeof_copy_paste_args(which)
+DISTANCE_STRUCTS = (DistanceTransformArgs, SegRegionArgs)   # order of mtbt_sizeof_distance_args(which)
 _lib = None
 
 
@@ -436,7 +454,8 @@ def load():
         for sizeof, structs in ((lib.mtbt_sizeof_frame_args, FRAME_STRUCTS), (lib.mtbt_sizeof_mask_eval_args, MASK_EVAL_STRUCTS),
                                 (lib.mtbt_sizeof_tile_args, TILE_STRUCTS), (lib.mtbt_sizeof_surface_args, SURFACE_STRUCTS),
                                 (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS), (lib.mtbt_sizeof_fill_polygons_args, POLYGON_STRUCTS),
-                                (lib.mtbt_sizeof_clahe_args, CLAHE_STRUCTS), (lib.mtbt_sizeof_copy_paste_args, COPY_PASTE_STRUCTS)):
+                                (lib.mtbt_sizeof_clahe_args, CLAHE_STRUCTS), (lib.mtbt_sizeof_copy_paste_args, COPY_PASTE_STRUCTS),
+                                (lib.mtbt_sizeof_distance_args, DISTANCE_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

@@ -13,7 +13,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib as L
-from .postprocess import _mask_call, _need_cuda, _nhwc_rows, _stream
+from .postprocess import _mask_call, _need_cuda, _nhwc_rows, _stream, distance_transform, pack_masks
 
 
 def group_gt_boxes(gt_boxes: torch.Tensor, n_images: int, img_size: float):
@@ -67,12 +67,14 @@ def det_loss_args(det_maps: Sequence[torch.Tensor], gt_boxes: torch.Tensor, *, i
 def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_logits: torch.Tensor, gt_boxes: torch.Tensor,
                    gt_masks: torch.Tensor, gt_cls: torch.Tensor, proj_weight: torch.Tensor, proj_bias: torch.Tensor, *, img_size: int,
                    nc_det: int, reg_max: int = 16, iou_match_thresh: float = 0.5, label_smoothing: float = 0.0, training: bool = True,
-                   weights=(1.0, 2.0, 1.5, 0.5, 1.0), with_grads: bool = False, grad_out=None):
+                   weights=(1.0, 2.0, 1.5, 0.5, 1.0), with_grads: bool = False, grad_out=None, want_seg_logits: bool = False):
     """det_maps: the raw Detect maps of `forward(x, "train")` (3 x [B, 4*reg_max+nc, h, w]); protos [B, nm, hp, wp];
     gt_masks [B,1,S,S] float; gt_cls [B] int64; proj_*: the trainer's `seg_proto_projector` (`:186`).
     Returns the reference's tuple as 0-d fp32 tensors: (total, seg, box, dfl, cls_det, img_cls[, n_pos, mean matched IoU]).
     `with_grads=True` returns `(that tuple, grads)` where grads = d total / d {det_maps (list, like det_maps), seg_logits [B,1,S,S]
-    (the projector output after the bilinear resize, `:251-255`), img_logits}: the first operator of the backward pass."""
+    (the projector output after the bilinear resize, `:251-255`), img_logits}: the first operator of the backward pass.
+    `want_seg_logits=True` appends one more element to what is returned: the fp32 [B, 1, S, S] segmentation logits this function builds
+    anyway, WITHOUT the projector bias (the kernels add it), for `seg_region_loss(..., bias=proj_bias)`."""
     lib = L.load()
     _need_cuda(det_maps[0], "multitask_loss")
     dev = det_maps[0].device
@@ -98,7 +100,7 @@ def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_l
     res = tuple(out[i] for i in range(8 if training else 6))
     if not with_grads:
         del keep
-        return res
+        return (res, seg_logits.view(B, 1, img_size, img_size)) if want_seg_logits else res
     # gradient of the total w.r.t. the head outputs (csrc/loss.hip: det_loss_grad_kernel, seg_img_grad_kernel)
     no = 4 * reg_max + nc_det
     # grad_out = {"det_maps": [NHWC fp32 buffers], "img_logits": [B, n] fp32}: write straight into a training plan's input buffers
@@ -112,7 +114,7 @@ def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_l
     del keep
     grads = {"det_maps": [t.permute(0, 3, 1, 2) for t in d_maps],      # [B, no, h, w] views of channels-last memory
              "seg_logits": d_seg.view(B, 1, img_size, img_size), "img_logits": d_img}
-    return res, grads
+    return (res, grads, seg_logits.view(B, 1, img_size, img_size)) if want_seg_logits else (res, grads)
 
 
 # ---- instance-mask loss (YOLOv8-seg single_mask_loss / crop_mask): csrc/mask_loss.hip ------------------------------------------
@@ -243,6 +245,107 @@ class InstanceMaskLoss(torch.autograd.Function):
     def backward(ctx, g_loss, _g_npos):
         d_mc, d_pr = ctx.saved_tensors
         return ((d_mc * g_loss).to(ctx.dtypes[0]), (d_pr * g_loss).to(ctx.dtypes[1])) + (None,) * (7 + ctx.n_maps)
+
+
+# ---- region terms of the segmentation loss (soft Dice, Kervadec's boundary loss): csrc/distance_transform.hip ------------------
+def seg_region_loss(seg_logits: torch.Tensor, gt_masks: torch.Tensor, *, bias: Optional[torch.Tensor] = None, dice_weight: float = 1.0,
+                    boundary_weight: float = 0.0, smooth: float = 1.0, with_grads: bool = False, grad_out: Optional[torch.Tensor] = None,
+                    accumulate: bool = False, W: Optional[int] = None):
+    """Soft Dice and the boundary loss of the semantic segmentation head on the device (definitions: include/mtbt_hip.h,
+    `mtbt_seg_region_args`).  Extensions beyond the reference's `_multitask_loss`, whose segmentation term is BCE alone.
+
+    seg_logits: [B, 1, H, W] or [B, H, W] fp32 logits; `bias` (one fp32 value on the device) is added in the kernel, so the bias-free
+    tensor of `multitask_loss(want_seg_logits=True)` can be passed as it is.  gt_masks: [B, 1, H, W] or [B, H, W] float, bool or uint8,
+    packed through `pack_masks` (bit = value > 0); with `W=` given, gt_masks is taken as already packed uint8 [B, H, pitch] planes of
+    that width.  Returns (dice, boundary, dice_weight * dice + boundary_weight * boundary) as 0-d fp32 device tensors without autograd
+    history.  The distance transform of the targets runs only when boundary_weight != 0 (boundary is 0 otherwise).
+    `with_grads=True` returns `(that tuple, {"seg_logits": [B, 1, H, W] fp32})`, the gradient of the weighted sum.  `grad_out` = a
+    contiguous fp32 buffer of B * H * W elements takes the gradient instead of a fresh tensor; `accumulate=True` ADDS it to what the
+    buffer holds (`TrainStep` adds it to the BCE gradient that way).  Asynchronous: no host synchronisation."""
+    if seg_logits.dim() == 4 and seg_logits.shape[1] == 1:
+        seg_logits = seg_logits[:, 0]
+    if seg_logits.dim() != 3 or seg_logits.dtype != torch.float32:
+        raise ValueError(f"seg_region_loss: seg_logits must be fp32 [B, 1, H, W] or [B, H, W], not {seg_logits.dtype} {tuple(seg_logits.shape)}")
+    B, H, Wd = (int(v) for v in seg_logits.shape)
+    pitch = 8 * ((Wd + 63) // 64)
+    dev = seg_logits.device
+    if not float(dice_weight) >= 0 or not float(boundary_weight) >= 0 or not float(smooth) >= 0:
+        raise ValueError("seg_region_loss: dice_weight, boundary_weight and smooth must be >= 0")
+    if B < 1:
+        raise ValueError("seg_region_loss: an empty batch")
+    if W is not None:
+        if int(W) != Wd or gt_masks.dtype != torch.uint8 or tuple(gt_masks.shape) != (B, H, pitch):
+            raise ValueError(f"seg_region_loss: packed gt_masks of width {W} must be uint8 [{B}, {H}, {pitch}] for logits {tuple(seg_logits.shape)}")
+    else:
+        dense = gt_masks[:, 0] if gt_masks.dim() == 4 and gt_masks.shape[1] == 1 else gt_masks
+        if tuple(dense.shape) != (B, H, Wd):
+            raise ValueError(f"seg_region_loss: gt_masks {tuple(gt_masks.shape)} does not fit logits {tuple(seg_logits.shape)}")
+    _need_cuda(seg_logits, "seg_region_loss")
+    _need_cuda(gt_masks, "seg_region_loss")
+    lib = L.load()
+    if W is not None:
+        planes = gt_masks.contiguous()
+        planes = planes if planes.data_ptr() % 8 == 0 else planes.clone()
+    else:
+        planes = pack_masks(dense if dense.dtype in (torch.bool, torch.uint8, torch.float32) else dense.float())
+    z = seg_logits.detach().contiguous()
+    keep = [z, planes]
+    a = L.SegRegionArgs()
+    a.logits, a.targets = z.data_ptr(), planes.data_ptr()
+    if bias is not None:
+        _need_cuda(bias, "seg_region_loss")
+        if bias.numel() != 1:
+            raise ValueError("seg_region_loss: bias is one value")
+        bias = bias.detach().reshape(-1).float().contiguous()
+        keep.append(bias)
+        a.bias = bias.data_ptr()
+    if float(boundary_weight) != 0:
+        keep += list(distance_transform(planes, Wd, to="both"))
+        a.d2_set, a.d2_unset = keep[-2].data_ptr(), keep[-1].data_ptr()
+    grads = None
+    if with_grads or grad_out is not None:
+        if grad_out is not None:
+            if grad_out.dtype != torch.float32 or grad_out.numel() != B * H * Wd or not grad_out.is_contiguous() or grad_out.device != dev:
+                raise ValueError(f"seg_region_loss: grad_out must be a contiguous fp32 buffer of {B} * {H} * {Wd} elements on {dev}")
+            d = grad_out
+        else:
+            d = (torch.zeros if accumulate else torch.empty)((B, H, Wd), dtype=torch.float32, device=dev)
+        a.d_logits, a.accumulate = d.data_ptr(), int(bool(accumulate))
+        grads = {"seg_logits": d.view(B, 1, H, Wd)}
+    nbytes = int(lib.mtbt_seg_region_loss_workspace_bytes(B, H, Wd))
+    if nbytes < 0:
+        L.check(nbytes, "mtbt_seg_region_loss_workspace_bytes")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
+    a.B, a.H, a.W, a.pitch = B, H, Wd, pitch
+    a.smooth, a.w_dice, a.w_boundary = float(smooth), float(dice_weight), float(boundary_weight)
+    with torch.cuda.device(dev):
+        L.check(lib.mtbt_seg_region_loss(C.byref(a), _stream(dev)), "mtbt_seg_region_loss")
+    del keep
+    res = (out[0], out[1], out[2])
+    return (res, grads) if grads is not None else res
+
+
+class SegRegionLoss(torch.autograd.Function):
+    """`dice_weight * dice + boundary_weight * boundary` as an autograd node for the drop-in route: a trainer adds element 0 to the loss
+    it computes on its own segmentation logits (the full logits, bias included).
+        SegRegionLoss.apply(seg_logits, gt_masks, dice_weight, boundary_weight, smooth) -> (weighted sum, dice, boundary)
+    Forward runs the value and the gradient; backward scales it by the incoming gradient and hands it out in the logits' dtype."""
+
+    @staticmethod
+    def forward(ctx, seg_logits, gt_masks, dice_weight=1.0, boundary_weight=0.0, smooth=1.0):
+        (dice, boundary, total), g = seg_region_loss(seg_logits.detach().float(), gt_masks, dice_weight=dice_weight, boundary_weight=boundary_weight,
+                                                     smooth=smooth, with_grads=True)
+        ctx.save_for_backward(g["seg_logits"])
+        ctx.shape, ctx.dtype = seg_logits.shape, seg_logits.dtype
+        ctx.mark_non_differentiable(dice, boundary)
+        return total, dice, boundary
+
+    @staticmethod
+    def backward(ctx, g_total, _g_dice, _g_boundary):
+        (d,) = ctx.saved_tensors
+        return (d * g_total).view(ctx.shape).to(ctx.dtype), None, None, None, None
 
 
 # ---- task-aligned detection loss (TaskAlignedAssigner + CIoU + DFL + BCE over all anchors): csrc/det_loss_tal.hip ---------------

@@ -828,6 +828,53 @@ def components_to_instances(packed: torch.Tensor, W: int, *, max_instances: int 
     return {"masks": masks, "boxes": boxes, "areas": areas, "counts": counts}
 
 
+# ---- exact Euclidean distance transform of bit-packed planes (include/mtbt_hip.h `mtbt_distance_transform`) -------------------------
+D2_NONE = 0xFFFFFFFF             # the word of a map whose plane holds no target pixel at all
+
+
+def distance_transform(packed: torch.Tensor, W: int, *, to: str = "set"):
+    """Squared Euclidean distance maps of n bit-packed planes, exact integers, on the device (`mtbt_distance_transform`).
+
+    packed: uint8 [n, H, pitch] with pitch = 8 * ceil(W / 64) (`pack_masks`, `masks_to_frames`); bits X >= W never count.
+    `to="set"`: uint32 [n, H, W], at every pixel the minimum of dy^2 + dx^2 over the SET pixels of its plane (0 on a set pixel;
+    `scipy.ndimage.distance_transform_edt(~m) ** 2`).  `to="unset"`: the same over the unset pixels inside the image
+    (`distance_transform_edt(m) ** 2`).  `to="both"`: the pair (to set, to unset) from one call.  A map whose plane holds no such
+    pixel (an empty plane; a full one) is `D2_NONE` = 0xFFFFFFFF everywhere.  Asynchronous: no host synchronisation."""
+    if to not in ("set", "unset", "both"):
+        raise ValueError(f"distance_transform: to = 'set', 'unset' or 'both', not {to!r}")
+    W = int(W)
+    n, H, pitch, planes, _ = _component_planes("distance_transform", packed, W)
+    dev = packed.device
+    d_set = torch.empty((n, H, W), dtype=torch.uint32, device=dev) if to != "unset" else None
+    d_unset = torch.empty((n, H, W), dtype=torch.uint32, device=dev) if to != "set" else None
+    if n:
+        lib = L.load()
+        ws_bytes = int(lib.mtbt_distance_transform_workspace_bytes(n, H, W))
+        if ws_bytes < 0:
+            L.check(ws_bytes, "mtbt_distance_transform_workspace_bytes")
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        a = L.DistanceTransformArgs()
+        a.packed, a.workspace, a.workspace_bytes = planes.data_ptr(), ws.data_ptr(), ws_bytes
+        a.d2_set = d_set.data_ptr() if d_set is not None else None
+        a.d2_unset = d_unset.data_ptr() if d_unset is not None else None
+        a.n, a.H, a.W, a.pitch = n, H, W, pitch
+        with torch.cuda.device(dev):
+            L.check(lib.mtbt_distance_transform(C.byref(a), _stream(dev)), "mtbt_distance_transform")
+    return (d_set, d_unset) if to == "both" else (d_set if to == "set" else d_unset)
+
+
+def signed_distance(packed: torch.Tensor, W: int) -> torch.Tensor:
+    """The signed distance map of Kervadec et al.'s boundary loss (`one_hot2dist`), fp32 [n, H, W]: +sqrt(d2 to set) on an unset pixel,
+    -(sqrt(d2 to unset) - 1) on a set pixel, 0 where the map it needs has no target (an empty and a full plane are zero everywhere).
+    `distance_transform(to="both")` and torch ops on its maps (sqrt in float64: above 2^24 a float32 no longer holds d2)."""
+    d_set, d_unset = distance_transform(packed, W, to="both")
+    t = unpack_masks(packed, int(W))
+    d2 = torch.where(t, d_unset.to(torch.int64), d_set.to(torch.int64))
+    d = d2.to(torch.float64).sqrt().to(torch.float32)
+    phi = torch.where(t, -(d - 1.0), d)
+    return torch.where(d2 == D2_NONE, torch.zeros_like(phi), phi)
+
+
 # ---- polygons -> bit-packed planes (the project's own fill rule: include/mtbt_hip.h `mtbt_fill_polygons`) ---------------------------
 POLYGON_MAX_COORD = 32768.0      # |v| in pixels: 16 v fits int32 with room, and stays inside the kernel's clamp
 

@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import code_of, reserved_stream
-from .loss import instance_mask_loss, multitask_loss, task_aligned_det_loss
+from .loss import instance_mask_loss, multitask_loss, seg_region_loss, task_aligned_det_loss
 from .dist_train import FlatBuckets
 from .train import TrainPlan, make_arena
 
@@ -100,7 +100,8 @@ class TrainStep:
                  betas=(0.9, 0.999), eps: float = 1e-8, momentum: float = 0.9, nesterov: bool = False, clip_norm: Optional[float] = 10.0,
                  iou_match_thresh: float = 0.5, label_smoothing: float = 0.1, loss_weights=(1.0, 2.0, 1.5, 0.5, 1.0),
                  projector: Optional[nn.Conv2d] = None, process_group=None, overlap: bool = True, instance_mask_weight: float = 0.0, ema=None,
-                 det_loss: str = "reference", tal=None, mask_assign: str = "iou"):
+                 det_loss: str = "reference", tal=None, mask_assign: str = "iou", seg_dice_weight: float = 0.0,
+                 seg_boundary_weight: float = 0.0, seg_dice_smooth: float = 1.0):
         """batch_shape [B,3,S,S] per rank.  `projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1),
         running_main_v3.py:186); created (seeded default init) when not given.  A live `torch.distributed` process group with more than
         one rank turns on the gradient exchange; parameters are broadcast from rank 0 first (what DDP does at construction).
@@ -117,7 +118,15 @@ class TrainStep:
         `mask_assign="tal"` (needs `det_loss="tal"` and `instance_mask_weight` > 0) gives the instance-mask term the task-aligned
         assignment's foreground anchors and their assigned GT rows in place of its own IoU match (`v8SegmentationLoss`): the mask
         positives' count (element 9) then equals the number of foreground anchors (element 6) and `iou_match_thresh` is not read.
-        "iou" (default): nothing changes."""
+        "iou" (default): nothing changes.
+        `seg_dice_weight` / `seg_boundary_weight` > 0 add the region terms of `loss.seg_region_loss` (csrc/distance_transform.hip: soft
+        Dice with `seg_dice_smooth`, Kervadec's boundary loss over the device distance transform of the step's masks; not terms of the
+        reference's loss) to the total: their gradient is added to the BCE gradient of the segmentation logits before the projector's
+        backward, and two elements are appended after everything else: dice, boundary.  They are plain attributes of the same names,
+        read at every step, so a schedule is an assignment between steps.  With both at 0 (default) nothing changes."""
+        self.seg_dice_weight, self.seg_boundary_weight, self.seg_dice_smooth = float(seg_dice_weight), float(seg_boundary_weight), float(seg_dice_smooth)
+        if not self.seg_dice_weight >= 0 or not self.seg_boundary_weight >= 0 or not self.seg_dice_smooth >= 0:
+            raise ValueError("seg_dice_weight, seg_boundary_weight and seg_dice_smooth must be >= 0")
         if det_loss not in ("reference", "tal"):
             raise ValueError(f"det_loss: 'reference' (the reference trainer's _multitask_loss) or 'tal' (task-aligned), not {det_loss!r}")
         self.det_loss = det_loss
@@ -268,7 +277,8 @@ class TrainStep:
     def step(self, x: torch.Tensor, gt_boxes: torch.Tensor, gt_masks: torch.Tensor, gt_cls: torch.Tensor) -> torch.Tensor:
         """One optimisation step on this rank's shard.  Returns the loss tuple of `_multitask_loss` as an 8-element device tensor view
         (total, seg, box, dfl, cls_det, img_cls, #positives, mean matched IoU) -- no host synchronisation.  With `instance_mask_weight` > 0
-        the total includes `weight * mask_loss` and two elements are appended: mask_loss and its positive count."""
+        the total includes `weight * mask_loss` and two elements are appended: mask_loss and its positive count.  With a region weight
+        > 0 the total includes the weighted region terms and two more elements follow after everything else: dice, boundary."""
         loss = self.forward_backward(x, gt_boxes, gt_masks, gt_cls)
         self._clip_and_update()
         self.m.mark_weights_updated()                      # inference plans folded the old weights
@@ -280,10 +290,14 @@ class TrainStep:
         tp, lib, dev = self.tp, self.lib, self.dev
         tp.run_forward(x)
         nm = self.m.proto_ch
-        res, g = multitask_loss([m.nchw() for m in tp.det_maps], tp.protos.nchw(), tp.logits, gt_boxes, gt_masks, gt_cls, self.projector.weight,
-                                self.projector.bias, with_grads=True,
-                                grad_out={"det_maps": [d.buf for d in tp.d_in["det"]], "img_logits": tp.d_in["logits"]}, **self.loss_kw)
+        region = self.seg_dice_weight > 0 or self.seg_boundary_weight > 0
+        res, g, *seg_logits = multitask_loss([m.nchw() for m in tp.det_maps], tp.protos.nchw(), tp.logits, gt_boxes, gt_masks, gt_cls,
+                                             self.projector.weight, self.projector.bias, with_grads=True, want_seg_logits=region,
+                                             grad_out={"det_maps": [d.buf for d in tp.d_in["det"]], "img_logits": tp.d_in["logits"]}, **self.loss_kw)
         dseg = g["seg_logits"]
+        if region:                   # ADDED to the BCE gradient in dseg: the projector's backward below then carries both
+            reg = seg_region_loss(seg_logits[0], gt_masks.to(dev), bias=self.projector.bias, dice_weight=self.seg_dice_weight,
+                                  boundary_weight=self.seg_boundary_weight, smooth=self.seg_dice_smooth, grad_out=dseg, accumulate=True)[0]
         assigned = None
         if self.det_loss == "tal":   # overwrites d_in["det"] whole
             r = task_aligned_det_loss([m.nchw() for m in tp.det_maps], gt_boxes, img_size=self.S, nc_det=self.loss_kw["nc_det"],
@@ -303,9 +317,11 @@ class TrainStep:
                                             self.pj_grad.data_ptr(), self.pj_grad.data_ptr() + 4 * nm, 0, self.B, self.S // 4, self.S // 4, nm, self.S, self.S,
                                             self.pj_ws.data_ptr(), self.pj_ws.numel() * 4, _s(dev)), "mtbt_projector_backward")
         self._backward_and_exchange()
-        if mask is None:
-            return torch.stack(res)
-        return torch.stack((res[0] + self.mask_w * mask[0],) + tuple(res[1:]) + mask)
+        if mask is not None:
+            res = (res[0] + self.mask_w * mask[0],) + tuple(res[1:]) + mask
+        if region:
+            res = (res[0] + reg[2],) + tuple(res[1:]) + reg[:2]
+        return torch.stack(res)
 
     def _backward_and_exchange(self):
         main = torch.cuda.current_stream(self.dev)
@@ -463,7 +479,8 @@ class TrainStep:
                             (`checkpoints.strip_lightning_prefix` reads it);
           "ema_state_dict"  the same names without the `net.` prefix, from the averaged weights (only with `ema=`);
           "optimizer"       {name: {"exp_avg", "exp_avg_sq"}} or {name: {"momentum_buffer"}}, the names of "state_dict";
-          "steps", "ema_updates", "lr", "optimizer_name", "det_loss", "mask_assign".
+          "steps", "ema_updates", "lr", "optimizer_name", "det_loss", "mask_assign";
+          "seg_dice_weight", "seg_boundary_weight", "seg_dice_smooth": the region weights at the time of saving, for the record only.
         Every tensor is keyed by parameter name and has the parameter's own shape, so the file does not depend on the bucket layout."""
         sd, esd = self._live_tensors()
         out = {"state_dict": {k: _cpu(v) for k, v in sd.items()}}
@@ -475,6 +492,9 @@ class TrainStep:
                 opt.setdefault(name, {})[slot] = _cpu(v)
         out.update(optimizer=opt, steps=int(self.steps), ema_updates=int(self.ema_updates), lr=float(self.lr), optimizer_name=str(self.opt),
                    det_loss=str(self.det_loss), mask_assign=str(self.mask_assign))
+        # informational (the weights are attributes a schedule moves: loading checks none of them, and a state without them loads)
+        out.update(seg_dice_weight=float(self.seg_dice_weight), seg_boundary_weight=float(self.seg_boundary_weight),
+                   seg_dice_smooth=float(self.seg_dice_smooth))
         return out
 
     @torch.no_grad()
