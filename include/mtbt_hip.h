@@ -652,6 +652,90 @@ int mtbt_vote_tile_masks(const mtbt_tile_mask_args* a, const mtbt_frame* frames,
 int mtbt_sizeof_tile_args(int which);
 
 /* ---------------------------------------------------------------------------------------------
+ * The SEMANTIC mask in the original image frame (mtbt_seg_to_frames): the trainer's seg_proto_projector (a 1x1 conv over the 32
+ * prototypes, running_main_v3.py:186, :251-257) averaged over several forward passes -- the views of test-time augmentation, the
+ * models of an ensemble, the tiles of sliced inference -- and sampled at the image's own pixels, one bit per pixel and optionally the
+ * averaged logit itself.  The reference has NO counterpart of the averaging; this arithmetic is the project's own definition
+ * (tests/seg_frame_reference.py restates it).  Every fp32 operation below is one correctly rounded operation in the order written (no
+ * FMA contraction).
+ *
+ * SOURCES.  Image n owns sources s in [first[n], first[n+1]), at most 64 (MTBT_TILE_MAX_PER_IMAGE).  A source is one forward pass over
+ * one window of the image:
+ *   tiles[s]      its mtbt_tile descriptor exactly as sliced inference writes it (window wx0..wy1, step, pox, poy, height, width).  A
+ *                 whole-image pass (a TTA view, an ensemble member) is the descriptor of the full view: window = the frame, pox = poy = 0,
+ *                 step = the frame's
+ *   sources[s]    pass, slot: its prototypes P_s = protos[pass] + slot * G * G * 32, fp32 NHWC [G, G, 32] in the frame of its own VIEW
+ *                 (hp == wp == G, nm == 32); pass < n_passes <= 64, slot < pass_items[pass]
+ *                 orient 0..7: the dihedral view the pass saw, codes as in mtbt_augment_batch;  weight > 0;
+ *                 proj: row of the projector table q float [n_proj, 33], 32 weights then the bias;  blend 0 or 1
+ * LAUNCH 1, the projector at prototype resolution, into the caller's fp32 workspace [n_sources, G, G] (source s at s * G * G):
+ *   L_s[y,x] = (((0 + q[j,0] * P_s[y,x,0]) + q[j,1] * P_s[y,x,1]) + ... + q[j,31] * P_s[y,x,31]) + q[j,32]          j = proj_s
+ *   a serial fp32 sum, c ascending, multiply then add, the bias last (NOT the MFMA order of the instance kernels).
+ * LAUNCH 2, the blend into the frame.  For frame pixel (X, Y) of image n, over the sources s ascending whose window holds (X, Y), with
+ * num = den = 0 at the start:
+ *   (x0, x1, lx) = mtbt_vote_tile_masks' tap of X with step_s, pox_s against G;  (y0, y1, ly) likewise with poy_s
+ *   U_s[y,x]     = L_s[fy(a), fx(b)],  (a,b) = (x,y) if orient bit 2 else (y,x),  fy(a) = G-1-a if bit 1,  fx(b) = G-1-b if bit 0
+ *                  (mtbt_vote_masks' upright rule)
+ *   tap          = (1-ly)*((1-lx)*U[y0,x0] + lx*U[y0,x1]) + ly*((1-lx)*U[y1,x0] + lx*U[y1,x1])
+ *   bx           = blend_s ? (1-lx)*tab[x0] + lx*tab[x1] : 1.f;   by likewise with y;   w = weight_s * (bx * by)
+ *   num = num + w * tap;   den = den + w
+ *   v   = den > 0 ? num / den (one true division) : 0;      bit = den > 0 && v > threshold
+ * `tab` float [G]: the blend window along one axis of a tile's upright prototype grid, every entry finite and > 0; NULL is allowed
+ * when no source has blend = 1.  A pixel that no source sees has v = 0 and bit = 0.
+ * OUTPUTS.  One packed plane per image under the mtbt_frame descriptors (K = 1; height, width, pitch, offset are read, step and scale
+ * ignored, as in mtbt_vote_tile_masks); mtbt_masks_to_frames' layout contract holds: little-endian bits, zero padding bits, every byte
+ * written exactly once, no memset, no atomics.  With `logits` != NULL also v as dense fp32 [H0, W0], image n at logits +
+ * logits_offset[n] floats (a multiple of 4, the image inside logits_floats); every element is written.
+ * `sources` / `tiles` / `tab` are HOST copies (validated, never dereferenced on the device), `sources_dev` / `tiles_dev` / `tab_dev` the
+ * caller's DEVICE copies of the same (read by the kernels); `first` is a host array of absolute indices into the tables (first[0] may be
+ * > 0).  A call projects and blends the sources first[0] .. first[N] - 1 only.  No allocation and no synchronisation inside the library.
+ * mtbt_seg_frame_workspace_bytes(n_sources, G) = 4 n_sources G^2 (0 for arguments the launch would refuse).
+ * Order of the checks, all MTBT_EINVAL before any launch: NULL a / frames / proj / sources / sources_dev / tiles / tiles_dev / first /
+ * workspace / out; n_passes outside 1..64, a NULL protos[p] or pass_items[p] < 1 for p < n_passes; n_frames outside 1..32 or != N; nm != 32,
+ * hp < 1, hp != wp, n_proj < 1, reserved != 0; a bad `first` (first[0] < 0, decreasing, more than 64 sources for an image, past
+ * n_sources); per source: a pass or slot outside the passes, an orient outside 0..7, a weight not > 0 (NaN included) or infinite, proj
+ * outside the table, a blend not 0 or 1 or blend = 1 without tab and tab_dev, reserved != 0; a tab entry (tab given) that is not finite and
+ * > 0; a NaN threshold; a workspace that is too
+ * small; a bad tile descriptor (as mtbt_vote_tile_masks; height / width must equal the frame's); the frame descriptor checks of
+ * mtbt_masks_to_frames with K = 1; a logits_offset that is negative, no multiple of 4 or whose image leaves logits_floats.  Then
+ * MTBT_EALIGN for a protos[p] / out / workspace / logits not 16-byte aligned.
+ * ------------------------------------------------------------------------------------------- */
+#define MTBT_SEG_MAX_PASSES 64
+typedef struct mtbt_seg_source {
+  int32_t pass, slot;
+  int32_t orient, proj, blend;
+  float weight;
+  int32_t reserved[2];
+} mtbt_seg_source;
+
+typedef struct mtbt_seg_frame_args {
+  const float* protos[MTBT_SEG_MAX_PASSES];   /* DEVICE, pass p: [pass_items[p], G, G, 32] */
+  int32_t pass_items[MTBT_SEG_MAX_PASSES];
+  const float* proj;                  /* DEVICE [n_proj, 33] */
+  const mtbt_seg_source* sources;     /* HOST [n_sources] */
+  const mtbt_seg_source* sources_dev; /* DEVICE [n_sources] */
+  const mtbt_tile* tiles;             /* HOST [n_sources] */
+  const mtbt_tile* tiles_dev;         /* DEVICE [n_sources] */
+  const int32_t* first;               /* HOST [N+1] */
+  const float* tab;                   /* HOST [G] or NULL */
+  const float* tab_dev;               /* DEVICE [G] or NULL */
+  float* workspace;                   /* DEVICE [n_sources, G, G] */
+  int64_t workspace_bytes;
+  uint8_t* out;                       /* packed planes of all images, one per image */
+  int64_t out_bytes;
+  float* logits;                      /* DEVICE or NULL */
+  int64_t logits_floats;
+  int64_t logits_offset[32];          /* floats, image n of this call */
+  float threshold;
+  int32_t N, n_sources, n_passes, n_proj, nm, hp, wp, reserved;
+} mtbt_seg_frame_args;
+
+int mtbt_seg_to_frames(const mtbt_seg_frame_args* a, const mtbt_frame* frames, int n_frames, void* stream);
+int64_t mtbt_seg_frame_workspace_bytes(int n_sources, int G);
+/* sizeof() of the two structs above as the library was compiled: which = 0 mtbt_seg_source, 1 mtbt_seg_frame_args; -1 otherwise */
+int mtbt_sizeof_seg_frame_args(int which);
+
+/* ---------------------------------------------------------------------------------------------
  * Multitask loss VALUE (forward only), MultiTaskLitModel._multitask_loss, running_main_v3.py:232-387:
  *   per (image, anchor): trainer decode (:268-290), IoU against the image's GT boxes (:316), positives = max IoU >
  *   iou_thresh (:319-321), sum(1 - IoU) (:331), BCE-with-logits(sum) of the class logits against one-hot /

@@ -44,7 +44,7 @@ from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, 
 from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
 from .postprocess import (components_to_instances, distance_transform, fill_polygons, filter_components, label_components, merge_tiles, vote_masks,  # noqa: F401
-                          signed_distance, vote_tile_masks, yolo_seg_planes)
+                          seg_to_frames, signed_distance, vote_tile_masks, yolo_seg_planes)
 from .sliced import detect_sliced  # noqa: F401
 from .trainstep import TrainStep, ema_decay_at  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

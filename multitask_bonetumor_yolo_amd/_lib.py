@@ -218,6 +218,22 @@ class TileMaskArgs(C.Structure):  # mtbt_tile_mask_args
                 ("nm", C.c_int32), ("hp", C.c_int32), ("wp", C.c_int32), ("crop", C.c_int32), ("reserved", C.c_int32)]
 
 
+class SegSource(C.Structure):  # mtbt_seg_source
+    _fields_ = [("pass_", C.c_int32), ("slot", C.c_int32), ("orient", C.c_int32), ("proj", C.c_int32), ("blend", C.c_int32),
+                ("weight", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class SegFrameArgs(C.Structure):  # mtbt_seg_frame_args
+    _fields_ = [("protos", C.c_void_p * 64), ("pass_items", C.c_int32 * 64), ("proj", C.c_void_p),
+                ("sources", C.POINTER(SegSource)), ("sources_dev", C.c_void_p),
+                ("tiles", C.POINTER(Tile)), ("tiles_dev", C.c_void_p), ("first", C.POINTER(C.c_int32)),
+                ("tab", C.POINTER(C.c_float)), ("tab_dev", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("out", C.c_void_p), ("out_bytes", C.c_int64),
+                ("logits", C.c_void_p), ("logits_floats", C.c_int64), ("logits_offset", C.c_int64 * 32), ("threshold", C.c_float),
+                ("N", C.c_int32), ("n_sources", C.c_int32), ("n_passes", C.c_int32), ("n_proj", C.c_int32),
+                ("nm", C.c_int32), ("hp", C.c_int32), ("wp", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SurfaceArgs(C.Structure):  # mtbt_surface_args
     _fields_ = [("a", C.c_void_p), ("b", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
                 ("n_edge", C.c_void_p), ("max_d2", C.c_void_p), ("n_within", C.c_void_p), ("sum_d", C.c_void_p), ("rank_d2", C.c_void_p),
@@ -399,6 +415,9 @@ SYMBOLS = {
     "mtbt_merge_tiles": (C.c_int, [C.POINTER(TileMergeArgs), C.c_void_p]),
     "mtbt_vote_tile_masks": (C.c_int, [C.POINTER(TileMaskArgs), C.POINTER(Frame), C.c_int, C.c_void_p]),
     "mtbt_sizeof_tile_args": (C.c_int, [C.c_int]),
+    "mtbt_seg_to_frames": (C.c_int, [C.POINTER(SegFrameArgs), C.POINTER(Frame), C.c_int, C.c_void_p]),
+    "mtbt_seg_frame_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "mtbt_sizeof_seg_frame_args": (C.c_int, [C.c_int]),
     "mtbt_surface_distances_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mtbt_surface_distances": (C.c_int, [C.POINTER(SurfaceArgs), C.c_void_p]),
     "mtbt_sizeof_surface_args": (C.c_int, [C.c_int]),
@@ -424,6 +443,7 @@ ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, Raw
 FRAME_STRUCTS = (Frame, FrameMaskArgs)   # order of mtbt_sizeof_frame_args(which)
 MASK_EVAL_STRUCTS = (PackMasksArgs, MaskImage, MaskPairArgs, MaskEvalArgs)   # order of mtbt_sizeof_mask_eval_args(which)
 TILE_STRUCTS = (Tile, TileMergeArgs, TileMaskArgs)   # order of mtbt_sizeof_tile_args(which)
+SEG_FRAME_STRUCTS = (SegSource, SegFrameArgs)   # order of mtbt_sizeof_seg_frame_args(which)
 SURFACE_STRUCTS = (SurfaceArgs,)   # order of mtbt_sizeof_surface_args(which)
 COMPONENTS_STRUCTS = (ComponentsArgs, SelectComponentsArgs)   # order of mtbt_sizeof_components_args(which)
 POLYGON_STRUCTS = (FillPolygonsArgs,)   # order of mtbt_sizeof_fill_polygons_args(which)
@@ -455,7 +475,7 @@ def load():
                                 (lib.mtbt_sizeof_tile_args, TILE_STRUCTS), (lib.mtbt_sizeof_surface_args, SURFACE_STRUCTS),
                                 (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS), (lib.mtbt_sizeof_fill_polygons_args, POLYGON_STRUCTS),
                                 (lib.mtbt_sizeof_clahe_args, CLAHE_STRUCTS), (lib.mtbt_sizeof_copy_paste_args, COPY_PASTE_STRUCTS),
-                                (lib.mtbt_sizeof_distance_args, DISTANCE_STRUCTS)):
+                                (lib.mtbt_sizeof_distance_args, DISTANCE_STRUCTS), (lib.mtbt_sizeof_seg_frame_args, SEG_FRAME_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

@@ -10,7 +10,7 @@
 // step = scale / up prototype pixels per frame pixel): no letterboxed S x S plane exists in between.  All coordinate
 // and box arithmetic is separate fp32 multiplies and adds so that it rounds like the CPU restatements in tests/frame_reference.py,
 // tests/vote_reference.py and tests/slice_reference.py.  INCLUDE THIS HEADER ONLY FROM FILES BUILT WITH -ffp-contract=off (build.py
-// EXTRA_FLAGS: exactly the three files above): contracted into FMAs the taps and the bilinear value round differently.
+// EXTRA_FLAGS: the three files above and seg_frame.hip, which walks the same tiles for the semantic mask): contracted into FMAs the taps and the bilinear value round differently.
 //
 // A workgroup owns one tile of one image: 2^wl 64-pixel words wide and th rows tall, both picked per image on the host
 // (frame_pick_tile) so that the prototype patch under the tile (first tap of the first pixel .. second tap of the last) fits
@@ -86,22 +86,27 @@ inline int frame_span(int len, int w0, int w1, float step, int po, int size) {
 // the largest tile (2^wl words x th rows, at most max_units units and 2^max_hl rows) under which the patch of every one of the T windows
 // (each with its own step and prototype offset) fits NPX_CAP; wider wins a tie (longer contiguous stores).  False when not even a
 // 64 x 1 tile fits, which cannot happen for step <= 1 (at most 66 x 2 prototype pixels); wl = 0, th = 1 then.
-inline bool frame_pick_tile(const mtbt_frame& fr, const mtbt_tile* win, int T, int hp, int wp, int max_units, int max_hl, int& wl, int& th) {
+// `cap`: the patch buffer in prototype pixels (NPX_CAP for the instance kernels; seg_frame.hip keeps one float per pixel and passes its own).
+// `snug`: among the largest tiles the one that pads the plane least wins instead (units of tiles that hang over the right or bottom
+// edge are idle lanes: a 10-word row under 8-word tiles runs at 10 / 16), wider only among equals.
+inline bool frame_pick_tile(const mtbt_frame& fr, const mtbt_tile* win, int T, int hp, int wp, int max_units, int max_hl, int& wl, int& th,
+                            int cap = NPX_CAP, bool snug = false) {
   const int words_x = fr.pitch >> 3;
   wl = 0; th = 1;
-  long best = 0;
+  long best = 0, best_padded = 0;
   for (int l = 3; l >= 0; --l)
     for (int h = max_hl; h >= 0; --h) {
       if (((1 << l) << h) > max_units || (l > 0 && (1 << (l - 1)) >= words_x) || (h > 0 && (1 << (h - 1)) >= fr.height)) continue;
       const long area = 1L << (l + h);
-      if (area <= best) continue;
+      const long padded = (long)(((words_x + (1 << l) - 1) >> l) << l) * (((fr.height + (1 << h) - 1) >> h) << h);
+      if (area < best || (area == best && !(snug && padded < best_padded))) continue;
       bool fits = true;
       for (int t = 0; t < T && fits; ++t) {
         const mtbt_tile& d = win[t];
         const int n = frame_span(64 << l, d.wx0, d.wx1, d.step, d.pox, wp) * frame_span(1 << h, d.wy0, d.wy1, d.step, d.poy, hp);
-        fits = ((n + 15) & ~15) <= NPX_CAP;
+        fits = ((n + 15) & ~15) <= cap;
       }
-      if (fits) { best = area; wl = l; th = 1 << h; }
+      if (fits) { best = area; best_padded = padded; wl = l; th = 1 << h; }
     }
   return best > 0;
 }
@@ -110,7 +115,8 @@ inline bool frame_pick_tile(const mtbt_frame& fr, const mtbt_tile* win, int T, i
 // number of workgroups.  Without `tiles` an image is one window, the frame at its own step; with them (sliced inference: image i's windows
 // are tiles[first[i] .. first[i + 1])) the frame's own step and scale are not used, every tile carries its own.
 inline int frame_layout(const mtbt_frame* frames, int n_frames, int K, int hp, int wp, bool with_boxes, int64_t out_bytes,
-                        const mtbt_tile* tiles, const int32_t* first, int max_units, int max_hl, FrameD* f, long& blocks) {
+                        const mtbt_tile* tiles, const int32_t* first, int max_units, int max_hl, FrameD* f, long& blocks, int cap = NPX_CAP,
+                        bool snug = false) {
   blocks = 0;
   for (int i = 0; i < n_frames; ++i) {
     const mtbt_frame& fr = frames[i];
@@ -123,8 +129,8 @@ inline int frame_layout(const mtbt_frame* frames, int n_frames, int K, int hp, i
     FrameD& d = f[i];
     mtbt_tile own = {};
     own.wx1 = fr.width; own.wy1 = fr.height; own.step = fr.step;
-    const bool fits = tiles ? frame_pick_tile(fr, tiles + first[i], first[i + 1] - first[i], hp, wp, max_units, max_hl, d.wl, d.th)
-                            : frame_pick_tile(fr, &own, 1, hp, wp, max_units, max_hl, d.wl, d.th);
+    const bool fits = tiles ? frame_pick_tile(fr, tiles + first[i], first[i + 1] - first[i], hp, wp, max_units, max_hl, d.wl, d.th, cap, snug)
+                            : frame_pick_tile(fr, &own, 1, hp, wp, max_units, max_hl, d.wl, d.th, cap, snug);
     if (!fits && !tiles) return MTBT_EINVAL;   // (the tile kernel never reads a patch that did not fit)
     d.offset = fr.offset; d.step = fr.step; d.scale = fr.scale;
     d.H0 = fr.height; d.W0 = fr.width; d.pitch = fr.pitch; d.pad_ = 0;
@@ -275,6 +281,15 @@ __device__ __forceinline__ void stage_patch(float* patch, const float* pr, const
     }
     float* d = patch + px * PPITCH + c4 * 4;
     d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+  }
+}
+
+// the same walk for a plane that holds ONE float per prototype pixel (seg_frame.hip: the projector's logits): patch[px] <- lo[at(y, x)]
+template <class At>
+__device__ __forceinline__ void stage_patch1(float* patch, const float* lo, const Patch& pt, At at) {
+  for (int px = threadIdx.x; px < pt.NPX; px += 256) {
+    const int py = px / pt.PW, pxx = px - py * pt.PW;
+    patch[px] = lo[at(pt.pya + py, pt.pxa + pxx)];
   }
 }
 

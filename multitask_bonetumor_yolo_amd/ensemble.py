@@ -14,7 +14,7 @@ from typing import Optional, Sequence
 import torch
 
 from .postprocess import (CONF_TH, NMS_IOU, TOP_K, FUSE_MAX_SOURCES, assemble_masks, detect_and_segment, fuse_detections, orient_batch,
-                          unorient_batch, unpack_masks, vote_masks)
+                          seg_to_frames, unorient_batch, unpack_masks, vote_masks)
 
 
 def _leader_masks(fused, outs, views, S: int) -> torch.Tensor:
@@ -39,7 +39,7 @@ def _leader_masks(fused, outs, views, S: int) -> torch.Tensor:
 @torch.no_grad()
 def detect_fused(models, images: torch.Tensor, img_size: int, *, views: Sequence[int] = (0,), weights: Optional[Sequence[float]] = None,
                  conf_th: float = CONF_TH, iou_th: float = NMS_IOU, top_k: int = TOP_K, wbf_iou: float = 0.55, skip_thr: float = 0.0,
-                 masks=False, frames=None, crop: bool = False):
+                 masks=False, frames=None, crop: bool = False, semantic=None, seg_threshold: float = 0.0):
     """Detections of `images` [B,3,S,S] (S = img_size) fused over models x views.
 
     `models`: one eval-mode model or a list of them (the k models of a k-fold run; the raw and the EMA weights of a `TrainStep`).
@@ -56,12 +56,17 @@ def detect_fused(models, images: torch.Tensor, img_size: int, *, views: Sequence
     logits, every source turned upright, so that the mask belongs to the same members as the averaged box.  The result gains
     `member_slot`, `vote_coeff` and, without `frames`, `masks` uint8 [B,top_k,S,S] (identity frames (S, S, 1.0), unpacked); with `frames`
     ([(H0, W0, scale)] per image, `frames_of`) it gains `boxes_frame` [B,top_k,4] and the bit-packed `masks_frame` instead, as
-    `detect_and_segment` returns them, cropped to the fused boxes with `crop`.  `frames` / `crop` need `masks="vote"`."""
+    `detect_and_segment` returns them, cropped to the fused boxes with `crop`.  `frames` / `crop` need `masks="vote"`.
+
+    `semantic` (the trainer's `seg_proto_projector`: an nn.Conv2d(32, 1, 1) or (weight, bias), or a list of one per model) adds the
+    SEMANTIC mask averaged over models x views with the sources' weights (`postprocess.seg_to_frames`): `seg_frame`, the bit-packed
+    planes uint8 [1, H0, pitch] per image (logit > `seg_threshold`), and `seg_logits`, fp32 [H0, W0] per image -- in `frames` when
+    given, else in identity frames (S, S, 1.0).  None: not one launch changes."""
     if masks not in (False, True, "vote"):
         raise ValueError(f"detect_fused: masks is False, True (the leaders' masks) or 'vote', not {masks!r}")
     vote = isinstance(masks, str)
-    if (frames is not None or crop) and not vote:
-        raise ValueError("detect_fused: frames / crop come with masks='vote'")
+    if (frames is not None and not vote and semantic is None) or (crop and not vote):
+        raise ValueError("detect_fused: frames / crop come with masks='vote' (frames also with semantic=)")
     models = list(models) if isinstance(models, (list, tuple)) else [models]
     views = [int(v) for v in views]
     weights = [1.0] * len(models) if weights is None else [float(w) for w in weights]
@@ -96,4 +101,13 @@ def detect_fused(models, images: torch.Tensor, img_size: int, *, views: Sequence
             fused["boxes_frame"], fused["masks_frame"] = r["boxes"], r["masks"]
     elif masks:
         fused["masks"] = _leader_masks(fused, outs, src_views, S)
+    if semantic is not None:
+        if isinstance(semantic, list):
+            if len(semantic) != len(models):
+                raise ValueError(f"detect_fused: {len(semantic)} projectors for {len(models)} models")
+            semantic = [pj for pj in semantic for _ in views]
+        protos = [out["segment_protos"][2] for out in outs]
+        r = seg_to_frames(protos, semantic, [(S, S, 1.0)] * images.shape[0] if frames is None else frames, orients=src_views,
+                          weights=src_weights, threshold=seg_threshold, logits=True, up=S / protos[0].shape[3])
+        fused["seg_frame"], fused["seg_logits"], fused["_seg"] = r["masks"], r["logits"], r
     return fused

@@ -723,6 +723,41 @@ class SegmentationMetrics:
         self._counts.append(counts)
         self._psum.append(psum)
 
+    def update_packed(self, pred_packed, gt_packed, W0):
+        """The same counts from BIT-PACKED planes in the image frame (`postprocess.seg_to_frames`' "masks", `detect_sliced`'s
+        `seg_frame`; ground truth from `pack_masks` / `fill_polygons`): TP / FP / FN / TN per image from popcounts
+        (`mtbt_mask_pair_counts` with one plane per image).  pred_packed, gt_packed: uint8 [B, H, pitch] (or [B, 1, H, pitch], or
+        [H, pitch]) tensors with one `W0`, or lists of per-image planes ([H_b, pitch_b] or [1, H_b, pitch_b]) with a list of widths.
+        A packed plane carries no probabilities: the mask score's numerator is TP + FP, i.e. the score is 1.  Asynchronous."""
+        if isinstance(pred_packed, torch.Tensor):
+            p = pred_packed.reshape((-1,) + tuple(pred_packed.shape[-2:]))
+            g = gt_packed.reshape((-1,) + tuple(gt_packed.shape[-2:]))
+            pred, gt, widths = list(p), list(g), [int(W0)] * p.shape[0]
+        else:
+            pred, gt = [t.reshape(t.shape[-2:]) for t in pred_packed], [t.reshape(t.shape[-2:]) for t in gt_packed]
+            widths = [int(w) for w in W0] if isinstance(W0, (list, tuple)) else [int(W0)] * len(pred)
+        if len(pred) != len(gt) or len(widths) != len(pred):
+            raise ValueError(f"SegmentationMetrics.update_packed: {len(pred)} predictions, {len(gt)} ground truths, {len(widths)} widths")
+        for a, b, w in zip(pred, gt, widths):
+            if not (a.is_cuda and b.is_cuda):
+                raise RuntimeError("SegmentationMetrics.update_packed: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+            if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.shape != b.shape or a.shape[1] != _mask_pitch(w):
+                raise ValueError(f"SegmentationMetrics.update_packed: planes {tuple(a.shape)} / {tuple(b.shape)} for width {w}; expected uint8 "
+                                 f"[H, {_mask_pitch(w)}] both")
+        if not pred:
+            return
+        dev = pred[0].device
+        pred, gt = [t.contiguous() for t in pred], [t.contiguous() for t in gt]
+        for c0 in range(0, len(pred), MASK_EVAL_MAX_IMAGES):
+            nb = min(MASK_EVAL_MAX_IMAGES, len(pred) - c0)
+            images = [(pred[b].shape[0], widths[b], pred[b], gt[b], b - c0, 1) for b in range(c0, c0 + nb)]
+            inter, det_area, gt_px = _pair_counts(images, 1, None, torch.arange(nb, dtype=torch.int32, device=dev), nb, dev)
+            u = lambda t: t.reshape(-1).to(torch.int64) & 0xFFFFFFFF            # the tables are uint32 counts in int32 words
+            tp, d, g = u(inter), u(det_area), u(gt_px)
+            px = torch.tensor([pred[b].shape[0] * widths[b] for b in range(c0, c0 + nb)], dtype=torch.int64).to(dev, non_blocking=True)
+            self._counts.append(torch.stack([tp, d - tp, g - tp, px - d - g + tp], 1))
+            self._psum.append(d.to(torch.float32))
+
     def per_image(self, sync: bool = False):
         """-> (counts [N,4] int64 = TP, FP, FN, TN; mask scores [N] = sum(prob * mask) / (sum(mask) + 1e-6), :483).
         `sync`: the images of all ranks in rank order (a collective)."""

@@ -706,6 +706,196 @@ def vote_tile_masks(merged: dict, det: dict, mc: torch.Tensor, protos: torch.Ten
     return {"boxes": boxes, "masks": packed.views(), "buffer": out, "vote_coeff": W, "vote_weight": Ss, "_keep": (table, first, table_dev, pr, mc, scores, anchors)}
 
 
+# ---- the semantic mask in the image frame: views averaged, tiles blended (include/mtbt_hip.h `mtbt_seg_to_frames`) ----------------
+SEG_MAX_PASSES = 64
+SEG_BLENDS = ("constant", "gaussian", "tent")
+
+
+def seg_blend_table(blend, G: int) -> Optional[np.ndarray]:
+    """The blend window along one axis of a tile's upright G-pixel prototype grid, float32 [G], or None for "constant".
+    "gaussian": MONAI's sliding-window importance map along one axis, exp(-(i - (G-1)/2)^2 / (2 (0.125 G)^2)) in float64, rounded to
+    float32 and floored at its smallest positive entry; "tent": min(i, G-1-i) + 1, normalised to a maximum of 1; an array [G] is used as
+    given.  Every entry must be finite and > 0 (ValueError)."""
+    G = int(G)
+    if isinstance(blend, str):
+        if blend not in SEG_BLENDS:
+            raise ValueError(f"seg_to_frames: blend {blend!r} (one of {SEG_BLENDS}, or a float array [G])")
+        if blend == "constant":
+            return None
+        i = np.arange(G, dtype=np.float64)
+        if blend == "gaussian":
+            tab = np.exp(-((i - (G - 1) / 2.0) ** 2) / (2.0 * (0.125 * G) ** 2)).astype(np.float32)
+            tab = np.maximum(tab, tab[tab > 0].min())
+        else:
+            tab = np.minimum(i, G - 1 - i) + 1.0
+            tab = (tab / tab.max()).astype(np.float32)
+    else:
+        tab = np.asarray(blend.detach().cpu() if isinstance(blend, torch.Tensor) else blend, dtype=np.float32)
+    tab = np.ascontiguousarray(tab, dtype=np.float32)
+    if tab.shape != (G,) or not np.all(np.isfinite(tab)) or not np.all(tab > 0):
+        raise ValueError(f"seg_to_frames: the blend table must be [{G}] floats, every entry finite and > 0")
+    return tab
+
+
+def _seg_projectors(projector, M: int):
+    """`projector` -> ([(weight [32], bias [1])] tensors, one per distinct projector, the index of each of the M passes into that list)."""
+    def pair(p):
+        w, b = (p.weight, p.bias) if hasattr(p, "weight") else p
+        w = w.detach().reshape(-1).float()
+        if w.numel() != 32:
+            raise ValueError(f"seg_to_frames: a projector has {w.numel()} weights; the kernel supports 32 prototype channels")
+        b = torch.zeros(1, device=w.device) if b is None else b.detach().reshape(-1).float()
+        return w, b
+    if isinstance(projector, list):
+        if len(projector) != M:
+            raise ValueError(f"seg_to_frames: {len(projector)} projectors for {M} passes")
+        return [pair(p) for p in projector], list(range(M))
+    return [pair(projector)], [0] * M
+
+
+def _seg_plan(shapes, frames, orients, weights, tiles, blend, up, proj_of=None):
+    """The host's share of `seg_to_frames`, without a device: the checks, and per image its sources (pass m ascending, then tile
+    ascending) as `mtbt_seg_source` / `mtbt_tile` rows.  Returns (sources array, tile array, first int32 [N+1], blend table or None, G)."""
+    M = len(shapes)
+    if not 1 <= M <= SEG_MAX_PASSES:
+        raise ValueError(f"seg_to_frames: {M} passes (1..{SEG_MAX_PASSES})")
+    N = len(frames)
+    NT = N if tiles is None else sum(len(per) for per in tiles)
+    G = int(shapes[0][2])
+    for m, sh in enumerate(shapes):
+        if len(sh) != 4 or sh[1] != 32 or sh[2] != sh[3] or sh[2] != G or sh[0] != NT:
+            raise ValueError(f"seg_to_frames: pass {m} has prototypes {tuple(sh)}; expected [{NT}, 32, {G}, {G}]")
+    if tiles is not None and len(tiles) != N:
+        raise ValueError(f"seg_to_frames: {len(tiles)} tile lists for {N} frames")
+    orients = [int(o) for o in orients]
+    if len(orients) == 1:
+        orients = orients * M
+    weights = [1.0] * M if weights is None else [float(w) for w in weights]
+    if len(orients) != M or len(weights) != M or any(not 0 <= o <= 7 for o in orients):
+        raise ValueError(f"seg_to_frames: {len(orients)} orients (0..7) and {len(weights)} weights for {M} passes")
+    if any(not (w > 0 and np.isfinite(w)) for w in weights):
+        raise ValueError(f"seg_to_frames: weights must be finite and > 0, not {weights}")
+    tab = seg_blend_table(blend, G)
+    per_image = []
+    for n, fr in enumerate(frames):
+        H0, W0 = int(fr[0]), int(fr[1])
+        if tiles is None:
+            scale = float(fr[2])
+            own = [{"image": n, "pox": 0, "poy": 0, "wx0": 0, "wy0": 0, "wx1": W0, "wy1": H0, "height": H0, "width": W0,
+                    "step": C.c_float(scale / up).value, "scale": C.c_float(scale).value, "fox": 0.0, "foy": 0.0, "_slot": n}]
+        else:
+            t0 = sum(len(per) for per in tiles[:n])
+            own = [dict(t, _slot=t0 + i) for i, t in enumerate(tiles[n])]
+            if any((t["height"], t["width"]) != (H0, W0) for t in own):
+                raise ValueError(f"seg_to_frames: the tiles of image {n} are not of its frame ({H0}, {W0})")
+        if M * len(own) > TILE_MAX_PER_IMAGE:
+            raise ValueError(f"seg_to_frames: image {n} has {M} passes x {len(own)} tiles = {M * len(own)} sources ({TILE_MAX_PER_IMAGE} at most)")
+        per_image.append(own)
+    NS = sum(M * len(own) for own in per_image)
+    src, table = (L.SegSource * max(NS, 1))(), (L.Tile * max(NS, 1))()
+    first = (C.c_int32 * (N + 1))()
+    s = 0
+    for n, own in enumerate(per_image):
+        rows = []
+        for t in own:                                  # one descriptor per tile, copied whole for every pass
+            d = L.Tile()
+            for k in _TILE_FIELDS:
+                setattr(d, k, t[k])
+            whole = (t["wx0"], t["wy0"], t["wx1"], t["wy1"]) == (0, 0, t["width"], t["height"])   # a whole-image source: constant
+            rows.append((d, t["_slot"], int(tab is not None and tiles is not None and not whole)))
+        for m in range(M):
+            for d, slot, bl in rows:
+                table[s] = d
+                src[s] = L.SegSource(m, slot, orients[m], proj_of[m] if proj_of else 0, bl, weights[m])
+                s += 1
+        first[n + 1] = s
+    return src, table, first, tab, G
+
+
+def seg_to_frames(protos, projector, frames, *, orients: Sequence[int] = (0,), weights: Optional[Sequence[float]] = None, tiles=None,
+                  blend="constant", threshold: float = 0.0, logits: bool = False, out: Optional[torch.Tensor] = None,
+                  up: Optional[float] = None, want_low: bool = False):
+    """The SEMANTIC mask in the coordinates of the original images: the projector's logit (the trainer's `seg_proto_projector`, a 1x1
+    conv over the prototypes) averaged over several forward passes and sampled at the image's own pixels, one bit per pixel
+    (`mtbt_seg_to_frames`: one launch for the projector at prototype resolution, one for the blend).
+
+    `protos`: one tensor or a list of M passes (TTA views, ensemble members), each [N,32,G,G] in the frame of the view that pass saw; with
+    `tiles` (`slice_geometry`'s lists) each is [NT,32,G,G], tile-major as `detect_sliced` concatenates them.  Any memory format.
+    `projector`: an nn.Conv2d(32, 1, 1), or (weight, bias), or a list of M of them (one per pass).  `orients` (codes 0..7, one per pass;
+    a single one holds for all) and `weights` (> 0, default 1) per pass.  `frames`, `up`, `out` and the packed layout: as in
+    `masks_to_frames`, one plane per image.  The sources of image n are its passes, m ascending, then its tiles ascending (at most 64):
+
+      logit v   = sum_s w_s tap_s / sum_s w_s over the sources whose window holds the pixel, w_s = weight_s * blend window at the pixel's
+                  place in the source's upright prototype grid, tap_s = the bilinear tap of the source's upright projector logits
+      mask bit  = some source sees the pixel and v > threshold (a logit: 0.0 is sigmoid 0.5)
+
+    `blend` ("constant", "gaussian", "tent" or a float array [G], `seg_blend_table`) weighs the tile sources down towards their borders,
+    which removes the seams an equal-weight sum leaves where overlapping tiles disagree; sources that see the whole image (a TTA view,
+    sliced inference's full view) are constant.
+
+    Returns {"masks": [uint8 [1, H0, pitch] per image], "logits": [fp32 [H0, W0] per image] with `logits=True` (or a caller's flat fp32
+    buffer; image b starts at a multiple of 4 floats, every element is written) else None, "buffer":
+    the flat uint8 buffer, "logits_buffer": the flat fp32 one or None} (and "low", the projector logits [NS, G, G] per source, with
+    `want_low`).  Nothing synchronises with the device."""
+    passes = list(protos) if isinstance(protos, (list, tuple)) else [protos]
+    up = 4.0 if up is None else float(up)
+    src, table, first, tab, G = _seg_plan([tuple(p.shape) for p in passes], frames, orients, weights, tiles, blend, up,
+                                          list(range(len(passes))) if isinstance(projector, list) else None)
+    if float(threshold) != float(threshold):
+        raise ValueError("seg_to_frames: threshold is NaN")
+    lib = L.load()
+    for p in passes:
+        _need_cuda(p, "seg_to_frames")
+    dev = passes[0].device
+    M, N, NS = len(passes), len(frames), int(first[len(frames)])
+    pairs, _ = _seg_projectors(projector, M)
+    q = torch.stack([torch.cat([w.to(dev), b.to(dev)]) for w, b in pairs]).contiguous()
+    rows = [_proto_rows(p) for p in passes]
+    # with tiles the frame's own step and scale are not used (1 here): every tile carries its own
+    packed = _PackedFrames("seg_to_frames", frames if tiles is None else [(fr[0], fr[1], 1.0) for fr in frames], 1, up if tiles is None else 1.0,
+                           out, dev)
+    offs, total = [], 0
+    for H0, W0 in ((r[0], r[1]) for r in packed.rows):
+        offs.append(total)
+        total = (total + H0 * W0 + 3) // 4 * 4
+    lbuf = None
+    if isinstance(logits, torch.Tensor):        # the caller's flat fp32 buffer
+        lbuf = logits
+        if lbuf.dtype != torch.float32 or lbuf.dim() != 1 or not lbuf.is_contiguous() or lbuf.numel() < total or lbuf.device != dev:
+            raise ValueError(f"seg_to_frames: logits must be True or a contiguous flat float32 buffer of at least {total} elements on {dev}")
+        logits = True
+    elif logits:
+        lbuf = torch.empty((total,), dtype=torch.float32, device=dev)
+    low = torch.empty((max(NS, 1) * G * G,), dtype=torch.float32, device=dev)
+    src_dev = torch.frombuffer(bytearray(bytes(src)), dtype=torch.uint8).to(dev)
+    table_dev = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+    tab_dev = torch.from_numpy(tab).to(dev) if tab is not None else None
+    with torch.cuda.device(dev):
+        for c0, nb, fr in packed.chunks():
+            a = L.SegFrameArgs()
+            for m, pr in enumerate(rows):
+                a.protos[m], a.pass_items[m] = pr.data_ptr(), pr.shape[0]
+            a.proj, a.sources, a.sources_dev, a.tiles, a.tiles_dev = q.data_ptr(), src, src_dev.data_ptr(), table, table_dev.data_ptr()
+            a.first = C.cast(C.byref(first, 4 * c0), C.POINTER(C.c_int32))
+            if tab is not None:
+                a.tab, a.tab_dev = tab.ctypes.data_as(C.POINTER(C.c_float)), tab_dev.data_ptr()
+            a.workspace, a.workspace_bytes = low.data_ptr(), low.numel() * 4
+            a.out, a.out_bytes = packed.out.data_ptr(), packed.out.numel()
+            if logits:
+                a.logits, a.logits_floats = lbuf.data_ptr(), total
+                for i in range(nb):
+                    a.logits_offset[i] = offs[c0 + i]
+            a.threshold = float(threshold)
+            a.N, a.n_sources, a.n_passes, a.n_proj, a.nm, a.hp, a.wp = nb, NS, M, len(pairs), 32, G, G
+            L.check(lib.mtbt_seg_to_frames(C.byref(a), fr, nb, _stream(dev)), "mtbt_seg_to_frames")
+    r = {"masks": packed.views(), "buffer": packed.out, "logits_buffer": lbuf,
+         "logits": [lbuf[o:o + H0 * W0].view(H0, W0) for o, (H0, W0) in zip(offs, ((r[0], r[1]) for r in packed.rows))] if logits else None,
+         "_keep": (rows, q, src, table, first, tab, src_dev, table_dev, tab_dev, low)}
+    if want_low:
+        r["low"] = low[:NS * G * G].view(NS, G, G)
+    return r
+
+
 # ---- connected components of packed planes ----------------------------------------------------------------------------------------
 COMPONENTS_MAX_DIM = 16384       # H and W of mtbt_label_components
 COMPONENTS_MAX_TABLE = 65536     # max_components

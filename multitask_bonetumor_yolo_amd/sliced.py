@@ -13,7 +13,7 @@ from typing import Sequence
 
 import torch
 
-from .postprocess import CONF_TH, NMS_IOU, TOP_K, detect_and_segment, merge_tiles, vote_tile_masks
+from .postprocess import CONF_TH, NMS_IOU, TOP_K, detect_and_segment, merge_tiles, seg_to_frames, vote_tile_masks
 from .preprocess import slice_batch, slice_geometry
 
 
@@ -21,7 +21,7 @@ from .preprocess import slice_batch, slice_geometry
 def detect_sliced(model, raw_images: Sequence[torch.Tensor], img_size: int, *, zoom: float = 1.0, overlap: float = 0.2,
                   full_view: bool = True, batch: int = 16, conf_th: float = CONF_TH, iou_th: float = NMS_IOU, tile_top_k: int = TOP_K,
                   metric: str = "ios", thr: float = 0.5, skip_thr: float = 0.0, top_k: int = TOP_K, class_agnostic: bool = False,
-                  masks=False, crop: bool = False):
+                  masks=False, crop: bool = False, semantic=None, blend="gaussian", seg_threshold: float = 0.0):
     """Detections (and instance masks) of raw images of any sizes, in their own pixel coordinates.
 
     `raw_images`: decoded BGR uint8 [H0, W0, 3] CUDA tensors.  Each is cut by `slice_geometry(sizes, img_size, zoom, overlap, full_view)`
@@ -32,6 +32,12 @@ def detect_sliced(model, raw_images: Sequence[torch.Tensor], img_size: int, *, z
     lead_slot, lead_anchor, member_slot, n_left, tiles.  `masks="vote"` adds `masks_frame` (bit-packed uint8 [top_k, H0_n, pitch_n] per
     image, cropped to the merged boxes with `crop`) and `vote_coeff` (`postprocess.vote_tile_masks`); the result then feeds
     `DeviceMaskMeanAveragePrecision.update_batched` as it is.
+
+    `semantic` (the trainer's `seg_proto_projector`: an nn.Conv2d(32, 1, 1) or (weight, bias)) adds the SEMANTIC mask at the image's own
+    resolution from the tiles that were run anyway (`postprocess.seg_to_frames`): `seg_frame`, bit-packed uint8 [1, H0_n, pitch_n] per
+    image (logit > `seg_threshold`), and `seg_logits`, fp32 [H0_n, W0_n].  Overlapping tiles are averaged under the `blend` window
+    ("gaussian", "tent", "constant" or a float array [G]) so that no seam is left where they disagree; the full view takes part as a
+    constant source.  None: not one launch changes.
 
     Memory: the mask coefficients and prototypes of every tile are concatenated tile-major before the vote: 32 * (S / 4)^2 fp32 = 3.3 MB
     of prototypes per tile at S = 640 (43 MB for the 13 tiles of a 2048 x 1536 image), plus 32 * A fp32 of coefficients."""
@@ -52,6 +58,7 @@ def detect_sliced(model, raw_images: Sequence[torch.Tensor], img_size: int, *, z
         dets.append(detect_and_segment(out["detect_features"], mc, pr, S, conf_th, iou_th, tile_top_k, masks=False))
         if masks:
             mcs.append(mc.float())
+        if masks or semantic is not None:
             protos.append(pr.float())
     det = {k: torch.cat([d[k] for d in dets]) for k in ("boxes", "scores", "labels", "counts", "keep_anchor")}
     frames = [(H0, W0, S / max(H0, W0)) for H0, W0 in sizes]
@@ -60,4 +67,8 @@ def detect_sliced(model, raw_images: Sequence[torch.Tensor], img_size: int, *, z
         r = vote_tile_masks(merged, det, torch.cat(mcs), torch.cat(protos), tiles, frames, crop=crop)
         merged["masks_frame"], merged["vote_coeff"] = r["masks"], r["vote_coeff"]
         merged["_keep"] = (merged["_keep"], r["_keep"])
+    if semantic is not None:
+        r = seg_to_frames(torch.cat(protos), semantic, frames, tiles=tiles, blend=blend, threshold=seg_threshold, logits=True,
+                          up=S / protos[0].shape[3])
+        merged["seg_frame"], merged["seg_logits"], merged["_seg"] = r["masks"], r["logits"], r
     return merged

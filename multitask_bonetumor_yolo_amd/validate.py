@@ -21,7 +21,7 @@ from .loss import instance_mask_loss, multitask_loss, task_aligned_det_loss
 from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, DeviceMeanAveragePrecision, ImageClassificationMetrics,
                       LesionMetrics, SegmentationMetrics, SurfaceDistanceMetrics, _sum_over_ranks)
 from .postprocess import (CONF_TH, NMS_IOU, TOP_K, decode_boxes, fuse_detections, masks_to_frames, nms_batched, orient_batch, pack_masks,
-                          proto_projector_logits, vote_masks)
+                          proto_projector_logits, seg_to_frames, vote_masks)
 
 LOSS_NAMES = ("total", "seg", "box_iou", "dfl", "det_cls", "img_cls")       # running_main_v3.py:578-582
 MASK_LOSS_NAME = "mask"                                                      # appended with instance_mask_weight > 0
@@ -60,7 +60,7 @@ class ValidationStep:
                  top_k: int = TOP_K, map_max_detections: int = 100, dist_sync: bool = True, process_group=None,
                  instance_masks: bool = False, mask_crop: bool = True, det_loss: str = "reference", tal=None,
                  instance_mask_weight: float = 0.0, mask_assign: str = "iou", views: Optional[Sequence[int]] = None, wbf_iou: float = 0.55,
-                 fused_masks: Optional[str] = None, surface=None, lesions=None):
+                 fused_masks: Optional[str] = None, surface=None, lesions=None, seg_views: bool = False):
         """`projector` = the trainer's `seg_proto_projector` (Conv2d(proto_ch, 1, 1), running_main_v3.py:186); created with torch's default
         init when not given.  The loss hyper-parameters default to the reference's (and TrainStep's); `label_smoothing` is accepted for
         symmetry with TrainStep but the eval-mode loss never smooths (:337).  conf_th / nms_iou / top_k: `:54-56`;
@@ -79,10 +79,13 @@ class ValidationStep:
         are updated from the weighted-boxes fusion (`fuse_detections`, IoU `wbf_iou`) of one detection list per view: view 0 is the
         step's own identity pass (the same maps the losses see), every other view one more forward of the oriented batch with the whole
         module in eval mode (`model(x, "infer")`), decoded and filtered like the identity pass.  The losses, the confusion matrices and
-        the segmentation metrics stay on the identity pass, and `compute()` keeps its keys.  `views=None`: not one launch changes.
+        the segmentation metrics stay on the identity pass (the last unless `seg_views`), and `compute()` keeps its keys.  `views=None`: not one launch changes.
         `fused_masks="vote"` (with `views` and `instance_masks`): the instance-mask mAP is fed from the fused list too -- every view's pass
         keeps its mask coefficients and prototypes, and the packed planes are voted over each cluster's members (`vote_masks`, as
         `detect_fused(masks="vote")`).  `views` with `instance_masks` needs it: there is no other fused mask to score.
+        `seg_views=True` (with `views`): the SEMANTIC metrics take part in the test-time augmentation too -- `self.seg`, `surface` and
+        `lesions` are fed the projector logits averaged over the views (`seg_to_frames` on every view's prototypes at identity
+        frames, its `logits` output as [B,1,S,S]) instead of the identity pass's.  False: not one launch changes.
         `surface` (True, or a dict of `SurfaceDistanceMetrics`' options quantile / tolerance / spacing / percentile_mode / undefined):
         also the boundary metrics of the semantic mask -- one `SurfaceDistanceMetrics.update` on the projector logits `self.seg` sees;
         `compute()` gains seg_hd_epoch, seg_hd95_epoch, seg_assd_epoch, seg_nsd_epoch and seg_surface_undefined.  None: not one
@@ -99,6 +102,9 @@ class ValidationStep:
         if fused_masks is not None and (self.views is None or not instance_masks):
             raise ValueError("fused_masks='vote' scores the voted masks of the fused list: it needs views and instance_masks=True")
         self.fused_masks = fused_masks
+        self.seg_views = bool(seg_views)
+        if self.seg_views and self.views is None:
+            raise ValueError("seg_views=True averages the semantic logits over the views: it needs views")
         if self.views is not None:
             if instance_masks and fused_masks is None:
                 raise NotImplementedError("ValidationStep: views with instance_masks=True needs fused_masks='vote' (the voted masks of "
@@ -222,20 +228,20 @@ class ValidationStep:
                                       iou_match_thresh=self.loss_kw["iou_match_thresh"], weight=self.mask_w, mc_layout="bnA", assigned=assigned)
             losses = (losses[0] + self.mask_w * mask[0],) + tuple(losses[1:]) + (mask[0], mask[1])
         self.losses.update(losses, B)
-        seg_logits = proto_projector_logits(protos, pj.weight, pj.bias, self.S)
-        self.seg.update(seg_logits, masks_gt)
-        if self.surface is not None:
-            self.surface.update(seg_logits, masks_gt)
-        if self.lesions is not None:
-            self.lesions.update(seg_logits, masks_gt)
+        if not self.seg_views:
+            self._seg_update(proto_projector_logits(protos, pj.weight, pj.bias, self.S), masks_gt)
         self.img.update(logits, cls_gt)
         self.det_cm.update(det, det_gt)
         d = decode_boxes(det, self.S, reg_max=self.reg_max, want_scores=False)
         k = nms_batched(d["boxes"], d["best_score"], d["best_label"], float(self.S), **self.nms_kw)
+        per_view = None
+        if self.views is not None:
+            per_view = [(k, (seg_out[1], protos)) if v == 0 else self._view_detections(imgs, v) for v in self.views]
+        if self.seg_views:
+            self._seg_update(self._view_seg_logits([s[1] for _, s in per_view]), masks_gt)
         sources = None
         if self.views is not None:
             vote = self.fused_masks is not None
-            per_view = [(k, (seg_out[1], protos)) if v == 0 else self._view_detections(imgs, v) for v in self.views]
             k = fuse_detections([d for d, _ in per_view], img_size=self.S, orients=self.views, iou_thr=self.wbf_iou, top_k=self.nms_kw["top_k"],
                                 want_members=vote)
             sources = [s for _, s in per_view] if vote else None
@@ -244,6 +250,22 @@ class ValidationStep:
         if self.instance_masks:
             self._mask_update(seg_out[1], protos, k, det_gt, masks_gt, sources)
         return losses
+
+    def _seg_update(self, seg_logits, masks_gt):
+        """The semantic mask's metrics, all from the same logits [B,1,S,S]."""
+        self.seg.update(seg_logits, masks_gt)
+        if self.surface is not None:
+            self.surface.update(seg_logits, masks_gt)
+        if self.lesions is not None:
+            self.lesions.update(seg_logits, masks_gt)
+
+    def _view_seg_logits(self, protos_per_view):
+        """The projector logits averaged over the views, upright, [B,1,S,S]: `seg_to_frames` at identity frames, its dense output (the
+        images are back to back in its buffer since S * S is a multiple of 4)."""
+        S, B = self.S, protos_per_view[0].shape[0]
+        r = seg_to_frames(list(protos_per_view), self.projector, [(S, S, 1.0)] * B, orients=self.views, logits=True,
+                          up=S / protos_per_view[0].shape[3])
+        return r["logits_buffer"][:B * S * S].view(B, 1, S, S) if (S * S) % 4 == 0 else torch.stack(r["logits"])[:, None]
 
     def _view_detections(self, imgs, view: int):
         """The detection list of one more view: `model(orient_batch(imgs, view), "infer")` with every module in eval mode (flags restored
