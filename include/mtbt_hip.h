@@ -1550,6 +1550,105 @@ int mtbt_seg_region_loss(const mtbt_seg_region_args* a, void* stream);
 /* sizeof() of the structs above as the library was compiled: which = 0 mtbt_distance_transform_args, 1 mtbt_seg_region_args; -1 otherwise */
 int mtbt_sizeof_distance_args(int which);
 
+/* ---------------------------------------------------------------------------------------------
+ * Bit-packed planes -> polygons (csrc/contours.hip; `postprocess.trace_contours`, `contour_polygons`, `yolo_seg_rows`,
+ * `labelme_shapes`): the way back from mtbt_fill_polygons.  Packed layout, alignment and shape limits as mtbt_label_components (planes
+ * 8-byte aligned, 8-byte accesses only, pitch = 8 * ceil(W / 64), bits X >= W never count, H and W in [1, 16384]); everything outside
+ * the plane is unset.
+ * THE CONTOUR RULE, exact in integers (tests/contour_reference.py restates it):
+ *   Lattice     pixel (X, Y) is the square [X, X + 1] x [Y, Y + 1].  A vertex is an integer point (x, y), 0 <= x <= W, 0 <= y <= H;
+ *               its key is y * (W + 1) + x.
+ *   Edges       a set pixel contributes up to four directed boundary edges: its top side (X, Y) -> (X + 1, Y) heading E when the pixel
+ *               above is unset, its right side (X + 1, Y) -> (X + 1, Y + 1) heading S when the pixel to the right is unset, its bottom
+ *               side (X + 1, Y + 1) -> (X, Y + 1) heading W when the pixel below is unset, its left side (X, Y + 1) -> (X, Y) heading N
+ *               when the pixel to the left is unset.  The set pixel always lies to the right of the direction of travel.
+ *   Successor   the edge that follows e starts where e ends.  Where two edges start there the vertex is a saddle (exactly two diagonal
+ *               pixels set): connectivity 4 takes the edge that turns right, in the cycle E -> S -> W -> N -> E, and the contour stays on
+ *               the same pixel; connectivity 8 takes the edge that turns left and the contour crosses to the diagonal pixel.  The
+ *               successor is a permutation of the edges; its cycles are the contours.
+ *   Vertices    the vertices of a contour are the start points of those of its edges whose predecessor has a different direction: no
+ *               three consecutive vertices are collinear, consecutive edges alternate between horizontal and vertical.  A contour may
+ *               pass through a lattice vertex twice; it never repeats a directed edge.
+ *   Start       the start point of the contour's E-heading edge with the smallest key (always a vertex of the contour); the vertices are
+ *               listed from there in successor order.
+ *   Order       the contours of a plane are sorted by the key of their start, ascending.
+ *   Area        area2 = sum over i of x_i * y_{i+1} - x_{i+1} * y_i, int64: > 0 for an outer contour, < 0 for a hole.
+ * What follows from the rule: every contour filled on its own by mtbt_fill_polygons (vertices as pixel coordinates: multiples of 16 in its
+ * fixed point against centres at 16 X + 8, so no tie) and the fills XOR-ed give back the plane; the sum of area2 is twice the popcount;
+ * the outer contours, in order, are the components of mtbt_label_components at the same connectivity in id order, the k-th starting at
+ * the k-th component's first pixel; the holes are the components of the complement, at the complementary connectivity, that do not reach
+ * the outside.
+ *   n_vertices  int32 [n]        the true number of contour vertices of the plane, never capped (<= 2 H W + 2)
+ *   n_contours  int32 [n]        the true count, or -1 when n_vertices > V = max_vertices
+ *   vertices    int32 [n][V][2]  x, y: the contours of the plane back to back, in contour order
+ *   offset      int32 [n][C]     first vertex row of contour i, C = max_contours in [1, 65536]
+ *   count       int32 [n][C]     its number of vertices
+ *   area2       int64 [n][C]
+ *   box         int32 [n][C][4]  x1, y1, x2, y2 over its vertices, lattice coordinates: for an outer contour the pixel box with exclusive
+ *                                maxima, the convention of mtbt_label_components
+ *   start       int32 [n][C]     the key of its start
+ * The tables hold the first min(n_contours, C) contours; the rows beyond are zero.  OVERFLOW: a plane with n_vertices > V has zero
+ * tables and n_contours = -1; its vertex rows are unspecified (nothing is written outside them).  Every other output word is defined
+ * after the call: the caller does not pre-zero.  Vertex rows from n_vertices on are not written.
+ * COUNT ONLY: vertices == NULL with every table pointer NULL (n_contours is then ignored, and so are workspace, max_contours and
+ * max_vertices): only n_vertices is written, by one pass that counts 2 x 2 pixel patterns (one vertex where one or three of the four
+ * pixels round a lattice point are set, two where exactly two diagonal ones are) -- no ranking, no workspace.
+ * Asynchronous on `stream`, no host synchronisation, graph-capturable, a pure function of the input (integer atomics only).  No
+ * workgroup waits on another; every loop bound is a host-side number (H, W, V, a round count from min(V, 2 H W + 2)), never device
+ * data.  `workspace`: >= mtbt_contours_workspace_bytes(n, H, W, max_vertices) bytes, 16-byte aligned (about 32 bytes per vertex of
+ * capacity; the query returns MTBT_EINVAL for a shape refused below).
+ * MTBT_EINVAL before any launch: NULL args, packed or n_vertices; n < 0, H or W outside [1, 16384], pitch != 8 * ceil(W / 64); a
+ * connectivity other than 4 or 8; and, unless the call is count only: a NULL vertices, n_contours or table pointer (so also tables
+ * given without vertices), max_contours outside [1, 65536], max_vertices < 0, workspace NULL or workspace_bytes below the query.
+ * MTBT_EALIGN: packed or area2 not 8-byte, workspace not 16-byte, the other pointers not 4-byte aligned.  n == 0 launches nothing. */
+typedef struct mtbt_contours_args {
+  const uint8_t* packed;   /* [n][H][pitch] */
+  void* workspace;
+  int64_t workspace_bytes;
+  int32_t* n_vertices;     /* [n] */
+  int32_t* n_contours;     /* [n] */
+  int32_t* vertices;       /* [n][V][2] or NULL: count only */
+  int32_t* offset;         /* [n][C] */
+  int32_t* count;          /* [n][C] */
+  int64_t* area2;          /* [n][C] */
+  int32_t* box;            /* [n][C][4] */
+  int32_t* start;          /* [n][C] */
+  int32_t n, H, W, pitch;
+  int32_t connectivity;    /* 4 or 8 */
+  int32_t max_contours;    /* C */
+  int32_t max_vertices;    /* V, per plane */
+  int32_t reserved;        /* 0 */
+} mtbt_contours_args;
+int64_t mtbt_contours_workspace_bytes(int n, int H, int W, int max_vertices);
+int mtbt_trace_contours(const mtbt_contours_args* a, void* stream);
+
+/* Bit-packed planes -> COCO run lengths (`postprocess.rle_encode`, `coco_segm_results`).  Same planes as above.
+ * THE RUN RULE (tests/contour_reference.py restates it): the pixels of a plane read COLUMN-MAJOR, index x * H + y, fall into runs of
+ * equal pixels; the runs are listed from a run of UNSET pixels, which is 0 when pixel (0, 0) is set, and alternate from there.  Their
+ * sum is H * W.  This is the uncompressed `counts` of a COCO RLE of size [H, W].
+ *   n_runs  int32  [n]     the true number of runs, never capped (<= H W + 1)
+ *   counts  uint32 [n][R]  the first min(n_runs, R) runs, R = max_runs >= 0; the words from n_runs on are not written; NULL: only
+ *                          n_runs is written (then max_runs is ignored)
+ * Asynchronous on `stream`, no host synchronisation, no atomics, graph-capturable; loop bounds are host-side numbers.  `workspace`:
+ * >= mtbt_rle_workspace_bytes(n, H, W) bytes, 16-byte aligned (8 bytes per column and 128-row band).
+ * MTBT_EINVAL before any launch: NULL args, packed or n_runs; workspace NULL when the query is > 0; n < 0, H or W outside [1, 16384],
+ * pitch != 8 * ceil(W / 64), max_runs < 0 with counts given, workspace_bytes below the query.  MTBT_EALIGN: packed not 8-byte, workspace not 16-byte, counts or
+ * n_runs not 4-byte aligned.  n == 0 launches nothing. */
+typedef struct mtbt_rle_args {
+  const uint8_t* packed;   /* [n][H][pitch] */
+  void* workspace;
+  int64_t workspace_bytes;
+  uint32_t* counts;        /* [n][R] or NULL */
+  int32_t* n_runs;         /* [n] */
+  int32_t n, H, W, pitch;
+  int32_t max_runs;        /* R */
+  int32_t reserved;        /* 0 */
+} mtbt_rle_args;
+int64_t mtbt_rle_workspace_bytes(int n, int H, int W);
+int mtbt_rle_encode(const mtbt_rle_args* a, void* stream);
+/* sizeof() of the structs above as the library was compiled: which = 0 mtbt_contours_args, 1 mtbt_rle_args; -1 otherwise */
+int mtbt_sizeof_contours_args(int which);
+
 /* Weight gradient of a k x k convolution (any stride / padding; 1x1 and the 2x2 stride-2 downsample included), bf16 (MFMA) or fp32 operands:
  *   dw[k][r][s][c] (fp32, packed [K][R*S*C] like the forward weight) (+)= sum_p dy[p][k] * x[n][y*stride + r - pad][x*stride + s - pad][c]
  * x [N,H,W,C], dy [N,Ho,Wo,K] (Ho = (H + 2 pad - R) / stride + 1) NHWC with pixel / batch strides in elements (multiples of 8; C % 8 == K % 8 == 0;

@@ -23,6 +23,8 @@
     from multitask_bonetumor_yolo_amd import copy_paste_batch, sample_copy_paste   # instances pasted between the canvases of a batch
     from multitask_bonetumor_yolo_amd import distance_transform, signed_distance   # exact Euclidean distance maps of packed masks
     from multitask_bonetumor_yolo_amd import seg_region_loss, SegRegionLoss   # soft Dice + boundary terms of the segmentation loss
+    from multitask_bonetumor_yolo_amd import trace_contours, yolo_seg_rows, labelme_shapes   # packed masks -> polygons (YOLO-seg rows, LabelMe shapes)
+    from multitask_bonetumor_yolo_amd import rle_encode, coco_segm_results   # packed masks -> COCO run lengths and a segm results list
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
@@ -45,6 +47,8 @@ from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
 from .postprocess import (components_to_instances, distance_transform, fill_polygons, filter_components, label_components, merge_tiles, vote_masks,  # noqa: F401
                           seg_to_frames, signed_distance, vote_tile_masks, yolo_seg_planes)
+from .postprocess import (coco_segm_results, contour_polygons, count_contour_vertices, labelme_shapes, rle_encode, rle_from_string,  # noqa: F401
+                          rle_to_string, trace_contours, yolo_seg_polygons, yolo_seg_rows)
 from .sliced import detect_sliced  # noqa: F401
 from .trainstep import TrainStep, ema_decay_at  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

@@ -285,6 +285,19 @@ class SegRegionArgs(C.Structure):  # mtbt_seg_region_args
                 ("smooth", C.c_float), ("w_dice", C.c_float), ("w_boundary", C.c_float), ("accumulate", C.c_int32)]
 
 
+class ContoursArgs(C.Structure):  # mtbt_contours_args
+    _fields_ = [("packed", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("n_vertices", C.c_void_p),
+                ("n_contours", C.c_void_p), ("vertices", C.c_void_p), ("offset", C.c_void_p), ("count", C.c_void_p), ("area2", C.c_void_p),
+                ("box", C.c_void_p), ("start", C.c_void_p), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32),
+                ("connectivity", C.c_int32), ("max_contours", C.c_int32), ("max_vertices", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RleArgs(C.Structure):  # mtbt_rle_args
+    _fields_ = [("packed", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("counts", C.c_void_p),
+                ("n_runs", C.c_void_p), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32),
+                ("max_runs", C.c_int32), ("reserved", C.c_int32)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -437,6 +450,11 @@ SYMBOLS = {
     "mtbt_seg_region_loss_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mtbt_seg_region_loss": (C.c_int, [C.POINTER(SegRegionArgs), C.c_void_p]),
     "mtbt_sizeof_distance_args": (C.c_int, [C.c_int]),
+    "mtbt_contours_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mtbt_trace_contours": (C.c_int, [C.POINTER(ContoursArgs), C.c_void_p]),
+    "mtbt_rle_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "mtbt_rle_encode": (C.c_int, [C.POINTER(RleArgs), C.c_void_p]),
+    "mtbt_sizeof_contours_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -450,6 +468,7 @@ POLYGON_STRUCTS = (FillPolygonsArgs,)   # order of mtbt_sizeof_fill_polygons_arg
 CLAHE_STRUCTS = (ClaheImage,)   # order of mtbt_sizeof_clahe_args(which)
 COPY_PASTE_STRUCTS = (CopyPasteArgs,)   # order of mtbt_sizeof_copy_paste_args(which)
 DISTANCE_STRUCTS = (DistanceTransformArgs, SegRegionArgs)   # order of mtbt_sizeof_distance_args(which)
+CONTOURS_STRUCTS = (ContoursArgs, RleArgs)   # order of mtbt_sizeof_contours_args(which)
 _lib = None
 
 
@@ -475,7 +494,8 @@ def load():
                                 (lib.mtbt_sizeof_tile_args, TILE_STRUCTS), (lib.mtbt_sizeof_surface_args, SURFACE_STRUCTS),
                                 (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS), (lib.mtbt_sizeof_fill_polygons_args, POLYGON_STRUCTS),
                                 (lib.mtbt_sizeof_clahe_args, CLAHE_STRUCTS), (lib.mtbt_sizeof_copy_paste_args, COPY_PASTE_STRUCTS),
-                                (lib.mtbt_sizeof_distance_args, DISTANCE_STRUCTS), (lib.mtbt_sizeof_seg_frame_args, SEG_FRAME_STRUCTS)):
+                                (lib.mtbt_sizeof_distance_args, DISTANCE_STRUCTS), (lib.mtbt_sizeof_seg_frame_args, SEG_FRAME_STRUCTS),
+                                (lib.mtbt_sizeof_contours_args, CONTOURS_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

@@ -1171,6 +1171,15 @@ def yolo_seg_planes(rows: Sequence[Sequence[float]], H0: int, W0: int, device=No
     [G]) on the device: one plane per row in the image's own pixels, vertices at (x * W0, y * H0), filled by `fill_polygons`.  Rows of
     fewer than 3 points are skipped.  The per-image ground truth `DeviceMaskMeanAveragePrecision.update_batched` and
     `SurfaceDistanceMetrics.update_packed` take."""
+    polys, labels = yolo_seg_polygons(rows, H0, W0)
+    packed = fill_polygons(polys, H0, W0, device=device)
+    labels = torch.tensor(labels, dtype=torch.int64)
+    return packed, (labels.pin_memory().to(packed.device, non_blocking=True) if labels.numel() else labels.to(packed.device))
+
+
+def yolo_seg_polygons(rows: Sequence[Sequence[float]], H0: int, W0: int):
+    """The row parser of `yolo_seg_planes`, on the host: YOLO-seg rows -> (list of float64 [k, 2] polygons in the image's pixels,
+    list of int classes).  Rows of fewer than 3 points are skipped."""
     polys, labels = [], []
     for r in rows:
         pts = [float(v) for v in r[1:]]
@@ -1180,6 +1189,233 @@ def yolo_seg_planes(rows: Sequence[Sequence[float]], H0: int, W0: int, device=No
         v = np.asarray(pts[:2 * k], dtype=np.float64).reshape(k, 2)
         polys.append(v * np.asarray([float(W0), float(H0)]))
         labels.append(int(r[0]))
-    packed = fill_polygons(polys, H0, W0, device=device)
-    labels = torch.tensor(labels, dtype=torch.int64)
-    return packed, (labels.pin_memory().to(packed.device, non_blocking=True) if labels.numel() else labels.to(packed.device))
+    return polys, labels
+
+
+# ---- bit-packed planes -> polygons (THE CONTOUR RULE: include/mtbt_hip.h `mtbt_trace_contours`) -------------------------------------
+def _count_contour_vertices(lib, planes, n, H, W, pitch, connectivity, dev):
+    n_vertices = torch.empty((n,), dtype=torch.int32, device=dev)
+    a = L.ContoursArgs()
+    a.packed, a.n_vertices = planes.data_ptr(), n_vertices.data_ptr()
+    a.n, a.H, a.W, a.pitch, a.connectivity = n, H, W, pitch, connectivity
+    with torch.cuda.device(dev):
+        L.check(lib.mtbt_trace_contours(C.byref(a), _stream(dev)), "mtbt_trace_contours")
+    return n_vertices
+
+
+def count_contour_vertices(packed: torch.Tensor, W: int) -> torch.Tensor:
+    """int32 [n]: the number of contour vertices of every plane (the count-only call of `mtbt_trace_contours`: one pass over 2 x 2
+    pixel patterns, the same for both connectivities).  Asynchronous."""
+    W = int(W)
+    n, H, pitch, planes, _ = _component_planes("count_contour_vertices", packed, W)
+    if n == 0:
+        return torch.empty((0,), dtype=torch.int32, device=packed.device)
+    return _count_contour_vertices(L.load(), planes, n, H, W, pitch, 4, packed.device)
+
+
+def trace_contours(packed: torch.Tensor, W: int, *, connectivity: int = 4, max_contours: int = 1024, max_vertices: Optional[int] = None,
+                   labels: Optional[torch.Tensor] = None):
+    """The boundary polygons of n bit-packed planes, on the device (`mtbt_trace_contours`; THE CONTOUR RULE is in include/mtbt_hip.h).
+
+    packed: uint8 [n, H, pitch] with pitch = 8 * ceil(W / 64) (`pack_masks`, `masks_to_frames`, `seg_to_frames`); bits X >= W never
+    count.  A contour runs along pixel edges with the set pixels on its right; its vertices are lattice points (x, y), 0 <= x <= W,
+    0 <= y <= H, the corners only.  At a vertex where two diagonal pixels meet, `connectivity` 4 keeps them apart and 8 joins them:
+    the outer contours are then exactly the components of `label_components(connectivity=same)`, in id order.  Filling every contour
+    with `fill_polygons` and XOR-ing the fills gives the plane back.  Returns a dict of device tensors:
+      `n_vertices` int32 [n] (true), `n_contours` int32 [n] (true, or -1 for a plane with more than `max_vertices` vertices: its
+      tables are then zero), `vertices` int32 [n, V, 2] (x, y; the contours back to back in order of their start),
+      and for the first min(n_contours, max_contours) contours `offset`, `count`, `start` int32 [n, C] (start = y * (W + 1) + x of the
+      first vertex, the top-left corner of the contour's first pixel row), `area2` int64 [n, C] (twice the signed area: > 0 outer,
+      < 0 hole), `boxes` float32 [n, C, 4] xyxy over the vertices (for an outer contour the pixel box with exclusive maxima, as
+      `label_components` returns it), `hole` bool [n, C];
+      `component` int32 [n, C] when `labels` = label_components(..., connectivity=same)["labels"] is given: labels[y, x] of the pixel
+      under the start edge, i.e. the component an outer contour bounds or a hole lies in (None otherwise; 0 in unused rows).
+    `shape` = (H, W).  With max_vertices=None the vertices are counted first (`count_contour_vertices`), the largest count is read
+    back and `vertices` is allocated exactly: ONE host synchronisation.  An explicit `max_vertices` never synchronises."""
+    W, connectivity, C_ = int(W), int(connectivity), int(max_contours)
+    n, H, pitch, planes, _ = _component_planes("trace_contours", packed, W)
+    if connectivity not in (4, 8):
+        raise ValueError(f"trace_contours: connectivity 4 or 8, not {connectivity}")
+    if not 1 <= C_ <= COMPONENTS_MAX_TABLE:
+        raise ValueError(f"trace_contours: max_contours {C_} is outside [1, {COMPONENTS_MAX_TABLE}]")
+    if max_vertices is not None and not 0 <= int(max_vertices) < 2 ** 31:
+        raise ValueError("trace_contours: max_vertices must be >= 0 (and fit 32 bits)")
+    dev = packed.device
+    if labels is not None and (not isinstance(labels, torch.Tensor) or tuple(labels.shape) != (n, H, W) or labels.device != dev):
+        raise ValueError(f"trace_contours: labels must be the [{n}, {H}, {W}] label map of label_components, on the planes' device")
+    lib = L.load() if n else None
+    if max_vertices is None:
+        V = int(_count_contour_vertices(lib, planes, n, H, W, pitch, connectivity, dev).max()) if n else 0   # the host synchronisation
+    else:
+        V = int(max_vertices)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    out = {"n_vertices": i32(n), "n_contours": i32(n), "vertices": i32(n, V, 2), "offset": i32(n, C_), "count": i32(n, C_),
+           "area2": torch.empty((n, C_), dtype=torch.int64, device=dev), "start": i32(n, C_), "shape": (H, W), "component": None}
+    box = i32(n, C_, 4)
+    if n:
+        ws_bytes = int(lib.mtbt_contours_workspace_bytes(n, H, W, V))
+        if ws_bytes < 0:
+            L.check(ws_bytes, "mtbt_contours_workspace_bytes")
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        a = L.ContoursArgs()
+        a.packed, a.workspace, a.workspace_bytes = planes.data_ptr(), ws.data_ptr(), ws_bytes
+        a.n_vertices, a.n_contours, a.vertices = out["n_vertices"].data_ptr(), out["n_contours"].data_ptr(), out["vertices"].data_ptr()
+        a.vertices = a.vertices or ws.data_ptr()               # V = 0: an empty tensor has no address; nothing is stored through it
+        a.offset, a.count, a.area2, a.box, a.start = (out["offset"].data_ptr(), out["count"].data_ptr(), out["area2"].data_ptr(),
+                                                      box.data_ptr(), out["start"].data_ptr())
+        a.n, a.H, a.W, a.pitch, a.connectivity, a.max_contours, a.max_vertices = n, H, W, pitch, connectivity, C_, V
+        with torch.cuda.device(dev):
+            L.check(lib.mtbt_trace_contours(C.byref(a), _stream(dev)), "mtbt_trace_contours")
+    out["boxes"] = box.float()
+    out["hole"] = out["area2"] < 0
+    if labels is not None:
+        used = out["count"] > 0
+        sy, sx = torch.div(out["start"], W + 1, rounding_mode="floor"), out["start"] % (W + 1)
+        flat = (sy.long() * W + sx.long()).clamp_(0, H * W - 1)                        # the pixel under the start edge is (x, y) itself
+        out["component"] = torch.where(used, torch.gather(labels.reshape(n, H * W), 1, flat).to(torch.int32), torch.zeros_like(out["start"]))
+    return out
+
+
+def contour_polygons(result: dict, plane: int, holes: bool = False):
+    """The polygons of one plane of a `trace_contours` result as a list of int32 [k, 2] numpy arrays (x, y), in contour order; the
+    holes only with holes=True.  Reads the small tables and the plane's vertices back: synchronises.  A plane that did not fit
+    `max_vertices` (n_contours = -1) or has more contours than `max_contours` raises ValueError."""
+    plane = int(plane)
+    nc, nv = int(result["n_contours"][plane]), int(result["n_vertices"][plane])
+    C_ = int(result["offset"].shape[1])
+    if nc < 0:
+        raise ValueError(f"contour_polygons: plane {plane} has {nv} vertices, more than max_vertices = {int(result['vertices'].shape[1])}")
+    if nc > C_:
+        raise ValueError(f"contour_polygons: plane {plane} has {nc} contours, more than max_contours = {C_}")
+    verts = result["vertices"][plane, :nv].cpu().numpy()
+    off, cnt, hole = (result[k][plane, :nc].cpu().numpy() for k in ("offset", "count", "hole"))
+    return [verts[o:o + c].astype(np.int32) for o, c, h in zip(off, cnt, hole) if holes or not h]
+
+
+def yolo_seg_rows(result: dict, labels, W0: int, H0: int):
+    """YOLO-seg label rows of a `trace_contours` result over planes of an image of W0 x H0 pixels: one row `[cls, x1, y1, x2, y2, ...]`
+    per OUTER contour, coordinates normalised by W0 and H0, cls = labels[plane] (a sequence or tensor of one class per plane).  What
+    `yolo_seg_planes` reads.  HOLES ARE OMITTED: the format cannot carry them, so a plane with holes comes back filled.  Synchronises."""
+    labels = labels.tolist() if isinstance(labels, (torch.Tensor, np.ndarray)) else list(labels)
+    n = int(result["n_contours"].shape[0])
+    if len(labels) != n:
+        raise ValueError(f"yolo_seg_rows: {len(labels)} labels for {n} planes")
+    scale = np.asarray([float(W0), float(H0)])
+    rows = []
+    for b in range(n):
+        for poly in contour_polygons(result, b):
+            rows.append([int(labels[b])] + (poly.astype(np.float64) / scale).reshape(-1).tolist())
+    return rows
+
+
+def labelme_shapes(result: dict, plane: int, label: str):
+    """The `shapes` list of a LabelMe file for one plane of a `trace_contours` result: one {"label", "points": [[x, y], ...],
+    "shape_type": "polygon"} per OUTER contour (plus LabelMe's empty "group_id" and "flags").  HOLES ARE OMITTED: a LabelMe polygon
+    cannot carry them.  Synchronises."""
+    return [{"label": str(label), "points": poly.astype(np.float64).tolist(), "group_id": None, "shape_type": "polygon", "flags": {}}
+            for poly in contour_polygons(result, plane)]
+
+
+# ---- bit-packed planes -> COCO run lengths (THE RUN RULE: include/mtbt_hip.h `mtbt_rle_encode`) ------------------------------------
+def rle_encode(packed: torch.Tensor, W: int, max_runs: Optional[int] = None):
+    """The uncompressed COCO run lengths of n bit-packed planes, on the device (`mtbt_rle_encode`): the pixels read column-major
+    (index x * H + y), runs alternating from a run of unset pixels (0 when pixel (0, 0) is set); their sum is H * W.
+
+    Returns (`counts` int32 [n, R], `n_runs` int32 [n], the true number of runs).  Row b of `counts` holds its first
+    min(n_runs[b], R) runs (every run is at most H * W < 2^31); the words beyond are unspecified.  With max_runs=None the runs are
+    counted first, the largest count is read back and R is exact: ONE host synchronisation.  An explicit `max_runs` never
+    synchronises; a plane with n_runs > R is cut."""
+    W = int(W)
+    n, H, pitch, planes, _ = _component_planes("rle_encode", packed, W)
+    if max_runs is not None and not 0 <= int(max_runs) < 2 ** 31:
+        raise ValueError("rle_encode: max_runs must be >= 0 (and fit 32 bits)")
+    dev = packed.device
+    n_runs = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n == 0:
+        return torch.empty((0, int(max_runs or 0)), dtype=torch.int32, device=dev), n_runs
+    lib = L.load()
+    ws_bytes = int(lib.mtbt_rle_workspace_bytes(n, H, W))
+    if ws_bytes < 0:
+        L.check(ws_bytes, "mtbt_rle_workspace_bytes")
+    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    a = L.RleArgs()
+    a.packed, a.workspace, a.workspace_bytes, a.n_runs = planes.data_ptr(), ws.data_ptr(), ws_bytes, n_runs.data_ptr()
+    a.n, a.H, a.W, a.pitch = n, H, W, pitch
+    with torch.cuda.device(dev):
+        if max_runs is None:
+            L.check(lib.mtbt_rle_encode(C.byref(a), _stream(dev)), "mtbt_rle_encode")
+            R = int(n_runs.max())                               # the host synchronisation
+        else:
+            R = int(max_runs)
+        counts = torch.empty((n, R), dtype=torch.int32, device=dev)
+        if R > 0 or max_runs is not None:
+            a.counts, a.max_runs = (counts.data_ptr() if R > 0 else None), R
+            L.check(lib.mtbt_rle_encode(C.byref(a), _stream(dev)), "mtbt_rle_encode")
+    return counts, n_runs
+
+
+def rle_to_string(counts) -> str:
+    """A run-length list as the compressed `counts` string of a COCO RLE (the pycocotools scheme): x[i] -= x[i - 2] for i > 2, every
+    value in 5-bit groups, least significant first, 0x20 the continuation bit, bit 0x10 of the last group the sign, each group + 48
+    as ASCII."""
+    counts = [int(c) for c in counts]
+    out = []
+    for i, x in enumerate(counts):
+        if i > 2:
+            x -= counts[i - 2]
+        more = True
+        while more:
+            c = x & 0x1F
+            x >>= 5
+            more = (x != -1) if (c & 0x10) else (x != 0)
+            out.append(chr((c | 0x20 if more else c) + 48))
+    return "".join(out)
+
+
+def rle_from_string(s: str):
+    """The inverse of `rle_to_string`: the list of run lengths."""
+    counts, p = [], 0
+    while p < len(s):
+        x, k, more = 0, 0, True
+        while more:
+            c = ord(s[p]) - 48
+            x |= (c & 0x1F) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << (5 * k)
+        if len(counts) > 2:
+            x += counts[-2]
+        counts.append(x)
+    return counts
+
+
+def coco_segm_results(out: dict, image_ids, category_ids=None, frames=None):
+    """The instance results of a batch as the list a COCO `segm` results file holds: for every kept detection
+    {"image_id", "category_id", "score", "bbox": [x, y, w, h], "segmentation": {"size": [H0, W0], "counts": str}}.
+
+    `out`: a `detect_and_segment(..., frames=...)` result (or `detect_fused` / `detect_sliced`): `masks_frame` (bit-packed planes per
+    image), `boxes_frame`, `scores`, `labels`, `counts`.  `frames`: the [(H0, W0, scale)] the result was made with (or `out["frames"]`):
+    the packed planes do not carry their width.  `image_ids`: one id per image.  `category_ids`: a sequence or dict from the label to the
+    dataset's category id (None: the label itself).  The masks are run-length encoded on the device (`rle_encode`), only the runs come
+    to the host; the strings are the pycocotools compression (`rle_to_string`).  Synchronises."""
+    frames = out.get("frames") if frames is None else frames
+    B = len(out["masks_frame"])
+    if frames is None or len(frames) != B or len(image_ids) != B:
+        raise ValueError(f"coco_segm_results: {B} images need as many frames (H0, W0, scale) and image ids")
+    n_kept, scores, labels, boxes = (out[k].cpu().numpy() for k in ("counts", "scores", "labels", "boxes_frame"))
+    results = []
+    for b in range(B):
+        H0, W0, k = int(frames[b][0]), int(frames[b][1]), int(n_kept[b])
+        if k == 0:
+            continue
+        runs, n_runs = rle_encode(out["masks_frame"][b][:k], W0)
+        runs, n_runs = runs.cpu().numpy(), n_runs.cpu().numpy()
+        for j in range(k):
+            lab = int(labels[b, j])
+            x1, y1, x2, y2 = (float(v) for v in boxes[b, j])
+            results.append({"image_id": image_ids[b], "category_id": lab if category_ids is None else category_ids[lab], "score": float(scores[b, j]),
+                            "bbox": [x1, y1, x2 - x1, y2 - y1],
+                            "segmentation": {"size": [H0, W0], "counts": rle_to_string(runs[j, :n_runs[j]].tolist())}})
+    return results
