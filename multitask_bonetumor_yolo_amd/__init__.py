@@ -3,6 +3,7 @@
     from multitask_bonetumor_yolo_amd import ConvNeXtBiFPNYOLO          # == reference main_model.ConvNeXtBiFPNYOLO
     from multitask_bonetumor_yolo_amd import postprocess                 # decode / NMS / masks on the GPU
     from multitask_bonetumor_yolo_amd import preprocess                  # letterbox / BGR->RGB / /255 of a batch on the GPU
+    from multitask_bonetumor_yolo_amd import planes                      # bit-packed mask planes: pack, components, distances, polygons, RLE
     from multitask_bonetumor_yolo_amd import augment_samples             # training augmentation fused into that launch (the reference has none)
     from multitask_bonetumor_yolo_amd import mosaic_samples              # the same with four images per canvas
     from multitask_bonetumor_yolo_amd import affine_samples, affine_samples_seg   # rotation and shear: an affine map per canvas, labels moved with it
@@ -29,7 +30,7 @@
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
 """
-from . import postprocess, preprocess  # noqa: F401
+from . import planes, postprocess, preprocess  # noqa: F401
 from .preprocess import (affine_coefficients, affine_forward, affine_polygons, affine_samples, affine_samples_seg, affine_yolo_labels,  # noqa: F401
                          sample_affine, warp_batch)
 from .preprocess import copy_paste_batch, sample_copy_paste  # noqa: F401
@@ -45,10 +46,10 @@ from .metrics import (DetectionConfusionMatrix, DeviceMaskMeanAveragePrecision, 
                       lesion_hits, surface_distances, surface_metrics)
 from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
-from .postprocess import (components_to_instances, distance_transform, fill_polygons, filter_components, label_components, merge_tiles, vote_masks,  # noqa: F401
-                          seg_to_frames, signed_distance, vote_tile_masks, yolo_seg_planes)
-from .postprocess import (coco_segm_results, contour_polygons, count_contour_vertices, labelme_shapes, rle_encode, rle_from_string,  # noqa: F401
-                          rle_to_string, trace_contours, yolo_seg_polygons, yolo_seg_rows)
+from .postprocess import merge_tiles, seg_to_frames, vote_masks, vote_tile_masks  # noqa: F401
+from .planes import (coco_segm_results, components_to_instances, contour_polygons, count_contour_vertices, distance_transform, fill_polygons,  # noqa: F401
+                     filter_components, label_components, labelme_shapes, rle_encode, rle_from_string, rle_to_string, signed_distance,
+                     trace_contours, yolo_seg_planes, yolo_seg_polygons, yolo_seg_rows)
 from .sliced import detect_sliced  # noqa: F401
 from .trainstep import TrainStep, ema_decay_at  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

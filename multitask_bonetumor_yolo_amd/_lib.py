@@ -2,6 +2,8 @@
 import ctypes as C
 import os
 
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmtbt_hip.so")
 
@@ -513,3 +515,17 @@ def load():
 def check(code: int, what: str):
     if code != 0:
         raise RuntimeError(f"{what}: {ERRORS.get(code, code)}")
+
+
+def stream(dev):
+    """The current stream of `dev`, as the `void* stream` every entry point takes last."""
+    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def workspace(fn, *dims, device, what: str):
+    """The scratch buffer a `*_workspace_bytes` query `fn(*dims)` asks for -> (uint8 tensor, nbytes).  A negative answer is the query's
+    refusal of the shape and raises through `check` under the name `what`; the tensor has at least 16 bytes, so that it has an address."""
+    nbytes = int(fn(*dims))
+    if nbytes < 0:
+        check(nbytes, what)
+    return torch.empty(max(nbytes, 16), dtype=torch.uint8, device=device), nbytes

@@ -12,7 +12,6 @@ deterministic split reduction; 3x3 / stride 1 from an LDS halo tile).  The helpe
 that keeps what backward needs, the backward launch plan with plan-resident scratch, the autograd boundary -- is `train.py` /
 `trainstep.py` (DESIGN.md section 7).  The plan-building helpers (`conv_dgrad`, `dwconv_dgrad`, ...) append launches to an `engine.Plan`;
 weights are re-laid out once by the `*_weight` helpers (device tensors, any dtype the kernels take)."""
-import ctypes as C
 
 import torch
 
@@ -71,7 +70,7 @@ def conv_wgrad(x: Act, dy: Act, *, R: int, S: int, pad: int, stride: int = 1, ou
     nbytes = lib.mtbt_conv_wgrad_workspace_bytes(x.N, x.H, x.W, Cc, K, R, S)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     L.check(lib.mtbt_conv_wgrad(x.ptr, dy.ptr, out.data_ptr(), x.N, x.H, x.W, Cc, K, R, S, pad, stride, x.batch_stride, x.ld, dy.batch_stride, dy.ld,
-                                x.code, int(accumulate), ws.data_ptr(), nbytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                                x.code, int(accumulate), ws.data_ptr(), nbytes, L.stream(dev)),
             "mtbt_conv_wgrad")
     return out
 
@@ -83,7 +82,7 @@ def act_backward(dy: Act, z: Act, act: int, out: Act = None) -> Act:
     if out is None:
         out = Act.of(torch.empty_like(dy.buf))
     dev = dy.buf.device
-    L.check(lib.mtbt_act_backward(dy.ptr, z.ptr, out.ptr, dy.buf.numel(), act, dy.code, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+    L.check(lib.mtbt_act_backward(dy.ptr, z.ptr, out.ptr, dy.buf.numel(), act, dy.code, L.stream(dev)),
             "mtbt_act_backward")
     return out
 
@@ -101,7 +100,7 @@ def channel_sum(x: Act, out: torch.Tensor = None, accumulate: bool = False, time
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     L.check(lib.mtbt_channel_sum(x.ptr, times.ptr if times is not None else None, P, x.C, x.ld, times.ld if times is not None else 0, x.code,
                                  out.data_ptr(), int(accumulate), ws.data_ptr(), nbytes,
-                                 C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_channel_sum")
+                                 L.stream(dev)), "mtbt_channel_sum")
     return out
 
 
@@ -126,7 +125,7 @@ def batchnorm_train_backward(dz: Act, u: Act, gamma: torch.Tensor, beta: torch.T
     out = Act.of(torch.empty_like(dz.buf))
     a, b, d = a.contiguous(), b.contiguous(), d.contiguous()
     L.check(lib.mtbt_channel_affine2(dz.ptr, u.ptr, a.data_ptr(), b.data_ptr(), d.data_ptr(), out.ptr, dz.N * dz.H * dz.W, dz.C, dz.code,
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_channel_affine2")
+                                     L.stream(dev)), "mtbt_channel_affine2")
     out._keep = (a, b, d)                               # the launch is asynchronous
     return out, d_gamma, d_beta
 
@@ -140,7 +139,7 @@ def layernorm_backward(x: Act, dy: Act, gamma: torch.Tensor, eps: float):
     dx, xhat = Act.of(torch.empty_like(x.buf)), Act.of(torch.empty_like(x.buf))
     g = gamma.float().contiguous()
     L.check(lib.mtbt_layernorm_backward_nhwc(x.ptr, dy.ptr, g.data_ptr(), eps, dx.ptr, xhat.ptr, x.N * x.H * x.W, x.C, x.code, 0,
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_layernorm_backward_nhwc")
+                                             L.stream(dev)), "mtbt_layernorm_backward_nhwc")
     dx._keep = g
     return dx, channel_sum(dy, times=xhat), channel_sum(dy)
 
@@ -155,5 +154,5 @@ def dwconv_wgrad(x: Act, dy: Act, ksize: int, out: torch.Tensor = None, accumula
     nbytes = lib.mtbt_dwconv_wgrad_workspace_bytes(x.N, x.H, x.W, x.C, ksize)
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     L.check(lib.mtbt_dwconv_wgrad(x.ptr, dy.ptr, out.data_ptr(), x.N, x.H, x.W, x.C, ksize, x.code, int(accumulate), ws.data_ptr(), nbytes,
-                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_dwconv_wgrad")
+                                  L.stream(dev)), "mtbt_dwconv_wgrad")
     return out

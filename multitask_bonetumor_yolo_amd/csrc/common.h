@@ -192,6 +192,47 @@ __device__ __forceinline__ float wave_sum(float v) {
   return v;
 }
 
+// the same butterfly on unsigned integers: exact, so the order cannot show
+__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Sums over a workgroup of NW waves with a fixed tree; every thread gets the result.  `red` holds NW words of LDS; two barriers.
+template <int NW>
+__device__ __forceinline__ unsigned block_sum_u32(unsigned v, unsigned* red, int lane, int wave) {
+  v = wave_sum_u32(v);
+  __syncthreads();                 // the previous result has been read by every thread
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  unsigned s = 0u;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) s += red[w];
+  return s;
+}
+// ... and the maximum (MAX) or minimum over it, under the same contract
+template <int NW, bool MAX>
+__device__ __forceinline__ unsigned block_extreme_u32(unsigned v, unsigned* red, int lane, int wave) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned u = __shfl_xor(v, o, 64);
+    v = MAX ? max(v, u) : min(v, u);
+  }
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  unsigned s = red[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) s = MAX ? max(s, red[w]) : min(s, red[w]);
+  return s;
+}
+
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // One-time (per kernel instantiation AND per device) opt-in to more than 64 KiB of dynamic LDS.  The flag array is racy

@@ -34,17 +34,13 @@
 //                    surface_select_kernel (at most 31 passes), ties to the lower id by a prefix over the ids, the keep flag into bit 31
 //                    of the area word, n_kept.
 // cc_write_kernel    word kernel.  run start -> root -> id -> keep flag, a ballot per word, lane 0 stores the 8 bytes (padding zero).
-#include "common.h"
+#include "bitplane.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int CHUNK = 64;                 // planes per launch group (grid z)
 constexpr int WT = 256;                   // threads of every workgroup here
 constexpr int WW = WT / 64;               // waves per workgroup
 constexpr int WORDS_PER_WAVE = 8;
-constexpr int MAX_DIM = 16384;
 constexpr int MAX_COMPONENTS = 65536;
 constexpr unsigned KEEP = 0x80000000u;    // keep flag in the per-id area word (an area is below 2^31)
 
@@ -52,12 +48,10 @@ struct Layout {   // byte offsets of the sections of the workspace (all n planes
   int64_t parent, area, roots, rowoff, tot, total;
 };
 
-int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 int64_t max_ids(int64_t H, int64_t W) { return (H * W + 1) / 2; }   // a checkerboard under 4-connectivity
 
 Layout layout_of(int64_t n, int64_t H, int64_t W) {
-  const int64_t nw = (W + 63) / 64;
+  const int64_t nw = plane_words(W);
   Layout l;
   int64_t off = 0;
   l.parent = off; off = up16(off + n * H * W * 4);
@@ -88,11 +82,6 @@ struct CompP {
   int plane0, H, W, words_x, conn8, C;
   unsigned ids_per_plane, min_area, keep_largest;
 };
-
-__device__ __forceinline__ u64 valid_bits(int w, int W) {   // the bits X < W of row word w
-  const int nv = W - w * 64;
-  return nv >= 64 ? ~0ull : (nv <= 0 ? 0ull : (1ull << nv) - 1ull);
-}
 
 // first bit of the run of set bits of m that holds bit x (bit x is set)
 __device__ __forceinline__ int run_start(u64 m, int x) {
@@ -325,24 +314,6 @@ __global__ __launch_bounds__(WT) void cc_label_kernel(const CompP p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- select
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// Sums over the workgroup with a fixed tree; every thread gets the result.  `red` holds WW words; two barriers.
-__device__ __forceinline__ unsigned block_sum_u32(unsigned v, unsigned* red, int lane, int wave) {
-  v = wave_sum_u32(v);
-  __syncthreads();                 // the previous result has been read by every thread
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  unsigned s = 0u;
-#pragma unroll
-  for (int w = 0; w < WW; ++w) s += red[w];
-  return s;
-}
-
 __global__ __launch_bounds__(WT) void cc_choose_kernel(const CompP p) {
   __shared__ unsigned red[WW];
   const int pl = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -356,8 +327,7 @@ __global__ __launch_bounds__(WT) void cc_choose_kernel(const CompP p) {
     unsigned mx = 0u;
     for (unsigned i = tid; i < m; i += WT) mx = max(mx, list[i] & ~KEEP);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor(mx, o, 64));
-    __syncthreads();
+    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor(mx, o, 64));    __syncthreads();
     if (lane == 0) red[wave] = mx;
     __syncthreads();
     mx = max(max(red[0], red[1]), max(red[2], red[3]));
@@ -366,11 +336,11 @@ __global__ __launch_bounds__(WT) void cc_choose_kernel(const CompP p) {
       const unsigned t = T | (1u << b);
       unsigned c = 0u;
       for (unsigned i = tid; i < m; i += WT) c += (list[i] & ~KEEP) < t ? 1u : 0u;
-      if (block_sum_u32(c, red, lane, wave) <= m - k) T = t;
+      if (block_sum_u32<WW>(c, red, lane, wave) <= m - k) T = t;
     }
     unsigned above = 0u;
     for (unsigned i = tid; i < m; i += WT) above += (list[i] & ~KEEP) > T ? 1u : 0u;
-    allow = k - block_sum_u32(above, red, lane, wave);         // >= 1 components of area T are kept: those of the lowest ids
+    allow = k - block_sum_u32<WW>(above, red, lane, wave);         // >= 1 components of area T are kept: those of the lowest ids
   }
 
   unsigned kept = 0u, ties_before = 0u;
@@ -395,7 +365,7 @@ __global__ __launch_bounds__(WT) void cc_choose_kernel(const CompP p) {
       kept += keep ? 1u : 0u;
     }
   }
-  kept = block_sum_u32(kept, red, lane, wave);
+  kept = block_sum_u32<WW>(kept, red, lane, wave);
   if (tid == 0) p.n_kept[plane] = (int)kept;
 }
 
@@ -424,11 +394,7 @@ __global__ __launch_bounds__(WT) void cc_write_kernel(const CompP p) {
   }
 }
 
-bool aligned_n(const void* ptr, uintptr_t n) { return (reinterpret_cast<uintptr_t>(ptr) & (n - 1)) == 0; }
-
-bool shape_ok(int n, int H, int W) {
-  return n >= 0 && H >= 1 && H <= MAX_DIM && W >= 1 && W <= MAX_DIM && (int64_t)H * W < (1LL << 31);
-}
+bool shape_ok(int n, int H, int W) { return n >= 0 && plane_dims_ok(H, W) && plane_area_ok(H, W); }
 
 void set_workspace(CompP& p, void* workspace, int n, int H, int W) {
   const Layout l = layout_of(n, H, W);
@@ -439,7 +405,7 @@ void set_workspace(CompP& p, void* workspace, int n, int H, int W) {
   p.rowoff = reinterpret_cast<unsigned*>(ws + l.rowoff);
   p.tot = reinterpret_cast<unsigned*>(ws + l.tot);
   p.ids_per_plane = (unsigned)max_ids(H, W);
-  p.H = H; p.W = W; p.words_x = (W + 63) / 64;
+  p.H = H; p.W = W; p.words_x = (int)plane_words(W);
 }
 
 unsigned word_blocks(int H, int words_x) {
@@ -462,7 +428,7 @@ extern "C" int64_t mtbt_components_workspace_bytes(int n, int H, int W) {
 extern "C" int mtbt_label_components(const mtbt_components_args* args, void* stream) {
   if (!args) return MTBT_EINVAL;
   const mtbt_components_args& a = *args;
-  if (!shape_ok(a.n, a.H, a.W) || (int64_t)a.pitch != 8 * (((int64_t)a.W + 63) / 64)) return MTBT_EINVAL;
+  if (!shape_ok(a.n, a.H, a.W) || !plane_pitch_ok(a.W, a.pitch)) return MTBT_EINVAL;
   if ((a.connectivity != 4 && a.connectivity != 8) || a.max_components < 1 || a.max_components > MAX_COMPONENTS) return MTBT_EINVAL;
   if (!a.packed || !a.n_components || !a.area || !a.box || !a.first) return MTBT_EINVAL;
   if ((a.other != nullptr) != (a.inter != nullptr)) return MTBT_EINVAL;
@@ -503,7 +469,7 @@ extern "C" int mtbt_label_components(const mtbt_components_args* args, void* str
 extern "C" int mtbt_select_components(const mtbt_select_components_args* args, void* stream) {
   if (!args) return MTBT_EINVAL;
   const mtbt_select_components_args& a = *args;
-  if (!shape_ok(a.n, a.H, a.W) || (int64_t)a.pitch != 8 * (((int64_t)a.W + 63) / 64) || a.keep_largest < 0) return MTBT_EINVAL;
+  if (!shape_ok(a.n, a.H, a.W) || !plane_pitch_ok(a.W, a.pitch) || a.keep_largest < 0) return MTBT_EINVAL;
   if (!a.packed || !a.out || !a.n_kept) return MTBT_EINVAL;
   const int64_t need = mtbt_components_workspace_bytes(a.n, a.H, a.W);
   if (a.workspace_bytes < need || (need > 0 && !a.workspace)) return MTBT_EINVAL;

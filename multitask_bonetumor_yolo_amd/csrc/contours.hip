@@ -38,25 +38,19 @@
 // pixel of the column to the left; unset before pixel (0, 0)): 64 columns at a time, word[y] ^ word[y - 1].  One wave walks the rows of a
 // 128-row band of one word column, lane = column, and counts; a prefix over (column, band) in column-major order gives every band the
 // number of the run it opens and the position of the transition before it; the second walk stores position differences.
-#include "common.h"
+#include "bitplane.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int CHUNK = 64;                 // planes per launch group (grid z)
 constexpr int WT = 256;                   // threads of every workgroup here
 constexpr int WW = WT / 64;               // waves per workgroup
 constexpr int WORDS_PER_WAVE = 4;         // ct_link_kernel
 constexpr int ITEMS = 8;                  // passes per thread of the tile kernels
 constexpr int TILE = WT * ITEMS;
-constexpr int MAX_DIM = 16384;
 constexpr int MAX_CONTOURS = 65536;
 constexpr int BAND = 128;                 // rows of a run-length band
 constexpr unsigned NONE = 0xFFFFFFFFu;    // "no E pass seen yet" in the high half of a (start, distance) pair
 constexpr unsigned KEY_MASK = 0x3FFFFFFFu;   // a key is below (16385)^2 < 2^30; the two bits above hold the direction
-
-int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 int64_t pass_capacity(int64_t H, int64_t W, int64_t V) {   // more passes than 2 H W + 2 no plane has
   const int64_t most = 2 * H * W + 2;
@@ -97,11 +91,6 @@ struct CtP {
   int plane0, H, W, nw, nwv, conn8, C, V, Ve, ntiles;
 };
 
-__device__ __forceinline__ u64 valid_bits(int w, int W) {   // the bits X < W of row word w
-  const int nv = W - w * 64;
-  return nv >= 64 ? ~0ull : (nv <= 0 ? 0ull : (1ull << nv) - 1ull);
-}
-
 // pixel word w of row y; zero outside the plane
 __device__ __forceinline__ u64 row_word(const u64* plane, int y, int w, int H, int W, int nw) {
   if (y < 0 || y >= H || w < 0 || w >= nw) return 0ull;
@@ -132,12 +121,6 @@ __device__ __forceinline__ unsigned passes_of(const VMasks& m) {
 __device__ __forceinline__ unsigned passes_below(const VMasks& m, int bit) {   // passes at the vertices of the word before `bit`
   const u64 lo = (1ull << bit) - 1ull;
   return (unsigned)(__popcll(m.pE & lo) + __popcll(m.pS & lo) + __popcll(m.pW & lo) + __popcll(m.pN & lo));
-}
-
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- count
@@ -495,9 +478,7 @@ __global__ __launch_bounds__(WT) void rle_scan_kernel(const RleP p) {
   }
 }
 
-bool aligned_n(const void* ptr, uintptr_t n) { return (reinterpret_cast<uintptr_t>(ptr) & (n - 1)) == 0; }
-
-bool shape_ok(int n, int H, int W) { return n >= 0 && H >= 1 && H <= MAX_DIM && W >= 1 && W <= MAX_DIM; }
+bool shape_ok(int n, int H, int W) { return n >= 0 && plane_dims_ok(H, W); }
 
 int rounds_for(int64_t Ve) {                                   // the smallest K >= 1 with 2^K >= Ve: a window as long as the longest cycle
   int k = 1;
@@ -522,7 +503,7 @@ extern "C" int64_t mtbt_contours_workspace_bytes(int n, int H, int W, int max_ve
 extern "C" int mtbt_trace_contours(const mtbt_contours_args* args, void* stream) {
   if (!args) return MTBT_EINVAL;
   const mtbt_contours_args& a = *args;
-  if (!shape_ok(a.n, a.H, a.W) || (int64_t)a.pitch != 8 * (((int64_t)a.W + 63) / 64)) return MTBT_EINVAL;
+  if (!shape_ok(a.n, a.H, a.W) || !plane_pitch_ok(a.W, a.pitch)) return MTBT_EINVAL;
   if ((a.connectivity != 4 && a.connectivity != 8) || !a.packed || !a.n_vertices) return MTBT_EINVAL;
   const bool count_only = !a.vertices && !a.offset && !a.count && !a.area2 && !a.box && !a.start;
   if (!count_only) {
@@ -540,7 +521,7 @@ extern "C" int mtbt_trace_contours(const mtbt_contours_args* args, void* stream)
   CtP p = {};
   p.src = reinterpret_cast<const u64*>(a.packed);
   p.n_vertices = a.n_vertices;
-  p.H = a.H; p.W = a.W; p.nw = (a.W + 63) / 64; p.nwv = a.W / 64 + 1; p.conn8 = a.connectivity == 8;
+  p.H = a.H; p.W = a.W; p.nw = (int)plane_words(a.W); p.nwv = a.W / 64 + 1; p.conn8 = a.connectivity == 8;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int64_t words = (int64_t)(a.H + 1) * p.nwv;
   const unsigned gw = (unsigned)((words + WT - 1) / WT);
@@ -620,7 +601,7 @@ extern "C" int64_t mtbt_rle_workspace_bytes(int n, int H, int W) {
 extern "C" int mtbt_rle_encode(const mtbt_rle_args* args, void* stream) {
   if (!args) return MTBT_EINVAL;
   const mtbt_rle_args& a = *args;
-  if (!shape_ok(a.n, a.H, a.W) || (int64_t)a.pitch != 8 * (((int64_t)a.W + 63) / 64)) return MTBT_EINVAL;
+  if (!shape_ok(a.n, a.H, a.W) || !plane_pitch_ok(a.W, a.pitch)) return MTBT_EINVAL;
   if (!a.packed || !a.n_runs || (a.counts && a.max_runs < 0)) return MTBT_EINVAL;
   const int64_t need = mtbt_rle_workspace_bytes(a.n, a.H, a.W);
   if (a.workspace_bytes < need || (need > 0 && !a.workspace)) return MTBT_EINVAL;
@@ -632,7 +613,7 @@ extern "C" int mtbt_rle_encode(const mtbt_rle_args* args, void* stream) {
   p.cnt = reinterpret_cast<unsigned*>(a.workspace);
   p.last = reinterpret_cast<int*>(reinterpret_cast<unsigned char*>(a.workspace) + need / 2);
   p.counts = a.counts; p.n_runs = a.n_runs;
-  p.H = a.H; p.W = a.W; p.nw = (a.W + 63) / 64; p.nbands = (a.H + BAND - 1) / BAND; p.R = a.counts ? a.max_runs : 0;
+  p.H = a.H; p.W = a.W; p.nw = (int)plane_words(a.W); p.nbands = (a.H + BAND - 1) / BAND; p.R = a.counts ? a.max_runs : 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)p.nw, (unsigned)((p.nbands + WW - 1) / WW), 1);
   for (int p0 = 0; p0 < a.n; p0 += CHUNK) {

@@ -20,7 +20,7 @@
 //
 // Every output byte is written exactly once; the input is only read.  Roof: the bytes of the canvases and planes, once in and once out,
 // plus the donor pixels of the pasted area; the measured ratio to a plain copy of the same bytes is in DESIGN.md.
-#include "common.h"
+#include "bitplane.h"
 #include "copy_paste_check.h"
 
 namespace {
@@ -32,16 +32,12 @@ constexpr int MAXE = copy_paste::MAX_ENTRIES;
 constexpr int WORDS = 64;        // words of a block
 constexpr int PT = 256;          // threads of a block: 16 per word in the pixel phase, four passes
 
-typedef unsigned long long u64;
-
 struct Params {
   const float* images; const u64* planes; const float* rows_in;
   float* out_images; u64* out_planes; float* out_masks; float* rows_out;
   uint32_t* area_before; uint32_t* area; int32_t* box;
   int S, nw, M;
 };
-
-__device__ __forceinline__ u64 low_bits(int k) { return k <= 0 ? 0ull : (k >= 64 ? ~0ull : (1ull << k) - 1ull); }
 
 // word q of a donor row, zero outside the row, bits x >= S dropped
 __device__ __forceinline__ u64 donor_word(const u64* __restrict__ row, int q, int nw, int S) {
@@ -55,29 +51,18 @@ __device__ __forceinline__ u64 window(const u64* __restrict__ row, int p, int nw
   return (lo >> s) | (donor_word(row, q + 1, nw, S) << (64 - s));
 }
 
-__device__ __forceinline__ unsigned wave_max_u(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned wave_add_u(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-  return v;
-}
-
 // area_before / area / box of output row `pl` from this wave's words: `before` and `after` are the lane's word of the plane before and after
 // the layering.  Wave-uniform control flow: the whole of wave 0 calls it.
 __device__ __forceinline__ void record(const Params& p, long pl, u64 before, u64 after, int X0, int Y, int lane) {
   if (__ballot(before != 0ull) == 0ull) return;                        // after is a subset of before
-  const unsigned nb = wave_add_u((unsigned)__popcll(before));
+  const unsigned nb = wave_sum_u32((unsigned)__popcll(before));
   if (lane == 0) atomicAdd(p.area_before + pl, nb);
   if (__ballot(after != 0ull) == 0ull) return;
-  const unsigned na = wave_add_u((unsigned)__popcll(after));
-  const unsigned b0 = wave_max_u(after ? (unsigned)(p.S - (X0 + __ffsll((long long)after) - 1)) : 0u);
-  const unsigned b1 = wave_max_u(after ? (unsigned)(p.S - Y) : 0u);
-  const unsigned b2 = wave_max_u(after ? (unsigned)(X0 + 64 - __clzll((long long)after)) : 0u);
-  const unsigned b3 = wave_max_u(after ? (unsigned)(Y + 1) : 0u);
+  const unsigned na = wave_sum_u32((unsigned)__popcll(after));
+  const unsigned b0 = wave_max_u32(after ? (unsigned)(p.S - (X0 + __ffsll((long long)after) - 1)) : 0u);
+  const unsigned b1 = wave_max_u32(after ? (unsigned)(p.S - Y) : 0u);
+  const unsigned b2 = wave_max_u32(after ? (unsigned)(X0 + 64 - __clzll((long long)after)) : 0u);
+  const unsigned b3 = wave_max_u32(after ? (unsigned)(Y + 1) : 0u);
   if (lane == 0) {
     atomicAdd(p.area + pl, na);
     atomicMax(p.box + 4 * pl + 0, (int)b0);

@@ -4,6 +4,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "bitplane.h"
 #include "mtbt_hip.h"
 
 namespace copy_paste {
@@ -26,7 +27,7 @@ inline int check(const mtbt_copy_paste_args* a) {
   if (!a || !a->row_off || !a->paste_off) return MTBT_EINVAL;
   const mtbt_copy_paste_args& p = *a;
   if (p.B < 0 || p.M < 0 || p.P < 0 || p.B > (1 << 30) || p.S < 4 || p.S % 4 || p.S > 32768 || p.entry_stride != 8) return MTBT_EINVAL;
-  if ((int64_t)p.pitch != 8 * (((int64_t)p.S + 63) / 64) || (int64_t)p.M + p.P > 0x7fffffffLL) return MTBT_EINVAL;
+  if (!plane_pitch_ok(p.S, p.pitch) || (int64_t)p.M + p.P > 0x7fffffffLL) return MTBT_EINVAL;
   const int64_t N = (int64_t)p.M + p.P;
   if ((p.B > 0 && (!p.images || !p.out_images)) || (p.M > 0 && !p.planes) || (p.P > 0 && !p.entries)) return MTBT_EINVAL;
   if (N > 0 && (!p.out_planes || !p.area_before || !p.area || !p.box)) return MTBT_EINVAL;

@@ -33,31 +33,20 @@
 // region_grad_kernel   d_logits (+)= p (1 - p) (factor[t] + k_boundary phi).
 #include <cmath>
 
-#include "common.h"
+#include "bitplane.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int CHUNK = 64;                       // planes per launch group
-constexpr int64_t CHUNK_BYTES = 1LL << 30;      // ... and as many as fit this much workspace (at least one)
 constexpr unsigned NONE16 = 0xFFFFu;
 constexpr int INF_G = 1 << 15;                  // g of a row without a target, as the envelope takes it
 constexpr unsigned D2_NONE = 0xFFFFFFFFu;
 constexpr unsigned D2_LIMIT = 1u << 30;         // INF_G^2: no true d2 reaches it
-constexpr int MAX_DIM = 16384;
 constexpr int RT = 256;                         // threads of the loss workgroups
 constexpr int SLICE = RT * 64;                  // pixels per workgroup of the loss kernels
 
-int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+int64_t g_bytes(int64_t c, int64_t H, int64_t W) { return up16(c * 2 * H * (plane_words(W) * 64) * 2); }
 
-int64_t g_bytes(int64_t c, int64_t H, int64_t W) { return up16(c * 2 * H * (((W + 63) / 64) * 64) * 2); }
-
-int chunk_of(int n, int H, int W) {
-  int64_t c = CHUNK_BYTES / g_bytes(1, H, W);
-  c = c < 1 ? 1 : (c > CHUNK ? CHUNK : c);
-  return (int)(c < n ? c : n);
-}
+int chunk_of(int n, int H, int W) { return ::chunk_of(n, g_bytes(1, H, W)); }   // planes per launch group
 
 struct EdtP {
   const u64* packed;
@@ -65,11 +54,6 @@ struct EdtP {
   unsigned* out[2];       // d2_set, d2_unset: [n][H][W] or NULL
   int plane0, H, W, words_x;
 };
-
-__device__ __forceinline__ u64 valid_bits(int w, int W) {   // the bits X < W of row word w
-  const int nv = W - w * 64;
-  return nv >= 64 ? ~0ull : (nv <= 0 ? 0ull : (1ull << nv) - 1ull);
-}
 
 // ---------------------------------------------------------------------------------------------------------------- rows
 __global__ __launch_bounds__(256) void edt_rows_kernel(const EdtP p) {
@@ -260,10 +244,6 @@ __global__ __launch_bounds__(RT) void region_grad_kernel(const RegP r) {
   }
 }
 
-bool aligned_n(const void* ptr, uintptr_t n) { return (reinterpret_cast<uintptr_t>(ptr) & (n - 1)) == 0; }
-
-bool dims_ok(int H, int W) { return H >= 1 && H <= MAX_DIM && W >= 1 && W <= MAX_DIM; }
-
 int slices_of(int H, int W) { return (int)(((int64_t)H * W + SLICE - 1) / SLICE); }
 
 }  // namespace
@@ -273,7 +253,7 @@ extern "C" int mtbt_sizeof_distance_args(int which) {
 }
 
 extern "C" int64_t mtbt_distance_transform_workspace_bytes(int n, int H, int W) {
-  if (n < 0 || !dims_ok(H, W)) return MTBT_EINVAL;
+  if (n < 0 || !plane_dims_ok(H, W)) return MTBT_EINVAL;
   if (n == 0) return 0;
   return g_bytes(chunk_of(n, H, W), H, W);
 }
@@ -281,7 +261,7 @@ extern "C" int64_t mtbt_distance_transform_workspace_bytes(int n, int H, int W) 
 extern "C" int mtbt_distance_transform(const mtbt_distance_transform_args* args, void* stream) {
   if (!args) return MTBT_EINVAL;
   const mtbt_distance_transform_args& a = *args;
-  if (a.n < 0 || !dims_ok(a.H, a.W) || (int64_t)a.pitch != 8 * (((int64_t)a.W + 63) / 64)) return MTBT_EINVAL;
+  if (a.n < 0 || !plane_dims_ok(a.H, a.W) || !plane_pitch_ok(a.W, a.pitch)) return MTBT_EINVAL;
   if (!a.packed || (!a.d2_set && !a.d2_unset)) return MTBT_EINVAL;
   const int64_t need = mtbt_distance_transform_workspace_bytes(a.n, a.H, a.W);
   if (a.workspace_bytes < need || (need > 0 && !a.workspace)) return MTBT_EINVAL;
@@ -307,14 +287,14 @@ extern "C" int mtbt_distance_transform(const mtbt_distance_transform_args* args,
 }
 
 extern "C" int64_t mtbt_seg_region_loss_workspace_bytes(int B, int H, int W) {
-  if (B < 1 || B > 65535 || !dims_ok(H, W)) return MTBT_EINVAL;
+  if (B < 1 || B > 65535 || !plane_dims_ok(H, W)) return MTBT_EINVAL;
   return up16((int64_t)B * slices_of(H, W) * 4 * 8) + up16((int64_t)B * 2 * 4);
 }
 
 extern "C" int mtbt_seg_region_loss(const mtbt_seg_region_args* args, void* stream) {
   if (!args) return MTBT_EINVAL;
   const mtbt_seg_region_args& a = *args;
-  if (a.B < 1 || a.B > 65535 || !dims_ok(a.H, a.W) || (int64_t)a.pitch != 8 * (((int64_t)a.W + 63) / 64)) return MTBT_EINVAL;
+  if (a.B < 1 || a.B > 65535 || !plane_dims_ok(a.H, a.W) || !plane_pitch_ok(a.W, a.pitch)) return MTBT_EINVAL;
   if (!a.logits || !a.targets || !a.out || !a.workspace) return MTBT_EINVAL;
   if (!(a.smooth >= 0.f) || !(a.w_dice >= 0.f) || !(a.w_boundary >= 0.f) || std::isinf(a.smooth) || std::isinf(a.w_dice) || std::isinf(a.w_boundary))
     return MTBT_EINVAL;                                  // NaN fails the comparisons

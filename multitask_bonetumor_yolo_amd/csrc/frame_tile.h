@@ -26,7 +26,7 @@
 // With cropping a (unit, box) pair whose word lies wholly outside the box costs nothing but the zero it stores, and a
 // group of 16 boxes that all miss the tile skips the MFMA phase too.  Planes k >= counts[n] are zero-filled (zero_tail).
 #pragma once
-#include "common.h"
+#include "bitplane.h"
 
 namespace frame_tile {
 
@@ -122,7 +122,7 @@ inline int frame_layout(const mtbt_frame* frames, int n_frames, int K, int hp, i
     const mtbt_frame& fr = frames[i];
     if (fr.height < 1 || fr.width < 1 || (!tiles && !(fr.step > 0.f && fr.step <= 1.f))) return MTBT_EINVAL;
     if (with_boxes && !(fr.scale > 0.f)) return MTBT_EINVAL;
-    if ((int64_t)fr.pitch != 8 * (((int64_t)fr.width + 63) / 64)) return MTBT_EINVAL;
+    if (!plane_pitch_ok(fr.width, fr.pitch)) return MTBT_EINVAL;
     if (fr.offset < 0 || fr.offset % 16) return MTBT_EINVAL;
     const int64_t bytes = (int64_t)K * fr.height * fr.pitch;
     if (fr.offset > out_bytes || bytes > out_bytes - fr.offset) return MTBT_EINVAL;

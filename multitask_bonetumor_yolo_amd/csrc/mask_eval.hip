@@ -19,7 +19,7 @@
 // mask_eval_kernel    the walk of box_eval_kernel (semantics at the top of box_eval.hip), written out here with the IoU taken from the
 //                     pixel-count tables: inter / (det_area + gt_px - inter) in fp64 from exact integers, 0 for an empty union; areas
 //                     are pixel counts; GT membership, order and class from gt_image / gt_label.  Latency-bound like its model.
-#include "common.h"
+#include "bitplane.h"
 #include "coco_eval.h"
 
 namespace {
@@ -28,8 +28,6 @@ constexpr int MAX_IMAGES = 32;   // images per pair-count launch (descriptors tr
 constexpr int PT = 256;          // threads of the pack and pair-count workgroups
 constexpr int PW = PT / 64;
 constexpr int GG = 4;            // GT planes per register group
-
-typedef unsigned long long u64;
 
 // ---------------------------------------------------------------------------------------------------------------- pack
 template <typename T>
@@ -81,12 +79,6 @@ struct PairP {
   int B, K, M, pad_;
   PairImg im[MAX_IMAGES];
 };
-
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 __global__ __launch_bounds__(PT) void pair_counts_kernel(const PairP p) {
   __shared__ int gidx[PT];
@@ -323,12 +315,7 @@ __global__ __launch_bounds__(NT) void mask_eval_kernel(const mtbt_mask_eval_args
   }
 }
 
-template <typename T> bool aligned_to(const T* ptr) { return (reinterpret_cast<uintptr_t>(ptr) % sizeof(T)) == 0; }
-bool aligned8(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 7) == 0; }
-bool plane_shape_ok(int H, int W, int pitch) {
-  if (H < 1 || W < 1 || (int64_t)H * W >= (1LL << 31)) return false;
-  return (int64_t)pitch == 8 * (((int64_t)W + 63) / 64);
-}
+bool plane_shape_ok(int H, int W, int pitch) { return plane_area_ok(H, W) && plane_pitch_ok(W, pitch); }
 
 }  // namespace
 

@@ -20,16 +20,13 @@
 //                       of a polygon, not all of them.
 // finish_box_kernel     the box is gathered as maxima of (W - X, H - Y, X + 1, Y + 1) over zeroed memory (an empty plane stays
 //                       all zero); one thread per plane turns the first two back into minima.
-#include "common.h"
+#include "bitplane.h"
 
 namespace {
 
 constexpr int PT = 256;          // threads of a block = words of its band = edges of a chunk
 constexpr int LIM = 1 << 24;     // coordinates are clamped to [-LIM, LIM]: every product below stays under 2^52
 
-typedef unsigned long long u64;
-
-__device__ __forceinline__ u64 low_bits(long k) { return k <= 0 ? 0ull : (k >= 64 ? ~0ull : (1ull << k) - 1ull); }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 __global__ __launch_bounds__(PT) void fill_polygons_kernel(const mtbt_fill_polygons_args p, const int nw, const int plane0) {
@@ -127,8 +124,6 @@ __global__ __launch_bounds__(PT) void finish_box_kernel(int* box, const int n, c
   }
 }
 
-template <typename T> bool aligned_to(const T* ptr) { return (reinterpret_cast<uintptr_t>(ptr) % sizeof(T)) == 0; }
-
 }  // namespace
 
 extern "C" int mtbt_sizeof_fill_polygons_args(int which) { return which == 0 ? (int)sizeof(mtbt_fill_polygons_args) : -1; }
@@ -137,8 +132,8 @@ extern "C" int mtbt_fill_polygons(const mtbt_fill_polygons_args* a, void* stream
   if (!a || !a->out || !a->poly_offsets || !a->plane_offsets) return MTBT_EINVAL;
   const mtbt_fill_polygons_args& p = *a;
   if (p.n < 0 || p.n_polys < 0 || p.n_vertices < 0 || (p.n_vertices > 0 && !p.vertices)) return MTBT_EINVAL;
-  if (p.H < 1 || p.W < 1 || (int64_t)p.H * p.W >= (1LL << 31) || (int64_t)p.pitch != 8 * (((int64_t)p.W + 63) / 64)) return MTBT_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(p.out) & 7) != 0 || !aligned_to(p.vertices) || !aligned_to(p.poly_offsets) || !aligned_to(p.plane_offsets) ||
+  if (!plane_area_ok(p.H, p.W) || !plane_pitch_ok(p.W, p.pitch)) return MTBT_EINVAL;
+  if (!aligned8(p.out) || !aligned_to(p.vertices) || !aligned_to(p.poly_offsets) || !aligned_to(p.plane_offsets) ||
       !aligned_to(p.clip) || !aligned_to(p.area) || !aligned_to(p.box))
     return MTBT_EALIGN;
   if (p.n == 0) return MTBT_OK;

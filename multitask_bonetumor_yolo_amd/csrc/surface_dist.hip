@@ -25,27 +25,20 @@
 //                        adds items t, t + 256, ... in order, then a fixed tree: the same bits on every run) and the order
 //                        statistics by bitwise search from the top bit of the maximum down: v | 1 << b is kept when
 //                        count(list < v | 1 << b) <= k.  The statistic at k + 1 costs one more pass (count <= v, least item > v).
-#include "common.h"
+#include "bitplane.h"
 
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int CHUNK = 64;                       // pairs per launch group
-constexpr int64_t CHUNK_BYTES = 1LL << 30;      // ... and as many as fit this much workspace (at least one)
 constexpr int RT = 256;                         // threads of the scan, row and select workgroups
 constexpr int RW = RT / 64;
 constexpr unsigned NONE16 = 0xFFFFu;
-constexpr int MAX_DIM = 16384;
 
 struct Layout {   // byte offsets of one chunk's sections in the workspace, each 16-byte aligned
   int64_t edge, g, rowoff, tot, list, total;
 };
 
-int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
-
 Layout layout_of(int64_t c, int64_t H, int64_t W) {
-  const int64_t pitch = 8 * ((W + 63) / 64), Wp = pitch * 8;
+  const int64_t pitch = plane_pitch(W), Wp = pitch * 8;
   Layout l;
   int64_t off = 0;
   l.edge = off;   off = up16(off + c * 2 * H * pitch);
@@ -57,12 +50,7 @@ Layout layout_of(int64_t c, int64_t H, int64_t W) {
   return l;
 }
 
-int chunk_of(int n, int H, int W) {
-  const int64_t per_pair = layout_of(1, H, W).total;
-  int64_t c = CHUNK_BYTES / per_pair;
-  c = c < 1 ? 1 : (c > CHUNK ? CHUNK : c);
-  return (int)(c < n ? c : n);
-}
+int chunk_of(int n, int H, int W) { return ::chunk_of(n, layout_of(1, H, W).total); }   // pairs per launch group
 
 struct SurfP {
   const u64* a;
@@ -82,11 +70,6 @@ struct SurfP {
   unsigned tol2;
   int Q;
 };
-
-__device__ __forceinline__ u64 valid_bits(int w, int W) {   // the bits X < W of row word w
-  const int nv = W - w * 64;
-  return nv >= 64 ? ~0ull : (nv <= 0 ? 0ull : (1ull << nv) - 1ull);
-}
 
 // ---------------------------------------------------------------------------------------------------------------- edges + columns
 __global__ __launch_bounds__(64) void surface_edges_kernel(const SurfP p) {
@@ -121,12 +104,6 @@ __global__ __launch_bounds__(64) void surface_edges_kernel(const SurfP p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- row offsets
-__device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(RT) void surface_scan_kernel(const SurfP p) {
   __shared__ unsigned part[RT];
   const int side = blockIdx.x, pr = blockIdx.y, tid = threadIdx.x;
@@ -200,33 +177,6 @@ __global__ __launch_bounds__(RT) void surface_rows_kernel(const SurfP p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- select + reduce
-// Sums over the workgroup with a fixed tree; every thread gets the result.  `red` holds RW words; two barriers.
-__device__ __forceinline__ unsigned block_sum_u32(unsigned v, unsigned* red, int lane, int wave) {
-  v = wave_sum_u32(v);
-  __syncthreads();                 // the previous result has been read by every thread
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  unsigned s = 0u;
-#pragma unroll
-  for (int w = 0; w < RW; ++w) s += red[w];
-  return s;
-}
-
-__device__ __forceinline__ unsigned block_op_u32(unsigned v, unsigned* red, int lane, int wave, bool take_max) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned u = __shfl_xor(v, o, 64);
-    v = take_max ? max(v, u) : min(v, u);
-  }
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  unsigned s = red[0];
-#pragma unroll
-  for (int w = 1; w < RW; ++w) s = take_max ? max(s, red[w]) : min(s, red[w]);
-  return s;
-}
-
 __global__ __launch_bounds__(RT) void surface_select_kernel(const SurfP p) {
   __shared__ unsigned red[RW];
   __shared__ double dred[RT];
@@ -245,9 +195,9 @@ __global__ __launch_bounds__(RT) void surface_select_kernel(const SurfP p) {
     within += v <= p.tol2 ? 1u : 0u;
     if (seg < 2) sum += sqrt((double)v);
   }
-  mx = block_op_u32(mx, red, lane, wave, true);
+  mx = block_extreme_u32<RW, true>(mx, red, lane, wave);
   if (seg < 2) {
-    within = block_sum_u32(within, red, lane, wave);
+    within = block_sum_u32<RW>(within, red, lane, wave);
     dred[tid] = sum;
     __syncthreads();
     for (int s = RT / 2; s > 0; s >>= 1) {
@@ -271,7 +221,7 @@ __global__ __launch_bounds__(RT) void surface_select_kernel(const SurfP p) {
         const unsigned t = lo_v | (1u << b);
         unsigned c = 0u;
         for (unsigned i = tid; i < m; i += RT) c += list[i] < t ? 1u : 0u;
-        if (block_sum_u32(c, red, lane, wave) <= k) lo_v = t;
+        if (block_sum_u32<RW>(c, red, lane, wave) <= k) lo_v = t;
       }
       unsigned c = 0u, nxt = 0xFFFFFFFFu;
       for (unsigned i = tid; i < m; i += RT) {
@@ -279,8 +229,8 @@ __global__ __launch_bounds__(RT) void surface_select_kernel(const SurfP p) {
         c += v <= lo_v ? 1u : 0u;
         if (v > lo_v) nxt = min(nxt, v);
       }
-      c = block_sum_u32(c, red, lane, wave);
-      nxt = block_op_u32(nxt, red, lane, wave, false);
+      c = block_sum_u32<RW>(c, red, lane, wave);
+      nxt = block_extreme_u32<RW, false>(nxt, red, lane, wave);
       hi_v = c > k_hi ? lo_v : nxt;                      // c <= k_hi < m: an item above lo_v exists
     }
     if (tid == 0) {
@@ -291,9 +241,7 @@ __global__ __launch_bounds__(RT) void surface_select_kernel(const SurfP p) {
   }
 }
 
-bool aligned_n(const void* ptr, uintptr_t n) { return (reinterpret_cast<uintptr_t>(ptr) & (n - 1)) == 0; }
-
-bool shape_ok(int n, int H, int W) { return n >= 0 && H >= 1 && H <= MAX_DIM && W >= 1 && W <= MAX_DIM; }
+bool shape_ok(int n, int H, int W) { return n >= 0 && plane_dims_ok(H, W); }
 
 }  // namespace
 
@@ -308,7 +256,7 @@ extern "C" int64_t mtbt_surface_distances_workspace_bytes(int n, int H, int W) {
 extern "C" int mtbt_surface_distances(const mtbt_surface_args* args, void* stream) {
   if (!args) return MTBT_EINVAL;
   const mtbt_surface_args& a = *args;
-  if (!shape_ok(a.n, a.H, a.W) || (int64_t)a.pitch != 8 * (((int64_t)a.W + 63) / 64)) return MTBT_EINVAL;
+  if (!shape_ok(a.n, a.H, a.W) || !plane_pitch_ok(a.W, a.pitch)) return MTBT_EINVAL;
   if (a.Q < 0 || a.Q > 4) return MTBT_EINVAL;
   for (int i = 0; i < a.Q; ++i)
     if (!(a.q[i] >= 0.0 && a.q[i] <= 1.0)) return MTBT_EINVAL;   // NaN fails both comparisons

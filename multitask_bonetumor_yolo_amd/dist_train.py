@@ -10,7 +10,6 @@ backward pass produces gradients, so bucket 0 can be reduced while earlier layer
 `FlatBuckets` is also the storage of the training step's parameter / gradient arenas (`train.make_arena`, kernel layouts, a leading
 bucket for parameters the loss never reaches); the step that fills the gradient buckets, all-reduces each one under the rest of the
 backward pass and applies the fused optimiser is `trainstep.TrainStep` (DESIGN.md sections 6-7)."""
-import ctypes as C
 from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import torch
@@ -126,7 +125,7 @@ class FlatAdamW:
             if not p.is_cuda:
                 raise RuntimeError("FlatAdamW.step: expected CUDA/HIP buckets on an MI355X (no CPU path)")
             L.check(lib.mtbt_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), self.lr, self.betas[0], self.betas[1],
-                                        self.eps, self.weight_decay, self.steps, None, C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)),
+                                        self.eps, self.weight_decay, self.steps, None, L.stream(p.device)),
                     "mtbt_adamw_step")
 
     def cosine_lr(self, base_lr: float, epoch: int, t_max: int, eta_min_ratio: float = 0.01):

@@ -204,7 +204,7 @@ class Plan:
         unwrap = (lambda r: r) if isinstance(marks, dict) else (lambda r: r.get("_", []))
         sequential = stream is not None or start != 0 or (end is not None and end != len(self.launches)) or self.lanes() <= 1
         if sequential:
-            s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream if stream is None else stream)
+            s = L.stream(self.device) if stream is None else C.c_void_p(stream)
             at = {}
             for name, idx in groups.items():
                 if idx:
@@ -378,7 +378,7 @@ class Plan:
         (calibrated in the same pass, ~2.5 us): uncorrected the figures sit ~5 % above rocprofv3's kernel durations of the same
         launches, with the full pair subtracted ~7 % below; half the pair lands within ~1 %.  Slower than run(); for roofline
         accounting."""
-        s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        s = L.stream(self.device)
         evs, empty = [], []
         for i, l in enumerate(self.launches):
             if i % 8 == 0:  # calibration pairs, interleaved with the real ones

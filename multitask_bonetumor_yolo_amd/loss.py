@@ -13,7 +13,8 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib as L
-from .postprocess import _mask_call, _need_cuda, _nhwc_rows, _stream, distance_transform, pack_masks
+from .planes import _need_cuda, distance_transform, pack_masks, plane_pitch
+from .postprocess import _mask_call, _nhwc_rows
 
 
 def group_gt_boxes(gt_boxes: torch.Tensor, n_images: int, img_size: float):
@@ -96,7 +97,7 @@ def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_l
     ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
     out = torch.empty(8, dtype=torch.float32, device=dev)
     a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
-    L.check(lib.mtbt_multitask_loss(C.byref(a), _stream(dev)), "mtbt_multitask_loss")
+    L.check(lib.mtbt_multitask_loss(C.byref(a), L.stream(dev)), "mtbt_multitask_loss")
     res = tuple(out[i] for i in range(8 if training else 6))
     if not with_grads:
         del keep
@@ -110,7 +111,7 @@ def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_l
     lds = (C.c_int32 * 3)(*([no] * len(d_maps)), *([0] * (3 - len(d_maps))))
     d_seg = torch.empty_like(seg_logits)
     d_img = grad_out["img_logits"] if grad_out is not None else torch.empty_like(il)
-    L.check(lib.mtbt_multitask_loss_grad(C.byref(a), ptrs, lds, d_seg.data_ptr(), d_img.data_ptr(), _stream(dev)), "mtbt_multitask_loss_grad")
+    L.check(lib.mtbt_multitask_loss_grad(C.byref(a), ptrs, lds, d_seg.data_ptr(), d_img.data_ptr(), L.stream(dev)), "mtbt_multitask_loss_grad")
     del keep
     grads = {"det_maps": [t.permute(0, 3, 1, 2) for t in d_maps],      # [B, no, h, w] views of channels-last memory
              "seg_logits": d_seg.view(B, 1, img_size, img_size), "img_logits": d_img}
@@ -215,9 +216,9 @@ def instance_mask_loss(box_maps: Sequence[torch.Tensor], mc: torch.Tensor, proto
     out = torch.empty(2, dtype=torch.float32, device=dev)
     a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
     if assigned is None:
-        L.check(lib.mtbt_instance_mask_loss(C.byref(a), _stream(dev)), "mtbt_instance_mask_loss")
+        L.check(lib.mtbt_instance_mask_loss(C.byref(a), L.stream(dev)), "mtbt_instance_mask_loss")
     else:
-        L.check(lib.mtbt_instance_mask_loss_assigned(C.byref(a), assigned.data_ptr(), _stream(dev)), "mtbt_instance_mask_loss_assigned")
+        L.check(lib.mtbt_instance_mask_loss_assigned(C.byref(a), assigned.data_ptr(), L.stream(dev)), "mtbt_instance_mask_loss_assigned")
     del keep
     res = (out[0], out[1])
     return (res, grads) if grads is not None else res
@@ -267,7 +268,7 @@ def seg_region_loss(seg_logits: torch.Tensor, gt_masks: torch.Tensor, *, bias: O
     if seg_logits.dim() != 3 or seg_logits.dtype != torch.float32:
         raise ValueError(f"seg_region_loss: seg_logits must be fp32 [B, 1, H, W] or [B, H, W], not {seg_logits.dtype} {tuple(seg_logits.shape)}")
     B, H, Wd = (int(v) for v in seg_logits.shape)
-    pitch = 8 * ((Wd + 63) // 64)
+    pitch = plane_pitch(Wd)
     dev = seg_logits.device
     if not float(dice_weight) >= 0 or not float(boundary_weight) >= 0 or not float(smooth) >= 0:
         raise ValueError("seg_region_loss: dice_weight, boundary_weight and smooth must be >= 0")
@@ -312,16 +313,13 @@ def seg_region_loss(seg_logits: torch.Tensor, gt_masks: torch.Tensor, *, bias: O
             d = (torch.zeros if accumulate else torch.empty)((B, H, Wd), dtype=torch.float32, device=dev)
         a.d_logits, a.accumulate = d.data_ptr(), int(bool(accumulate))
         grads = {"seg_logits": d.view(B, 1, H, Wd)}
-    nbytes = int(lib.mtbt_seg_region_loss_workspace_bytes(B, H, Wd))
-    if nbytes < 0:
-        L.check(nbytes, "mtbt_seg_region_loss_workspace_bytes")
-    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    ws, nbytes = L.workspace(lib.mtbt_seg_region_loss_workspace_bytes, B, H, Wd, device=dev, what="mtbt_seg_region_loss_workspace_bytes")
     out = torch.empty(3, dtype=torch.float32, device=dev)
     a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
     a.B, a.H, a.W, a.pitch = B, H, Wd, pitch
     a.smooth, a.w_dice, a.w_boundary = float(smooth), float(dice_weight), float(boundary_weight)
     with torch.cuda.device(dev):
-        L.check(lib.mtbt_seg_region_loss(C.byref(a), _stream(dev)), "mtbt_seg_region_loss")
+        L.check(lib.mtbt_seg_region_loss(C.byref(a), L.stream(dev)), "mtbt_seg_region_loss")
     del keep
     res = (out[0], out[1], out[2])
     return (res, grads) if grads is not None else res
@@ -429,7 +427,7 @@ def task_aligned_det_loss(det_maps: Sequence[torch.Tensor], gt_boxes: torch.Tens
     ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
     out = torch.empty(8, dtype=torch.float32, device=dev)
     a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
-    L.check(lib.mtbt_tal_det_loss(C.byref(a), _stream(dev)), "mtbt_tal_det_loss")
+    L.check(lib.mtbt_tal_det_loss(C.byref(a), L.stream(dev)), "mtbt_tal_det_loss")
     del keep
     res = [tuple(out[i] for i in range(5))]
     if d_maps is not None:

@@ -48,6 +48,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .planes import filter_components, label_components, pack_masks, packed_planes, plane_pitch
 
 
 def _world(group=None) -> int:
@@ -389,7 +390,7 @@ class DeviceMeanAveragePrecision(_DeviceCocoRecords):
             a.iou_thresholds[t] = float(v)
         a.B, a.K, a.M, a.T, a.max_det, a.gt_format, a.img_size = B, K, M, len(self.iou_thresholds), self.max_dets[-1], gt_format, float(img_size)
         with torch.cuda.device(dev):                                            # launch on the tensors' device, whatever is current
-            L.check(lib.mtbt_box_eval(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_box_eval")
+            L.check(lib.mtbt_box_eval(C.byref(a), L.stream(dev)), "mtbt_box_eval")
         self._keep(scores, labels, rank, mi, gt[:, :2].view(torch.int32), gt_area)
 
     def update_batched(self, det: Dict[str, torch.Tensor], gt_rows: torch.Tensor, img_size: float):
@@ -443,10 +444,6 @@ class DeviceMeanAveragePrecision(_DeviceCocoRecords):
 MASK_EVAL_MAX_IMAGES = 32    # images per mtbt_mask_pair_counts launch (the image descriptors travel as kernel arguments)
 
 
-def _mask_pitch(W: int) -> int:
-    return 8 * ((int(W) + 63) // 64)
-
-
 def _mask_launch_layout(n_gt: Sequence[int], chunk: int = MASK_EVAL_MAX_IMAGES):
     """A list of images with n_gt[b] ground-truth planes each -> the launches of `mtbt_mask_pair_counts`, `chunk` images at a time:
     [(first image, one past the last image, g0 per image, gt_image int32 [M])].  The GT planes of a launch form one flat row list in
@@ -483,9 +480,9 @@ def _pair_counts(images, K: int, counts, gt_image, M: int, dev, out=None):
     im = (L.MaskImage * B)()
     for i, (H, W, det, gt, g0, planes) in enumerate(images):
         im[i].det, im[i].gt_base = det.data_ptr(), gt.data_ptr()
-        im[i].H, im[i].W, im[i].pitch, im[i].g0, im[i].gt_planes = H, W, _mask_pitch(W), g0, planes
+        im[i].H, im[i].W, im[i].pitch, im[i].g0, im[i].gt_planes = H, W, plane_pitch(W), g0, planes
     with torch.cuda.device(dev):
-        L.check(lib.mtbt_mask_pair_counts(C.byref(a), im, B, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_mask_pair_counts")
+        L.check(lib.mtbt_mask_pair_counts(C.byref(a), im, B, L.stream(dev)), "mtbt_mask_pair_counts")
     return inter, det_area, gt_px
 
 
@@ -535,21 +532,20 @@ class DeviceMaskMeanAveragePrecision(_DeviceCocoRecords):
             a.iou_thresholds[t] = float(v)
         a.B, a.K, a.M, a.T, a.max_det = B, K, M, len(self.iou_thresholds), self.max_dets[-1]
         with torch.cuda.device(dev):
-            L.check(lib.mtbt_mask_eval(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_mask_eval")
+            L.check(lib.mtbt_mask_eval(C.byref(a), L.stream(dev)), "mtbt_mask_eval")
         self._keep(scores, labels, rank, mi, torch.stack([gt_image, gt_label], 1), gt_area)
 
     # ---- images with their own sizes -------------------------------------------------------------------------------------------
     @staticmethod
     def _packed_of(d: Dict, who: str):
         """-> (packed uint8 [n, H, pitch] on the device, H, W) of one image's dict."""
-        from .postprocess import pack_masks
         m = d["masks"]
         if not isinstance(m, torch.Tensor) or not m.is_cuda or m.dim() != 3:
             raise RuntimeError(f"DeviceMaskMeanAveragePrecision.{who}: masks must be [n, H, W] CUDA/HIP tensors on an MI355X (no CPU path)")
         if "width" in d:
             W = int(d["width"])
-            if m.dtype != torch.uint8 or m.shape[2] != _mask_pitch(W):
-                raise ValueError(f"DeviceMaskMeanAveragePrecision.{who}: packed masks of width {W} are uint8 [n, H, {_mask_pitch(W)}]")
+            if m.dtype != torch.uint8 or m.shape[2] != plane_pitch(W):
+                raise ValueError(f"DeviceMaskMeanAveragePrecision.{who}: packed masks of width {W} are uint8 [n, H, {plane_pitch(W)}]")
             m = m.contiguous()
             return (m if m.data_ptr() % 8 == 0 else m.clone()), int(m.shape[1]), W
         return pack_masks(m), int(m.shape[1]), int(m.shape[2])
@@ -716,10 +712,9 @@ class SegmentationMetrics:
         dev = x.device
         counts = torch.empty(B, 4, dtype=torch.int64, device=dev)
         psum = torch.empty(B, dtype=torch.float32, device=dev)
-        ws_bytes = lib.mtbt_seg_confusion_workspace_bytes(B)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        ws, ws_bytes = L.workspace(lib.mtbt_seg_confusion_workspace_bytes, B, device=dev, what="mtbt_seg_confusion_workspace_bytes")
         L.check(lib.mtbt_seg_confusion(x.data_ptr(), t.data_ptr(), B, n, counts.data_ptr(), psum.data_ptr(), ws.data_ptr(), ws_bytes,
-                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_seg_confusion")
+                                       L.stream(dev)), "mtbt_seg_confusion")
         self._counts.append(counts)
         self._psum.append(psum)
 
@@ -741,9 +736,9 @@ class SegmentationMetrics:
         for a, b, w in zip(pred, gt, widths):
             if not (a.is_cuda and b.is_cuda):
                 raise RuntimeError("SegmentationMetrics.update_packed: expected CUDA/HIP tensors on an MI355X (no CPU path)")
-            if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.shape != b.shape or a.shape[1] != _mask_pitch(w):
+            if a.dtype != torch.uint8 or b.dtype != torch.uint8 or a.shape != b.shape or a.shape[1] != plane_pitch(w):
                 raise ValueError(f"SegmentationMetrics.update_packed: planes {tuple(a.shape)} / {tuple(b.shape)} for width {w}; expected uint8 "
-                                 f"[H, {_mask_pitch(w)}] both")
+                                 f"[H, {plane_pitch(w)}] both")
         if not pred:
             return
         dev = pred[0].device
@@ -895,7 +890,7 @@ class ImageClassificationMetrics(_ConfusionCounts):
         x, t = logits.float().contiguous(), target.long().contiguous()
         counts, status = self._buffers(dev)
         L.check(lib.mtbt_cls_confusion(x.data_ptr(), t.data_ptr(), x.shape[0], self.num_classes, counts, status,
-                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_cls_confusion")
+                                       L.stream(dev)), "mtbt_cls_confusion")
 
     def compute(self) -> Dict[str, object]:
         cm = self.counts()
@@ -939,7 +934,7 @@ class DetectionConfusionMatrix(_ConfusionCounts):
         a, keep = det_loss_args(det_maps, gt_rows, img_size=self.img_size, nc_det=self.num_classes, reg_max=self.reg_max,
                                 iou_match_thresh=self.iou_match_thresh)
         counts, status = self._buffers(dev)
-        L.check(lib.mtbt_det_confusion(C.byref(a), counts, status, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_det_confusion")
+        L.check(lib.mtbt_det_confusion(C.byref(a), counts, status, L.stream(dev)), "mtbt_det_confusion")
         del keep
 
     def compute(self) -> Dict[str, object]:
@@ -967,19 +962,10 @@ def surface_distances(a_packed: torch.Tensor, b_packed: torch.Tensor, W: int, *,
     Returns a dict of device tensors -- n_edge, max_d2, n_within int32 [n, 2] (A->B, B->A; the values are below 2^31), sum_d float64
     [n, 2], rank_d2 int32 [n, Q, 3, 2] (A->B, B->A, pooled; the order statistics at floor(q (m - 1)) and the next) -- plus the host
     values `quantiles`, `tol2` and `shape` = (H, W) that `surface_metrics` needs.  Asynchronous: no host synchronisation."""
-    for t in (a_packed, b_packed):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise RuntimeError("surface_distances: expected CUDA/HIP tensors on an MI355X (no CPU path)")
     W = int(W)
-    if a_packed.dim() != 3 or a_packed.dtype != torch.uint8 or b_packed.dtype != torch.uint8 or a_packed.shape != b_packed.shape:
-        raise ValueError("surface_distances: a_packed and b_packed must be uint8 [n, H, pitch] of the same shape")
-    if a_packed.device != b_packed.device:
-        raise ValueError("surface_distances: the two sides are on different devices")
-    n, H, pitch = (int(v) for v in a_packed.shape)
-    if not (1 <= H <= SURFACE_MAX_DIM and 1 <= W <= SURFACE_MAX_DIM):
-        raise ValueError(f"surface_distances: planes of {H} x {W} pixels (1 <= H, W <= {SURFACE_MAX_DIM})")
-    if pitch != _mask_pitch(W):
-        raise ValueError(f"surface_distances: packed planes of width {W} are uint8 [n, H, {_mask_pitch(W)}]")
+    same = "a_packed and b_packed must be uint8 [n, H, pitch] of the same shape"
+    n, H, pitch, a_planes, b_planes = packed_planes("surface_distances", a_packed, W, b_packed, max_dim=SURFACE_MAX_DIM,
+                                                    words=(same, same, "the two sides are on different devices"))
     q = tuple(float(v) for v in quantiles)
     if len(q) > SURFACE_MAX_QUANTILES or any(not 0.0 <= v <= 1.0 for v in q):
         raise ValueError(f"surface_distances: at most {SURFACE_MAX_QUANTILES} quantiles, each in [0, 1]")
@@ -994,23 +980,16 @@ def surface_distances(a_packed: torch.Tensor, b_packed: torch.Tensor, W: int, *,
     if n == 0:
         return out
     lib = L.load()
-    planes = []
-    for t in (a_packed, b_packed):
-        t = t.contiguous()
-        planes.append(t if t.data_ptr() % 8 == 0 else t.clone())
-    ws_bytes = int(lib.mtbt_surface_distances_workspace_bytes(n, H, W))
-    if ws_bytes < 0:
-        L.check(ws_bytes, "mtbt_surface_distances_workspace_bytes")
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    ws, ws_bytes = L.workspace(lib.mtbt_surface_distances_workspace_bytes, n, H, W, device=dev, what="mtbt_surface_distances_workspace_bytes")
     a = L.SurfaceArgs()
-    a.a, a.b, a.workspace, a.workspace_bytes = planes[0].data_ptr(), planes[1].data_ptr(), ws.data_ptr(), ws_bytes
+    a.a, a.b, a.workspace, a.workspace_bytes = a_planes.data_ptr(), b_planes.data_ptr(), ws.data_ptr(), ws_bytes
     a.n_edge, a.max_d2, a.n_within, a.sum_d = (out[k].data_ptr() for k in ("n_edge", "max_d2", "n_within", "sum_d"))
     a.rank_d2 = out["rank_d2"].data_ptr() if Q else None
     for i, v in enumerate(q):
         a.q[i] = v
     a.n, a.H, a.W, a.pitch, a.tol2, a.Q = n, H, W, pitch, tol2, Q
     with torch.cuda.device(dev):
-        L.check(lib.mtbt_surface_distances(C.byref(a), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "mtbt_surface_distances")
+        L.check(lib.mtbt_surface_distances(C.byref(a), L.stream(dev)), "mtbt_surface_distances")
     return out
 
 
@@ -1108,7 +1087,6 @@ class SurfaceDistanceMetrics:
             self._records.append(rec)
 
     def update(self, seg_logits: torch.Tensor, masks_gt: torch.Tensor):
-        from .postprocess import pack_masks
         if not (isinstance(seg_logits, torch.Tensor) and isinstance(masks_gt, torch.Tensor) and seg_logits.is_cuda and masks_gt.is_cuda):
             raise RuntimeError("SurfaceDistanceMetrics.update: expected CUDA/HIP tensors on an MI355X (no CPU path)")
         if seg_logits.shape != masks_gt.shape:
@@ -1194,7 +1172,6 @@ class LesionMetrics:
 
     def update_packed(self, pred: torch.Tensor, gt: torch.Tensor, W: int):
         """Asynchronous: launches on the current stream and keeps its records on the device."""
-        from .postprocess import filter_components, label_components
         kw = dict(connectivity=self.connectivity, max_components=self.max_components, want_labels=False)
         if self.min_area > 0:
             pred =filter_components(pred, W, min_area=self.min_area, connectivity=self.connectivity)[0]
@@ -1203,7 +1180,6 @@ class LesionMetrics:
             self._records.append({f"{s}_{k}": r[k] for s, r in (("pred", p), ("gt", g)) for k in ("n_components", "area", "inter")})
 
     def update(self, seg_logits: torch.Tensor, masks_gt: torch.Tensor):
-        from .postprocess import pack_masks
         if not (isinstance(seg_logits, torch.Tensor) and isinstance(masks_gt, torch.Tensor) and seg_logits.is_cuda and masks_gt.is_cuda):
             raise RuntimeError("LesionMetrics.update: expected CUDA/HIP tensors on an MI355X (no CPU path)")
         if seg_logits.shape != masks_gt.shape:

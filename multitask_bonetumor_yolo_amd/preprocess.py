@@ -33,6 +33,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .planes import fill_polygons, plane_pitch, unpack_masks
 
 
 def _descriptors(images, masks, who: str):
@@ -225,10 +226,7 @@ def clahe_batch(images: Sequence[torch.Tensor], clip_limit=2.0, grid=(8, 8), out
         d.src, d.dst, d.height, d.width, d.channels, d.clip = src.data_ptr(), dst.data_ptr(), src.shape[0], src.shape[1], 1 if src.dim() == 2 else 3, clip
         d.src_row_stride = src.stride(0) if src.shape[0] > 1 else src.shape[1] * d.channels
         d.dst_row_stride = dst.stride(0) if dst.shape[0] > 1 else dst.shape[1] * d.channels
-    nbytes = int(lib.mtbt_clahe_workspace_bytes(descs, n, gx, gy))
-    if nbytes < 0:
-        L.check(nbytes, "mtbt_clahe_workspace_bytes")
-    workspace = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    workspace, nbytes = L.workspace(lib.mtbt_clahe_workspace_bytes, descs, n, gx, gy, device=dev, what="mtbt_clahe_workspace_bytes")
     stream = torch.cuda.current_stream(dev)
     L.check(lib.mtbt_clahe_batch(descs, n, gx, gy, workspace.data_ptr(), nbytes, C.c_void_p(stream.cuda_stream)), "mtbt_clahe_batch")
     for t in keep:   # the launches are asynchronous: keep the buffers alive until the stream has consumed them
@@ -600,7 +598,6 @@ def _seg_outputs(per_canvas, canvas_rects, img_size: int, dev):
     """per_canvas: for every canvas its list of (row6, vertices, rect); canvas_rects: for every canvas the G rectangles its polygons are
     clipped to (one for a plain canvas, the four tiles of a mosaic) -> (masks [B,1,S,S], gt_rows [M,6], inst) of the `*_samples_seg`
     functions: one fill for the M instance planes, one for the B x G unions of the polygons that share a rectangle."""
-    from .postprocess import fill_polygons, unpack_masks
     S, B, G = int(img_size), len(per_canvas), len(canvas_rects[0])
     items = [(i, it) for i, canvas in enumerate(per_canvas) for it in canvas]
     gt_rows = _upload(collate_boxes([[it[0] for it in canvas] for canvas in per_canvas]), dev)
@@ -868,7 +865,7 @@ def copy_paste_batch(imgs: torch.Tensor, planes: torch.Tensor, row_off, gt_rows:
     if imgs.dtype != torch.float32 or imgs.dim() != 4 or imgs.shape[1] != 3 or imgs.shape[2] != imgs.shape[3]:
         raise ValueError("copy_paste_batch: imgs must be float32 [B, 3, S, S]")
     B, S = int(imgs.shape[0]), int(imgs.shape[3])
-    pitch = 8 * ((S + 63) // 64)
+    pitch = plane_pitch(S)
     if planes.dtype != torch.uint8 or planes.dim() != 3 or tuple(planes.shape[1:]) != (S, pitch):
         raise ValueError(f"copy_paste_batch: planes must be uint8 [M, {S}, {pitch}]")
     M = int(planes.shape[0])

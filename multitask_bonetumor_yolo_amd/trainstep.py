@@ -20,7 +20,6 @@ has none) in a second set of buckets of the same layout, updated by the optimise
 it as `ema_model` / `ema_projector`.  `state_dict()` / `load_state_dict()` carry everything a step needs to continue where it stopped.
 """
 import copy
-import ctypes as C
 import math
 from typing import Optional, Sequence
 
@@ -70,10 +69,6 @@ def _ema_config(ema):
 
 def _cpu(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to("cpu", copy=True).contiguous()
-
-
-def _s(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def bucket_writers(launches, buckets):
@@ -315,7 +310,7 @@ class TrainStep:
                                       mc_layout="bAn", grad_out={"mc": tp.d_in["mc"], "protos": tp.d_in["protos"]}, assigned=assigned)[0]
         L.check(lib.mtbt_projector_backward(dseg.data_ptr(), tp.protos.ptr, self.pj.data_ptr(), tp.d_in["protos"].data_ptr(), tp.code, int(mask is not None),
                                             self.pj_grad.data_ptr(), self.pj_grad.data_ptr() + 4 * nm, 0, self.B, self.S // 4, self.S // 4, nm, self.S, self.S,
-                                            self.pj_ws.data_ptr(), self.pj_ws.numel() * 4, _s(dev)), "mtbt_projector_backward")
+                                            self.pj_ws.data_ptr(), self.pj_ws.numel() * 4, L.stream(dev)), "mtbt_projector_backward")
         self._backward_and_exchange()
         if mask is not None:
             res = (res[0] + self.mask_w * mask[0],) + tuple(res[1:]) + mask
@@ -405,7 +400,7 @@ class TrainStep:
         t.copy_(h)
 
     def _clip_and_update(self):
-        lib, s = self.lib, _s(self.dev)
+        lib, s = self.lib, L.stream(self.dev)
         self.steps += 1
         live = list(range(self.n_skip, len(self.grads.buckets)))
         scale = None

@@ -307,3 +307,18 @@ def test_validation_step_with_lesion_metrics():
     assert want["n_images"] == Bn and want["n_gt"] == 3 and want["n_pred"] > 0
     on.reset()
     assert on.compute()["val_epoch/seg_lesion_recall"] == 0.0
+
+
+@pytest.mark.parametrize("shape", [(7, 63), (9, 127)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_one_padding_bit_in_the_last_word(shape):
+    """W % 64 == 63, below and above 64: one padding bit in the last word, where a wrong valid_bits shows: a full plane, noise, and a plane whose last column and middle row are set, padding bits set on the way in."""
+    H, W = shape
+    rng = np.random.default_rng(W)
+    planes = [np.ones((H, W), bool), rng.uniform(size=(H, W)) < 0.5, np.zeros((H, W), bool)]
+    planes[2][:, W - 1] = planes[2][H // 2, :] = True
+    others = [rng.uniform(size=(H, W)) < 0.3 for _ in planes]
+    for conn in CONNS:
+        want = _reference(planes, others, conn)
+        got = label_components(_pack(planes, True), W, connectivity=conn, max_components=CAP, other=_pack(others, True))
+        _assert_records(got, want, f"{shape} {conn}")
+        _assert_filter(_pack(planes, True), W, conn, want, planes, 2, 3, f"{shape} {conn}")

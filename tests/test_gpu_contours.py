@@ -344,3 +344,17 @@ def test_coco_results_decode_back_to_the_frame_masks():
             assert r["bbox"] == [x1, y1, x2 - x1, y2 - y1]
             runs = rle_from_string(r["segmentation"]["counts"])
             assert sum(runs) == H0 * W0 and np.array_equal(R.rle_decode(runs, H0, W0), dense[j]), (b, j)
+
+
+@pytest.mark.parametrize("shape", [(7, 63), (9, 127)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_one_padding_bit_in_the_last_word(shape):
+    """W % 64 == 63, below and above 64: one padding bit in the last word, where a wrong valid_bits shows: contours and run lengths of a full plane, noise, and a last column with a middle row, padding bits set."""
+    H, W = shape
+    rng = np.random.default_rng(W)
+    planes = [np.ones((H, W), bool), rng.uniform(size=(H, W)) < 0.5, np.zeros((H, W), bool)]
+    planes[2][:, W - 1] = planes[2][H // 2, :] = True
+    for conn in CONNS:
+        got = trace_contours(_pack(planes, True), W, connectivity=conn, max_contours=CAP)
+        _assert_result(got, R.stack_records(planes, conn, CAP), f"{shape} {conn}")
+    want = _assert_runs(planes, W, True)
+    assert want[0] == [0, H * W]

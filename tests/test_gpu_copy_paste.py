@@ -183,3 +183,15 @@ def test_augment_samples_seg_with_the_option_equals_the_steps():
     assert clean and torch.equal(got[0].cpu(), torch.from_numpy(ref["images"])) and torch.equal(got[1].cpu(), torch.from_numpy(ref["masks"]))
     assert np.array_equal(got[2].cpu().numpy().view(np.int32), ref["rows"].view(np.int32))
     assert np.array_equal(got[3]["planes"].cpu().numpy(), R.pack(ref["planes"]))
+
+
+@pytest.mark.parametrize("S", [60, 124])
+def test_last_word_four_bits_short(S):
+    """A canvas side is a multiple of 4, so S % 64 == 60 is as close under a word boundary as it gets (S = 60: a single, partial word):
+    shifts by one pixel either way and by a whole row but one, both flips, donors on the other canvas."""
+    rng = np.random.default_rng(S)
+    images = rng.random((2, 3, S, S), dtype=np.float32)
+    planes = noise_planes(rng, 2, S)
+    entries = [[[1, 1, 0, 0], [1, -1, 2, 1]], [[0, S - 1, -3, 1], [0, 1 - S, 0, 0]]]
+    want = check(images, planes, [1, 1], label_rows(rng, [1, 1]), entries)
+    assert (want["area"][2:] > 0).all()

@@ -485,3 +485,12 @@ def test_step_with_instance_masks_does_not_synchronise():
     finally:
         torch.cuda.set_sync_debug_mode(0)
     assert "val_epoch/mask_map_iou50_95_map" in vs.compute()
+
+
+@pytest.mark.parametrize("W", [63, 65, 127])
+def test_pack_next_to_a_word_boundary(W):
+    """W % 64 == 63 (below and above 64) and 1: the last word holds all but one pixel, or one."""
+    v, bits = _planes(5, W, "bool", n=3)
+    out = torch.full((3, 5, pitch_of(W)), 255, dtype=torch.uint8, device=DEV)
+    got = pp.pack_masks(torch.from_numpy(v).to(DEV), out=out)
+    assert np.array_equal(got.cpu().numpy(), pack_np(bits)) and torch.equal(pp.unpack_masks(got, W).cpu(), torch.from_numpy(bits))

@@ -218,3 +218,17 @@ def test_train_step_takes_the_polygon_ground_truth():
     loss = ts.step(imgs, gt_rows, masks, torch.tensor([1, 0], device=DEV))
     torch.cuda.synchronize()
     assert loss.shape == (10,) and bool(torch.isfinite(loss).all())
+
+
+@pytest.mark.parametrize("H,W", [(7, 63), (9, 127)])
+def test_one_padding_bit_in_the_last_word(H, W):
+    """W % 64 == 63, below and above 64: one padding bit in the last word, where a wrong valid_bits shows: a rectangle that overshoots the plane on every side, a triangle into the last column, and the rectangle clipped
+    to the last column alone; the caller's buffer is full of ones."""
+    over = np.asarray([(-5.0, -5.0), (W + 5.0, -5.0), (W + 5.0, H + 5.0), (-5.0, H + 5.0)])
+    tri = np.asarray([(W - 20.0, 0.0), (float(W), H / 2.0), (W - 20.0, float(H))])
+    planes, rects = [over, tri, over], [(0, 0, W, H), (0, 0, W + 64, H), (W - 1, 0, W + 1, H)]
+    want = [R.fill([p], H, W, r) for p, r in zip(planes, rects)]
+    out = torch.full((3, H, 8 * ((W + 63) // 64)), 0xFF, dtype=torch.uint8, device=DEV)
+    got, area, boxes = pp.fill_polygons(planes, H, W, clip=np.asarray(rects, dtype=np.int32), out=out, records=True)
+    _check(["over", "triangle", "last column"], got, area, boxes, want)
+    assert want[0].all() and want[1][:, W - 1].any() and int(want[2].sum()) == H

@@ -125,3 +125,14 @@ def test_autograd_node_hands_out_the_operator_gradient(shape):
     assert total.requires_grad and not dice.requires_grad and not boundary.requires_grad
     (2.0 * total).backward()
     assert torch.equal(zz.grad, 2.0 * g["seg_logits"])
+
+
+@pytest.mark.parametrize("shape", [(9, 63), (9, 65)])
+def test_widths_next_to_a_word_boundary(shape):
+    """W % 64 == 63 (and below 64) and W % 64 == 1: one padding bit, and one pixel in a word of its own; dense and packed targets."""
+    z, m = dev_inputs(shape)
+    ref = ref_of(shape, W_DICE, W_BOUNDARY)
+    for mm, kw in ((m, {}), (pack_masks(m[:, 0]), dict(W=shape[1]))):
+        res, g = seg_region_loss(z, mm, dice_weight=W_DICE, boundary_weight=W_BOUNDARY, smooth=SMOOTH, with_grads=True, **kw)
+        check_values(res, ref)
+        check_grad(g["seg_logits"], ref[3])

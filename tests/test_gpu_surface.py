@@ -215,3 +215,17 @@ def test_validation_step_with_surface_metrics():
     assert r_on["val_epoch/seg_surface_undefined"] == want["n_undefined"] == 1 and want["n_pairs"] == Bn and want["hd"] > 0
     on.reset()
     assert on.compute()["val_epoch/seg_hd_epoch"] == -1.0
+
+
+@pytest.mark.parametrize("shape", [(7, 63), (9, 127)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_one_padding_bit_in_the_last_word(shape):
+    """W % 64 == 63, below and above 64: one padding bit in the last word, where a wrong valid_bits shows: a full plane against noise, noise against noise, and a last column against a first one, padding bits set."""
+    H, W = shape
+    rng = np.random.default_rng(W)
+    noise = lambda: rng.uniform(size=(H, W)) < 0.5
+    last, first = np.zeros((H, W), bool), np.zeros((H, W), bool)
+    last[:, W - 1] = first[:, 0] = True
+    pairs = [(np.ones((H, W), bool), noise()), (noise(), noise()), (last, first)]
+    want = R.batch_records(pairs, QUANTILES, TOL2)
+    _assert_records(_device_records(pairs, W, pad_ones=True), want, str(shape))
+    assert want["max_d2"][2].tolist() == [(W - 1) ** 2] * 2
