@@ -216,7 +216,21 @@ __device__ __forceinline__ unsigned block_sum_u32(unsigned v, unsigned* red, int
   for (int w = 0; w < NW; ++w) s += red[w];
   return s;
 }
-// ... and the maximum (MAX) or minimum over it, under the same contract
+// K float sums at once over a workgroup of 4 waves, in a fixed order: the wave butterfly, then (w0 + w1) + (w2 + w3).  Every thread gets
+// the K totals back in v.  `red` holds 4 x K floats of LDS; one barrier, so a kernel that calls it twice puts a barrier between the calls.
+template <int K>
+__device__ __forceinline__ void block_sum_f32(float (&v)[K], float (*red)[K]) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    const float r = wave_sum(v[k]);
+    if (lane == 0) red[wave][k] = r;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) v[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+}
+// ... and the maximum (MAX) or minimum over block_sum_u32's tree, under its contract
 template <int NW, bool MAX>
 __device__ __forceinline__ unsigned block_extreme_u32(unsigned v, unsigned* red, int lane, int wave) {
 #pragma unroll

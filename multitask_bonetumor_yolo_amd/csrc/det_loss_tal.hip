@@ -1,5 +1,6 @@
 // Task-aligned detection loss (TaskAlignedAssigner + CIoU + DFL + BCE over all anchors) and its gradient with respect to the raw
-// Detect maps.  Definition: include/mtbt_hip.h (mtbt_tal_loss_args).  Decode conventions and bce_logits: loss_match.h.
+// Detect maps.  Definition: include/mtbt_hip.h (mtbt_tal_loss_args).  Anchor walk, side decode, DFL target and gradient, bce_logits and the
+// host's level table: loss_match.h, shared with the reference loss.
 //
 //   tal_decode_kernel    4 lanes per (image, anchor), one per box side: (max, sum-exp, expectation) of the side's distribution and the
 //                        decoded box -> workspace
@@ -40,34 +41,10 @@ struct TalP {
   int* assigned;     // [N * A]
   float* tscore;     // [N * A]
   float* partial;    // [blocks][6]: sum t, box, dfl, cls, #fg, sum ov
-  float* dmap[3];
-  int dld[3];
+  GradMaps d;
   int accumulate;
   float* out;
 };
-
-struct AnchorAt {
-  int n, a, l;
-  long pix;
-  float st, ax, ay;
-};
-
-__device__ __forceinline__ AnchorAt anchor_at(const LossP& p, int n, int a) {
-  AnchorAt r;
-  int l = 0;
-  if (p.n_levels > 1 && a >= p.off[1]) l = 1;
-  if (p.n_levels > 2 && a >= p.off[2]) l = 2;
-  const int cell = a - p.off[l];
-  const int w = p.w[l], hw = p.h[l] * w;
-  const int cy = cell / w, cx = cell - cy * w;
-  r.n = n; r.a = a; r.l = l;
-  r.pix = (long)n * hw + cell;
-  r.st = p.stride[l];
-  r.ax = (cx + 0.5f) * r.st; r.ay = (cy + 0.5f) * r.st;
-  return r;
-}
-
-__device__ __forceinline__ float sigmoid_(float x) { return 1.f / (1.f + expf(-x)); }
 
 __device__ __forceinline__ bool inside_box(float ax, float ay, const float4 g) {
   return fminf(fminf(ax - g.x, ay - g.y), fminf(g.z - ax, g.w - ay)) > 1e-9f;
@@ -112,29 +89,17 @@ __device__ __forceinline__ float ciou_dcorner(const CiouQ& q, const float4 p, co
   return diou - dpen - q.alpha * dv;
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 __global__ __launch_bounds__(256) void tal_decode_kernel(const TalP q) {
   const LossP& p = q.l;
   const long i = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
   const int side = threadIdx.x & 3;
   const bool live = i < (long)p.N * p.A;
-  const long ii = live ? i : 0;                                   // every lane takes part in the exchange below
-  const int n = (int)(ii / p.A), a = (int)(ii - (long)n * p.A);
-  const AnchorAt at = anchor_at(p, n, a);
-  const float* d = p.map[at.l] + at.pix * p.ld[at.l] + side * p.reg_max;
-  float m = -INFINITY;
-  for (int k = 0; k < p.reg_max; ++k) m = fmaxf(m, d[k]);
-  float s = 0.f;
-  for (int k = 0; k < p.reg_max; ++k) s += expf(d[k] - m);
-  float dist = 0.f;
-  for (int k = 0; k < p.reg_max; ++k) dist += (expf(d[k] - m) / s) * (float)k;
-  const int qbase = (threadIdx.x & 63) & ~3;
-  const float x1 = at.ax - __shfl(dist, qbase + 0, 64) * at.st, y1 = at.ay - __shfl(dist, qbase + 1, 64) * at.st;
-  const float x2 = at.ax + __shfl(dist, qbase + 2, 64) * at.st, y2 = at.ay + __shfl(dist, qbase + 3, 64) * at.st;
+  const AnchorAt at = anchor_at(p, live ? i : 0);                 // every lane takes part in decode_box's exchange
+  const SideDist sd = side_dist(anchor_row(p, at) + side * p.reg_max, p.reg_max);
+  const float4 box = decode_box(at, sd.dist);
   if (!live) return;
-  *reinterpret_cast<f32x4*>(q.stat + (i * 4 + side) * 4) = f32x4{m, s, dist, 0.f};
-  if (side == 0) *reinterpret_cast<f32x4*>(q.boxes + i * 4) = f32x4{x1, y1, x2, y2};
+  *reinterpret_cast<f32x4*>(q.stat + (i * 4 + side) * 4) = f32x4{sd.m, sd.s, sd.dist, 0.f};
+  if (side == 0) *reinterpret_cast<f32x4*>(q.boxes + i * 4) = f32x4{box.x, box.y, box.z, box.w};
 }
 
 __global__ __launch_bounds__(256) void tal_topk_kernel(const TalP q) {
@@ -167,7 +132,7 @@ __global__ __launch_bounds__(256) void tal_topk_kernel(const TalP q) {
     if (inside_box(at.ax, at.ay, b)) {
       const float4 pb = ld4(q.boxes + ((long)n * A + a) * 4);
       ov = fmaxf(ciou_q(pb, b).val, 0.f);
-      const float sc = cok ? sigmoid_(p.map[at.l][at.pix * p.ld[at.l] + 4 * p.reg_max + gc]) : 0.f;
+      const float sc = cok ? sigmoid(anchor_row(p, at)[4 * p.reg_max + gc]) : 0.f;
       m = powf(sc, q.alpha) * powf(ov, q.beta);
     }
     met[a] = m; ovl[a] = ov;
@@ -240,27 +205,16 @@ __global__ __launch_bounds__(256) void tal_gtmax_kernel(const TalP q) {
   q.gmax[2 * g] = M; q.gmax[2 * g + 1] = O;
 }
 
-// the side's DFL target: clamp(distance from the anchor point to the GT side / stride, 0, reg_max - 1 - 0.01) -> tl, wl, wr (tr = tl + 1)
-__device__ __forceinline__ void dfl_target(const AnchorAt& at, const float4 b, int side, int reg_max, int& tl, float& wl, float& wr) {
-  const float apc = (side & 1) ? at.ay : at.ax;
-  const float gtc = side == 0 ? b.x : side == 1 ? b.y : side == 2 ? b.z : b.w;
-  float t = ((side < 2) ? (apc - gtc) : (gtc - apc)) / at.st;
-  t = fminf(fmaxf(t, 0.f), (float)reg_max - 1.01f);
-  tl = min(max((int)floorf(t), 0), reg_max - 2);
-  wl = (float)(tl + 1) - t;
-  wr = 1.f - wl;
-}
-
 __global__ __launch_bounds__(256) void tal_value_kernel(const TalP q) {
   __shared__ float red[4][6];
   const LossP& p = q.l;
   const long i = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
   const int side = threadIdx.x & 3;
-  float v_t = 0.f, v_box = 0.f, v_dfl = 0.f, v_cls = 0.f, v_cnt = 0.f, v_ov = 0.f;
+  float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // sum t, box, dfl, cls, #fg, sum ov
   if (i < (long)p.N * p.A) {
-    const int n = (int)(i / p.A), a = (int)(i - (long)n * p.A);
-    const AnchorAt at = anchor_at(p, n, a);
-    const float* row = p.map[at.l] + at.pix * p.ld[at.l];
+    const AnchorAt at = anchor_at(p, i);
+    const int a = at.a;
+    const float* row = anchor_row(p, at);
     const int g = q.assigned[i];
     float t = 0.f;
     int gc = -1;
@@ -269,32 +223,26 @@ __global__ __launch_bounds__(256) void tal_value_kernel(const TalP q) {
       gc = p.gt_cls[g];
     }
     if (side == 0) q.tscore[i] = t;
-    for (int c = side; c < p.nc; c += 4) v_cls += bce_logits(row[4 * p.reg_max + c], c == gc ? t : 0.f);
+    for (int c = side; c < p.nc; c += 4) v[3] += bce_logits(row[4 * p.reg_max + c], c == gc ? t : 0.f);
     if (g >= 0) {
       const float4 b = ld4(p.gt_xyxy + 4 * (long)g);
       const float4 st = ld4(q.stat + (i * 4 + side) * 4);
       const float lse = st.x + logf(st.y);
       const float* d = row + side * p.reg_max;
-      int tl;
-      float wl, wr;
-      dfl_target(at, b, side, p.reg_max, tl, wl, wr);
-      v_dfl = t * (0.25f * ((lse - d[tl]) * wl + (lse - d[tl + 1]) * wr));
+      const DflTarget tg = dfl_target(at, b, side, p.reg_max);
+      const float wl = (float)tg.tr - tg.t, wr = 1.f - wl;
+      v[2] = t * (0.25f * ((lse - d[tg.tl]) * wl + (lse - d[tg.tr]) * wr));
       if (side == 0) {
         const float4 pb = ld4(q.boxes + i * 4);
-        v_box = (1.f - ciou_q(pb, b).val) * t;
-        v_t = t; v_cnt = 1.f; v_ov = q.ovl[(long)g * p.A + a];
+        v[1] = (1.f - ciou_q(pb, b).val) * t;
+        v[0] = t; v[4] = 1.f; v[5] = q.ovl[(long)g * p.A + a];
       }
     }
   }
-  float vals[6] = {v_t, v_box, v_dfl, v_cls, v_cnt, v_ov};
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  block_sum_f32<6>(v, red);
+  if (threadIdx.x == 0)
 #pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const float r = wave_sum(vals[k]);
-    if (lane == 0) red[wave][k] = r;
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) q.partial[(long)blockIdx.x * 6 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    for (int k = 0; k < 6; ++k) q.partial[(long)blockIdx.x * 6 + k] = v[k];
 }
 
 __global__ __launch_bounds__(256) void tal_finalize_kernel(const TalP q, int blocks) {
@@ -303,16 +251,9 @@ __global__ __launch_bounds__(256) void tal_finalize_kernel(const TalP q, int blo
   for (int b = threadIdx.x; b < blocks; b += 256)
 #pragma unroll
     for (int k = 0; k < 6; ++k) v[k] += q.partial[(long)b * 6 + k];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const float r = wave_sum(v[k]);
-    if (lane == 0) red[wave][k] = r;
-  }
-  __syncthreads();
+  block_sum_f32<6>(v, red);
   if (threadIdx.x == 0) {
-    float t[6];
-    for (int k = 0; k < 6; ++k) t[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+    const float* t = v;
     const float T = fmaxf(t[0], 1.f);
     const float box = t[1] / T, dfl = t[2] / T, cls = t[3] / T;
     q.out[0] = box; q.out[1] = dfl; q.out[2] = cls;
@@ -329,10 +270,9 @@ __global__ __launch_bounds__(256) void tal_grad_kernel(const TalP q) {
   const long i = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
   const int side = threadIdx.x & 3;
   if (i >= (long)p.N * p.A) return;
-  const int n = (int)(i / p.A), a = (int)(i - (long)n * p.A);
-  const AnchorAt at = anchor_at(p, n, a);
-  const float* row = p.map[at.l] + at.pix * p.ld[at.l];
-  float* drow = q.dmap[at.l] + at.pix * q.dld[at.l];
+  const AnchorAt at = anchor_at(p, i);
+  const float* row = anchor_row(p, at);
+  float* drow = q.d.map[at.l] + at.pix * q.d.ld[at.l];
   const bool acc = q.accumulate != 0;
   const float invT = 1.f / q.out[5];
   const int g = q.assigned[i];
@@ -340,7 +280,7 @@ __global__ __launch_bounds__(256) void tal_grad_kernel(const TalP q) {
   const int gc = g >= 0 ? p.gt_cls[g] : -1;
   const float kc = q.w_cls * invT;
   for (int c = side; c < p.nc; c += 4) {
-    const float v = kc * (sigmoid_(row[4 * p.reg_max + c]) - (c == gc ? t : 0.f));
+    const float v = kc * (sigmoid(row[4 * p.reg_max + c]) - (c == gc ? t : 0.f));
     float* d = drow + 4 * p.reg_max + c;
     *d = acc ? *d + v : v;
   }
@@ -353,22 +293,13 @@ __global__ __launch_bounds__(256) void tal_grad_kernel(const TalP q) {
   const float4 b = ld4(p.gt_xyxy + 4 * (long)g);
   const float4 pb = ld4(q.boxes + i * 4);
   const float4 st = ld4(q.stat + (i * 4 + side) * 4);
-  const float m = st.x, s = st.y, dist = st.z;
+  const SideDist sd{st.x, st.y, st.z};
   const CiouQ cq = ciou_q(pb, b);
   const float dcorner = -q.w_box * t * invT * ciou_dcorner(cq, pb, b, side);   // d total / d corner
   const float ddist = dcorner * (side < 2 ? -at.st : at.st);                   // corner = anchor -/+ dist * stride
-  int tl;
-  float wl, wr;
-  dfl_target(at, b, side, p.reg_max, tl, wl, wr);
-  const float kd = q.w_dfl * t * invT * 0.25f;
-  const float* d = row + side * p.reg_max;
-  for (int k = 0; k < p.reg_max; ++k) {
-    const float pj = expf(d[k] - m) / s;
-    float gv = ddist * pj * ((float)k - dist) + kd * (wl + wr) * pj;
-    if (k == tl) gv -= kd * wl;
-    if (k == tl + 1) gv -= kd * wr;
-    dd[k] = acc ? dd[k] + gv : gv;
-  }
+  const DflTarget tg = dfl_target(at, b, side, p.reg_max);
+  const float wl = (float)tg.tr - tg.t, wr = 1.f - wl;
+  dfl_side_grad(row + side * p.reg_max, sd, p.reg_max, ddist, q.w_dfl * t * invT * 0.25f, tg, wl, wr, dd, acc);
 }
 
 inline int64_t align16(int64_t v) { return (v + 15) & ~(int64_t)15; }
@@ -410,32 +341,19 @@ extern "C" int mtbt_tal_det_loss(const mtbt_tal_loss_args* a, void* stream) {
   if (a->n_levels < 1 || a->n_levels > 3 || a->N <= 0 || a->nc <= 0 || a->reg_max < 2 || a->reg_max > 64) return MTBT_EINVAL;
   if (a->topk < 1 || a->topk > TAL_MAX_TOPK || a->n_gt < 0 || !(a->img_size > 0.f)) return MTBT_EINVAL;
   const int no = 4 * a->reg_max + a->nc;
-  TalP q;
+  TalP q{};
   LossP& p = q.l;
   int n_dmap = 0;
   for (int l = 0; l < a->n_levels; ++l) n_dmap += a->d_map[l] ? 1 : 0;
   if (n_dmap != 0 && n_dmap != a->n_levels) return MTBT_EINVAL;
-  long A = 0;
-  for (int l = 0; l < 3; ++l) {
-    p.off[l] = (int)A;
-    q.dmap[l] = nullptr; q.dld[l] = 0;
-    if (l < a->n_levels) {
-      if (!a->map[l] || a->h[l] <= 0 || a->w[l] <= 0 || a->map_pixel_stride[l] < no) return MTBT_EINVAL;
-      if (n_dmap && a->d_map_pixel_stride[l] < no) return MTBT_EINVAL;
-      p.map[l] = a->map[l]; p.h[l] = a->h[l]; p.w[l] = a->w[l]; p.ld[l] = a->map_pixel_stride[l];
-      p.stride[l] = a->img_size / (float)a->w[l];
-      q.dmap[l] = a->d_map[l]; q.dld[l] = a->d_map_pixel_stride[l];
-      A += (long)a->h[l] * a->w[l];
-      if (A > 0x7fffffffL) return MTBT_EINVAL;
-    } else { p.map[l] = nullptr; p.h[l] = p.w[l] = 1; p.ld[l] = 0; p.stride[l] = 0.f; }
-  }
+  if (int rc = fill_levels(a, no, p, n_dmap ? &q.d : nullptr, a->d_map, a->d_map_pixel_stride)) return rc;
+  const long A = p.A;
   const long NA = (long)a->N * A;
   if (NA > 0x7fffffffL / 64 || a->N > 0x7fffffff / 64) return MTBT_EINVAL;
   if (!aligned16(a->gt_xyxy) || !aligned16(a->workspace)) return MTBT_EALIGN;
   const TalLayout lay = layout_of(a->N, A, a->n_gt);
   if (a->workspace_bytes < lay.total) return MTBT_EWORKSPACE;
-  p.off[3] = (int)A;
-  p.n_levels = a->n_levels; p.N = a->N; p.A = (int)A; p.nc = a->nc; p.reg_max = a->reg_max;
+  p.N = a->N; p.nc = a->nc; p.reg_max = a->reg_max;
   p.gt_xyxy = a->gt_xyxy; p.gt_cls = a->gt_cls; p.gt_off = a->gt_off;
   p.iou_thresh = 0.f; p.smoothing = 0.f; p.training = 1; p.partial = nullptr;
   q.G = a->n_gt; q.topk = a->topk;

@@ -14,7 +14,7 @@
 //                     the detection confusion matrix of the eval-mode loss (`temp_matched_preds_for_cm`, :349-350): the same
 //                     anchors and positives, argmax of each positive's class logits against its GT class, integer counts.
 // det_loss_kernel, det_loss_grad_kernel and det_confusion_kernel share one per-anchor decode + match prologue (match_anchor,
-// loss_match.h: also the instance-mask loss's).
+// loss_match.h: also the instance-mask loss's), and with the task-aligned loss the DFL target and gradient and the host's level table.
 // Deterministic (fixed reduction orders); fp32 with libm exp / log (this file is built with -ffp-contract=off like the rest
 // of the post-process so that the IoU matches torch's arithmetic).
 #include <cmath>
@@ -26,59 +26,37 @@ namespace {
 
 __global__ __launch_bounds__(256) void det_loss_kernel(const LossP p) {
   __shared__ float red[4][5];
-  const AnchorMatch am = match_anchor(p, (long)blockIdx.x * 64 + (threadIdx.x >> 2), threadIdx.x & 3);
   const int side = threadIdx.x & 3;
-  const float* row = am.row;
-  const float* d = am.d;
-  const float lse = am.m + logf(am.s);
-  const float ax = am.ax, ay = am.ay, st = am.st, best = am.best;
-  const int bi = am.bi;
-  const bool pos = am.pos;
-
-  float v_cnt = 0.f, v_box = 0.f, v_iou = 0.f, v_cls = 0.f, v_dfl = 0.f;
-  if (pos) {
-    const float4 b = *reinterpret_cast<const float4*>(p.gt_xyxy + 4 * bi);
-    // DFL target of this side (running_main_v3.py:351-367)
-    const float apc = (side & 1) ? ay : ax;
-    const float gtc = side == 0 ? b.x : side == 1 ? b.y : side == 2 ? b.z : b.w;
-    float t = ((side < 2) ? (apc - gtc) : (gtc - apc)) / st;
-    t = fminf(fmaxf(t, 0.f), (float)p.reg_max - 1.01f);
-    int tl = (int)floorf(t);
-    tl = min(max(tl, 0), p.reg_max - 1);
-    const int tr = min(tl + 1, p.reg_max - 1);
-    const float wl = (float)tr - t, wr = t - (float)tl;
-    v_dfl = (lse - d[tl]) * wl + (lse - d[tr]) * wr;
+  const AnchorMatch am = match_anchor(p, (long)blockIdx.x * 64 + (threadIdx.x >> 2), side);
+  float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};   // n_pos, sum(1 - iou), sum(iou), sum(cls bce), sum(dfl)
+  if (am.pos) {
+    const float lse = am.sd.m + logf(am.sd.s);
+    const DflTarget tg = dfl_target(am.at, ld4(p.gt_xyxy + 4 * am.bi), side, p.reg_max);
+    const float wl = (float)tg.tr - tg.t, wr = tg.t - (float)tg.tl;
+    v[4] = (lse - am.d[tg.tl]) * wl + (lse - am.d[tg.tr]) * wr;
     // class BCE: the group's lanes split the classes
-    const int gc = p.gt_cls[bi];
+    const int gc = p.gt_cls[am.bi];
     const bool smooth = p.smoothing > 0.f && p.training;
     for (int c = side; c < p.nc; c += 4) {
       const float tgt = smooth ? (c == gc ? 1.f - p.smoothing : p.smoothing / (float)(p.nc - 1)) : (c == gc ? 1.f : 0.f);
-      v_cls += bce_logits(row[4 * p.reg_max + c], tgt);
+      v[3] += bce_logits(am.row[4 * p.reg_max + c], tgt);
     }
-    if (side == 0) { v_cnt = 1.f; v_box = 1.f - best; v_iou = best; }
+    if (side == 0) { v[0] = 1.f; v[1] = 1.f - am.best; v[2] = am.best; }
   }
-  // workgroup reduction in a fixed order: wave sums, then 4 wave partials
-  float vals[5] = {v_cnt, v_box, v_iou, v_cls, v_dfl};
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  block_sum_f32<5>(v, red);   // fixed order, no atomics
+  if (threadIdx.x == 0)
 #pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    const float r = wave_sum(vals[q]);
-    if (lane == 0) red[wave][q] = r;
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) p.partial[(long)blockIdx.x * 5 + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+    for (int q = 0; q < 5; ++q) p.partial[(long)blockIdx.x * 5 + q] = v[q];
 }
 
 __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ x, const float* __restrict__ t, const float* __restrict__ bias,
                                                   long n, float* __restrict__ partial) {
-  __shared__ float red[4];
+  __shared__ float red[4][1];
   const float b = bias ? *bias : 0.f;
-  float s = 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s += bce_logits(x[i] + b, t[i]);
-  const float r = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  float s[1] = {0.f};
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s[0] += bce_logits(x[i] + b, t[i]);
+  block_sum_f32<1>(s, red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s[0];
 }
 
 struct FinP {
@@ -90,7 +68,7 @@ struct FinP {
 };
 
 __global__ __launch_bounds__(256) void finalize_kernel(const FinP p) {
-  __shared__ float red[4][8];
+  __shared__ float red[4][7];
   float v[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // 5 detection sums, seg sum, img CE sum
   for (int b = threadIdx.x; b < p.det_blocks; b += 256)
 #pragma unroll
@@ -104,16 +82,9 @@ __global__ __launch_bounds__(256) void finalize_kernel(const FinP p) {
     for (int c = 0; c < p.n_img_classes; ++c) s += expf(lg[c] - m);
     v[6] += (m + logf(s)) - lg[p.img_gt[i]];
   }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-  for (int q = 0; q < 7; ++q) {
-    const float r = wave_sum(v[q]);
-    if (lane == 0) red[wave][q] = r;
-  }
-  __syncthreads();
+  block_sum_f32<7>(v, red);
   if (threadIdx.x == 0) {
-    float t[7];
-    for (int q = 0; q < 7; ++q) t[q] = (red[0][q] + red[1][q]) + (red[2][q] + red[3][q]);
+    const float* t = v;
     const float n_pos = t[0];
     const float norm = n_pos > 0.f ? n_pos : (float)p.N;                 // running_main_v3.py:371
     const float box = t[1] / norm, cls = t[3] / norm, dfl = t[4] / norm;
@@ -140,35 +111,26 @@ inline long seg_blocks_of(long n) { long b = (n + 256 * 8 - 1) / (256 * 8); retu
 // not positives get zeros.  The positives mask and the matched GT index carry no gradient (comparison / argmax).
 struct GradP {
   LossP l;
-  float* dmap[3];
-  int dld[3];
+  GradMaps d;
   const float* fwd_out;   // out[8] of mtbt_multitask_loss
   float w_box, w_dfl, w_cls;
 };
 
 __global__ __launch_bounds__(256) void det_loss_grad_kernel(const GradP q) {
   const LossP& p = q.l;
-  const AnchorMatch am = match_anchor(p, (long)blockIdx.x * 64 + (threadIdx.x >> 2), threadIdx.x & 3);
   const int side = threadIdx.x & 3;
-  const float* row = am.row;
-  const float* d = am.d;
-  float* drow = q.dmap[am.l] + am.pix * q.dld[am.l];
-  const float m = am.m, s = am.s, dist = am.dist;
-  const float ax = am.ax, ay = am.ay, st = am.st;
-  const float x1 = am.x1, y1 = am.y1, x2 = am.x2, y2 = am.y2;
-  const int bi = am.bi;
-  const bool live = am.live, pos = am.pos;
-  if (!live) return;
-  const int no = 4 * p.reg_max + p.nc;
-  if (!pos) {
+  const AnchorMatch am = match_anchor(p, (long)blockIdx.x * 64 + (threadIdx.x >> 2), side);
+  if (!am.live) return;
+  float* drow = q.d.map[am.at.l] + am.at.pix * q.d.ld[am.at.l];
+  if (!am.pos) {
     for (int i = 0; i < p.reg_max; ++i) drow[side * p.reg_max + i] = 0.f;
     for (int c = side; c < p.nc; c += 4) drow[4 * p.reg_max + c] = 0.f;
-    (void)no;
     return;
   }
+  const float x1 = am.box.x, y1 = am.box.y, x2 = am.box.z, y2 = am.box.w, st = am.at.st;
   const float n_pos = q.fwd_out[6];
   const float inv = 1.f / (n_pos > 0.f ? n_pos : (float)p.N);
-  const float4 b = *reinterpret_cast<const float4*>(p.gt_xyxy + 4 * bi);
+  const float4 b = ld4(p.gt_xyxy + 4 * am.bi);
   // d IoU / d (this lane's corner)
   const float iwr = fminf(x2, b.z) - fmaxf(x1, b.x), ihr = fminf(y2, b.w) - fmaxf(y1, b.y);
   const float iw = fmaxf(iwr, 0.f), ih = fmaxf(ihr, 0.f);
@@ -183,29 +145,14 @@ __global__ __launch_bounds__(256) void det_loss_grad_kernel(const GradP q) {
   const float diou = (dinter * uni - inter * (darea - dinter)) / (uni * uni);
   const float dcorner = -q.w_box * inv * diou;                       // d total / d corner
   const float ddist = dcorner * (side < 2 ? -st : st);               // corner = anchor -/+ dist * stride
-  // DFL target of this side
-  const float apc = (side & 1) ? ay : ax;
-  const float gtc = side == 0 ? b.x : side == 1 ? b.y : side == 2 ? b.z : b.w;
-  float t = ((side < 2) ? (apc - gtc) : (gtc - apc)) / st;
-  t = fminf(fmaxf(t, 0.f), (float)p.reg_max - 1.01f);
-  int tl = (int)floorf(t);
-  tl = min(max(tl, 0), p.reg_max - 1);
-  const int tr = min(tl + 1, p.reg_max - 1);
-  const float wl = (float)tr - t, wr = t - (float)tl;
-  const float kd = q.w_dfl * inv;
-  for (int i = 0; i < p.reg_max; ++i) {
-    const float pj = expf(d[i] - m) / s;
-    float gv = ddist * pj * ((float)i - dist) + kd * (wl + wr) * pj;
-    if (i == tl) gv -= kd * wl;
-    if (i == tr) gv -= kd * wr;
-    drow[side * p.reg_max + i] = gv;
-  }
-  const int gc = p.gt_cls[bi];
+  const DflTarget tg = dfl_target(am.at, b, side, p.reg_max);
+  const float wl = (float)tg.tr - tg.t, wr = tg.t - (float)tg.tl;
+  dfl_side_grad(am.d, am.sd, p.reg_max, ddist, q.w_dfl * inv, tg, wl, wr, drow + side * p.reg_max, false);
+  const int gc = p.gt_cls[am.bi];
   const bool smooth = p.smoothing > 0.f && p.training;
   for (int c = side; c < p.nc; c += 4) {
     const float tgt = smooth ? (c == gc ? 1.f - p.smoothing : p.smoothing / (float)(p.nc - 1)) : (c == gc ? 1.f : 0.f);
-    const float x = row[4 * p.reg_max + c];
-    drow[4 * p.reg_max + c] = q.w_cls * inv * (1.f / (1.f + expf(-x)) - tgt);
+    drow[4 * p.reg_max + c] = q.w_cls * inv * (sigmoid(am.row[4 * p.reg_max + c]) - tgt);
   }
 }
 
@@ -215,7 +162,7 @@ __global__ __launch_bounds__(256) void seg_img_grad_kernel(const float* __restri
                                                            const long long* __restrict__ img_gt, int N, int ncls, float k_img,
                                                            float* __restrict__ dimg) {
   const float b = bias ? *bias : 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dx[i] = k_seg * (1.f / (1.f + expf(-(x[i] + b))) - t[i]);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) dx[i] = k_seg * (sigmoid(x[i] + b) - t[i]);
   if (blockIdx.x == 0 && dimg) {
     for (int i = threadIdx.x; i < N; i += 256) {
       const float* lg = img_logits + (long)i * ncls;
@@ -267,23 +214,13 @@ __global__ __launch_bounds__(256) void det_confusion_kernel(const LossP p, unsig
 
 }  // namespace
 
-// validated detection fields (maps, GT boxes, match threshold): what det_loss_kernel's prologue reads
-static int fill_det_params(const mtbt_loss_args* a, LossP& p, int& A) {
+// validated detection fields (maps, GT boxes, match threshold): what det_loss_kernel's prologue reads; with `g`, the gradient maps too
+static int fill_det_params(const mtbt_loss_args* a, LossP& p, GradMaps* g = nullptr, float* const* d_map = nullptr, const int32_t* d_ld = nullptr) {
   if (a->n_levels < 1 || a->n_levels > 3 || a->N <= 0 || a->nc <= 0 || a->reg_max <= 0 || a->reg_max > 64) return MTBT_EINVAL;
   if (!a->gt_xyxy || !a->gt_cls || !a->gt_off) return MTBT_EINVAL;
   if (!aligned16(a->gt_xyxy)) return MTBT_EALIGN;
-  A = 0;
-  for (int l = 0; l < 3; ++l) {
-    p.off[l] = A;
-    if (l < a->n_levels) {
-      if (!a->map[l] || a->h[l] <= 0 || a->w[l] <= 0 || a->map_pixel_stride[l] < 4 * a->reg_max + a->nc) return MTBT_EINVAL;
-      p.map[l] = a->map[l]; p.h[l] = a->h[l]; p.w[l] = a->w[l]; p.ld[l] = a->map_pixel_stride[l];
-      p.stride[l] = a->img_size / (float)a->w[l];                       // running_main_v3.py:266
-      A += a->h[l] * a->w[l];
-    } else { p.map[l] = nullptr; p.h[l] = p.w[l] = 1; p.ld[l] = 0; p.stride[l] = 0.f; }
-  }
-  p.off[3] = A;
-  p.n_levels = a->n_levels; p.N = a->N; p.A = A; p.nc = a->nc; p.reg_max = a->reg_max;
+  if (int rc = fill_levels(a, 4 * a->reg_max + a->nc, p, g, d_map, d_ld)) return rc;
+  p.N = a->N; p.nc = a->nc; p.reg_max = a->reg_max;
   p.gt_xyxy = a->gt_xyxy; p.gt_cls = a->gt_cls; p.gt_off = a->gt_off;
   p.iou_thresh = a->iou_thresh; p.smoothing = a->label_smoothing; p.training = a->training;
   p.partial = nullptr;
@@ -291,10 +228,10 @@ static int fill_det_params(const mtbt_loss_args* a, LossP& p, int& A) {
 }
 
 // validated kernel parameters shared by the value and the gradient entry points
-static int fill_loss_params(const mtbt_loss_args* a, LossP& p, int& A) {
+static int fill_loss_params(const mtbt_loss_args* a, LossP& p, GradMaps* g = nullptr, float* const* d_map = nullptr, const int32_t* d_ld = nullptr) {
   if (!a || !a->out || !a->img_logits || !a->img_gt || a->n_img_classes <= 0) return MTBT_EINVAL;
   if ((a->seg_n > 0) != (a->seg_logits != nullptr && a->seg_targets != nullptr)) return MTBT_EINVAL;
-  return fill_det_params(a, p, A);
+  return fill_det_params(a, p, g, d_map, d_ld);
 }
 
 extern "C" int64_t mtbt_loss_workspace_bytes(int N, int A, int64_t seg_n) {
@@ -305,11 +242,10 @@ extern "C" int64_t mtbt_loss_workspace_bytes(int N, int A, int64_t seg_n) {
 extern "C" int mtbt_multitask_loss(const mtbt_loss_args* a, void* stream) {
   if (!a || !a->workspace) return MTBT_EINVAL;
   LossP p;
-  int A = 0;
-  if (int rc = fill_loss_params(a, p, A)) return rc;
-  const long db = det_blocks_of(a->N, A), sb = a->seg_n > 0 ? seg_blocks_of(a->seg_n) : 0;
+  if (int rc = fill_loss_params(a, p)) return rc;
+  const long db = det_blocks_of(a->N, p.A), sb = a->seg_n > 0 ? seg_blocks_of(a->seg_n) : 0;
   if (db > 0x7fffffffL) return MTBT_EINVAL;
-  if (a->workspace_bytes < mtbt_loss_workspace_bytes(a->N, A, a->seg_n)) return MTBT_EWORKSPACE;
+  if (a->workspace_bytes < mtbt_loss_workspace_bytes(a->N, p.A, a->seg_n)) return MTBT_EWORKSPACE;
   float* det_partial = a->workspace;
   float* seg_partial = det_partial + db * 5;
   p.partial = det_partial;
@@ -330,19 +266,10 @@ extern "C" int mtbt_multitask_loss_grad(const mtbt_loss_args* a, float* const* d
                                         float* d_img_logits, void* stream) {
   if (!a || !d_map || !d_map_pixel_stride) return MTBT_EINVAL;
   GradP q;
-  int A = 0;
-  if (int rc = fill_loss_params(a, q.l, A)) return rc;
-  for (int l = 0; l < 3; ++l) {
-    q.dmap[l] = nullptr; q.dld[l] = 0;
-    if (l < a->n_levels) {
-      if (!d_map[l] || d_map_pixel_stride[l] < 4 * a->reg_max + a->nc) return MTBT_EINVAL;
-      q.dmap[l] = d_map[l]; q.dld[l] = d_map_pixel_stride[l];
-    }
-  }
+  if (int rc = fill_loss_params(a, q.l, &q.d, d_map, d_map_pixel_stride)) return rc;
   if (a->seg_n > 0 && !d_seg_logits) return MTBT_EINVAL;
-  q.l.partial = nullptr;
   q.fwd_out = a->out; q.w_box = a->w_box; q.w_dfl = a->w_dfl; q.w_cls = a->w_cls;
-  const long db = det_blocks_of(a->N, A);
+  const long db = det_blocks_of(a->N, q.l.A);
   if (db > 0x7fffffffL) return MTBT_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(det_loss_grad_kernel, dim3((unsigned)db), dim3(256), 0, s, q);
@@ -357,9 +284,8 @@ extern "C" int mtbt_multitask_loss_grad(const mtbt_loss_args* a, float* const* d
 extern "C" int mtbt_det_confusion(const mtbt_loss_args* a, int64_t* counts, int32_t* status, void* stream) {
   if (!a || !counts || !status || a->nc > MTBT_CONFUSION_MAX_NC) return MTBT_EINVAL;
   LossP p;
-  int A = 0;
-  if (int rc = fill_det_params(a, p, A)) return rc;
-  const long db = det_blocks_of(a->N, A);
+  if (int rc = fill_det_params(a, p)) return rc;
+  const long db = det_blocks_of(a->N, p.A);
   const unsigned grid = (unsigned)(db < 1024 ? db : 1024);
   hipLaunchKernelGGL(det_confusion_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), p,
                      reinterpret_cast<unsigned long long*>(counts), reinterpret_cast<int*>(status));

@@ -58,8 +58,6 @@ struct MaskLossP {
   float* out;
 };
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 struct BoxQ {
   float x1, y1, x2, y2, area;
   int xs, xe, ys, ye;          // a superset of the inside pixels, clipped to the map (the float predicate decides)
@@ -70,7 +68,7 @@ struct BoxQ {
 };
 
 __device__ __forceinline__ BoxQ box_of(const MaskLossP& p, int g) {
-  const float4 b = *reinterpret_cast<const float4*>(p.l.gt_xyxy + 4 * (long)g);
+  const float4 b = ld4(p.l.gt_xyxy + 4 * (long)g);
   BoxQ q;
   q.x1 = b.x * p.sx; q.y1 = b.y * p.sy; q.x2 = b.z * p.sx; q.y2 = b.w * p.sy;
   q.area = (q.x2 - q.x1) * (q.y2 - q.y1);
@@ -81,17 +79,22 @@ __device__ __forceinline__ BoxQ box_of(const MaskLossP& p, int g) {
   return q;
 }
 
-__global__ __launch_bounds__(256) void ml_match_kernel(const MaskLossP p) {
-  const long g = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
-  const int side = threadIdx.x & 3;
-  const AnchorMatch am = match_anchor(p.l, g, side);
-  if (!am.live) return;
-  if (side == 0) p.match[g] = am.pos ? am.bi : -1;
-  if (p.d_mc && !p.acc_dmc && !am.pos) {
+// What both match kernels end in: match[g] = `row` (a GT row, or -1), and the d_mc row of an anchor that is not a positive zeroed, 8
+// floats per lane of the anchor's 4 (the value kernel writes the positives' rows only).
+__device__ __forceinline__ void store_match(const MaskLossP& p, long g, int side, int row) {
+  if (side == 0) p.match[g] = row;
+  if (p.d_mc && !p.acc_dmc && row < 0) {
     f32x4* d = reinterpret_cast<f32x4*>(p.d_mc + g * NM + side * 8);
     d[0] = f32x4{0.f, 0.f, 0.f, 0.f};
     d[1] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
+}
+
+__global__ __launch_bounds__(256) void ml_match_kernel(const MaskLossP p) {
+  const long g = (long)blockIdx.x * 64 + (threadIdx.x >> 2);
+  const int side = threadIdx.x & 3;
+  const AnchorMatch am = match_anchor(p.l, g, side);
+  if (am.live) store_match(p, g, side, am.pos ? am.bi : -1);
 }
 
 // The match from a given assignment: 4 lanes per (image, anchor) like ml_match_kernel, so that a non-foreground anchor's d_mc row is
@@ -104,13 +107,7 @@ __global__ __launch_bounds__(256) void ml_assigned_kernel(const MaskLossP p, con
   const int n = (int)(g / p.l.A);
   const int v = assigned[g];
   const int g0 = max(p.l.gt_off[n], 0), g1 = min(p.l.gt_off[n + 1], p.G);
-  const bool pos = v >= g0 && v < g1;
-  if (side == 0) p.match[g] = pos ? v : -1;
-  if (p.d_mc && !p.acc_dmc && !pos) {
-    f32x4* d = reinterpret_cast<f32x4*>(p.d_mc + g * NM + side * 8);
-    d[0] = f32x4{0.f, 0.f, 0.f, 0.f};
-    d[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+  store_match(p, g, side, v >= g0 && v < g1 ? v : -1);
 }
 
 __global__ __launch_bounds__(256) void ml_list_kernel(const MaskLossP p) {
@@ -213,7 +210,7 @@ __global__ __launch_bounds__(256) void ml_value_kernel(const MaskLossP p) {
         const int yy = pv ? idx / bw : 0, xx = pv ? idx - yy * bw : 0;
         const float* pp = pr + ((long)(q.ys + yy) * p.wp + (q.xs + xx)) * NM + j * 8;
         float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0;
-        if (pv) { v0 = *reinterpret_cast<const float4*>(pp); v1 = *reinterpret_cast<const float4*>(pp + 4); }
+        if (pv) { v0 = ld4(pp); v1 = ld4(pp + 4); }
         pa[0] = v0.x; pa[1] = v0.y; pa[2] = v0.z; pa[3] = v0.w; pa[4] = v1.x; pa[5] = v1.y; pa[6] = v1.z; pa[7] = v1.w;
       }
       f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -234,7 +231,7 @@ __global__ __launch_bounds__(256) void ml_value_kernel(const MaskLossP p) {
         if (in) {
           const float t = tg[(long)(y * p.ry) * p.S + x * p.rx];
           lsum += bce_logits(acc[r], t);
-          rv = kg * (sigmoidf_(acc[r]) - t);
+          rv = kg * (sigmoid(acc[r]) - t);
         }
         rr[r] = rv;
       }
@@ -326,7 +323,7 @@ __global__ __launch_bounds__(256) void ml_dprotos_kernel(const MaskLossP p, int 
     t[cg] = 0.f;
     if (pv) {
       const float* pp = pr + ((long)y * p.wp + x) * NM + j * 8;
-      v0 = *reinterpret_cast<const float4*>(pp); v1 = *reinterpret_cast<const float4*>(pp + 4);
+      v0 = ld4(pp); v1 = ld4(pp + 4);
       t[cg] = tg[(long)(y * p.ry) * p.S + x * p.rx];
     }
     pb[cg][0] = v0.x; pb[cg][1] = v0.y; pb[cg][2] = v0.z; pb[cg][3] = v0.w; pb[cg][4] = v1.x; pb[cg][5] = v1.y; pb[cg][6] = v1.z; pb[cg][7] = v1.w;
@@ -383,7 +380,7 @@ __global__ __launch_bounds__(256) void ml_dprotos_kernel(const MaskLossP p, int 
         // acc[r] = logit of positive 4 j + r at this lane's pixel of row cg
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float rr = (in[cg] && rvalid[r]) ? kg * (sigmoidf_(acc[r]) - t[cg]) : 0.f;
+          const float rr = (in[cg] && rvalid[r]) ? kg * (sigmoid(acc[r]) - t[cg]) : 0.f;
 #pragma unroll
           for (int mt = 0; mt < 2; ++mt) accp[cg][mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a3[mt][r], rr, accp[cg][mt], 0, 0, 0);
         }
@@ -404,22 +401,20 @@ __global__ __launch_bounds__(256) void ml_dprotos_kernel(const MaskLossP p, int 
 }
 
 __global__ __launch_bounds__(256) void ml_finalize_kernel(const MaskLossP p) {
-  __shared__ float red[4];
+  __shared__ float red[4][1];
   const int A = p.l.A;
-  float s = 0.f;
+  float s[1] = {0.f};
   for (int n = 0; n < p.l.N; ++n) {
     int k = 0;
     for (int g = p.l.gt_off[n]; g < min(p.l.gt_off[n + 1], p.G); ++g) k += p.cnt[g];
     const float* lp = p.loss_pos + (long)n * A;
-    for (int i = threadIdx.x; i < k; i += 256) s += lp[i];
+    for (int i = threadIdx.x; i < k; i += 256) s[0] += lp[i];
   }
-  const float r = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = r;
-  __syncthreads();
+  block_sum_f32<1>(s, red);
   if (threadIdx.x == 0) {
     const int np = *p.n_pos;
     const float norm = np > 0 ? (float)np : (float)p.l.N;
-    p.out[0] = ((red[0] + red[1]) + (red[2] + red[3])) / norm;
+    p.out[0] = s[0] / norm;
     p.out[1] = (float)np;
   }
 }
@@ -448,25 +443,15 @@ static int run_mask_loss(const mtbt_mask_loss_args* a, const int32_t* assigned, 
   if (S <= 0 || (float)S != a->img_size || S % a->hp || S % a->wp) return MTBT_EINVAL;
   if (a->dprotos_dtype != MTBT_F32 && a->dprotos_dtype != MTBT_BF16 && a->dprotos_dtype != MTBT_F16) return MTBT_EINVAL;
   MaskLossP p;
-  long A = 0;
-  for (int l = 0; l < 3; ++l) {
-    p.l.off[l] = (int)A;
-    if (l < a->n_levels) {
-      if (a->h[l] <= 0 || a->w[l] <= 0) return MTBT_EINVAL;
-      if (!by_assignment && (!a->map[l] || a->map_pixel_stride[l] < 4 * a->reg_max)) return MTBT_EINVAL;
-      p.l.map[l] = by_assignment ? nullptr : a->map[l]; p.l.h[l] = a->h[l]; p.l.w[l] = a->w[l]; p.l.ld[l] = a->map_pixel_stride[l];
-      p.l.stride[l] = a->img_size / (float)a->w[l];
-      A += (long)a->h[l] * a->w[l];
-    } else { p.l.map[l] = nullptr; p.l.h[l] = p.l.w[l] = 1; p.l.ld[l] = 0; p.l.stride[l] = 0.f; }
-  }
+  if (int rc = fill_levels(a, by_assignment ? 0 : 4 * a->reg_max, p.l)) return rc;
+  const long A = p.l.A;
   const long NA = (long)a->N * A;
   if (NA > 0x7fffffffL / NM || a->n_gt > NA || a->N > 65535) return MTBT_EINVAL;
   if (a->workspace_bytes < mtbt_mask_loss_workspace_bytes(a->N, (int)A, a->hp, a->wp, a->nm)) return MTBT_EINVAL;
   if (!aligned16(a->gt_xyxy) || !aligned16(a->protos) || !aligned16(a->workspace) || (a->d_mc && !aligned16(a->d_mc)) ||
       (a->d_protos && !aligned16(a->d_protos)))
     return MTBT_EALIGN;
-  p.l.off[3] = (int)A;
-  p.l.n_levels = a->n_levels; p.l.N = a->N; p.l.A = (int)A; p.l.nc = 0; p.l.reg_max = a->reg_max;
+  p.l.N = a->N; p.l.nc = 0; p.l.reg_max = a->reg_max;
   p.l.gt_xyxy = a->gt_xyxy; p.l.gt_cls = nullptr; p.l.gt_off = a->gt_off;
   p.l.iou_thresh = a->iou_thresh; p.l.smoothing = 0.f; p.l.training = 0; p.l.partial = nullptr;
   p.mc = a->mc; p.mbs = a->mc_batch_stride; p.mas = a->mc_anchor_stride; p.mcs = a->mc_channel_stride;

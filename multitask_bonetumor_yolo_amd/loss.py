@@ -43,22 +43,47 @@ def group_gt_boxes(gt_boxes: torch.Tensor, n_images: int, img_size: float):
     return xyxy.contiguous(), g[:, 1].int().contiguous(), off
 
 
+def _fill_levels(a, maps: Sequence[torch.Tensor], *, reg_max: int, img_size: float, read_maps: bool = True):
+    """The fields every loss argument block starts with (`L.LossArgs`, `L.MaskLossArgs`, `L.TalLossArgs`): map / h / w / map_pixel_stride
+    from the raw Detect maps as NHWC rows, n_levels, N, reg_max, img_size.  -> (the tensors `a` points into: keep them alive until the
+    launch is issued; the anchor count A).  `read_maps=False` fills the shapes only and leaves the map pointers null: what an entry
+    point that reads no map takes."""
+    keep = []
+    for i, m in enumerate(maps):
+        a.h[i], a.w[i] = m.shape[2], m.shape[3]
+        if read_maps:
+            t, ld = _nhwc_rows(m.detach())
+            keep.append(t)
+            a.map[i], a.map_pixel_stride[i] = t.data_ptr(), ld
+    a.n_levels, a.N, a.reg_max, a.img_size = len(maps), maps[0].shape[0], reg_max, float(img_size)
+    return keep, sum(m.shape[2] * m.shape[3] for m in maps)
+
+
+def _map_grad_buffers(who: str, det_maps: Sequence[torch.Tensor], no: int, grad_out, zero: bool = False):
+    """The gradient with respect to the Detect maps goes into one contiguous fp32 NHWC [B, h, w, no] buffer per map: `grad_out`'s
+    (a training plan's input buffers, validated here) or fresh ones (zeroed with `zero`, for a launch that adds to them).
+    -> (the buffers, their [B, no, h, w] views)."""
+    B, dev = det_maps[0].shape[0], det_maps[0].device
+    if grad_out is not None:
+        bufs = list(grad_out)
+        if len(bufs) != len(det_maps) or any(t.dtype != torch.float32 or t.numel() != B * m.shape[2] * m.shape[3] * no or not t.is_contiguous()
+                                             for t, m in zip(bufs, det_maps)):
+            raise ValueError(f"{who}: grad_out must hold one contiguous fp32 [B, h, w, no] buffer per map")
+    else:
+        bufs = [(torch.zeros if zero else torch.empty)(B, m.shape[2], m.shape[3], no, dtype=torch.float32, device=dev) for m in det_maps]
+    return bufs, [t.view(B, m.shape[2], m.shape[3], no).permute(0, 3, 1, 2) for t, m in zip(bufs, det_maps)]
+
+
 def det_loss_args(det_maps: Sequence[torch.Tensor], gt_boxes: torch.Tensor, *, img_size: float, nc_det: int, reg_max: int = 16,
                   iou_match_thresh: float = 0.5):
     """The detection fields of the loss's argument block (`L.LossArgs`): the raw Detect maps as NHWC rows, the GT rows grouped by
     image (`group_gt_boxes`), nc, reg_max, img_size and the match threshold.  -> (args, tensors the args point into: keep them alive
     until the launch is issued).  Shared by `multitask_loss` and `metrics.DetectionConfusionMatrix`, so that both decode and match the
     same anchors."""
-    dev = det_maps[0].device
-    B = det_maps[0].shape[0]
     a = L.LossArgs()
-    keep = []
-    for i, m in enumerate(det_maps):
-        t, ld = _nhwc_rows(m)
-        keep.append(t)
-        a.map[i], a.h[i], a.w[i], a.map_pixel_stride[i] = t.data_ptr(), m.shape[2], m.shape[3], ld
-    a.n_levels, a.N, a.nc, a.reg_max, a.img_size = len(det_maps), B, nc_det, reg_max, float(img_size)
-    xyxy, gcls, off = group_gt_boxes(gt_boxes.to(dev), B, float(img_size))
+    keep, _ = _fill_levels(a, det_maps, reg_max=reg_max, img_size=img_size)
+    a.nc = nc_det
+    xyxy, gcls, off = group_gt_boxes(gt_boxes.to(det_maps[0].device), a.N, float(img_size))
     keep += [xyxy, gcls, off]
     a.gt_xyxy, a.gt_cls, a.gt_off = xyxy.data_ptr(), gcls.data_ptr(), off.data_ptr()
     a.iou_thresh = float(iou_match_thresh)
@@ -93,8 +118,7 @@ def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_l
     ig = gt_cls.to(dev).long().contiguous()
     a.img_logits, a.img_gt, a.n_img_classes = il.data_ptr(), ig.data_ptr(), il.shape[1]
     a.w_seg, a.w_box, a.w_dfl, a.w_cls, a.w_img = (float(v) for v in weights)
-    nbytes = lib.mtbt_loss_workspace_bytes(B, A, seg_logits.numel())
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    ws, nbytes = L.workspace(lib.mtbt_loss_workspace_bytes, B, A, seg_logits.numel(), device=dev, what="mtbt_loss_workspace_bytes")
     out = torch.empty(8, dtype=torch.float32, device=dev)
     a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
     L.check(lib.mtbt_multitask_loss(C.byref(a), L.stream(dev)), "mtbt_multitask_loss")
@@ -105,15 +129,14 @@ def multitask_loss(det_maps: Sequence[torch.Tensor], protos: torch.Tensor, img_l
     # gradient of the total w.r.t. the head outputs (csrc/loss.hip: det_loss_grad_kernel, seg_img_grad_kernel)
     no = 4 * reg_max + nc_det
     # grad_out = {"det_maps": [NHWC fp32 buffers], "img_logits": [B, n] fp32}: write straight into a training plan's input buffers
-    d_maps = (list(grad_out["det_maps"]) if grad_out is not None else
-              [torch.empty(m.shape[0], m.shape[2], m.shape[3], no, dtype=torch.float32, device=dev) for m in det_maps])
+    d_maps, d_views = _map_grad_buffers("multitask_loss", det_maps, no, grad_out["det_maps"] if grad_out is not None else None)
     ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in d_maps], *([None] * (3 - len(d_maps))))
     lds = (C.c_int32 * 3)(*([no] * len(d_maps)), *([0] * (3 - len(d_maps))))
     d_seg = torch.empty_like(seg_logits)
     d_img = grad_out["img_logits"] if grad_out is not None else torch.empty_like(il)
     L.check(lib.mtbt_multitask_loss_grad(C.byref(a), ptrs, lds, d_seg.data_ptr(), d_img.data_ptr(), L.stream(dev)), "mtbt_multitask_loss_grad")
     del keep
-    grads = {"det_maps": [t.permute(0, 3, 1, 2) for t in d_maps],      # [B, no, h, w] views of channels-last memory
+    grads = {"det_maps": d_views,                                      # [B, no, h, w] views of channels-last memory
              "seg_logits": d_seg.view(B, 1, img_size, img_size), "img_logits": d_img}
     return (res, grads, seg_logits.view(B, 1, img_size, img_size)) if want_seg_logits else (res, grads)
 
@@ -166,13 +189,8 @@ def instance_mask_loss(box_maps: Sequence[torch.Tensor], mc: torch.Tensor, proto
             raise ValueError(f"instance_mask_loss: assigned must be an int32 [B, A] = {(B, A)} tensor, not {assigned.dtype} {tuple(assigned.shape)}")
         assigned = assigned.contiguous()
         keep.append(assigned)
-    for i, m in enumerate(box_maps):
-        a.h[i], a.w[i] = m.shape[2], m.shape[3]
-        if assigned is None:
-            t, ld = _nhwc_rows(m)
-            keep.append(t)
-            a.map[i], a.map_pixel_stride[i] = t.data_ptr(), ld
-    a.n_levels, a.N, a.reg_max, a.img_size, a.iou_thresh = len(box_maps), B, reg_max, float(img_size), float(iou_match_thresh)
+    keep += _fill_levels(a, box_maps, reg_max=reg_max, img_size=img_size, read_maps=assigned is None)[0]
+    a.iou_thresh = float(iou_match_thresh)
     xyxy, off = group_gt_rows(gt_boxes.to(dev), B, float(img_size))
     a.n_gt, a.gt_xyxy, a.gt_off = int(gt_boxes.shape[0]), xyxy.data_ptr(), off.data_ptr()
     mcf = mc.detach()
@@ -211,8 +229,7 @@ def instance_mask_loss(box_maps: Sequence[torch.Tensor], mc: torch.Tensor, proto
         a.d_mc, a.d_protos, a.dprotos_dtype = d_mc.data_ptr(), d_pr.data_ptr(), _CODE_OF[d_pr.dtype]
         a.accumulate_dmc = a.accumulate_dprotos = int(accumulate)
         grads = {"mc": d_mc.view(B, A, nm), "protos": d_pr.view(B, hp, wp, nm).permute(0, 3, 1, 2)}
-    nbytes = lib.mtbt_mask_loss_workspace_bytes(B, A, hp, wp, nm)
-    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
+    ws, nbytes = L.workspace(lib.mtbt_mask_loss_workspace_bytes, B, A, hp, wp, nm, device=dev, what="mtbt_mask_loss_workspace_bytes")
     out = torch.empty(2, dtype=torch.float32, device=dev)
     a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
     if assigned is None:
@@ -387,34 +404,21 @@ def task_aligned_det_loss(det_maps: Sequence[torch.Tensor], gt_boxes: torch.Tens
     dev = det_maps[0].device
     B = det_maps[0].shape[0]
     no = 4 * reg_max + nc_det
-    A = sum(m.shape[2] * m.shape[3] for m in det_maps)
-    a = L.TalLossArgs()
-    keep = []
     for i, m in enumerate(det_maps):
         if m.shape[1] != no:
             raise ValueError(f"task_aligned_det_loss: map {i} has {m.shape[1]} channels, expected 4 * reg_max + nc_det = {no}")
-        t, ld = _nhwc_rows(m.detach())
-        keep.append(t)
-        a.map[i], a.h[i], a.w[i], a.map_pixel_stride[i] = t.data_ptr(), m.shape[2], m.shape[3], ld
-    a.n_levels, a.N, a.nc, a.reg_max, a.img_size = len(det_maps), B, nc_det, reg_max, float(img_size)
+    a = L.TalLossArgs()
+    keep, A = _fill_levels(a, det_maps, reg_max=reg_max, img_size=img_size)
+    a.nc = nc_det
     xyxy, gcls, off = group_gt_rows_cls(gt_boxes.to(dev), B, float(img_size))
     keep += [xyxy, gcls, off]
     G = int(gt_boxes.shape[0])
     a.n_gt, a.gt_xyxy, a.gt_cls, a.gt_off = G, xyxy.data_ptr(), gcls.data_ptr(), off.data_ptr()
     a.topk, a.alpha, a.beta = int(topk), float(alpha), float(beta)
     a.w_box, a.w_dfl, a.w_cls = (float(v) for v in weights)
-    d_maps = None
+    d_views = None
     if with_grads or grad_out is not None:
-        if grad_out is not None:
-            d_maps = list(grad_out)
-            for t, m in zip(d_maps, det_maps):
-                if t.dtype != torch.float32 or t.numel() != B * m.shape[2] * m.shape[3] * no or not t.is_contiguous():
-                    raise ValueError("task_aligned_det_loss: grad_out must hold one contiguous fp32 [B, h, w, no] buffer per map")
-            if len(d_maps) != len(det_maps):
-                raise ValueError("task_aligned_det_loss: grad_out must hold one buffer per map")
-        else:
-            mk = torch.zeros if accumulate else torch.empty
-            d_maps = [mk(B, m.shape[2], m.shape[3], no, dtype=torch.float32, device=dev) for m in det_maps]
+        d_maps, d_views = _map_grad_buffers("task_aligned_det_loss", det_maps, no, grad_out, zero=accumulate)
         for i, t in enumerate(d_maps):
             a.d_map[i], a.d_map_pixel_stride[i] = t.data_ptr(), no
         a.accumulate = int(accumulate)
@@ -423,15 +427,14 @@ def task_aligned_det_loss(det_maps: Sequence[torch.Tensor], gt_boxes: torch.Tens
         assigned = torch.empty(B, A, dtype=torch.int32, device=dev)
         tscore = torch.empty(B, A, dtype=torch.float32, device=dev)
         a.assigned, a.target_score = assigned.data_ptr(), tscore.data_ptr()
-    nbytes = lib.mtbt_tal_loss_workspace_bytes(B, A, G)
-    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.int32, device=dev)
+    ws, nbytes = L.workspace(lib.mtbt_tal_loss_workspace_bytes, B, A, G, device=dev, what="mtbt_tal_loss_workspace_bytes")
     out = torch.empty(8, dtype=torch.float32, device=dev)
     a.workspace, a.workspace_bytes, a.out = ws.data_ptr(), nbytes, out.data_ptr()
     L.check(lib.mtbt_tal_det_loss(C.byref(a), L.stream(dev)), "mtbt_tal_det_loss")
     del keep
     res = [tuple(out[i] for i in range(5))]
-    if d_maps is not None:
-        res.append([t.view(B, m.shape[2], m.shape[3], no).permute(0, 3, 1, 2) for t, m in zip(d_maps, det_maps)])
+    if d_views is not None:
+        res.append(d_views)
     if want_assignment:
         res += [assigned, tscore]
     return res[0] if len(res) == 1 else tuple(res)

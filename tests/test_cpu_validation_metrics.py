@@ -52,6 +52,70 @@ def test_det_confusion_rejects_bad_arguments_without_launching(lib, field, value
     assert lib.mtbt_det_confusion(C.byref(a), 4096, 4096, None) == -1
 
 
+# ---- the level table every loss entry point builds with one function (csrc/loss_match.h, fill_levels) --------------------------------
+def _loss_args():
+    a = _det_args()
+    a.img_logits = a.img_gt = a.out = a.workspace = 4096
+    a.n_img_classes, a.workspace_bytes = 2, 1 << 40
+    return a
+
+
+def _tal_args():
+    a = L.TalLossArgs()
+    a.n_levels, a.N, a.nc, a.reg_max, a.img_size, a.n_gt, a.topk = 1, 2, 2, 16, 640.0, 1, 10
+    a.map[0], a.h[0], a.w[0], a.map_pixel_stride[0] = 4096, 20, 20, 66
+    a.gt_xyxy = a.gt_cls = a.gt_off = a.out = a.workspace = 4096
+    a.workspace_bytes = 1 << 40
+    return a
+
+
+def _mask_args():
+    a = L.MaskLossArgs()
+    a.n_levels, a.N, a.reg_max, a.img_size, a.iou_thresh, a.n_gt = 1, 2, 16, 640.0, 0.5, 1
+    a.map[0], a.h[0], a.w[0], a.map_pixel_stride[0] = 4096, 20, 20, 66
+    a.gt_xyxy = a.gt_off = a.mc = a.protos = a.gt_masks = a.workspace = a.out = 4096
+    a.mc_batch_stride, a.mc_anchor_stride, a.mc_channel_stride = 400 * 32, 32, 1
+    a.hp, a.wp, a.nm, a.weight, a.workspace_bytes = 160, 160, 32, 1.0, 1 << 40
+    return a
+
+
+def _grad_maps():
+    return (C.c_void_p * 3)(4096, None, None), (C.c_int32 * 3)(66, 0, 0)
+
+
+# (arguments with one valid level, the call on them, the narrowest pixel stride the entry point accepts: 0 = it reads no map)
+LEVEL_USERS = {
+    "multitask_loss": (_loss_args, lambda lib, a: lib.mtbt_multitask_loss(C.byref(a), None), 66),
+    "multitask_loss_grad": (_loss_args, lambda lib, a: lib.mtbt_multitask_loss_grad(C.byref(a), *_grad_maps(), 4096, 4096, None), 66),
+    "det_confusion": (_det_args, lambda lib, a: lib.mtbt_det_confusion(C.byref(a), 4096, 4096, None), 66),
+    "tal_det_loss": (_tal_args, lambda lib, a: lib.mtbt_tal_det_loss(C.byref(a), None), 66),
+    "instance_mask_loss": (_mask_args, lambda lib, a: lib.mtbt_instance_mask_loss(C.byref(a), None), 64),
+    "instance_mask_loss_assigned": (_mask_args, lambda lib, a: lib.mtbt_instance_mask_loss_assigned(C.byref(a), 4096, None), 0),
+}
+BAD_LEVELS = ["n_levels=0", "n_levels=4", "h=0", "w=0", "narrow_stride", "null_map", "hw_above_int_max"]
+# a narrow stride and a null map are no errors of an entry point that reads no map: those rows do not exist for it
+LEVEL_CASES = [(u, b) for u, (_, _, min_ld) in LEVEL_USERS.items() for b in BAD_LEVELS if min_ld or b not in ("narrow_stride", "null_map")]
+
+
+@pytest.mark.parametrize("user,bad", LEVEL_CASES)
+def test_every_loss_entry_point_rejects_bad_level_fields_without_launching(lib, user, bad):
+    """One table of bad level fields against all the entry points that fill their level table with `fill_levels`: MTBT_EINVAL before any
+    launch (the pointers are dummies).  46341 * 46341 anchors on one level exceed INT_MAX: the sum is taken in 64 bits and refused."""
+    make, call, min_ld = LEVEL_USERS[user]
+    a = make()
+    if bad.startswith("n_levels"):
+        a.n_levels = int(bad[-1])
+    elif bad in ("h=0", "w=0"):
+        setattr(a, bad[0], (C.c_int32 * 3)(0, 0, 0))
+    elif bad == "narrow_stride":
+        a.map_pixel_stride[0] = min_ld - 1
+    elif bad == "null_map":
+        a.map[0] = None
+    else:
+        a.h[0] = a.w[0] = 46341
+    assert call(lib, a) == -1
+
+
 @pytest.mark.parametrize("args", [(None, 4096, 8, 2, 4096, 4096), (4096, None, 8, 2, 4096, 4096), (4096, 4096, 0, 2, 4096, 4096),
                                   (4096, 4096, 8, 0, 4096, 4096), (4096, 4096, 8, L.CONFUSION_MAX_NC + 1, 4096, 4096),
                                   (4096, 4096, 8, 2, None, 4096), (4096, 4096, 8, 2, 4096, None)])
