@@ -69,148 +69,31 @@ __device__ __forceinline__ float4 gt_box(const float* r, int fmt, float S) {
                      clamp_s((cy + h / 2.f) * S, S));
 }
 
-__global__ __launch_bounds__(NT) void box_eval_kernel(const mtbt_box_eval_args p) {
-  __shared__ float4 dbox[CAP];
-  __shared__ int dkey[CAP], dlab[CAP], order[CAP];
-  __shared__ unsigned mword[CAP], iword[CAP];
-  __shared__ float4 gbox[CAP];
-  __shared__ int gcls[CAP], gign[CAP];
-  __shared__ int wcnt[NW];
-
-  const int b = blockIdx.x, a = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = p.K, M = p.M, fmt = p.gt_format;
-  const float S = p.img_size;
-
-  // every GT row's area-range set, each row written by exactly one workgroup of the grid
-  for (long g = (long)(b * NA + a) * NT + tid; g < M; g += (long)p.B * NA * NT) {
+// a pair = (detection box, GT box), both staged in LDS; the IoU is recomputed in fp64 per pair (no D x G matrix)
+struct BoxPairs {
+  using Args = mtbt_box_eval_args;
+  struct Lds { float4 dbox[CAP], gbox[CAP]; };
+  const Args& p;
+  Lds& s;
+  __device__ bool gt_in_batch(long g, double& area) const {
     const float* r = p.gt + g * 6;
     const float bi = r[0];
-    unsigned bits = 0;
-    if (bi >= 0.f && bi < (float)p.B && bi == truncf(bi)) {
-      const double area = box_area(gt_box(r, fmt, S));
-#pragma unroll
-      for (int q = 0; q < NA; ++q) bits |= in_area(area, q) ? 1u << q : 0u;
-    }
-    p.gt_area[g] = bits;
+    if (!(bi >= 0.f && bi < (float)p.B && bi == truncf(bi))) return false;
+    area = box_area(gt_box(r, p.gt_format, p.img_size));
+    return true;
   }
-
-  int n = K;
-  if (p.counts) {
-    n = p.counts[b];
-    n = n < 0 ? 0 : (n > K ? K : n);
+  __device__ void load_det(int i, long at) { s.dbox[i] = reinterpret_cast<const float4*>(p.boxes)[at]; }
+  __device__ bool gt_of(int g, int b) const { return p.gt[(long)g * 6] == (float)b; }
+  __device__ double load_gt(int g, int pos, int& cls) {
+    const float* r = p.gt + (long)g * 6;
+    const float4 box = gt_box(r, p.gt_format, p.img_size);
+    s.gbox[pos] = box;
+    cls = (int)(long long)r[1];
+    return box_area(box);
   }
-  const long row = (long)b * K;
-  if (tid < n) {
-    dbox[tid] = reinterpret_cast<const float4*>(p.boxes)[row + tid];
-    dkey[tid] = score_key(p.scores[row + tid]);
-    dlab[tid] = (int)p.labels[row + tid];
-    mword[tid] = 0u;
-    iword[tid] = 0u;
-  }
-  __syncthreads();   // the rank loop reads every slot; the GT loop below has barriers only when M > 0
-
-  // the image's GT rows, compacted in row order (ballot prefix within a wave, wave counts across the workgroup)
-  int ng = 0;
-  for (int base = 0; base < M; base += NT) {
-    const int g = base + tid;
-    bool mine = false;
-    float4 box = make_float4(0.f, 0.f, 0.f, 0.f);
-    int cls = 0;
-    if (g < M) {
-      const float* r = p.gt + (long)g * 6;
-      mine = r[0] == (float)b;
-      if (mine) {
-        box = gt_box(r, fmt, S);
-        cls = (int)(long long)r[1];
-      }
-    }
-    const unsigned long long bal = __ballot(mine);
-    if (lane == 0) wcnt[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      off += w < wave ? wcnt[w] : 0;
-      tot += wcnt[w];
-    }
-    const int pos = ng + off + __popcll(bal & ((1ull << lane) - 1ull));
-    if (mine && pos < CAP) {
-      gbox[pos] = box;
-      gcls[pos] = cls;
-      gign[pos] = in_area(box_area(box), a) ? 0 : 1;
-    }
-    ng += tot;
-    __syncthreads();
-  }
-
-  if (ng > CAP) {   // uniform over the workgroup: the image is reported, its detections are written as invalid
-    if (tid == 0) p.status[0] = 1;
-    if (tid < K) {
-      if (a == 0) p.rank[row + tid] = -1;
-      p.match[(row + tid) * NA + a] = 0u;
-      p.ignore[(row + tid) * NA + a] = 0u;
-    }
-    return;
-  }
-
-  // rank within (image, class) and position in the image's global score order
-  if (tid < n) {
-    const int ki = dkey[tid], li = dlab[tid];
-    int pos = 0, rk = 0;
-    for (int j = 0; j < n; ++j) {
-      const int kj = dkey[j];
-      const bool before = kj > ki || (kj == ki && j < tid);
-      pos += before;
-      rk += (before && dlab[j] == li) ? 1 : 0;
-    }
-    const bool kept = rk < p.max_det;
-    order[pos] = kept ? tid : -1;
-    if (a == 0) p.rank[row + tid] = kept ? rk : -1;
-  } else if (tid < K && a == 0) {
-    p.rank[row + tid] = -1;
-  }
-  __syncthreads();
-
-  const int nchunk = (ng + 63) >> 6;   // <= 16 (ng <= CAP)
-  for (int t = wave; t < p.T; t += NW) {
-    const double lim = fmin(p.iou_thresholds[t], 1.0 - 1e-10);
-    unsigned used = 0u;   // bit c: GT box c * 64 + lane is matched
-    for (int q = 0; q < n; ++q) {
-      const int i = order[q];
-      if (i < 0) continue;
-      const float4 d = dbox[i];
-      const int lab = dlab[i];
-      double vn = -INFINITY, vi = -INFINITY;
-      int jn = -1, ji = -1;
-      for (int c = 0; c < nchunk; ++c) {
-        const int j = (c << 6) + lane;
-        if (j < ng && gcls[j] == lab && !((used >> c) & 1u)) {
-          const double v = box_iou(d, gbox[j]);
-          if (v >= lim) {
-            if (gign[j]) {
-              if (v >= vi) { vi = v; ji = j; }
-            } else if (v >= vn) {
-              vn = v; jn = j;
-            }
-          }
-        }
-      }
-      wave_argmax(vn, jn);
-      wave_argmax(vi, ji);
-      const int m = jn >= 0 ? jn : ji;
-      if (m >= 0 && (m & 63) == lane) used |= 1u << (m >> 6);
-      if (lane == 0) {
-        if (m >= 0) atomicOr(&mword[i], 1u << t);
-        if (m >= 0 ? jn < 0 : !in_area(box_area(d), a)) atomicOr(&iword[i], 1u << t);
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < K) {
-    p.match[(row + tid) * NA + a] = tid < n ? mword[tid] : 0u;
-    p.ignore[(row + tid) * NA + a] = tid < n ? iword[tid] : 0u;
-  }
-}
+  __device__ double iou(int i, int j) const { return box_iou(s.dbox[i], s.gbox[j]); }
+  __device__ double det_area(int i) const { return box_area(s.dbox[i]); }
+};
 
 template <typename T> bool aligned_to(const T* ptr) { return (reinterpret_cast<uintptr_t>(ptr) % sizeof(T)) == 0; }
 
@@ -228,7 +111,7 @@ extern "C" int mtbt_box_eval(const mtbt_box_eval_args* args, void* stream) {
       !aligned_to(p.rank) || !aligned_to(p.match) || !aligned_to(p.ignore) || !aligned_to(p.gt_area) || !aligned_to(p.status))
     return MTBT_EALIGN;
   if (p.B == 0) return MTBT_OK;
-  hipLaunchKernelGGL(box_eval_kernel, dim3((unsigned)p.B, NA), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL(coco_match_kernel<BoxPairs>, dim3((unsigned)p.B, NA), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), p);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }

@@ -2,8 +2,9 @@
 // mtbt_fuse_detections.  The arithmetic is the project's own definition (include/mtbt_hip.h; tests/fuse_reference.py restates it in
 // numpy) and the results are bit-exact restatements of it: no FMA contraction, IEEE division, stable ordering, no floating-point atomics.
 #include "common.h"
+#include "det_order.h"
 
-// No FMA contraction in this file (built with -ffp-contract=off, see build.py), as in postprocess.hip.
+// No FMA contraction in this file (built with -ffp-contract=off, see build.py and det_order.h).
 
 namespace {
 
@@ -20,15 +21,9 @@ struct FuseP {
   int orient[MTBT_FUSE_MAX_SOURCES];
   int M, K, top_k, C, P2, acc_in_lds;
   float S, iou_thr, skip_thr, wsum;
-  float* out_boxes;
-  float* out_scores;
-  long long* out_labels;
+  RowOut out;
   int* out_counts;
   int* n_clusters;
-  int* n_members;
-  int* lead_source;
-  int* lead_slot;
-  int* lead_anchor;
   int* member_slot;   // [N, C] or nullptr: the cluster index during the greedy pass, the output row after the write-out
   char* ws;
   long ws_per_image;
@@ -40,44 +35,12 @@ struct Acc {
   int n, lead, pad;
 };
 
-__device__ __forceinline__ unsigned orderable(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// iou_gt's arithmetic of postprocess.hip (torchvision nms_kernel.cpp), i = the cluster's fused box, j = the candidate
-__device__ __forceinline__ float overlap(const float4 bi, const float4 bj) {
-  const float iarea = __fmul_rn(__fsub_rn(bi.z, bi.x), __fsub_rn(bi.w, bi.y));
-  const float jarea = __fmul_rn(__fsub_rn(bj.z, bj.x), __fsub_rn(bj.w, bj.y));
-  const float xx1 = fmaxf(bi.x, bj.x), yy1 = fmaxf(bi.y, bj.y);
-  const float xx2 = fminf(bi.z, bj.z), yy2 = fminf(bi.w, bj.w);
-  const float w = fmaxf(0.f, __fsub_rn(xx2, xx1)), h = fmaxf(0.f, __fsub_rn(yy2, yy1));
-  const float inter = __fmul_rn(w, h);
-  return __fdiv_rn(inter, __fsub_rn(__fadd_rn(iarea, jarea), inter));
-}
-
-// ascending bitonic sort of keys[0, P), P a power of two, whole workgroup
-__device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int P, int tid) {
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (P >> 1); t += FUSE_NT) {
-        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int hi = lo | j;
-        const bool up = (lo & k) == 0;
-        const unsigned long long x = keys[lo], y = keys[hi];
-        if ((x > y) == up) { keys[lo] = y; keys[hi] = x; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
 __device__ __forceinline__ float cluster_score(const Acc& a, int M, float wsum) {
   return __fdiv_rn(__fmul_rn(__fdiv_rn(a.ss, (float)a.n), (float)min(a.n, M)), wsum);
 }
 
 // One 256-thread workgroup per image.
-//  1. candidates: key[c] = ~orderable(s) << 32 | c for every kept (m, k), c = m K + k; bitonic sort == stable descending s, ascending c
+//  1. candidates: det_order.h's key of (s, c) for every kept (m, k), c = m K + k; its sort == stable descending s, ascending c
 //  2. the sorted candidates (un-oriented box, s, label, c) go to the workspace
 //  3. greedy clustering by wave 0: 64 sorted candidates per step live in registers (lane = candidate) and are broadcast one at a time;
 //     each lane scans clusters lane, lane + 64, ... in LDS, a butterfly (value, index) arg-max picks the winner, lane 0 applies the update.
@@ -108,28 +71,14 @@ __global__ __launch_bounds__(FUSE_NT) void fuse_kernel(const FuseP p) {
   if (mslot)
     for (int c = tid; c < C; c += FUSE_NT) mslot[c] = -1;
   __syncthreads();
-  int mine = 0;
-  for (int c = tid; c < p.P2; c += FUSE_NT) {
-    unsigned long long key = ~0ull;
-    if (c < C) {
-      const int m = c / K, k = c - m * K;
-      if (k < min(p.counts[m][n], K)) {
-        const float s = __fmul_rn(p.scores[m][(long)n * K + k], p.weight[m]);
-        if (s > p.skip_thr) { key = ((unsigned long long)(~orderable(s)) << 32) | (unsigned)c; ++mine; }
-      }
-    }
-    keys[c] = key;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
-  if (lane == 0 && mine) atomicAdd(&s_cnt, mine);
-  __syncthreads();
-  const int nc = s_cnt;
-  bitonic_sort(keys, p.P2, tid);   // (the dropped slots carry the largest key: the nc candidates come first)
+  const int nc = sorted_candidates<FUSE_NT>(keys, p.P2, C, p.skip_thr, s_cnt, tid, [&](int c, auto listed) {
+    const int m = c / K, k = c - m * K;
+    if (k < min(p.counts[m][n], K)) listed(__fmul_rn(p.scores[m][(long)n * K + k], p.weight[m]));
+  });
 
   // ---- 2. sorted candidates, un-oriented ----
   for (int i = tid; i < nc; i += FUSE_NT) {
-    const int c = (int)(keys[i] & 0xffffffffu);
+    const int c = key_index(keys[i]);
     const int m = c / K, k = c - m * K;
     const long at = (long)n * K + k;
     float4 b = reinterpret_cast<const float4*>(p.boxes[m])[at];
@@ -210,43 +159,32 @@ __global__ __launch_bounds__(FUSE_NT) void fuse_kernel(const FuseP p) {
 
   // ---- 4. cluster order and write-out ----
   const int ncl = s_ncl;
-  int Pc = 1;
-  while (Pc < ncl) Pc <<= 1;
-  for (int i = tid; i < Pc; i += FUSE_NT)
-    keys[i] = i < ncl ? ((unsigned long long)(~orderable(cluster_score(acc[i], M, p.wsum))) << 32) | (unsigned)i : ~0ull;
+  const int Pc = pow2ceil(ncl);
+  for (int i = tid; i < Pc; i += FUSE_NT) keys[i] = i < ncl ? order_key(cluster_score(acc[i], M, p.wsum), i) : KEY_NONE;
   __syncthreads();
-  bitonic_sort(keys, Pc, tid);
+  bitonic_sort<FUSE_NT>(keys, Pc, tid);
   const int top_k = p.top_k, nout = min(ncl, top_k);
   const long row = (long)n * top_k;
   for (int r = tid; r < top_k; r += FUSE_NT) {
-    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-    float sc = 0.f;
-    long long lab = -1;
-    int nm = 0, ls = -1, lk = -1, la = -1;
+    Row o;
     if (r < nout) {
-      const int i = (int)(keys[r] & 0xffffffffu);
+      const int i = key_index(keys[r]);
       const Acc a = acc[i];
-      b = fused[i];
-      sc = cluster_score(a, M, p.wsum);
-      lab = clabel[i];
-      nm = a.n;
-      ls = a.lead / K;
-      lk = a.lead - ls * K;
-      if (p.lead_anchor) la = p.anchors[ls][(long)n * K + lk];
+      o.box = fused[i];
+      o.score = cluster_score(a, M, p.wsum);
+      o.label = clabel[i];
+      o.members = a.n;
+      o.lead_source = a.lead / K;
+      o.lead_slot = a.lead - o.lead_source * K;
+      if (p.out.lead_anchor) o.lead_anchor = p.anchors[o.lead_source][(long)n * K + o.lead_slot];
     }
-    reinterpret_cast<float4*>(p.out_boxes)[row + r] = b;
-    p.out_scores[row + r] = sc;
-    p.out_labels[row + r] = lab;
-    p.n_members[row + r] = nm;
-    p.lead_source[row + r] = ls;
-    p.lead_slot[row + r] = lk;
-    if (p.lead_anchor) p.lead_anchor[row + r] = la;
+    store_row(p.out, row + r, o);
   }
   if (tid == 0) { p.out_counts[n] = nout; p.n_clusters[n] = ncl; }
   if (mslot) {
     // cluster index -> output row (-1 past the cut), through the sorted candidates' score array: the greedy pass was its last reader
     int* row_of = reinterpret_cast<int*>(cs);
-    for (int r = tid; r < ncl; r += FUSE_NT) row_of[(int)(keys[r] & 0xffffffffu)] = r < nout ? r : -1;
+    for (int r = tid; r < ncl; r += FUSE_NT) row_of[key_index(keys[r])] = r < nout ? r : -1;
     __threadfence_block();
     __syncthreads();
     for (int c = tid; c < C; c += FUSE_NT) {
@@ -256,7 +194,6 @@ __global__ __launch_bounds__(FUSE_NT) void fuse_kernel(const FuseP p) {
   }
 }
 
-inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 inline long fuse_ws_per_image(int C) { return ((long)C * 64 + 255) / 256 * 256; }
 
 }  // namespace
@@ -310,9 +247,8 @@ static int fuse_launch(const mtbt_box_fuse_args* a, int32_t* member_slot, bool w
   const long lds_small = (long)C * 24 + (long)p.P2 * 8, lds_acc = lds_small + (long)C * (long)sizeof(Acc);
   p.acc_in_lds = lds_acc <= FUSE_LDS_BUDGET ? 1 : 0;
   p.S = a->img_size; p.iou_thr = a->iou_thr; p.skip_thr = a->skip_thr; p.wsum = wsum;
-  p.out_boxes = a->out_boxes; p.out_scores = a->out_scores; p.out_labels = reinterpret_cast<long long*>(a->out_labels);
-  p.out_counts = a->out_counts; p.n_clusters = a->n_clusters; p.n_members = a->n_members;
-  p.lead_source = a->lead_source; p.lead_slot = a->lead_slot; p.lead_anchor = a->lead_anchor;
+  p.out = RowOut{a->out_boxes, a->out_scores, reinterpret_cast<long long*>(a->out_labels), a->n_members, a->lead_source, a->lead_slot, a->lead_anchor};
+  p.out_counts = a->out_counts; p.n_clusters = a->n_clusters;
   p.member_slot = want_members ? member_slot : nullptr;
   p.ws = reinterpret_cast<char*>(a->workspace); p.ws_per_image = per;
   const size_t lds = (size_t)(p.acc_in_lds ? lds_acc : lds_small);

@@ -10,15 +10,15 @@
 //                     the ballot of unit j and one 512-byte store writes the run.  Cropped-away pixels are not read.  Bound: the
 //                     source read (1 or 4 bytes per pixel against 1 bit written).
 // pair_counts_kernel  one 256-thread workgroup per (image, detection plane k).  The image's GT rows are compacted into LDS (ballot
-//                     prefix, as box_eval_kernel compacts GT rows), 256 candidate rows at a time, and taken in groups of 4 with
+//                     prefix, as coco_match_kernel compacts GT rows), 256 candidate rows at a time, and taken in groups of 4 with
 //                     register accumulators: thread t walks words t, t + 256, ... of the detection plane and of the group's GT
 //                     planes, popcount(d & g) per pair; wave reduction, LDS reduction, one plain store per (m, k).  Typical G is 1 - 3:
 //                     one pass over the detection plane; a further group re-reads it from L2.  The workgroup of plane 0 also counts
 //                     the GT planes' own areas.  No atomics: a workgroup owns its (b, k).  Bound: HBM on the detection planes (the
 //                     GT planes of an image are shared by its K workgroups and stay in L2).
-// mask_eval_kernel    the walk of box_eval_kernel (semantics at the top of box_eval.hip), written out here with the IoU taken from the
+// coco_match_kernel<PlanePairs>  coco_eval.h's walk (semantics at the top of box_eval.hip) with the IoU taken from the
 //                     pixel-count tables: inter / (det_area + gt_px - inter) in fp64 from exact integers, 0 for an empty union; areas
-//                     are pixel counts; GT membership, order and class from gt_image / gt_label.  Latency-bound like its model.
+//                     are pixel counts; GT membership, order and class from gt_image / gt_label.  Latency-bound like the box walk.
 #include "bitplane.h"
 #include "coco_eval.h"
 
@@ -183,137 +183,30 @@ __device__ __forceinline__ double count_iou(unsigned inter, unsigned da, unsigne
   return uni > 0.0 ? it / uni : 0.0;
 }
 
-__global__ __launch_bounds__(NT) void mask_eval_kernel(const mtbt_mask_eval_args p) {
-  __shared__ int dkey[CAP], dlab[CAP], order[CAP];
-  __shared__ unsigned darea[CAP], mword[CAP], iword[CAP];
-  __shared__ int gidx[CAP], gcls[CAP], gign[CAP];
-  __shared__ unsigned garea[CAP];
-  __shared__ int wcnt[NW];
-
-  const int b = blockIdx.x, a = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int K = p.K, M = p.M;
-
-  // every GT row's area-range set, each row written by exactly one workgroup of the grid
-  for (long g = (long)(b * NA + a) * NT + tid; g < M; g += (long)p.B * NA * NT) {
+// a pair = (detection plane, GT plane) of the pixel-count tables; LDS holds the areas and the GT rows' indices into `inter`
+struct PlanePairs {
+  using Args = mtbt_mask_eval_args;
+  struct Lds { unsigned darea[CAP], garea[CAP]; int gidx[CAP]; };
+  const Args& p;
+  Lds& s;
+  __device__ bool gt_in_batch(long g, double& area) const {
     const int gi = p.gt_image[g];
-    unsigned bits = 0;
-    if (gi >= 0 && gi < p.B) {
-      const double area = (double)p.gt_px[g];
-#pragma unroll
-      for (int q = 0; q < NA; ++q) bits |= in_area(area, q) ? 1u << q : 0u;
-    }
-    p.gt_area[g] = bits;
+    if (!(gi >= 0 && gi < p.B)) return false;
+    area = (double)p.gt_px[g];
+    return true;
   }
-
-  int n = K;
-  if (p.counts) {
-    n = p.counts[b];
-    n = n < 0 ? 0 : (n > K ? K : n);
+  __device__ void load_det(int i, long at) { s.darea[i] = p.det_area[at]; }
+  __device__ bool gt_of(int g, int b) const { return p.gt_image[g] == b; }
+  __device__ double load_gt(int g, int pos, int& cls) {
+    const unsigned px = p.gt_px[g];
+    s.gidx[pos] = g;
+    s.garea[pos] = px;
+    cls = p.gt_label[g];
+    return (double)px;
   }
-  const long row = (long)b * K;
-  if (tid < n) {
-    darea[tid] = p.det_area[row + tid];
-    dkey[tid] = score_key(p.scores[row + tid]);
-    dlab[tid] = (int)p.labels[row + tid];
-    mword[tid] = 0u;
-    iword[tid] = 0u;
-  }
-  __syncthreads();   // the rank loop reads every slot; the GT loop below has barriers only when M > 0
-
-  // the image's GT rows, compacted in row order (ballot prefix within a wave, wave counts across the workgroup)
-  int ng = 0;
-  for (int base = 0; base < M; base += NT) {
-    const int g = base + tid;
-    const bool mine = g < M && p.gt_image[g] == b;
-    const unsigned long long bal = __ballot(mine);
-    if (lane == 0) wcnt[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      off += w < wave ? wcnt[w] : 0;
-      tot += wcnt[w];
-    }
-    const int pos = ng + off + __popcll(bal & ((1ull << lane) - 1ull));
-    if (mine && pos < CAP) {
-      const unsigned px = p.gt_px[g];
-      gidx[pos] = g;
-      gcls[pos] = p.gt_label[g];
-      garea[pos] = px;
-      gign[pos] = in_area((double)px, a) ? 0 : 1;
-    }
-    ng += tot;
-    __syncthreads();
-  }
-
-  if (ng > CAP) {   // uniform over the workgroup: the image is reported, its detections are written as invalid
-    if (tid == 0) p.status[0] = 1;
-    if (tid < K) {
-      if (a == 0) p.rank[row + tid] = -1;
-      p.match[(row + tid) * NA + a] = 0u;
-      p.ignore[(row + tid) * NA + a] = 0u;
-    }
-    return;
-  }
-
-  // rank within (image, class) and position in the image's global score order
-  if (tid < n) {
-    const int ki = dkey[tid], li = dlab[tid];
-    int pos = 0, rk = 0;
-    for (int j = 0; j < n; ++j) {
-      const int kj = dkey[j];
-      const bool before = kj > ki || (kj == ki && j < tid);
-      pos += before;
-      rk += (before && dlab[j] == li) ? 1 : 0;
-    }
-    const bool kept = rk < p.max_det;
-    order[pos] = kept ? tid : -1;
-    if (a == 0) p.rank[row + tid] = kept ? rk : -1;
-  } else if (tid < K && a == 0) {
-    p.rank[row + tid] = -1;
-  }
-  __syncthreads();
-
-  const int nchunk = (ng + 63) >> 6;   // <= 16 (ng <= CAP)
-  for (int t = wave; t < p.T; t += NW) {
-    const double lim = fmin(p.iou_thresholds[t], 1.0 - 1e-10);
-    unsigned used = 0u;   // bit c: GT plane c * 64 + lane is matched
-    for (int q = 0; q < n; ++q) {
-      const int i = order[q];
-      if (i < 0) continue;
-      const unsigned da = darea[i];
-      const int lab = dlab[i];
-      double vn = -INFINITY, vi = -INFINITY;
-      int jn = -1, ji = -1;
-      for (int c = 0; c < nchunk; ++c) {
-        const int j = (c << 6) + lane;
-        if (j < ng && gcls[j] == lab && !((used >> c) & 1u)) {
-          const double v = count_iou(p.inter[(long)gidx[j] * K + i], da, garea[j]);
-          if (v >= lim) {
-            if (gign[j]) {
-              if (v >= vi) { vi = v; ji = j; }
-            } else if (v >= vn) {
-              vn = v; jn = j;
-            }
-          }
-        }
-      }
-      wave_argmax(vn, jn);
-      wave_argmax(vi, ji);
-      const int m = jn >= 0 ? jn : ji;
-      if (m >= 0 && (m & 63) == lane) used |= 1u << (m >> 6);
-      if (lane == 0) {
-        if (m >= 0) atomicOr(&mword[i], 1u << t);
-        if (m >= 0 ? jn < 0 : !in_area((double)da, a)) atomicOr(&iword[i], 1u << t);
-      }
-    }
-  }
-  __syncthreads();
-  if (tid < K) {
-    p.match[(row + tid) * NA + a] = tid < n ? mword[tid] : 0u;
-    p.ignore[(row + tid) * NA + a] = tid < n ? iword[tid] : 0u;
-  }
-}
+  __device__ double iou(int i, int j) const { return count_iou(p.inter[(long)s.gidx[j] * p.K + i], s.darea[i], s.garea[j]); }
+  __device__ double det_area(int i) const { return (double)s.darea[i]; }
+};
 
 bool plane_shape_ok(int H, int W, int pitch) { return plane_area_ok(H, W) && plane_pitch_ok(W, pitch); }
 
@@ -390,7 +283,7 @@ extern "C" int mtbt_mask_eval(const mtbt_mask_eval_args* args, void* stream) {
       !aligned_to(p.ignore) || !aligned_to(p.gt_area) || !aligned_to(p.status))
     return MTBT_EALIGN;
   if (p.B == 0) return MTBT_OK;
-  hipLaunchKernelGGL(mask_eval_kernel, dim3((unsigned)p.B, NA), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), p);
+  hipLaunchKernelGGL(coco_match_kernel<PlanePairs>, dim3((unsigned)p.B, NA), dim3(NT), 0, reinterpret_cast<hipStream_t>(stream), p);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }

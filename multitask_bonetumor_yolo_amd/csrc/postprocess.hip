@@ -2,10 +2,10 @@
 // Integer / index results (NMS) are bit-exact restatements of the reference's CPU arithmetic:
 // no FMA contraction, IEEE division, stable ordering.
 #include "common.h"
+#include "det_order.h"
 
-// No FMA contraction in this file (built with -ffp-contract=off, see build.py): the NMS suppression test and the
-// pairwise IoU must round exactly like the CPU reference (torchvision / torch eager evaluate every product and sum
-// separately).  hipcc's default contracts in the backend, and the __fmul_rn / __fadd_rn spellings are plain operators.
+// No FMA contraction in this file (built with -ffp-contract=off, see build.py and det_order.h): the NMS suppression test and
+// the pairwise IoU must round exactly like the CPU reference (torchvision / torch eager).
 
 namespace {
 
@@ -116,28 +116,11 @@ __global__ void decode_kernel(const DecodeP p) {
 //     a strictly smaller score than every one selected, so the sorted selection IS the head of the full order.  If the
 //     greedy pass runs out of selected candidates before top_k boxes are kept, the whole list is sorted and the pass redone
 //     (same result as sorting everything up front, which is what attempt 1 is).
-//  3. bitonic sort of 64-bit keys (~orderable(score) << 32 | cand index): descending score,
+//  3. bitonic sort of det_order.h's keys (score, candidate index): descending score,
 //     ascending candidate index on ties == torch's stable descending sort
 //  4. greedy pass by wave 0, 64 sorted candidates per step: each lane tests its candidate against
-//     every box kept so far, the 64x64 in-chunk dependencies are bitmasks resolved by a scalar scan
+//     every box kept so far (det_order.h's overlap), the 64x64 in-chunk dependencies are bitmasks resolved by a scalar scan
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool iou_gt(const float4 bi, const float4 bj, float thr) {
-  // torchvision nms_kernel.cpp arithmetic, i = kept (earlier) box, j = candidate
-  const float iarea = __fmul_rn(__fsub_rn(bi.z, bi.x), __fsub_rn(bi.w, bi.y));
-  const float jarea = __fmul_rn(__fsub_rn(bj.z, bj.x), __fsub_rn(bj.w, bj.y));
-  const float xx1 = fmaxf(bi.x, bj.x), yy1 = fmaxf(bi.y, bj.y);
-  const float xx2 = fminf(bi.z, bj.z), yy2 = fminf(bi.w, bj.w);
-  const float w = fmaxf(0.f, __fsub_rn(xx2, xx1)), h = fmaxf(0.f, __fsub_rn(yy2, yy1));
-  const float inter = __fmul_rn(w, h);
-  const float ovr = __fdiv_rn(inter, __fsub_rn(__fadd_rn(iarea, jarea), inter));
-  return ovr > thr;
-}
-
-__device__ __forceinline__ unsigned orderable(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 constexpr int NMS_KEPT_LDS = 1024;  // kept boxes cached in LDS; beyond that they are read back from out_boxes
 constexpr int NMS_NT = 1024, NMS_NW = NMS_NT / 64;
 constexpr int NMS_BINS = 4096;      // score histogram (aliases the kept-box cache: 16 KiB, used before the greedy pass)
@@ -252,36 +235,24 @@ __global__ __launch_bounds__(NMS_NT) void nms_kernel(const float* __restrict__ b
       const int pos = p0 + lane;
       const float v = pos < M ? sc[cand_anchor[pos]] : 0.f;
       if (attempt == 1) {
-        if (pos < M) keys[pos] = ((unsigned long long)(~orderable(v)) << 32) | (unsigned)pos;
+        if (pos < M) keys[pos] = order_key(v, pos);
       } else {
         const bool f = pos < M && nms_bin(v, b_lo, b_scale) >= sel_bin;
         const unsigned long long bal = __ballot(f);
         int base = 0;
         if (lane == 0 && bal) base = atomicAdd(&s_cnt, __popcll(bal));
         base = __shfl(base, 0, 64);
-        if (f) keys[base + __popcll(bal & below)] = ((unsigned long long)(~orderable(v)) << 32) | (unsigned)pos;   // (any slot: sorted next)
+        if (f) keys[base + __popcll(bal & below)] = order_key(v, pos);   // (any slot: sorted next)
       }
     }
-    int P = 1;
-    while (P < Ms) P <<= 1;
-    for (int i = Ms + tid; i < P; i += NMS_NT) keys[i] = ~0ull;
+    const int P = pow2ceil(Ms);
+    for (int i = Ms + tid; i < P; i += NMS_NT) keys[i] = KEY_NONE;
     __syncthreads();
-    for (int k = 2; k <= P; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int t = tid; t < (P >> 1); t += NMS_NT) {
-          const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-          const int hi = lo | j;
-          const bool up = (lo & k) == 0;
-          const unsigned long long x = keys[lo], y = keys[hi];
-          if ((x > y) == up) { keys[lo] = y; keys[hi] = x; }
-        }
-        __syncthreads();
-      }
-    }
+    bitonic_sort<NMS_NT>(keys, P, tid);
 
     // sorted, clamped boxes to workspace
     for (int i = tid; i < Ms; i += NMS_NT) {
-      const int ci = (int)(keys[i] & 0xffffffffu);
+      const int ci = key_index(keys[i]);
       float4 b = bx[cand_anchor[ci]];
       b.x = fminf(fmaxf(b.x, 0.f), clamp_max); b.y = fminf(fmaxf(b.y, 0.f), clamp_max);
       b.z = fminf(fmaxf(b.z, 0.f), clamp_max); b.w = fminf(fmaxf(b.w, 0.f), clamp_max);
@@ -313,7 +284,7 @@ __global__ __launch_bounds__(NMS_NT) void nms_kernel(const float* __restrict__ b
           kb.z = __hip_atomic_load(g + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           kb.w = __hip_atomic_load(g + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
-        if (iou_gt(kb, mine4, iou_th)) dead = true;
+        if (overlap(kb, mine4) > iou_th) dead = true;
       }
       unsigned long long supp_by = 0ull;         // bit i set: earlier chunk member i would suppress me
 #pragma unroll
@@ -321,7 +292,7 @@ __global__ __launch_bounds__(NMS_NT) void nms_kernel(const float* __restrict__ b
         const int i = wave * (64 / NMS_NW) + t;
         float4 o;
         o.x = __shfl(mine4.x, i, 64); o.y = __shfl(mine4.y, i, 64); o.z = __shfl(mine4.z, i, 64); o.w = __shfl(mine4.w, i, 64);
-        if (i < lane && iou_gt(o, mine4, iou_th)) supp_by |= 1ull << i;
+        if (i < lane && overlap(o, mine4) > iou_th) supp_by |= 1ull << i;
       }
       part_supp[wave * 64 + lane] = supp_by;
       const unsigned long long dead_mask = __ballot(dead);
@@ -343,8 +314,7 @@ __global__ __launch_bounds__(NMS_NT) void nms_kernel(const float* __restrict__ b
         const bool kept = (keepmask >> lane) & 1ull;
         const int pos = nkept + __popcll(keepmask & below);
         if (kept && pos < top_k) {
-          const unsigned long long key = keys[j];
-          const int ci = (int)(key & 0xffffffffu);
+          const int ci = key_index(keys[j]);
           const int a = cand_anchor[ci];
           ki[pos] = ci;
           ka[pos] = a;
@@ -478,7 +448,6 @@ __global__ __launch_bounds__(256) void mask_kernel(const MaskP p) {
   }
 }
 
-inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 inline long nms_ws_per_image(int A) {
   long b = (long)A * 20;
   b += (16 - b % 16) % 16;

@@ -2,9 +2,10 @@
 // project's own definition (include/mtbt_hip.h; tests/slice_reference.py restates it) and the results are bit-exact restatements of it: no
 // FMA contraction, IEEE division, stable ordering, no floating-point atomics.
 #include "common.h"
+#include "det_order.h"
 #include "tile_check.h"
 
-// No FMA contraction in this file (built with -ffp-contract=off, see build.py), as in box_fuse.hip.
+// No FMA contraction in this file (built with -ffp-contract=off, see build.py and det_order.h).
 
 namespace {
 
@@ -20,59 +21,20 @@ struct MergeP {
   const mtbt_tile* tiles;
   int n_tiles, K, top_k, metric, class_agnostic;
   float thr, skip_thr;
-  float* out_boxes;
-  float* out_scores;
-  long long* out_labels;
+  RowOut out;         // lead_source = the leader's tile
   int* out_counts;
-  int* n_members;
-  int* lead_tile;
-  int* lead_slot;
-  int* lead_anchor;
   int* member_slot;
   int* n_left;
 };
-
-__device__ __forceinline__ unsigned orderable(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// the NMS arithmetic of postprocess.hip (torchvision nms_kernel.cpp) up to the intersection; then IoU or intersection over the smaller
-__device__ __forceinline__ float overlap(const float4 bi, const float4 bj, int metric) {
-  const float iarea = __fmul_rn(__fsub_rn(bi.z, bi.x), __fsub_rn(bi.w, bi.y));
-  const float jarea = __fmul_rn(__fsub_rn(bj.z, bj.x), __fsub_rn(bj.w, bj.y));
-  const float xx1 = fmaxf(bi.x, bj.x), yy1 = fmaxf(bi.y, bj.y);
-  const float xx2 = fminf(bi.z, bj.z), yy2 = fminf(bi.w, bj.w);
-  const float w = fmaxf(0.f, __fsub_rn(xx2, xx1)), h = fmaxf(0.f, __fsub_rn(yy2, yy1));
-  const float inter = __fmul_rn(w, h);
-  const float den = metric == MTBT_MERGE_IOS ? fminf(iarea, jarea) : __fsub_rn(__fadd_rn(iarea, jarea), inter);
-  return __fdiv_rn(inter, den);
-}
 
 // clamp((v + off) / scale, 0, hi): frame_tile.h's frame_box with the tile's offset added first
 __device__ __forceinline__ float to_frame(float v, float off, float scale, float hi) {
   return fminf(fmaxf(__fdiv_rn(__fadd_rn(v, off), scale), 0.f), hi);
 }
 
-// ascending bitonic sort of keys[0, P), P a power of two, whole workgroup
-__device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int P, int tid) {
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < (P >> 1); t += MERGE_NT) {
-        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int hi = lo | j;
-        const bool up = (lo & k) == 0;
-        const unsigned long long x = keys[lo], y = keys[hi];
-        if ((x > y) == up) { keys[lo] = y; keys[hi] = x; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // One 256-thread workgroup per image.
 //  1. the image's tiles are found in the tile table (they are consecutive); member_slot of all their slots starts at -1
-//  2. keys of the candidates, bitonic sort == stable descending s, ascending c; the sorted candidates' frame boxes and labels go to LDS
+//  2. det_order.h's keys of the candidates and its sort == stable descending s, ascending c; the sorted candidates' frame boxes and labels go to LDS
 //  3. the greedy pass walks the sorted candidates: one that is still free opens a row and every thread tests its share of the later free
 //     candidates against the LEADER's own box (one barrier per row, none for an absorbed candidate)
 //  4. per row a wave reduces the union box and the member count (min / max are exact, any order), then the write-out
@@ -95,31 +57,15 @@ __global__ __launch_bounds__(MERGE_NT) void merge_kernel(const MergeP p, int Cma
   __syncthreads();
   const int t0 = min(s_t0, s_t1), T = min(s_t1 - t0, Cmax / K);   // (the host checked T K <= Cmax; the min keeps a table that differs from the host's in bounds)
   const int C = T * K;
-  int P2 = 1;
-  while (P2 < C) P2 <<= 1;
   int* mslot = p.member_slot + (long)t0 * K;
 
   // ---- 2. keys, order, frame boxes ----
-  int mine = 0;
-  for (int c = tid; c < P2; c += MERGE_NT) {
-    unsigned long long key = ~0ull;
-    if (c < C) {
-      const int t = t0 + c / K, k = c - (c / K) * K;
-      if (k < min(p.counts[t], K)) {
-        const float s = p.scores[(long)t * K + k];
-        if (s > p.skip_thr) { key = ((unsigned long long)(~orderable(s)) << 32) | (unsigned)c; ++mine; }
-      }
-    }
-    keys[c] = key;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
-  if (lane == 0 && mine) atomicAdd(&s_cnt, mine);
-  __syncthreads();
-  const int nc = s_cnt;
-  bitonic_sort(keys, P2, tid);   // (the dropped slots carry the largest key: the nc candidates come first)
+  const int nc = sorted_candidates<MERGE_NT>(keys, pow2ceil(C), C, p.skip_thr, s_cnt, tid, [&](int c, auto listed) {
+    const int t = t0 + c / K, k = c - (c / K) * K;
+    if (k < min(p.counts[t], K)) listed(p.scores[(long)t * K + k]);
+  });
   for (int i = tid; i < nc; i += MERGE_NT) {
-    const int c = (int)(keys[i] & 0xffffffffu);
+    const int c = key_index(keys[i]);
     const int t = t0 + c / K, k = c - (c / K) * K;
     const mtbt_tile& d = p.tiles[t];
     const float4 b = reinterpret_cast<const float4*>(p.boxes)[(long)t * K + k];
@@ -166,26 +112,19 @@ __global__ __launch_bounds__(MERGE_NT) void merge_kernel(const MergeP p, int Cma
       lead = min(lead, __shfl_xor(lead, o, 64));
     }
     if (lane == 0) {
-      float sc = 0.f;
-      long long lab = -1;
-      int lt = -1, lk = -1, la = -1;
+      Row o;
       if (r < rows) {
-        const int c = (int)(keys[lead] & 0xffffffffu);   // the leader is the row's first candidate in the order
-        lt = t0 + c / K;
-        lk = c - (c / K) * K;
-        sc = p.scores[(long)lt * K + lk];
-        lab = clab[lead];
-        if (p.lead_anchor) la = p.anchors[(long)lt * K + lk];
-      } else {
-        u = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int c = key_index(keys[lead]);   // the leader is the row's first candidate in the order
+        o.box = u;
+        o.members = nm;
+        o.lead_source = t0 + c / K;
+        o.lead_slot = c - (c / K) * K;
+        const long at = (long)o.lead_source * K + o.lead_slot;
+        o.score = p.scores[at];
+        o.label = clab[lead];
+        if (p.out.lead_anchor) o.lead_anchor = p.anchors[at];
       }
-      reinterpret_cast<float4*>(p.out_boxes)[row0 + r] = u;
-      p.out_scores[row0 + r] = sc;
-      p.out_labels[row0 + r] = lab;
-      p.n_members[row0 + r] = nm;
-      p.lead_tile[row0 + r] = lt;
-      p.lead_slot[row0 + r] = lk;
-      if (p.lead_anchor) p.lead_anchor[row0 + r] = la;
+      store_row(p.out, row0 + r, o);
     }
   }
   // membership: every slot of the image's tiles is written once.  keys is free after the leaders were looked up
@@ -195,7 +134,7 @@ __global__ __launch_bounds__(MERGE_NT) void merge_kernel(const MergeP p, int Cma
   __syncthreads();
   int left = 0;
   for (int i = tid; i < nc; i += MERGE_NT) {
-    row_of[(int)(keys[i] & 0xffffffffu)] = state[i];
+    row_of[key_index(keys[i])] = state[i];
     left += state[i] == FREE;
   }
 #pragma unroll
@@ -205,8 +144,6 @@ __global__ __launch_bounds__(MERGE_NT) void merge_kernel(const MergeP p, int Cma
   for (int c = tid; c < C; c += MERGE_NT) mslot[c] = row_of[c];
   if (tid == 0) { p.out_counts[n] = rows; p.n_left[n] = s_left; }
 }
-
-inline int pow2ceil(int v) { int p = 2; while (p < v) p <<= 1; return p; }   // (>= 2: the boxes behind the keys stay 16-byte aligned)
 
 }  // namespace
 
@@ -231,10 +168,9 @@ extern "C" int mtbt_merge_tiles(const mtbt_tile_merge_args* a, void* stream) {
   p.anchors = a->anchors; p.tiles = a->tiles_dev;
   p.n_tiles = a->n_tiles; p.K = a->K; p.top_k = a->top_k; p.metric = a->metric; p.class_agnostic = a->class_agnostic ? 1 : 0;
   p.thr = a->thr; p.skip_thr = a->skip_thr;
-  p.out_boxes = a->out_boxes; p.out_scores = a->out_scores; p.out_labels = reinterpret_cast<long long*>(a->out_labels);
-  p.out_counts = a->out_counts; p.n_members = a->n_members; p.lead_tile = a->lead_tile; p.lead_slot = a->lead_slot;
-  p.lead_anchor = a->lead_anchor; p.member_slot = a->member_slot; p.n_left = a->n_left;
-  const int Cmax = (Tbig > 0 ? Tbig : 1) * a->K, P2max = pow2ceil(Cmax);
+  p.out = RowOut{a->out_boxes, a->out_scores, reinterpret_cast<long long*>(a->out_labels), a->n_members, a->lead_tile, a->lead_slot, a->lead_anchor};
+  p.out_counts = a->out_counts; p.member_slot = a->member_slot; p.n_left = a->n_left;
+  const int Cmax = (Tbig > 0 ? Tbig : 1) * a->K, P2max = pow2ceil(Cmax, 2);   // (>= 2: the boxes behind the keys stay 16-byte aligned)
   const size_t lds = (size_t)P2max * 8 + (size_t)Cmax * 28;
   if (int rc = mtbt_allow_lds(merge_kernel, (int)((size_t)MTBT_FUSE_MAX_CANDIDATES * 36))) return rc;
   hipLaunchKernelGGL(merge_kernel, dim3(a->N), dim3(MERGE_NT), lds, reinterpret_cast<hipStream_t>(stream), p, Cmax, P2max);

@@ -322,6 +322,38 @@ def _det_tensors(d: dict, with_anchor: bool):
     return src
 
 
+def _row_tensors(a, N: int, top_k: int, dev, boxes: str, lead: str, with_anchor: bool) -> dict:
+    """The padded output rows that the fusion and merge kernels write, [N, top_k] each, under the caller's names for the boxes and for
+    the leader's list (`lead`: also the struct's field); their pointers go into the argument struct `a`."""
+    i32 = {"dtype": torch.int32, "device": dev}
+    o = {
+        boxes: torch.empty((N, top_k, 4), dtype=torch.float32, device=dev),
+        "scores": torch.empty((N, top_k), dtype=torch.float32, device=dev),
+        "labels": torch.empty((N, top_k), dtype=torch.int64, device=dev),
+        "counts": torch.empty((N,), **i32),
+        "n_members": torch.empty((N, top_k), **i32),
+        lead: torch.empty((N, top_k), **i32),
+        "lead_slot": torch.empty((N, top_k), **i32),
+    }
+    if with_anchor:
+        o["lead_anchor"] = torch.empty((N, top_k), **i32)
+    field = {boxes: "out_boxes", "scores": "out_scores", "labels": "out_labels", "counts": "out_counts"}
+    for key, t in o.items():
+        setattr(a, field.get(key, key), t.data_ptr())
+    return o
+
+
+def _per_source(who: str, M: int, orients, weights, codes: Optional[range] = None):
+    """`orients` / `weights` of M sources with their defaults (0 / 1), as lists of M.  With `codes` every orient must be one of them
+    (without, the library refuses a bad one)."""
+    orients = [0] * M if orients is None else [int(o) for o in orients]
+    weights = [1.0] * M if weights is None else [float(w) for w in weights]
+    if len(orients) != M or len(weights) != M or (codes is not None and any(o not in codes for o in orients)):
+        note = "" if codes is None else f" ({codes[0]}..{codes[-1]})"
+        raise ValueError(f"{who}: {len(orients)} orients{note} and {len(weights)} weights for {M} sources")
+    return orients, weights
+
+
 def _fuse_args(dets, img_size, orients, weights, iou_thr, skip_thr, top_k):
     """The checked `mtbt_box_fuse_args` of a `fuse_detections` call, its output dict (which keeps every tensor the struct points to
     alive under "_keep") and the device."""
@@ -341,10 +373,7 @@ def _fuse_args(dets, img_size, orients, weights, iou_thr, skip_thr, top_k):
                              f"{tuple(d['counts'].shape)}; source 0 has B = {B}, K = {K}")
     if K < 1 or M * K > FUSE_MAX_CANDIDATES:
         raise ValueError(f"fuse_detections: {M} sources of K = {K} slots ({FUSE_MAX_CANDIDATES} slots at most, K >= 1)")
-    orients = [0] * M if orients is None else [int(o) for o in orients]
-    weights = [1.0] * M if weights is None else [float(w) for w in weights]
-    if len(orients) != M or len(weights) != M:
-        raise ValueError(f"fuse_detections: {len(orients)} orients and {len(weights)} weights for {M} sources")
+    orients, weights = _per_source("fuse_detections", M, orients, weights)
     top_k = K if top_k is None else int(top_k)
     with_anchor = all("keep_anchor" in d for d in dets)
     a = L.BoxFuseArgs()
@@ -356,25 +385,12 @@ def _fuse_args(dets, img_size, orients, weights, iou_thr, skip_thr, top_k):
         a.boxes[m], a.scores[m], a.labels[m], a.counts[m] = (t.data_ptr() for t in src[:4])
         a.orient[m], a.weight[m] = orients[m], weights[m]
         keep.append(src)
-    o = {
-        "boxes": torch.empty((B, top_k, 4), dtype=torch.float32, device=dev),
-        "scores": torch.empty((B, top_k), dtype=torch.float32, device=dev),
-        "labels": torch.empty((B, top_k), dtype=torch.int64, device=dev),
-        "counts": torch.empty((B,), dtype=torch.int32, device=dev),
-        "n_clusters": torch.empty((B,), dtype=torch.int32, device=dev),
-        "n_members": torch.empty((B, top_k), dtype=torch.int32, device=dev),
-        "lead_source": torch.empty((B, top_k), dtype=torch.int32, device=dev),
-        "lead_slot": torch.empty((B, top_k), dtype=torch.int32, device=dev),
-    }
-    if with_anchor:
-        o["lead_anchor"] = torch.empty((B, top_k), dtype=torch.int32, device=dev)
-        a.lead_anchor = o["lead_anchor"].data_ptr()
+    o = _row_tensors(a, B, top_k, dev, "boxes", "lead_source", with_anchor)
+    o["n_clusters"] = torch.empty((B,), dtype=torch.int32, device=dev)
     ws, wsb = L.workspace(lib.mtbt_fuse_workspace_bytes, M, B, K, device=dev, what="mtbt_fuse_workspace_bytes")
     a.n_sources, a.N, a.K, a.top_k = M, B, K, top_k
     a.img_size, a.iou_thr, a.skip_thr = float(img_size), float(iou_thr), float(skip_thr)
-    a.out_boxes, a.out_scores, a.out_labels, a.out_counts = o["boxes"].data_ptr(), o["scores"].data_ptr(), o["labels"].data_ptr(), o["counts"].data_ptr()
-    a.n_clusters, a.n_members, a.lead_source, a.lead_slot = (o[k].data_ptr() for k in ("n_clusters", "n_members", "lead_source", "lead_slot"))
-    a.workspace, a.workspace_bytes = ws.data_ptr(), wsb
+    a.n_clusters, a.workspace, a.workspace_bytes = o["n_clusters"].data_ptr(), ws.data_ptr(), wsb
     o["_keep"] = (keep, ws)
     return a, o, dev
 
@@ -432,10 +448,7 @@ def vote_masks(fused: dict, sources: Sequence, orients: Optional[Sequence[int]],
     M = len(srcs)
     if len(sources) != M or any(len(s) < 5 for s in srcs):
         raise ValueError(f"vote_masks: {len(sources)} sources for a fusion of {M}, each of which must carry keep_anchor")
-    orients = [0] * M if orients is None else [int(o) for o in orients]
-    weights = [1.0] * M if weights is None else [float(w) for w in weights]
-    if len(orients) != M or len(weights) != M or any(not 0 <= o <= 7 for o in orients):
-        raise ValueError(f"vote_masks: {len(orients)} orients (0..7) and {len(weights)} weights for {M} sources")
+    orients, weights = _per_source("vote_masks", M, orients, weights, codes=range(8))
     member_slot, counts, boxes = fused["member_slot"], fused["counts"], fused["boxes"]
     _need_cuda(member_slot, "vote_masks")
     dev = member_slot.device
@@ -560,27 +573,16 @@ def merge_tiles(det: dict, tiles: Sequence[Sequence[dict]], frames, *, metric: s
     top_k = int(top_k)
     table, first, table_dev = tile_table(tiles, dev)
     src = _det_tensors(det, "keep_anchor" in det)
-    o = {
-        "boxes_frame": torch.empty((N, top_k, 4), dtype=torch.float32, device=dev),
-        "scores": torch.empty((N, top_k), dtype=torch.float32, device=dev),
-        "labels": torch.empty((N, top_k), dtype=torch.int64, device=dev),
-        "counts": torch.empty((N,), dtype=torch.int32, device=dev),
-        "n_members": torch.empty((N, top_k), dtype=torch.int32, device=dev),
-        "lead_tile": torch.empty((N, top_k), dtype=torch.int32, device=dev),
-        "lead_slot": torch.empty((N, top_k), dtype=torch.int32, device=dev),
-        "member_slot": torch.empty((NT, K), dtype=torch.int32, device=dev),
-        "n_left": torch.empty((N,), dtype=torch.int32, device=dev),
-    }
     a = L.TileMergeArgs()
+    o = _row_tensors(a, N, top_k, dev, "boxes_frame", "lead_tile", "keep_anchor" in det)
+    o["member_slot"] = torch.empty((NT, K), dtype=torch.int32, device=dev)
+    o["n_left"] = torch.empty((N,), dtype=torch.int32, device=dev)
     a.boxes, a.scores, a.labels, a.counts = (t.data_ptr() for t in src[:4])
     if "keep_anchor" in det:
-        o["lead_anchor"] = torch.empty((N, top_k), dtype=torch.int32, device=dev)
-        a.anchors, a.lead_anchor = src[4].data_ptr(), o["lead_anchor"].data_ptr()
+        a.anchors = src[4].data_ptr()
     a.tiles, a.tiles_dev, a.first = table, table_dev.data_ptr(), first
     a.N, a.n_tiles, a.K, a.top_k = N, NT, K, top_k
     a.metric, a.class_agnostic, a.thr, a.skip_thr = MERGE_METRICS[metric], int(bool(class_agnostic)), float(thr), float(skip_thr)
-    a.out_boxes, a.out_scores, a.out_labels, a.out_counts = o["boxes_frame"].data_ptr(), o["scores"].data_ptr(), o["labels"].data_ptr(), o["counts"].data_ptr()
-    a.n_members, a.lead_tile, a.lead_slot = o["n_members"].data_ptr(), o["lead_tile"].data_ptr(), o["lead_slot"].data_ptr()
     a.member_slot, a.n_left = o["member_slot"].data_ptr(), o["n_left"].data_ptr()
     with torch.cuda.device(dev):
         L.check(lib.mtbt_merge_tiles(C.byref(a), L.stream(dev)), "mtbt_merge_tiles")

@@ -16,7 +16,7 @@ import torch
 import augment_reference as AR
 import frame_reference as FR
 import slice_reference as SR
-from test_cpu_slice import A, BAND, BIT_CASES, K, MERGE_CASES, S, SEED, SHARE, SIZES, UP, inputs, merged_case
+from test_cpu_slice import A, BAND, BIT_CASES, EMPTY, K, MERGE_CASES, S, SEED, SHARE, SIZES, UP, inputs, merged_case, tiles_of
 
 pytestmark = pytest.mark.gpu
 
@@ -93,6 +93,22 @@ def test_merge_is_bit_equal(case):
     assert got["boxes"] is got["boxes_frame"] and (want["n_members"] >= 2).any() and int(want["counts"][3]) == 0
     if case in (1, 3, 4):
         assert (want["n_left"] > 0).any()
+
+
+def test_merge_with_more_candidates_than_threads():
+    """10 tiles of K = 128: 1280 slots and 2048 keys against the kernel's 256 threads, so its strided loops, its sort above 512 keys
+    and its LDS layout at a large Cmax run (the cases above have 210 slots).  400 objects per image; once uncut, once cut at 16 rows."""
+    tiles = tiles_of()
+    det = SR.tile_lists(tiles, 128, SEED, S, A=A, n_obj=400, empty=EMPTY)[0]
+    listed = [int((det["scores"][t0:t0 + 10] > 0).sum()) for t0 in (0, 10)]
+    assert max(listed) > 1024, listed
+    d = _dev(det)
+    for top_k in (100, 16):
+        want = SR.merge_tiles(det, tiles, "ios", 0.5, 0.0, top_k, False)
+        got = pp.merge_tiles(d, tiles, _frames(SIZES), metric="ios", thr=0.5, skip_thr=0.0, top_k=top_k, class_agnostic=False)
+        torch.cuda.synchronize()
+        _assert_merge_equal(got, want)
+        assert (want["n_left"] > 0).any() == (top_k == 16), (top_k, want["n_left"])
 
 
 @pytest.mark.parametrize("case", range(len(MERGE_CASES)))

@@ -2,7 +2,7 @@
 COCO IoU thresholds 0.5:0.95 (T = 10), max-dets [1, 10, 100].
 
   rocprofv3 --kernel-trace --stats -d OUT -o box --output-format csv -- python tools/box_eval_probe.py --kernel
-      130 launches of mtbt_box_eval (30 warm-up + 100 timed); the per-launch kernel time is box_eval_kernel's AverageNs in
+      130 launches of mtbt_box_eval (30 warm-up + 100 timed); the per-launch kernel time is coco_match_kernel<BoxPairs>'s AverageNs in
       OUT/.../box_kernel_stats.csv
   python tools/box_eval_probe.py --host
       host time of compute() over ~5000 images: DeviceMeanAveragePrecision (records from update_batched) against the
