@@ -1649,6 +1649,66 @@ int mtbt_rle_encode(const mtbt_rle_args* a, void* stream);
 /* sizeof() of the structs above as the library was compiled: which = 0 mtbt_contours_args, 1 mtbt_rle_args; -1 otherwise */
 int mtbt_sizeof_contours_args(int which);
 
+/* ---------------------------------------------------------------------------------------------
+ * Measurements of regions of bit-packed planes or label maps (csrc/measure.hip, csrc/measure_exact.h; `postprocess.measure_regions`,
+ * `measure_components`, `region_properties`, `measure_detections`): sums, the lattice convex hull, Feret diameters, the minimum-area
+ * rectangle.  Packed layout, alignment and shape limits as mtbt_label_components (planes 8-byte aligned, 8-byte accesses only,
+ * pitch = 8 * ceil(W / 64), bits X >= W never count, H and W in [1, 16384]).
+ * THE MEASURE RULE, exact in integers (tests/measure_reference.py restates it):
+ *   Regions     PLANE MODE (labels == NULL): region 1 of plane p is the set bits of packed[p] with X < W; n planes, one region each,
+ *               max_regions = C = 1.  LABEL MODE (labels int32 [n][H][W], as mtbt_label_components writes them; packed may be NULL):
+ *               region i is {label == i} for 1 <= i <= C = max_regions in [1, 65536].  Labels <= 0 are background; labels > C belong
+ *               to no reported region but are "not this region" for the perimeter.  Any label map will do; a region need not be
+ *               connected in either mode.  Pixel (X, Y) is the square [X, X + 1] x [Y, Y + 1], the lattice of THE CONTOUR RULE.
+ *   Sums        sums uint64 [n][C][8] = area, perimeter (the unit pixel sides of the region whose 4-neighbour across the side is outside
+ *               the plane or not in the region), sum X, sum Y, sum X^2, sum X Y, sum Y^2, 0 over the region's pixel indices X, Y.
+ *   Hull        the convex hull of the region's closed pixel squares, i.e. of their lattice corners, strictly convex (a point collinear
+ *               with its neighbours is no vertex), listed from the vertex with the smallest key y * (W + 1) + x in the sense of an outer
+ *               contour of THE CONTOUR RULE (E -> S -> W -> N, the region on the right).  n_hull int32 [n][C] is the true count h, never
+ *               capped; hull int32 [n][C][Vh][2] (or NULL) holds the first min(h, Vh) vertices x, y, the rows after them zero,
+ *               Vh = max_hull >= 4; hull_area2 int64 [n][C] by the contour rule's area2 formula (> 0).  No measurement depends on max_hull.
+ *   Calipers    over the FULL hull p_0 .. p_{h-1}, p_h = p_0, e_i = p_{i+1} - p_i, len2_i = |e_i|^2, cross(a, b) = ax by - ay bx:
+ *     diameter    d2 = max |p_i - p_j|^2; the pair (a, b) = (p_i, p_j) with the smallest i, then the smallest j > i, among the maxima.
+ *     extent      with u = p_j - p_i of that pair, perp = max_q cross(u, q - p_i) - min_q cross(u, q - p_i) over the hull vertices q
+ *                 (the extent perpendicular to the diameter is perp / sqrt(d2)).
+ *     width       h_i = max_q |cross(e_i, q - p_i)|; the minimum over i of h_i^2 / len2_i, compared as exact fractions, a tie going to
+ *                 the smallest i: w_edge = i, w_num = h_i, w_len2 = len2_i, w_vertex = the smallest hull index q attaining h_i.
+ *     rectangle   tmin_i, tmax_i = min, max over q of dot(e_i, q - p_i), t_i = tmax_i - tmin_i; the minimum over i of
+ *                 h_i t_i / len2_i (the area), exact, a tie to the smallest i: r_edge, r_h, r_t, r_tmin, r_len2.
+ *               The cross-multiplied fractions reach 2^87: they are compared in 128 bits (csrc/measure_exact.h), never in floating
+ *               point or wrapped 64-bit words.
+ *   Tables      caliper int64 [n][C][8] = d2, perp, w_num, w_len2, r_h, r_t, r_tmin, r_len2;
+ *               caliper_at int32 [n][C][8] = xa, ya, xb, yb, w_edge, w_vertex, r_edge, 0.
+ * An empty region (or id) has every word zero; a non-empty one has n_hull >= 4.  Every output word is defined after the call: the caller
+ * does not pre-zero.  Asynchronous on `stream`, no host synchronisation, graph-capturable, a pure function of the input (integer atomics
+ * only, no floating point).  No workgroup waits on another; every loop bound is a host-side number (H, W, 2 (H + 1)) or a count the
+ * kernel has clamped by one.  `workspace`: >= mtbt_measure_workspace_bytes(n, H, W, max_regions) bytes, 16-byte aligned: 8 bytes per
+ * (region, lattice row) of the planes of one launch group (the query returns MTBT_EINVAL for a shape refused below).
+ * MTBT_EINVAL before any launch: NULL args, sums, n_hull, hull_area2, caliper or caliper_at; packed and labels both NULL; n < 0, H or W
+ * outside [1, 16384], pitch != 8 * ceil(W / 64); max_regions outside [1, 65536], or != 1 in plane mode; max_hull < 4; a non-zero
+ * reserved field; workspace NULL or workspace_bytes below the query.  MTBT_EALIGN: packed, sums, hull_area2 or caliper not 8-byte,
+ * workspace not 16-byte, the other pointers not 4-byte aligned.  n == 0 launches nothing. */
+typedef struct mtbt_measure_args {
+  const uint8_t* packed;   /* [n][H][pitch]; may be NULL in label mode */
+  const int32_t* labels;   /* [n][H][W] or NULL: plane mode */
+  void* workspace;
+  int64_t workspace_bytes;
+  uint64_t* sums;          /* [n][C][8] */
+  int32_t* n_hull;         /* [n][C] */
+  int32_t* hull;           /* [n][C][Vh][2] or NULL */
+  int64_t* hull_area2;     /* [n][C] */
+  int64_t* caliper;        /* [n][C][8] */
+  int32_t* caliper_at;     /* [n][C][8] */
+  int32_t n, H, W, pitch;
+  int32_t max_regions;     /* C */
+  int32_t max_hull;        /* Vh */
+  int32_t reserved[2];     /* 0 */
+} mtbt_measure_args;
+int64_t mtbt_measure_workspace_bytes(int n, int H, int W, int max_regions);
+int mtbt_measure_regions(const mtbt_measure_args* a, void* stream);
+/* sizeof() of the struct above as the library was compiled: which = 0 mtbt_measure_args; -1 otherwise */
+int mtbt_sizeof_measure_args(int which);
+
 /* Weight gradient of a k x k convolution (any stride / padding; 1x1 and the 2x2 stride-2 downsample included), bf16 (MFMA) or fp32 operands:
  *   dw[k][r][s][c] (fp32, packed [K][R*S*C] like the forward weight) (+)= sum_p dy[p][k] * x[n][y*stride + r - pad][x*stride + s - pad][c]
  * x [N,H,W,C], dy [N,Ho,Wo,K] (Ho = (H + 2 pad - R) / stride + 1) NHWC with pixel / batch strides in elements (multiples of 8; C % 8 == K % 8 == 0;

@@ -26,6 +26,7 @@
     from multitask_bonetumor_yolo_amd import seg_region_loss, SegRegionLoss   # soft Dice + boundary terms of the segmentation loss
     from multitask_bonetumor_yolo_amd import trace_contours, yolo_seg_rows, labelme_shapes   # packed masks -> polygons (YOLO-seg rows, LabelMe shapes)
     from multitask_bonetumor_yolo_amd import rle_encode, coco_segm_results   # packed masks -> COCO run lengths and a segm results list
+    from multitask_bonetumor_yolo_amd import measure_regions, region_properties, measure_detections   # hull, Feret diameters, moments of lesions
 
 The HIP library (csrc/libmtbt_hip.so, C ABI in include/mtbt_hip.h) is built by
 `python -m multitask_bonetumor_yolo_amd.build`; nothing here falls back to the CPU.
@@ -48,8 +49,9 @@ from .validate import ValidationStep  # noqa: F401
 from .ensemble import detect_fused  # noqa: F401
 from .postprocess import merge_tiles, seg_to_frames, vote_masks, vote_tile_masks  # noqa: F401
 from .planes import (coco_segm_results, components_to_instances, contour_polygons, count_contour_vertices, distance_transform, fill_polygons,  # noqa: F401
-                     filter_components, label_components, labelme_shapes, rle_encode, rle_from_string, rle_to_string, signed_distance,
-                     trace_contours, yolo_seg_planes, yolo_seg_polygons, yolo_seg_rows)
+                     filter_components, label_components, labelme_shapes, measure_components, measure_detections, measure_regions,
+                     region_properties, rle_encode, rle_from_string, rle_to_string, signed_distance, trace_contours, yolo_seg_planes,
+                     yolo_seg_polygons, yolo_seg_rows)
 from .sliced import detect_sliced  # noqa: F401
 from .trainstep import TrainStep, ema_decay_at  # noqa: F401
 from .model import ConvNeXtBiFPNYOLO, ConvNeXtBiFPNYOLOv0, ConvNeXtBiFPNYOLOv2, calibrate_synthetic_heads_, init_synthetic_, synthetic_images  # noqa: F401

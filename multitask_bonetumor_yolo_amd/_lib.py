@@ -300,6 +300,13 @@ class RleArgs(C.Structure):  # mtbt_rle_args
                 ("max_runs", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MeasureArgs(C.Structure):  # mtbt_measure_args
+    _fields_ = [("packed", C.c_void_p), ("labels", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("sums", C.c_void_p), ("n_hull", C.c_void_p), ("hull", C.c_void_p), ("hull_area2", C.c_void_p), ("caliper", C.c_void_p),
+                ("caliper_at", C.c_void_p), ("n", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32),
+                ("max_regions", C.c_int32), ("max_hull", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 SYMBOLS = {
     "mtbt_abi_version": (C.c_int, []),
     "mtbt_sizeof_args": (C.c_int, [C.c_int]),
@@ -457,6 +464,9 @@ SYMBOLS = {
     "mtbt_rle_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "mtbt_rle_encode": (C.c_int, [C.POINTER(RleArgs), C.c_void_p]),
     "mtbt_sizeof_contours_args": (C.c_int, [C.c_int]),
+    "mtbt_measure_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "mtbt_measure_regions": (C.c_int, [C.POINTER(MeasureArgs), C.c_void_p]),
+    "mtbt_sizeof_measure_args": (C.c_int, [C.c_int]),
 }
 
 ARG_STRUCTS = (ConvArgs, FuseArgs, DecodeArgs, MaskArgs, LossArgs, PrepDesc, RawImage, UpconvArgs, NodeArgs, BoxEvalArgs)   # order of mtbt_sizeof_args(which)
@@ -471,6 +481,7 @@ CLAHE_STRUCTS = (ClaheImage,)   # order of mtbt_sizeof_clahe_args(which)
 COPY_PASTE_STRUCTS = (CopyPasteArgs,)   # order of mtbt_sizeof_copy_paste_args(which)
 DISTANCE_STRUCTS = (DistanceTransformArgs, SegRegionArgs)   # order of mtbt_sizeof_distance_args(which)
 CONTOURS_STRUCTS = (ContoursArgs, RleArgs)   # order of mtbt_sizeof_contours_args(which)
+MEASURE_STRUCTS = (MeasureArgs,)   # order of mtbt_sizeof_measure_args(which)
 _lib = None
 
 
@@ -497,7 +508,7 @@ def load():
                                 (lib.mtbt_sizeof_components_args, COMPONENTS_STRUCTS), (lib.mtbt_sizeof_fill_polygons_args, POLYGON_STRUCTS),
                                 (lib.mtbt_sizeof_clahe_args, CLAHE_STRUCTS), (lib.mtbt_sizeof_copy_paste_args, COPY_PASTE_STRUCTS),
                                 (lib.mtbt_sizeof_distance_args, DISTANCE_STRUCTS), (lib.mtbt_sizeof_seg_frame_args, SEG_FRAME_STRUCTS),
-                                (lib.mtbt_sizeof_contours_args, CONTOURS_STRUCTS)):
+                                (lib.mtbt_sizeof_contours_args, CONTOURS_STRUCTS), (lib.mtbt_sizeof_measure_args, MEASURE_STRUCTS)):
             for which, st in enumerate(structs):
                 if sizeof(which) != C.sizeof(st):
                     raise RuntimeError(f"libmtbt_hip.so was built with sizeof({st.__name__}) = {sizeof(which)}, this binding lays it "

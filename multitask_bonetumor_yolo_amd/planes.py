@@ -1,5 +1,6 @@
 """Operators on bit-packed mask planes, on the device: the layout in one place (`plane_pitch`, `packed_planes`), packing and unpacking,
-connected components, the exact distance transform, polygons in (`fill_polygons`) and out (`trace_contours`), COCO run lengths.
+connected components, region measurements (hull, Feret diameters, moments), the exact distance transform, polygons in (`fill_polygons`)
+and out (`trace_contours`), COCO run lengths.
 
 A stack of planes is uint8 [n, H, pitch] with pitch = 8 * ceil(W / 64) bytes per row: 64 pixels per 8-byte word, pixel X is bit X & 7 of
 byte X >> 3 (numpy.packbits(bitorder="little")), padding bits X >= W never count.  `postprocess.masks_to_frames`, `vote_masks`,
@@ -205,6 +206,137 @@ def components_to_instances(packed: torch.Tensor, W: int, *, max_instances: int 
     for b in range(n):
         pack_masks(rec["labels"][b][None] == ids[b][:, None, None], out=masks[b])
     return {"masks": masks, "boxes": boxes, "areas": areas, "counts": counts}
+
+
+# ---- measurements of regions: sums, lattice hull, Feret diameters, minimum rectangle (THE MEASURE RULE: include/mtbt_hip.h) ----------
+def measure_regions(packed: Optional[torch.Tensor], W: int, *, labels: Optional[torch.Tensor] = None, max_regions: int = 1024,
+                    max_hull: int = 512) -> dict:
+    """The exact integer measurements of regions, on the device (`mtbt_measure_regions`; THE MEASURE RULE is in include/mtbt_hip.h).
+
+    Plane mode (labels=None): packed uint8 [n, H, pitch]; the one region of a plane is its set bits with X < W, connected or not
+    (C = 1, `max_regions` is ignored): `det["masks_frame"][b]` and `seg_frame` as they are.  Label mode: labels int32 [n, H, W] (as
+    `label_components` returns them; any label map will do), region i is {label == i} for 1 <= i <= C = max_regions; `packed` may
+    then be None.  Returns a dict of device tensors, no read-back: `sums` int64 [n, C, 8] (area, perimeter, sum X, sum Y, sum X^2,
+    sum X Y, sum Y^2, 0), `n_hull` int32 [n, C] (true), `hull` int32 [n, C, max_hull, 2] (x, y; the first min(n_hull, max_hull)
+    vertices of the convex hull of the pixel squares, from the top-left one, clockwise on the screen; zero rows after them),
+    `hull_area2` int64 [n, C], `caliper` int64 [n, C, 8] (d2, perp, w_num, w_len2, r_h, r_t, r_tmin, r_len2) and `caliper_at` int32
+    [n, C, 8] (xa, ya, xb, yb, w_edge, w_vertex, r_edge, 0).  `shape` = (H, W).  An empty region is all zeros.  No measurement depends
+    on `max_hull`.  `region_properties` turns the tables into lengths, areas and angles.  Asynchronous."""
+    W, Vh = int(W), int(max_hull)
+    if labels is None:
+        n, H, pitch, planes, _ = packed_planes("measure_regions", packed, W)
+        C_, dev = 1, packed.device
+    else:
+        if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+            raise RuntimeError("measure_regions: expected CUDA/HIP tensors on an MI355X (no CPU path)")
+        if labels.dim() != 3 or labels.dtype != torch.int32 or int(labels.shape[2]) != W:
+            raise ValueError(f"measure_regions: labels must be int32 [n, H, {W}]")
+        n, H = int(labels.shape[0]), int(labels.shape[1])
+        if not (1 <= H <= COMPONENTS_MAX_DIM and 1 <= W <= COMPONENTS_MAX_DIM):
+            raise ValueError(f"measure_regions: maps of {H} x {W} pixels (1 <= H, W <= {COMPONENTS_MAX_DIM})")
+        C_, dev, pitch, planes = int(max_regions), labels.device, plane_pitch(W), None
+        labels = labels.contiguous()
+        if not 1 <= C_ <= COMPONENTS_MAX_TABLE:
+            raise ValueError(f"measure_regions: max_regions {C_} is outside [1, {COMPONENTS_MAX_TABLE}]")
+    if Vh < 4 or Vh >= 2 ** 31:
+        raise ValueError(f"measure_regions: max_hull {Vh} is below 4 (one pixel has four hull vertices)")
+    out = {"sums": torch.empty((n, C_, 8), dtype=torch.int64, device=dev), "n_hull": torch.empty((n, C_), dtype=torch.int32, device=dev),
+           "hull": torch.empty((n, C_, Vh, 2), dtype=torch.int32, device=dev), "hull_area2": torch.empty((n, C_), dtype=torch.int64, device=dev),
+           "caliper": torch.empty((n, C_, 8), dtype=torch.int64, device=dev), "caliper_at": torch.empty((n, C_, 8), dtype=torch.int32, device=dev),
+           "shape": (H, W)}
+    if n == 0:
+        return out
+    lib = L.load()
+    ws, ws_bytes = L.workspace(lib.mtbt_measure_workspace_bytes, n, H, W, C_, device=dev, what="mtbt_measure_workspace_bytes")
+    a = L.MeasureArgs()
+    a.packed, a.labels = planes.data_ptr() if planes is not None else None, labels.data_ptr() if labels is not None else None
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws_bytes
+    a.sums, a.n_hull, a.hull, a.hull_area2 = out["sums"].data_ptr(), out["n_hull"].data_ptr(), out["hull"].data_ptr(), out["hull_area2"].data_ptr()
+    a.caliper, a.caliper_at = out["caliper"].data_ptr(), out["caliper_at"].data_ptr()
+    a.n, a.H, a.W, a.pitch, a.max_regions, a.max_hull = n, H, W, pitch, C_, Vh
+    with torch.cuda.device(dev):
+        L.check(lib.mtbt_measure_regions(C.byref(a), L.stream(dev)), "mtbt_measure_regions")
+    return out
+
+
+def measure_components(packed: torch.Tensor, W: int, *, connectivity: int = 4, max_components: int = 1024, max_hull: int = 512):
+    """`label_components`, then `measure_regions` in label mode over its label map: the measurements of every connected component, id i
+    in row i - 1.  Returns (the components dict, the measurements dict).  Asynchronous."""
+    rec = label_components(packed, W, connectivity=connectivity, max_components=max_components)
+    return rec, measure_regions(None, W, labels=rec["labels"], max_regions=max_components, max_hull=max_hull)
+
+
+def region_properties(result: dict, *, spacing: float = 1.0) -> dict:
+    """The tables of `measure_regions` as float64 numpy arrays of shape [n, C] (points [n, C, 2], `min_rect` [n, C, 4, 2]): reads the
+    small tables back (synchronises) and finishes the floats on the host, as `surface_metrics` does.
+
+    `area`, `perimeter` (pixel sides), `centroid` (sum X / A + 0.5, sum Y / A + 0.5: lattice coordinates), `mu20`, `mu02`, `mu11` (central
+    second moments with the pixel's own 1/12), `orientation` = atan2(2 mu11, mu20 - mu02) / 2, `major_axis` and `minor_axis` = 4 sqrt of
+    the eigenvalues, `eccentricity`, `equivalent_diameter` = sqrt(4 A / pi), `hull_area`, `solidity` = A / hull_area, `feret_max` with
+    its end points `feret_a`, `feret_b`, `feret_perp` (the extent across it), `who_product` = feret_max * feret_perp, `feret_min` (the
+    caliper width) and `min_rect` (the four corners of the minimum-area rectangle, in hull order) with `min_rect_area`; `n_hull`.
+    `spacing` (length of a pixel side) scales lengths and points, its square areas and moments.  An empty region has 0 for sizes and
+    NaN for ratios, angles and points; `min_rect` is also NaN where the rectangle's edge lies beyond the `max_hull` stored vertices
+    (`min_rect_area` does not need them)."""
+    sp = float(spacing)
+    s = result["sums"].cpu().numpy().astype(np.float64)
+    cal = result["caliper"].cpu().numpy()
+    at = result["caliper_at"].cpu().numpy()
+    hull = result["hull"].cpu().numpy().astype(np.float64)
+    n_hull = result["n_hull"].cpu().numpy()
+    a2 = result["hull_area2"].cpu().numpy().astype(np.float64)
+    A = s[..., 0]
+    nz = A > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mx, my = s[..., 2] / A, s[..., 3] / A
+        mu20, mu02, mu11 = s[..., 4] / A - mx * mx + 1.0 / 12.0, s[..., 6] / A - my * my + 1.0 / 12.0, s[..., 5] / A - mx * my
+        half, root = (mu20 + mu02) / 2.0, np.sqrt(((mu20 - mu02) / 2.0) ** 2 + mu11 ** 2)
+        l1, l2 = half + root, np.maximum(half - root, 0.0)
+        d2, perp = cal[..., 0].astype(np.float64), cal[..., 1].astype(np.float64)
+        fmax = np.sqrt(d2)
+        fperp = perp / fmax
+        fmin = cal[..., 2].astype(np.float64) / np.sqrt(cal[..., 3].astype(np.float64))
+        r_h, r_t, r_tmin, r_len2 = (cal[..., k].astype(np.float64) for k in (4, 5, 6, 7))
+        solidity = A / (a2 / 2.0)
+        ecc = np.sqrt(1.0 - l2 / l1)
+        # the rectangle on edge r_edge = p -> p + e: along e from tmin to tmax (in units of |e|^2), across it from 0 to h on the hull's side
+        Vh = hull.shape[2]
+        i0 = at[..., 6].astype(np.int64)
+        i1 = (i0 + 1) % np.maximum(n_hull, 1)
+        known = nz & (i0 < Vh) & (i1 < Vh)                                                # both ends of the edge are among the stored vertices
+        row = lambda i: np.take_along_axis(hull, np.broadcast_to(np.clip(i, 0, Vh - 1)[..., None, None], i.shape + (1, 2)), axis=2)[..., 0, :]
+        p0, p1 = row(i0), row(i1)
+        e = p1 - p0
+        nrm = np.stack([-e[..., 1], e[..., 0]], axis=-1)                                  # e turned clockwise on the screen: towards the hull
+        lo, hi, hh = (r_tmin / r_len2)[..., None], ((r_tmin + r_t) / r_len2)[..., None], (r_h / r_len2)[..., None]
+        rect = np.stack([p0 + lo * e, p0 + hi * e, p0 + hi * e + hh * nrm, p0 + lo * e + hh * nrm], axis=-2)
+        rect_area = r_h * r_t / r_len2
+    rect = np.where(known[..., None, None], rect, np.nan)
+    nan = lambda v: np.where(nz, v, np.nan)
+    zero = lambda v: np.where(nz, v, 0.0)
+    pts = lambda k: np.where(nz[..., None], at[..., k:k + 2].astype(np.float64), np.nan) * sp
+    return {"area": A * sp * sp, "perimeter": s[..., 1] * sp, "centroid": np.stack([nan(mx + 0.5), nan(my + 0.5)], axis=-1) * sp,
+            "mu20": nan(mu20) * sp * sp, "mu02": nan(mu02) * sp * sp, "mu11": nan(mu11) * sp * sp,
+            "orientation": nan(0.5 * np.arctan2(2.0 * mu11, mu20 - mu02)), "major_axis": zero(4.0 * np.sqrt(l1)) * sp,
+            "minor_axis": zero(4.0 * np.sqrt(l2)) * sp, "eccentricity": nan(ecc), "equivalent_diameter": np.sqrt(4.0 * A / np.pi) * sp,
+            "hull_area": a2 / 2.0 * sp * sp, "solidity": nan(solidity), "feret_max": zero(fmax) * sp, "feret_a": pts(0), "feret_b": pts(2),
+            "feret_perp": zero(fperp) * sp, "who_product": zero(fmax * fperp) * sp * sp, "feret_min": zero(fmin) * sp,
+            "min_rect": rect * sp, "min_rect_area": zero(rect_area) * sp * sp, "n_hull": n_hull}
+
+
+def measure_detections(out: dict, *, spacing: float = 1.0, frames=None, max_hull: int = 512):
+    """The measurements of the kept instance masks of a batch: a list, one `region_properties` dict per image, over the first
+    counts[b] planes of `out["masks_frame"][b]` (plane mode; arrays of shape [counts[b], 1]).
+
+    `out`: a `detect_and_segment(..., frames=...)` result (or `detect_fused` / `detect_sliced`); `frames`: the [(H0, W0, scale)] it was
+    made with (or `out["frames"]`): the packed planes do not carry their width.  Synchronises."""
+    frames = out.get("frames") if frames is None else frames
+    B = len(out["masks_frame"])
+    if frames is None or len(frames) != B:
+        raise ValueError(f"measure_detections: {B} images need as many frames (H0, W0, scale)")
+    n_kept = out["counts"].cpu().numpy()
+    return [region_properties(measure_regions(out["masks_frame"][b][:int(n_kept[b])], int(frames[b][1]), max_hull=max_hull), spacing=spacing)
+            for b in range(B)]
 
 
 # ---- exact Euclidean distance transform of bit-packed planes (include/mtbt_hip.h `mtbt_distance_transform`) -------------------------

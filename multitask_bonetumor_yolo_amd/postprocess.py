@@ -15,8 +15,9 @@ from .planes import _need_cuda, plane_pitch
 # the operators on packed planes live in planes.py; they stay importable from here
 from .planes import (COMPONENTS_MAX_DIM, COMPONENTS_MAX_TABLE, D2_NONE, POLYGON_MAX_COORD, coco_segm_results, components_to_instances,  # noqa: F401
                      contour_polygons, count_contour_vertices, distance_transform, fill_polygons, filter_components, label_components,
-                     labelme_shapes, pack_masks, rle_encode, rle_from_string, rle_to_string, signed_distance, trace_contours, unpack_masks,
-                     yolo_seg_planes, yolo_seg_polygons, yolo_seg_rows)
+                     labelme_shapes, measure_components, measure_detections, measure_regions, pack_masks, region_properties, rle_encode,
+                     rle_from_string, rle_to_string, signed_distance, trace_contours, unpack_masks, yolo_seg_planes, yolo_seg_polygons,
+                     yolo_seg_rows)
 
 CONF_TH, NMS_IOU, TOP_K = 0.05, 0.6, 100  # running_main_v3.py:54-56
 
