@@ -1,51 +1,116 @@
-// BatchNorm2d forward with BATCH statistics (module in train mode), NHWC, fused activation.
+// BatchNorm2d with BATCH statistics (module in train mode), NHWC, fused activation: forward and backward.
 // Needed for drop-in parity of `forward(mode="train")`: the reference flips the Detect/Segment heads to train
 // mode for that call (main_model.py:358-359), so their BatchNorms normalise with batch statistics
 // and update running_mean / running_var (momentum, unbiased variance) even under Lightning validation.
 //
-// Deterministic statistics: per-workgroup (mean, M2) partials in a workspace, combined exactly in a fixed order; no atomics.
+// Forward:  xhat = (x - mean) * rstd, u = xhat * gamma + beta, y = act(u)
+// Backward: du = dy * act'(u);  s1 = sum_p du;  s2 = sum_p du * xhat;  d beta = s1;  d gamma = s2
+//   batch statistics:    dx = gamma * rstd * (du - s1 / M - xhat * s2 / M)
+//   running statistics:  dx = gamma * rstd * du
+// Deterministic: every sum is one of the fixed-order reductions of rowreduce.h (per-workgroup partial rows in a workspace, then one wave
+// per channel); no atomics.
+#include <type_traits>
+
 #include "common.h"
 #include "rowreduce.h"
 
 namespace {
 
-// ---- single-pass statistics: every workgroup reduces its ROWS_PER_BLOCK rows to a per-channel (mean_b, M2_b)
+struct Row8 { float v[8]; };
+
+// The per-channel constants of an 8-channel piece.  Where the piece a thread works on is the same for all its rows (the workgroup size is
+// a multiple of the pieces per row) they are read ONCE per thread and the row loop holds only the 16-byte loads and the arithmetic, four
+// rows deep.  (Round 3: with the four parameter vectors re-read and one row in flight per trip the backward statistics pass ran at
+// 2.0 TB/s, SLOWER than the apply pass that also writes a tensor, and the forward apply at 2.5 TB/s.)
+struct BnChan { float mu[8], rs[8], ga[8], be[8]; };
+__device__ __forceinline__ BnChan bn_chan(const float* mean, const float* var, const float* gamma, const float* beta, float eps, int c0) {
+  BnChan k;
+  float va[8];
+  ld8<float>(mean + c0, k.mu);
+  ld8<float>(var + c0, va);
+  ld8<float>(gamma + c0, k.ga);
+  ld8<float>(beta + c0, k.be);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) k.rs[e] = rsqrtf(va[e] + eps);
+  return k;
+}
+// du = dy * act'(xhat * gamma + beta), xhat = (x - mean) * rstd.  ACT: the activation as a compile-time constant, or -1 = the run-time `act`
+template <int ACT>
+__device__ __forceinline__ void bn_du_k(const float (&a)[8], const float (&b)[8], const BnChan& k, int act, float (&du)[8], float (&xh)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    xh[e] = (b[e] - k.mu[e]) * k.rs[e];
+    du[e] = a[e] * act_grad(xh[e] * k.ga[e] + k.be[e], ACT < 0 ? act : ACT);
+  }
+}
+
+// The ACT x FIXED instantiation a launch takes: f(integral_constant<int, ACT>, integral_constant<bool, FIXED>).  The three activations of
+// the network are compile-time constants on the fixed path; everything else reads the run-time `act` (ACT = -1).
+template <typename F>
+void bn_dispatch(int act, bool fixed, F f) {
+  using std::integral_constant;
+  if (!fixed) f(integral_constant<int, -1>{}, std::false_type{});
+  else if (act == MTBT_ACT_SILU) f(integral_constant<int, MTBT_ACT_SILU>{}, std::true_type{});
+  else if (act == MTBT_ACT_ELU) f(integral_constant<int, MTBT_ACT_ELU>{}, std::true_type{});
+  else if (act == MTBT_ACT_NONE) f(integral_constant<int, MTBT_ACT_NONE>{}, std::true_type{});
+  else f(integral_constant<int, -1>{}, std::true_type{});
+}
+
+// workgroups of an apply pass: FIXED takes four pieces per thread and trip and at most 2048 workgroups (8 per CU)
+unsigned bn_apply_grid(long pieces, bool fixed, long general_cap) {
+  const long per = fixed ? 1024 : 256, cap = fixed ? 2048 : general_cap;
+  const long g = (pieces + per - 1) / per;
+  return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+
+// ---- forward statistics in a single pass: every workgroup reduces its ROWS_PER_BLOCK rows to a per-channel (mean_b, M2_b)
 // with sums SHIFTED by the block's first row (no cancellation for |mean| >> sigma); the final kernel combines the blocks exactly
 // (Chan et al.): mean = sum n_b mean_b / N, M2 = sum (M2_b + n_b (mean_b - mean)^2), one WAVE per channel striding over the blocks.
 // One read of x for the statistics instead of two, and no serial loop over thousands of partial rows. ----
 template <typename T>
 __global__ __launch_bounds__(256) void bn_block_stats_kernel(const T* __restrict__ x, long pixels, int C, float* __restrict__ partial /* [blocks][2C] */) {
-  __shared__ float red[256 * 16];
-  const int CH8 = C >> 3, G = 256 / CH8;
-  const int tid = threadIdx.x, cg = tid % CH8, g = tid / CH8;
+  __builtin_assume(C <= 2048);            // (the entry point refuses more: rows_reduce's branch for wider rows compiles away)
   const long r0 = (long)blockIdx.x * ROWS_PER_BLOCK;
   const long r1 = r0 + ROWS_PER_BLOCK < pixels ? r0 + ROWS_PER_BLOCK : pixels;
   const float nb = (float)(r1 - r0);
-  float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, q[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sh[8];
-  if (g < G) {
-    ld8<T>(x + r0 * C + cg * 8, sh);
-    for (long r = r0 + g; r < r1; r += G) {
-      float v[8];
-      ld8<T>(x + r * C + cg * 8, v);
+  float sh[8];                                  // of this thread's piece: tid % pieces in every row of rows_reduce's grouped path
+  ld8<T>(x + r0 * C + threadIdx.x % (C >> 3) * 8, sh);
+  float* dst = partial + (long)blockIdx.x * 2 * C;
+  rows_reduce<2>(
+      r0, r1, C >> 3, [&](long r, int ch) { Row8 v; ld8<T>(x + r * C + ch * 8, v.v); return v; },
+      [&](const Row8& v, float (&t)[2][8]) {
 #pragma unroll
-      for (int e = 0; e < 8; ++e) { const float d = v[e] - sh[e]; s[e] += d; q[e] += d * d; }
-    }
+        for (int e = 0; e < 8; ++e) { const float d = v.v[e] - sh[e]; t[0][e] = d; t[1][e] = d * d; }
+      },
+      [&](int ch, const float (&tot)[2][8]) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { red[(g * CH8 + cg) * 16 + e] = s[e]; red[(g * CH8 + cg) * 16 + 8 + e] = q[e]; }
-  }
-  __syncthreads();
-  if (g == 0) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float ts = 0.f, tq = 0.f;
-      for (int k = 0; k < G; ++k) { ts += red[(k * CH8 + cg) * 16 + e]; tq += red[(k * CH8 + cg) * 16 + 8 + e]; }
-      const float md = ts / nb;                                    // mean of the shifted values
-      partial[(long)blockIdx.x * 2 * C + cg * 8 + e] = sh[e] + md;            // block mean
-      partial[(long)blockIdx.x * 2 * C + C + cg * 8 + e] = tq - ts * md;      // block M2 = sum d^2 - (sum d)^2 / n
-    }
-  }
+        for (int e = 0; e < 8; ++e) {
+          const float ts = tot[0][e], tq = tot[1][e];
+          const float md = ts / nb;                     // mean of the shifted values
+          dst[ch * 8 + e] = sh[e] + md;                 // block mean
+          dst[C + ch * 8 + e] = tq - ts * md;           // block M2 = sum d^2 - (sum d)^2 / n
+        }
+      });
 }
 
+// The tail of the three statistics kernels: channel c's mean and biased variance from (mu, M2), and the running updates (unbiased variance).
+__device__ __forceinline__ void bn_write_stats(int c, float mu, float m2, long pixels, float* mean, float* var, float* running_mean, float* running_var,
+                                               float momentum) {
+  mean[c] = mu;
+  var[c] = m2 / (float)pixels;
+  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
+  if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (pixels > 1 ? m2 / (float)(pixels - 1) : m2 / (float)pixels);
+}
+// ... from s1 = sum (x - shift), s2 = sum (x - shift)^2.  shift may BE running_mean: it is read before bn_write_stats updates that.
+__device__ __forceinline__ void bn_write_stats_shifted(int c, float s1, float s2, const float* shift, long pixels, float* mean, float* var,
+                                                       float* running_mean, float* running_var, float momentum) {
+  const float n = (float)pixels;
+  const float sh = shift ? shift[c] : 0.f;
+  const float m1 = s1 / n;
+  bn_write_stats(c, sh + m1, fmaxf(s2 - n * m1 * m1, 0.f), pixels, mean, var, running_mean, running_var, momentum);
+}
+
+// (its two sums are weighted by the blocks' row counts and the second needs the first's result: column_sums does not fit)
 __global__ __launch_bounds__(256) void bn_combine_stats_kernel(const float* __restrict__ partial, int nblocks, int C, long pixels, float* __restrict__ mean,
                                                                float* __restrict__ var, float* __restrict__ running_mean,
                                                                float* __restrict__ running_var, float momentum) {
@@ -61,132 +126,296 @@ __global__ __launch_bounds__(256) void bn_combine_stats_kernel(const float* __re
     m2 += partial[(long)b * 2 * C + C + c] + (b == nblocks - 1 ? (float)last : (float)ROWS_PER_BLOCK) * d * d;
   }
   m2 = wave_sum(m2);
-  if (lane == 0) {
-    mean[c] = mu;
-    var[c] = m2 / (float)pixels;
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-    if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (pixels > 1 ? m2 / (float)(pixels - 1) : m2 / (float)pixels);
-  }
+  if (lane == 0) bn_write_stats(c, mu, m2, pixels, mean, var, running_mean, running_var, momentum);
 }
 
-// y = act((x - mean) * rstd * gamma + beta).  FIXED (256 % (C / 8) == 0): a thread's 8-channel piece is the same in every trip of the
-// grid-stride loop, so the four parameter vectors and the rsqrt are taken ONCE per thread and four rows are in flight per trip; ACT = the
-// activation as a compile-time constant or -1 for the run-time `act` (round 3: the general loop re-read 4 x 32 B of parameters and held one
-// 16-byte load per trip -- 2.5 TB/s over the step's BatchNorm family).
-template <typename T, int ACT, bool FIXED>
-__global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ mean, const float* __restrict__ var,
-                                const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int act, long pixels, int C,
-                                int y_ld) {
-  const int CH8 = C >> 3;
-  const long total = pixels * CH8;
-  if constexpr (FIXED) {
-    const int cg = threadIdx.x % CH8;
-    const int sh = 31 - __builtin_clz(CH8);              // CH8 is a power of two here: pixel = piece >> sh (a 64-bit division per piece otherwise)
-    float mu[8], rs[8], ga[8], be[8];
-    ld8<float>(mean + cg * 8, mu);
-    ld8<float>(var + cg * 8, rs);
-    ld8<float>(gamma + cg * 8, ga);
-    ld8<float>(beta + cg * 8, be);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) rs[e] = rsqrtf(rs[e] + eps);
-    const long stride = (long)gridDim.x * 256;
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    for (; i + 3 * stride < total; i += 4 * stride) {
-      float v[4][8];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) ld8<T>(x + (i + u * stride) * 8, v[u]);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[u][e] = act_apply((v[u][e] - mu[e]) * rs[e] * ga[e] + be[e], ACT < 0 ? act : ACT);
-        st8<T>(y + ((i + u * stride) >> sh) * y_ld + cg * 8, v[u]);
-      }
-    }
-    for (; i < total; i += stride) {
-      float v[8];
-      ld8<T>(x + i * 8, v);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) v[e] = act_apply((v[e] - mu[e]) * rs[e] * ga[e] + be[e], ACT < 0 ? act : ACT);
-      st8<T>(y + (i >> sh) * y_ld + cg * 8, v);
-    }
-    return;
-  }
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int cg = (int)(i % CH8);
-    const long pix = i / CH8;
-    float v[8], mu[8], va[8], ga[8], be[8];
-    ld8<T>(x + i * 8, v);
-    ld8<float>(mean + cg * 8, mu);
-    ld8<float>(var + cg * 8, va);
-    ld8<float>(gamma + cg * 8, ga);
-    ld8<float>(beta + cg * 8, be);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = act_apply((v[e] - mu[e]) * rsqrtf(va[e] + eps) * ga[e] + be[e], act);
-    st8<T>(y + pix * y_ld + cg * 8, v);
-  }
-}
-
-template <typename T>
-void launch_bn_apply(const void* x, void* y, const float* mean, const float* var, const float* gamma, const float* beta, float eps, int act, long pixels,
-                     int C, int y_ld, hipStream_t s) {
-  const int CH8 = C >> 3;
-  const bool fixed = 256 % CH8 == 0;
-  const long total = pixels * CH8;
-  long g = (total + (fixed ? 1023 : 255)) / (fixed ? 1024 : 256);      // FIXED: four pieces per thread and trip, at most 8 workgroups per CU
-  const long cap = fixed ? 2048 : 8192;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-#define BA(A, F) hipLaunchKernelGGL((bn_apply_kernel<T, A, F>), dim3((unsigned)g), dim3(256), 0, s, (const T*)x, (T*)y, mean, var, gamma, beta, eps, act, pixels, C, y_ld)
-  if (!fixed) BA(-1, false);
-  else if (act == MTBT_ACT_SILU) BA(MTBT_ACT_SILU, true);
-  else if (act == MTBT_ACT_ELU) BA(MTBT_ACT_ELU, true);
-  else if (act == MTBT_ACT_NONE) BA(MTBT_ACT_NONE, true);
-  else BA(-1, true);
-#undef BA
-}
-
-// batch statistics straight from the conv epilogue's PARTIAL rows ([rows][pitch]: sum (x - s) in [0, C), sum (x - s)^2 in [C, 2C)): one wave per
-// channel, lanes stride over the rows, butterfly (fixed order) -- the second level of the column sums and the statistics in one launch
+// batch statistics straight from the conv epilogue's PARTIAL rows ([rows][pitch]: sum (x - s) in [0, C), sum (x - s)^2 in [C, 2C)): the
+// second level of the column sums and the statistics in one launch
 __global__ __launch_bounds__(256) void bn_stats_from_partials_kernel(const float* __restrict__ partial, int rows, int pitch, const float* __restrict__ shift,
                                                                      long pixels, int C, float* __restrict__ mean, float* __restrict__ var,
                                                                      float* __restrict__ running_mean, float* __restrict__ running_var, float momentum) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c >= C) return;                                   // whole waves leave together
-  float s1 = 0.f, s2 = 0.f;
-  for (int r = lane; r < rows; r += 64) { s1 += partial[(long)r * pitch + c]; s2 += partial[(long)r * pitch + C + c]; }
-  s1 = wave_sum(s1); s2 = wave_sum(s2);
-  if (lane == 0) {
-    const float n = (float)pixels;
-    const float sh = shift ? shift[c] : 0.f;            // (may BE running_mean[c]: read before it is updated below)
-    const float m1 = s1 / n;
-    const float mu = sh + m1;
-    const float m2 = fmaxf(s2 - n * m1 * m1, 0.f);
-    mean[c] = mu;
-    var[c] = m2 / n;
-    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-    if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (pixels > 1 ? m2 / (float)(pixels - 1) : m2 / n);
-  }
+  float s[2];
+  column_sums<2>(partial, rows, pitch, {c, C + c}, s);
+  if ((threadIdx.x & 63) == 0) bn_write_stats_shifted(c, s[0], s[1], shift, pixels, mean, var, running_mean, running_var, momentum);
 }
 
 // batch statistics from the column sums the producing conv's epilogue accumulated (mtbt_conv_args.colsum): sum (x - s), sum (x - s)^2
 __global__ void bn_stats_from_sums_kernel(const float* __restrict__ sums, const float* __restrict__ shift, long pixels, int C, float* __restrict__ mean,
                                           float* __restrict__ var, float* __restrict__ running_mean, float* __restrict__ running_var, float momentum) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float n = (float)pixels;
-  const float sh = shift ? shift[c] : 0.f;          // (may BE running_mean[c]: read before it is updated below)
-  const float m1 = sums[c] / n;
-  const float mu = sh + m1;
-  const float m2 = fmaxf(sums[C + c] - n * m1 * m1, 0.f);   // sum (x - mu)^2
-  mean[c] = mu;
-  var[c] = m2 / n;
-  if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
-  if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (pixels > 1 ? m2 / (float)(pixels - 1) : m2 / n);
+  if (c < C) bn_write_stats_shifted(c, sums[c], sums[C + c], shift, pixels, mean, var, running_mean, running_var, momentum);
 }
 
 __global__ void bn_copy_stats_kernel(const float* __restrict__ rm, const float* __restrict__ rv, float* __restrict__ mean, float* __restrict__ var, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c < C) { mean[c] = rm[c]; var[c] = rv[c]; }
+}
+
+// y = act((x - mean) * rstd * gamma + beta); y rows of y_ld elements.  FIXED (256 % (C / 8) == 0): a thread's 8-channel piece is the same in
+// every trip of the grid-stride loop, so its constants are taken ONCE per thread, the pixel is a shift (C / 8 is a power of two; a 64-bit
+// division per piece otherwise) and four pieces are in flight per trip.  Otherwise the plain grid-stride loop, bn_chan per piece.
+template <typename T, int ACT, bool FIXED>
+__global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ x, T* __restrict__ y, const float* __restrict__ mean, const float* __restrict__ var,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int act, long pixels, int C,
+                                                       int y_ld) {
+  const int CH8 = C >> 3;
+  const long total = pixels * CH8, stride = (long)gridDim.x * 256;
+  long i = (long)blockIdx.x * 256 + threadIdx.x;
+  auto one = [&](float (&v)[8], const BnChan& k, long pix, int cg) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = act_apply((v[e] - k.mu[e]) * k.rs[e] * k.ga[e] + k.be[e], ACT < 0 ? act : ACT);
+    st8<T>(y + pix * y_ld + cg * 8, v);
+  };
+  if constexpr (FIXED) {
+    const int cg = threadIdx.x % CH8;
+    const int sh = 31 - __builtin_clz(CH8);
+    const BnChan k = bn_chan(mean, var, gamma, beta, eps, cg * 8);
+    for (; i + 3 * stride < total; i += 4 * stride) {
+      float v[4][8];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) ld8<T>(x + (i + u * stride) * 8, v[u]);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) one(v[u], k, (i + u * stride) >> sh, cg);
+    }
+    for (; i < total; i += stride) {
+      float v[8];
+      ld8<T>(x + i * 8, v);
+      one(v, k, i >> sh, cg);
+    }
+  } else {
+    for (; i < total; i += stride) {
+      const int cg = (int)(i % CH8);
+      float v[8];
+      ld8<T>(x + i * 8, v);
+      one(v, bn_chan(mean, var, gamma, beta, eps, cg * 8), i / CH8, cg);
+    }
+  }
+}
+
+void launch_bn_apply(int dtype, const void* x, void* y, const float* mean, const float* var, const float* gamma, const float* beta, float eps, int act,
+                     long pixels, int C, int y_ld, hipStream_t s) {
+  const bool fixed = 256 % (C >> 3) == 0;
+  const unsigned g = bn_apply_grid(pixels * (C >> 3), fixed, 8192);
+  bn_dispatch(act, fixed, [&](auto A, auto F) {
+    if (dtype == MTBT_F32)
+      hipLaunchKernelGGL((bn_apply_kernel<float, decltype(A)::value, decltype(F)::value>), dim3(g), dim3(256), 0, s, (const float*)x, (float*)y, mean, var, gamma, beta, eps, act, pixels, C, y_ld);
+    else
+      hipLaunchKernelGGL((bn_apply_kernel<bf16_t, decltype(A)::value, decltype(F)::value>), dim3(g), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, mean, var, gamma, beta, eps, act, pixels, C, y_ld);
+  });
+}
+
+// ---- backward.  Pass 1 forms per-workgroup partial (s1, s2) rows; pass 2 sums them (one wave per column); pass 3 recomputes du and writes
+// dx.  dy may be a channel slice (row pitch dy_ld); x (the conv output the forward normalised) and dx are dense. ----
+// bn_bwd_partial and bn_bwd_apply keep their own loops, and bn_du, the per-row form of bn_chan + bn_du_k that their serial / general
+// branches call.  bn_bwd_partial is rows_reduce<2> written out (the same order of additions); through the template, and bn_bwd_apply over a
+// walk shared with bn_apply_kernel, the same source compiled to a slower schedule of the loads and to other contractions of the products into
+// the sums, that is other bits of d beta and dx (profiles/train_reductions_refactor.txt).
+template <typename T>
+__device__ __forceinline__ void bn_du(const T* dy, long dy_off, const T* x, long x_off, const float* mean, const float* var, const float* gamma,
+                                      const float* beta, float eps, int act, int c0, float (&du)[8], float (&xh)[8], float (&gr)[8]) {
+  float a[8], b[8], mu[8], va[8], ga[8], be[8];
+  ld8<T>(dy + dy_off, a);
+  ld8<T>(x + x_off, b);
+  ld8<float>(mean + c0, mu);
+  ld8<float>(var + c0, va);
+  ld8<float>(gamma + c0, ga);
+  ld8<float>(beta + c0, be);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float rstd = rsqrtf(va[e] + eps);
+    xh[e] = (b[e] - mu[e]) * rstd;
+    du[e] = a[e] * act_grad(xh[e] * ga[e] + be[e], act);
+    gr[e] = ga[e] * rstd;
+  }
+}
+
+// ACT: the activation as a compile-time constant (MTBT_ACT_NONE / SILU / ELU), or -1 = the run-time `act`
+template <typename T, int ACT>
+__global__ __launch_bounds__(256) void bn_bwd_partial(const T* __restrict__ dy, int dy_ld, const T* __restrict__ x, long P, int C,
+                                                      const float* __restrict__ mean, const float* __restrict__ var,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int act,
+                                                      float* __restrict__ partial /* [blocks][2C] */) {
+  __shared__ float red[256 * 16];
+  const int tid = threadIdx.x, chunks = C >> 3;
+  const long p0 = (long)blockIdx.x * ROWS_PER_BLOCK, p1 = min(P, p0 + ROWS_PER_BLOCK);
+  float* dst = partial + (long)blockIdx.x * 2 * C;
+  if (chunks >= 256) {   // (C >= 2048: not used by this network; serial over the rows)
+    for (int ch = tid; ch < chunks; ch += 256) {
+      float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      for (long p = p0; p < p1; ++p) {
+        float du[8], xh[8], gr[8];
+        bn_du<T>(dy, p * dy_ld + ch * 8, x, p * C + ch * 8, mean, var, gamma, beta, eps, act, ch * 8, du, xh, gr);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { s1[k] += du[k]; s2[k] += du[k] * xh[k]; }
+      }
+#pragma unroll
+      for (int k = 0; k < 8; ++k) { dst[ch * 8 + k] = s1[k]; dst[C + ch * 8 + k] = s2[k]; }
+    }
+    return;
+  }
+  const int rpp = 256 / chunks, rg = tid / chunks, ch = tid - rg * chunks;
+  float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (rg < rpp) {
+    const BnChan k = bn_chan(mean, var, gamma, beta, eps, ch * 8);
+    const T* dyp = dy + ch * 8;
+    const T* xp = x + ch * 8;
+    long p = p0 + rg;
+    for (; p + 3 * rpp < p1; p += 4 * rpp) {      // (rows are added in the same order as one at a time)
+      float a[4][8], b[4][8];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { ld8<T>(dyp + (p + u * rpp) * dy_ld, a[u]); ld8<T>(xp + (p + u * rpp) * C, b[u]); }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        float du[8], xh[8];
+        bn_du_k<ACT>(a[u], b[u], k, act, du, xh);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) { s1[e] += du[e]; s2[e] += du[e] * xh[e]; }
+      }
+    }
+    for (; p < p1; p += rpp) {
+      float a[8], b[8], du[8], xh[8];
+      ld8<T>(dyp + p * dy_ld, a); ld8<T>(xp + p * C, b);
+      bn_du_k<ACT>(a, b, k, act, du, xh);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { s1[e] += du[e]; s2[e] += du[e] * xh[e]; }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { red[(rg * chunks + ch) * 16 + e] = s1[e]; red[(rg * chunks + ch) * 16 + 8 + e] = s2[e]; }
+  }
+  __syncthreads();
+  if (rg == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      float t1 = 0.f, t2 = 0.f;
+      for (int g = 0; g < rpp; ++g) { t1 += red[(g * chunks + ch) * 16 + k]; t2 += red[(g * chunks + ch) * 16 + 8 + k]; }
+      dst[ch * 8 + k] = t1;
+      dst[C + ch * 8 + k] = t2;
+    }
+  }
+}
+
+// one wave per column of the [blocks][2C] partials: sums[0..C) = s1 = d beta, sums[C..2C) = s2 = d gamma
+__global__ __launch_bounds__(256) void bn_bwd_final(const float* __restrict__ partial, int blocks, int pitch, int C, float* __restrict__ sums,
+                                                    float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= 2 * C) return;
+  float s[1];
+  column_sums<1>(partial, blocks, pitch, {c}, s);
+  if ((threadIdx.x & 63) == 0) {
+    sums[c] = s[0];
+    float* out = c < C ? (dbeta ? dbeta + c : nullptr) : (dgamma ? dgamma + (c - C) : nullptr);
+    if (out) *out = accumulate ? *out + s[0] : s[0];
+  }
+}
+
+// FIXED: 256 % (C / 8) == 0 -- a thread's 8-channel piece is the same in every trip of the grid-stride loop (constants hoisted, four
+// rows in flight); otherwise the general loop
+template <typename T, int ACT, bool FIXED>
+__global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, int dy_ld, const T* __restrict__ x, T* __restrict__ dx, long P, int C,
+                                                    const float* __restrict__ mean, const float* __restrict__ var,
+                                                    const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int act,
+                                                    const float* __restrict__ sums, int use_running) {
+  const int chunks = C >> 3;
+  const long n8 = P * chunks;
+  const float invM = 1.0f / (float)P;
+  if constexpr (FIXED) {
+    const int ch = threadIdx.x % chunks;
+    const int sh = 31 - __builtin_clz(chunks);           // chunks is a power of two here: pixel = piece >> sh (a 64-bit division per piece otherwise)
+    const BnChan k = bn_chan(mean, var, gamma, beta, eps, ch * 8);
+    float m1[8], m2[8], gr[8];
+    if (use_running) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { m1[e] = 0.f; m2[e] = 0.f; }
+    } else {
+      ld8<float>(sums + ch * 8, m1);
+      ld8<float>(sums + C + ch * 8, m2);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { m1[e] = m1[e] * invM; m2[e] = m2[e] * invM; }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gr[e] = k.ga[e] * k.rs[e];
+    const long stride = (long)gridDim.x * 256;
+    long i = (long)blockIdx.x * 256 + threadIdx.x;
+    auto one = [&](const float (&a)[8], const float (&b)[8], long idx) {
+      float du[8], xh[8], o[8];
+      bn_du_k<ACT>(a, b, k, act, du, xh);
+      if (use_running) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = gr[e] * du[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = gr[e] * (du[e] - m1[e] - xh[e] * m2[e]);
+      }
+      st8<T>(dx + idx * 8, o);
+    };
+    for (; i + 3 * stride < n8; i += 4 * stride) {
+      float a[4][8], b[4][8];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long idx = i + u * stride;
+        ld8<T>(dy + (idx >> sh) * dy_ld + ch * 8, a[u]);
+        ld8<T>(x + idx * 8, b[u]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) one(a[u], b[u], i + u * stride);
+    }
+    for (; i < n8; i += stride) {
+      float a[8], b[8];
+      ld8<T>(dy + (i >> sh) * dy_ld + ch * 8, a);
+      ld8<T>(x + i * 8, b);
+      one(a, b, i);
+    }
+    return;
+  }
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
+    const int ch = (int)(i % chunks);
+    const long p = i / chunks;
+    float du[8], xh[8], gr[8], o[8];
+    bn_du<T>(dy, p * dy_ld + ch * 8, x, i * 8, mean, var, gamma, beta, eps, act, ch * 8, du, xh, gr);
+    if (use_running) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = gr[k] * du[k];
+    } else {
+      float s1[8], s2[8];
+      ld8<float>(sums + ch * 8, s1);
+      ld8<float>(sums + C + ch * 8, s2);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) o[k] = gr[k] * (du[k] - s1[k] * invM - xh[k] * (s2[k] * invM));
+    }
+    st8<T>(dx + i * 8, o);
+  }
+}
+
+template <typename T>
+void launch_bn_backward(const void* dy, int dy_ld, const void* x, void* dx, long P, int C, const float* stats, const float* gamma, const float* beta, float eps,
+                        int act, int use_running, float* partial, float* sums, float* dgamma, float* dbeta, int accumulate, hipStream_t s) {
+  const long blocks = (P + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+  const float* mean = stats;
+  const float* var = stats + C;
+  const bool fixed = 256 % (C >> 3) == 0;
+  const unsigned ga = bn_apply_grid(P * (C >> 3), fixed, 2048);
+  bn_dispatch(act, fixed, [&](auto A, auto F) {
+    hipLaunchKernelGGL((bn_bwd_partial<T, decltype(A)::value>), dim3((unsigned)blocks), dim3(256), 0, s, (const T*)dy, dy_ld, (const T*)x, P, C, mean, var, gamma, beta, eps, act,
+                       partial);
+    long rr = blocks;
+    int pp = 2 * C;
+    colsum_prereduce(partial, rr, pp, 0, 2 * C, s);
+    hipLaunchKernelGGL(bn_bwd_final, dim3((unsigned)((2 * C + 3) / 4)), dim3(256), 0, s, partial, (int)rr, pp, C, sums, dgamma, dbeta, accumulate);
+    hipLaunchKernelGGL((bn_bwd_apply<T, decltype(A)::value, decltype(F)::value>), dim3(ga), dim3(256), 0, s, (const T*)dy, dy_ld, (const T*)x, (T*)dx, P, C, mean, var, gamma, beta, eps, act, sums,
+                       use_running);
+  });
+}
+
+// what the three forward entry points ask of their common arguments
+int bn_forward_check(const void* x, const void* y, int32_t y_pixel_stride, const float* gamma, const float* beta, const float* stats, int64_t pixels, int C,
+                     int dtype, int act) {
+  if (!x || !y || !gamma || !beta || !stats || pixels <= 0 || C <= 0 || C % 8 || C > 2048 || y_pixel_stride < C || y_pixel_stride % 8) return MTBT_EINVAL;
+  if (dtype != MTBT_F32 && dtype != MTBT_BF16) return MTBT_EINVAL;
+  if (act < MTBT_ACT_NONE || act > MTBT_ACT_GELU_POLY) return MTBT_EINVAL;
+  if (!aligned16(x) || !aligned16(y) || !aligned16(gamma) || !aligned16(beta) || !aligned16(stats)) return MTBT_EALIGN;
+  return MTBT_OK;
 }
 
 }  // namespace
@@ -203,24 +432,15 @@ extern "C" int64_t mtbt_bn_train_workspace_bytes(int64_t pixels, int C) {
 extern "C" int mtbt_bn_forward_nhwc(const void* x, void* y, int32_t y_pixel_stride, const float* gamma, const float* beta, float* running_mean,
                                     float* running_var, float momentum, float eps, int act, int64_t pixels, int C, int dtype, int use_running,
                                     float* stats, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!x || !y || !gamma || !beta || !stats || pixels <= 0 || C <= 0 || C % 8 || C > 2048 || y_pixel_stride < C || y_pixel_stride % 8) return MTBT_EINVAL;
-  if (dtype != MTBT_F32 && dtype != MTBT_BF16) return MTBT_EINVAL;
-  if (act < MTBT_ACT_NONE || act > MTBT_ACT_GELU_POLY) return MTBT_EINVAL;
-  if (!aligned16(x) || !aligned16(y) || !aligned16(gamma) || !aligned16(beta) || !aligned16(stats)) return MTBT_EALIGN;
+  if (const int rc = bn_forward_check(x, y, y_pixel_stride, gamma, beta, stats, pixels, C, dtype, act)) return rc;
   if (use_running && (!running_mean || !running_var)) return MTBT_EINVAL;
   const long nb = (pixels + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
   if (nb > 0x7fffffffL) return MTBT_EINVAL;
-  const int CH8 = C / 8;
-  if (CH8 > 256) return MTBT_EINVAL;
   float* mean = stats;
   float* var = stats + C;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const unsigned fb = (unsigned)((C + 255) / 256);
-  const long total = pixels * CH8;
-  long g = (total + 255) / 256;
-  if (g > 8192) g = 8192;
   if (use_running) {
-    hipLaunchKernelGGL(bn_copy_stats_kernel, dim3(fb), dim3(256), 0, s, running_mean, running_var, mean, var, C);
+    hipLaunchKernelGGL(bn_copy_stats_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, running_mean, running_var, mean, var, C);
   } else {
     if (!workspace || !aligned16(workspace)) return MTBT_EALIGN;
     if (workspace_bytes < nb * 2 * C * (int64_t)sizeof(float)) return MTBT_EWORKSPACE;
@@ -230,8 +450,7 @@ extern "C" int mtbt_bn_forward_nhwc(const void* x, void* y, int32_t y_pixel_stri
     hipLaunchKernelGGL(bn_combine_stats_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, (int)nb, C, (long)pixels, mean, var, running_mean,
                        running_var, momentum);
   }
-  if (dtype == MTBT_F32) launch_bn_apply<float>(x, y, mean, var, gamma, beta, eps, act, (long)pixels, C, y_pixel_stride, s);
-  else launch_bn_apply<bf16_t>(x, y, mean, var, gamma, beta, eps, act, (long)pixels, C, y_pixel_stride, s);
+  launch_bn_apply(dtype, x, y, mean, var, gamma, beta, eps, act, (long)pixels, C, y_pixel_stride, s);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }
@@ -241,22 +460,12 @@ extern "C" int mtbt_bn_forward_nhwc(const void* x, void* y, int32_t y_pixel_stri
 extern "C" int mtbt_bn_forward_sums_nhwc(const void* x, void* y, int32_t y_pixel_stride, const float* gamma, const float* beta, float* running_mean,
                                          float* running_var, float momentum, float eps, int act, int64_t pixels, int C, int dtype,
                                          const float* sums, const float* shift, float* stats, void* stream) {
-  if (!x || !y || !gamma || !beta || !stats || !sums || pixels <= 0 || C <= 0 || C % 8 || C > 2048 || y_pixel_stride < C || y_pixel_stride % 8) return MTBT_EINVAL;
-  if (dtype != MTBT_F32 && dtype != MTBT_BF16) return MTBT_EINVAL;
-  if (act < MTBT_ACT_NONE || act > MTBT_ACT_GELU_POLY) return MTBT_EINVAL;
-  if (!aligned16(x) || !aligned16(y) || !aligned16(gamma) || !aligned16(beta) || !aligned16(stats)) return MTBT_EALIGN;
-  const int CH8 = C / 8;
-  if (CH8 > 256) return MTBT_EINVAL;
+  if (!sums) return MTBT_EINVAL;
+  if (const int rc = bn_forward_check(x, y, y_pixel_stride, gamma, beta, stats, pixels, C, dtype, act)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  float* mean = stats;
-  float* var = stats + C;
-  hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, sums, shift, (long)pixels, C, mean, var, running_mean,
+  hipLaunchKernelGGL(bn_stats_from_sums_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, s, sums, shift, (long)pixels, C, stats, stats + C, running_mean,
                      running_var, momentum);
-  const long total = pixels * CH8;
-  long g = (total + 255) / 256;
-  if (g > 8192) g = 8192;
-  if (dtype == MTBT_F32) launch_bn_apply<float>(x, y, mean, var, gamma, beta, eps, act, (long)pixels, C, y_pixel_stride, s);
-  else launch_bn_apply<bf16_t>(x, y, mean, var, gamma, beta, eps, act, (long)pixels, C, y_pixel_stride, s);
+  launch_bn_apply(dtype, x, y, stats, stats + C, gamma, beta, eps, act, (long)pixels, C, y_pixel_stride, s);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }
@@ -265,24 +474,15 @@ extern "C" int mtbt_bn_forward_sums_nhwc(const void* x, void* y, int32_t y_pixel
 extern "C" int mtbt_bn_forward_partials_nhwc(const void* x, void* y, int32_t y_pixel_stride, const float* gamma, const float* beta, float* running_mean,
                                              float* running_var, float momentum, float eps, int act, int64_t pixels, int C, int dtype,
                                              float* partial, int64_t rows, int32_t pitch, const float* shift, float* stats, void* stream) {
-  if (!x || !y || !gamma || !beta || !stats || !partial || rows <= 0 || rows > 0x7fffffffL || pitch < 2 * C || pixels <= 0 || C <= 0 || C % 8 || C > 2048 ||
-      y_pixel_stride < C || y_pixel_stride % 8)
-    return MTBT_EINVAL;
-  if (dtype != MTBT_F32 && dtype != MTBT_BF16) return MTBT_EINVAL;
-  if (act < MTBT_ACT_NONE || act > MTBT_ACT_GELU_POLY) return MTBT_EINVAL;
-  if (!aligned16(x) || !aligned16(y) || !aligned16(gamma) || !aligned16(beta) || !aligned16(stats)) return MTBT_EALIGN;
-  const int CH8 = C / 8;
-  if (CH8 > 256) return MTBT_EINVAL;
+  if (!partial || rows <= 0 || rows > 0x7fffffffL || pitch < 2 * C) return MTBT_EINVAL;
+  if (const int rc = bn_forward_check(x, y, y_pixel_stride, gamma, beta, stats, pixels, C, dtype, act)) return rc;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  float* mean = stats;
-  float* var = stats + C;
   long rr = rows;
   int pp = pitch;
   colsum_prereduce(partial, rr, pp, 0, 2 * C, s);      // tall matrices: folded in place first (rowreduce.h)
-  hipLaunchKernelGGL(bn_stats_from_partials_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, (int)rr, pp, shift, (long)pixels, C, mean, var,
+  hipLaunchKernelGGL(bn_stats_from_partials_kernel, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, (int)rr, pp, shift, (long)pixels, C, stats, stats + C,
                      running_mean, running_var, momentum);
-  if (dtype == MTBT_F32) launch_bn_apply<float>(x, y, mean, var, gamma, beta, eps, act, (long)pixels, C, y_pixel_stride, s);
-  else launch_bn_apply<bf16_t>(x, y, mean, var, gamma, beta, eps, act, (long)pixels, C, y_pixel_stride, s);
+  launch_bn_apply(dtype, x, y, stats, stats + C, gamma, beta, eps, act, (long)pixels, C, y_pixel_stride, s);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }
@@ -298,4 +498,30 @@ extern "C" int mtbt_bn_train_nhwc(const void* x, void* y, const float* gamma, co
   float* stats = reinterpret_cast<float*>(workspace) + nb * 2 * C;
   return mtbt_bn_forward_nhwc(x, y, C, gamma, beta, running_mean, running_var, momentum, eps, act, pixels, C, dtype, 0, stats, workspace,
                               workspace_bytes, stream);
+}
+
+extern "C" int64_t mtbt_bn_backward_workspace_bytes(int64_t pixels, int C) {
+  if (pixels <= 0 || C <= 0) return 0;
+  return (((pixels + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK) * 2 * (int64_t)C + 2 * (int64_t)C) * (int64_t)sizeof(float);
+}
+
+extern "C" int mtbt_bn_backward_nhwc(const void* dy, int32_t dy_pixel_stride, const void* x, const float* stats, const float* gamma, const float* beta,
+                                     float eps, int act, int use_running, void* dx, float* dgamma, float* dbeta, int accumulate, int64_t pixels, int C,
+                                     int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!dy || !x || !stats || !gamma || !beta || !dx || !workspace || pixels <= 0 || C <= 0 || C % 8 || C > 2048) return MTBT_EINVAL;
+  if (dy_pixel_stride < C || dy_pixel_stride % 8 || act < MTBT_ACT_NONE || act > MTBT_ACT_GELU_POLY) return MTBT_EINVAL;
+  if (dtype != MTBT_F32 && dtype != MTBT_BF16) return MTBT_EINVAL;
+  if (!aligned16(dy) || !aligned16(x) || !aligned16(dx) || !aligned16(stats) || !aligned16(gamma) || !aligned16(beta) || !aligned16(workspace)) return MTBT_EALIGN;
+  if (workspace_bytes < mtbt_bn_backward_workspace_bytes(pixels, C)) return MTBT_EWORKSPACE;
+  const long blocks = (pixels + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
+  if (blocks > 0x7fffffffL) return MTBT_EINVAL;
+  float* partial = reinterpret_cast<float*>(workspace);
+  float* sums = partial + blocks * 2 * C;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (dtype == MTBT_F32)
+    launch_bn_backward<float>(dy, dy_pixel_stride, x, dx, (long)pixels, C, stats, gamma, beta, eps, act, use_running, partial, sums, dgamma, dbeta, accumulate, s);
+  else
+    launch_bn_backward<bf16_t>(dy, dy_pixel_stride, x, dx, (long)pixels, C, stats, gamma, beta, eps, act, use_running, partial, sums, dgamma, dbeta, accumulate, s);
+  MTBT_LAUNCH_CHECK();
+  return MTBT_OK;
 }

@@ -14,6 +14,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "rowreduce.h"
 
 namespace {
 
@@ -127,32 +128,13 @@ __global__ __launch_bounds__(256) void ema_kernel(const float* __restrict__ src,
   }
 }
 
-// sum of squares of a flat fp32 buffer, deterministic: per-workgroup partials (fixed element -> thread mapping, LDS tree), then one
-// workgroup over the partials; *out (+)= the sum.
+// sum of squares of a flat fp32 buffer, deterministic: per-workgroup partials (fixed element -> thread mapping, block_tree_sum), then
+// scalar_final over the partials (rowreduce.h); *out (+)= the sum.
 __global__ __launch_bounds__(256) void sumsq_partial(const float* __restrict__ g, long n, float* __restrict__ partial) {
-  __shared__ float red[256];
   float s = 0.f;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) s += g[i] * g[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-__global__ __launch_bounds__(256) void sumsq_final(const float* __restrict__ partial, int n, float* __restrict__ out, int accumulate) {
-  __shared__ float red[256];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = accumulate ? *out + red[0] : red[0];
+  s = block_tree_sum(s);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // torch.nn.utils.clip_grad_norm_: total_norm = sqrt(sumsq); coef = clamp(max_norm / (total_norm + 1e-6), max = 1)
@@ -250,7 +232,7 @@ extern "C" int mtbt_sumsq(const float* g, int64_t n, float* out, int accumulate,
   blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(sumsq_partial, dim3((unsigned)blocks), dim3(256), 0, s, g, (long)n, reinterpret_cast<float*>(workspace));
-  hipLaunchKernelGGL(sumsq_final, dim3(1), dim3(256), 0, s, reinterpret_cast<const float*>(workspace), (int)blocks, out, accumulate);
+  hipLaunchKernelGGL(scalar_final, dim3(1), dim3(256), 0, s, reinterpret_cast<const float*>(workspace), (int)blocks, out, accumulate);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }

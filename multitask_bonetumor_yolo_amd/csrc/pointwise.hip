@@ -320,7 +320,7 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ x, const T* __restric
 
 // LayerNorm backward WITH the parameter gradients: a wave walks LNB_ITERS consecutive groups of its 64/LP pixels and keeps, per lane,
 // the running sums of dy * xhat (d gamma) and dy (d beta) of its channels; at the end the pixel groups of the wave are folded by
-// shuffles and ONE partial row [d beta | d gamma] per wave goes to the workspace (second level: channel_sum_final_pitch).  Saves the
+// shuffles and ONE partial row [d beta | d gamma] per wave goes to the workspace (second level: channel_sum_final).  Saves the
 // xhat tensor (a write and two reads) and two channel-sum passes over dy per LayerNorm.
 constexpr int LNB_ITERS = 64;   // at most; fewer when the tensor is small (keep >= ~4096 waves in flight)
 static inline int lnb_iters(long pixels, int ppw) {
@@ -705,8 +705,8 @@ extern "C" int mtbt_layernorm_backward_params_nhwc(const void* x, const void* dy
 #undef LNP_BY_C
 #undef LNP_LAUNCH
   const int rows = (int)blocks;           // (waves past the last pixel contribute zeros)
-  hipLaunchKernelGGL(channel_sum_final_pitch, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, rows, 2 * C, 0, C, dbeta, accumulate_params);
-  hipLaunchKernelGGL(channel_sum_final_pitch, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, rows, 2 * C, C, C, dgamma, accumulate_params);
+  hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, rows, 2 * C, 0, C, dbeta, accumulate_params);
+  hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, rows, 2 * C, C, C, dgamma, accumulate_params);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }

@@ -48,16 +48,21 @@ template <typename T>
 __global__ __launch_bounds__(256) void channel_sum_partial(const T* __restrict__ x, const T* __restrict__ x2, long P, int C, int ld, int ld2,
                                                            float* __restrict__ partial) {
   const long p0 = (long)blockIdx.x * ROWS_PER_BLOCK, p1 = min(P, p0 + ROWS_PER_BLOCK);
-  rows_reduce(p0, p1, C >> 3, partial + (long)blockIdx.x * C, [&](long p, int ch, float (&v)[8]) {
-    ld8(x + p * ld + ch * 8, v);
-    if (x2) {
-      float u[8];
-      ld8(x2 + p * ld2 + ch * 8, u);
+  float* dst = partial + (long)blockIdx.x * C;
+  struct Row { float v[8], u[8]; };
+  rows_reduce<1>(
+      p0, p1, C >> 3,
+      [&](long p, int ch) {
+        Row r;
+        ld8(x + p * ld + ch * 8, r.v);
+        if (x2) ld8(x2 + p * ld2 + ch * 8, r.u);
+        return r;
+      },
+      [&](const Row& r, float (&t)[1][8]) {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] *= u[k];
-    }
-    return true;
-  });
+        for (int k = 0; k < 8; ++k) t[0][k] = x2 ? r.v[k] * r.u[k] : r.v[k];
+      },
+      [&](int ch, const float (&tot)[1][8]) { st8<float>(dst + ch * 8, tot[0]); });
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -246,7 +251,7 @@ extern "C" int mtbt_channel_sum(const void* x, const void* x2, int64_t pixels, i
     hipLaunchKernelGGL(channel_sum_partial<float>, dim3((unsigned)blocks), dim3(256), 0, s, (const float*)x, (const float*)x2, (long)pixels, C, pixel_stride, pixel_stride2, partial);
   else
     return MTBT_EINVAL;
-  hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, (int)blocks, C, out, accumulate);
+  hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, (int)blocks, C, 0, C, out, accumulate);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }
@@ -308,8 +313,8 @@ static int dw_wgrad_entry(const void* x, const void* dy, float* dw, float* dbias
   else { if (ksize == 7) DWT(float, 7); else DWT(float, 3); }
 #undef DWT
   const int rows = blocks / chunks, pitch = n + C;
-  hipLaunchKernelGGL(channel_sum_final_pitch, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, partial, rows, pitch, 0, n, dw, accumulate);
-  if (dbias) hipLaunchKernelGGL(channel_sum_final_pitch, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, rows, pitch, n, C, dbias, accumulate);
+  hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, partial, rows, pitch, 0, n, dw, accumulate);
+  if (dbias) hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((C + 3) / 4)), dim3(256), 0, s, partial, rows, pitch, n, C, dbias, accumulate);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }

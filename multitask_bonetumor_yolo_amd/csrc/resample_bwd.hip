@@ -119,11 +119,11 @@ __device__ __forceinline__ void fetch_resampled(const T* src, int mode, int n, i
   }
 }
 
-// partial[block] = sum over this block's (output pixel, chunk) items of dy . resample(x): fixed item -> thread mapping, LDS tree
+// partial[block] = sum over this block's (output pixel, chunk) items of dy . resample(x): fixed item -> thread mapping,
+// block_tree_sum; second level: scalar_final (rowreduce.h)
 template <typename T>
 __global__ __launch_bounds__(256) void fuse_bwd_dot(const T* __restrict__ dy, const T* __restrict__ xin, int mode, int N, int H, int W, int C,
                                                     float* __restrict__ partial) {
-  __shared__ float red[256];
   const int CH8 = C >> 3;
   const long total = (long)N * H * W * CH8;
   float s = 0.f;
@@ -140,26 +140,8 @@ __global__ __launch_bounds__(256) void fuse_bwd_dot(const T* __restrict__ dy, co
 #pragma unroll
     for (int e = 0; e < 8; ++e) s += t[e] * g[e];
   }
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
-}
-
-__global__ __launch_bounds__(256) void scalar_final(const float* __restrict__ partial, int n, float* __restrict__ out, int accumulate) {
-  __shared__ float red[256];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
-  red[threadIdx.x] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = accumulate ? *out + red[0] : red[0];
+  s = block_tree_sum(s);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
 // ---- projector backward ----
@@ -210,18 +192,28 @@ __global__ __launch_bounds__(256) void proj_bwd_protos(const float* __restrict__
 __global__ __launch_bounds__(256) void proj_bwd_w_partial(const float* __restrict__ dlow, const float* __restrict__ protos, long P, int nm, float* __restrict__ partial) {
   const long p0 = (long)blockIdx.x * ROWS_PER_BLOCK, p1 = min(P, p0 + ROWS_PER_BLOCK);
   const int chunks = (nm >> 3) + 1;
-  rows_reduce(p0, p1, chunks, partial + (long)blockIdx.x * chunks * 8, [&](long p, int ch, float (&v)[8]) {
-    const float d = dlow[p];
-    if (ch * 8 < nm) {
-      ld8<float>(protos + p * nm + ch * 8, v);
+  float* dst = partial + (long)blockIdx.x * chunks * 8;
+  struct Row { float v[8]; };
+  rows_reduce<1>(
+      p0, p1, chunks,
+      [&](long p, int ch) {          // the row's addend itself: the product is rounded here, not contracted into the sum
+        Row r;
+        const float d = dlow[p];
+        if (ch * 8 < nm) {
+          ld8<float>(protos + p * nm + ch * 8, r.v);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] *= d;
-    } else {
+          for (int k = 0; k < 8; ++k) r.v[k] *= d;
+        } else {
 #pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = d;
-    }
-    return true;
-  });
+          for (int k = 0; k < 8; ++k) r.v[k] = d;
+        }
+        return r;
+      },
+      [&](const Row& r, float (&t)[1][8]) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t[0][k] = r.v[k];
+      },
+      [&](int ch, const float (&tot)[1][8]) { st8<float>(dst + ch * 8, tot[0]); });
 }
 
 __global__ void proj_bwd_w_out(const float* __restrict__ sums, int nm, float* __restrict__ dw, float* __restrict__ db, int accumulate) {
@@ -374,7 +366,7 @@ extern "C" int mtbt_projector_backward(const float* dseg, const float* protos, c
     const int cols = nm + 8;
     float* sums = partial + blocks * cols;
     hipLaunchKernelGGL(proj_bwd_w_partial, dim3((unsigned)blocks), dim3(256), 0, s, dlow, protos, P, nm, partial);
-    hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((cols + 3) / 4)), dim3(256), 0, s, partial, (int)blocks, cols, sums, 0);
+    hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((cols + 3) / 4)), dim3(256), 0, s, partial, (int)blocks, cols, 0, cols, sums, 0);
     hipLaunchKernelGGL(proj_bwd_w_out, dim3(1), dim3(256), 0, s, sums, nm, dw, db, accumulate_dw);
   }
   MTBT_LAUNCH_CHECK();

@@ -1,6 +1,12 @@
-// Deterministic two-level reductions over the pixel rows of an NHWC tensor, shared by the backward kernels
-// (pointwise_bwd.hip, train_ops.hip): level 1 = per-workgroup partial rows (row groups added in a fixed order through LDS),
-// level 2 = one wave per output element over the workgroup partials.
+// The fixed-order reductions of the training step (bn_train.hip, pointwise_bwd.hip, train_ops.hip, resample_bwd.hip, optim.hip, wgrad.hip,
+// pointwise.hip, conv_igemm.hip).  Nothing here uses an atomic, and THE ORDER OF THE ADDITIONS IS THE CONTRACT -- a step is reproducible
+// bit for bit because of it:
+//   rows_reduce    a thread adds its rows in ascending order, starting from 0.f; the row groups are then added in row-group order, starting
+//                  from 0.f.  The row loop is unrolled four deep for the loads only: unrolling never re-associates a sum.
+//   column_sums    lane l adds rows l, l + 64, ... in ascending order, starting from 0.f; then the wave butterfly (wave_sum: offsets 32 .. 1)
+//   block_tree_sum the 256-thread LDS halving tree: red[t] += red[t + o] for o = 128, 64, .. 1
+//   fold4          four row groups: ((r0 + r1) + r2) + r3
+// Level 1 = per-workgroup partial rows in a workspace, level 2 = one wave per output element over those rows.
 #pragma once
 #include "common.h"
 
@@ -8,61 +14,123 @@ namespace {
 
 constexpr int ROWS_PER_BLOCK = 256;   // pixels per workgroup in the first level
 
-// A thread owns one 16-byte chunk (8 channels) of a pixel; with fewer than 256 chunks per pixel the workgroup's threads split into
-// row groups that walk the workgroup's ROWS_PER_BLOCK pixels in parallel and are then added in row-group order through LDS
-// (deterministic).  `fetch(p, ch, v)` returns false when pixel p contributes nothing.
-template <typename F>
-__device__ __forceinline__ void rows_reduce(long p0, long p1, int chunks, float* __restrict__ dst /* [chunks*8] of this workgroup */, F fetch) {
-  __shared__ float red[256 * 8];
+// rows p, p + step, ... < p1 of one 8-channel piece into the NS sums s; `load(p, ch)` returns what a row needs from memory (by value) and
+// `terms(raw, t)` turns it into the row's NS x 8 addends.  Four rows' loads are issued before their arithmetic.
+template <int NS, typename Load, typename Terms>
+__device__ __forceinline__ void rows_accumulate(long p, long p1, int step, int ch, float (&s)[NS][8], Load load, Terms terms) {
+  using Raw = decltype(load(p, ch));
+  auto add = [&](const Raw& raw) {
+    float t[NS][8];
+    terms(raw, t);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+#pragma unroll
+      for (int n = 0; n < NS; ++n) s[n][k] += t[n][k];
+  };
+  for (; p + 3 * step < p1; p += 4 * step) {
+    Raw raw[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) raw[u] = load(p + u * step, ch);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) add(raw[u]);
+  }
+  for (; p < p1; p += step) add(load(p, ch));
+}
+
+// First level: NS sums per 8-channel piece (16-byte chunk) over the pixels [p0, p1) of a 256-thread workgroup.  With at most 256 pieces
+// per pixel the threads split into 256 / chunks row groups that walk the pixels in parallel and are then added in row-group order through
+// LDS; wider rows (mtbt_channel_sum has no cap on C) give every thread whole columns of pieces, serial over the rows.  `store(ch, tot)`
+// receives the NS x 8 totals of piece ch.  In the grouped path a thread's piece is threadIdx.x % chunks for all its rows, so a caller may
+// take the piece's constants once, before the call.
+template <int NS, typename Load, typename Terms, typename Store>
+__device__ __forceinline__ void rows_reduce(long p0, long p1, int chunks, Load load, Terms terms, Store store) {
+  __shared__ float red[256 * 8 * NS];
   const int tid = threadIdx.x;
-  if (chunks >= 256) {
+  if (chunks > 256) {
     for (int ch = tid; ch < chunks; ch += 256) {
-      float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      for (long p = p0; p < p1; ++p) {
-        float v[8];
-        if (fetch(p, ch, v)) {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) s[k] += v[k];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) dst[ch * 8 + k] = s[k];
+      float s[NS][8] = {};
+      rows_accumulate<NS>(p0, p1, 1, ch, s, load, terms);
+      store(ch, s);
     }
     return;
   }
   const int rpp = 256 / chunks, rg = tid / chunks, ch = tid - rg * chunks;
-  float s[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (rg < rpp) {
-    for (long p = p0 + rg; p < p1; p += rpp) {
-      float v[8];
-      if (fetch(p, ch, v)) {
+    float s[NS][8] = {};
+    rows_accumulate<NS>(p0 + rg, p1, rpp, ch, s, load, terms);
 #pragma unroll
-        for (int k = 0; k < 8; ++k) s[k] += v[k];
-      }
-    }
+    for (int n = 0; n < NS; ++n)
 #pragma unroll
-    for (int k = 0; k < 8; ++k) red[(rg * chunks + ch) * 8 + k] = s[k];
+      for (int k = 0; k < 8; ++k) red[(rg * chunks + ch) * 8 * NS + n * 8 + k] = s[n][k];
   }
   __syncthreads();
   if (rg == 0) {
+    float tot[NS][8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float t = 0.f;
-      for (int g = 0; g < rpp; ++g) t += red[(g * chunks + ch) * 8 + k];
-      dst[ch * 8 + k] = t;
+#pragma unroll
+      for (int n = 0; n < NS; ++n) tot[n][k] = 0.f;
+      for (int g = 0; g < rpp; ++g)
+#pragma unroll
+        for (int n = 0; n < NS; ++n) tot[n][k] += red[(g * chunks + ch) * 8 * NS + n * 8 + k];
     }
+    store(ch, tot);
   }
 }
 
-// second level: one wave per output element; its lanes stride over the workgroup partials and are combined by a butterfly (fixed
-// order: deterministic).  A serial loop per element took longer than the first level once there were ~1000 partial rows.
-__global__ __launch_bounds__(256) void channel_sum_final(const float* __restrict__ partial, int blocks, int C, float* __restrict__ out, int accumulate) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+// Second level, one wave per output element: the lanes stride over the rows of N columns of a [rows][pitch] partial matrix and are combined
+// by the butterfly; every lane gets the N sums.  (A serial loop per element took longer than the first level once there were ~1000 rows.)
+template <int N>
+__device__ __forceinline__ void column_sums(const float* __restrict__ partial, int rows, int pitch, const int (&col)[N], float (&s)[N]) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int n = 0; n < N; ++n) s[n] = 0.f;
+  for (int b = lane; b < rows; b += 64)
+#pragma unroll
+    for (int n = 0; n < N; ++n) s[n] += partial[(long)b * pitch + col[n]];
+#pragma unroll
+  for (int n = 0; n < N; ++n) s[n] = wave_sum(s[n]);
+}
+
+// out[c] (+)= the sum of column c0 + c of a [blocks][pitch] partial matrix, c < C
+__global__ __launch_bounds__(256) void channel_sum_final(const float* __restrict__ partial, int blocks, int pitch, int c0, int C, float* __restrict__ out,
+                                                         int accumulate) {
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (c >= C) return;                     // whole waves leave together
+  float s[1];
+  column_sums<1>(partial, blocks, pitch, {c0 + c}, s);
+  if ((threadIdx.x & 63) == 0) out[c] = accumulate ? out[c] + s[0] : s[0];
+}
+
+// The sum of one value per thread over a 256-thread workgroup by the LDS halving tree; every thread gets it.  ONE call per kernel: there
+// is no barrier after the last read, so a second call would overwrite red[] under a thread that still reads it.
+__device__ __forceinline__ float block_tree_sum(float s) {
+  __shared__ float red[256];
+  red[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// second level of the scalar sums (mtbt_sumsq, the BiFPN weight gradient): one workgroup over the n workgroup partials; *out (+)= the sum
+__global__ __launch_bounds__(256) void scalar_final(const float* __restrict__ partial, int n, float* __restrict__ out, int accumulate) {
   float s = 0.f;
-  for (int b = lane; b < blocks; b += 64) s += partial[(long)b * C + c];
-  s = wave_sum(s);
-  if (lane == 0) out[c] = accumulate ? out[c] + s : s;
+  for (int i = threadIdx.x; i < n; i += 256) s += partial[i];
+  s = block_tree_sum(s);
+  if (threadIdx.x == 0) *out = accumulate ? *out + s : s;
+}
+
+// A workgroup of 64 columns (lane = column) x 4 row groups (wave = row group): the four row groups' sums of a column, added in row-group
+// order; every thread gets its column's total.  ONE call per kernel (no barrier after the reads, as in block_tree_sum).
+__device__ __forceinline__ float fold4(float s) {
+  __shared__ float red[4][64];
+  const int lane = threadIdx.x & 63;
+  red[threadIdx.x >> 6][lane] = s;
+  __syncthreads();
+  return ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
 }
 
 // Pre-reduction of a TALL partial matrix, in place.  The one-wave-per-column second levels read a column with one 4-byte access per row:
@@ -108,17 +176,6 @@ static inline void colsum_prereduce(float* partial, long& rows, int& pitch, int 
   hipLaunchKernelGGL(colsum_tile_kernel, dim3((unsigned)((cols + 15) / 16), (unsigned)S), dim3(256), 0, s, partial, (int)rows, pitch, c0, cols, (int)per);
   rows = S;
   pitch = (int)(per * pitch);
-}
-
-// the same over a [blocks][pitch] partial matrix, columns [c0, c0 + C)
-__global__ __launch_bounds__(256) void channel_sum_final_pitch(const float* __restrict__ partial, int blocks, int pitch, int c0, int C, float* __restrict__ out,
-                                                               int accumulate) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (c >= C) return;
-  float s = 0.f;
-  for (int b = lane; b < blocks; b += 64) s += partial[(long)b * pitch + c0 + c];
-  s = wave_sum(s);
-  if (lane == 0) out[c] = accumulate ? out[c] + s : s;
 }
 
 }  // namespace

@@ -1,6 +1,5 @@
 // HBM-bound kernels of the TRAINING step (configs[2]-[3]: forward in train mode, backward, parameter gradients), NHWC, 16-byte
-// accesses, fp32 arithmetic, deterministic (fixed-order two-level reductions, no atomics):
-//   mtbt_bn_backward_nhwc        activation derivative + BatchNorm backward (batch or running statistics) in two passes over (dy, x)
+// accesses, fp32 arithmetic, deterministic (the fixed-order reductions of rowreduce.h, no atomics; the BatchNorm backward is in bn_train.hip):
 //   mtbt_weight_prep             ONE launch per step that re-lays out every master weight (fp32, any strides) into the kernels' packed
 //                                compute-dtype layouts (forward KRSC, dgrad CRSK flipped, folded per-row / per-column scales)
 //   mtbt_bifpn_norm_weights(_backward)   the BiFPN fusion weights ELU(w) / (sum_0 ELU(w) + eps) on the device (main_model.py:194-196)
@@ -17,218 +16,6 @@ namespace {
 inline unsigned grid_cap(long work, int block, long cap = 8192) {
   long g = (work + block - 1) / block;
   return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// BatchNorm backward.  Forward (bn_train.hip): xhat = (x - mean) * rstd, u = xhat * gamma + beta, y = act(u).
-//   du = dy * act'(u);  s1 = sum_p du;  s2 = sum_p du * xhat;  d beta = s1;  d gamma = s2
-//   batch statistics:    dx = gamma * rstd * (du - s1 / M - xhat * s2 / M)
-//   running statistics:  dx = gamma * rstd * du
-// Pass 1 forms per-workgroup partial (s1, s2) rows; pass 2 sums them (one wave per column); pass 3 recomputes du and writes dx.
-// dy may be a channel slice (row pitch dy_ld); x (the conv output the forward normalised) and dx are dense.
-// ------------------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ void bn_du(const T* dy, long dy_off, const T* x, long x_off, const float* mean, const float* var, const float* gamma,
-                                      const float* beta, float eps, int act, int c0, float (&du)[8], float (&xh)[8], float (&gr)[8]) {
-  float a[8], b[8], mu[8], va[8], ga[8], be[8];
-  ld8<T>(dy + dy_off, a);
-  ld8<T>(x + x_off, b);
-  ld8<float>(mean + c0, mu);
-  ld8<float>(var + c0, va);
-  ld8<float>(gamma + c0, ga);
-  ld8<float>(beta + c0, be);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const float rstd = rsqrtf(va[e] + eps);
-    xh[e] = (b[e] - mu[e]) * rstd;
-    du[e] = a[e] * act_grad(xh[e] * ga[e] + be[e], act);
-    gr[e] = ga[e] * rstd;
-  }
-}
-
-// The per-channel constants of a lane's 8-channel piece: in every kernel below the piece a thread works on is the same for all its
-// rows (the workgroup size is a multiple of the pieces per row), so mean / rstd / gamma / beta are read ONCE per thread and the row loop
-// holds only the two 16-byte loads and the arithmetic -- unrolled four rows deep so eight loads are in flight per lane.  (Round 3: with
-// the four parameter vectors re-read and one row in flight per trip the statistics pass ran at 2.0 TB/s, SLOWER than the apply pass that
-// also writes a tensor: 39 against 25 us on average over the 98 BatchNorms of the step.)
-struct BnChan { float mu[8], rs[8], ga[8], be[8]; };
-__device__ __forceinline__ BnChan bn_chan(const float* mean, const float* var, const float* gamma, const float* beta, float eps, int c0) {
-  BnChan k;
-  float va[8];
-  ld8<float>(mean + c0, k.mu);
-  ld8<float>(var + c0, va);
-  ld8<float>(gamma + c0, k.ga);
-  ld8<float>(beta + c0, k.be);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) k.rs[e] = rsqrtf(va[e] + eps);
-  return k;
-}
-// du = dy * act'(xhat * gamma + beta), xhat = (x - mean) * rstd  (the arithmetic of bn_du above with the constants hoisted)
-template <int ACT>
-__device__ __forceinline__ void bn_du_k(const float (&a)[8], const float (&b)[8], const BnChan& k, int act, float (&du)[8], float (&xh)[8]) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    xh[e] = (b[e] - k.mu[e]) * k.rs[e];
-    du[e] = a[e] * act_grad(xh[e] * k.ga[e] + k.be[e], ACT < 0 ? act : ACT);
-  }
-}
-
-// ACT: the activation as a compile-time constant (MTBT_ACT_NONE / SILU / ELU), or -1 = the run-time `act`
-template <typename T, int ACT>
-__global__ __launch_bounds__(256) void bn_bwd_partial(const T* __restrict__ dy, int dy_ld, const T* __restrict__ x, long P, int C,
-                                                      const float* __restrict__ mean, const float* __restrict__ var,
-                                                      const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int act,
-                                                      float* __restrict__ partial /* [blocks][2C] */) {
-  __shared__ float red[256 * 16];
-  const int tid = threadIdx.x, chunks = C >> 3;
-  const long p0 = (long)blockIdx.x * ROWS_PER_BLOCK, p1 = min(P, p0 + ROWS_PER_BLOCK);
-  float* dst = partial + (long)blockIdx.x * 2 * C;
-  if (chunks >= 256) {   // (C >= 2048: not used by this network; serial over the rows)
-    for (int ch = tid; ch < chunks; ch += 256) {
-      float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-      for (long p = p0; p < p1; ++p) {
-        float du[8], xh[8], gr[8];
-        bn_du<T>(dy, p * dy_ld + ch * 8, x, p * C + ch * 8, mean, var, gamma, beta, eps, act, ch * 8, du, xh, gr);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) { s1[k] += du[k]; s2[k] += du[k] * xh[k]; }
-      }
-#pragma unroll
-      for (int k = 0; k < 8; ++k) { dst[ch * 8 + k] = s1[k]; dst[C + ch * 8 + k] = s2[k]; }
-    }
-    return;
-  }
-  const int rpp = 256 / chunks, rg = tid / chunks, ch = tid - rg * chunks;
-  float s1[8] = {0, 0, 0, 0, 0, 0, 0, 0}, s2[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (rg < rpp) {
-    const BnChan k = bn_chan(mean, var, gamma, beta, eps, ch * 8);
-    const T* dyp = dy + ch * 8;
-    const T* xp = x + ch * 8;
-    long p = p0 + rg;
-    for (; p + 3 * rpp < p1; p += 4 * rpp) {      // (rows are added in the same order as one at a time)
-      float a[4][8], b[4][8];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) { ld8<T>(dyp + (p + u * rpp) * dy_ld, a[u]); ld8<T>(xp + (p + u * rpp) * C, b[u]); }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        float du[8], xh[8];
-        bn_du_k<ACT>(a[u], b[u], k, act, du, xh);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { s1[e] += du[e]; s2[e] += du[e] * xh[e]; }
-      }
-    }
-    for (; p < p1; p += rpp) {
-      float a[8], b[8], du[8], xh[8];
-      ld8<T>(dyp + p * dy_ld, a); ld8<T>(xp + p * C, b);
-      bn_du_k<ACT>(a, b, k, act, du, xh);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { s1[e] += du[e]; s2[e] += du[e] * xh[e]; }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[(rg * chunks + ch) * 16 + e] = s1[e]; red[(rg * chunks + ch) * 16 + 8 + e] = s2[e]; }
-  }
-  __syncthreads();
-  if (rg == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float t1 = 0.f, t2 = 0.f;
-      for (int g = 0; g < rpp; ++g) { t1 += red[(g * chunks + ch) * 16 + k]; t2 += red[(g * chunks + ch) * 16 + 8 + k]; }
-      dst[ch * 8 + k] = t1;
-      dst[C + ch * 8 + k] = t2;
-    }
-  }
-}
-
-// one wave per column of the [blocks][2C] partials: sums[0..C) = s1 = d beta, sums[C..2C) = s2 = d gamma
-__global__ __launch_bounds__(256) void bn_bwd_final(const float* __restrict__ partial, int blocks, int pitch, int C, float* __restrict__ sums,
-                                                    float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate) {
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (c >= 2 * C) return;
-  float s = 0.f;
-  for (int b = lane; b < blocks; b += 64) s += partial[(long)b * pitch + c];
-  s = wave_sum(s);
-  if (lane == 0) {
-    sums[c] = s;
-    float* out = c < C ? (dbeta ? dbeta + c : nullptr) : (dgamma ? dgamma + (c - C) : nullptr);
-    if (out) *out = accumulate ? *out + s : s;
-  }
-}
-
-// FIXED: 256 % (C / 8) == 0 -- a thread's 8-channel piece is the same in every trip of the grid-stride loop (constants hoisted, four
-// rows in flight); otherwise the general loop
-template <typename T, int ACT, bool FIXED>
-__global__ __launch_bounds__(256) void bn_bwd_apply(const T* __restrict__ dy, int dy_ld, const T* __restrict__ x, T* __restrict__ dx, long P, int C,
-                                                    const float* __restrict__ mean, const float* __restrict__ var,
-                                                    const float* __restrict__ gamma, const float* __restrict__ beta, float eps, int act,
-                                                    const float* __restrict__ sums, int use_running) {
-  const int chunks = C >> 3;
-  const long n8 = P * chunks;
-  const float invM = 1.0f / (float)P;
-  if constexpr (FIXED) {
-    const int ch = threadIdx.x % chunks;
-    const int sh = 31 - __builtin_clz(chunks);           // chunks is a power of two here: pixel = piece >> sh (a 64-bit division per piece otherwise)
-    const BnChan k = bn_chan(mean, var, gamma, beta, eps, ch * 8);
-    float m1[8], m2[8], gr[8];
-    if (use_running) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { m1[e] = 0.f; m2[e] = 0.f; }
-    } else {
-      ld8<float>(sums + ch * 8, m1);
-      ld8<float>(sums + C + ch * 8, m2);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { m1[e] = m1[e] * invM; m2[e] = m2[e] * invM; }
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) gr[e] = k.ga[e] * k.rs[e];
-    const long stride = (long)gridDim.x * 256;
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    auto one = [&](const float (&a)[8], const float (&b)[8], long idx) {
-      float du[8], xh[8], o[8];
-      bn_du_k<ACT>(a, b, k, act, du, xh);
-      if (use_running) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = gr[e] * du[e];
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = gr[e] * (du[e] - m1[e] - xh[e] * m2[e]);
-      }
-      st8<T>(dx + idx * 8, o);
-    };
-    for (; i + 3 * stride < n8; i += 4 * stride) {
-      float a[4][8], b[4][8];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const long idx = i + u * stride;
-        ld8<T>(dy + (idx >> sh) * dy_ld + ch * 8, a[u]);
-        ld8<T>(x + idx * 8, b[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) one(a[u], b[u], i + u * stride);
-    }
-    for (; i < n8; i += stride) {
-      float a[8], b[8];
-      ld8<T>(dy + (i >> sh) * dy_ld + ch * 8, a);
-      ld8<T>(x + i * 8, b);
-      one(a, b, i);
-    }
-    return;
-  }
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
-    const int ch = (int)(i % chunks);
-    const long p = i / chunks;
-    float du[8], xh[8], gr[8], o[8];
-    bn_du<T>(dy, p * dy_ld + ch * 8, x, i * 8, mean, var, gamma, beta, eps, act, ch * 8, du, xh, gr);
-    if (use_running) {
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = gr[k] * du[k];
-    } else {
-      float s1[8], s2[8];
-      ld8<float>(sums + ch * 8, s1);
-      ld8<float>(sums + C + ch * 8, s2);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = gr[k] * (du[k] - s1[k] * invM - xh[k] * (s2[k] * invM));
-    }
-    st8<T>(dx + i * 8, o);
-  }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -412,10 +199,9 @@ __global__ __launch_bounds__(256) void scale_grad_rows(const float* __restrict__
   }
 }
 
-// workgroup = 64 columns x 4 row groups (lane = column: 256-byte row segments); the row groups are added in a fixed order through LDS
+// workgroup = 64 columns x 4 row groups (lane = column: 256-byte row segments); the row groups are added by fold4 (rowreduce.h)
 __global__ __launch_bounds__(256) void scale_grad_cols(const float* __restrict__ G, const float* __restrict__ W, const float* __restrict__ vec,
                                                        float* __restrict__ dW, float* __restrict__ dvec, int K, int C, int accumulate) {
-  __shared__ float red[4][64];
   const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane;
   float dot = 0.f;
@@ -428,12 +214,8 @@ __global__ __launch_bounds__(256) void scale_grad_cols(const float* __restrict__
       dW[(long)k * C + c] = accumulate ? dW[(long)k * C + c] + gv * v : gv * v;
     }
   }
-  red[rg][lane] = dot;
-  __syncthreads();
-  if (rg == 0 && c < C) {
-    const float t = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-    dvec[c] = accumulate ? dvec[c] + t : t;
-  }
+  const float t = fold4(dot);
+  if (rg == 0 && c < C) dvec[c] = accumulate ? dvec[c] + t : t;
 }
 
 template <typename T>
@@ -456,49 +238,6 @@ __global__ __launch_bounds__(256) void add_kernel(T* __restrict__ dst, long dbs,
 }
 
 }  // namespace
-
-extern "C" int64_t mtbt_bn_backward_workspace_bytes(int64_t pixels, int C) {
-  if (pixels <= 0 || C <= 0) return 0;
-  return (((pixels + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK) * 2 * (int64_t)C + 2 * (int64_t)C) * (int64_t)sizeof(float);
-}
-
-extern "C" int mtbt_bn_backward_nhwc(const void* dy, int32_t dy_pixel_stride, const void* x, const float* stats, const float* gamma, const float* beta,
-                                     float eps, int act, int use_running, void* dx, float* dgamma, float* dbeta, int accumulate, int64_t pixels, int C,
-                                     int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!dy || !x || !stats || !gamma || !beta || !dx || !workspace || pixels <= 0 || C <= 0 || C % 8 || C > 2048) return MTBT_EINVAL;
-  if (dy_pixel_stride < C || dy_pixel_stride % 8 || act < MTBT_ACT_NONE || act > MTBT_ACT_GELU_POLY) return MTBT_EINVAL;
-  if (dtype != MTBT_F32 && dtype != MTBT_BF16) return MTBT_EINVAL;
-  if (!aligned16(dy) || !aligned16(x) || !aligned16(dx) || !aligned16(stats) || !aligned16(gamma) || !aligned16(beta) || !aligned16(workspace)) return MTBT_EALIGN;
-  if (workspace_bytes < mtbt_bn_backward_workspace_bytes(pixels, C)) return MTBT_EWORKSPACE;
-  const long blocks = (pixels + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK;
-  if (blocks > 0x7fffffffL) return MTBT_EINVAL;
-  float* partial = reinterpret_cast<float*>(workspace);
-  float* sums = partial + blocks * 2 * C;
-  const float* mean = stats;
-  const float* var = stats + C;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  // the apply pass: four 8-channel pieces per thread and trip, at most 2048 workgroups (8 per CU)
-  const bool fixed = 256 % (C / 8) == 0;
-  const unsigned ga = grid_cap(pixels * (C / 8), fixed ? 1024 : 256, 2048);
-#define BNB2(T, A, F)                                                                                                                      \
-  hipLaunchKernelGGL((bn_bwd_partial<T, A>), dim3((unsigned)blocks), dim3(256), 0, s, (const T*)dy, dy_pixel_stride, (const T*)x, (long)pixels, C, mean, var, \
-                     gamma, beta, eps, act, partial);                                                                                      \
-  { long rr = blocks; int pp = 2 * C; colsum_prereduce(partial, rr, pp, 0, 2 * C, s);                                                      \
-    hipLaunchKernelGGL(bn_bwd_final, dim3((unsigned)((2 * C + 3) / 4)), dim3(256), 0, s, partial, (int)rr, pp, C, sums, dgamma, dbeta, accumulate); }  \
-  hipLaunchKernelGGL((bn_bwd_apply<T, A, F>), dim3(ga), dim3(256), 0, s, (const T*)dy, dy_pixel_stride, (const T*)x, (T*)dx, (long)pixels, C, mean, var, gamma, \
-                     beta, eps, act, sums, use_running);
-#define BNB(T)                                                                        \
-  if (!fixed) { BNB2(T, -1, false) }                                                  \
-  else if (act == MTBT_ACT_SILU) { BNB2(T, MTBT_ACT_SILU, true) }                     \
-  else if (act == MTBT_ACT_ELU) { BNB2(T, MTBT_ACT_ELU, true) }                       \
-  else if (act == MTBT_ACT_NONE) { BNB2(T, MTBT_ACT_NONE, true) }                     \
-  else { BNB2(T, -1, true) }
-  if (dtype == MTBT_F32) { BNB(float) } else { BNB(bf16_t) }
-#undef BNB
-#undef BNB2
-  MTBT_LAUNCH_CHECK();
-  return MTBT_OK;
-}
 
 extern "C" int mtbt_weight_prep_blocks(int64_t elements) { return elements <= 0 ? 0 : (int)((elements + PREP_ELEMS - 1) / PREP_ELEMS); }
 

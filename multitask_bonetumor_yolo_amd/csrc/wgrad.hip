@@ -249,9 +249,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
 }
 
 // small tensors with many slices (a serial walk of the slices by n / 256 workgroups is latency-bound): workgroup = 64 elements x 4 slice
-// groups, added in a fixed order through LDS
+// groups, added by fold4 (rowreduce.h)
 __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const float* __restrict__ partial, float* __restrict__ dw, long n, int nsplit, int accumulate) {
-  __shared__ float red[4][64];
   const int lane = threadIdx.x & 63, g = threadIdx.x >> 6;
   const long i = (long)blockIdx.x * 64 + lane;
   float s = 0.f;
@@ -259,12 +258,8 @@ __global__ __launch_bounds__(256) void wgrad_reduce4_kernel(const float* __restr
 #pragma unroll 4
     for (int k = g; k < nsplit; k += 4) s += partial[(long)k * n + i];
   }
-  red[g][lane] = s;
-  __syncthreads();
-  if (g == 0 && i < n) {
-    const float t = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-    dw[i] = accumulate ? dw[i] + t : t;
-  }
+  const float t = fold4(s);
+  if (g == 0 && i < n) dw[i] = accumulate ? dw[i] + t : t;
 }
 
 static inline void launch_wgrad_reduce(const float* partial, float* dw, long n, int nsplit, int accumulate, hipStream_t st) {
@@ -780,7 +775,7 @@ extern "C" int mtbt_stem_wgrad(const float* x, const void* d, float* dw, int N, 
   if (dtype == MTBT_F32) SW(float); else SW(bf16_t);
 #undef SW
   const int n = K * 48;
-  hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, partial, (int)blocks, n, dw, accumulate);
+  hipLaunchKernelGGL(channel_sum_final, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, partial, (int)blocks, n, 0, n, dw, accumulate);
   MTBT_LAUNCH_CHECK();
   return MTBT_OK;
 }

@@ -1,7 +1,8 @@
 """The training kernels on the paths the batch-32 step takes and the one-shape tests never reach: the tall-matrix pre-reduction of
 csrc/rowreduce.h (more than 768 partial rows), the four-rows-in-flight trip and the grid caps of the BatchNorm apply passes, the general
 (C / 8 not a power of two) BatchNorm kernels, the multi-workgroup partials and grid caps of csrc/resample_bwd.hip, the projector backward at
-non-integer resize ratios, and mtbt_gap_fc_backward / mtbt_sumsq / mtbt_add_nhwc at the sizes where their launch shape changes.
+non-integer resize ratios, and mtbt_gap_fc_backward / mtbt_channel_sum / mtbt_sumsq / mtbt_add_nhwc at the sizes where their launch shape
+or reduction path changes.
 
 References: CPU float64, plain torch (autograd through F.interpolate / F.max_pool2d / an explicit BatchNorm / Linear, or explicit sums), from
 the inputs the kernel sees (bf16 cases: the inputs are rounded to bf16 first, then taken to float64, so only the kernel's own arithmetic and
@@ -588,6 +589,7 @@ BN_CASES = [
     (64, 600, "silu", 0),      # P * C / 8 = 4800 >= 4096: the four-rows-in-flight trip of the fixed apply passes runs (5 workgroups, 3 * 1280 < 4800)
     (8, 5000, "gelu", 0),      # the same trip with one chunk per pixel and the run-time activation on the fixed path
     (96, 44000, "elu", 0),     # general path: 528 000 pieces, past the backward apply pass's 2048 workgroups of 256
+    (2048, 300, "silu", 0),    # the channel cap: 256 pieces per pixel = one row group per workgroup; a full workgroup of rows and a ragged one of 44
 ]
 BN_CASES_BF16_ONLY = [
     (512, 33000, "none", 0),   # fixed path: 2 112 000 pieces, past 2048 workgroups of 1024 pieces (forward and backward apply)
@@ -680,7 +682,7 @@ def test_bn_reference_is_batchnorm2d():
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
-# D. mtbt_gap_fc_backward, mtbt_sumsq, mtbt_add_nhwc
+# D. mtbt_gap_fc_backward, mtbt_channel_sum, mtbt_sumsq, mtbt_add_nhwc
 # ----------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
 @pytest.mark.parametrize("HW", [1, 20, 400])
@@ -718,6 +720,36 @@ def test_gap_fc_backward_shapes(Cc, nout, HW, dtype):
         within(f"{tag} dw accumulate {acc_dw}", dw, want, U[F32] * want.abs() + 2 * ACC * t_dw)
         want = bl.grad + acc_dw * prev_b.double()
         within(f"{tag} db accumulate {acc_dw}", db, want, U[F32] * want.abs() + ACC * dl.abs().sum(0))
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=["f32", "bf16"])
+@pytest.mark.parametrize("second", [0, 1], ids=["sum", "product"])
+def test_channel_sum_wider_than_a_workgroup(second, dtype):
+    """D.  mtbt_channel_sum at C = 2056: 257 pieces per pixel, more than the 256 threads of a workgroup, so rows_reduce (csrc/rowreduce.h)
+    gives every thread whole columns of pieces, serial over the rows (thread 0 takes pieces 0 and 256); P = 300 = a full workgroup of rows
+    and a ragged one of 44.  Both operands are read from rows wider than C (different pitches), with and without the second operand,
+    accumulate 0 and 1.  Terms: the |x| (or |x * x2|) of the column.  A second call gives the same bits."""
+    lib = L.load()
+    Cc, P, LD, LD2, OFF = 2056, 300, 2056 + 24, 2056 + 8, 8
+    g = torch.Generator().manual_seed(2056 + second)
+    a, b = rnd(torch.randn(P, LD, generator=g), dtype), rnd(torch.randn(P, LD2, generator=g) + 0.5, dtype)
+    prev = torch.randn(Cc, generator=g)
+    terms = a[:, OFF:OFF + Cc].double() * (b[:, :Cc].double() if second else 1.0)
+    ad, bd = a.to(DEV, dtype), b.to(DEV, dtype)
+    nb = lib.mtbt_channel_sum_workspace_bytes(P, Cc)
+    ws = torch.empty(nb // 4, device=DEV)
+    es = ad.element_size()
+    for accumulate in (0, 1):
+        outs = []
+        for _ in range(2):
+            out = prev.clone().to(DEV)
+            L.check(lib.mtbt_channel_sum(ad.data_ptr() + OFF * es, bd.data_ptr() if second else None, P, Cc, LD, LD2, CODE[dtype], out.data_ptr(), accumulate,
+                                         ws.data_ptr(), nb, S()), "channel_sum")
+            torch.cuda.synchronize()
+            outs.append(out)
+        want = terms.sum(0) + accumulate * prev.double()
+        within(f"channel_sum C {Cc} P {P} second {second} accumulate {accumulate} {dtype}", outs[0], want, U[F32] * want.abs() + ACC * terms.abs().sum(0))
+        assert torch.equal(outs[0], outs[1]), "a second call gives other bits"
 
 
 @pytest.mark.parametrize("n", [0, 1, 4095, 4097, 1024 * 4096 + 5])
